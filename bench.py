@@ -7,13 +7,17 @@ benchmark orbit.  Inputs are resident in HBM before the timed 
 Prints ONE JSON line on rank 0.  The CPU oracle is used here only for the `cpu_baseline` leg.
 
     python bench.py                       # N=1, cfg4 scene (10 M Gaussians, SH-3, 1920x1080)
+    python bench.py --full                # ... and every other figure and check listed below
+    python bench.py --dump-outputs DIR    # ... and the last timed frame as DIR/framebuffer.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 --steps K --warmup W
 
-What one N=1 run measures, all in the same process on the same resident scene (nothing is read from profiles/):
-  value                 fps of max(K, 240) frames — at least one whole orbit, whatever --steps is — in the default schedule
-                        (progressive slabs + temporal occlusion speculation); value_short_window: the K-step window that was asked for.
-                        Every other timed loop of the line is at least one orbit long as well ("steps_timed").
+A plain run sets up the scene, warms up W frames, times exactly K frames and prints the line: `value` (fps of those K frames in the
+default schedule: progressive slabs + temporal occlusion speculation), `ms_per_step`, `config`.  With --dump-outputs DIR it writes
+what the last timed frame computed (the arrays a caller of the path receives) to DIR before it prints.
+
+What one N=1 run with --full measures besides, all in the same process on the same resident scene (nothing is read from profiles/);
+every timed loop of it other than the headline one runs max(K, --min-steps) frames, at least one whole orbit:
   value_unspeculated    fps with speculative = 0 (what every first frame / incoherent pose costs)
   value_synchronised    fps when the host waits for every frame: gsx_render_frame + gsx_sync (SURVEY 8d's definition of
                         the metric), and value_reference_protocol: the app's own sequence with its two blocking waits per frame —
@@ -64,8 +68,12 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=120)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--min-steps", type=int, default=240, help="every timed loop runs at least this many frames (a whole orbit) whatever "
-                    "--steps says; `steps` on the line stays what was asked for, `steps_timed` says what was timed (tests pass 0)")
+    ap.add_argument("--full", action="store_true", help="also run every figure and check besides the headline loop (PMC passes, the "
+                    "other schedules, frame and oracle checks, robustness and cfg5 legs, CPU baseline); off: set up, warm up, time, print")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed (the frame a caller "
+                    "receives) to DIR/<name>.npy, float32")
+    ap.add_argument("--min-steps", type=int, default=240, help="--full: every timed loop other than the headline one runs at least this "
+                    "many frames (a whole orbit) whatever --steps says (tests pass 0); the headline loop times exactly --steps")
     ap.add_argument("--workload", default="cfg4", help="cfg2 (1 M) | cfg3 (5.8 M) | cfg4 (10 M, headline)")
     ap.add_argument("--gaussians", type=int, default=0, help="override the Gaussian count (debug)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -102,6 +110,8 @@ def parse_args():
     ap.add_argument("--pod", default="single/single", help="pod storage sh/cov3d: single|half|norm8|none / single|half "
                     "(reference default is norm8/half; the headline metric is quoted on the f32 pod)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     a.frames_in_flight_given = a.frames_in_flight is not None   # (an explicit value is taken as it is: no probe)
     if a.frames_in_flight is None:
         a.frames_in_flight = 2
@@ -153,6 +163,24 @@ def oracle_check_of(gpu, ref, pose):
     out["linf"] = max(out["linf_plain"], out["linf_speculated"])
     out["ok"] = bool(out["n_visible_equal"] and out["keys_equal"] and out["rects_equal"] and out["depth_order_equal"] and out["linf"] <= out["tolerance"])
     return out
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  An array larger than what is left of the 64 MB budget is written as
+    a fixed, seeded sample of its rows (the last axis kept whole: one pixel = one row), in index order."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float32)
+        if a.nbytes > left:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = max(left // (rows.shape[1] * 4), 1)
+            a = rows[np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def cfg5_leg(steps=60, warmup=12):
@@ -326,9 +354,9 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
-    # Every timed loop of this file runs over at least one whole orbit (240 poses): a 20-step window misses the speculation tuner's
-    # probe frames and the expensive quarter of the orbit, and read 13-16 % above the same run's whole-orbit rate in rounds 3 and 4.
-    # "steps" on the line stays what the caller asked for; "steps_timed" is what every loop timed.
+    # The headline loop times exactly --steps frames (steps_requested).  Every other timed loop of --full runs over at least one whole
+    # orbit (240 poses): a 20-step window misses the speculation tuner's probe frames and the expensive quarter of the orbit, and read
+    # 13-16 % above the same run's whole-orbit rate in rounds 3 and 4 (steady_state is the headline schedule over a whole orbit).
     steps_requested = args.steps
     if not args.pmc_child:
         args.steps = max(args.steps, args.min_steps)  # args.steps = max(args.steps, 240) by default
@@ -344,7 +372,7 @@ def main():
     # PMC child passes first: nothing in this process has initialised the GPU yet
     traffic, traffic_note = None, "skipped"
     single = world == 1 and not args.force_dist
-    if single and not args.no_pmc and not args.pmc_child and not args.render_options:
+    if single and args.full and not args.no_pmc and not args.pmc_child and not args.render_options:
         traffic, traffic_note = pmc_traffic(args)
 
     import torch
@@ -520,32 +548,37 @@ def main():
         set_opts(frames_in_flight=lanes)
     if lib_index:
         viewer.shard_stats(reset=True)
-    # `value` is timed over a whole orbit (>= 240 frames) whatever --steps is: a K = 20 window misses the speculation tuner's probe
-    # frames and read 13-16 % above the same run's whole-orbit rate in rounds 3 and 4.  The K-step window is
-    # kept beside it as value_short_window.
-    # (args.steps is the timed length from here on — main() raised it to a whole orbit; steps_requested is what the caller passed)
-    elapsed_short = None
-    if steps_requested != args.steps:
-        elapsed_short, _, _ = timed_loop(0, steps_requested)
-        if lib_index:
-            viewer.shard_stats(reset=True)
-    elapsed, timing, last_idx = timed_loop(0)
+    # `value`: exactly the K = --steps frames asked for.  (args.steps is the length of every OTHER timed loop from here on — main()
+    # raised it to a whole orbit for --full; steady_state is the headline schedule over such a loop.)
+    elapsed, timing, last_idx = timed_loop(0, steps_requested)
+    timing_steps = steps_requested   # the loop `timing` (per-pass HIP-event sums) was taken over
     launches["headline"] = launches["per_frame"]
     shard_stats_timed = viewer.shard_stats(reset=True) if lib_index else None
     # what the library holds on the device for this scene and this schedule, right after the headline loop (every DevBuf of the process:
     # the model's planes, its shade records, sort / bin / list buffers of every lane, framebuffers)
-    resident_bytes = viewer_mod.device_bytes()
+    resident_bytes = viewer_mod.device_bytes() if args.full else None
     if args.host_profile and use_dist and rank == 0:
-        print("host ms/frame by section:", {k: round(1e3 * x / args.steps, 4) for k, x in renderer.profile.items()}, file=sys.stderr)
+        print("host ms/frame by section:", {k: round(1e3 * x / steps_requested, 4) for k, x in renderer.profile.items()}, file=sys.stderr)
     renderer.profile = None
 
-    # ---- the last timed frame is still in the framebuffer: keep it for the frame check ----
+    # ---- the last timed frame is still in the framebuffer: keep it for the frame check and --dump-outputs ----
     frame_check = None
     fb_last = None
-    if single:
+    if single and (args.full or args.dump_outputs):
         renderer.poll()
         fb_last = renderer.framebuffer().copy()
-    if lib_index and world > 1:
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step (the device work of every rank ended at the loop's closing fence)
+        renderer.poll()
+        if single or gather == "float":
+            last = {"framebuffer": fb_last if single else renderer.framebuffer()}   # float32 [H, W, 4]: premultiplied rgb + T
+        elif afr:   # the frames of the last round by rank: the last step's frame is rank (K - 1) % N's
+            last = {"frame_rgba8": renderer.frames_rgba8()[(steps_requested - 1) % world]}
+        else:
+            last = {"frame_rgba8": renderer.frame_rgba8()}
+        dump_outputs(args.dump_outputs, last)
+        del last
+    if lib_index and world > 1 and args.full:
         # N > 1: rank 0 holds the last timed frame (the bands were gathered to it); it renders that pose once more from the WHOLE
         # scene with the plainest single-GPU schedule and the two must be equal bit for bit.  The other ranks wait at the barrier.
         renderer.poll()
@@ -567,13 +600,13 @@ def main():
             if not equal:
                 raise SystemExit(f"bench.py: the sharded frame differs from the single-GPU frame: {frame_check}")
         dist.barrier()
-    acct = accounting(rounds(args.warmup))
+    acct = accounting(rounds(args.warmup)) if args.full else None
     # N > 1 (index shards): the same K steps with the exchange unfiltered and every shard projected and shaded in full
     # (gsx_shard_render_frame(speculate = 0)) — the schedule whose dominant pass shards 1 / N; read it against the N = 1 line's
     # value_unspeculated
     elapsed_dist_u = None
     shard_stats_unspec = None
-    if lib_index and world > 1 and not args.no_extra_legs:
+    if lib_index and world > 1 and args.full and not args.no_extra_legs:
         renderer.speculate = False
         viewer.shard_stats(reset=True)
         elapsed_dist_u, _, _ = timed_loop(0)
@@ -583,16 +616,17 @@ def main():
             frame(i)
         renderer.poll()
     elapsed_1 = elapsed_ul = None
-    if lanes > 1 and (single or world == 1):   # (N > 1: one timed loop, as the contract says)
+    if lanes > 1 and (single or world == 1) and args.full:   # (N > 1: one timed loop, as the contract says)
         set_opts()
         elapsed_1, timing, _ = timed_loop(0)
+        timing_steps = args.steps
         launches["speculated_one_frame_in_flight"] = launches["per_frame"]
         acct = accounting(rounds(args.warmup))
 
     # ---- N = 1: the unspeculated loop of the same run (value_unspeculated + the SURVEY 8d projection roofline) ----
     elapsed_u = timing_u = acct_u = None
     elapsed_f = timing_f = acct_f = None
-    if single and "speculative" not in overrides:
+    if single and args.full and "speculative" not in overrides:
         viewer.set_render_options(**dict(overrides, speculative=0))
         elapsed_u, timing_u, _ = timed_loop(0)
         launches["unspeculated"] = launches["per_frame"]
@@ -621,7 +655,7 @@ def main():
             raise SystemExit(f"bench.py: the last timed frame differs from the speculative=0, progressive=0 frame: {frame_check}")
     # ---- N = 1: what a host that WAITS gets, a whole-orbit figure, and every pass against its bytes ----
     extra = None
-    if single and not overrides and not args.no_extra_legs and not args.pose_stride > 1 and args.pose_order == "orbit":
+    if single and args.full and not overrides and not args.no_extra_legs and not args.pose_stride > 1 and args.pose_order == "orbit":
         extra = {}
         key = renderer.KEY
 
@@ -730,7 +764,7 @@ def main():
 
     # ---- N = 1: the GPU side of the oracle check — pose 0 of the whole scene, the frame cpu_baseline renders on the host cores ----
     gpu_pose0 = None
-    if single and not overrides and not args.no_cpu_baseline and not args.cpu_sample and args.pose_order == "orbit" and args.pose_stride == 1:
+    if single and args.full and not overrides and not args.no_cpu_baseline and not args.cpu_sample and args.pose_order == "orbit" and args.pose_stride == 1:
         key = renderer.KEY
         set_opts(speculative=0, progressive=0)
         renderer.stages.set_uniforms(key, orbit[0], (w, h))
@@ -752,7 +786,7 @@ def main():
 
     # ---- N = 1: speculation robustness legs (same process, same resident scene) ----
     robustness = None
-    if single and not overrides and not args.no_robustness and not args.pose_stride > 1 and args.pose_order == "orbit":
+    if single and args.full and not overrides and not args.no_robustness and not args.pose_stride > 1 and args.pose_order == "orbit":
         from wgpu_3dgs_viewer_app_amd.mask import MaskEvaluator, MaskOp, MaskShape, MaskShapeKind
 
         def leg():
@@ -803,24 +837,26 @@ def main():
                                                "cover hundreds of tiles — opacity logits N(2, 1.5)")
         robustness["note"] = ("speculated frames are bit-identical to unspeculated ones whatever the poses (tests/test_gpu_speculation.py); "
                               "the viewer pauses speculation by itself when it keeps repairing without admitting less (gsx_frame.cpp)")
-    overflow_slabs = int(max(acct[:, 6].max(), acct_u[:, 6].max() if acct_u is not None else 0))
-    if overflow_slabs:
-        raise SystemExit(f"bench.py: {overflow_slabs} depth slabs overflowed the tile-pair buffers during the run (slow pair-free path)")
+    overflow_slabs = allr = None
+    if args.full:
+        overflow_slabs = int(max(acct[:, 6].max(), acct_u[:, 6].max() if acct_u is not None else 0))
+        if overflow_slabs:
+            raise SystemExit(f"bench.py: {overflow_slabs} depth slabs overflowed the tile-pair buffers during the run (slow pair-free path)")
 
-    # gather per-rank numbers for the roofline of the projection pass (dominant HBM stream of the path)
-    local = torch.tensor([acct[:, 0].mean(), acct[:, 1].mean(), acct[:, 2].mean(), acct[:, 3].mean(), acct[:, 4].mean(),
-                          acct[:, 5].mean(), timing["project"]["ms"] * 1e3, timing["project"]["launches"]], dtype=torch.float64, device="cuda")
-    if use_dist:
-        allr = [torch.zeros_like(local) for _ in range(world)]
-        dist.all_gather(allr, local)
-    else:
-        allr = [local]
-    allr = torch.stack(allr).cpu().numpy()
+        # gather per-rank numbers for the roofline of the projection pass (dominant HBM stream of the path)
+        local = torch.tensor([acct[:, 0].mean(), acct[:, 1].mean(), acct[:, 2].mean(), acct[:, 3].mean(), acct[:, 4].mean(),
+                              acct[:, 5].mean(), timing["project"]["ms"] * 1e3, timing["project"]["launches"]], dtype=torch.float64, device="cuda")
+        if use_dist:
+            allr = [torch.zeros_like(local) for _ in range(world)]
+            dist.all_gather(allr, local)
+        else:
+            allr = [local]
+        allr = torch.stack(allr).cpu().numpy()
 
     # ---- N > 1 (index shards): what every rank did, so that a scaling run can be read — the library's own bookkeeping of the
     #      timed loop (gsx_shard_get_stats: host side, never synchronises) and a second, short loop with every pass bracketed ----
     per_rank = None
-    if lib_index:
+    if lib_index and args.full:
         frames_stats = max(shard_stats_timed["frames"], 1)
         renderer.set_pass_timing(True, None)
         renderer.get_pass_timing()
@@ -870,7 +906,7 @@ def main():
 
     comm_info = viewer.comm_info() if lib_index else None
     if rank == 0:
-        fps = args.steps / elapsed
+        fps = steps_requested / elapsed
         sh_bytes = {0: 180, 1: 96, 2: 48, 3: 0}[sh_kind if sh > 0 else 3]
         cov_bytes = {0: 24, 1: 12}[cov_kind]
         pod_bytes = 16 + sh_bytes + cov_bytes
@@ -904,11 +940,10 @@ def main():
                     "traffic_source": traffic_note if tr else (traffic_note if traffic is None else "no dispatch of this kernel in the PMC passes"),
                     "traffic_detail": tr}
 
-        n_loc, nvis_loc, nsort_loc, spec_frac, repair_frac, entries = allr[0][:6]
         passes = {}
         for name, tv in timing.items():
             if args.pass_timing == "all" or name in ("project", "project_geom"):
-                passes[name] = round(tv["ms"] / max(rounds(args.steps), 1), 4)
+                passes[name] = round(tv["ms"] / max(rounds(timing_steps), 1), 4)
         if not use_dist:
             sharding, scaling = "one GPU", "strong"
         elif afr:
@@ -930,9 +965,9 @@ def main():
             "unit": "frames/s",
             "n_gpus": world,
             "steps": steps_requested,
-            "steps_timed": args.steps,
+            "steps_timed": steps_requested,
             "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+            "ms_per_step": round(1e3 * elapsed / steps_requested, 4),
             "higher_is_better": True,
             "scaling": scaling,
             "vs_baseline": None,
@@ -945,17 +980,18 @@ def main():
                 "sharding": sharding, "schedule": "progressive depth slabs + temporal occlusion speculation (gsx_render_options defaults)"
                 if not overrides else f"overrides: {args.render_options}",
                 "frames_in_flight": lanes,
-                "n_visible_rank0": int(nvis_loc), "n_depth_sorted_rank0": int(nsort_loc), "tile_entries_rank0": int(entries),
-                "speculated_frames": round(float(spec_frac), 3), "frames_with_repair_round": round(float(repair_frac), 3),
                 "pass_ms_per_frame_rank0": passes,
                 "upload_GBps_pcie_inclusive": round(upload_gbs, 2), "scene_gen_s": round(t_gen, 1),
             },
-            "overflow_slabs": overflow_slabs,
         }
-        if elapsed_short is not None:
-            out["value_short_window"] = round(steps_requested / elapsed_short, 3)
-            out["value_note"] = (f"value / ms_per_step: {args.steps} frames (a whole orbit) between the fences — every timed loop of this line is at "
-                                 f"least one orbit long; value_short_window: the {steps_requested}-step window that was asked for, same loop, timed first")
+        if args.full:
+            n_loc, nvis_loc, nsort_loc, spec_frac, repair_frac, entries = allr[0][:6]
+            out["config"].update({
+                "n_visible_rank0": int(nvis_loc), "n_depth_sorted_rank0": int(nsort_loc), "tile_entries_rank0": int(entries),
+                "speculated_frames": round(float(spec_frac), 3), "frames_with_repair_round": round(float(repair_frac), 3)})
+            out["overflow_slabs"] = overflow_slabs
+            out["value_note"] = (f"value / ms_per_step: the {steps_requested} steps asked for, between the fences; every other timed loop of this "
+                                 f"line runs {args.steps} frames (at least one orbit, --min-steps); steady_state is the headline loop over such a loop")
         if elapsed_1 is not None:
             out["value_one_frame_in_flight"] = round(args.steps / elapsed_1, 3)
             out["ms_per_step_one_frame_in_flight"] = round(1e3 * elapsed_1 / args.steps, 4)
@@ -967,7 +1003,7 @@ def main():
                 "value_unspeculated, both rooflines and the robustness legs run with ONE frame in flight (kernel times uncontended).  "
                 f"Throughput, not latency: with {lanes} frames in flight a frame spends about {lanes} x ms_per_step on the device from its first "
                 "kernel to its last (ms_per_step_one_frame_in_flight is the latency of a frame that has the device to itself).")
-            out["frame_latency_ms_estimate"] = round(lanes * 1e3 * elapsed / args.steps, 4)
+            out["frame_latency_ms_estimate"] = round(lanes * 1e3 * elapsed / steps_requested, 4)
             if lanes_probe is not None:
                 out["frames_in_flight_probe"] = dict(lanes_probe, note="untimed, before the timed region: 48 frames with one frame in flight and 48 "
                                                      "with the default; the headline loop keeps the default unless it is below 0.85 x the one-lane rate")
@@ -988,7 +1024,7 @@ def main():
                                           "unspeculated, fully projecting timed loop of this run (slab_shading = 0)")
             out["roofline_speculated"] = roofline_of(acct, timing, "projection pass")
             out["config"]["tile_entries_unspeculated"] = int(acct_u[:, 5].mean())
-        else:
+        elif args.full:
             out["roofline"] = roofline_of(acct, timing, "projection pass: SH colour + cov2d + cull + depth key")
         if out.get("roofline") is not None:
             out["roofline"]["belongs_to"] = ("value_unspeculated_full_projection: that loop runs this kernel once per frame; the headline loop "
@@ -1059,26 +1095,27 @@ def main():
                                               "full, the exchange unfiltered (whole-shard slots); compare with value_unspeculated of the N = 1 line")
         if per_rank is not None:
             out["per_rank"] = per_rank
-        if lib_index and world > 1:
+        if lib_index and world > 1 and args.full:
             out["predicted"] = predicted_for(world, args.workload)
         if frame_check is not None and "frame_check" not in out:
             out["frame_check"] = frame_check
         if one_device:
             out["one_device_emulation"] = (f"GSX_BENCH_ONE_DEVICE=1: the {world} ranks are processes sharing ONE GPU, RCCL over sockets on lo — the N > 1 "
                                            "code ran for real, `value` measures nothing")
-        if launches:
+        if launches and args.full:
             out["launches_per_frame"] = {k: v for k, v in launches.items() if k != "per_frame"}
-        out["resident_bytes"] = {"device_bytes_after_headline_loop": int(resident_bytes), "per_gaussian_of_this_rank": round(resident_bytes / max(count, 1), 1),
-                                 "gaussians_of_this_rank": int(count),
-                                 "what": "gsx_debug_device_bytes(): every device buffer the library holds in this process (planes, shade records, sort / bin / "
-                                         "list buffers of every lane, framebuffers); the planes alone are 236 B per Gaussian for the f32 pod"}
+        if resident_bytes is not None:
+            out["resident_bytes"] = {"device_bytes_after_headline_loop": int(resident_bytes), "per_gaussian_of_this_rank": round(resident_bytes / max(count, 1), 1),
+                                     "gaussians_of_this_rank": int(count),
+                                     "what": "gsx_debug_device_bytes(): every device buffer the library holds in this process (planes, shade records, sort / bin / "
+                                             "list buffers of every lane, framebuffers); the planes alone are 236 B per Gaussian for the f32 pod"}
         if extra and "launch_graphs" in extra:
             out["launch_graphs"] = extra["launch_graphs"]
         if robustness is not None:
             out["robustness"] = robustness
         # the figures a reader wants side by side, as the LAST keys of the line (a log tail that truncates the line keeps them)
-        summary = {"value": out["value"], "frames_in_flight": lanes, "steps_timed": args.steps}
-        for k_out, k_sum in (("value_short_window", "value_short_window"), ("value_one_frame_in_flight", "value_one_frame_in_flight"),
+        summary = {"value": out["value"], "frames_in_flight": lanes, "steps_timed": steps_requested}
+        for k_out, k_sum in (("value_one_frame_in_flight", "value_one_frame_in_flight"),
                              ("value_synchronised", "value_synchronised"), ("value_reference_protocol", "value_reference_protocol"),
                              ("value_unspeculated", "value_unspeculated"), ("value_unspeculated_full_projection", "value_unspeculated_full_projection"),
                              ("value_synchronised_unspeculated", "value_synchronised_unspeculated")):
@@ -1096,7 +1133,7 @@ def main():
         if "passes" in out:
             summary["passes_us"] = {sch: {k: v["us_per_frame"] for k, v in out["passes"][sch].items() if isinstance(v, dict)}
                                     for sch in ("speculated", "unspeculated", "full_projection")}
-        if launches:
+        if "launches_per_frame" in out:
             summary["launches_per_frame"] = out["launches_per_frame"]
         if robustness is not None:
             summary["robustness_fps"] = {k: [v["speculated"]["fps"], v["unspeculated"]["fps"]] for k, v in robustness.items() if isinstance(v, dict)}
@@ -1109,10 +1146,10 @@ def main():
         renderer.close()
         closed = True
         cpu_res = None
-        if single and not overrides and not args.no_cfg5 and not args.no_extra_legs:
+        if single and args.full and not overrides and not args.no_cfg5 and not args.no_extra_legs:
             out["cfg5"] = cfg5_leg()
             summary["cfg5_fps"] = [out["cfg5"]["fps_one_frame_in_flight"], out["cfg5"]["fps_two_frames_in_flight"], out["cfg5"]["fps_unspeculated"]]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu_res, oracle_frame = cpu_baseline(cfg, args.cpu_sample, keep=True)
             if gpu_pose0 is not None and oracle_frame is not None:
                 out["oracle_check"] = oracle_check_of(gpu_pose0, oracle_frame, 0)

@@ -5,7 +5,9 @@ import glob
 import json
 import os
 import re
+import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -156,3 +158,74 @@ def test_profiled_kernel_time_agrees_with_bench():
         o = json.loads(open(own[-1]).read().strip())
         us_own = o["roofline"]["avg_launch_us"]
         assert abs(avg_ns / 1e3 - us_own) / us_own < 0.05, (avg_ns / 1e3, us_own)
+
+
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("gsx_bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bench_arguments_plain_run_and_exact_steps(monkeypatch):
+    """a plain run is the default (--full off, no dump); --steps is taken as given and must be at least 1"""
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert "elapsed, timing, last_idx = timed_loop(0, steps_requested)" in src, "the headline loop times exactly --steps frames"
+
+
+def test_dump_outputs_float32_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per array; an array over the budget becomes the same seeded sample of whole rows every time"""
+    bench = _bench_module()
+    fb = np.arange(6 * 5 * 4, dtype=np.float32).reshape(6, 5, 4)
+    bench.dump_outputs(str(tmp_path / "a"), {"framebuffer": fb})
+    got = np.load(tmp_path / "a" / "framebuffer.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, fb)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 10 * 4 * 4)   # room for 10 of the 30 pixels
+    bench.dump_outputs(str(tmp_path / "b"), {"frame_rgba8": fb.astype(np.uint8)})
+    bench.dump_outputs(str(tmp_path / "c"), {"frame_rgba8": fb.astype(np.uint8)})
+    b, c = np.load(tmp_path / "b" / "frame_rgba8.npy"), np.load(tmp_path / "c" / "frame_rgba8.npy")
+    assert b.dtype == np.float32 and b.shape == (10, 4) and b.nbytes <= 10 * 4 * 4 and np.array_equal(b, c)
+    rows = fb.astype(np.uint8).astype(np.float32).reshape(-1, 4)
+    assert all(any(np.array_equal(r, x) for x in rows) for r in b), "every sampled row is a pixel of the frame"
+
+
+def _run_plain_bench(out_dir):
+    import subprocess
+
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "4", "--gaussians", "400000",
+           "--dump-outputs", str(out_dir)]
+    p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-4000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_steps_and_dumps_the_last_frame(tmp_path):
+    """GPU: a plain run times exactly --steps frames, carries the headline fields and none of --full's, and writes the last timed
+    frame; a second run with the same arguments writes the same bytes"""
+    d = _run_plain_bench(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 12 and d["steps_timed"] == 12 and d["warmup"] == 4 and d["unit"] == "frames/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) / d["value"] < 1e-2
+    for k in ("roofline", "value_unspeculated", "frame_check", "robustness", "cfg5", "cpu_baseline"):
+        assert k not in d, k
+    fb = np.load(tmp_path / "a" / "framebuffer.npy")
+    assert fb.dtype == np.float32 and fb.shape == (d["config"]["height"], d["config"]["width"], 4)
+    assert np.isfinite(fb).all() and (fb[..., 3] < 1.0).any(), "something was drawn"
+    _run_plain_bench(tmp_path / "b")
+    assert np.array_equal(fb, np.load(tmp_path / "b" / "framebuffer.npy"))

@@ -20,7 +20,7 @@ def _launch(world, extra, port, timeout=420):
     env = dict(os.environ)
     env.update({"GSX_BENCH_ONE_DEVICE": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0", "PYTHONPATH": ROOT})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "12", "--warmup", "4",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--steps", "12", "--warmup", "4",
            "--min-steps", "0", "--gaussians", "400000"] + extra
     p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, start_new_session=True)
     try:

@@ -7,6 +7,6 @@ mkdir -p "$OUT"
 export GSX_BENCH_ONE_DEVICE=1
 for N in ${@:-2 4 8}; do
   timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $((29600 + N)) \
-    bench.py --gpus "$N" > "$OUT/world$N.json" 2> "$OUT/world$N.err"
+    bench.py --full --gpus "$N" > "$OUT/world$N.json" 2> "$OUT/world$N.err"
   echo "N=$N rc=$? $(cut -c1-160 "$OUT/world$N.json")"
 done

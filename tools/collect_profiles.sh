@@ -11,15 +11,15 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 if want A; then
 # 1. the bench line exactly as the driver runs it (PMC child passes, every timed loop, frame check, synchronised / steady / per-pass
 #    legs, robustness legs, full CPU baseline), and with the driver's short window
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2>> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2>> $OUT/bench.err
 # 2. kernel trace + stats of the same command (the timed loops are in it: k_project<3,0,0> and k_project_geom averages must agree
 #    with roofline.avg_launch_us / roofline_speculated.avg_launch_us of the line it prints itself)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py --no-cpu-baseline --no-pmc --no-extra-legs --no-robustness > $OUT/kt_bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py --full --no-cpu-baseline --no-pmc --no-extra-legs --no-robustness > $OUT/kt_bench.log 2>&1
 # 3. per-frame kernel breakdowns of the speculated and of the unspeculated loop alone, and of the sharded frame at world 1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_spec -o kt -- python3 bench.py --steps 100 --warmup 10 --min-steps 0 --no-cpu-baseline --no-pmc --render-options speculative=1 > $OUT/kt_spec.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_nospec -o kt -- python3 bench.py --steps 100 --warmup 10 --min-steps 0 --no-cpu-baseline --no-pmc --render-options speculative=0 > $OUT/kt_nospec.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_dist -o kt -- python3 bench.py --force-dist --steps 100 --warmup 10 --min-steps 0 --no-cpu-baseline --no-pmc --dist-frames-in-flight 1 > $OUT/kt_dist.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_spec -o kt -- python3 bench.py --full --steps 100 --warmup 10 --min-steps 0 --no-cpu-baseline --no-pmc --render-options speculative=1 > $OUT/kt_spec.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_nospec -o kt -- python3 bench.py --full --steps 100 --warmup 10 --min-steps 0 --no-cpu-baseline --no-pmc --render-options speculative=0 > $OUT/kt_nospec.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_dist -o kt -- python3 bench.py --full --force-dist --steps 100 --warmup 10 --min-steps 0 --no-cpu-baseline --no-pmc --dist-frames-in-flight 1 > $OUT/kt_dist.log 2>&1
 python3 tools/kernel_breakdown.py $OUT/kt_spec 143 40 > $OUT/kt_spec_breakdown.txt
 python3 tools/kernel_breakdown.py $OUT/kt_nospec 143 40 > $OUT/kt_nospec_breakdown.txt
 python3 tools/kernel_breakdown.py $OUT/kt_dist 143 40 > $OUT/kt_dist_breakdown.txt
@@ -31,13 +31,13 @@ python3 tools/pmc_summary.py $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE $OUT/pmc_su
 fi
 if want B; then
 # 5. the other workloads / pods / the index-sharded path on one rank (frames in flight 1, 2, 3)
-for w in cfg2 cfg3; do python3 bench.py --workload $w --no-cpu-baseline --no-pmc > $OUT/bench_$w.json 2>> $OUT/bench.err; done
-python3 bench.py --pod half/half --no-cpu-baseline --no-pmc --no-robustness --no-extra-legs > $OUT/bench_half_half.json 2>> $OUT/bench.err
-python3 bench.py --pod norm8/half --no-cpu-baseline --no-pmc --no-robustness --no-extra-legs > $OUT/bench_norm8_half.json 2>> $OUT/bench.err
-for L in 1 2 3; do python3 bench.py --force-dist --no-cpu-baseline --no-pmc --dist-frames-in-flight $L > $OUT/bench_index_world1_inflight$L.json 2>> $OUT/bench.err; done
+for w in cfg2 cfg3; do python3 bench.py --full --workload $w --no-cpu-baseline --no-pmc > $OUT/bench_$w.json 2>> $OUT/bench.err; done
+python3 bench.py --full --pod half/half --no-cpu-baseline --no-pmc --no-robustness --no-extra-legs > $OUT/bench_half_half.json 2>> $OUT/bench.err
+python3 bench.py --full --pod norm8/half --no-cpu-baseline --no-pmc --no-robustness --no-extra-legs > $OUT/bench_norm8_half.json 2>> $OUT/bench.err
+for L in 1 2 3; do python3 bench.py --full --force-dist --no-cpu-baseline --no-pmc --dist-frames-in-flight $L > $OUT/bench_index_world1_inflight$L.json 2>> $OUT/bench.err; done
 # 6. frames in flight on the single-GPU path: one / three lanes for the headline loop
-python3 bench.py --no-cpu-baseline --no-pmc --no-robustness --no-extra-legs --frames-in-flight 1 > $OUT/bench_inflight1.json 2>> $OUT/bench.err
-python3 bench.py --no-cpu-baseline --no-pmc --no-robustness --no-extra-legs --frames-in-flight 3 > $OUT/bench_inflight3.json 2>> $OUT/bench.err
+python3 bench.py --full --no-cpu-baseline --no-pmc --no-robustness --no-extra-legs --frames-in-flight 1 > $OUT/bench_inflight1.json 2>> $OUT/bench.err
+python3 bench.py --full --no-cpu-baseline --no-pmc --no-robustness --no-extra-legs --frames-in-flight 3 > $OUT/bench_inflight3.json 2>> $OUT/bench.err
 # 7. BASELINE configs[4] on one GPU: 4 x 6 M Gaussians at 3840x2160, with and without the stored selection + edit
 (python3 tools/bench_cfg5.py; python3 tools/bench_cfg5.py --edit 0; python3 tools/bench_cfg5.py --edit 0 --shard 1) 2>> $OUT/bench.err | grep '^{' > $OUT/bench_cfg5.json
 tools/bench_hbm > $OUT/bench_hbm.txt 2>&1
@@ -53,7 +53,7 @@ if want C; then
 tools/bench_launch > $OUT/bench_launch.txt 2>&1
 python3 tools/graph_probe.py 200 > $OUT/graph_probe.txt 2>> $OUT/bench.err
 for N in 2 8; do
-  GSX_BENCH_ONE_DEVICE=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600+N)) bench.py --gpus $N --steps 20 --warmup 5 > $OUT/bench_ranks_on_one_gpu_world$N.json 2>> $OUT/bench.err
+  GSX_BENCH_ONE_DEVICE=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600+N)) bench.py --full --gpus $N --steps 20 --warmup 5 > $OUT/bench_ranks_on_one_gpu_world$N.json 2>> $OUT/bench.err
 done
 
 # 9. round 4: per-tile profile of the block compositor (index order against expensive-first), the A/B of that order on the bench
