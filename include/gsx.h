@@ -219,6 +219,39 @@ gsx_status gsx_render(gsx_viewer* v, const char* const* keys_far_to_near, uint32
 /* preprocess + sort for every key, then render: one call per frame. */
 gsx_status gsx_render_frame(gsx_viewer* v, const char* const* keys_far_to_near, uint32_t n_keys);
 
+/* ---- depth test against the caller's depth buffer: the `depth_stencil` of gs::MultiModelViewer::new_with,
+ *      DepthStencilState { Depth32Float, depth_write_enabled: false, Less } (scene.rs:1969-1980).  The app draws the mask
+ *      gizmos and the measurement lines with depth write on first (scene.rs:2145-2160, renderer/measurement.rs:110-115); a
+ *      splat behind them is hidden at that pixel (spec §6, "Depth test").
+ *  - The buffer is float32 [height][width] (row 0 at the top, like the framebuffer) of NDC depth in [0, 1], viewport-sized.
+ *    A splat's fragments carry the depth of its centre; with GSX_DEPTH_LESS it is blended at pixel p only if it lies in front
+ *    of D(p).  Nothing is written to the buffer.  Every model of a frame is tested against the same buffer.  D >= 1 (a cleared
+ *    buffer) hides nothing: the frame is the one without the test, bit for bit; D <= 0 or NaN hides everything.
+ *  - The test is made in the depth-key domain and needs a projection whose third and fourth rows depend on view z alone
+ *    (P20 = P21 = P30 = P31 = P33 = 0, P32 = -1: perspective_rh, perspective_infinite_rh); gsx_preprocess refuses any other
+ *    with GSX_ERR_INVALID_ARG while the test is on, as it refuses a buffer whose size is not the viewport's.
+ *  - When the contents are read: on the viewer's stream, by the first gsx_preprocess of a frame (gsx_render_frame's
+ *    included) — that snapshot decides which splats enter the depth sort and which pixels they reach; gsx_sort and gsx_render
+ *    use it.  The buffer is read again by the next gsx_preprocess after gsx_render / gsx_render_frame, after gsx_update_camera,
+ *    or for a model already preprocessed against the current snapshot (a new frame, whether or not the last one was rendered);
+ *    every gsx_render_frame reads it.  Writing into a device buffer between gsx_preprocess and gsx_render changes nothing of
+ *    that frame.  Calling gsx_viewer_set_depth_test,
+ *    gsx_viewer_set_depth_buffer_device or gsx_viewer_upload_depth_buffer between gsx_preprocess and gsx_render makes
+ *    gsx_render refuse the frame (GSX_ERR_INVALID_ARG): preprocess + sort the models again.
+ *  - gsx_shard_* frames (and gsx_render_more) return GSX_ERR_INVALID_ARG while the test is on.
+ *  - With frames_in_flight > 1, a depth-tested frame runs on the viewer itself, one at a time (like a frame with a query). */
+typedef enum gsx_depth_compare { GSX_DEPTH_ALWAYS = 0 /* no test (default) */, GSX_DEPTH_LESS = 1 } gsx_depth_compare;
+gsx_status gsx_viewer_set_depth_test(gsx_viewer* v, gsx_depth_compare compare);
+/* Caller-owned DEVICE memory, 4-byte aligned, read in place: `height` rows of `width` floats, row_pitch_bytes apart (>= 4 * width, a
+ * multiple of 4); it must
+ * stay valid while frames that read it are in flight.  NULL detaches it (an uploaded buffer, if any, is used again). */
+gsx_status gsx_viewer_set_depth_buffer_device(gsx_viewer* v, const float* d_ptr, uint32_t width, uint32_t height,
+                                              uint64_t row_pitch_bytes);
+/* A copy of host memory (width * height floats, tightly packed) into a viewer-owned buffer, ordered on the viewer's stream; it waits
+ * for the stream (≈ 0.2 ms a call at 1920x1080: prefer the device buffer for a depth attachment that changes every frame);
+ * replaces any device buffer set before. */
+gsx_status gsx_viewer_upload_depth_buffer(gsx_viewer* v, const float* host, uint32_t width, uint32_t height);
+
 /* ---- readback (buffer.download(&device,&queue), app.rs:789, app.rs:806) ---- */
 /* float32 [height][width][4] = premultiplied r,g,b and transmittance T. Synchronises. */
 gsx_status gsx_download_framebuffer(gsx_viewer* v, float* rgbt, uint64_t n_floats);

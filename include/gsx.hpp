@@ -197,11 +197,21 @@ public:
     Cov3dCompression cov3d;
     UVec2 size{1, 1};
 
-    // MultiModelViewer::new_with(&device, format, depth_stencil, size): the target format / depth state of the
-    // reference have no meaning for a float (rgb,T) framebuffer and are dropped.
+    // MultiModelViewer::new_with(&device, format, depth_stencil, size): the target format has no meaning for a float (rgb,T)
+    // framebuffer and is dropped; depth_stencil = Some(DepthStencilState { Depth32Float, depth_write_enabled: false, Less }) is
+    // depth_test = GSX_DEPTH_LESS (scene.rs:1969-1980) — hand the frame's depth attachment over with update_depth_buffer.
     static MultiModelViewer new_with(int device, UVec2 size, ShCompression sh = ShCompression::Single,
-                                     Cov3dCompression cov3d = Cov3dCompression::Single) {
-        return MultiModelViewer(device, size, sh, cov3d);
+                                     Cov3dCompression cov3d = Cov3dCompression::Single,
+                                     gsx_depth_compare depth_test = GSX_DEPTH_ALWAYS) {
+        MultiModelViewer v(device, size, sh, cov3d);
+        v.set_depth_test(depth_test);
+        return v;
+    }
+    void set_depth_test(gsx_depth_compare c) { check(gsx_viewer_set_depth_test(v_, c)); }
+    // float32 [size.y][size.x] NDC depth, row 0 at the top: copied (host memory) or read in place (device memory, row pitch in bytes)
+    void update_depth_buffer(const float* host, UVec2 sz) { check(gsx_viewer_upload_depth_buffer(v_, host, sz.x, sz.y)); }
+    void set_depth_buffer_device(const float* d_ptr, UVec2 sz, uint64_t row_pitch_bytes) {
+        check(gsx_viewer_set_depth_buffer_device(v_, d_ptr, sz.x, sz.y, row_pitch_bytes));
     }
     MultiModelViewer(int device, UVec2 sz, ShCompression sh_, Cov3dCompression cov_) : sh(sh_), cov3d(cov_), size(sz) {
         gsx_viewer_desc d{GSX_ABI_VERSION, device, nullptr, sz.x, sz.y};

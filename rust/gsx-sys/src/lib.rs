@@ -120,6 +120,9 @@ pub struct gsx_buffer {
 #[repr(i32)]
 #[derive(Clone, Copy, PartialEq, Eq)]
 pub enum gsx_buffer_kind { Mask = 0, Edits = 1, Selection = 2 }
+#[repr(i32)]
+#[derive(Clone, Copy, PartialEq, Eq)]
+pub enum gsx_depth_compare { Always = 0, Less = 1 } // the compare of new_with's depth_stencil, src/tab/scene.rs:1969-1980
 /// the two collectives of a caller-supplied transport: they ENQUEUE on `hip_stream` and return 0 or a gsx_status
 pub type gsx_comm_all_to_all_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, d_send: *const c_void, d_recv: *mut c_void, bytes_per_peer: u64, hip_stream: *mut c_void) -> gsx_status>;
 pub type gsx_comm_all_gather_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, d_send: *const c_void, d_recv: *mut c_void, bytes_per_rank: u64, hip_stream: *mut c_void) -> gsx_status>;
@@ -171,6 +174,9 @@ extern "C" {
     pub fn gsx_sync(v: *mut gsx_viewer) -> gsx_status;
     pub fn gsx_render(v: *mut gsx_viewer, keys_far_to_near: *const *const c_char, n_keys: u32) -> gsx_status;
     pub fn gsx_render_frame(v: *mut gsx_viewer, keys_far_to_near: *const *const c_char, n_keys: u32) -> gsx_status;
+    pub fn gsx_viewer_set_depth_test(v: *mut gsx_viewer, compare: gsx_depth_compare) -> gsx_status;
+    pub fn gsx_viewer_set_depth_buffer_device(v: *mut gsx_viewer, d_ptr: *const f32, width: u32, height: u32, row_pitch_bytes: u64) -> gsx_status;
+    pub fn gsx_viewer_upload_depth_buffer(v: *mut gsx_viewer, host: *const f32, width: u32, height: u32) -> gsx_status;
     pub fn gsx_download_framebuffer(v: *mut gsx_viewer, rgbt: *mut f32, n_floats: u64) -> gsx_status;
     pub fn gsx_download_rgba8(v: *mut gsx_viewer, background_rgb: *const f32, rgba: *mut u8, n_bytes: u64) -> gsx_status;
     pub fn gsx_framebuffer_device_ptr(v: *mut gsx_viewer, out_ptr: *mut *mut c_void, out_w: *mut u32, out_h: *mut u32) -> gsx_status;

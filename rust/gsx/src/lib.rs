@@ -187,14 +187,29 @@ pub struct MultiModelViewer<G: GaussianPod> {
     _pod: PhantomData<G>,
 }
 impl<G: GaussianPod> MultiModelViewer<G> {
-    /// `MultiModelViewer::new_with(&device, target_format, depth_stencil, uvec2(1, 1))` (scene.rs:1969-1980); format and depth
-    /// state do not apply (the result is an (rgb, T) float image).
-    pub fn new_with<D, F, S>(_device: &D, _format: F, _depth_stencil: Option<S>, size: (u32, u32)) -> Result<Self, Error> {
+    /// `MultiModelViewer::new_with(&device, target_format, depth_stencil, uvec2(1, 1))` (scene.rs:1969-1980).  The format does not
+    /// apply (the result is an (rgb, T) float image); `depth_stencil = Some(..)` — the app's
+    /// `DepthStencilState { Depth32Float, depth_write_enabled: false, Less }` — turns on the depth test against the buffer given to
+    /// `update_depth_buffer` each frame (`None`: no test).  The state itself is not inspected: libgsx has `Less` without depth write
+    /// only (the app's state), so ANY `Some(..)` — another compare, depth write on — is taken as that; map other states yourself.
+    pub fn new_with<D, F, S>(_device: &D, _format: F, depth_stencil: Option<S>, size: (u32, u32)) -> Result<Self, Error> {
         let desc = sys::gsx_viewer_desc { abi_version: sys::GSX_ABI_VERSION, device: 0, stream: std::ptr::null_mut(), width: size.0, height: size.1 };
         let mut v = std::ptr::null_mut();
         check(unsafe { sys::gsx_viewer_create(&desc, &mut v) })?;
-        Ok(Self { handle: Handle(v), models: HashMap::new(), preprocessor: Preprocessor(v), radix_sorter: RadixSorter(v), renderer: Renderer(v),
-                  postprocessor: Postprocessor(v), _pod: PhantomData })
+        let viewer = Self { handle: Handle(v), models: HashMap::new(), preprocessor: Preprocessor(v), radix_sorter: RadixSorter(v), renderer: Renderer(v),
+                            postprocessor: Postprocessor(v), _pod: PhantomData };
+        if depth_stencil.is_some() {
+            check(unsafe { sys::gsx_viewer_set_depth_test(v, sys::gsx_depth_compare::Less) })?;
+        }
+        Ok(viewer)
+    }
+    /// The frame's depth attachment after the gizmo and measurement passes (`Depth32Float`, `[height][width]`, row 0 at the top),
+    /// copied; read by the frame's first preprocess.
+    pub fn update_depth_buffer(&mut self, depth: &[f32], size: (u32, u32)) -> Result<(), Error> {
+        if depth.len() != size.0 as usize * size.1 as usize {
+            return Err(Error::Gsx { status: sys::GSX_ERR_INVALID_ARG, message: "update_depth_buffer: depth.len() != width * height".into() });
+        }
+        check(unsafe { sys::gsx_viewer_upload_depth_buffer(self.handle.0, depth.as_ptr(), size.0, size.1) })
     }
     /// `GaussianBuffers::new_empty(&device, count)` + `BindGroups::new(..)` + `models.insert(key, ..)` (scene.rs:2111-2139)
     pub fn insert_model(&mut self, key: &str, count: usize) -> Result<(), Error> {

@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""What the depth test (gsx_viewer_set_depth_test) costs on cfg4's orbit (10 M Gaussians, SH-3, 1920x1080), one process, one GPU.
+
+Four modes, in alternating blocks of --block frames so that drift of the box hits them alike:
+  off              no depth test (the headline schedule)
+  cleared          GSX_DEPTH_LESS against a cleared buffer (all 1.0): the same pixels, the extra work of the test
+  occluder         GSX_DEPTH_LESS against a box at view depth --box-depth over the middle quarter of the screen (half the width, half the height)
+  occluder_upload  the same box, handed over from host memory EVERY frame (gsx_viewer_upload_depth_buffer: a copy and a wait)
+cleared and occluder read a device buffer in place (gsx_viewer_set_depth_buffer_device, set once), as an app whose depth attachment is
+device memory does: the buffer is read by every frame's first preprocess whether or not it changed.
+The host waits for every frame (gsx_render_frame + gsx_sync), as the app does.  Prints ONE JSON line: fps per mode (median of its
+blocks, and every block), and the ratios to `off`.
+
+    python tools/bench_depth.py [--blocks 6] [--block 120] [--warmup 60]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from wgpu_3dgs_viewer_app_amd import camera, scene  # noqa: E402
+from wgpu_3dgs_viewer_app_amd.viewer import DepthCompare, GaussianDisplayMode, GaussianShDegree, MultiModelViewer  # noqa: E402
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="cfg4")
+    ap.add_argument("--blocks", type=int, default=6, help="blocks per mode")
+    ap.add_argument("--block", type=int, default=120, help="frames per block")
+    ap.add_argument("--warmup", type=int, default=60, help="frames per mode before the first timed block")
+    ap.add_argument("--box-depth", type=float, default=3.0, help="view depth of the occluding box (the orbit's radius is 6; the scene saturates at ~4-5)")
+    a = ap.parse_args()
+
+    import torch
+
+    torch.zeros(1, device="cuda")   # (torch's lazy device initialisation fails behind gigabytes of libgsx allocations: first)
+    n, sh, w, h, seed = scene.CONFIGS[a.config]
+    g = scene.synthetic_gaussians(n, seed, sh)
+    v = MultiModelViewer()
+    v.add_model("m", n)
+    v.models["m"].gaussian_buffers.gaussians_buffer.update_range(0, g)
+    del g
+    v.update_gaussian_transform(1.0, GaussianDisplayMode.Splat, GaussianShDegree.new(sh), False)
+    orbit = [camera.PrecomputedCamera(camera.orbit_pose(k), w / h) for k in range(240)]
+    p = np.asarray(orbit[0].projection(w / h), np.float32).reshape(16)
+    box = np.float32(np.float32(p[14]) / np.float32(a.box_depth) - np.float32(p[10]))   # the NDC depth a surface there writes
+    cleared = np.ones((h, w), np.float32)
+    occluder = cleared.copy()
+    occluder[h // 4: 3 * h // 4, w // 4: 3 * w // 4] = box
+    dev = {"cleared": torch.from_numpy(cleared).cuda(), "occluder": torch.from_numpy(occluder).cuda()}
+    torch.cuda.synchronize()
+    modes = {"off": None, "cleared": cleared, "occluder": occluder, "occluder_upload": occluder}
+    frame = [0]
+
+    def select(mode: str) -> None:
+        v.set_depth_test(DepthCompare.Always if modes[mode] is None else DepthCompare.Less)
+        if mode in dev:
+            v.set_depth_buffer_device(dev[mode].data_ptr(), w, h, 4 * w)
+        elif modes[mode] is not None:
+            v.update_depth_buffer(modes[mode])
+
+    def run(mode: str, frames: int) -> float:
+        select(mode)
+        upload = mode == "occluder_upload"
+        v.poll()
+        t0 = time.perf_counter()
+        for _ in range(frames):
+            if upload:
+                v.update_depth_buffer(occluder)
+            v.update_camera(orbit[frame[0] % 240], (w, h))
+            v.render_frame(["m"])
+            v.poll()
+            frame[0] += 1
+        return frames / (time.perf_counter() - t0)
+
+    for m in modes:
+        run(m, a.warmup)
+    fps = {m: [] for m in modes}
+    for _ in range(a.blocks):
+        for m in modes:
+            fps[m].append(run(m, a.block))
+    stats = {}
+    for m in modes:
+        select(m)
+        v.update_camera(orbit[0], (w, h))
+        v.render_frame(["m"])
+        v.poll()
+        stats[m] = v.frame_stats("m")
+    v.set_depth_buffer_device(None, 0, 0, 0)
+    v.close()
+    med = {m: statistics.median(x) for m, x in fps.items()}
+    print(json.dumps({
+        "tool": "bench_depth", "config": a.config, "gaussians": n, "size": [w, h], "host_waits_per_frame": True,
+        "fps": {m: round(x, 1) for m, x in med.items()},
+        "fps_blocks": {m: [round(y, 1) for y in x] for m, x in fps.items()},
+        "ratio_to_off": {m: round(med[m] / med["off"], 4) for m in modes},
+        "pose0_stats": stats,
+    }))
+
+
+if __name__ == "__main__":
+    main()

@@ -12,7 +12,8 @@ code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
 protos = re.findall(r"^(gsx_status|void|uint32_t|uint64_t|const char\*)\s+(gsx_\w+)\s*\(([^;]*?)\);", code, flags=re.M | re.S)
 
 SCALAR = {"uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i32", "float": "f32", "char": "c_char", "void": "c_void",
-          "gsx_sh_kind": "gsx_sh_kind", "gsx_cov3d_kind": "gsx_cov3d_kind", "gsx_display_mode": "gsx_display_mode", "gsx_status": "gsx_status", "gsx_buffer_kind": "gsx_buffer_kind"}
+          "gsx_sh_kind": "gsx_sh_kind", "gsx_cov3d_kind": "gsx_cov3d_kind", "gsx_display_mode": "gsx_display_mode", "gsx_status": "gsx_status", "gsx_buffer_kind": "gsx_buffer_kind",
+          "gsx_depth_compare": "gsx_depth_compare"}
 
 
 def rust_type(ctype: str) -> str:
@@ -168,6 +169,9 @@ pub struct gsx_buffer {
 #[repr(i32)]
 #[derive(Clone, Copy, PartialEq, Eq)]
 pub enum gsx_buffer_kind { Mask = 0, Edits = 1, Selection = 2 }
+#[repr(i32)]
+#[derive(Clone, Copy, PartialEq, Eq)]
+pub enum gsx_depth_compare { Always = 0, Less = 1 } // the compare of new_with's depth_stencil, src/tab/scene.rs:1969-1980
 /// the two collectives of a caller-supplied transport: they ENQUEUE on `hip_stream` and return 0 or a gsx_status
 pub type gsx_comm_all_to_all_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, d_send: *const c_void, d_recv: *mut c_void, bytes_per_peer: u64, hip_stream: *mut c_void) -> gsx_status>;
 pub type gsx_comm_all_gather_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, d_send: *const c_void, d_recv: *mut c_void, bytes_per_rank: u64, hip_stream: *mut c_void) -> gsx_status>;

@@ -101,7 +101,7 @@ static gsx_status lane_create(gsx_viewer* v, gsx_viewer** out) {
 // the owner prepares before the frame is dealt out, prepare_edits_for_lanes)
 static bool frame_may_overlap(gsx_viewer* v, const char* const* keys, uint32_t n_keys) {
     if (v->parent || v->options.frames_in_flight < 2 || v->query.kind != GSX_QUERY_NONE || v->ext_fb || v->band_lo != 0 ||
-        v->band_hi != 0xFFFFFFFFu)
+        v->band_hi != 0xFFFFFFFFu || v->depth_compare != GSX_DEPTH_ALWAYS)  // (a depth-tested frame reads the viewer's depth snapshot)
         return false;
     for (uint32_t i = 0; i < n_keys; ++i) {
         Model* m = find_model(v, keys ? keys[i] : nullptr);
@@ -502,6 +502,7 @@ gsx_status gsx_update_camera(gsx_viewer* v, const float view[16], const float pr
     memcpy(v->proj, proj, sizeof(float) * 16);
     v->width = width;
     v->height = height;
+    v->depth_frame_closed = true;  // a new camera: the next gsx_preprocess takes a new depth snapshot
     return GSX_OK;
 }
 
@@ -665,12 +666,14 @@ gsx_status gsx_render(gsx_viewer* v, const char* const* keys, uint32_t n_keys) {
     v->latest = nullptr;
     TraceScope trace(v, TRACE_RENDER);
     if ((st = do_render(v, keys, n_keys))) return st;
+    v->depth_frame_closed = true;  // the next gsx_preprocess reads the depth buffer again
     v->host_waited = false;   // (until the app waits again)
     return trace.finish();
 }
 
 gsx_status gsx_render_frame(gsx_viewer* v, const char* const* keys, uint32_t n_keys) {
     if (!v) return fail(GSX_ERR_INVALID_ARG, "viewer is null");
+    v->depth_frame_closed = true;  // one whole frame: its first preprocess reads the depth buffer, whatever the frame before left
     gsx_status st = GSX_OK;
     gsx_viewer* lane = v;
     if (frame_may_overlap(v, keys, n_keys)) {
@@ -690,6 +693,7 @@ gsx_status gsx_render_frame(gsx_viewer* v, const char* const* keys, uint32_t n_k
             if ((st = do_sort(lane, m))) return st;
         }
         if ((st = do_render(lane, keys, n_keys))) return st;
+        v->depth_frame_closed = true;  // the next gsx_preprocess reads the depth buffer again
         v->host_waited = false;   // (until the app waits again: gsx_sync, a blocking readback)
         if ((st = trace.finish())) return st;
     }

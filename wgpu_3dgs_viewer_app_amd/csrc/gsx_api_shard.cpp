@@ -37,6 +37,59 @@ gsx_status gsx_viewer_set_external_framebuffer(gsx_viewer* v, void* d_ptr, uint6
 }
 
 
+gsx_status gsx_viewer_set_depth_test(gsx_viewer* v, gsx_depth_compare compare) {
+    if (compare != GSX_DEPTH_ALWAYS && compare != GSX_DEPTH_LESS)
+        return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_set_depth_test: unknown compare %d (GSX_DEPTH_ALWAYS, GSX_DEPTH_LESS)", (int)compare);
+    gsx_status st = viewer_bind(v);
+    if (st) return st;
+    if (v->parent) return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_set_depth_test: called on a lane");
+    if (v->depth_compare != (uint32_t)compare) v->depth_cfg += 1;  // (frames preprocessed under the old setting are refused by gsx_render)
+    v->depth_compare = (uint32_t)compare;
+    return GSX_OK;
+}
+
+gsx_status gsx_viewer_set_depth_buffer_device(gsx_viewer* v, const float* d_ptr, uint32_t width, uint32_t height, uint64_t row_pitch_bytes) {
+    gsx_status st = viewer_bind(v);
+    if (st) return st;
+    if (v->parent) return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_set_depth_buffer_device: called on a lane");
+    if (d_ptr && (width == 0 || height == 0 || row_pitch_bytes < 4ull * width || (row_pitch_bytes & 3u)))
+        return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_set_depth_buffer_device: %ux%u with a row pitch of %llu bytes (needs >= 4 x width, a multiple of 4)",
+                    width, height, (unsigned long long)row_pitch_bytes);
+    if (d_ptr && (reinterpret_cast<uintptr_t>(d_ptr) & 3u))
+        return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_set_depth_buffer_device: the buffer is not 4-byte aligned");
+    v->depth_dev = d_ptr;
+    v->depth_pitch = d_ptr ? row_pitch_bytes : 0;
+    if (d_ptr) {
+        v->depth_w = width;
+        v->depth_h = height;
+    } else {  // back to the uploaded copy, if there is one
+        v->depth_w = v->depth_owned.bytes ? v->depth_up_w : 0;
+        v->depth_h = v->depth_owned.bytes ? v->depth_up_h : 0;
+    }
+    v->depth_cfg += 1;
+    return GSX_OK;
+}
+
+gsx_status gsx_viewer_upload_depth_buffer(gsx_viewer* v, const float* host, uint32_t width, uint32_t height) {
+    gsx_status st = viewer_bind(v);
+    if (st) return st;
+    if (v->parent) return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_upload_depth_buffer: called on a lane");
+    if (!host || width == 0 || height == 0) return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_upload_depth_buffer: null buffer or empty size");
+    const size_t bytes = 4 * (size_t)width * height;
+    if (v->depth_owned.bytes < bytes) {
+        HIPCHK(gsx::op::StreamSynchronize(v->stream));  // (the snapshot kernel of a frame in flight may still read the old one)
+        HIPCHK(v->depth_owned.ensure(bytes));
+    }
+    HIPCHK(gsx::op::MemcpyAsync(v->depth_owned.p, host, bytes, hipMemcpyHostToDevice, v->stream));
+    HIPCHK(gsx::op::StreamSynchronize(v->stream));
+    v->depth_dev = nullptr;
+    v->depth_pitch = 0;
+    v->depth_w = v->depth_up_w = width;
+    v->depth_h = v->depth_up_h = height;
+    v->depth_cfg += 1;
+    return GSX_OK;
+}
+
 gsx_status gsx_resolve_rgba8_device(gsx_viewer* v, const float bg[3], uint32_t y0, uint32_t y1, void* d_rgba) {
     gsx_status st = viewer_bind(v);
     if (st) return st;
@@ -56,6 +109,7 @@ gsx_status gsx_shard_pack(gsx_viewer* v, const char* key, uint32_t world, const 
                           uint64_t capacity_records, uint64_t* counts) {
     gsx_status st = viewer_bind(v);
     if (st) return st;
+    if ((st = depth_refuses_shard(v, "gsx_shard_pack"))) return st;
     Model* m = find_model(v, key);
     if (!m) return fail(GSX_ERR_NOT_FOUND, "gsx_shard_pack: no model '%s'", key ? key : "(null)");
     if (!m->preprocessed) return fail(GSX_ERR_INVALID_ARG, "gsx_shard_pack: model '%s' has no projection this frame (gsx_preprocess first)", key);
@@ -133,6 +187,7 @@ gsx_status gsx_viewer_set_band(gsx_viewer* v, uint32_t row_lo, uint32_t row_hi) 
 gsx_status gsx_shard_set_windows(gsx_viewer* v, const char* key, const uint32_t* d_tile_window) {
     gsx_status st = viewer_bind(v);
     if (st) return st;
+    if ((st = depth_refuses_shard(v, "gsx_shard_set_windows"))) return st;
     Model* m = find_model(v, key);
     if (!m) return fail(GSX_ERR_NOT_FOUND, "gsx_shard_set_windows: no model '%s'", key ? key : "(null)");
     m->shard_win_set = d_tile_window != nullptr;
@@ -152,6 +207,7 @@ gsx_status gsx_shard_import(gsx_viewer* v, const char* key, const void* d_recv, 
                             uint32_t rank, const uint32_t* d_tile_window) {
     gsx_status st = viewer_bind(v);
     if (st) return st;
+    if ((st = depth_refuses_shard(v, "gsx_shard_import"))) return st;
     Model* m = find_model(v, key);
     if (!m) return fail(GSX_ERR_NOT_FOUND, "gsx_shard_import: no model '%s'", key ? key : "(null)");
     if (!m->preprocessed) return fail(GSX_ERR_INVALID_ARG, "gsx_shard_import: model '%s' has no frame constants (gsx_preprocess first)", key);
@@ -237,6 +293,7 @@ extern "C" {
 gsx_status gsx_render_more(gsx_viewer* v, const char* const* keys, uint32_t n_keys) {
     gsx_status st = viewer_bind(v);
     if (st) return st;
+    if ((st = depth_refuses_shard(v, "gsx_render_more"))) return st;
     return do_render(v, keys, n_keys, true);
 }
 
@@ -368,6 +425,7 @@ extern "C" {
 gsx_status gsx_shard_frame_begin(gsx_viewer* v, const char* key, uint32_t world, uint32_t rank, uint32_t speculate, const uint32_t* d_limit_override) {
     gsx_status st = viewer_bind(v);
     if (st) return st;
+    if ((st = depth_refuses_shard(v, "gsx_shard_frame_begin"))) return st;
     Model* m = find_model(v, key);
     if (!m) return fail(GSX_ERR_NOT_FOUND, "gsx_shard_frame_begin: no model '%s'", key ? key : "(null)");
     if (world == 0 || world > 64 || rank >= world) return fail(GSX_ERR_INVALID_ARG, "gsx_shard_frame_begin: bad world/rank %u/%u", world, rank);
@@ -430,6 +488,7 @@ gsx_status gsx_shard_slot_records(gsx_viewer* v, const char* key, uint32_t world
 }
 
 gsx_status gsx_shard_pack_slots(gsx_viewer* v, const char* key, uint32_t world, uint32_t round, void* d_send, uint32_t slot_records) {
+    if (gsx_status dst = depth_refuses_shard(v, "gsx_shard_pack_slots")) return dst;
     if (world == 0 || world > 64 || slot_records == 0) return fail(GSX_ERR_INVALID_ARG, "gsx_shard_pack_slots: bad argument");
     return shard_pack_slots(v, key, world, round, d_send, uniform_slots(world, slot_records));
 }
@@ -490,6 +549,7 @@ gsx_status gsx_shard_post_counts(gsx_viewer* v, uint32_t world, const void* d_co
 
 gsx_status gsx_shard_import_slots(gsx_viewer* v, const char* key, const void* d_recv, uint32_t world, uint32_t rank, uint32_t round_flags,
                                   uint32_t slot_records) {
+    if (gsx_status dst = depth_refuses_shard(v, "gsx_shard_import_slots")) return dst;
     if (world == 0 || world > 64 || slot_records == 0) return fail(GSX_ERR_INVALID_ARG, "gsx_shard_import_slots: bad argument");
     return shard_import_slots(v, key, d_recv, world, rank, round_flags, uniform_slots(world, slot_records));
 }

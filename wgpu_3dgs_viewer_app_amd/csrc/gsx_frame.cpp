@@ -380,6 +380,54 @@ gsx_status prepare_edits(gsx_viewer* v, Model* m, bool* launched) {
 
 static gsx_status ensure_msd(gsx_viewer* v, Model* m, DevBuf& ws);
 
+// Depth test (gsx_viewer_set_depth_test): this frame's snapshot of the caller's depth buffer — per-pixel limit keys, per-tile windows
+// {0, depth bound} and their [max | min] pyramids (kernels_depth.hip) — taken by the frame's first gsx_preprocess.  The models of one
+// frame share it; it is taken again when anything it was computed from may have changed: the compare or the buffer (depth_cfg), the
+// viewport or P22 / P23 (recorded with it; gsx_update_camera ends it as well), the end of a frame (gsx_render / gsx_render_frame; every
+// gsx_render_frame starts with a fresh one), and a model preprocessed a second time against it (a new frame whose predecessor failed or
+// was never rendered).  Nothing is ever composited against another frame's snapshot.
+static gsx_status depth_snapshot(gsx_viewer* v, const Model* m) {
+    // z_ndc = z_c / w_c < D  <=>  view depth < P23 / (D + P22) needs the third and fourth rows to depend on view z alone
+    const float* P = v->proj;  // column-major: P[col * 4 + row]
+    if (!(P[2] == 0.0f && P[6] == 0.0f && P[3] == 0.0f && P[7] == 0.0f && P[15] == 0.0f && P[11] == -1.0f))
+        return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: the depth test needs a perspective projection (P20 = P21 = P30 = P31 = P33 = 0, "
+                    "P32 = -1, as perspective_rh); this one is not");
+    const float* src = v->depth_dev ? v->depth_dev : v->depth_owned.as<float>();
+    if (!src || !v->depth_w) return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: the depth test is on and no depth buffer was given "
+                                         "(gsx_viewer_upload_depth_buffer / gsx_viewer_set_depth_buffer_device)");
+    if (v->depth_w != v->width || v->depth_h != v->height)
+        return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: the depth buffer is %ux%u, the viewport %ux%u", v->depth_w, v->depth_h, v->width, v->height);
+    if (v->depth_snap && !v->depth_frame_closed && v->depth_snap_cfg == v->depth_cfg && v->depth_snap_w == v->width &&
+        v->depth_snap_h == v->height && v->depth_snap_p22 == P[10] && v->depth_snap_p23 == P[14] && m->depth_snap != v->depth_snap)
+        return GSX_OK;
+    const uint32_t tiles_x = (v->width + GSX_TILE - 1) / GSX_TILE, tiles_y = (v->height + GSX_TILE - 1) / GSX_TILE;
+    HIPCHK(v->depth_lim.ensure(4 * (size_t)v->width * v->height));
+    HIPCHK(v->depth_win.ensure(sizeof(uint2) * (size_t)tiles_x * tiles_y));
+    HIPCHK(launch_depth_limits(v->stream, src, v->depth_dev ? v->depth_pitch : 4ull * v->depth_w, v->width, v->height, P[10], P[14],
+                               v->depth_lim.as<uint32_t>(), v->depth_win.as<uint2>()));
+    v->depth_snap += 1;
+    v->depth_snap_cfg = v->depth_cfg;
+    v->depth_snap_w = v->width;
+    v->depth_snap_h = v->height;
+    v->depth_snap_p22 = P[10];
+    v->depth_snap_p23 = P[14];
+    v->depth_frame_closed = false;
+    return GSX_OK;
+}
+
+// ... and the [max | min] pyramids of its windows, for the frames that are not speculated (built once per snapshot, when one needs them:
+// a speculated frame builds its own from its capped windows)
+static gsx_status depth_pyramid(gsx_viewer* v) {
+    if (v->depth_pyr_snap == v->depth_snap) return GSX_OK;
+    const uint32_t tiles_x = (v->depth_snap_w + GSX_TILE - 1) / GSX_TILE, tiles_y = (v->depth_snap_h + GSX_TILE - 1) / GSX_TILE;
+    const size_t pw = window_pyramid_words(tiles_x, tiles_y);
+    HIPCHK(v->depth_pyr.ensure(8 * pw));
+    HIPCHK(launch_window_pyramid(v->stream, v->depth_win.as<uint2>(), tiles_x, tiles_y, v->depth_pyr.as<uint32_t>(), false, nullptr,
+                                 v->depth_pyr.as<uint32_t>() + pw));
+    v->depth_pyr_snap = v->depth_snap;
+    return GSX_OK;
+}
+
 gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
     frame_consts_setup(v->view, v->proj, v->width, v->height, m->mt, v->size, v->display_mode, v->sh_deg, v->no_sh0,
                        v->params, &m->fc);
@@ -427,7 +475,32 @@ gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
     HIPCHK(m->adm_counts.ensure(4 * (std::max<size_t>(std::max(admit_blocks(m->n), (size_t)(m->n + 255) / 256), 1) + 4)));
     const bool shard_lazy = m->shard_win_set && m->shard_tiles_x == m->fc.tiles_x && m->shard_tiles_y == m->fc.tiles_y;
     if (shard_lazy) m->spec_round1 = false;  // a sharded frame: the windows come from the caller, not from this viewer's last frame
-    if (m->spec_round1) adm.pyramid = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, m->spec_coarse.as<uint32_t>());
+    // depth test: every tile's window ends at its depth bound — on plain frames too: a record hidden on every tile of its rectangle
+    // never enters the depth sort (exact, not speculative: it could not be blended anyway)
+    const bool depth = v->depth_compare == GSX_DEPTH_LESS;
+    if (depth) {
+        if (shard_lazy || m->use_imported) return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess('%s'): sharded frames do not support the depth test", m->key.c_str());
+        st = depth_snapshot(v, m);   // (reads which snapshot this model was preprocessed against last)
+        m->depth_snap = st ? 0 : v->depth_snap;
+        if (st) return st;
+    } else {
+        m->depth_snap = 0;
+    }
+    if (m->spec_round1 && depth) {  // last frame's windows capped by this frame's depth bounds, and their pyramids
+        const uint32_t n_tiles = m->fc.tiles_x * m->fc.tiles_y;
+        const size_t pw = window_pyramid_words(m->fc.tiles_x, m->fc.tiles_y);
+        HIPCHK(m->spec_dwin.ensure(sizeof(uint2) * (size_t)n_tiles));
+        HIPCHK(m->spec_dpyr.ensure(8 * pw));
+        HIPCHK(launch_depth_cap_windows(v->stream, m->spec_win.as<uint2>(), v->depth_win.as<uint2>(), m->spec_dwin.as<uint2>(), n_tiles));
+        HIPCHK(launch_window_pyramid(v->stream, m->spec_dwin.as<uint2>(), m->fc.tiles_x, m->fc.tiles_y, m->spec_dpyr.as<uint32_t>(), false, nullptr,
+                                     m->spec_dpyr.as<uint32_t>() + pw));
+        adm.pyramid = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, m->spec_dpyr.as<uint32_t>());
+    } else if (m->spec_round1) {
+        adm.pyramid = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, m->spec_coarse.as<uint32_t>());
+    } else if (depth) {
+        if ((st = depth_pyramid(v))) return st;
+        adm.pyramid = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, v->depth_pyr.as<uint32_t>());
+    }
     if (shard_lazy) adm.pyramid = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, m->shard_pyr.as<uint32_t>());
     adm.ballots = m->adm_ballots.as<unsigned long long>();
     adm.block_counts = m->adm_counts.as<uint32_t>();
@@ -438,8 +511,9 @@ gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
     // slab shading (gsx_render_options): a progressive frame without windows projects geometry only as well; its depth slabs then shade
     // exactly the records some block of tiles still takes (k_block_bin's list).  Only frames that bin by blocks, slab by slab:
     // a model small enough for ONE slab keeps complete per-tile lists and its full records (gsx_model_download_tile_lists).
+    // (a depth-tested frame has windows: its admission already dropped the hidden records, and it projects the admitted ones in full)
     m->slab_shading = v->options.slab_shading && v->options.progressive && v->bin_mode == 1 && v->bin_fused && !m->spec_round1 && !shard_lazy &&
-                      m->n > v->options.min_slab && m->pod().sh_aos != nullptr;
+                      !depth && m->n > v->options.min_slab && m->pod().sh_aos != nullptr;
     // ... and only while it pays: a scene where next to nothing saturates (translucent) has every visible record taken by some block — then
     // the streaming projection of everything (k_project: 0.67 of HBM peak) beats gathering the same records slab by slab.  Measured, lazily:
     // the last slab-shaded frame's count (Counters::n_shaded_total); tried again every 256th plain frame.
@@ -727,6 +801,14 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
                     "that frame replaced)", m->key.c_str(), m->key.c_str());
     if (m->fc.w_px != v->width || m->fc.h_px != v->height)
         return fail(GSX_ERR_INVALID_ARG, "gsx_render: viewport changed since gsx_preprocess('%s')", m->key.c_str());
+    // depth test: the model's admission was made against a depth snapshot; it must be the one this frame composites with
+    const bool depth = m->depth_snap != 0;
+    if (v->depth_compare == GSX_DEPTH_LESS ? (m->depth_snap != v->depth_snap || v->depth_snap_cfg != v->depth_cfg || v->depth_snap_w != m->fc.w_px ||
+                                              v->depth_snap_h != m->fc.h_px) : depth)
+        return fail(GSX_ERR_INVALID_ARG, "gsx_render: the depth test or its depth buffer changed since gsx_preprocess('%s'); call gsx_preprocess + "
+                    "gsx_sort('%s') again", m->key.c_str(), m->key.c_str());
+    const uint32_t* depth_lim = depth ? v->depth_lim.as<uint32_t>() : nullptr;
+    const uint2* depth_bound = depth ? v->depth_win.as<uint2>() : nullptr;
     const uint32_t n_tiles = m->fc.tiles_x * m->fc.tiles_y;
     const uint32_t row_words = (m->fc.tiles_x + 31) / 32;
     const bool progressive = v->options.progressive != 0;
@@ -788,7 +870,8 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
     const uint32_t row_lo = std::min(m->row_lo, m->fc.tiles_y), row_hi = std::min(m->row_hi, m->fc.tiles_y);
     const uint32_t owned_tiles = (row_hi > row_lo ? row_hi - row_lo : 0) * m->fc.tiles_x;
     const uint2* window = (m->use_imported && m->has_window) ? (m->window_ptr ? m->window_ptr : m->window.as<uint2>()) : nullptr;
-    if (m->spec_round1) window = m->spec_win.as<uint2>();
+    if (m->spec_round1) window = depth ? m->spec_dwin.as<uint2>() : m->spec_win.as<uint2>();
+    else if (depth) window = depth_bound;
     uint32_t* tile_sat = progressive ? done + row_words * m->fc.tiles_y : nullptr;  // [count | bitmap | saturation keys | row work]
     // multi-GPU: what the tiles of every tile row walked, summed — the next frame's bands are balanced by it (gsx_shard_frame.cpp)
     uint32_t* row_work = (progressive && m->use_imported) ? tile_sat + (size_t)n_tiles : nullptr;
@@ -1029,10 +1112,10 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
                                                d_n, m->sorted_idx, m->sk_out.as<uint32_t>(),
                                                (v->tile_profile && slab_index == 0) ? v->tile_prof.as<uint4>() : nullptr,
                                                (order_buf && m->tile_order_valid) ? order_buf + 1 + n_tiles : nullptr,
-                                               order_buf ? order_buf + 1 : nullptr, m->rec().rect8 /* (null for imported records) */));
+                                               order_buf ? order_buf + 1 : nullptr, m->rec().rect8 /* (null for imported records) */, depth_lim));
             } else {
                 HIPCHK(launch_composite(v->stream, m->fc, m->ranges.as<uint2>(), m->tile_list, m->rec(), fb_ptr(v),
-                                        later, done, row_words, done_count, clear_ranges, tile_sat, row_work));
+                                        later, done, row_words, done_count, clear_ranges, tile_sat, row_work, depth_lim));
                 m->ranges_clean = clear_ranges;  // the compositor zeroed every range it consumed
             }
             v->pass_launches[GSX_PASS_COMPOSITE] += 1;
@@ -1040,7 +1123,7 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
             // pair-free, so the frame is complete without a host round trip; otherwise this launch falls through
             if (!blocks)
                 HIPCHK(launch_composite_spill(v->stream, m->fc, dc, j1, d_n, m->sorted_idx, m->sk_out.as<uint32_t>(), m->rec(), fb_ptr(v),
-                                              done, row_words, done_count, tile_sat, row_lo, row_hi, win));
+                                              done, row_words, done_count, tile_sat, row_lo, row_hi, win, depth_lim));
         }
         return GSX_OK;
     };
@@ -1050,7 +1133,11 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
     bool have_min_ends = false;
     if (m->spec_round1) {
         const size_t pw = window_pyramid_words(m->fc.tiles_x, m->fc.tiles_y);
-        min_ends = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, m->spec_coarse.as<uint32_t>() + pw);
+        min_ends = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, (depth ? m->spec_dpyr.as<uint32_t>() : m->spec_coarse.as<uint32_t>()) + pw);
+        have_min_ends = true;
+    } else if (depth) {  // the depth windows start at 0 as well (a speculated frame redone unspeculated may not have built them yet)
+        if ((st = depth_pyramid(v))) return st;
+        min_ends = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, v->depth_pyr.as<uint32_t>() + window_pyramid_words(m->fc.tiles_x, m->fc.tiles_y));
         have_min_ends = true;
     } else if (imported_windows && m->import_min_ends) {  // round 0 of an index-sharded frame: windows [0, limit), pyramid built at frame begin
         min_ends = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, m->import_min_ends);
@@ -1064,7 +1151,7 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
     auto enqueue_next_windows = [&]() -> gsx_status {  // this model's windows for its next frame
         ScopedPass t(v, GSX_PASS_COMPOSITE);
         HIPCHK(launch_spec_next(v->stream, tile_sat, done, done_before, row_words, m->fc.tiles_x, m->fc.tiles_y,
-                                v->options.spec_margin, v->options.spec_radius, m->spec_win.as<uint2>(), row_lo, row_hi));
+                                v->options.spec_margin, v->options.spec_radius, m->spec_win.as<uint2>(), row_lo, row_hi, depth_bound));
         // [max-pyramid of the window ends: admission in k_project | min-pyramid: "every tile takes it" in the binning]
         // (the two as ONE launch — the last workgroup of k_spec_next building the pyramids — was measured, round 4: 20 us against
         //  4.9 + 7.2: the device-scope fence in front of the ticket writes back what the compositor has just left dirty in the L2)
@@ -1117,10 +1204,10 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
             // 260-350 us here) and the repair slab's block table
             HIPCHK(m->spec_coarse2.ensure(4 * window_pyramid_words(m->fc.tiles_x, m->fc.tiles_y)));
             const BlockGrid grid = block_grid(bsx, bsy, m->fc.tiles_x, row_lo, row_hi);
-                HIPCHK(launch_spec_verify(v->stream, m->spec_win.as<uint2>(), done, row_words, m->fc.tiles_x, m->fc.tiles_y,
+                HIPCHK(launch_spec_verify(v->stream, window, done, row_words, m->fc.tiles_x, m->fc.tiles_y,
                                       m->spec_win2.as<uint2>(), m->spec_need.as<uint32_t>(), &dc->spec_need, row_lo, row_hi,
                                       post ? v->h_verdict : nullptr, seq, m->spec_coarse2.as<uint32_t>(), blocks ? &grid : nullptr,
-                                      blocks ? m->block_table.as<uint4>() : nullptr, blocks ? m->ranges.as<uint2>() : nullptr));
+                                      blocks ? m->block_table.as<uint4>() : nullptr, blocks ? m->ranges.as<uint2>() : nullptr, depth_bound));
             if (ask) {
                 // Nothing to repair (most frames): the ~20 launches of the second round would all fall through, at a few
                 // microseconds of stream time each.  So the verdict comes to the host: one pinned word, written by the

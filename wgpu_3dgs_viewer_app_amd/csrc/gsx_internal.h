@@ -657,7 +657,8 @@ hipError_t launch_composite_blocks(hipStream_t s, const FrameConsts& f, const ui
                                    const uint32_t* sorted_keys /* the slab's tail behind stats->slab_cut is composited pair-free by the same launch */,
                                    uint4* tile_prof = nullptr /* development: per tile {start, duration (10 ns ticks), chunks walked | list chunks << 16, takers} */,
                                    const uint32_t* tile_order = nullptr /* the tile workgroup i composites (nullptr: tile i) */,
-                                   uint32_t* tile_cost = nullptr /* += what each tile cost: tile_order_job's input for the model's next frame */, const uint32_t* rect8 = nullptr /* slab shading: the pair-free tail reads rectangles from the packed plane */);
+                                   uint32_t* tile_cost = nullptr /* += what each tile cost: tile_order_job's input for the model's next frame */, const uint32_t* rect8 = nullptr /* slab shading: the pair-free tail reads rectangles from the packed plane */,
+                                   const uint32_t* depth_lim = nullptr /* as launch_composite */);
 
 // Selection / edits / queries (kernels_edit.hip).
 hipError_t launch_edit_prepare(hipStream_t s, uint32_t n, const uint32_t* selection, uint32_t* edited, float4* edit_a,
@@ -709,13 +710,23 @@ hipError_t launch_admit(hipStream_t s, const Records& rec, uint32_t n, const uin
 hipError_t launch_spec_verify(hipStream_t s, const uint2* win1, const uint32_t* done, uint32_t row_words, uint32_t tiles_x,
                               uint32_t tiles_y, uint2* win2, uint32_t* need_bits, uint32_t* d_need, uint32_t band_lo, uint32_t band_hi,
                               unsigned long long* host_verdict /* pinned host word or null */, uint32_t seq, uint32_t* pyr2_data,
-                              const BlockGrid* grid, uint4* table, uint2* ranges);
+                              const BlockGrid* grid, uint4* table, uint2* ranges,
+                              const uint2* depth_bound = nullptr /* depth test: per tile {0, bound}; a window ending at its bound is complete, the repair
+                                                                    window is [hi, bound) */);
 hipError_t launch_zero_words(hipStream_t s, uint32_t* a, uint32_t na, uint32_t* b, uint32_t nb);
 hipError_t launch_validate_tiles(hipStream_t s, const uint2* ranges, uint32_t n_tiles, const uint32_t* list, const uint32_t* d_entries,
                                  uint32_t capacity, uint32_t n_records, uint32_t* report);
 hipError_t launch_spec_next(hipStream_t s, const uint32_t* tile_sat, const uint32_t* done, const uint32_t* done_before,
                             uint32_t row_words, uint32_t tiles_x, uint32_t tiles_y, float margin, uint32_t radius, uint2* win_next,
-                            uint32_t band_lo, uint32_t band_hi);
+                            uint32_t band_lo, uint32_t band_hi,
+                            const uint2* depth_bound = nullptr /* depth test: an open tile with a finite bound counts as closed at that bound */);
+
+// Depth test against the caller's depth buffer (kernels_depth.hip).  lim: u32 per pixel, row-major [h][w] — the depth key at and behind
+// which a splat is hidden there (0: everything, 0xFFFFFFFF: nothing); window: per tile {0, max of its pixels' limits}.
+hipError_t launch_depth_limits(hipStream_t s, const float* depth, uint64_t pitch_bytes, uint32_t w, uint32_t h, float p22, float p23,
+                               uint32_t* lim, uint2* window);
+// out[t] = {spec[t].x, min(spec[t].y, bound[t].y)}
+hipError_t launch_depth_cap_windows(hipStream_t s, const uint2* spec, const uint2* bound, uint2* out, uint32_t n_tiles);
 
 // Multi-GPU exchange support (kernels_shard.hip).
 // d_n (nullable) / tile: only the first ceil(*d_n / tile) columns of every row hold anything (a candidate list shorter than the grid)
@@ -811,14 +822,16 @@ void quat_to_rows(const float q[4], float r[9]);
 // depth feedback (nullable): when a tile saturates, *depth_needed = max(., sorted_keys[min(slab_end, *d_n_vis) - 1])
 hipError_t launch_composite(hipStream_t s, const FrameConsts& f, uint2* ranges, const uint32_t* list,
                             const Records& rec, float4* fb, bool carry, uint32_t* done, uint32_t row_words,
-                            uint32_t* d_done_count, bool clear_ranges, uint32_t* tile_sat, uint32_t* row_work = nullptr /* per tile row: += list entries walked */);
+                            uint32_t* d_done_count, bool clear_ranges, uint32_t* tile_sat, uint32_t* row_work = nullptr /* per tile row: += list entries walked */,
+                            const uint32_t* depth_lim = nullptr /* depth test: per-pixel limit keys (launch_depth_limits); a pixel closes at its first
+                                                                   record whose key is >= its limit.  Closed by depth is not saturated: no done bit */);
 // The splats [stats->slab_cut, min(j1, *d_n)) of the depth order, composited WITHOUT tile pairs (an overflowing slab's tail):
 // one workgroup per live tile scans them, keeps those whose rectangle (and window) takes the tile, blends them like
 // k_composite.  Falls through when the slab was not cut.
 hipError_t launch_composite_spill(hipStream_t s, const FrameConsts& f, const SlabStats* stats, uint32_t j1, const uint32_t* d_n,
                                   const uint32_t* sorted_idx, const uint32_t* sorted_keys, const Records& rec, float4* fb,
                                   uint32_t* done, uint32_t row_words, uint32_t* d_done_count, uint32_t* tile_sat, uint32_t row_lo,
-                                  uint32_t row_hi, const uint2* window);
+                                  uint32_t row_hi, const uint2* window, const uint32_t* depth_lim = nullptr /* as launch_composite */);
 hipError_t launch_clear_fb(hipStream_t s, float4* fb, uint32_t n_px);
 hipError_t launch_resolve_rgba8(hipStream_t s, const float4* fb, uint32_t n_px, float bg_r, float bg_g, float bg_b,
                                 uint32_t* out_rgba8);

@@ -619,6 +619,7 @@ gsx_status gsx_shard_render_frame_keys(gsx_viewer* v, const char* const* keys_fa
     if (!v || !keys_far_to_near || !shard_records_max || n_keys == 0 || n_keys > 1024)
         return fail(GSX_ERR_INVALID_ARG, "gsx_shard_render_frame_keys: null argument or no keys");
     if (v->parent) return fail(GSX_ERR_INVALID_ARG, "gsx_shard_render_frame_keys: called on a lane");
+    if (gsx_status dst = depth_refuses_shard(v, "gsx_shard_render_frame")) return dst;
     HIPCHK(hipSetDevice(v->device));
     if (!has_comm(v)) return fail(GSX_ERR_RCCL, "gsx_shard_render_frame: no communicator (gsx_viewer_comm_init / _init_group / _init_custom)");
     for (uint32_t i = 0; i < n_keys; ++i) {

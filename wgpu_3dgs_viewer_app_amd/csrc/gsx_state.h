@@ -174,6 +174,10 @@ struct Model {
     // windows of the current one, the saturated-tile bitmap as it was before this model was composited
     DevBuf spec_win, spec_win2, spec_done_before, spec_need, spec_coarse, spec_coarse2;
     bool spec_valid = false, spec_round1 = false;
+    // depth test (gsx_viewer_set_depth_test): the viewer's depth snapshot this model was preprocessed against (0: none, the test was
+    // off), and a speculated frame's windows capped by the depth bounds with their [max | min] pyramids
+    uint64_t depth_snap = 0;
+    DevBuf spec_dwin, spec_dpyr;
     // speculation that keeps repairing does not pay (sparse scenes whose tiles hover around saturation): the lazily read
     // statistics keep a history of "this frame needed the repair round"; too many -> unspeculated frames for a while
     uint64_t mask_program_hash = 0;    // of the last gsx_mask_evaluate program (0: none / uploaded words)
@@ -441,6 +445,19 @@ struct gsx_viewer {
     DevBuf shard_fb, shard_send, shard_recv, shard_sat_band, shard_sat_all, shard_counts;  // gsx_shard_render_frame's own buffers
     void* ext_fb = nullptr;              // caller-owned framebuffer (multi-GPU: the RCCL gather target)
     uint64_t ext_fb_bytes = 0;
+    // depth test against the caller's depth buffer (gsx_viewer_set_depth_test, kernels_depth.hip).  The buffer: caller-owned device
+    // memory (depth_dev) or the viewer's copy of an upload (depth_owned).  depth_cfg counts changes of the compare or the buffer; a
+    // snapshot (per-pixel limits, per-tile windows {0, bound}, their [max | min] pyramids) is taken by the first gsx_preprocess of a
+    // frame and belongs to that frame until gsx_render / gsx_render_frame ends it
+    uint32_t depth_compare = GSX_DEPTH_ALWAYS;
+    const float* depth_dev = nullptr;
+    uint64_t depth_pitch = 0;
+    uint32_t depth_w = 0, depth_h = 0, depth_up_w = 0, depth_up_h = 0;
+    DevBuf depth_owned, depth_lim, depth_win, depth_pyr;
+    uint64_t depth_cfg = 1, depth_snap = 0, depth_snap_cfg = 0, depth_pyr_snap = 0;
+    bool depth_frame_closed = true;
+    uint32_t depth_snap_w = 0, depth_snap_h = 0;  // what the snapshot was computed from (depth_snapshot retakes it when they change)
+    float depth_snap_p22 = 0.0f, depth_snap_p23 = 0.0f;
     gsx_render_options options{1u, 16u, 131072u, 2u, 1u, 0.25f, 3u, 0u, 1u, 1u};  // = gsx_render_options_default (a CPU test compares the two: gsx_viewer_get_render_options)
     bool host_waited = false;  // the host has waited for this viewer's device work (gsx_sync, a blocking readback) since its last frame was enqueued:
                                // the app synchronises per frame, so asking for a speculated frame's verdict costs it nothing (host_verify = 2)
@@ -573,6 +590,12 @@ inline gsx_status ensure_fb(gsx_viewer* v) {
 }
 // readback entry points refer to the newest frame, whichever lane rendered it
 inline gsx_viewer* result_lane(gsx_viewer* v) { return v->latest ? v->latest : v; }
+// the depth test is not part of the sharded (multi-GPU) frames yet: every entry point of theirs refuses while it is on
+inline gsx_status depth_refuses_shard(const gsx_viewer* v, const char* fn) {
+    if (v && v->depth_compare != GSX_DEPTH_ALWAYS)
+        return fail(GSX_ERR_INVALID_ARG, "%s: sharded frames do not support the depth test (gsx_viewer_set_depth_test(v, GSX_DEPTH_ALWAYS) first)", fn);
+    return GSX_OK;
+}
 inline float4* fb_ptr(gsx_viewer* v) { return v->ext_fb ? static_cast<float4*>(v->ext_fb) : reinterpret_cast<float4*>(v->fb.p); }
 
 // lane `index` (0 = the viewer itself) brought up to date for a frame of `keys` (gsx_api.cpp)

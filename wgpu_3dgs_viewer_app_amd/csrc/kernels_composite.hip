@@ -37,19 +37,25 @@ __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elem
 // Measured on cfg4 (a counting build, round 4): 60 % of the (record, wave) evaluations hit a pixel — the rest leave after the ten
 // instructions of q and the two compares — and a hit covers 65 % of the wave's 128 pixels; ~144 evaluations and ~87 hits per wave
 // and tile, 80 % of the kernel's vector instructions.
-template <int MODE, int kGroup, bool CLAMP>
+// DEPTH (depth test, kernels_depth.hip): dl0 / dl1 are the pixels' limit keys; records arrive in ascending key order, so a pixel closes
+// (lim = 0) at its first record whose key (s_rgb[j].w) is >= its limit — one compare more per (record, pixel).  DEPTH = false compiles
+// to the loop without it.
+template <int MODE, int kGroup, bool CLAMP, bool DEPTH = false>
 __device__ __forceinline__ void blend_batch(const FrameConsts& f, const uint32_t cnt, const float2* s_mean, const float4* s_conic,
                                             const float4* s_rgb, const float pxf, const v2f pyf, uint32_t& lim0, uint32_t& lim1,
-                                            v2f& T, v2f& C0, v2f& C1, v2f& C2, uint32_t& stop_key) {
+                                            v2f& T, v2f& C0, v2f& C1, v2f& C2, uint32_t& stop_key, const uint32_t dl0 = 0u,
+                                            const uint32_t dl1 = 0u) {
     for (uint32_t j0 = 0; j0 < cnt; j0 += kGroup) {
         if (!__ballot((lim0 | lim1) != 0u)) break;
         // the group's records first, so the LDS round trips overlap instead of each splat waiting for its own
         float2 gm[kGroup];
         float4 gc[kGroup];
+        uint32_t gk[kGroup];
 #pragma unroll
         for (uint32_t u = 0; u < kGroup; ++u) {
             gm[u] = s_mean[j0 + u];
             gc[u] = s_conic[j0 + u];
+            if (DEPTH) gk[u] = __float_as_uint(s_rgb[j0 + u].w);
         }
 #pragma unroll
         for (uint32_t u = 0; u < kGroup; ++u) {
@@ -60,6 +66,10 @@ __device__ __forceinline__ void blend_batch(const FrameConsts& f, const uint32_t
             const v2f dy = pyf - splat2(m.y);
             // q = fma(a*dx, dx, fma(c*dy, dy, ((2b)*dx)*dy))
             const v2f q = fma2(splat2(co.x * dx), splat2(dx), fma2(splat2(co.z) * dy, dy, splat2(co.y * dx) * dy));
+            if (DEPTH) {
+                lim0 = gk[u] >= dl0 ? 0u : lim0;
+                lim1 = gk[u] >= dl1 ? 0u : lim1;
+            }
             const bool h0 = __float_as_uint(q.x) < lim0, h1 = __float_as_uint(q.y) < lim1;
             if (h0 || h1) {
                 v2f alpha;
@@ -95,6 +105,15 @@ __device__ __forceinline__ void blend_batch(const FrameConsts& f, const uint32_t
     }
 }
 
+// Both pixels of this lane are done for the tile's done bit: outside the image or T < t_epsilon.  Without the depth test that is
+// lim == 0 (only those two close a pixel); with it a pixel closed by its depth limit is NOT saturated — a model composited later (behind,
+// in the far -> near list) may still cover it, and the done bits carry from model to model — so the bit follows T alone.
+template <bool DEPTH>
+__device__ __forceinline__ bool lane_saturated(const FrameConsts& f, bool in0, bool in1, v2f T, uint32_t lim0, uint32_t lim1) {
+    if (DEPTH) return !((in0 && !(T.x < f.t_eps)) || (in1 && !(T.y < f.t_eps)));
+    return (lim0 | lim1) == 0u;
+}
+
 // One 128-lane workgroup (two waves) per 16x16 tile; every lane owns the two vertically adjacent pixels
 // (x, 2r) and (x, 2r+1), so wave w covers rows 8w..8w+7.  Two pixels per lane because the loop is bound by VALU
 // issue and by the LDS return path (every splat record is broadcast to all lanes): gfx950's packed fp32
@@ -102,7 +121,7 @@ __device__ __forceinline__ void blend_batch(const FrameConsts& f, const uint32_t
 // and each LDS broadcast now feeds two pixels.  Per pixel the operation sequence is exactly the oracle's (spec §6;
 // packed ops round like their scalar forms), a pixel that is not hit takes alpha = 0, which leaves (C, T) unchanged
 // bit for bit for finite colour records.
-template <int MODE /* 0 splat (gaussian falloff), 1 constant alpha inside the cutoff */, bool CLAMP /* blend_batch */>
+template <int MODE /* 0 splat (gaussian falloff), 1 constant alpha inside the cutoff */, bool CLAMP /* blend_batch */, bool DEPTH = false>
 __global__ __launch_bounds__(128) void k_composite(const FrameConsts f, uint2* __restrict__ ranges,
                                                     const uint32_t* __restrict__ list,
                                                     const float4* __restrict__ rec_a, const float4* __restrict__ rec_b,
@@ -110,7 +129,7 @@ __global__ __launch_bounds__(128) void k_composite(const FrameConsts f, uint2* _
                                                     const int carry, uint32_t* __restrict__ done_bits,
                                                     const uint32_t row_words, uint32_t* __restrict__ done_count,
                                                     const int clear_ranges, uint32_t* __restrict__ tile_sat,
-                                                    uint32_t* __restrict__ row_work) {
+                                                    uint32_t* __restrict__ row_work, const uint32_t* __restrict__ depth_lim) {
     __shared__ float2 s_mean[kBatch];
     __shared__ uint32_t s_sat;
     __shared__ float4 s_conic[kBatch];  // (a, 2b, c, opacity)
@@ -155,6 +174,11 @@ __global__ __launch_bounds__(128) void k_composite(const FrameConsts f, uint2* _
     // predicate logic off the scalar unit, which was busier than the vector ALU in this loop (110 M vs 77 M instructions).
     const uint32_t live = f.k2 > 0.0f ? __float_as_uint(f.k2) + 1u : (f.k2 == 0.0f ? 1u : 0u);
     uint32_t lim0 = (in0 && !(T.x < f.t_eps)) ? live : 0u, lim1 = (in1 && !(T.y < f.t_eps)) ? live : 0u;
+    uint32_t dl0 = 0u, dl1 = 0u;  // DEPTH: the pixels' limit keys
+    if (DEPTH) {
+        dl0 = in0 ? depth_lim[fbo] : 0u;
+        dl1 = in1 ? depth_lim[fbo + f.w_px] : 0u;
+    }
     uint32_t stop_key = 0;  // depth key of this lane's last hit: once both its pixels are saturated, the key of the splat
                             // that saturated the later one (keys ascend along the list)
     if (tid == 0) s_sat = 0;
@@ -201,7 +225,7 @@ __global__ __launch_bounds__(128) void k_composite(const FrameConsts f, uint2* _
             }
         }
         const uint32_t cnt = min((uint32_t)kBatch, range.y - base);
-        blend_batch<MODE, kGroupTiles, CLAMP>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key);
+        blend_batch<MODE, kGroupTiles, CLAMP, DEPTH>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key, dl0, dl1);
     }
     if (in0) fb[fbo] = make_float4(C0.x, C1.x, C2.x, T.x);
     if (in1) fb[fbo + f.w_px] = make_float4(C0.y, C1.y, C2.y, T.y);
@@ -209,7 +233,7 @@ __global__ __launch_bounds__(128) void k_composite(const FrameConsts f, uint2* _
     // multi-GPU: what this tile cost (tile_work, gsx_internal.h: here every entry walked is blended); the next frame's bands are
     // balanced by the rows' sums (gsx_shard_frame.cpp, k_shard_verify)
     if (row_work && tid == 0) atomicAdd(&row_work[ty], tile_work(min(base, range.y) - range.x, min(base, range.y) - range.x, range.y - range.x, 1u));
-    if (done_bits && __syncthreads_and((lim0 | lim1) == 0u)) {
+    if (done_bits && __syncthreads_and(lane_saturated<DEPTH>(f, in0, in1, T, lim0, lim1))) {
         // the tile saturated in this launch: its last pixels stopped here, behind everything blended earlier
         if (tile_sat) {
             if (stop_key) atomicMax(&s_sat, stop_key);
@@ -238,7 +262,7 @@ __device__ __forceinline__ uint32_t tile_cost_units(uint32_t chunks, uint32_t ta
 constexpr int kCand = 1;                         // candidates per lane and iteration (1 / 2 / 3 measured alike, round 2)
 constexpr uint32_t kChunk = 128u * kCand;
 
-template <int MODE, bool CLAMP, bool SORTED /* brec is in list order (below) */>
+template <int MODE, bool CLAMP, bool SORTED /* brec is in list order (below) */, bool DEPTH = false>
 __global__ __launch_bounds__(128) void k_composite_blocks(const FrameConsts f, const uint2* __restrict__ ranges,
                                                            const uint32_t* __restrict__ list, const uint4* __restrict__ brec,
                                                            const float4* __restrict__ rec_a, const float4* __restrict__ rec_b,
@@ -252,7 +276,8 @@ __global__ __launch_bounds__(128) void k_composite_blocks(const FrameConsts f, c
                                                            const uint32_t* __restrict__ d_n, const uint32_t* __restrict__ sorted_idx,
                                                            const uint32_t* __restrict__ sorted_keys, uint4* __restrict__ tile_prof,
                                                            const uint32_t* __restrict__ tile_order, uint32_t* __restrict__ tile_cost,
-                                                           const uint32_t* __restrict__ rect8 /* slab shading: rectangles of records nobody shaded */) {
+                                                           const uint32_t* __restrict__ rect8 /* slab shading: rectangles of records nobody shaded */,
+                                                           const uint32_t* __restrict__ depth_lim) {
     const unsigned long long t_start = tile_prof ? wall_clock64() : 0ull;  // (development: gsx_debug_tile_profile)
     __shared__ float2 s_mean[kChunk + kGroupBlocks];
     __shared__ float4 s_conic[kChunk + kGroupBlocks];
@@ -303,6 +328,11 @@ __global__ __launch_bounds__(128) void k_composite_blocks(const FrameConsts f, c
     }
     const uint32_t live = f.k2 > 0.0f ? __float_as_uint(f.k2) + 1u : (f.k2 == 0.0f ? 1u : 0u);
     uint32_t lim0 = (in0 && !(T.x < f.t_eps)) ? live : 0u, lim1 = (in1 && !(T.y < f.t_eps)) ? live : 0u;
+    uint32_t dl0 = 0u, dl1 = 0u;  // DEPTH: the pixels' limit keys
+    if (DEPTH) {
+        dl0 = in0 ? depth_lim[fbo] : 0u;
+        dl1 = in1 ? depth_lim[fbo + f.w_px] : 0u;
+    }
     uint32_t stop_key = 0;
     if (tid == 0) s_sat = 0;
 
@@ -400,7 +430,7 @@ __global__ __launch_bounds__(128) void k_composite_blocks(const FrameConsts f, c
             }
         }
         taken += cnt;
-        if (cnt) blend_batch<MODE, kGroupBlocks, CLAMP>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key);
+        if (cnt) blend_batch<MODE, kGroupBlocks, CLAMP, DEPTH>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key, dl0, dl1);
     }
     if (spill) {
         for (uint32_t sb = spill_cut; sb < spill_end; sb += 128u) {
@@ -437,7 +467,7 @@ __global__ __launch_bounds__(128) void k_composite_blocks(const FrameConsts f, c
                 s_rgb[cnt + tid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
             __syncthreads();
-            if (cnt) blend_batch<MODE, kGroupBlocks, CLAMP>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key);
+            if (cnt) blend_batch<MODE, kGroupBlocks, CLAMP, DEPTH>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key, dl0, dl1);
         }
     }
     if (in0) fb[fbo] = make_float4(C0.x, C1.x, C2.x, T.x);
@@ -448,7 +478,7 @@ __global__ __launch_bounds__(128) void k_composite_blocks(const FrameConsts f, c
     if (tile_prof && tid == 0)  // {start, duration in 10 ns ticks, list entries walked | list length << 16 (in chunks), takers blended}
         tile_prof[tile] = make_uint4((uint32_t)t_start, (uint32_t)(wall_clock64() - t_start),
                                      ((min(base, range.y) - range.x + kChunk - 1u) / kChunk) | (((range.y - range.x + kChunk - 1u) / kChunk) << 16), taken);
-    if (done_bits && __syncthreads_and((lim0 | lim1) == 0u)) {
+    if (done_bits && __syncthreads_and(lane_saturated<DEPTH>(f, in0, in1, T, lim0, lim1))) {
         if (tile_sat) {
             if (stop_key) atomicMax(&s_sat, stop_key);
             __syncthreads();
@@ -467,7 +497,7 @@ __global__ __launch_bounds__(128) void k_composite_blocks(const FrameConsts f, c
 // with the compositor's own code: the per-pixel operation sequence is that of a frame with larger buffers, so the pixels are
 // the same.  O(tiles x tail) rectangle tests: a rare path that trades speed for never delivering an incomplete frame; the
 // host grows the buffers as soon as it learns of the overflow.  A slab that was not cut: two loads, then return.
-template <int MODE, bool CLAMP>
+template <int MODE, bool CLAMP, bool DEPTH = false>
 __global__ __launch_bounds__(128) void k_composite_spill(const FrameConsts f, const SlabStats* __restrict__ stats, const uint32_t j1,
                                                           const uint32_t* __restrict__ d_n, const uint32_t* __restrict__ sorted_idx,
                                                           const uint32_t* __restrict__ sorted_keys, const float4* __restrict__ rec_a,
@@ -475,7 +505,7 @@ __global__ __launch_bounds__(128) void k_composite_spill(const FrameConsts f, co
                                                           float4* __restrict__ fb, uint32_t* __restrict__ done_bits,
                                                           const uint32_t row_words, uint32_t* __restrict__ done_count,
                                                           uint32_t* __restrict__ tile_sat, const uint32_t row_lo, const uint32_t row_hi,
-                                                          const uint2* __restrict__ window) {
+                                                          const uint2* __restrict__ window, const uint32_t* __restrict__ depth_lim) {
     const uint32_t end = min(j1, *d_n), cut = stats->slab_cut;
     if (cut >= end) return;
     __shared__ float2 s_mean[128 + kGroupTiles];
@@ -507,6 +537,11 @@ __global__ __launch_bounds__(128) void k_composite_spill(const FrameConsts f, co
     }
     const uint32_t live = f.k2 > 0.0f ? __float_as_uint(f.k2) + 1u : (f.k2 == 0.0f ? 1u : 0u);
     uint32_t lim0 = (in0 && !(T.x < f.t_eps)) ? live : 0u, lim1 = (in1 && !(T.y < f.t_eps)) ? live : 0u;
+    uint32_t dl0 = 0u, dl1 = 0u;  // DEPTH: the pixels' limit keys
+    if (DEPTH) {
+        dl0 = in0 ? depth_lim[fbo] : 0u;
+        dl1 = in1 ? depth_lim[fbo + f.w_px] : 0u;
+    }
     uint32_t stop_key = 0;
     if (tid == 0) s_sat = 0;
     for (uint32_t base = cut; base < end; base += 128u) {
@@ -542,11 +577,11 @@ __global__ __launch_bounds__(128) void k_composite_spill(const FrameConsts f, co
             s_rgb[cnt + tid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
         __syncthreads();
-        blend_batch<MODE, kGroupTiles, CLAMP>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key);
+        blend_batch<MODE, kGroupTiles, CLAMP, DEPTH>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key, dl0, dl1);
     }
     if (in0) fb[fbo] = make_float4(C0.x, C1.x, C2.x, T.x);
     if (in1) fb[fbo + f.w_px] = make_float4(C0.y, C1.y, C2.y, T.y);
-    if (done_bits && __syncthreads_and((lim0 | lim1) == 0u)) {
+    if (done_bits && __syncthreads_and(lane_saturated<DEPTH>(f, in0, in1, T, lim0, lim1))) {
         if (tile_sat) {
             if (stop_key) atomicMax(&s_sat, stop_key);
             __syncthreads();
@@ -582,20 +617,20 @@ __global__ __launch_bounds__(256) void k_resolve_rgba8(const float4* __restrict_
 
 hipError_t launch_composite(hipStream_t s, const FrameConsts& f, uint2* ranges, const uint32_t* list,
                             const Records& rec, float4* fb, bool carry, uint32_t* done, uint32_t row_words,
-                            uint32_t* d_done_count, bool clear_ranges, uint32_t* tile_sat, uint32_t* row_work) {
+                            uint32_t* d_done_count, bool clear_ranges, uint32_t* tile_sat, uint32_t* row_work, const uint32_t* depth_lim) {
     dim3 grid(f.tiles_x * f.tiles_y), block(128);
     const bool clamp = f.alpha_max < 1.0f || f.alpha_min > 0.0f;  // (blend_batch: the default constants need no clamping)
-    if (f.display_mode == GSX_DISPLAY_SPLAT) {
-        if (clamp) GSX_LAUNCH((k_composite<0, true>), grid, block, 0, s, f, ranges, list, rec.a, rec.b, rec.c, fb, carry ? 1 : 0, done, row_words, d_done_count,
-                           clear_ranges ? 1 : 0, tile_sat, row_work);
-        else GSX_LAUNCH((k_composite<0, false>), grid, block, 0, s, f, ranges, list, rec.a, rec.b, rec.c, fb, carry ? 1 : 0, done, row_words, d_done_count,
-                           clear_ranges ? 1 : 0, tile_sat, row_work);
+#define GSX_C(M, C, D)                                                                                                              \
+    GSX_LAUNCH((k_composite<M, C, D>), grid, block, 0, s, f, ranges, list, rec.a, rec.b, rec.c, fb, carry ? 1 : 0, done, row_words, d_done_count, \
+               clear_ranges ? 1 : 0, tile_sat, row_work, depth_lim)
+    if (depth_lim) {
+        if (f.display_mode == GSX_DISPLAY_SPLAT) { if (clamp) GSX_C(0, true, true); else GSX_C(0, false, true); }
+        else { if (clamp) GSX_C(1, true, true); else GSX_C(1, false, true); }
     } else {
-        if (clamp) GSX_LAUNCH((k_composite<1, true>), grid, block, 0, s, f, ranges, list, rec.a, rec.b, rec.c, fb, carry ? 1 : 0, done, row_words, d_done_count,
-                           clear_ranges ? 1 : 0, tile_sat, row_work);
-        else GSX_LAUNCH((k_composite<1, false>), grid, block, 0, s, f, ranges, list, rec.a, rec.b, rec.c, fb, carry ? 1 : 0, done, row_words, d_done_count,
-                           clear_ranges ? 1 : 0, tile_sat, row_work);
+        if (f.display_mode == GSX_DISPLAY_SPLAT) { if (clamp) GSX_C(0, true, false); else GSX_C(0, false, false); }
+        else { if (clamp) GSX_C(1, true, false); else GSX_C(1, false, false); }
     }
+#undef GSX_C
     return hipGetLastError();
 }
 
@@ -604,22 +639,26 @@ hipError_t launch_composite_blocks(hipStream_t s, const FrameConsts& f, const ui
                                    uint32_t* d_done_count, uint32_t* tile_sat, const uint2* window, uint32_t row_lo,
                                    uint32_t row_hi, uint32_t bsx, uint32_t bsy, uint32_t* row_work, const SlabStats* stats, uint32_t j1,
                                    const uint32_t* d_n, const uint32_t* sorted_idx, const uint32_t* sorted_keys, uint4* tile_prof,
-                                   const uint32_t* tile_order, uint32_t* tile_cost, const uint32_t* rect8) {
+                                   const uint32_t* tile_order, uint32_t* tile_cost, const uint32_t* rect8, const uint32_t* depth_lim) {
     dim3 grid(f.tiles_x * f.tiles_y), block(128);
     const uint32_t blocks_x = (f.tiles_x + (1u << bsx) - 1u) >> bsx;
     const bool clamp = f.alpha_max < 1.0f || f.alpha_min > 0.0f;  // (blend_batch: the default constants need no clamping)
     const bool sorted = list == nullptr;                          // brec in list order (the block sort gathered it)
-#define GSX_CB(M, C, S)                                                                                                              \
-    GSX_LAUNCH((k_composite_blocks<M, C, S>), grid, block, 0, s, f, ranges, list, brec, rec.a, rec.b, rec.c, fb, carry ? 1 : 0, done, row_words, \
+#define GSX_CB(M, C, S, D)                                                                                                           \
+    GSX_LAUNCH((k_composite_blocks<M, C, S, D>), grid, block, 0, s, f, ranges, list, brec, rec.a, rec.b, rec.c, fb, carry ? 1 : 0, done, row_words, \
                d_done_count, tile_sat, window, row_lo, row_hi, bsx, bsy, blocks_x, row_work, stats, j1, d_n, sorted_idx, sorted_keys, tile_prof,    \
-               tile_order, tile_cost, rect8)
-    if (f.display_mode == GSX_DISPLAY_SPLAT) {
-        if (clamp) { if (sorted) GSX_CB(0, true, true); else GSX_CB(0, true, false); }
-        else { if (sorted) GSX_CB(0, false, true); else GSX_CB(0, false, false); }
-    } else {
-        if (clamp) { if (sorted) GSX_CB(1, true, true); else GSX_CB(1, true, false); }
-        else { if (sorted) GSX_CB(1, false, true); else GSX_CB(1, false, false); }
+               tile_order, tile_cost, rect8, depth_lim)
+#define GSX_CB_MODE(D)                                                                                                               \
+    if (f.display_mode == GSX_DISPLAY_SPLAT) {                                                                                       \
+        if (clamp) { if (sorted) GSX_CB(0, true, true, D); else GSX_CB(0, true, false, D); }                                         \
+        else { if (sorted) GSX_CB(0, false, true, D); else GSX_CB(0, false, false, D); }                                             \
+    } else {                                                                                                                         \
+        if (clamp) { if (sorted) GSX_CB(1, true, true, D); else GSX_CB(1, true, false, D); }                                         \
+        else { if (sorted) GSX_CB(1, false, true, D); else GSX_CB(1, false, false, D); }                                             \
     }
+    if (depth_lim) { GSX_CB_MODE(true) }
+    else { GSX_CB_MODE(false) }
+#undef GSX_CB_MODE
 #undef GSX_CB
     return hipGetLastError();
 }
@@ -627,20 +666,20 @@ hipError_t launch_composite_blocks(hipStream_t s, const FrameConsts& f, const ui
 hipError_t launch_composite_spill(hipStream_t s, const FrameConsts& f, const SlabStats* stats, uint32_t j1, const uint32_t* d_n,
                                   const uint32_t* sorted_idx, const uint32_t* sorted_keys, const Records& rec, float4* fb,
                                   uint32_t* done, uint32_t row_words, uint32_t* d_done_count, uint32_t* tile_sat, uint32_t row_lo,
-                                  uint32_t row_hi, const uint2* window) {
+                                  uint32_t row_hi, const uint2* window, const uint32_t* depth_lim) {
     dim3 grid(std::min<uint32_t>(f.tiles_x * f.tiles_y, 2048u)), block(128);
     const bool clamp = f.alpha_max < 1.0f || f.alpha_min > 0.0f;  // (blend_batch: the default constants need no clamping)
-    if (f.display_mode == GSX_DISPLAY_SPLAT) {
-        if (clamp) GSX_LAUNCH((k_composite_spill<0, true>), grid, block, 0, s, f, stats, j1, d_n, sorted_idx, sorted_keys, rec.a, rec.b, rec.c, fb, done,
-                           row_words, d_done_count, tile_sat, row_lo, row_hi, window);
-        else GSX_LAUNCH((k_composite_spill<0, false>), grid, block, 0, s, f, stats, j1, d_n, sorted_idx, sorted_keys, rec.a, rec.b, rec.c, fb, done,
-                           row_words, d_done_count, tile_sat, row_lo, row_hi, window);
+#define GSX_CS(M, C, D)                                                                                                              \
+    GSX_LAUNCH((k_composite_spill<M, C, D>), grid, block, 0, s, f, stats, j1, d_n, sorted_idx, sorted_keys, rec.a, rec.b, rec.c, fb, done, \
+               row_words, d_done_count, tile_sat, row_lo, row_hi, window, depth_lim)
+    if (depth_lim) {
+        if (f.display_mode == GSX_DISPLAY_SPLAT) { if (clamp) GSX_CS(0, true, true); else GSX_CS(0, false, true); }
+        else { if (clamp) GSX_CS(1, true, true); else GSX_CS(1, false, true); }
     } else {
-        if (clamp) GSX_LAUNCH((k_composite_spill<1, true>), grid, block, 0, s, f, stats, j1, d_n, sorted_idx, sorted_keys, rec.a, rec.b, rec.c, fb, done,
-                           row_words, d_done_count, tile_sat, row_lo, row_hi, window);
-        else GSX_LAUNCH((k_composite_spill<1, false>), grid, block, 0, s, f, stats, j1, d_n, sorted_idx, sorted_keys, rec.a, rec.b, rec.c, fb, done,
-                           row_words, d_done_count, tile_sat, row_lo, row_hi, window);
+        if (f.display_mode == GSX_DISPLAY_SPLAT) { if (clamp) GSX_CS(0, true, false); else GSX_CS(0, false, false); }
+        else { if (clamp) GSX_CS(1, true, false); else GSX_CS(1, false, false); }
     }
+#undef GSX_CS
     return hipGetLastError();
 }
 

@@ -1,0 +1,72 @@
+// kernels_depth.hip — the caller's depth buffer as per-pixel limits and per-tile depth bounds (gfx950).
+//
+// The reference draws its splats with a depth test against what the mask gizmos and the measurement lines wrote before them
+// (MultiModelViewer::new_with(.., Some(DepthStencilState { Depth32Float, depth_write_enabled: false, Less }), ..),
+// src/tab/scene.rs:1969-1980; SceneCallback::paint, scene.rs:2283-2314).  Here the test is made in the depth-key domain
+// (spec §6, "Depth test"): with a projection whose third and fourth rows depend on view z alone (P32 = -1), NDC depth
+// z_ndc = P23 / d - P22 of a splat at view depth d is < D(p) exactly when d < P23 / (D(p) + P22).  So every pixel gets the
+// limit key bits(P23 / (D + P22)) once per frame, and the compositor compares one key per (record, pixel).
+// Per 16x16 tile the maximum of its pixels' limits is the depth bound: no record at or behind it can touch any pixel of the
+// tile, so it caps the tile's window (admission, binning) and such records never enter the depth sort.
+// Bandwidth-trivial: 4 bytes read and 4 written per pixel (8 MB at 1080p), one workgroup per tile.
+#include <algorithm>
+
+#include "gsx_internal.h"
+
+namespace gsx {
+
+constexpr uint32_t kDepthNoLimit = 0xFFFFFFFFu;
+
+// D >= 1 (a cleared buffer): no limit.  D <= 0 or NaN: every splat hidden (`Less` against NaN is false).
+__device__ __forceinline__ uint32_t depth_limit_key(float d, float p22, float p23) {
+    if (!(d > 0.0f)) return 0u;
+    if (d >= 1.0f) return kDepthNoLimit;
+    const float lim = p23 / (d + p22);
+    return lim > 0.0f ? __float_as_uint(lim) : 0u;
+}
+
+// one 256-lane workgroup per tile, one pixel per lane
+__global__ __launch_bounds__(256) void k_depth_limits(const float* __restrict__ depth, uint64_t pitch_bytes, uint32_t w, uint32_t h,
+                                                       uint32_t tiles_x, float p22, float p23, uint32_t* __restrict__ lim,
+                                                       uint2* __restrict__ window) {
+    __shared__ uint32_t s_max[4];
+    const uint32_t tile = blockIdx.x, tx = tile % tiles_x, ty = tile / tiles_x;
+    const uint32_t x = tx * kTile + (threadIdx.x & 15u), y = ty * kTile + (threadIdx.x >> 4);
+    uint32_t l = 0u;  // (outside the image: no pixel to keep open)
+    if (x < w && y < h) {
+        const float d = reinterpret_cast<const float*>(reinterpret_cast<const char*>(depth) + (size_t)y * pitch_bytes)[x];
+        l = depth_limit_key(d, p22, p23);
+        lim[(size_t)y * w + x] = l;
+    }
+    uint32_t m = l;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63u) == 0u) s_max[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) window[tile] = make_uint2(0u, max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
+}
+
+// a speculated frame: its windows [0, hi) capped by the frame's depth bounds
+__global__ __launch_bounds__(256) void k_depth_cap_windows(const uint2* __restrict__ spec, const uint2* __restrict__ bound,
+                                                            uint2* __restrict__ out, uint32_t n_tiles) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n_tiles) return;
+    const uint2 s = spec[t];
+    out[t] = make_uint2(s.x, min(s.y, bound[t].y));
+}
+
+hipError_t launch_depth_limits(hipStream_t s, const float* depth, uint64_t pitch_bytes, uint32_t w, uint32_t h, float p22, float p23,
+                               uint32_t* lim, uint2* window) {
+    const uint32_t tiles_x = (w + kTile - 1) / kTile, tiles_y = (h + kTile - 1) / kTile;
+    if (!tiles_x || !tiles_y) return hipSuccess;
+    GSX_LAUNCH(k_depth_limits, dim3(tiles_x * tiles_y), dim3(256), 0, s, depth, pitch_bytes, w, h, tiles_x, p22, p23, lim, window);
+    return hipGetLastError();
+}
+
+hipError_t launch_depth_cap_windows(hipStream_t s, const uint2* spec, const uint2* bound, uint2* out, uint32_t n_tiles) {
+    if (!n_tiles) return hipSuccess;
+    GSX_LAUNCH(k_depth_cap_windows, dim3((n_tiles + 255) / 256), dim3(256), 0, s, spec, bound, out, n_tiles);
+    return hipGetLastError();
+}
+
+}  // namespace gsx

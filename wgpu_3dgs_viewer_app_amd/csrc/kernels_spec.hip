@@ -202,7 +202,8 @@ __global__ __launch_bounds__(1024) void k_spec_verify_fused(const uint2* __restr
                                                              uint32_t row_words, uint32_t tiles_x, uint32_t n_tiles,
                                                              uint2* __restrict__ win2, uint32_t* __restrict__ need_bits,
                                                              uint32_t* __restrict__ d_need, uint32_t band_lo, uint32_t band_hi,
-                                                             unsigned long long* __restrict__ host_verdict, uint32_t seq, VerifyTables vt) {
+                                                             unsigned long long* __restrict__ host_verdict, uint32_t seq, VerifyTables vt,
+                                                             const uint2* __restrict__ depth_bound) {
     __shared__ uint32_t s_need;
     __shared__ PyramidLds lds;
     if (threadIdx.x == 0) s_need = 0;
@@ -216,20 +217,22 @@ __global__ __launch_bounds__(1024) void k_spec_verify_fused(const uint2* __restr
     uint32_t mine = 0;
     for (uint32_t base = wave; base < items; base += 4u * 16u) {
         uint2 w[4];
-        uint32_t dw[4];
+        uint32_t dw[4], bd[4];
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k) {
             const uint32_t item = base + 16u * k, ty = item / pieces, tx = (item % pieces) * 64u + lane;
             const bool in = item < items && tx < tiles_x;
             w[k] = in ? win1[ty * tiles_x + tx] : make_uint2(0u, kKeyAll);
             dw[k] = in ? done[ty * row_words + (tx >> 5)] : 0u;
+            // depth test: a window that ends at the tile's depth bound holds every record the tile can show — complete, saturated or not
+            bd[k] = (in && depth_bound) ? depth_bound[ty * tiles_x + tx].y : kKeyAll;
         }
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k) {
             const uint32_t item = base + 16u * k, ty = item / pieces, tx = (item % pieces) * 64u + lane;
             const bool in = item < items && tx < tiles_x;
-            const bool need = in && ty >= band_lo && ty < band_hi && w[k].y != kKeyAll && !((dw[k] >> (tx & 31u)) & 1u);
-            if (in) win2[ty * tiles_x + tx] = need ? make_uint2(w[k].y, kKeyAll) : make_uint2(0u, 0u);
+            const bool need = in && ty >= band_lo && ty < band_hi && w[k].y != kKeyAll && w[k].y < bd[k] && !((dw[k] >> (tx & 31u)) & 1u);
+            if (in) win2[ty * tiles_x + tx] = need ? make_uint2(w[k].y, bd[k]) : make_uint2(0u, 0u);
             const unsigned long long nb = __ballot(need);
             if (item < items && (lane & 31u) == 0u && (tx >> 5) < row_words) need_bits[ty * row_words + (tx >> 5)] = (uint32_t)(nb >> lane);
             mine += need ? 1u : 0u;
@@ -269,7 +272,8 @@ constexpr int kNextBlock = 16, kNextMaxR = 16, kNextSpan = kNextBlock + 2 * kNex
 __global__ __launch_bounds__(256) void k_spec_next(const uint32_t* __restrict__ tile_sat, const uint32_t* __restrict__ done,
                                                     const uint32_t* __restrict__ done_before, uint32_t row_words,
                                                     uint32_t tiles_x, uint32_t tiles_y, float gain, int radius,
-                                                    uint2* __restrict__ win_next, int band_lo, int band_hi) {
+                                                    uint2* __restrict__ win_next, int band_lo, int band_hi,
+                                                    const uint2* __restrict__ depth_bound) {
     // per staged tile: depth (0 = contributes nothing) and an "open" flag; outside the band / image: neither
     __shared__ float s_deep[kNextSpan][kNextSpan + 1];
     __shared__ unsigned char s_open[kNextSpan][kNextSpan + 1];
@@ -285,7 +289,10 @@ __global__ __launch_bounds__(256) void k_spec_next(const uint32_t* __restrict__ 
         if (x >= 0 && x < (int)tiles_x && y >= band_lo && y < band_hi) {
             const uint32_t w = (uint32_t)y * row_words + ((uint32_t)x >> 5), bit = (uint32_t)x & 31u;
             if (!((done[w] >> bit) & 1u)) {
-                open = 1;
+                // depth test: a tile that stayed open below a finite depth bound took everything it can show; it counts as closed there
+                const uint32_t bd = depth_bound ? depth_bound[(uint32_t)y * tiles_x + (uint32_t)x].y : kKeyAll;
+                if (bd == kKeyAll) open = 1;
+                else deep = __uint_as_float(max(bd, 1u));
             } else if (!(done_before && ((done_before[w] >> bit) & 1u))) {
                 deep = __uint_as_float(tile_sat[(uint32_t)y * tiles_x + (uint32_t)x]);
             }
@@ -367,7 +374,7 @@ hipError_t launch_window_pyramid(hipStream_t s, const uint2* window, uint32_t ti
 hipError_t launch_spec_verify(hipStream_t s, const uint2* win1, const uint32_t* done, uint32_t row_words, uint32_t tiles_x,
                               uint32_t tiles_y, uint2* win2, uint32_t* need_bits, uint32_t* d_need, uint32_t band_lo, uint32_t band_hi,
                               unsigned long long* host_verdict, uint32_t seq, uint32_t* pyr2_data, const BlockGrid* grid, uint4* table,
-                              uint2* ranges) {
+                              uint2* ranges, const uint2* depth_bound) {
     const uint32_t n_tiles = tiles_x * tiles_y;
     VerifyTables vt{};
     vt.pyr2_data = pyr2_data;
@@ -381,16 +388,16 @@ hipError_t launch_spec_verify(hipStream_t s, const uint2* win1, const uint32_t* 
         vt.ranges = ranges;
     }
     GSX_LAUNCH(k_spec_verify_fused, dim3(1), dim3(1024), 0, s, win1, done, row_words, tiles_x, n_tiles, win2, need_bits, d_need,
-               std::min(band_lo, tiles_y), std::min(band_hi, tiles_y), host_verdict, seq, vt);
+               std::min(band_lo, tiles_y), std::min(band_hi, tiles_y), host_verdict, seq, vt, depth_bound);
     return hipGetLastError();
 }
 
 hipError_t launch_spec_next(hipStream_t s, const uint32_t* tile_sat, const uint32_t* done, const uint32_t* done_before,
                             uint32_t row_words, uint32_t tiles_x, uint32_t tiles_y, float margin, uint32_t radius, uint2* win_next,
-                            uint32_t band_lo, uint32_t band_hi) {
+                            uint32_t band_lo, uint32_t band_hi, const uint2* depth_bound) {
     GSX_LAUNCH(k_spec_next, dim3((tiles_x + kNextBlock - 1) / kNextBlock, (tiles_y + kNextBlock - 1) / kNextBlock), dim3(256), 0, s,
                        tile_sat, done, done_before, row_words, tiles_x, tiles_y, 1.0f + margin, (int)std::min<uint32_t>(radius, kNextMaxR), win_next,
-                       (int)std::min(band_lo, tiles_y), (int)std::min(band_hi, tiles_y));
+                       (int)std::min(band_lo, tiles_y), (int)std::min(band_hi, tiles_y), depth_bound);
     return hipGetLastError();
 }
 

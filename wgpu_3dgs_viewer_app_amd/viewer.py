@@ -55,6 +55,13 @@ class GaussianShDegree:
         return self.deg
 
 
+class DepthCompare(enum.IntEnum):
+    """``wgpu::CompareFunction`` of the viewer's depth test (gsx_depth_compare): Always = no test, Less = the reference's."""
+
+    Always = 0
+    Less = 1
+
+
 class ShKind(enum.IntEnum):
     """``GaussianSh{Single,Half,Norm8,None}Config`` (src/app.rs:386-403)."""
 
@@ -415,6 +422,24 @@ class MultiModelViewer:
             setattr(sp, k, float(val))
         _lib.check(self._L.gsx_viewer_set_spec_params(self._h, C.byref(sp)))
         return sp
+
+    # -- depth test against the caller's depth buffer (gs::MultiModelViewer::new_with's depth_stencil, scene.rs:1969-1980) --
+    def set_depth_test(self, compare) -> None:
+        """``DepthStencilState { Depth32Float, depth_write_enabled: false, compare }``: ``DepthCompare.Less`` hides a splat behind the
+        depth buffer at that pixel, ``DepthCompare.Always`` (default) turns the test off."""
+        _lib.check(self._L.gsx_viewer_set_depth_test(self._h, int(compare)))
+
+    def update_depth_buffer(self, depth: np.ndarray) -> None:
+        """float32 [height, width] NDC depth in [0, 1], row 0 at the top (what the gizmo and measurement passes wrote); copied."""
+        d = np.ascontiguousarray(depth, np.float32)
+        if d.ndim != 2:
+            raise ValueError("depth buffer must be [height, width]")
+        _lib.check(self._L.gsx_viewer_upload_depth_buffer(self._h, _f32p(d), int(d.shape[1]), int(d.shape[0])))
+
+    def set_depth_buffer_device(self, ptr, width: int, height: int, row_pitch_bytes: int) -> None:
+        """Caller-owned device memory (e.g. ``tensor.data_ptr()``), read in place; ``ptr = None`` detaches it."""
+        _lib.check(self._L.gsx_viewer_set_depth_buffer_device(self._h, C.c_void_p(ptr) if ptr else None, int(width), int(height),
+                                                              int(row_pitch_bytes)))
 
     def set_render_options(self, **kw) -> None:
         """``gsx_render_options``: progressive depth slabs (default on), first_slab_divisor, min_slab, growth."""
