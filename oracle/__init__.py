@@ -75,6 +75,14 @@ def lib():
         L.gsxo_composite_tiles.restype = None
         L.gsxo_render_model.argtypes = [C.POINTER(Frame), C.c_uint64, fp, u32p, fp, fp, u32p, fp]
         L.gsxo_render_model.restype = C.c_uint64
+        L.gsxo_rasterize_depth.argtypes = [C.POINTER(Frame), C.c_uint64, u32p, u32p, fp, fp, fp, u32p, u32p, fp]
+        L.gsxo_rasterize_depth.restype = None
+        L.gsxo_composite_tiles_depth.argtypes = [C.POINTER(Frame), u32p, u32p, fp, fp, fp, u32p, u32p, fp]
+        L.gsxo_composite_tiles_depth.restype = None
+        L.gsxo_render_model_depth.argtypes = [C.POINTER(Frame), C.c_uint64, fp, u32p, fp, fp, u32p, u32p, fp]
+        L.gsxo_render_model_depth.restype = C.c_uint64
+        L.gsxo_depth_limits.argtypes = [fp, fp, C.c_uint64, C.c_uint32, C.c_uint32, u32p]
+        L.gsxo_depth_limits.restype = None
         L.gsxo_mask_evaluate.argtypes = [C.c_uint64, fp, fp, fp, fp, vp, C.c_uint32, vp, C.c_uint32, u32p]
         L.gsxo_mask_evaluate.restype = None
         L.gsxo_num_threads.restype = C.c_int
@@ -163,21 +171,55 @@ def new_framebuffer(frame: Frame) -> np.ndarray:
     return fb
 
 
-def rasterize(frame: Frame, proj: dict, sorted_idx, n_visible, fb: np.ndarray) -> None:
-    lib().gsxo_rasterize(C.byref(frame), n_visible, _up(sorted_idx), _up(proj["rect"]), _fp(proj["mean2d"]),
-                         _fp(proj["conic_opacity"]), _fp(proj["rgb"]), _fp(fb))
+def _lim(frame: Frame, lim):
+    lim = np.ascontiguousarray(lim, np.uint32)
+    assert lim.shape == (frame.h_px, frame.w_px), "depth limits must be [h, w]"
+    return lim
 
 
-def composite_tiles(frame: Frame, proj: dict, tile_offsets, tile_list, fb: np.ndarray) -> None:
+def depth_limits(proj, depth) -> np.ndarray:
+    """Per-pixel depth-test limit keys (spec §6 "Depth test") of a Depth32Float image ``depth`` ([h, w] f32, any row stride in
+    whole floats) under the projection ``proj`` (16 floats, column-major): uint32 [h, w]."""
+    d = np.asarray(depth, np.float32)
+    assert d.ndim == 2 and d.strides[1] == 4 and d.strides[0] % 4 == 0
+    h, w = d.shape
+    lim = np.empty((h, w), np.uint32)
+    lib().gsxo_depth_limits(_fp(_f32(proj, 16)), d.ctypes.data_as(C.POINTER(C.c_float)), d.strides[0], w, h, _up(lim))
+    return lim
+
+
+def rasterize(frame: Frame, proj: dict, sorted_idx, n_visible, fb: np.ndarray, lim=None) -> None:
+    """Back to front over ``fb``.  lim ([h, w] uint32, ``depth_limits``): the depth test — a (record, pixel) pair is blended only
+    when the record's key is < lim at that pixel; None = off."""
+    if lim is None:
+        lib().gsxo_rasterize(C.byref(frame), n_visible, _up(sorted_idx), _up(proj["rect"]), _fp(proj["mean2d"]),
+                             _fp(proj["conic_opacity"]), _fp(proj["rgb"]), _fp(fb))
+        return
+    lim = _lim(frame, lim)
+    lib().gsxo_rasterize_depth(C.byref(frame), n_visible, _up(sorted_idx), _up(proj["rect"]), _fp(proj["mean2d"]),
+                               _fp(proj["conic_opacity"]), _fp(proj["rgb"]), _up(np.ascontiguousarray(proj["key"], np.uint32)),
+                               _up(lim), _fp(fb))
+
+
+def composite_tiles(frame: Frame, proj: dict, tile_offsets, tile_list, fb: np.ndarray, lim=None) -> None:
+    """Front to back per tile.  lim: the depth test with the spec's early stop (a pixel stops at its first record whose key is
+    >= its limit); None = off."""
     lst = tile_list if tile_list.size else np.zeros(1, np.uint32)
-    lib().gsxo_composite_tiles(C.byref(frame), _up(tile_offsets), _up(lst), _fp(proj["mean2d"]),
-                               _fp(proj["conic_opacity"]), _fp(proj["rgb"]), _fp(fb))
+    if lim is None:
+        lib().gsxo_composite_tiles(C.byref(frame), _up(tile_offsets), _up(lst), _fp(proj["mean2d"]),
+                                   _fp(proj["conic_opacity"]), _fp(proj["rgb"]), _fp(fb))
+        return
+    lim = _lim(frame, lim)
+    lib().gsxo_composite_tiles_depth(C.byref(frame), _up(tile_offsets), _up(lst), _fp(proj["mean2d"]), _fp(proj["conic_opacity"]),
+                                     _fp(proj["rgb"]), _up(np.ascontiguousarray(proj["key"], np.uint32)), _up(lim), _fp(fb))
 
 
-def render_model(frame: Frame, pos, color, sh, cov3d, fb: np.ndarray, mask=None) -> int:
-    """project -> depth sort -> back-to-front rasterise one model over ``fb`` (paint far models first)."""
-    return int(lib().gsxo_render_model(C.byref(frame), pos.shape[0], _fp(pos), _up(color), _fp(sh), _fp(cov3d),
-                                       _up(mask), _fp(fb)))
+def render_model(frame: Frame, pos, color, sh, cov3d, fb: np.ndarray, mask=None, lim=None) -> int:
+    """project -> depth sort -> back-to-front rasterise one model over ``fb`` (paint far models first); lim: the depth test."""
+    if lim is not None:
+        lim = _lim(frame, lim)
+    return int(lib().gsxo_render_model_depth(C.byref(frame), pos.shape[0], _fp(pos), _up(color), _fp(sh), _fp(cov3d),
+                                             _up(mask), _up(lim), _fp(fb)))
 
 
 def num_threads() -> int:

@@ -448,8 +448,11 @@ static inline float splat_alpha(const gsxo_frame* f, float px, float py, const f
     return a;
 }
 
-void gsxo_rasterize(const gsxo_frame* f, uint64_t n_visible, const uint32_t* sorted_idx, const uint32_t* rect,
-                    const float* mean2d, const float* conic_op, const float* rgb, float* fb) {
+/* key / lim: the depth test (spec §6 "Depth test"), NULL = off.  A (record, pixel) pair is blended only if the record's
+ * depth key lies in front of the pixel's limit key: key[i] < lim[y * w + x]. */
+static void rasterize_impl(const gsxo_frame* f, uint64_t n_visible, const uint32_t* sorted_idx, const uint32_t* rect,
+                           const float* mean2d, const float* conic_op, const float* rgb, const uint32_t* key,
+                           const uint32_t* lim, float* fb) {
     int H = (int)f->h_px, Wd = (int)f->w_px;
     int bands = (int)f->tiles_y;
 #pragma omp parallel for schedule(dynamic, 1)
@@ -467,6 +470,7 @@ void gsxo_rasterize(const gsxo_frame* f, uint64_t n_visible, const uint32_t* sor
                 float py = (float)y + 0.5f;
                 float* row = fb + ((size_t)y * Wd) * 4;
                 for (int x = x0; x < x1; ++x) {
+                    if (lim && !(key[i] < lim[(size_t)y * Wd + x])) continue;
                     float a = splat_alpha(f, (float)x + 0.5f, py, m, co);
                     if (a < 0.0f) continue;
                     float* p = row + 4 * x;
@@ -481,10 +485,24 @@ void gsxo_rasterize(const gsxo_frame* f, uint64_t n_visible, const uint32_t* sor
     }
 }
 
+void gsxo_rasterize(const gsxo_frame* f, uint64_t n_visible, const uint32_t* sorted_idx, const uint32_t* rect,
+                    const float* mean2d, const float* conic_op, const float* rgb, float* fb) {
+    rasterize_impl(f, n_visible, sorted_idx, rect, mean2d, conic_op, rgb, NULL, NULL, fb);
+}
+
+void gsxo_rasterize_depth(const gsxo_frame* f, uint64_t n_visible, const uint32_t* sorted_idx, const uint32_t* rect,
+                          const float* mean2d, const float* conic_op, const float* rgb, const uint32_t* key,
+                          const uint32_t* lim, float* fb) {
+    rasterize_impl(f, n_visible, sorted_idx, rect, mean2d, conic_op, rgb, key, lim, fb);
+}
+
 /* Front-to-back tile compositor — the HIP path's algorithm restated on the CPU WITHOUT early
- * termination, used only to localise a parity failure (tile lists vs blending). */
-void gsxo_composite_tiles(const gsxo_frame* f, const uint32_t* tile_offsets, const uint32_t* list,
-                          const float* mean2d, const float* conic_op, const float* rgb, float* fb) {
+ * termination, used only to localise a parity failure (tile lists vs blending).  key / lim: the depth test
+ * (NULL = off) with the spec's early stop — lists are in ascending key order, so a pixel stops at its first
+ * record whose key is not in front of its limit. */
+static void composite_tiles_impl(const gsxo_frame* f, const uint32_t* tile_offsets, const uint32_t* list,
+                                 const float* mean2d, const float* conic_op, const float* rgb, const uint32_t* key,
+                                 const uint32_t* lim, float* fb) {
     int H = (int)f->h_px, Wd = (int)f->w_px;
     int tiles = (int)(f->tiles_x * f->tiles_y);
 #pragma omp parallel for schedule(dynamic, 4)
@@ -498,6 +516,7 @@ void gsxo_composite_tiles(const gsxo_frame* f, const uint32_t* tile_offsets, con
                 float A0 = 0, A1 = 0, A2 = 0, Tm = 1.0f;
                 for (uint32_t e = tile_offsets[t]; e < tile_offsets[t + 1]; ++e) {
                     uint64_t i = list[e];
+                    if (lim && key[i] >= lim[(size_t)y * Wd + x]) break;
                     float a = splat_alpha(f, (float)x + 0.5f, (float)y + 0.5f, mean2d + 2 * i, conic_op + 4 * i);
                     if (a < 0.0f) continue;
                     float wgt = Tm * a;
@@ -515,10 +534,46 @@ void gsxo_composite_tiles(const gsxo_frame* f, const uint32_t* tile_offsets, con
     }
 }
 
+void gsxo_composite_tiles(const gsxo_frame* f, const uint32_t* tile_offsets, const uint32_t* list,
+                          const float* mean2d, const float* conic_op, const float* rgb, float* fb) {
+    composite_tiles_impl(f, tile_offsets, list, mean2d, conic_op, rgb, NULL, NULL, fb);
+}
+
+void gsxo_composite_tiles_depth(const gsxo_frame* f, const uint32_t* tile_offsets, const uint32_t* list,
+                                const float* mean2d, const float* conic_op, const float* rgb, const uint32_t* key,
+                                const uint32_t* lim, float* fb) {
+    composite_tiles_impl(f, tile_offsets, list, mean2d, conic_op, rgb, key, lim, fb);
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * Depth test limits (spec §6 "Depth test"): the caller's Depth32Float buffer D ([h] rows of w floats,
+ * `pitch` bytes apart) and the projection P (column-major) -> one limit key per pixel, lim[y * w + x].
+ * The spec: d_lim = P23 / (D + P22) in f32, a splat passes iff key < bits(d_lim); D >= 1 is no limit
+ * (every key passes: 0xFFFFFFFF), D <= 0 or NaN lets nothing pass (0), and so does a quotient that is not
+ * positive (no depth key, all of them > 0, lies in front of it).
+ * ---------------------------------------------------------------------------------------------- */
+void gsxo_depth_limits(const float proj[16], const float* depth, uint64_t pitch, uint32_t w, uint32_t h, uint32_t* lim) {
+    const float p22 = proj[2 * 4 + 2], p23 = proj[3 * 4 + 2]; /* [row][col], column-major storage: element col * 4 + row */
+    for (uint32_t y = 0; y < h; ++y) {
+        const float* row = (const float*)((const char*)depth + (size_t)y * pitch);
+        for (uint32_t x = 0; x < w; ++x) {
+            const float d = row[x];
+            uint32_t out = 0u;
+            if (d >= 1.0f) {
+                out = 0xFFFFFFFFu;
+            } else if (d > 0.0f) {
+                const float q = p23 / (d + p22);
+                if (q > 0.0f) memcpy(&out, &q, sizeof out);
+            }
+            lim[(size_t)y * w + x] = out;
+        }
+    }
+}
+
 /* Whole frame for one model on top of fb (far models first): project -> sort -> rasterise.
- * Scratch is allocated internally.  Returns n_visible. */
-uint64_t gsxo_render_model(const gsxo_frame* f, uint64_t n, const float* pos, const uint32_t* color,
-                           const float* sh, const float* cov3d, const uint32_t* mask, float* fb) {
+ * Scratch is allocated internally.  Returns n_visible.  lim: per-pixel depth-test limits (gsxo_depth_limits), NULL = off. */
+uint64_t gsxo_render_model_depth(const gsxo_frame* f, uint64_t n, const float* pos, const uint32_t* color,
+                                 const float* sh, const float* cov3d, const uint32_t* mask, const uint32_t* lim, float* fb) {
     uint32_t* key = (uint32_t*)malloc(sizeof(uint32_t) * (n ? n : 1));
     uint32_t* rect = (uint32_t*)malloc(sizeof(uint32_t) * 4 * (n ? n : 1));
     float* mean2d = (float*)malloc(sizeof(float) * 2 * (n ? n : 1));
@@ -527,9 +582,14 @@ uint64_t gsxo_render_model(const gsxo_frame* f, uint64_t n, const float* pos, co
     uint32_t* sorted = (uint32_t*)malloc(sizeof(uint32_t) * (n ? n : 1));
     gsxo_project(f, n, pos, color, sh, cov3d, mask, key, rect, mean2d, conic, rgb);
     uint64_t nvis = gsxo_depth_sort(n, key, sorted);
-    gsxo_rasterize(f, nvis, sorted, rect, mean2d, conic, rgb, fb);
+    rasterize_impl(f, nvis, sorted, rect, mean2d, conic, rgb, key, lim, fb);
     free(key); free(rect); free(mean2d); free(conic); free(rgb); free(sorted);
     return nvis;
+}
+
+uint64_t gsxo_render_model(const gsxo_frame* f, uint64_t n, const float* pos, const uint32_t* color,
+                           const float* sh, const float* cov3d, const uint32_t* mask, float* fb) {
+    return gsxo_render_model_depth(f, n, pos, color, sh, cov3d, mask, NULL, fb);
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -251,11 +251,21 @@ def project(view, proj, width, height, pos, color_u32, sh, cov3d, m_pos=(0, 0, 0
         if highlight is not None and float(highlight[3]) > 0:
             hl = np.asarray(highlight, np.float64)
             rgb[sel] = rgb[sel] + (hl[:3] - rgb[sel]) * hl[3]
-    return dict(visible=vis, depth=d, mean2d=np.stack([mx, my], 1), cov2d=np.stack([a, b, cc], 1), conic=conic,
+    return dict(visible=vis, depth=d, z_ndc=pc[:, 2] / w, mean2d=np.stack([mx, my], 1), cov2d=np.stack([a, b, cc], 1), conic=conic,
                 opacity=opacity, rgb=rgb, pix_aabb=np.stack([x0, y0, x1, y1], 1))
 
 
-def render(view, proj, width, height, models, size=1.0, display_mode=0, sh_deg=3, no_sh0=0, params=None, ambiguity_tol=None):
+# Depth test: the band |z_ndc - D| within which a float32 implementation may decide a (splat, pixel) pair the other way, as a
+# fraction of the splat's view depth d (render's `depth_tol`; in NDC the band is depth_tol x |P23| / d, since
+# dz_ndc / dd = -P23 / d^2).  The kernels compare the f32 key bits(d) with bits(P23 / (D + P22)): the key differs from the float64
+# d by the f32 rounding of the model/view transform — check_projection holds it to 1e-5 relative, and the fixtures show up to a
+# few 1e-7 — and the limit by one rounding of the division (2^-24 relative; D + P22 is exact for D >= |P22| / 2 by Sterbenz and
+# rounds by 2^-24 |P22| / |D + P22| <= 2^-23 below it).  1e-5 covers both with room; pixel centres in the band are rare.
+DEPTH_TOL = 1e-5
+
+
+def render(view, proj, width, height, models, size=1.0, display_mode=0, sh_deg=3, no_sh0=0, params=None, ambiguity_tol=None,
+           depth=None, depth_tol=DEPTH_TOL):
     """Full frame.  ``models`` = list of dicts(pos,color,sh,cov3d[,m_pos,m_quat,m_scale,mask]) in the
     reference's paint order FAR -> NEAR (src/tab/scene.rs:533-558).  Returns float64 [H,W,4] =
     premultiplied rgb + transmittance.
@@ -264,15 +274,24 @@ def render(view, proj, width, height, models, size=1.0, display_mode=0, sh_deg=3
     closer than ``ambiguity_tol`` to the cut.  The cut is a discontinuity of the spec itself: a contribution of
     opacity x exp(-k^2 / 2) (1.1 % at k = 3) is in or out, and an implementation in another precision may decide a pair that
     close the other way.  Per such pair the pixel's allowance grows by 2 x T x alpha x max(1, |rgb|) — its own contribution plus
-    what the changed transmittance does to everything behind it."""
+    what the changed transmittance does to everything behind it.
+
+    depth (optional, float32 [H, W]): the caller's Depth32Float buffer and the test `Less` (spec §6 "Depth test") in the
+    reference's own domain, NDC, in float64: splat g is blended at p iff z_ndc(g) = clip.z / clip.w of its centre < D(p) (NaN
+    compares false).  Not the kernels' key-domain restatement.  Pairs with |z_ndc - D(p)| < depth_tol x |P23| / d(g) (DEPTH_TOL)
+    go into the allowance like near-cut support decisions; with a depth buffer the allowance is always returned."""
     P_ = dict(DEFAULT_PARAMS)
     P_.update(params or {})
     k2 = P_["max_std_dev"] ** 2
     C = np.zeros((height, width, 3))
     T = np.ones((height, width))
-    amb = np.zeros((height, width)) if ambiguity_tol is not None else None
+    amb = np.zeros((height, width)) if ambiguity_tol is not None or depth is not None else None
     ys, xs = np.mgrid[0:height, 0:width]
     px, py = xs + 0.5, ys + 0.5
+    if depth is not None:
+        D = np.asarray(depth, np.float32).astype(np.float64)
+        assert D.shape == (height, width)
+        p23 = abs(float(np.asarray(proj, np.float64).reshape(4, 4).T[2, 3]))
     for mdl in reversed(models):  # front-to-back across models: nearest model first
         pr = project(view, proj, width, height, mdl["pos"], mdl["color"], mdl.get("sh"), mdl["cov3d"],
                      mdl.get("m_pos", (0, 0, 0)), mdl.get("m_quat", (0, 0, 0, 1)), mdl.get("m_scale", (1, 1, 1)),
@@ -296,7 +315,16 @@ def render(view, proj, width, height, models, size=1.0, display_mode=0, sh_deg=3
             al = np.minimum(P_["alpha_max"], pr["opacity"][i] * wgt)
             al = np.where((q <= k2) & (al >= P_["alpha_min"]), al, 0.0)
             Tl = T[y0:y1, x0:x1]
-            if amb is not None:
+            if depth is not None:
+                Dl = D[y0:y1, x0:x1]
+                z = float(pr["z_ndc"][i])
+                with np.errstate(invalid="ignore"):
+                    passes = z < Dl
+                    near_surface = np.abs(z - Dl) < depth_tol * p23 / float(pr["depth"][i])
+                a_edge = np.where(q <= k2, np.minimum(P_["alpha_max"], pr["opacity"][i] * wgt), 0.0)
+                amb[y0:y1, x0:x1] += np.where(near_surface, 2.0 * Tl * a_edge * max(1.0, float(np.abs(pr["rgb"][i]).max())), 0.0)
+                al = np.where(passes, al, 0.0)
+            if ambiguity_tol is not None:
                 edge = np.abs(q - k2) < ambiguity_tol
                 if edge.any():
                     a_edge = np.minimum(P_["alpha_max"], pr["opacity"][i] * wgt)

@@ -2,6 +2,7 @@
 import numpy as np
 
 import oracle
+from oracle.spec_f64 import quat_to_mat
 from wgpu_3dgs_viewer_app_amd import camera, scene
 
 
@@ -19,6 +20,49 @@ def default_transform():
 def odd_transform():
     return camera.ModelTransform(pos=np.array([0.3, -0.2, 0.5], np.float32), rot=np.array([20, -35, 50], np.float32),
                                  scale=np.array([1.2, 0.9, 1.1], np.float32))
+
+
+def surface_depth(cam, w, h, surfaces):
+    """A Depth32Float buffer as the gizmos write it: per pixel centre, the NDC depth (clip.z / clip.w, float64, stored as f32) of
+    the nearest surface the camera's ray hits; 1.0 (cleared) where none is hit.  surfaces: dict(kind "plane", point, normal) |
+    dict(kind "box" | "ellipsoid", pos, quat, scale (half extents / radii))."""
+    V = np.asarray(cam.view(), np.float64).reshape(4, 4).T
+    P = np.asarray(cam.projection(w / h), np.float64).reshape(4, 4).T
+    ys, xs = np.mgrid[0:h, 0:w]
+    nx, ny = (xs + 0.5) / w * 2.0 - 1.0, 1.0 - (ys + 0.5) / h * 2.0
+    dv = np.stack([nx / P[0, 0], ny / P[1, 1], -np.ones_like(nx)], -1)      # view-space ray, view depth d = t
+    R, t = V[:3, :3], V[:3, 3]
+    origin = -R.T @ t
+    dw = dv @ R                                                              # R^T dv per pixel
+    best = np.full((h, w), np.inf)
+    for s in surfaces:
+        if s["kind"] == "plane":
+            n = np.asarray(s["normal"], np.float64)
+            den = dw @ n
+            with np.errstate(divide="ignore", invalid="ignore"):
+                tt = ((np.asarray(s["point"], np.float64) - origin) @ n) / den
+        else:
+            Rs = quat_to_mat(s["quat"])
+            sc = np.asarray(s["scale"], np.float64)
+            o = ((origin - np.asarray(s["pos"], np.float64)) @ Rs) / sc                    # local frame: the unit shape
+            d = (dw @ Rs) / sc
+            if s["kind"] == "ellipsoid":
+                a, b, c = (d * d).sum(-1), 2.0 * (d @ o), o @ o - 1.0
+                disc = b * b - 4 * a * c
+                with np.errstate(invalid="ignore"):
+                    tt = np.where(disc >= 0, (-b - np.sqrt(np.maximum(disc, 0))) / (2 * a), np.inf)
+            else:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    t1, t2 = (-1.0 - o) / d, (1.0 - o) / d
+                tn, tf = np.minimum(t1, t2).max(-1), np.maximum(t1, t2).min(-1)
+                tt = np.where(tn <= tf, tn, np.inf)
+        tt = np.where(tt > 0, tt, np.inf)
+        best = np.minimum(best, tt)
+    with np.errstate(invalid="ignore"):
+        pv = dv * best[..., None]                                            # the hit in view space
+        pc = np.concatenate([pv, np.ones((h, w, 1))], -1) @ P.T
+        z = pc[..., 2] / pc[..., 3]
+    return np.where(np.isfinite(best) & (z < 1.0), z, 1.0).astype(np.float32)
 
 
 def oracle_frame(cam, w, h, mt=None, size=1.0, display_mode=0, sh_deg=3, no_sh0=0, params=None):

@@ -18,6 +18,9 @@ Fixture keys (i = model index in load order):
   params_<name>                                  gsx_spec_params that differ from the defaults (spec/RENDER_SPEC.md [BUILD-SPEC] constants)
   frame_ambiguity, ambiguity_tol                 (large fixtures) per pixel: how much of the value hangs on support decisions q <= k^2 closer
                                                  than ambiguity_tol to the cut — a discontinuity of the spec (oracle/spec_f64.render)
+  depth, depth_tol                               (depth fixtures) the caller's Depth32Float buffer f32 [H, W] (NDC depth, row 0 at the top) and
+                                                 the test `Less`; the frame is spec_f64.render's NDC-domain test, frame_ambiguity carries
+                                                 the pairs within depth_tol of the surface (and ambiguity_tol of the cut, if given)
   prior_view, prior_proj                         (large fixtures) another camera: a frame rendered from it first leaves windows that are
                                                  wrong for this one, so the speculated frame needs its repair round
 """
@@ -30,6 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 from oracle import spec_f64  # noqa: E402
+from tests.common import surface_depth  # noqa: E402
 from wgpu_3dgs_viewer_app_amd import camera, scene  # noqa: E402
 from wgpu_3dgs_viewer_app_amd.mask import MaskOp  # noqa: E402
 
@@ -45,10 +49,11 @@ def pod_f64(g):
 
 
 def make(name, models, cam, w, h, pod=None, mask=None, selection=None, sel_edit=None, highlight=None, params=None, prior_cam=None,
-         ambiguity_tol=None, **kw):
+         ambiguity_tol=None, depth=None, **kw):
     """pod = (sh_kind, cov_kind); mask = (expression, [dict(kind, pos, quat, scale)]) applied to every model;
     selection = seed of a random selection bitset (every model); sel_edit = dict(flag, color, contrast, exposure, gamma, alpha);
-    highlight = (r, g, b, a); kw: size, display_mode, sh_deg, no_sh0."""
+    highlight = (r, g, b, a); depth = the caller's Depth32Float buffer (f32 [h, w]) with the test `Less`; kw: size, display_mode,
+    sh_deg, no_sh0."""
     view, proj = cam.view(), cam.projection(w / h)
     out = dict(view=view, proj=proj, size=np.array([w, h]), n_models=np.array(len(models)))
     if pod:
@@ -103,12 +108,19 @@ def make(name, models, cam, w, h, pod=None, mask=None, selection=None, sel_edit=
     # paint order far -> near by centre distance (scene.rs:533-558)
     keys = camera.model_render_order(cam.pos, {i: mt.world_center() for i, (_, mt) in enumerate(models)})
     out["paint_order"] = np.array(keys)
-    if ambiguity_tol is not None:
-        frame, amb = spec_f64.render(view, proj, w, h, [spec_models[k] for k in keys], ambiguity_tol=ambiguity_tol, **kw)
+    if depth is not None:
+        depth = np.ascontiguousarray(depth, np.float32)
+        assert depth.shape == (h, w)
+        out["depth"], out["depth_tol"] = depth, np.array(spec_f64.DEPTH_TOL)
+    if ambiguity_tol is not None or depth is not None:
+        frame, amb = spec_f64.render(view, proj, w, h, [spec_models[k] for k in keys], ambiguity_tol=ambiguity_tol, depth=depth, **kw)
         out["frame_ambiguity"] = amb.astype(np.float32)
-        out["ambiguity_tol"] = np.array(ambiguity_tol)
-        print(name, "pixels whose value hangs on a support decision within", ambiguity_tol, "of the cut by more than 1e-4:",
-              int((amb > 1e-4).sum()), "of", amb.size, "max allowance", float(amb.max()))
+        if ambiguity_tol is not None:
+            out["ambiguity_tol"] = np.array(ambiguity_tol)
+        print(name, "pixels whose value hangs on a support decision within", ambiguity_tol, "of the cut or a depth decision within",
+              spec_f64.DEPTH_TOL if depth is not None else None, "of the surface by more than 1e-4:", int((amb > 1e-4).sum()), "of",
+              amb.size, "max allowance", float(amb.max()))
+        assert (amb > 1e-4).mean() < 0.02, f"{name}: too much of the frame hangs on near-cut decisions; pick another scene"
     else:
         frame = spec_f64.render(view, proj, w, h, [spec_models[k] for k in keys], **kw)
     out["frame"] = frame.astype(np.float32)
@@ -211,3 +223,47 @@ if __name__ == "__main__":
               (scene_small(300, 117), camera.ModelTransform(pos=np.array([1.0, 0.0, 1.0], np.float32), scale=np.array([0.8, 0.8, 0.8], np.float32)))],
              camera.orbit_pose(180), 112, 80, pod=(2, 1))
 
+    # the depth test (spec §6 "Depth test") against per-pixel depth buffers drawn from geometry seen by the fixture's own camera
+    if want("depth_plane_odd"):
+        cam = camera.orbit_pose(30)
+        # 83 x 51: partial last tile column and row, and a last pixel-pair row half outside the image; the slanted plane
+        # through the model changes the limit inside every tile and every pixel pair
+        plane = [dict(kind="plane", point=(0.1, 0.0, -0.2), normal=(0.8, 0.35, 0.5))]
+        make("frame_depth_plane_odd_83x51_n500_seed301", [(scene_small(500, 301), ident)], cam, 83, 51,
+             depth=surface_depth(cam, 83, 51, plane))
+    if want("depth_gizmo"):
+        # the app's default pod (Norm8 + Half) and the case the gizmos exist for: box + ellipsoid drawn into the buffer, a mask,
+        # a stored selection with a colour edit and a highlight
+        cam = camera.orbit_pose(70)
+        g = scene_small(600, 302)
+        g["sh"] *= np.float32(4.0)
+        gizmo = [dict(kind="box", pos=(0.5, 0.1, 0.4), quat=tuple(camera.quat_from_euler_zyx(0.3, 0.5, -0.2)), scale=(1.2, 0.9, 1.0)),
+                 dict(kind="ellipsoid", pos=(-0.7, -0.2, 0.1), quat=tuple(camera.quat_from_euler_zyx(-0.4, 0.2, 0.1)), scale=(1.0, 1.3, 0.9))]
+        shapes = [dict(kind=0, pos=(0.0, 0.0, 0.0), quat=tuple(camera.quat_from_euler_zyx(0.2, -0.1, 0.3)), scale=(2.6, 2.2, 2.8))]
+        make("frame_depth_gizmo_norm8_half_edit_96x64_n600_seed302", [(g, odd)], cam, 96, 64, pod=(2, 1), mask=("0", shapes),
+             selection=13, sel_edit=dict(flag=1, color=(0.2, 1.2, 0.9), contrast=0.2, exposure=0.5, gamma=1.2, alpha=0.8),
+             highlight=(0.0, 1.0, 0.5, 0.3), depth=surface_depth(cam, 96, 64, gizmo))
+    if want("depth_2models"):
+        # two layered models with TRS and an occluder between them: pixels closed by depth in the near model go on to the far one
+        cam = camera.orbit_pose(200)
+        near_mt = camera.ModelTransform(pos=np.array([0.2, 0.0, 1.6], np.float32), rot=np.array([10, 25, -15], np.float32),
+                                        scale=np.array([0.8, 0.9, 0.8], np.float32))
+        models = [(scene_small(500, 303), odd), (scene_small(400, 304), near_mt)]
+        mid = 0.5 * (odd.world_center().astype(np.float64) + near_mt.world_center().astype(np.float64))
+        occ = [dict(kind="box", pos=tuple(mid + np.array([0.6, 0.3, 0.0])), quat=tuple(camera.quat_from_euler_zyx(0.2, 0.6, 0.1)),
+                    scale=(2.0, 1.4, 0.15))]
+        make("frame_depth_2models_trs_occluder_112x80_seed303", models, cam, 112, 80, depth=surface_depth(cam, 112, 80, occ))
+    if want("depth_specials"):
+        # a strip of special values inside the splat-covered middle of the frame, over a slanted plane
+        cam = camera.orbit_pose(110)
+        d = surface_depth(cam, 80, 48, [dict(kind="plane", point=(0.0, 0.0, 0.0), normal=(-0.3, 1.0, 0.6))])
+        specials = [np.nan, 0.0, -0.0, -0.25, 1e-40, np.nextafter(np.float32(1), np.float32(0)), 1.0, 1.5, np.inf]
+        for j, v in enumerate(specials):
+            d[16:33, 13 + 6 * j: 19 + 6 * j] = np.float32(v)
+        make("frame_depth_specials_80x48_n500_seed305", [(scene_small(500, 305), ident)], cam, 80, 48, depth=d)
+    if want("depth_ellipse"):
+        cam = camera.orbit_pose(160)
+        shapes = [dict(kind="ellipsoid", pos=(0.3, 0.0, 0.0), quat=(0.0, 0.0, 0.0, 1.0), scale=(0.9, 1.4, 0.7)),
+                  dict(kind="plane", point=(0.0, -0.3, 0.0), normal=(0.2, 1.0, -0.4))]
+        make("frame_depth_ellipse_mode_80x48_n400_seed306", [(scene_small(400, 306), odd)], cam, 80, 48, display_mode=1,
+             depth=surface_depth(cam, 80, 48, shapes))

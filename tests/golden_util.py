@@ -38,6 +38,9 @@ class Fixture:
         # a discontinuity of the spec (1.1 % of opacity x colour at k = 3), decided differently by implementations of different
         # precision for pairs that close (oracle/spec_f64.render); None for the small fixtures, which hold no such pair that matters
         self.ambiguity = z["frame_ambiguity"] if "frame_ambiguity" in z else None
+        # depth fixtures: the caller's Depth32Float buffer (f32 [H, W]) the frame was rendered against with the test `Less`
+        # (spec §6 "Depth test"); the allowance above then also covers pairs within depth_tol of the surface
+        self.depth = z["depth"] if "depth" in z else None
 
     def gaussians(self, k):
         return self.z[f"g{k}"]

@@ -49,3 +49,98 @@ def test_header_documents_the_depth_test():
     assert re.search(r"GSX_DEPTH_ALWAYS = 0", hdr) and re.search(r"GSX_DEPTH_LESS = 1", hdr)
     spec = open(os.path.join(ROOT, "spec", "RENDER_SPEC.md")).read()
     assert "Depth test" in spec
+
+
+def _perspective_infinite_rh(fov_y, aspect, z_near):
+    """glam's Mat4::perspective_infinite_rh, column-major: P22 = -1, P23 = -z_near"""
+    f = np.float32(1.0 / np.tan(0.5 * fov_y))
+    m = np.zeros((4, 4), np.float32)
+    m[0, 0], m[1, 1] = f / np.float32(aspect), f
+    m[2, 2], m[2, 3], m[3, 2] = -1.0, -1.0, -np.float32(z_near)
+    return m.reshape(16)
+
+
+def _depth_sweep(proj, n=120_000, seed=0):
+    """D values where limits go wrong: every special, the NDC depths of splats 1 .. 50 units away (where D + P22 cancels) as
+    consecutive f32 neighbours, random bit patterns of [0, 1] and of all floats (negatives, NaNs, infinities, subnormals)"""
+    rng = np.random.default_rng(seed)
+    p = np.asarray(proj, np.float32)
+    specials = np.array([np.nan, -np.nan, 0.0, -0.0, -1.0, -1e-40, 1e-45, 1e-40, 1.17e-38, np.nextafter(np.float32(1), np.float32(0)),
+                         1.0, np.nextafter(np.float32(1), np.float32(2)), 1.5, np.inf, -np.inf, -p[10], np.nextafter(-p[10], np.float32(0)),
+                         np.nextafter(-p[10], np.float32(2))], np.float32)
+    near_bits = []
+    for d in (1.0, 2.0, 5.0, 6.0, 7.5, 20.0, 50.0):
+        z = np.float32(np.float32(p[14]) / np.float32(d) - np.float32(p[10]))
+        if 0 < z < 1:
+            b = int(z.view(np.uint32))
+            near_bits.append(np.arange(b - 2000, b + 2000, dtype=np.int64))
+    near = np.concatenate(near_bits).astype(np.uint32).view(np.float32)
+    m = max((n - specials.size - near.size) // 2, 0)
+    unit = rng.integers(0, 0x3F800001, m, dtype=np.int64).astype(np.uint32).view(np.float32)
+    anyb = rng.integers(0, 1 << 32, m, dtype=np.int64).astype(np.uint32).view(np.float32)
+    return np.concatenate([specials, near, unit, anyb])
+
+
+def test_oracle_limits_equal_the_numpy_restatement_bit_for_bit():
+    """oracle.depth_limits (written from spec §6) against test_gpu_depth_test.limit_key (the kernels' formula restated in numpy):
+    identical bits over >= 1e5 values of D, specials included, for the app's camera and for perspective_infinite_rh."""
+    import oracle
+    from tests.test_gpu_depth_test import limit_key
+
+    app = camera.orbit_pose(0).projection(256 / 176)
+    inf = _perspective_infinite_rh(np.deg2rad(45.0), 16 / 9, 0.1)
+    for proj in (app, inf):
+        d = _depth_sweep(proj)
+        assert d.size >= 100_000
+        got = oracle.depth_limits(proj, d.reshape(1, -1))[0]
+        with np.errstate(all="ignore"):
+            want = np.array([limit_key(proj, x) for x in d], np.uint32)
+        bad = np.nonzero(got != want)[0]
+        assert bad.size == 0, f"{bad.size} limits differ, first D = {d[bad[0]]!r}: {got[bad[0]]:#x} vs {want[bad[0]]:#x}"
+        # the sweep reaches every branch: no limit, nothing passes, and real limits
+        assert (got == 0xFFFFFFFF).any() and (got == 0).any() and ((got != 0) & (got != 0xFFFFFFFF)).sum() > 50_000
+    # a row pitch larger than the row reads the same pixels
+    d = _depth_sweep(app)[:32 * 101].reshape(32, 101)
+    padded = np.full((32, 128), 0.5, np.float32)
+    padded[:, :101] = d
+    assert np.array_equal(oracle.depth_limits(app, padded[:, :101]), oracle.depth_limits(app, np.ascontiguousarray(d)))
+
+
+def test_depth_tested_back_to_front_equals_front_to_back_tiles_with_early_stop():
+    """The oracle's two rasterisers under the same per-pixel limits (a slanted plane through the model, with holes of 0 and 1):
+    back to front skipping pairs at or behind the limit = front to back per tile stopping there, within the tolerance the
+    test without limits holds them to; a limit of 0xFFFFFFFF everywhere is the frame without the test bit for bit."""
+    import oracle
+    from tests import common
+
+    w, h = 203, 137
+    g = common.small_scene(4000, 5)
+    cam = camera.orbit_pose(60)
+    mt = common.odd_transform()
+    f, pr, idx, nvis, fb_plain = common.oracle_model_frame(g, cam, w, h, mt)
+    proj = cam.projection(w / h)
+    depth = common.surface_depth(cam, w, h, [dict(kind="plane", point=(0.2, 0.0, 0.1), normal=(0.7, 0.4, 0.6))])
+    depth[40:60, 30:70] = 0.0
+    depth[90:100, 120:150] = 1.0
+    lim = oracle.depth_limits(proj, depth)
+    vis_keys = pr["key"][idx[:nvis]]
+    # the limits cut through the model: many pixels see splats on both sides
+    assert ((lim > vis_keys.min()) & (lim < vis_keys.max())).mean() > 0.3
+    fb = oracle.new_framebuffer(f)
+    oracle.rasterize(f, pr, idx, nvis, fb, lim=lim)
+    off, lst = oracle.tile_lists(f, idx, nvis, pr["rect"])
+    fb2 = oracle.new_framebuffer(f)
+    oracle.composite_tiles(f, pr, off, lst, fb2, lim=lim)
+    assert np.abs(fb - fb2).max() <= 2e-6
+    assert (np.abs(fb - fb_plain).max(-1) > 1e-3).mean() > 0.2, "the limits should hide a good part of the model"
+    zero = depth == 0.0
+    assert np.all(fb[zero][:, :3] == 0.0) and np.all(fb[zero][:, 3] == 1.0)
+    assert np.array_equal(fb[depth == 1.0], fb_plain[depth == 1.0])
+    fb3 = oracle.new_framebuffer(f)
+    oracle.rasterize(f, pr, idx, nvis, fb3, lim=np.full((h, w), 0xFFFFFFFF, np.uint32))
+    assert np.array_equal(fb3, fb_plain)
+    # render_model with limits is project -> sort -> the same back-to-front pass
+    pos, color, sh, cov = oracle.convert(g)
+    fb4 = oracle.new_framebuffer(f)
+    oracle.render_model(f, pos, color, sh, cov, fb4, lim=lim)
+    assert np.array_equal(fb4, fb)

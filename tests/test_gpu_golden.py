@@ -12,7 +12,7 @@ import pytest
 
 from tests import golden_util
 from wgpu_3dgs_viewer_app_amd.mask import MaskEvaluator, MaskOp
-from wgpu_3dgs_viewer_app_amd.viewer import Cov3dKind, GaussianDisplayMode, GaussianShDegree, MultiModelViewer, ShKind
+from wgpu_3dgs_viewer_app_amd.viewer import Cov3dKind, DepthCompare, GaussianDisplayMode, GaussianShDegree, MultiModelViewer, ShKind
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +20,8 @@ pytestmark = pytest.mark.gpu
 def test_golden_set_covers_the_feature_list():
     names = " ".join(golden_util.IDS)
     for feature in ("sh3_identity", "2models", "sh0_nosh", "pod_norm8_half", "pod_half_single", "mask_box_minus_ellipsoid", "hsv_edit",
-                    "hidden_edit", "ellipse_mode", "point_mode", "large_2models_320x240", "inria_params"):
+                    "hidden_edit", "ellipse_mode", "point_mode", "large_2models_320x240", "inria_params", "depth_plane_odd_83x51",
+                    "depth_gizmo_norm8_half_edit", "depth_2models_trs_occluder", "depth_specials", "depth_ellipse_mode"):
         assert feature in names, f"tests/golden lacks a {feature} fixture (tests/golden/make_golden.py)"
 
 
@@ -60,6 +61,9 @@ def test_hip_path_matches_float64_fixture(path, schedule):
             v.update_selection_edit_with_pod(fx.edit_pod())
         if fx.highlight is not None:
             v.update_selection_highlight(fx.highlight)
+        if fx.depth is not None:
+            v.set_depth_test(DepthCompare.Less)
+            v.update_depth_buffer(fx.depth)
         v.update_camera_with_matrices(fx.view, fx.proj, (fx.w, fx.h))
         v.update_gaussian_transform(fx.size, GaussianDisplayMode(fx.display_mode), GaussianShDegree.new(fx.sh_deg), bool(fx.no_sh0))
         order = [keys[k] for k in fx.paint_order]

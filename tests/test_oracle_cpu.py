@@ -29,6 +29,7 @@ def test_c_oracle_matches_golden_fixture(path):
 
     fx = golden_util.Fixture(path)
     fb = None
+    lim = None if fx.depth is None else oracle.depth_limits(fx.proj, fx.depth)
     for k in fx.paint_order:
         g = fx.gaussians(k)
         n = g.shape[0]
@@ -58,7 +59,7 @@ def test_c_oracle_matches_golden_fixture(path):
         idx, nvis = oracle.depth_sort(pr["key"])
         if fb is None:
             fb = oracle.new_framebuffer(f)
-        oracle.rasterize(f, pr, idx, nvis, fb)
+        oracle.rasterize(f, pr, idx, nvis, fb, lim=lim)
     fx.check_frame(fb, tight=5e-5)
 
 

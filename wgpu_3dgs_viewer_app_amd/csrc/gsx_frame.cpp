@@ -387,11 +387,13 @@ static gsx_status ensure_msd(gsx_viewer* v, Model* m, DevBuf& ws);
 // gsx_render_frame starts with a fresh one), and a model preprocessed a second time against it (a new frame whose predecessor failed or
 // was never rendered).  Nothing is ever composited against another frame's snapshot.
 static gsx_status depth_snapshot(gsx_viewer* v, const Model* m) {
-    // z_ndc = z_c / w_c < D  <=>  view depth < P23 / (D + P22) needs the third and fourth rows to depend on view z alone
+    // z_ndc = z_c / w_c < D  <=>  view depth < P23 / (D + P22) needs the third and fourth rows to depend on view z alone, and
+    // z_ndc = P23 / d - P22 to grow with d towards 1 (P23 < 0, P22 <= -1: D + P22 < 0 for every D < 1).  A reversed-Z projection
+    // (P23 > 0) turns the inequality round: the limit would show exactly the splats the test hides.
     const float* P = v->proj;  // column-major: P[col * 4 + row]
-    if (!(P[2] == 0.0f && P[6] == 0.0f && P[3] == 0.0f && P[7] == 0.0f && P[15] == 0.0f && P[11] == -1.0f))
+    if (!(P[2] == 0.0f && P[6] == 0.0f && P[3] == 0.0f && P[7] == 0.0f && P[15] == 0.0f && P[11] == -1.0f && P[14] < 0.0f && P[10] <= -1.0f))
         return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: the depth test needs a perspective projection (P20 = P21 = P30 = P31 = P33 = 0, "
-                    "P32 = -1, as perspective_rh); this one is not");
+                    "P32 = -1, P23 < 0, P22 <= -1, as perspective_rh); this one is not");
     const float* src = v->depth_dev ? v->depth_dev : v->depth_owned.as<float>();
     if (!src || !v->depth_w) return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: the depth test is on and no depth buffer was given "
                                          "(gsx_viewer_upload_depth_buffer / gsx_viewer_set_depth_buffer_device)");
