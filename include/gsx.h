@@ -116,7 +116,7 @@ typedef struct gsx_spec_params {
  * (gsx_viewer_set_band), an external framebuffer or a sharded model run on the viewer itself, one at a time. */
 typedef struct gsx_render_options {
     uint32_t progressive;        /* default 1 */
-    uint32_t first_slab_divisor; /* default 16 */
+    uint32_t first_slab_divisor; /* default 16; 1: the first slab is the whole model — one slab */
     uint32_t min_slab;           /* models with N_vis <= min_slab use one slab; default 131072 */
     uint32_t growth;             /* default 2 */
     uint32_t speculative;        /* default 1 */
@@ -130,6 +130,9 @@ typedef struct gsx_render_options {
                                   * scene; 0: such a frame projects every Gaussian in full (the reference's K1 + K3 vertex work for every
                                   * visible Gaussian).  Same pixels either way. */
 } gsx_render_options;
+/* progressive, speculative and slab_shading are read by gsx_preprocess: changing one of them sends every model back through
+ * gsx_preprocess + gsx_sort.  first_slab_divisor, min_slab and growth are read by gsx_render and may change between gsx_sort and
+ * gsx_render: the frame equals the one drawn with the final options throughout, bit for bit. */
 
 typedef struct gsx_viewer_desc {
     uint32_t abi_version; /* GSX_ABI_VERSION */

@@ -22,6 +22,25 @@ def odd_transform():
                                  scale=np.array([1.2, 0.9, 1.1], np.float32))
 
 
+def cfg5_scene():
+    """BASELINE configs[4] as the benchmark's cfg5 leg builds it: four models `a b c d` of n = CONFIGS["cfg5"][0] // 4 Gaussians (seeds
+    seed + i), a TRS each, the `0 - 1` mask (box minus ellipsoid) for `a`, the stored rectangle selection (made at orbit pose 0) and
+    the HSV edit of what it selected.  Returns a dict: n, sh, w, h, seeds, tr, mask_op, mask_shapes, rect, edit."""
+    from wgpu_3dgs_viewer_app_amd import query
+    from wgpu_3dgs_viewer_app_amd.mask import MaskOp, MaskShape, MaskShapeKind
+
+    n_total, sh, w, h, seed = scene.CONFIGS["cfg5"]
+    tr = {"a": camera.ModelTransform(pos=np.array([0.0, 0.0, 2.5], np.float32)),
+          "b": camera.ModelTransform(pos=np.array([2.0, 0.2, -1.0], np.float32), rot=np.array([0, 35, 0], np.float32)),
+          "c": camera.ModelTransform(pos=np.array([-2.5, -0.1, -0.5], np.float32), scale=np.array([0.9, 0.9, 0.9], np.float32)),
+          "d": odd_transform()}
+    shapes = [MaskShape(MaskShapeKind.Box, pos=np.array([0.0, 0.0, 2.5], np.float32), scale=np.array([3.0, 3.0, 3.0], np.float32)),
+              MaskShape(MaskShapeKind.Ellipsoid, pos=np.array([0.0, 0.0, 2.5], np.float32), scale=np.array([1.5, 1.5, 1.5], np.float32))]
+    return dict(n=n_total // 4, sh=sh, w=w, h=h, seeds={k: seed + i for i, k in enumerate(tr)}, tr=tr, mask_op=MaskOp.parse("0 - 1"),
+                mask_shapes=shapes, rect=query.QueryPod.rect((1200.0, 600.0), (2600.0, 1500.0), query.QuerySelectionOp.Set),
+                edit=query.GaussianEditPod(query.GaussianEditFlag.ENABLED, (0.5, 1.0, 1.2), 0.1, 0.2, 1.0, 0.9))
+
+
 def surface_depth(cam, w, h, surfaces):
     """A Depth32Float buffer as the gizmos write it: per pixel centre, the NDC depth (clip.z / clip.w, float64, stored as f32) of
     the nearest surface the camera's ray hits; 1.0 (cleared) where none is hit.  surfaces: dict(kind "plane", point, normal) |

@@ -337,28 +337,22 @@ def test_full_size_bit_identity_on_scenes_the_speculation_does_not_like(variant)
 
 def test_cfg5_full_size_layered_models():
     """BASELINE.json configs[4] at full size: 4 models x 6 M Gaussians (24 M), each with its own TRS, a `0 - 1` mask op on one
-    of them, a rect selection with an HSV edit on another, 3840x2160.  No oracle finishes this; the properties checked:
+    of them, a rect selection with an HSV edit on another, 3840x2160.  The CPU oracle checks this workload in
+    tests/test_gpu_fullsize_oracle.py (selection, edit records, projections, depth order, the frame); the properties checked here:
     speculated frames equal unspeculated ones bit for bit, layering order matters, the mask and the edit take effect."""
     from wgpu_3dgs_viewer_app_amd import parallel, scene
-    from wgpu_3dgs_viewer_app_amd.mask import MaskEvaluator, MaskOp, MaskShape, MaskShapeKind
+    from wgpu_3dgs_viewer_app_amd.mask import MaskEvaluator, MaskOp
 
-    n_total, sh, w, h, seed = scene.CONFIGS["cfg5"]
-    n = n_total // 4
-    tr = {"a": camera.ModelTransform(pos=np.array([0.0, 0.0, 2.5], np.float32)),
-          "b": camera.ModelTransform(pos=np.array([2.0, 0.2, -1.0], np.float32), rot=np.array([0, 35, 0], np.float32)),
-          "c": camera.ModelTransform(pos=np.array([-2.5, -0.1, -0.5], np.float32), scale=np.array([0.9, 0.9, 0.9], np.float32)),
-          "d": common.odd_transform()}
+    sc = common.cfg5_scene()
+    n, sh, w, h, tr = sc["n"], sc["sh"], sc["w"], sc["h"], sc["tr"]
     spec, plain = MultiModelViewer(), MultiModelViewer()
     plain.set_render_options(speculative=0)
-    for i, k in enumerate(tr):
-        g = scene.synthetic_gaussians(n, seed + i, sh)
+    for k in tr:
+        g = scene.synthetic_gaussians(n, sc["seeds"][k], sh)
         for v in (spec, plain):
             _load(v, k, g, tr[k])
         del g
-    shapes = [MaskShape(MaskShapeKind.Box, pos=np.array([0.0, 0.0, 2.5], np.float32), scale=np.array([3.0, 3.0, 3.0], np.float32)),
-              MaskShape(MaskShapeKind.Ellipsoid, pos=np.array([0.0, 0.0, 2.5], np.float32), scale=np.array([1.5, 1.5, 1.5], np.float32))]
-    rect = query.QueryPod.rect((1200.0, 600.0), (2600.0, 1500.0), query.QuerySelectionOp.Set)
-    edit = query.GaussianEditPod(query.GaussianEditFlag.ENABLED, (0.5, 1.0, 1.2), 0.1, 0.2, 1.0, 0.9)
+    shapes, rect, edit = sc["mask_shapes"], sc["rect"], sc["edit"]
     frames = []
     for step, pose in enumerate([10, 11, 12, 13]):
         cam = camera.orbit_pose(pose)

@@ -515,7 +515,8 @@ gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
     // a model small enough for ONE slab keeps complete per-tile lists and its full records (gsx_model_download_tile_lists).
     // (a depth-tested frame has windows: its admission already dropped the hidden records, and it projects the admitted ones in full)
     m->slab_shading = v->options.slab_shading && v->options.progressive && v->bin_mode == 1 && v->bin_fused && !m->spec_round1 && !shard_lazy &&
-                      !depth && m->n > v->options.min_slab && m->pod().sh_aos != nullptr;
+                      !depth && m->n > v->options.min_slab && v->options.first_slab_divisor > 1 && m->pod().sh_aos != nullptr;
+    // (first_slab_divisor == 1: plan_slabs makes the first slab the whole model, one slab whatever min_slab says)
     // ... and only while it pays: a scene where next to nothing saturates (translucent) has every visible record taken by some block — then
     // the streaming projection of everything (k_project: 0.67 of HBM peak) beats gathering the same records slab by slab.  Measured, lazily:
     // the last slab-shaded frame's count (Counters::n_shaded_total); tried again every 256th plain frame.
@@ -931,6 +932,14 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
     // a single-slab front model keeps complete per-tile lists (gsx_model_download_tile_lists): that frame bins by tile
     const bool lists_wanted = bounds.size() == 2 && !carry && !m->spec_round1 && !imported_windows;
     const bool blocks = progressive && v->bin_mode == 1 && !lists_wanted;
+    // gsx_preprocess left the conic / colour records (and, in rect8 mode, the `a` records) to the depth slabs' shading lists, and the
+    // frame bins by tile after all: min_slab, first_slab_divisor or growth changed between gsx_preprocess and gsx_render so that one
+    // slab remains (gsx_viewer_set_render_options does not send the model back through gsx_preprocess for them).
+    // The per-tile kernels read every visible record whole: complete them (same values as the full projection)
+    if (m->slab_shading && m->lazy && !blocks) {
+        const gsx_status cst = complete_records(v, m);
+        if (cst) return cst;
+    }
     if (!blocks || bounds.size() < 2 || bounds[1] == bounds[0]) {  // no block-table kernel ahead (or no slab at all): zero here
         HIPCHK(launch_zero_words(v->stream, zero.a, zero.na, zero.b, zero.nb));
         zero_pending = false;
