@@ -681,7 +681,11 @@ typedef enum gsx_pass {
                                   other bytes — timed apart from GSX_PASS_PROJECT so that each average is one kernel's */
     GSX_PASS_SHADE = 6,        /* conic / colour records (SH colour, cov2d) for the Gaussians a lazily shaded frame admitted or a depth slab's
                                   blocks take: the deferred half of K1's arithmetic — k_shade_quads + the frame's colour ops, wherever in
-                                  the frame they run (inside the depth sort of a speculated frame, after each slab's binning otherwise) */
+                                  the frame they run (inside the depth sort of a speculated frame, after each slab's binning otherwise).
+                                  A speculated frame without colour ops normally has no shading launch at all: rider workgroups of the depth
+                                  sort's two launches shade (GSX_SHORT_CHAIN, the default), and that time is the depth sort's.  While THIS
+                                  pass is being timed the frame keeps the serial order, so its figure still means "shading alone" — and a
+                                  loop timed with every pass bracketed is not the loop the headline rate runs */
     GSX_PASS_COUNT = 7
 } gsx_pass;
 /* enabled: 0 = off, 1 = every pass, otherwise a mask with bit (p + 1) set for each pass p to bracket with events

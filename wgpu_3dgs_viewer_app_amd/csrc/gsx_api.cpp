@@ -67,6 +67,7 @@ static gsx_status lane_create(gsx_viewer* v, gsx_viewer** out) {
     l->tile_order_on = v->tile_order_on;
     l->bucket_sort = v->bucket_sort;
     l->bin_fused = v->bin_fused;
+    l->short_chain = v->short_chain;
     l->sorted_records = v->sorted_records;
     l->tile_profile = v->tile_profile;
     // a stream that does not share its hardware queue with the viewer's or another lane's: streams that do are kept (parked)
@@ -267,6 +268,7 @@ gsx_status gsx_viewer_create(const gsx_viewer_desc* desc, gsx_viewer** out) {
     if (const char* e = getenv("GSX_TILE_ORDER")) v->tile_order_on = atoi(e) != 0;
     if (const char* e = getenv("GSX_BUCKET_SORT")) v->bucket_sort = atoi(e) != 0;
     if (const char* e = getenv("GSX_BIN_FUSED")) v->bin_fused = atoi(e) != 0;
+    if (const char* e = getenv("GSX_SHORT_CHAIN")) v->short_chain = atoi(e) != 0;
     if (const char* e = getenv("GSX_BIN_BIG_RECT")) block_bin_set_big_rect((uint32_t)atoi(e));   // tests / tuning
     if (const char* e = getenv("GSX_BIN_BIG_SLAB")) block_bin_set_big_slab((uint32_t)atoi(e));   // tests: smaller slabs take the eight-per-lane tiles
     if (const char* e = getenv("GSX_BUCKET_CAP")) bucket_sort_set_cap((uint32_t)atoi(e));   // tests: buckets above this take the global-memory path

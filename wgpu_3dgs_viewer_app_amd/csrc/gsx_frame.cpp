@@ -656,6 +656,27 @@ gsx_status shade_admitted(gsx_viewer* v, Model* m, const LateProjection& late) {
     return GSX_OK;
 }
 
+// Shading of a speculated frame's admitted records as riders of the bucket sort's two launches (shade_quads.h) instead of a launch
+// in front of them: nothing before the compositor reads the conic / colour records.  Everything else keeps shade_admitted: frames
+// with colour ops (they run behind the record's shading, in a launch of their own), a shade pass that is being timed (its figure
+// means "shading alone"), GSX_VALIDATE, pods without the quad body, the ballot-matching sort.
+static bool shading_rides(gsx_viewer* v, Model* m) {
+    return v->short_chain && m->spec_round1 && m->lazy && !v->validate && !((v->timing >> GSX_PASS_SHADE) & 1u) && !m->frame_edits &&
+           !m->frame_highlight && shade_quads_applies(m->pod()) && bucket_sort_carries_riders();
+}
+static ShadeRide shade_ride(Model* m, const LateProjection& late) {
+    ShadeRide r{};
+    r.f = m->fc;
+    r.pod = m->pod();
+    r.pod.mask = m->last_pod_mask;
+    r.rec = m->proj_rec();
+    r.pairs = late.pairs;
+    r.d_n = late.d_n;
+    r.skip = late.shaded;
+    r.write_a = late.write_a ? 1u : 0u;
+    return r;
+}
+
 // (A single-launch depth sort for the ~0.3 M pairs of a speculated frame — one persistent grid, device-wide barriers between
 // the digit passes — was built and measured this round: 146 us against 66 us for one launch per digit at 0.3 M pairs, 499
 // against 95 at 1 M.  Seven grid barriers plus the per-tile offset lookups cost more than the five kernel boundaries they
@@ -731,14 +752,17 @@ gsx_status do_sort(gsx_viewer* v, Model* m, bool force_full) {
                                                      m->visible_count_pending ? m->block_vis.as<uint32_t>() : nullptr, &dc->n_visible));
                 }
                 m->visible_count_pending = false;
-                if (m->lazy) {  // the projection pass was geometry only: shade what it admitted
-                    gsx_status sst = shade_admitted(v, m, LateProjection{m->adm_pairs.as<uint2>(), &dc->n_sorted, nullptr, m->rect8_active});
+                const LateProjection late{m->adm_pairs.as<uint2>(), &dc->n_sorted, nullptr, m->rect8_active};
+                const bool rides = bucket && shading_rides(v, m);   // (the sort's launches shade beside their own work)
+                if (m->lazy && !rides) {  // the projection pass was geometry only: shade what it admitted
+                    gsx_status sst = shade_admitted(v, m, late);
                     if (sst) return sst;
                 }
                 RadixBuffers rb{nullptr, nullptr, m->adm_pairs.as<uint2>(), m->sk_out.as<uint32_t>(), m->sv_out.as<uint32_t>(),
                                 m->dp_a.as<uint2>(), m->dp_b.as<uint2>(), m->sort_ws.as<uint32_t>()};
                 if (bucket) {
-                    HIPCHK(launch_bucket_sort(v->stream, rb, n, &dc->n_sorted, false, m->msd_ws.as<uint32_t>(), seq, true));
+                    const ShadeRide ride = rides ? shade_ride(m, late) : ShadeRide{};
+                    HIPCHK(launch_bucket_sort(v->stream, rb, n, &dc->n_sorted, false, m->msd_ws.as<uint32_t>(), seq, true, rides ? &ride : nullptr));
                     launches_sort = 2;
                 } else {
                     HIPCHK(launch_radix_sort(v->stream, rb, n, &dc->n_sorted, 32, false));
@@ -1257,14 +1281,17 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
                                 row_words, pyr2, &dc->spec_need,
                                 m->adm_ballots2.as<unsigned long long>(), m->adm_counts2.as<uint32_t>(), &dc->n_sorted2,
                                 m->adm_pairs.as<uint2>(), bucket2 ? m->msd_ws2.as<uint32_t>() : nullptr, seq2));
-            if (m->lazy) {  // the repair round needs records the lazy projection did not shade
-                gsx_status sst = shade_admitted(v, m, LateProjection{m->adm_pairs.as<uint2>(), &dc->n_sorted2, m->adm_ballots.as<unsigned long long>(), m->rect8_active});
+            const LateProjection late2{m->adm_pairs.as<uint2>(), &dc->n_sorted2, m->adm_ballots.as<unsigned long long>(), m->rect8_active};
+            const bool rides2 = bucket2 && shading_rides(v, m);
+            if (m->lazy && !rides2) {  // the repair round needs records the lazy projection did not shade
+                gsx_status sst = shade_admitted(v, m, late2);
                 if (sst) return sst;
             }
             RadixBuffers rb{nullptr, nullptr, m->adm_pairs.as<uint2>(), m->sk_out.as<uint32_t>(), m->sv_out.as<uint32_t>(),
                             m->dp_a.as<uint2>(), m->dp_b.as<uint2>(), m->sort_ws.as<uint32_t>()};
             if (bucket2) {
-                HIPCHK(launch_bucket_sort(v->stream, rb, n, &dc->n_sorted2, false, m->msd_ws2.as<uint32_t>(), seq2, true));
+                const ShadeRide ride2 = rides2 ? shade_ride(m, late2) : ShadeRide{};
+                HIPCHK(launch_bucket_sort(v->stream, rb, n, &dc->n_sorted2, false, m->msd_ws2.as<uint32_t>(), seq2, true, rides2 ? &ride2 : nullptr));
             } else {
                 HIPCHK(launch_radix_sort(v->stream, rb, n, &dc->n_sorted2, 32, false));
             }

@@ -226,6 +226,20 @@ struct LateProjection {
     const unsigned long long* shaded;   // nullable: ballots of the records to skip (shaded already)
     bool write_a = false;               // the projection left no `a` record (Records::rect8 mode): k_shade writes it as well
 };
+// The same shading as rider workgroups of another kernel's launch (shade_quads.h; launch_bucket_sort): what such a launch is given.
+struct ShadeRide {
+    FrameConsts f;
+    PodPlanes pod;
+    Records rec;
+    const uint2* pairs;                 // (key, index): the compaction's output
+    const uint32_t* d_n;                // number of pairs, on the device
+    const unsigned long long* skip;     // nullable: ballots of the records that are shaded already
+    uint32_t write_a;
+    uint32_t own;                       // the carrier's own workgroups (set by the launcher)
+    uint32_t lo, hi;                    // this launch shades pairs [*d_n * lo / 256, *d_n * hi / 256) (set by the launcher)
+};
+// does the four-lanes-to-a-record body exist for this pod?  (Sh None models and pods without the record copy take k_shade)
+inline bool shade_quads_applies(const PodPlanes& pod) { return pod.sh_kind != GSX_SH_NONE && pod.sh_aos != nullptr && pod.aos_geo != 0u; }
 // d_block_visible: one count per 256-Gaussian workgroup (project_blocks(n) entries); launch_sum_counts
 // reduces them into *d_n_visible.
 hipError_t launch_project(hipStream_t s, const FrameConsts& f, uint32_t n, const PodPlanes& pod, const Records& rec,
@@ -365,8 +379,11 @@ hipError_t msd_workspace_init(hipStream_t s, uint32_t* ws, size_t words);
 // kernel that wrote buf.pairs_src (launch_admit_compact with the same ws and seq); otherwise k_msd_hist runs first.
 // buf: pairs_src, or keys_src (+ vals_src / iota_values); pairs_a, pairs_b scratch; keys_out / vals_out the sorted result;
 // workspace = the radix workspace (ticket + status words of the partition pass).
+// ride (nullable; only where bucket_sort_carries_riders() and buf.pairs_src): both launches carry rider workgroups that shade the admitted
+// records ride->pairs[0 .. *ride->d_n) between them (shade_quads.h) — the caller then enqueues no shading kernel of its own.
+bool bucket_sort_carries_riders();
 hipError_t launch_bucket_sort(hipStream_t s, const RadixBuffers& buf, uint32_t n, uint32_t* d_n, bool iota_values, uint32_t* msd_ws, uint32_t seq,
-                              bool hist_done);
+                              bool hist_done, const ShadeRide* ride = nullptr);
 // k_admit_compact (kernels_admit.hip): the admitted (key, index) pairs of a projection pass in index order from its ballots — one
 // launch (decoupled look-back over 65536-Gaussian tiles) instead of k_admit_scan + k_admit_scatter256 — and, msd_ws != nullptr, the fine
 // histogram + key range of sort `seq`.  *d_total = pairs; block_visible (nullable): the projection's per-workgroup visible counts are

@@ -469,6 +469,7 @@ struct gsx_viewer {
     uint32_t pass_launches[GSX_PASS_COUNT]{};
     DevBuf tile_prof;                    // GSX_TILE_PROFILE: what every tile of the LAST block-compositor launch of a frame's first slab cost
     bool tile_profile = false;
+    bool short_chain = true;             // GSX_SHORT_CHAIN=0: a speculated frame's shading is a launch of its own in front of the depth sort (A/B)
     bool bin_fused = true;               // GSX_BIN_FUSED=0: block binning as count + scan + emit + histogram launches (A/B)
     bool bucket_sort = true;             // GSX_BUCKET_SORT=0: speculated frames, repair rounds and imported bands keep the five-launch LSD depth sort (A/B)
     bool tile_order_on = true;           // GSX_TILE_ORDER=0: the block compositor takes its tiles in index order (A/B)

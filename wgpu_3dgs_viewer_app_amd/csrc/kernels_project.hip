@@ -14,6 +14,7 @@
 #include "edit_math.h"
 #include "gsx_internal.h"
 #include "project_math.h"
+#include "shade_quads.h"
 #include "window_scan.h"
 
 namespace gsx {
@@ -98,15 +99,9 @@ __device__ inline float ddot3(float a0, float a1, float a2, float b0, float b1, 
 __device__ inline uint32_t pack_h2(float a, float b) {
     return (uint32_t)__half_as_ushort(__float2half_rn(a)) | ((uint32_t)__half_as_ushort(__float2half_rn(b)) << 16);
 }
-__device__ inline float h_lo(uint32_t u) { return __half2float(__ushort_as_half((unsigned short)(u & 0xFFFFu))); }
-__device__ inline float h_hi(uint32_t u) { return __half2float(__ushort_as_half((unsigned short)(u >> 16))); }
 __device__ inline uint32_t q_snorm8(float v) {
     float c = fminf(fmaxf(v, -1.0f), 1.0f);
     return (uint32_t)(int)floorf(c * 127.0f + 0.5f) & 0xFFu;
-}
-__device__ inline float dq_snorm8(uint32_t word, int byte) {
-    int q = (int)(signed char)((word >> (8 * byte)) & 0xFFu);
-    return fmaxf((float)q * (1.0f / 127.0f), -1.0f);
 }
 
 __device__ inline void store_sh(const PodPlanes& pod, uint64_t model_n, uint64_t i, const float* s45) {
@@ -620,98 +615,13 @@ __global__ __launch_bounds__(256) void k_shade(const FrameConsts f, const uint32
     }
 }
 
-// k_shade for the 256-byte record copy (f32 SH + f32 covariance), four lanes to a record.  One record per lane meant sixteen 16-byte
-// loads 256 bytes apart from lane to lane: every load instruction touched 64 different lines, a wave's working set was 16 KB of a
-// 32 KB L1 shared by eight waves, and the sectors were fetched again and again (75 MB of records in 41 us: 1.8 TB/s).  Here the
-// four lanes of a quad load the record side by side — lane s takes words s, s + 4, s + 8, s + 12: every instruction reads whole
-// 64-byte sectors, sixteen sectors a wave — and hand each other their words by quad broadcasts (v_mov_dpp: no LDS, no barrier).
-// All four lanes then run the SAME arithmetic on the same sixteen words — the code of k_shade, value for value — and lane 0 stores.
-__device__ __forceinline__ uint32_t quad_bcast(uint32_t v, const int s) {
-    // quad_perm [s, s, s, s]
-    switch (s) {
-        case 0: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x00, 0xF, 0xF, false);
-        case 1: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x55, 0xF, 0xF, false);
-        case 2: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xAA, 0xF, 0xF, false);
-        default: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xFF, 0xF, 0xF, false);
-    }
-}
-// the SH words of a shade record (plane order, as the pod stores them) -> the stream's floats: what load_shade<.., AOS = true> feeds
-template <int DEG, int SHK>
-__device__ __forceinline__ void feed_record_words(ShStream<DEG>& st, const uint4* w) {
-    constexpr int kFloats = ShNeed<DEG>::floats;
-    if (SHK == GSX_SH_SINGLE) {
-#pragma unroll
-        for (int p = 0; p < ShNeed<DEG>::planes4; ++p) {
-            st.feed(4 * p, __uint_as_float(w[p].x)); st.feed(4 * p + 1, __uint_as_float(w[p].y));
-            st.feed(4 * p + 2, __uint_as_float(w[p].z)); st.feed(4 * p + 3, __uint_as_float(w[p].w));
-        }
-        if (DEG == 3) st.feed(44, __uint_as_float(w[11].x));
-    } else if (SHK == GSX_SH_HALF) {
-        constexpr int kP = (kFloats + 7) / 8;
-#pragma unroll
-        for (int p = 0; p < kP; ++p) {
-            st.feed(8 * p, h_lo(w[p].x)); st.feed(8 * p + 1, h_hi(w[p].x)); st.feed(8 * p + 2, h_lo(w[p].y)); st.feed(8 * p + 3, h_hi(w[p].y));
-            st.feed(8 * p + 4, h_lo(w[p].z)); st.feed(8 * p + 5, h_hi(w[p].z)); st.feed(8 * p + 6, h_lo(w[p].w)); st.feed(8 * p + 7, h_hi(w[p].w));
-        }
-    } else {
-        constexpr int kP = (kFloats + 15) / 16;
-#pragma unroll
-        for (int p = 0; p < kP; ++p) {
-            const uint32_t q[4] = {w[p].x, w[p].y, w[p].z, w[p].w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int bb = 0; bb < 4; ++bb) st.feed(16 * p + 4 * k + bb, dq_snorm8(q[k], bb));
-        }
-    }
-}
-
-// Four lanes to a shade record, every pod kind (round 5; f32 pods since round 4): the quad loads the record side by side — STRIDE / 4
-// coalesced 16-byte loads per lane, whole 64-byte sectors — and every lane gets every word by quad broadcasts.
+// Four lanes to a shade record (shade_quads.h): the stand-alone kernel of the serial order — the same body rides in the depth sort's
+// launches on speculated frames (kernels_sort.hip).
 template <int DEG, int SHK, int COVK>
 __global__ __launch_bounds__(256) void k_shade_quads(const FrameConsts f, const PodPlanes pod, const Records rec,
                                                       const uint2* __restrict__ pairs, const uint32_t* __restrict__ d_n,
                                                       const unsigned long long* __restrict__ skip, const int write_a) {
-    constexpr uint32_t kStride = SHK == GSX_SH_SINGLE ? 16u : (SHK == GSX_SH_HALF ? (COVK == GSX_COV3D_SINGLE ? 12u : 8u) : 8u);
-    constexpr uint32_t kGeo = SHK == GSX_SH_SINGLE ? 12u : (SHK == GSX_SH_HALF ? 6u : 3u);
-    constexpr int kLoads = (int)(kStride / 4u);
-    const uint32_t count = *d_n;
-    const uint32_t sub = threadIdx.x & 3u;
-    for (uint32_t j = (blockIdx.x * 256u + threadIdx.x) >> 2; j < count; j += gridDim.x * 64u) {  // (the quad's four lanes share j)
-        const uint32_t i = pairs[j].y;
-        if (skip && ((skip[i >> 6] >> (i & 63u)) & 1ull)) continue;
-        uint4 mine[kLoads];
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k) mine[k] = pod.sh_aos[(uint64_t)i * kStride + sub + 4u * (uint32_t)k];
-        uint4 w[kStride];   // the record's words, in every lane of the quad
-#pragma unroll
-        for (int k = 0; k < kLoads; ++k)
-#pragma unroll
-            for (int sl = 0; sl < 4; ++sl)
-                w[sl + 4 * k] = make_uint4(quad_bcast(mine[k].x, sl), quad_bcast(mine[k].y, sl), quad_bcast(mine[k].z, sl), quad_bcast(mine[k].w, sl));
-        const float4 pc = make_float4(__uint_as_float(w[kGeo].x), __uint_as_float(w[kGeo].y), __uint_as_float(w[kGeo].z), __uint_as_float(w[kGeo].w));
-        ViewClip vc;
-        Splat2D sp{};
-        if (!pm_view_cull(f, pc.x, pc.y, pc.z, vc)) continue;  // cannot happen: it is visible
-        if (COVK == GSX_COV3D_SINGLE) {
-            if (!pm_cov2d_rect(f, vc, __uint_as_float(w[kGeo + 1].x), __uint_as_float(w[kGeo + 1].y), __uint_as_float(w[kGeo + 1].z), __uint_as_float(w[kGeo + 1].w),
-                               __uint_as_float(w[kGeo + 2].x), __uint_as_float(w[kGeo + 2].y), sp))
-                continue;
-        } else {
-            const uint4 a = w[kGeo + 1];
-            if (!pm_cov2d_rect(f, vc, h_lo(a.x), h_hi(a.x), h_lo(a.y), h_hi(a.y), h_lo(a.z), h_hi(a.z), sp)) continue;
-        }
-        ShStream<DEG> st;   // (load_shade<DEG, SHK, true>, fed from registers)
-        st.begin(f, pc.x, pc.y, pc.z, __float_as_uint(pc.w));
-        feed_record_words<DEG, SHK>(st, w);
-        float r, g, b;
-        st.finish(r, g, b);
-        if (sub == 0u) {
-            if (write_a) rec.a[i] = make_float4(sp.mx, sp.my, __uint_as_float(sp.rx), __uint_as_float(sp.ry));
-            rec.b[i] = make_float4(sp.con_a, sp.con_b, sp.con_c, (float)(__float_as_uint(pc.w) >> 24) * (1.0f / 255.0f));
-            rec.c[i] = make_float4(r, g, b, vc.d);
-        }
-    }
+    shade_quads<DEG, SHK, COVK>(f, pod, rec, pairs, skip, write_a, (blockIdx.x * 256u + threadIdx.x) >> 2, *d_n, gridDim.x * 64u);
 }
 
 // N_vis = sum of the per-workgroup counts (single workgroup; <= 40 K entries at 10 M Gaussians)
@@ -821,7 +731,7 @@ hipError_t launch_shade(hipStream_t s, const FrameConsts& f, uint32_t n, const P
                         const LateProjection& late) {
     if (n == 0) return hipSuccess;
     // (four lanes to a record: + 3 % on the frame against one lane per record, same values — rounds 4 and 5, profiles/r05_*; the A/B switch is gone)
-    if (pod.sh_kind != GSX_SH_NONE && pod.sh_aos != nullptr && pod.aos_geo != 0u) {
+    if (shade_quads_applies(pod)) {
         const dim3 grid(8192), block(256);   // 0.5 M quads stride over the admitted records
 #define GSX_QUADS(SHK, COVK)                                                                                                                      \
     switch ((int)f.sh_deg) {                                                                                                                      \

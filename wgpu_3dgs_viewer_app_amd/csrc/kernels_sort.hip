@@ -27,6 +27,7 @@
 #include <cstdlib>
 
 #include "gsx_internal.h"
+#include "shade_quads.h"
 
 namespace gsx {
 
@@ -219,7 +220,8 @@ __device__ __forceinline__ void radix_sweep_tiles(const uint32_t* __restrict__ k
                                                           uint32_t* __restrict__ s_gbase /* LDS: 256 */, uint32_t* __restrict__ s_wtot /* LDS: kSweepWaves */,
                                                           uint32_t* __restrict__ s_misc /* LDS: [0] tile, [1] last, [2] tile_n */,
                                                           uint8_t* __restrict__ s_map = nullptr /* MSD, LDS: kMsdFine */, uint32_t* __restrict__ s_span = nullptr /* MSD, LDS: 512 */,
-                                                          const MsdMap msd_map = MsdMap{0u, 0u, 0u}) {
+                                                          const MsdMap msd_map = MsdMap{0u, 0u, 0u},
+                                                          const uint32_t own_grid = 0u /* the launch carries riders behind this many workgroups (0: none) */) {
     constexpr int kTile = kSweepThreads * ROUNDS;  // elements per tile
     auto digit_of = [&](uint32_t k) -> uint32_t {
         if constexpr (MSD) return s_map[msd_fine(k, msd_map)];
@@ -232,7 +234,7 @@ __device__ __forceinline__ void radix_sweep_tiles(const uint32_t* __restrict__ k
     const uint32_t n_tiles = (n + kTile - 1) / kTile;
     // the launch is sized by an upper bound; with a device-side n only min(grid, n_tiles) workgroups have anything to
     // do — the others leave without touching the ticket (768 same-address atomics alone cost ~9 us)
-    const uint32_t participants = min(gridDim.x, n_tiles);
+    const uint32_t participants = min(own_grid ? own_grid : gridDim.x, n_tiles);
     if (blockIdx.x >= participants) return;
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const bool dig = tid < 256u;  // this thread also owns digit `tid` (the scans below run over the first four waves; the others add 0)
@@ -758,12 +760,22 @@ __global__ __launch_bounds__(kRadixThreads) void k_msd_hist(const uint32_t* __re
 }
 
 // the partition pass: k_radix_onesweep with the bucket table as its digit
-template <int IN, bool LANE_ORDERED>
+// RIDE (shade_quads.h): workgroups behind the first ride.own shade a slice of the admitted records instead — they share nothing with the
+// sweep (no ticket, no status word, no LDS) and leave before its first barrier; NoRide: the kernel as it always was
+template <int IN, bool LANE_ORDERED, class RIDE = NoRide>
 __global__ __launch_bounds__(kSweepThreads) void k_msd_sweep(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
                                                               const uint2* __restrict__ pairs_in, uint2* __restrict__ pairs_out, uint32_t n_cap,
                                                               const uint32_t* __restrict__ d_n, uint32_t* __restrict__ fine, const uint32_t* __restrict__ hint,
                                                               uint32_t* __restrict__ ticket, u64* __restrict__ status, uint32_t epoch,
-                                                              uint2* __restrict__ ranges_out, uint32_t small_n) {
+                                                              uint2* __restrict__ ranges_out, uint32_t small_n, const typename RIDE::Args ride) {
+    uint32_t own = 0u;
+    if constexpr (RIDE::active) {
+        if (blockIdx.x >= ride.own) {  // (uniform)
+            RIDE::run(ride);
+            return;
+        }
+        own = ride.own;
+    }
     __shared__ uint2 s_pairs[kRadixTile];
     __shared__ uint32_t cnt[kSweepWaves][256];
     __shared__ uint32_t s_gbase[256];
@@ -780,11 +792,11 @@ __global__ __launch_bounds__(kSweepThreads) void k_msd_sweep(const uint32_t* __r
     if (n <= small_n)
         radix_sweep_tiles<IN, 0, LANE_ORDERED, false, kRadixRoundsSmall, true>(keys_in, vals_in, pairs_in, nullptr, nullptr, pairs_out, n, 0, 255u, fine, ticket, status,
                                                                                 epoch, fine, kMsdFine, nullptr, ranges_out, nullptr, nullptr, nullptr, nullptr, s_pairs, cnt, s_gbase,
-                                                                                s_wtot, s_misc, s_map, s_span, map);
+                                                                                s_wtot, s_misc, s_map, s_span, map, own);
     else
         radix_sweep_tiles<IN, 0, LANE_ORDERED, false, kRadixRounds, true>(keys_in, vals_in, pairs_in, nullptr, nullptr, pairs_out, n, 0, 255u, fine, ticket, status, epoch,
                                                                            fine, kMsdFine, nullptr, ranges_out, nullptr, nullptr, nullptr, nullptr, s_pairs, cnt, s_gbase, s_wtot, s_misc,
-                                                                           s_map, s_span, map);
+                                                                           s_map, s_span, map, own);
 }
 
 // ---- every bucket sorted on the key bits that vary inside it: stable LSD passes of up to 8 bits, per-wave counters ----
@@ -851,10 +863,19 @@ __device__ __forceinline__ void bucket_offsets(uint32_t (*__restrict__ cnt)[256]
     }
 }
 
-template <bool LANE_ORDERED>
+template <bool LANE_ORDERED, class RIDE = NoRide>
 __global__ __launch_bounds__(kSweepThreads) void k_bucket_sort(uint2* src /* the partitioned pairs (large buckets ping-pong between src and tmp) */, uint2* tmp,
                                                                 uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out, const uint2* __restrict__ ranges,
-                                                                uint32_t cap, uint32_t* __restrict__ hint, const uint32_t* __restrict__ acc) {
+                                                                uint32_t cap, uint32_t* __restrict__ hint, const uint32_t* __restrict__ acc,
+                                                                const typename RIDE::Args ride) {
+    uint32_t own = gridDim.x;
+    if constexpr (RIDE::active) {  // riders (k_msd_sweep): the other slice of the admitted records
+        if (blockIdx.x >= ride.own) {  // (uniform)
+            RIDE::run(ride);
+            return;
+        }
+        own = ride.own;
+    }
     uint2* const src_rw = src;
     // the last kernel of a sort: the union of the key ranges seen so far becomes the range the NEXT sort's kernels map keys by (they all
     // run behind this kernel: the snapshot is stable while they read it)
@@ -868,7 +889,7 @@ __global__ __launch_bounds__(kSweepThreads) void k_bucket_sort(uint2* src /* the
     __shared__ uint32_t s_mn[kSweepWaves], s_mx[kSweepWaves];
     __shared__ uint32_t s_base[256];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    for (uint32_t b = blockIdx.x; b < kMsdBuckets; b += gridDim.x) {
+    for (uint32_t b = blockIdx.x; b < kMsdBuckets; b += own) {
         const uint2 range = ranges[b];
         const uint32_t start = range.x, m = range.y - range.x;
         if (m == 0) continue;  // (uniform)
@@ -1069,8 +1090,19 @@ hipError_t msd_workspace_init(hipStream_t s, uint32_t* ws, size_t words) {
     return gsx::op::MemcpyAsync(ws + kMsdCells, cells, sizeof cells, hipMemcpyHostToDevice, s);
 }
 
+// Rider workgroups per carrier launch, and the share (of 256) of the admitted records that the partition pass's riders take: the
+// sweep is the longer carrier, and behind it stands a launch whose own 256 workgroups are all at work.  Riders are 512 threads
+// with the carrier's LDS block — two to a CU — so a launch holds 64 K quads at a time however many workgroups it has.
+#ifndef GSX_RIDE_WGS
+#define GSX_RIDE_WGS 768u
+#endif
+#ifndef GSX_RIDE_SPLIT
+#define GSX_RIDE_SPLIT 150u
+#endif
+bool bucket_sort_carries_riders() { return use_lane_ordered(); }
+
 hipError_t launch_bucket_sort(hipStream_t s, const RadixBuffers& buf, uint32_t n, uint32_t* d_n, bool iota_values, uint32_t* msd_ws, uint32_t seq,
-                              bool hist_done) {
+                              bool hist_done, const ShadeRide* ride) {
     if (n == 0) return hipSuccess;
     const MsdCells mc = msd_cells(msd_ws, seq);
     uint32_t* ticket = buf.workspace + 1024;
@@ -1088,7 +1120,27 @@ hipError_t launch_bucket_sort(hipStream_t s, const RadixBuffers& buf, uint32_t n
     const uint32_t grid = std::min<uint32_t>(grid_limit, tiles);
     const bool lane_ordered = use_lane_ordered();
     const uint32_t epoch = next_sort_epoch();
-#define GSX_MSD_ARGS dim3(grid), dim3(kSweepThreads), 0, s, buf.keys_src, buf.vals_src, buf.pairs_src, buf.pairs_a, n, d_n, mc.fine, mc.hint, ticket, status, epoch, mc.ranges, radix_small_n()
+    const uint32_t cap_dbg = g_bucket_cap.load(std::memory_order_relaxed);
+    const uint32_t cap = cap_dbg ? std::min(cap_dbg, kBucketCap) : kBucketCap;
+    if (ride) {  // the caller asked bucket_sort_carries_riders(): the lane-ordered instantiations, pairs in
+        if (!lane_ordered || !buf.pairs_src) return hipErrorInvalidValue;
+        ShadeRide r = *ride;
+        shade_rider_dispatch(r.f, r.pod, [&](auto rider) {
+            using R = decltype(rider);
+            r.own = grid;
+            r.lo = 0u;
+            r.hi = GSX_RIDE_SPLIT;
+            GSX_LAUNCH((k_msd_sweep<2, true, R>), dim3(grid + GSX_RIDE_WGS), dim3(kSweepThreads), 0, s, buf.keys_src, buf.vals_src, buf.pairs_src, buf.pairs_a, n, d_n, mc.fine,
+                       mc.hint, ticket, status, epoch, mc.ranges, radix_small_n(), r);
+            r.own = kMsdBuckets;
+            r.lo = GSX_RIDE_SPLIT;
+            r.hi = 256u;
+            GSX_LAUNCH((k_bucket_sort<true, R>), dim3(kMsdBuckets + GSX_RIDE_WGS), dim3(kSweepThreads), 0, s, buf.pairs_a, buf.pairs_b, buf.keys_out, buf.vals_out, mc.ranges, cap,
+                       const_cast<uint32_t*>(mc.hint), mc.acc, r);
+        });
+        return hipGetLastError();
+    }
+#define GSX_MSD_ARGS dim3(grid), dim3(kSweepThreads), 0, s, buf.keys_src, buf.vals_src, buf.pairs_src, buf.pairs_a, n, d_n, mc.fine, mc.hint, ticket, status, epoch, mc.ranges, radix_small_n(), 0u
     if (buf.pairs_src) {
         if (lane_ordered) GSX_LAUNCH((k_msd_sweep<2, true>), GSX_MSD_ARGS);
         else GSX_LAUNCH((k_msd_sweep<2, false>), GSX_MSD_ARGS);
@@ -1100,12 +1152,10 @@ hipError_t launch_bucket_sort(hipStream_t s, const RadixBuffers& buf, uint32_t n
         else GSX_LAUNCH((k_msd_sweep<1, false>), GSX_MSD_ARGS);
     }
 #undef GSX_MSD_ARGS
-    const uint32_t cap_dbg = g_bucket_cap.load(std::memory_order_relaxed);
-    const uint32_t cap = cap_dbg ? std::min(cap_dbg, kBucketCap) : kBucketCap;
     if (lane_ordered)
-        GSX_LAUNCH((k_bucket_sort<true>), dim3(kMsdBuckets), dim3(kSweepThreads), 0, s, buf.pairs_a, buf.pairs_b, buf.keys_out, buf.vals_out, mc.ranges, cap, const_cast<uint32_t*>(mc.hint), mc.acc);
+        GSX_LAUNCH((k_bucket_sort<true>), dim3(kMsdBuckets), dim3(kSweepThreads), 0, s, buf.pairs_a, buf.pairs_b, buf.keys_out, buf.vals_out, mc.ranges, cap, const_cast<uint32_t*>(mc.hint), mc.acc, 0u);
     else
-        GSX_LAUNCH((k_bucket_sort<false>), dim3(kMsdBuckets), dim3(kSweepThreads), 0, s, buf.pairs_a, buf.pairs_b, buf.keys_out, buf.vals_out, mc.ranges, cap, const_cast<uint32_t*>(mc.hint), mc.acc);
+        GSX_LAUNCH((k_bucket_sort<false>), dim3(kMsdBuckets), dim3(kSweepThreads), 0, s, buf.pairs_a, buf.pairs_b, buf.keys_out, buf.vals_out, mc.ranges, cap, const_cast<uint32_t*>(mc.hint), mc.acc, 0u);
     return hipGetLastError();
 }
 
