@@ -274,16 +274,19 @@ def query_flags(proj: dict, query_pod, texture=None) -> np.ndarray:
     return flags
 
 
-def query_hits(frame: Frame, proj: dict, coords) -> np.ndarray:
+def query_hits(frame: Frame, proj: dict, coords, capacity: int = 65536, with_count: bool = False):
+    """Hit results sorted by (depth, index); at most ``capacity`` are kept (the first in index order).
+    with_count: returns (hits, total), total = the unsaturated number of hits."""
     from wgpu_3dgs_viewer_app_amd.query import HIT_DTYPE
 
     n = proj["key"].shape[0]
-    out = np.zeros(65536, HIT_DTYPE)
+    out = np.zeros(max(int(capacity), 1), HIT_DTYPE)
     fn = lib().gsxo_query_hits
     fn.restype = C.c_uint64
     cnt = fn(C.byref(frame), C.c_uint64(n), _up(proj["key"]), _fp(proj["mean2d"]), _fp(proj["conic_opacity"]), _fp(_f32(coords, 2)),
-             C.c_void_p(out.ctypes.data), C.c_uint64(out.size))
-    return out[: min(int(cnt), out.size)].copy()
+             C.c_void_p(out.ctypes.data), C.c_uint64(int(capacity)))
+    hits = out[: min(int(cnt), int(capacity))].copy()
+    return (hits, int(cnt)) if with_count else hits
 
 
 def selection_op(op: int, flags: np.ndarray, selection: np.ndarray) -> np.ndarray:

@@ -255,6 +255,108 @@ def project(view, proj, width, height, pos, color_u32, sh, cov3d, m_pos=(0, 0, 0
                 opacity=opacity, rgb=rgb, pix_aabb=np.stack([x0, y0, x1, y1], 1))
 
 
+# Queries (spec §7).  A query's verdict is a discontinuous function of the projected mean (rect, brush, texture) or of q and alpha
+# (hit): an implementation in another precision may decide a Gaussian that sits within its own rounding of the cut the other way.
+# The bands below are 8 x the LARGEST difference measured between the float32 C oracle (oracle.project / oracle.query_hits) and this
+# file over every scene the query tests use (tests/test_query_cpu.py::test_tolerances_cover_the_f32_projection measures them again and
+# asserts the factor), Single/Single and Norm8/Half pods, Splat / Ellipse / Point:
+#   |mean2d_f32 - mean2d_f64|, visible Gaussians, 176 x 128:   3.5e-5 px (identity transform), 5.4e-5 px (common.odd_transform()); Point mode 2.8e-5
+#   |q_f32 - q_f64| / k^2, Gaussians with q <= 2 k^2 at the hit coordinates:   up to 3.0e-5 (1.0e-5 .. 3.0e-5 per scene)
+#   |alpha_f32 - alpha_f64|, the hits both sides return there (alpha from oracle.query_hits itself):   up to 4.4e-6 at 176 x 128, 7.9e-6 in the 64 x 48 scene of splats enlarged 400 x
+# The mean's error grows with the viewport (it is a few ulps of a pixel coordinate): QUERY_TOL is stated for viewports up to 176 px
+# wide, scale it by width / 176 above that.
+QUERY_TOL = 4.4e-4          # px
+QUERY_TOL_Q = 2.4e-4        # fraction of k^2
+QUERY_TOL_ALPHA = 6.4e-5    # absolute
+
+
+def _query_f32(pod):
+    """(kind, p0, p1, radius) of a query.QueryPod as the library receives them: gsx_query holds float32."""
+    f = lambda v: float(np.float32(v))  # noqa: E731
+    return int(pod.kind), (f(pod.p0[0]), f(pod.p0[1])), (f(pod.p1[0]), f(pod.p1[1])), f(pod.radius)
+
+
+def query_flags(p64, pod, texture=None, tol=QUERY_TOL):
+    """spec §7 "Query", rect / brush / texture, in float64 on the dict ``project`` returns.  pod: a query.QueryPod (kind 2 Rect |
+    3 Brush | 4 Texture); texture: uint8 [H, W].  Returns (flags bool[n], ambiguous bool[n]): ambiguous marks the visible Gaussians whose
+    mean lies within ``tol`` pixels of where the verdict changes — a rectangle edge, the brush's outline (|dist - radius| < tol), a
+    texel edge whose two texels differ, the viewport border under a non-zero texel."""
+    kind, p0, p1, radius = _query_f32(pod)
+    vis = np.asarray(p64["visible"], bool)
+    mx, my = p64["mean2d"][:, 0], p64["mean2d"][:, 1]
+    n = vis.shape[0]
+    with np.errstate(invalid="ignore"):
+        if kind == 2:
+            lo = np.array([min(p0[0], p1[0]), min(p0[1], p1[1])])
+            hi = np.array([max(p0[0], p1[0]), max(p0[1], p1[1])])
+            # signed Chebyshev distance to the rectangle: <= 0 inside (edges included), the verdict changes at 0
+            g = np.maximum.reduce([lo[0] - mx, mx - hi[0], lo[1] - my, my - hi[1]])
+            flags, amb = g <= 0.0, np.abs(g) < tol
+        elif kind == 3:
+            a, b = np.array(p0), np.array(p1)
+            ab = b - a
+            len2 = float(ab @ ab)
+            mu = np.stack([mx, my], 1)
+            if len2 > 0.0:   # the closest point of the segment: the foot of the perpendicular, or the nearer end
+                t = np.clip(((mu - a) @ ab) / len2, 0.0, 1.0)
+                foot = a + t[:, None] * ab
+            else:            # a degenerate segment is a disc
+                foot = np.broadcast_to(a, mu.shape)
+            dist = np.hypot(mu[:, 0] - foot[:, 0], mu[:, 1] - foot[:, 1])
+            flags, amb = dist <= radius, np.abs(dist - radius) < tol
+        elif kind == 4:
+            if texture is None:
+                flags, amb = np.zeros(n, bool), np.zeros(n, bool)
+            else:
+                tex = np.asarray(texture) != 0
+                th, tw = tex.shape
+
+                def lookup(x, y):
+                    fx, fy = np.floor(x), np.floor(y)
+                    inside = (fx >= 0) & (fy >= 0) & (fx < tw) & (fy < th)     # (NaN compares false)
+                    ix = np.where(inside, fx, 0).astype(np.int64)
+                    iy = np.where(inside, fy, 0).astype(np.int64)
+                    return inside & tex[iy, ix]
+
+                flags = lookup(mx, my)
+                amb = np.zeros(n, bool)
+                for dx in (-tol, 0.0, tol):   # a neighbour (texel or outside) within tol that answers differently
+                    for dy in (-tol, 0.0, tol):
+                        amb |= lookup(mx + dx, my + dy) != flags
+        else:
+            raise ValueError(f"query_flags: kind {kind} is not a rect, brush or texture query")
+    return flags & vis, amb & vis
+
+
+def query_hits(p64, coords, params=None, display_mode=0, tol_q=QUERY_TOL_Q, tol_alpha=QUERY_TOL_ALPHA):
+    """spec §7 "Hit" in float64 on the dict ``project`` returns (project with the same display_mode: Point replaces the conic).
+    q from the float64 conic at ``coords`` (float32, as gsx_query holds them), w = exp(-q / 2) in Splat mode and 1 otherwise,
+    alpha = min(alpha_max, opacity x w); a Gaussian is hit iff it is visible, q <= k^2 and alpha >= 1 / 255.  Returns (index, depth,
+    alpha, ambiguous): the hits sorted by (float32 depth, index) — uncapped — and ambiguous bool[n] = the visible Gaussians with
+    |q - k^2| < tol_q k^2, or inside the footprint with |alpha - 1 / 255| < tol_alpha."""
+    P_ = dict(DEFAULT_PARAMS)
+    P_.update(params or {})
+    k2 = float(P_["max_std_dev"]) ** 2
+    cx, cy = float(np.float32(coords[0])), float(np.float32(coords[1]))
+    vis = np.asarray(p64["visible"], bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        dx, dy = cx - p64["mean2d"][:, 0], cy - p64["mean2d"][:, 1]
+        ca, cb, cc = p64["conic"][:, 0], p64["conic"][:, 1], p64["conic"][:, 2]
+        q = ca * dx * dx + cc * dy * dy + 2.0 * cb * dx * dy
+        w = np.exp(-0.5 * q) if int(display_mode) == 0 else np.ones_like(q)
+        alpha = np.minimum(P_["alpha_max"], p64["opacity"] * w)
+        cut = 1.0 / 255.0
+        inside = (q <= k2) & (q >= 0.0)   # (q < 0 needs an indefinite conic: outside, as in gsx_oracle.c and k_query)
+        hit = vis & inside & (alpha >= cut)
+        near_q = np.abs(q - k2) < tol_q * k2
+        amb = vis & ((near_q & (alpha >= cut - tol_alpha)) | ((inside | near_q) & (np.abs(alpha - cut) < tol_alpha)))
+    idx = np.nonzero(hit)[0]
+    d32 = p64["depth"][idx].astype(np.float32)
+    order = np.lexsort((idx, d32))
+    idx = idx[order]
+    return idx.astype(np.uint32), p64["depth"][idx], alpha[idx], amb
+
+
 # Depth test: the band |z_ndc - D| within which a float32 implementation may decide a (splat, pixel) pair the other way, as a
 # fraction of the splat's view depth d (render's `depth_tol`; in NDC the band is depth_tol x |P23| / d, since
 # dz_ndc / dd = -P23 / d^2).  The kernels compare the f32 key bits(d) with bits(P23 / (D + P22)): the key differs from the float64
