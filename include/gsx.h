@@ -112,7 +112,8 @@ typedef struct gsx_spec_params {
  * framebuffer pointer stays valid until the same lane renders again (L frames later).  Calls that touch model data
  * (uploads, masks, selection / edits) are ordered after every frame in flight.  Frames with a selection, stored edits or the
  * highlight overlap like any other (the lanes read the viewer's selection and edit records; the per-frame preparation of those
- * runs only after one of its inputs changed, ordered between the frames in flight).  Frames with a query, a band
+ * runs only after one of its inputs changed, ordered between the frames in flight).  Depth-tested frames overlap as well (each
+ * lane takes its own snapshot of the depth buffer: the depth block below has the ordering).  Frames with a query, a band
  * (gsx_viewer_set_band), an external framebuffer or a sharded model run on the viewer itself, one at a time. */
 typedef struct gsx_render_options {
     uint32_t progressive;        /* default 1 */
@@ -242,7 +243,17 @@ gsx_status gsx_render_frame(gsx_viewer* v, const char* const* keys_far_to_near, 
  *    gsx_viewer_set_depth_buffer_device or gsx_viewer_upload_depth_buffer between gsx_preprocess and gsx_render makes
  *    gsx_render refuse the frame (GSX_ERR_INVALID_ARG): preprocess + sort the models again.
  *  - gsx_shard_* frames (and gsx_render_more) return GSX_ERR_INVALID_ARG while the test is on.
- *  - With frames_in_flight > 1, a depth-tested frame runs on the viewer itself, one at a time (like a frame with a query). */
+ *  - With frames_in_flight > 1 a depth-tested frame is dealt to a lane like any other; the lane takes its own snapshot, on its own
+ *    stream.  The buffer's contents are read AS IF on the viewer's stream at the gsx_render_frame that uses them:
+ *      (a) the lane's snapshot waits for what the viewer's stream held when the frame was dealt — every earlier library call
+ *          (gsx_viewer_upload_depth_buffer among them) and, when gsx_viewer_desc.stream is the caller's own, whatever the caller
+ *          enqueued there before the call (its writes into a device buffer);
+ *      (b) the viewer's stream waits for the snapshot (an event, no host wait) — not for the frame: a later
+ *          gsx_viewer_upload_depth_buffer or gsx_viewer_set_depth_buffer_device, and anything the caller enqueues on the viewer's
+ *          stream after gsx_render_frame has returned, comes after that frame's read of the old contents.
+ *    Frame k therefore sees the buffer as it was set for frame k, however many frames are in flight.  A caller that writes
+ *    the buffer from another stream orders those writes against the viewer's stream itself.  GSX_DEPTH_LANES=0 (read when the
+ *    viewer is created; A/B) keeps depth-tested frames on the viewer itself. */
 typedef enum gsx_depth_compare { GSX_DEPTH_ALWAYS = 0 /* no test (default) */, GSX_DEPTH_LESS = 1 } gsx_depth_compare;
 gsx_status gsx_viewer_set_depth_test(gsx_viewer* v, gsx_depth_compare compare);
 /* Caller-owned DEVICE memory, 4-byte aligned, read in place: `height` rows of `width` floats, row_pitch_bytes apart (>= 4 * width, a

@@ -208,7 +208,10 @@ public:
         return v;
     }
     void set_depth_test(gsx_depth_compare c) { check(gsx_viewer_set_depth_test(v_, c)); }
-    // float32 [size.y][size.x] NDC depth, row 0 at the top: copied (host memory) or read in place (device memory, row pitch in bytes)
+    // float32 [size.y][size.x] NDC depth, row 0 at the top: copied (host memory) or read in place (device memory, row pitch in bytes).
+    // With frames_in_flight > 1 a depth-tested frame is dealt to a lane like any other and the lane takes its own snapshot: the
+    // buffer is read as if on the viewer's stream at the render_frame that uses it — what is set or enqueued there afterwards
+    // waits for that read (no host wait), not for the frame (gsx.h, the depth block)
     void update_depth_buffer(const float* host, UVec2 sz) { check(gsx_viewer_upload_depth_buffer(v_, host, sz.x, sz.y)); }
     void set_depth_buffer_device(const float* d_ptr, UVec2 sz, uint64_t row_pitch_bytes) {
         check(gsx_viewer_set_depth_buffer_device(v_, d_ptr, sz.x, sz.y, row_pitch_bytes));

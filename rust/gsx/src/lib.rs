@@ -192,6 +192,9 @@ impl<G: GaussianPod> MultiModelViewer<G> {
     /// `DepthStencilState { Depth32Float, depth_write_enabled: false, Less }` — turns on the depth test against the buffer given to
     /// `update_depth_buffer` each frame (`None`: no test).  The state itself is not inspected: libgsx has `Less` without depth write
     /// only (the app's state), so ANY `Some(..)` — another compare, depth write on — is taken as that; map other states yourself.
+    /// With `frames_in_flight > 1` a depth-tested frame is dealt to a lane like any other and the lane takes its own snapshot: the
+    /// buffer is read as if on the viewer's stream at the `render_frame` that uses it — what is set or enqueued there afterwards
+    /// waits for that read (no host wait), not for the frame (`gsx.h`, the depth block).
     pub fn new_with<D, F, S>(_device: &D, _format: F, depth_stencil: Option<S>, size: (u32, u32)) -> Result<Self, Error> {
         let desc = sys::gsx_viewer_desc { abi_version: sys::GSX_ABI_VERSION, device: 0, stream: std::ptr::null_mut(), width: size.0, height: size.1 };
         let mut v = std::ptr::null_mut();

@@ -11,7 +11,12 @@ device memory does: the buffer is read by every frame's first preprocess whether
 The host waits for every frame (gsx_render_frame + gsx_sync), as the app does.  Prints ONE JSON line: fps per mode (median of its
 blocks, and every block), and the ratios to `off`.
 
-    python tools/bench_depth.py [--blocks 6] [--block 120] [--warmup 60]
+--inflight adds the loop that never waits (bench.py's `value` loop: a block of gsx_render_frame calls, one gsx_sync behind it) with one
+and with two frames in flight, for off / cleared / occluder: rows `<mode>_unsync_fif1` and `<mode>_unsync_fif2`, their ratios to the
+`off` row of the same loop, and what two frames in flight gain over one.  --inflight-only leaves the synchronised rows out.
+GSX_LIB selects another build of the library (the parent commit's, for a same-box A/B: tools/ab_depth.sh interleaves the two).
+
+    python tools/bench_depth.py [--blocks 6] [--block 120] [--warmup 60] [--inflight | --inflight-only]
 """
 from __future__ import annotations
 
@@ -37,7 +42,10 @@ def main() -> None:
     ap.add_argument("--block", type=int, default=120, help="frames per block")
     ap.add_argument("--warmup", type=int, default=60, help="frames per mode before the first timed block")
     ap.add_argument("--box-depth", type=float, default=3.0, help="view depth of the occluding box (the orbit's radius is 6; the scene saturates at ~4-5)")
+    ap.add_argument("--inflight", action="store_true", help="add the unsynchronised rows with one and two frames in flight")
+    ap.add_argument("--inflight-only", action="store_true", help="only those rows")
     a = ap.parse_args()
+    a.inflight |= a.inflight_only
 
     import torch
 
@@ -58,16 +66,18 @@ def main() -> None:
     dev = {"cleared": torch.from_numpy(cleared).cuda(), "occluder": torch.from_numpy(occluder).cuda()}
     torch.cuda.synchronize()
     modes = {"off": None, "cleared": cleared, "occluder": occluder, "occluder_upload": occluder}
+    buffers = dict(modes)
     frame = [0]
 
     def select(mode: str) -> None:
-        v.set_depth_test(DepthCompare.Always if modes[mode] is None else DepthCompare.Less)
+        v.set_depth_test(DepthCompare.Always if buffers[mode] is None else DepthCompare.Less)
         if mode in dev:
             v.set_depth_buffer_device(dev[mode].data_ptr(), w, h, 4 * w)
-        elif modes[mode] is not None:
-            v.update_depth_buffer(modes[mode])
+        elif buffers[mode] is not None:
+            v.update_depth_buffer(buffers[mode])
 
     def run(mode: str, frames: int) -> float:
+        v.set_render_options(frames_in_flight=1)   # (the --inflight rows leave two)
         select(mode)
         upload = mode == "occluder_upload"
         v.poll()
@@ -81,12 +91,33 @@ def main() -> None:
             frame[0] += 1
         return frames / (time.perf_counter() - t0)
 
+    def run_unsync(mode: str, fif: int, frames: int) -> float:
+        v.set_render_options(frames_in_flight=fif)
+        select(mode)
+        v.poll()
+        t0 = time.perf_counter()
+        for _ in range(frames):
+            v.update_camera(orbit[frame[0] % 240], (w, h))
+            v.render_frame(["m"])
+            frame[0] += 1
+        v.poll()
+        return frames / (time.perf_counter() - t0)
+
+    unsync = [(m, fif) for fif in (1, 2) for m in ("off", "cleared", "occluder")] if a.inflight else []
+    if a.inflight_only:
+        modes = {}
     for m in modes:
         run(m, a.warmup)
+    for m, fif in unsync:
+        run_unsync(m, fif, a.warmup)
     fps = {m: [] for m in modes}
+    fps_u = {f"{m}_unsync_fif{fif}": [] for m, fif in unsync}
     for _ in range(a.blocks):
         for m in modes:
             fps[m].append(run(m, a.block))
+        for m, fif in unsync:
+            fps_u[f"{m}_unsync_fif{fif}"].append(run_unsync(m, fif, a.block))
+    v.set_render_options(frames_in_flight=1)
     stats = {}
     for m in modes:
         select(m)
@@ -97,13 +128,21 @@ def main() -> None:
     v.set_depth_buffer_device(None, 0, 0, 0)
     v.close()
     med = {m: statistics.median(x) for m, x in fps.items()}
-    print(json.dumps({
+    out = {
         "tool": "bench_depth", "config": a.config, "gaussians": n, "size": [w, h], "host_waits_per_frame": True,
+        "lib": os.environ.get("GSX_LIB", "in-tree"),
         "fps": {m: round(x, 1) for m, x in med.items()},
         "fps_blocks": {m: [round(y, 1) for y in x] for m, x in fps.items()},
         "ratio_to_off": {m: round(med[m] / med["off"], 4) for m in modes},
         "pose0_stats": stats,
-    }))
+    }
+    if unsync:
+        mu = {r: statistics.median(x) for r, x in fps_u.items()}
+        out["unsync_fps"] = {r: round(x, 1) for r, x in mu.items()}
+        out["unsync_fps_blocks"] = {r: [round(y, 1) for y in x] for r, x in fps_u.items()}
+        out["unsync_ratio_to_off"] = {r: round(x / mu[f"off_unsync_fif{r[-1]}"], 4) for r, x in mu.items()}
+        out["unsync_two_over_one"] = {m: round(mu[f"{m}_unsync_fif2"] / mu[f"{m}_unsync_fif1"], 4) for m in ("off", "cleared", "occluder")}
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":

@@ -11,7 +11,8 @@ using namespace gsx;
 // A lane is a gsx_viewer of its own — stream, framebuffer, per-model records / sort / tile buffers, speculation windows —
 // created by the viewer it belongs to; its models are shadows that VIEW the owner's Gaussian data (DevBuf::borrow).
 // gsx_render_frame deals frames round-robin to the viewer and its lanes; nothing else in the library knows about lanes
-// except viewer_bind (gsx_state.h), which orders the viewer's stream after the lanes' frames before any other call.
+// except viewer_bind (gsx_state.h), which orders the viewer's stream after the lanes' frames before any other call, and
+// depth_snapshot (gsx_frame.cpp), which orders it after a lane's read of the depth buffer.
 static std::atomic<uint64_t> g_model_serial{0};  // (viewers of different host threads create models concurrently)
 static std::atomic<int> g_viewers_on_device[64];  // live top-level viewers of this process per device (lane_create's probe asks)
 
@@ -93,16 +94,18 @@ static gsx_status lane_create(gsx_viewer* v, gsx_viewer** out) {
     }
     l->own_stream = true;
     HIPCHK(hipEventCreateWithFlags(&l->lane_event, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&l->depth_event, hipEventDisableTiming));
     *out = l.release();
     return GSX_OK;
 }
 
 // may this frame go to a lane?  (a frame with a query — its flags feed gsx_postprocess — and everything multi-GPU stays on the
 // viewer; selections, edits and the highlight travel: a lane's shadow models view the owner's selection and edit buffers, which
-// the owner prepares before the frame is dealt out, prepare_edits_for_lanes)
+// the owner prepares before the frame is dealt out, prepare_edits_for_lanes; a depth-tested frame travels too: the lane takes its
+// own snapshot of the depth buffer, lane_sync / depth_snapshot — unless GSX_DEPTH_LANES=0 keeps it on the viewer)
 static bool frame_may_overlap(gsx_viewer* v, const char* const* keys, uint32_t n_keys) {
     if (v->parent || v->options.frames_in_flight < 2 || v->query.kind != GSX_QUERY_NONE || v->ext_fb || v->band_lo != 0 ||
-        v->band_hi != 0xFFFFFFFFu || v->depth_compare != GSX_DEPTH_ALWAYS)  // (a depth-tested frame reads the viewer's depth snapshot)
+        v->band_hi != 0xFFFFFFFFu || (v->depth_compare != GSX_DEPTH_ALWAYS && !v->depth_lanes))
         return false;
     for (uint32_t i = 0; i < n_keys; ++i) {
         Model* m = find_model(v, keys ? keys[i] : nullptr);
@@ -152,6 +155,15 @@ static gsx_status lane_sync(gsx_viewer* v, gsx_viewer* l, const char* const* key
     l->options = v->options;
     l->options.frames_in_flight = 1;
     l->timing = v->timing;
+    // the depth test: the compare and where the buffer is; the snapshot itself is the lane's own, taken by this frame's first preprocess
+    l->depth_compare = v->depth_compare;
+    l->depth_dev = v->depth_dev;
+    l->depth_pitch = v->depth_pitch;
+    l->depth_w = v->depth_w;
+    l->depth_h = v->depth_h;
+    l->depth_owned.borrow(v->depth_owned);
+    l->depth_cfg = v->depth_cfg;
+    l->depth_frame_closed = true;
     for (uint32_t i = 0; i < n_keys; ++i) {
         Model* pm = find_model(v, keys[i]);
         Model* sm = find_model(l, keys[i]);
@@ -191,8 +203,10 @@ static gsx_status lane_sync(gsx_viewer* v, gsx_viewer* l, const char* const* key
         sm->show_unedited = pm->show_unedited;
         sm->slot_force = pm->slot_force;  // gsx_shard_set_slot_records may have been called before this lane (or this shadow) existed
     }
-    // whatever the caller enqueued on the viewer's stream since this lane's last frame (uploads, masks) comes first
-    if (l->seen_epoch != v->epoch) {
+    // whatever the caller enqueued on the viewer's stream since this lane's last frame (uploads, masks) comes first — and, when that
+    // stream is the caller's own, whatever it wrote there into a device depth buffer this frame is tested against (no library call tells)
+    const bool caller_depth_writes = !v->own_stream && v->depth_compare != GSX_DEPTH_ALWAYS && v->depth_dev;
+    if (l->seen_epoch != v->epoch || caller_depth_writes) {
         if (!v->lane_event) HIPCHK(hipEventCreateWithFlags(&v->lane_event, hipEventDisableTiming));
         HIPCHK(gsx::op::EventRecord(v->lane_event, v->stream));
         HIPCHK(gsx::op::StreamWaitEvent(l->stream, v->lane_event, 0));
@@ -269,7 +283,7 @@ gsx_status gsx_viewer_create(const gsx_viewer_desc* desc, gsx_viewer** out) {
     if (const char* e = getenv("GSX_BUCKET_SORT")) v->bucket_sort = atoi(e) != 0;
     if (const char* e = getenv("GSX_BIN_FUSED")) v->bin_fused = atoi(e) != 0;
     if (const char* e = getenv("GSX_SHORT_CHAIN")) v->short_chain = atoi(e) != 0;
-    if (const char* e = getenv("GSX_BIN_BIG_RECT")) block_bin_set_big_rect((uint32_t)atoi(e));   // tests / tuning
+    if (const char* e = getenv("GSX_DEPTH_LANES")) v->depth_lanes = atoi(e) != 0;
     if (const char* e = getenv("GSX_BIN_BIG_SLAB")) block_bin_set_big_slab((uint32_t)atoi(e));   // tests: smaller slabs take the eight-per-lane tiles
     if (const char* e = getenv("GSX_BUCKET_CAP")) bucket_sort_set_cap((uint32_t)atoi(e));   // tests: buckets above this take the global-memory path
     if (const char* e = getenv("GSX_SORTED_RECORDS")) v->sorted_records = atoi(e) != 0 ? 1 : 0;
@@ -320,6 +334,7 @@ void gsx_viewer_destroy(gsx_viewer* v) {
     v->lanes.clear();
     (void)gsx::op::StreamSynchronize(v->stream);
     if (v->lane_event) (void)hipEventDestroy(v->lane_event);
+    if (v->depth_event) (void)hipEventDestroy(v->depth_event);
     for (hipStream_t ps : v->parked_streams) (void)hipStreamDestroy(ps);
     if (v->h_shard_verdict) (void)hipHostFree(v->h_shard_verdict);
     if (v->h_verdict_ring) (void)hipHostFree(v->h_verdict_ring);
@@ -695,7 +710,7 @@ gsx_status gsx_render_frame(gsx_viewer* v, const char* const* keys, uint32_t n_k
             if ((st = do_sort(lane, m))) return st;
         }
         if ((st = do_render(lane, keys, n_keys))) return st;
-        v->depth_frame_closed = true;  // the next gsx_preprocess reads the depth buffer again
+        v->depth_frame_closed = lane->depth_frame_closed = true;  // the next gsx_preprocess reads the depth buffer again
         v->host_waited = false;   // (until the app waits again: gsx_sync, a blocking readback)
         if ((st = trace.finish())) return st;
     }

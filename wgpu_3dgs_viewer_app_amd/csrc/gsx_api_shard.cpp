@@ -36,11 +36,22 @@ gsx_status gsx_viewer_set_external_framebuffer(gsx_viewer* v, void* d_ptr, uint6
     return GSX_OK;
 }
 
+// The depth calls do NOT come through viewer_bind: that orders the viewer's stream after the lanes' whole frames, and the lanes' next
+// frames after the viewer's stream — a depth buffer that changes every frame would put the frames in flight back in single file.  What
+// they need is less: every lane's snapshot has made the viewer's stream wait for its read of the buffer when the frame was dealt
+// (depth_snapshot), so whatever is enqueued there now comes after every read of the old contents; and a lane's next frame waits
+// for what an upload enqueues (epoch), for nothing else.
+static gsx_status depth_bind(gsx_viewer* v) {
+    if (!v) return fail(GSX_ERR_INVALID_ARG, "viewer is null");
+    HIPCHK(hipSetDevice(v->device));
+    if (!v->shard_pending.empty() && !v->shard_busy) return shard_complete_pending(v);
+    return GSX_OK;
+}
 
 gsx_status gsx_viewer_set_depth_test(gsx_viewer* v, gsx_depth_compare compare) {
     if (compare != GSX_DEPTH_ALWAYS && compare != GSX_DEPTH_LESS)
         return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_set_depth_test: unknown compare %d (GSX_DEPTH_ALWAYS, GSX_DEPTH_LESS)", (int)compare);
-    gsx_status st = viewer_bind(v);
+    gsx_status st = v && !v->depth_lanes ? viewer_bind(v) : depth_bind(v);
     if (st) return st;
     if (v->parent) return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_set_depth_test: called on a lane");
     if (v->depth_compare != (uint32_t)compare) v->depth_cfg += 1;  // (frames preprocessed under the old setting are refused by gsx_render)
@@ -49,7 +60,7 @@ gsx_status gsx_viewer_set_depth_test(gsx_viewer* v, gsx_depth_compare compare) {
 }
 
 gsx_status gsx_viewer_set_depth_buffer_device(gsx_viewer* v, const float* d_ptr, uint32_t width, uint32_t height, uint64_t row_pitch_bytes) {
-    gsx_status st = viewer_bind(v);
+    gsx_status st = v && !v->depth_lanes ? viewer_bind(v) : depth_bind(v);
     if (st) return st;
     if (v->parent) return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_set_depth_buffer_device: called on a lane");
     if (d_ptr && (width == 0 || height == 0 || row_pitch_bytes < 4ull * width || (row_pitch_bytes & 3u)))
@@ -71,7 +82,7 @@ gsx_status gsx_viewer_set_depth_buffer_device(gsx_viewer* v, const float* d_ptr,
 }
 
 gsx_status gsx_viewer_upload_depth_buffer(gsx_viewer* v, const float* host, uint32_t width, uint32_t height) {
-    gsx_status st = viewer_bind(v);
+    gsx_status st = v && !v->depth_lanes ? viewer_bind(v) : depth_bind(v);
     if (st) return st;
     if (v->parent) return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_upload_depth_buffer: called on a lane");
     if (!host || width == 0 || height == 0) return fail(GSX_ERR_INVALID_ARG, "gsx_viewer_upload_depth_buffer: null buffer or empty size");
@@ -87,6 +98,7 @@ gsx_status gsx_viewer_upload_depth_buffer(gsx_viewer* v, const float* host, uint
     v->depth_w = v->depth_up_w = width;
     v->depth_h = v->depth_up_h = height;
     v->depth_cfg += 1;
+    v->epoch += 1;  // a lane's next frame waits for the copy (lane_sync)
     return GSX_OK;
 }
 

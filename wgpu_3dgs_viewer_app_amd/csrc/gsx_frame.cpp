@@ -403,7 +403,7 @@ static gsx_status depth_snapshot(gsx_viewer* v, const Model* m) {
         v->depth_snap_h == v->height && v->depth_snap_p22 == P[10] && v->depth_snap_p23 == P[14] && m->depth_snap != v->depth_snap)
         return GSX_OK;
     const uint32_t tiles_x = (v->width + GSX_TILE - 1) / GSX_TILE, tiles_y = (v->height + GSX_TILE - 1) / GSX_TILE;
-    HIPCHK(v->depth_lim.ensure(4 * (size_t)v->width * v->height));
+    HIPCHK(v->depth_lim.ensure(4 * ((size_t)v->width * v->height + (size_t)tiles_x * tiles_y)));  // (+ one word per tile: "no pixel has a limit")
     HIPCHK(v->depth_win.ensure(sizeof(uint2) * (size_t)tiles_x * tiles_y));
     HIPCHK(launch_depth_limits(v->stream, src, v->depth_dev ? v->depth_pitch : 4ull * v->depth_w, v->width, v->height, P[10], P[14],
                                v->depth_lim.as<uint32_t>(), v->depth_win.as<uint2>()));
@@ -414,6 +414,12 @@ static gsx_status depth_snapshot(gsx_viewer* v, const Model* m) {
     v->depth_snap_p22 = P[10];
     v->depth_snap_p23 = P[14];
     v->depth_frame_closed = false;
+    // a lane's snapshot: whatever the owner's stream does next to the buffer (an upload, the caller's own writes) comes after this read — and
+    // waits for nothing else of the lane's frame
+    if (v->parent) {
+        HIPCHK(gsx::op::EventRecord(v->depth_event, v->stream));
+        HIPCHK(gsx::op::StreamWaitEvent(v->parent->stream, v->depth_event, 0));
+    }
     return GSX_OK;
 }
 
@@ -493,9 +499,8 @@ gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
         const size_t pw = window_pyramid_words(m->fc.tiles_x, m->fc.tiles_y);
         HIPCHK(m->spec_dwin.ensure(sizeof(uint2) * (size_t)n_tiles));
         HIPCHK(m->spec_dpyr.ensure(8 * pw));
-        HIPCHK(launch_depth_cap_windows(v->stream, m->spec_win.as<uint2>(), v->depth_win.as<uint2>(), m->spec_dwin.as<uint2>(), n_tiles));
-        HIPCHK(launch_window_pyramid(v->stream, m->spec_dwin.as<uint2>(), m->fc.tiles_x, m->fc.tiles_y, m->spec_dpyr.as<uint32_t>(), false, nullptr,
-                                     m->spec_dpyr.as<uint32_t>() + pw));
+        HIPCHK(launch_depth_cap_pyramid(v->stream, m->spec_win.as<uint2>(), v->depth_win.as<uint2>(), m->spec_dwin.as<uint2>(), m->fc.tiles_x,
+                                        m->fc.tiles_y, m->spec_dpyr.as<uint32_t>(), m->spec_dpyr.as<uint32_t>() + pw));
         adm.pyramid = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, m->spec_dpyr.as<uint32_t>());
     } else if (m->spec_round1) {
         adm.pyramid = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, m->spec_coarse.as<uint32_t>());

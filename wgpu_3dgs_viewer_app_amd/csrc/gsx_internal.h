@@ -393,7 +393,6 @@ hipError_t launch_admit_compact(hipStream_t s, const uint32_t* key, uint32_t n, 
                                 const uint32_t* d_skip = nullptr /* points at 0: nothing is admitted, no ballot is read */,
                                 bool histogram = true /* false: the compaction alone (msd_ws still holds its ticket and status words) */);
 uint32_t next_sort_epoch();  // status-word epochs of every look-back kernel of the process (kernels_sort.hip)
-void block_bin_set_big_rect(uint32_t blocks);    // tests / tuning: rectangles of more blocks than this are walked by the whole wave in k_block_bin (0: the default)
 void block_bin_set_big_slab(uint32_t records);  // tests: slabs of this many records and more take eight records per lane in k_block_bin (0: the default)
 void bucket_sort_set_cap(uint32_t cap);  // tests: buckets above `cap` pairs take the global-memory path (0: the LDS capacity)
 
@@ -739,11 +738,14 @@ hipError_t launch_spec_next(hipStream_t s, const uint32_t* tile_sat, const uint3
                             const uint2* depth_bound = nullptr /* depth test: an open tile with a finite bound counts as closed at that bound */);
 
 // Depth test against the caller's depth buffer (kernels_depth.hip).  lim: u32 per pixel, row-major [h][w] — the depth key at and behind
-// which a splat is hidden there (0: everything, 0xFFFFFFFF: nothing); window: per tile {0, max of its pixels' limits}.
+// which a splat is hidden there (0: everything, 0xFFFFFFFF: nothing) — and behind them one u32 per tile, 1 when no pixel of the tile has
+// a limit (the compositors read it: lim holds w * h + tiles words); window: per tile {0, max of its pixels' limits}.
 hipError_t launch_depth_limits(hipStream_t s, const float* depth, uint64_t pitch_bytes, uint32_t w, uint32_t h, float p22, float p23,
                                uint32_t* lim, uint2* window);
-// out[t] = {spec[t].x, min(spec[t].y, bound[t].y)}
-hipError_t launch_depth_cap_windows(hipStream_t s, const uint2* spec, const uint2* bound, uint2* out, uint32_t n_tiles);
+// out[t] = {spec[t].x, min(spec[t].y, bound[t].y)} and, in the same launch, the max-pyramid (data) and the min-pyramid (min_ends) of `out`
+// as launch_window_pyramid builds them (kernels_spec.hip)
+hipError_t launch_depth_cap_pyramid(hipStream_t s, const uint2* spec, const uint2* bound, uint2* out, uint32_t tiles_x, uint32_t tiles_y,
+                                    uint32_t* data, uint32_t* min_ends);
 
 // Multi-GPU exchange support (kernels_shard.hip).
 // d_n (nullable) / tile: only the first ceil(*d_n / tile) columns of every row hold anything (a candidate list shorter than the grid)

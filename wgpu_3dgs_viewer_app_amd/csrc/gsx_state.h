@@ -448,7 +448,9 @@ struct gsx_viewer {
     // depth test against the caller's depth buffer (gsx_viewer_set_depth_test, kernels_depth.hip).  The buffer: caller-owned device
     // memory (depth_dev) or the viewer's copy of an upload (depth_owned).  depth_cfg counts changes of the compare or the buffer; a
     // snapshot (per-pixel limits, per-tile windows {0, bound}, their [max | min] pyramids) is taken by the first gsx_preprocess of a
-    // frame and belongs to that frame until gsx_render / gsx_render_frame ends it
+    // frame and belongs to that frame until gsx_render / gsx_render_frame ends it.  The snapshot (depth_lim / _win / _pyr and the depth_snap*
+    // bookkeeping) lives with the viewer that renders the frame — the owner or a lane: lane_sync hands a lane the compare, the buffer (a
+    // view of depth_owned, or depth_dev) and depth_cfg, and the lane takes its own snapshot on its own stream
     uint32_t depth_compare = GSX_DEPTH_ALWAYS;
     const float* depth_dev = nullptr;
     uint64_t depth_pitch = 0;
@@ -458,6 +460,8 @@ struct gsx_viewer {
     bool depth_frame_closed = true;
     uint32_t depth_snap_w = 0, depth_snap_h = 0;  // what the snapshot was computed from (depth_snapshot retakes it when they change)
     float depth_snap_p22 = 0.0f, depth_snap_p23 = 0.0f;
+    hipEvent_t depth_event = nullptr;    // lane: its last snapshot has read the depth buffer (the owner's stream waits for it: depth_snapshot)
+    bool depth_lanes = true;             // GSX_DEPTH_LANES=0: depth-tested frames run on the viewer itself, one at a time (A/B)
     gsx_render_options options{1u, 16u, 131072u, 2u, 1u, 0.25f, 3u, 0u, 1u, 1u};  // = gsx_render_options_default (a CPU test compares the two: gsx_viewer_get_render_options)
     bool host_waited = false;  // the host has waited for this viewer's device work (gsx_sync, a blocking readback) since its last frame was enqueued:
                                // the app synchronises per frame, so asking for a speculated frame's verdict costs it nothing (host_verify = 2)

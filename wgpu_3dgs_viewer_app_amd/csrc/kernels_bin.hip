@@ -537,9 +537,7 @@ constexpr int kFuseThreads = 1024;
 constexpr int kFuseWaves = kFuseThreads / 64;
 constexpr uint32_t kFuseTile = 2u * kFuseThreads;   // records per tile: two per lane (eight on slabs of kFuseBigSlab records and more)
 constexpr uint32_t kFuseBigSlab = 1u << 20;
-constexpr uint32_t kBigRect = 32;   // blocks: larger rectangles are walked by the whole wave (block_bin_tiles)
-static std::atomic<uint32_t> g_big_rect{kBigRect};
-void block_bin_set_big_rect(uint32_t blocks) { g_big_rect.store(blocks ? blocks : kBigRect); }
+constexpr uint32_t kBigRect = 32;   // blocks: larger rectangles are walked by the whole wave (block_bin_tiles; swept 4 ... 64: profiles/r06_ab_big_rect.txt)
 static std::atomic<uint32_t> g_big_slab{kFuseBigSlab};
 void block_bin_set_big_slab(uint32_t records) { g_big_slab.store(records ? records : kFuseBigSlab); }
 constexpr uint32_t kFuseGrid = 256;
@@ -858,7 +856,7 @@ hipError_t launch_block_bin_fused(hipStream_t s, uint32_t j0, uint32_t j1, const
         GSX_LAUNCH(k_block_bin, dim3(nb + (zero.order_buf ? 1u : 0u)), dim3(kFuseThreads), 0, s, d_n_vis, j0, j1, sorted_idx, rec.a, sorted_keys, brec, pairs,
                    stats, capacity, row_lo, row_hi, d_done_count, owned_tiles, slab_index, g, table, window ? 1 : 0, zero.order_buf, zero.order_tiles,
                    zero.order_buf ? &stats->walk_max : nullptr, bin_ws, reinterpret_cast<u64b*>(bin_ws + 8), next_sort_epoch(), sort_ghist, passes, dbits,
-                   shade_pairs ? rec.rect8 : nullptr, shade_pairs, live ? sorted_code : nullptr, live, g_big_slab.load(), g_big_rect.load());
+                   shade_pairs ? rec.rect8 : nullptr, shade_pairs, live ? sorted_code : nullptr, live, g_big_slab.load(), kBigRect);
     return hipGetLastError();
 }
 

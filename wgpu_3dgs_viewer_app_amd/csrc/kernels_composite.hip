@@ -39,7 +39,8 @@ __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elem
 // and tile, 80 % of the kernel's vector instructions.
 // DEPTH (depth test, kernels_depth.hip): dl0 / dl1 are the pixels' limit keys; records arrive in ascending key order, so a pixel closes
 // (lim = 0) at its first record whose key (s_rgb[j].w) is >= its limit — one compare more per (record, pixel).  DEPTH = false compiles
-// to the loop without it.
+// to the loop without it — which a depth-tested frame takes as well on every tile none of whose pixels has a limit (a cleared depth
+// attachment, the app's common case: tile_has_limits below; the DEPTH loop with dl = 0xFFFFFFFF never closes a pixel, the same bits).
 template <int MODE, int kGroup, bool CLAMP, bool DEPTH = false>
 __device__ __forceinline__ void blend_batch(const FrameConsts& f, const uint32_t cnt, const float2* s_mean, const float4* s_conic,
                                             const float4* s_rgb, const float pxf, const v2f pyf, uint32_t& lim0, uint32_t& lim1,
@@ -104,6 +105,18 @@ __device__ __forceinline__ void blend_batch(const FrameConsts& f, const uint32_t
         }
     }
 }
+
+// Depth test: does any pixel of the tile have a limit?  k_depth_limits leaves one word per tile behind the w x h limit keys (1: none has).
+// One address for the whole workgroup: a scalar load and a uniform branch.
+__device__ __forceinline__ bool tile_has_limits(const FrameConsts& f, const uint32_t* __restrict__ depth_lim, uint32_t tile) {
+    return depth_lim[(size_t)f.w_px * f.h_px + tile] == 0u;
+}
+// blend_batch for a kernel compiled with the depth test: the DEPTH loop on tiles with limits, the plain one on the others
+#define GSX_BLEND(MODE, GROUP, CLAMP, DEPTH, limited, ...)                                           \
+    do {                                                                                             \
+        if (DEPTH && (limited)) blend_batch<MODE, GROUP, CLAMP, true>(__VA_ARGS__, dl0, dl1);        \
+        else blend_batch<MODE, GROUP, CLAMP, false>(__VA_ARGS__);                                    \
+    } while (0)
 
 // Both pixels of this lane are done for the tile's done bit: outside the image or T < t_epsilon.  Without the depth test that is
 // lim == 0 (only those two close a pixel); with it a pixel closed by its depth limit is NOT saturated — a model composited later (behind,
@@ -175,7 +188,8 @@ __global__ __launch_bounds__(128) void k_composite(const FrameConsts f, uint2* _
     const uint32_t live = f.k2 > 0.0f ? __float_as_uint(f.k2) + 1u : (f.k2 == 0.0f ? 1u : 0u);
     uint32_t lim0 = (in0 && !(T.x < f.t_eps)) ? live : 0u, lim1 = (in1 && !(T.y < f.t_eps)) ? live : 0u;
     uint32_t dl0 = 0u, dl1 = 0u;  // DEPTH: the pixels' limit keys
-    if (DEPTH) {
+    const bool limited = DEPTH && tile_has_limits(f, depth_lim, tile);
+    if (limited) {
         dl0 = in0 ? depth_lim[fbo] : 0u;
         dl1 = in1 ? depth_lim[fbo + f.w_px] : 0u;
     }
@@ -225,7 +239,7 @@ __global__ __launch_bounds__(128) void k_composite(const FrameConsts f, uint2* _
             }
         }
         const uint32_t cnt = min((uint32_t)kBatch, range.y - base);
-        blend_batch<MODE, kGroupTiles, CLAMP, DEPTH>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key, dl0, dl1);
+        GSX_BLEND(MODE, kGroupTiles, CLAMP, DEPTH, limited, f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key);
     }
     if (in0) fb[fbo] = make_float4(C0.x, C1.x, C2.x, T.x);
     if (in1) fb[fbo + f.w_px] = make_float4(C0.y, C1.y, C2.y, T.y);
@@ -329,7 +343,8 @@ __global__ __launch_bounds__(128) void k_composite_blocks(const FrameConsts f, c
     const uint32_t live = f.k2 > 0.0f ? __float_as_uint(f.k2) + 1u : (f.k2 == 0.0f ? 1u : 0u);
     uint32_t lim0 = (in0 && !(T.x < f.t_eps)) ? live : 0u, lim1 = (in1 && !(T.y < f.t_eps)) ? live : 0u;
     uint32_t dl0 = 0u, dl1 = 0u;  // DEPTH: the pixels' limit keys
-    if (DEPTH) {
+    const bool limited = DEPTH && tile_has_limits(f, depth_lim, tile);
+    if (limited) {
         dl0 = in0 ? depth_lim[fbo] : 0u;
         dl1 = in1 ? depth_lim[fbo + f.w_px] : 0u;
     }
@@ -430,7 +445,7 @@ __global__ __launch_bounds__(128) void k_composite_blocks(const FrameConsts f, c
             }
         }
         taken += cnt;
-        if (cnt) blend_batch<MODE, kGroupBlocks, CLAMP, DEPTH>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key, dl0, dl1);
+        if (cnt) GSX_BLEND(MODE, kGroupBlocks, CLAMP, DEPTH, limited, f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key);
     }
     if (spill) {
         for (uint32_t sb = spill_cut; sb < spill_end; sb += 128u) {
@@ -467,7 +482,7 @@ __global__ __launch_bounds__(128) void k_composite_blocks(const FrameConsts f, c
                 s_rgb[cnt + tid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
             __syncthreads();
-            if (cnt) blend_batch<MODE, kGroupBlocks, CLAMP, DEPTH>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key, dl0, dl1);
+            if (cnt) GSX_BLEND(MODE, kGroupBlocks, CLAMP, DEPTH, limited, f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key);
         }
     }
     if (in0) fb[fbo] = make_float4(C0.x, C1.x, C2.x, T.x);
@@ -538,7 +553,8 @@ __global__ __launch_bounds__(128) void k_composite_spill(const FrameConsts f, co
     const uint32_t live = f.k2 > 0.0f ? __float_as_uint(f.k2) + 1u : (f.k2 == 0.0f ? 1u : 0u);
     uint32_t lim0 = (in0 && !(T.x < f.t_eps)) ? live : 0u, lim1 = (in1 && !(T.y < f.t_eps)) ? live : 0u;
     uint32_t dl0 = 0u, dl1 = 0u;  // DEPTH: the pixels' limit keys
-    if (DEPTH) {
+    const bool limited = DEPTH && tile_has_limits(f, depth_lim, tile);
+    if (limited) {
         dl0 = in0 ? depth_lim[fbo] : 0u;
         dl1 = in1 ? depth_lim[fbo + f.w_px] : 0u;
     }
@@ -577,7 +593,7 @@ __global__ __launch_bounds__(128) void k_composite_spill(const FrameConsts f, co
             s_rgb[cnt + tid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
         __syncthreads();
-        blend_batch<MODE, kGroupTiles, CLAMP, DEPTH>(f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key, dl0, dl1);
+        GSX_BLEND(MODE, kGroupTiles, CLAMP, DEPTH, limited, f, cnt, s_mean, s_conic, s_rgb, pxf, pyf, lim0, lim1, T, C0, C1, C2, stop_key);
     }
     if (in0) fb[fbo] = make_float4(C0.x, C1.x, C2.x, T.x);
     if (in1) fb[fbo + f.w_px] = make_float4(C0.y, C1.y, C2.y, T.y);

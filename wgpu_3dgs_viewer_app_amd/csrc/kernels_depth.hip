@@ -25,34 +25,36 @@ __device__ __forceinline__ uint32_t depth_limit_key(float d, float p22, float p2
     return lim > 0.0f ? __float_as_uint(lim) : 0u;
 }
 
-// one 256-lane workgroup per tile, one pixel per lane
+// one 256-lane workgroup per tile, one pixel per lane.  Behind the w x h limits, one word per tile: 1 when no pixel of the tile has a
+// limit (the minimum of its pixels' limits is "none") — the compositors take such a tile through their loop without the compare.
 __global__ __launch_bounds__(256) void k_depth_limits(const float* __restrict__ depth, uint64_t pitch_bytes, uint32_t w, uint32_t h,
                                                        uint32_t tiles_x, float p22, float p23, uint32_t* __restrict__ lim,
                                                        uint2* __restrict__ window) {
-    __shared__ uint32_t s_max[4];
+    __shared__ uint32_t s_max[4], s_min[4];
     const uint32_t tile = blockIdx.x, tx = tile % tiles_x, ty = tile / tiles_x;
     const uint32_t x = tx * kTile + (threadIdx.x & 15u), y = ty * kTile + (threadIdx.x >> 4);
     uint32_t l = 0u;  // (outside the image: no pixel to keep open)
-    if (x < w && y < h) {
+    const bool in = x < w && y < h;
+    if (in) {
         const float d = reinterpret_cast<const float*>(reinterpret_cast<const char*>(depth) + (size_t)y * pitch_bytes)[x];
         l = depth_limit_key(d, p22, p23);
         lim[(size_t)y * w + x] = l;
     }
-    uint32_t m = l;
+    uint32_t m = l, mn = in ? l : kDepthNoLimit;  // (outside the image: nothing to limit either)
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    if ((threadIdx.x & 63u) == 0u) s_max[threadIdx.x >> 6] = m;
+    for (int o = 32; o > 0; o >>= 1) {
+        m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+        mn = min(mn, (uint32_t)__shfl_xor((int)mn, o, 64));
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        s_max[threadIdx.x >> 6] = m;
+        s_min[threadIdx.x >> 6] = mn;
+    }
     __syncthreads();
-    if (threadIdx.x == 0) window[tile] = make_uint2(0u, max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
-}
-
-// a speculated frame: its windows [0, hi) capped by the frame's depth bounds
-__global__ __launch_bounds__(256) void k_depth_cap_windows(const uint2* __restrict__ spec, const uint2* __restrict__ bound,
-                                                            uint2* __restrict__ out, uint32_t n_tiles) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= n_tiles) return;
-    const uint2 s = spec[t];
-    out[t] = make_uint2(s.x, min(s.y, bound[t].y));
+    if (threadIdx.x == 0) {
+        window[tile] = make_uint2(0u, max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
+        lim[(size_t)w * h + tile] = min(min(s_min[0], s_min[1]), min(s_min[2], s_min[3])) == kDepthNoLimit ? 1u : 0u;
+    }
 }
 
 hipError_t launch_depth_limits(hipStream_t s, const float* depth, uint64_t pitch_bytes, uint32_t w, uint32_t h, float p22, float p23,
@@ -60,12 +62,6 @@ hipError_t launch_depth_limits(hipStream_t s, const float* depth, uint64_t pitch
     const uint32_t tiles_x = (w + kTile - 1) / kTile, tiles_y = (h + kTile - 1) / kTile;
     if (!tiles_x || !tiles_y) return hipSuccess;
     GSX_LAUNCH(k_depth_limits, dim3(tiles_x * tiles_y), dim3(256), 0, s, depth, pitch_bytes, w, h, tiles_x, p22, p23, lim, window);
-    return hipGetLastError();
-}
-
-hipError_t launch_depth_cap_windows(hipStream_t s, const uint2* spec, const uint2* bound, uint2* out, uint32_t n_tiles) {
-    if (!n_tiles) return hipSuccess;
-    GSX_LAUNCH(k_depth_cap_windows, dim3((n_tiles + 255) / 256), dim3(256), 0, s, spec, bound, out, n_tiles);
     return hipGetLastError();
 }
 

@@ -83,9 +83,16 @@ struct PyramidLds {
     unsigned long long cells;
     uint32_t a[2][kPyrLds], m[2][kPyrLds];
 };
-// every thread of ONE workgroup (NT threads); `window` may have been written by this workgroup (barrier before the call)
-template <uint32_t NT>
-__device__ inline void build_window_pyramid(const uint2* __restrict__ window, const WindowPyramid& p, uint32_t* __restrict__ data,
+// every thread of ONE workgroup (NT threads).  `window(i)` is tile i's window: a load (WindowPlane; the plane may have been written by
+// this workgroup, barrier before the call) or a value made on the way (CappedWindows).  `window.leaf(i, w)` sees every tile once, with the
+// value level 0 was built from.
+struct WindowPlane {
+    const uint2* __restrict__ w;
+    __device__ __forceinline__ uint2 operator()(uint32_t i) const { return w[i]; }
+    __device__ __forceinline__ void leaf(uint32_t, const uint2&) const {}
+};
+template <uint32_t NT, class Window>
+__device__ inline void build_window_pyramid(const Window& window, const WindowPyramid& p, uint32_t* __restrict__ data,
                                             uint32_t* __restrict__ min_ends, PyramidLds& lds) {
     if (threadIdx.x == 0) lds.cells = 0ull;
     __syncthreads();
@@ -103,12 +110,13 @@ __device__ inline void build_window_pyramid(const uint2* __restrict__ window, co
 #pragma unroll
         for (uint32_t u = 0; u < kPyrBatch; ++u) {
             const uint32_t i = base + u * NT;
-            w[u] = i < n0 ? window[i] : make_uint2(0u, 0u);
+            w[u] = i < n0 ? window(i) : make_uint2(0u, 0u);
         }
 #pragma unroll
         for (uint32_t u = 0; u < kPyrBatch; ++u) {
             const uint32_t i = base + u * NT;
             if (i >= n0) continue;
+            window.leaf(i, w[u]);
             data[i] = leaf(w[u]);
             if (min_ends) min_ends[i] = leaf_min(w[u]);
             if (mos && w[u].y > w[u].x) cells |= 1ull << ((((i / px0) >> p.cell_sy) << 3) | ((i % px0) >> p.cell_sx));
@@ -131,10 +139,10 @@ __device__ inline void build_window_pyramid(const uint2* __restrict__ window, co
             for (uint32_t u = 0; u < kB1; ++u) {
                 const uint32_t i = min(base + u * NT, n1 - 1u);
                 const uint32_t x = 2u * (i % wx), y = 2u * (i / wx), x1 = min(x + 1u, px - 1u), y1 = min(y + 1u, py - 1u);
-                a[u] = window[y * px + x];
-                b[u] = window[y * px + x1];
-                c[u] = window[y1 * px + x];
-                d[u] = window[y1 * px + x1];
+                a[u] = window(y * px + x);
+                b[u] = window(y * px + x1);
+                c[u] = window(y1 * px + x);
+                d[u] = window(y1 * px + x1);
             }
 #pragma unroll
             for (uint32_t u = 0; u < kB1; ++u) {
@@ -181,7 +189,27 @@ __global__ __launch_bounds__(1024) void k_window_pyramid(const uint2* __restrict
                                                          const uint32_t* __restrict__ d_skip, uint32_t* __restrict__ min_ends) {
     if (d_skip && *d_skip == 0) return;  // repair round with nothing to repair
     __shared__ PyramidLds lds;
-    build_window_pyramid<1024>(window, p, data, min_ends, lds);
+    build_window_pyramid<1024>(WindowPlane{window}, p, data, min_ends, lds);
+}
+
+// Depth test, a speculated frame: last frame's windows [lo, hi) capped by this frame's depth bounds, and the [max | min] pyramids of the
+// capped windows, in ONE launch (they were two: a cap kernel, then k_window_pyramid over the plane it wrote).  The capped value is
+// made where level 0 and level 1 read their windows and goes into `out` once per tile on the way: binning, the verification and
+// k_spec_next read that plane.  One 1024-lane workgroup (16 wave64), as k_window_pyramid.
+struct CappedWindows {
+    const uint2* __restrict__ spec;
+    const uint2* __restrict__ bound;
+    uint2* __restrict__ out;
+    __device__ __forceinline__ uint2 operator()(uint32_t i) const {
+        const uint2 s = spec[i];
+        return make_uint2(s.x, min(s.y, bound[i].y));
+    }
+    __device__ __forceinline__ void leaf(uint32_t i, const uint2& w) const { out[i] = w; }
+};
+__global__ __launch_bounds__(1024) void k_depth_cap_pyramid(const uint2* __restrict__ spec, const uint2* __restrict__ bound, uint2* __restrict__ out,
+                                                            WindowPyramid p, uint32_t* __restrict__ data, uint32_t* __restrict__ min_ends) {
+    __shared__ PyramidLds lds;
+    build_window_pyramid<1024>(CappedWindows{spec, bound, out}, p, data, min_ends, lds);
 }
 
 // Verification of a speculated round, ONE workgroup (8 k tiles at 1080p: eight a thread):
@@ -255,7 +283,7 @@ __global__ __launch_bounds__(1024) void k_spec_verify_fused(const uint2* __restr
             for (uint32_t b = threadIdx.x; b < vt.grid.blocks_x * vt.grid.blocks_y; b += 1024u) vt.ranges[b] = make_uint2(0u, 0u);
         return;
     }
-    if (vt.pyr2_data) build_window_pyramid<1024>(win2, vt.pyr2, vt.pyr2_data, nullptr, lds);
+    if (vt.pyr2_data) build_window_pyramid<1024>(WindowPlane{win2}, vt.pyr2, vt.pyr2_data, nullptr, lds);
     if (vt.table) {
         const uint32_t n_blocks = vt.grid.blocks_x * vt.grid.blocks_y;
         for (uint32_t b = threadIdx.x >> 6; b < n_blocks; b += 16u)
@@ -368,6 +396,14 @@ hipError_t launch_window_pyramid(hipStream_t s, const uint2* window, uint32_t ti
     WindowPyramid p = window_pyramid_layout(tiles_x, tiles_y, data);
     p.min_of_starts = min_of_starts ? 1u : 0u;
     GSX_LAUNCH(k_window_pyramid, dim3(1), dim3(1024), 0, s, window, p, data, d_skip, min_ends);
+    return hipGetLastError();
+}
+
+hipError_t launch_depth_cap_pyramid(hipStream_t s, const uint2* spec, const uint2* bound, uint2* out, uint32_t tiles_x, uint32_t tiles_y,
+                                    uint32_t* data, uint32_t* min_ends) {
+    if (!tiles_x || !tiles_y) return hipSuccess;
+    const WindowPyramid p = window_pyramid_layout(tiles_x, tiles_y, data);  // (max of the ends: min_of_starts = 0)
+    GSX_LAUNCH(k_depth_cap_pyramid, dim3(1), dim3(1024), 0, s, spec, bound, out, p, data, min_ends);
     return hipGetLastError();
 }
 

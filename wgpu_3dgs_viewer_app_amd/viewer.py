@@ -426,7 +426,10 @@ class MultiModelViewer:
     # -- depth test against the caller's depth buffer (gs::MultiModelViewer::new_with's depth_stencil, scene.rs:1969-1980) --
     def set_depth_test(self, compare) -> None:
         """``DepthStencilState { Depth32Float, depth_write_enabled: false, compare }``: ``DepthCompare.Less`` hides a splat behind the
-        depth buffer at that pixel, ``DepthCompare.Always`` (default) turns the test off."""
+        depth buffer at that pixel, ``DepthCompare.Always`` (default) turns the test off.  With ``frames_in_flight > 1`` a depth-tested
+        frame is dealt to a lane like any other and the lane takes its own snapshot: the buffer is read as if on the viewer's stream at
+        the ``render_frame`` that uses it — what is set or enqueued there afterwards waits for that read (no host wait), not for the
+        frame (``gsx.h``, the depth block)."""
         _lib.check(self._L.gsx_viewer_set_depth_test(self._h, int(compare)))
 
     def update_depth_buffer(self, depth: np.ndarray) -> None:
@@ -437,7 +440,8 @@ class MultiModelViewer:
         _lib.check(self._L.gsx_viewer_upload_depth_buffer(self._h, _f32p(d), int(d.shape[1]), int(d.shape[0])))
 
     def set_depth_buffer_device(self, ptr, width: int, height: int, row_pitch_bytes: int) -> None:
-        """Caller-owned device memory (e.g. ``tensor.data_ptr()``), read in place; ``ptr = None`` detaches it."""
+        """Caller-owned device memory (e.g. ``tensor.data_ptr()``), read in place; ``ptr = None`` detaches it.  Frames in flight that
+        were dealt before the call keep reading the buffer they were dealt with (each lane's snapshot is its own)."""
         _lib.check(self._L.gsx_viewer_set_depth_buffer_device(self._h, C.c_void_p(ptr) if ptr else None, int(width), int(height),
                                                               int(row_pitch_bytes)))
 
