@@ -266,6 +266,35 @@ gsx_status gsx_viewer_set_depth_buffer_device(gsx_viewer* v, const float* d_ptr,
  * replaces any device buffer set before. */
 gsx_status gsx_viewer_upload_depth_buffer(gsx_viewer* v, const float* host, uint32_t width, uint32_t height);
 
+/* ---- overlay lines: the app's measurement pass (MeasurementRenderer, src/renderer/measurement.rs:90-120 and :170-174,
+ *      src/shader/measurement.wgsl:22-67), which SceneCallback::paint draws before the splats with depth write on.  Drawn by the
+ *      library, so a host that shows measurement lines hands no depth attachment over (spec §9, "Overlay lines").
+ *  - A line is the reference's HitPair: two world-space ends, an RGBA8 colour and a width; on screen a trapezoid whose half-width at
+ *    an end is 0.01 * line_width * height / (2 * distance of that end from the eye), extended past each end by the same length.
+ *    Lines are drawn in array order with `Less`, depth write on and straight alpha blending; a line with an end at w <= 0 and a
+ *    line whose ends project to one point are not drawn.
+ *  - When: where the depth snapshot is taken — by the first gsx_preprocess of a frame (gsx_render_frame's included), on the viewer's
+ *    stream, and again under the snapshot's rules (the depth block above).  Also with GSX_DEPTH_ALWAYS.
+ *  - The effective depth E(p): the caller's depth buffer D(p) where one is set (it must have the viewport's size), 1 otherwise, then
+ *    lowered by every line fragment that passes `Less` against it.  The caller's buffer is never written.  With GSX_DEPTH_LESS the
+ *    splats are tested against E — no caller buffer is needed while lines are set — with GSX_DEPTH_ALWAYS the lines lie behind every
+ *    splat.  Either way the frame is final = rgb + T * line colour: gsx_download_framebuffer keeps returning the splats' (rgb, T),
+ *    gsx_download_rgba8 and gsx_resolve_rgba8_device resolve over the overlay (rgb + T (C + (1 - A) background), alpha 1 - T (1 - A)).
+ *  - gsx_viewer_set_overlay_lines between gsx_preprocess and gsx_render makes gsx_render refuse the frame, as the depth calls do.
+ *  - While lines are set a frame runs on the viewer itself (frames_in_flight > 1: one at a time, like a frame with a query), and
+ *    gsx_shard_* frames, gsx_render_more, gsx_viewer_set_band frames and an external framebuffer return GSX_ERR_INVALID_ARG.
+ *  - With no lines set (never, or cleared with n = 0) nothing of this exists: the same launches, the same bits. */
+typedef struct gsx_overlay_line { float p0[3]; uint8_t color[4]; float p1[3]; float line_width; } gsx_overlay_line; /* 32 B */
+#define GSX_OVERLAY_MAX_LINES 4096u
+/* MeasurementRenderer::update_hit_pairs (measurement.rs:133-167); host array, copied; n = 0 clears */
+gsx_status gsx_viewer_set_overlay_lines(gsx_viewer* v, const gsx_overlay_line* lines, uint32_t n);
+/* last frame's overlay: premultiplied rgba float [h][w][4] (zeros where nothing), effective depth [h][w]; either nullable; synchronises.
+ * A frame without lines has no overlay: zeros, and the caller's depth buffer (1 where there is none). */
+gsx_status gsx_download_overlay(gsx_viewer* v, float* rgba, float* depth);
+/* zero-copy: colour (float4 per pixel, meaningful only in tiles whose flag is 1), per-tile flags (u32 per 16x16 tile, row-major),
+ * effective depth (float per pixel) — of the last frame rendered with lines set; GSX_ERR_INVALID_ARG when there is none */
+gsx_status gsx_overlay_device_ptrs(gsx_viewer* v, void** rgba, void** tile_flags, void** depth);
+
 /* ---- readback (buffer.download(&device,&queue), app.rs:789, app.rs:806) ---- */
 /* float32 [height][width][4] = premultiplied r,g,b and transmittance T. Synchronises. */
 gsx_status gsx_download_framebuffer(gsx_viewer* v, float* rgbt, uint64_t n_floats);

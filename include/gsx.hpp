@@ -216,6 +216,13 @@ public:
     void set_depth_buffer_device(const float* d_ptr, UVec2 sz, uint64_t row_pitch_bytes) {
         check(gsx_viewer_set_depth_buffer_device(v_, d_ptr, sz.x, sz.y, row_pitch_bytes));
     }
+    // MeasurementRenderer::update_hit_pairs (src/renderer/measurement.rs:133-167): the measurement lines, drawn by the library with depth
+    // write before the splats of every frame from then on (gsx.h, the overlay block); an empty vector clears them
+    void update_hit_pairs(const std::vector<gsx_overlay_line>& lines) {
+        check(gsx_viewer_set_overlay_lines(v_, lines.empty() ? nullptr : lines.data(), (uint32_t)lines.size()));
+    }
+    // last frame's overlay: premultiplied rgba [size.y][size.x][4] and the effective depth [size.y][size.x]; either may be null
+    void download_overlay(float* rgba, float* depth) { check(gsx_download_overlay(v_, rgba, depth)); }
     MultiModelViewer(int device, UVec2 sz, ShCompression sh_, Cov3dCompression cov_) : sh(sh_), cov3d(cov_), size(sz) {
         gsx_viewer_desc d{GSX_ABI_VERSION, device, nullptr, sz.x, sz.y};
         check(gsx_viewer_create(&d, &v_));

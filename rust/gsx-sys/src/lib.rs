@@ -16,6 +16,7 @@ pub const GSX_RECORD_BYTES: u32 = 48;
 pub const GSX_MASK_MAX_OPS: u32 = 64;
 pub const GSX_MASK_MAX_SHAPES: u32 = 32;
 pub const GSX_QUERY_MAX_HITS: u32 = 65536;
+pub const GSX_OVERLAY_MAX_LINES: u32 = 4096;
 pub const GSX_EDIT_ENABLED: u32 = 1;
 pub const GSX_EDIT_HIDDEN: u32 = 2;
 pub const GSX_EDIT_OVERRIDE_COLOR: u32 = 4;
@@ -123,6 +124,10 @@ pub enum gsx_buffer_kind { Mask = 0, Edits = 1, Selection = 2 }
 #[repr(i32)]
 #[derive(Clone, Copy, PartialEq, Eq)]
 pub enum gsx_depth_compare { Always = 0, Less = 1 } // the compare of new_with's depth_stencil, src/tab/scene.rs:1969-1980
+/// the app's measurement `HitPair` (src/renderer/measurement.rs:177-184), 32 bytes: world-space ends, RGBA8 colour, width
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gsx_overlay_line { pub p0: [f32; 3], pub color: [u8; 4], pub p1: [f32; 3], pub line_width: f32 }
 /// the two collectives of a caller-supplied transport: they ENQUEUE on `hip_stream` and return 0 or a gsx_status
 pub type gsx_comm_all_to_all_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, d_send: *const c_void, d_recv: *mut c_void, bytes_per_peer: u64, hip_stream: *mut c_void) -> gsx_status>;
 pub type gsx_comm_all_gather_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, d_send: *const c_void, d_recv: *mut c_void, bytes_per_rank: u64, hip_stream: *mut c_void) -> gsx_status>;
@@ -177,6 +182,9 @@ extern "C" {
     pub fn gsx_viewer_set_depth_test(v: *mut gsx_viewer, compare: gsx_depth_compare) -> gsx_status;
     pub fn gsx_viewer_set_depth_buffer_device(v: *mut gsx_viewer, d_ptr: *const f32, width: u32, height: u32, row_pitch_bytes: u64) -> gsx_status;
     pub fn gsx_viewer_upload_depth_buffer(v: *mut gsx_viewer, host: *const f32, width: u32, height: u32) -> gsx_status;
+    pub fn gsx_viewer_set_overlay_lines(v: *mut gsx_viewer, lines: *const gsx_overlay_line, n: u32) -> gsx_status;
+    pub fn gsx_download_overlay(v: *mut gsx_viewer, rgba: *mut f32, depth: *mut f32) -> gsx_status;
+    pub fn gsx_overlay_device_ptrs(v: *mut gsx_viewer, rgba: *mut *mut c_void, tile_flags: *mut *mut c_void, depth: *mut *mut c_void) -> gsx_status;
     pub fn gsx_download_framebuffer(v: *mut gsx_viewer, rgbt: *mut f32, n_floats: u64) -> gsx_status;
     pub fn gsx_download_rgba8(v: *mut gsx_viewer, background_rgb: *const f32, rgba: *mut u8, n_bytes: u64) -> gsx_status;
     pub fn gsx_framebuffer_device_ptr(v: *mut gsx_viewer, out_ptr: *mut *mut c_void, out_w: *mut u32, out_h: *mut u32) -> gsx_status;

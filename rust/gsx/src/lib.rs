@@ -214,6 +214,20 @@ impl<G: GaussianPod> MultiModelViewer<G> {
         }
         check(unsafe { sys::gsx_viewer_upload_depth_buffer(self.handle.0, depth.as_ptr(), size.0, size.1) })
     }
+    /// `MeasurementRenderer::update_hit_pairs(&device, &hit_pairs, &camera)` (src/renderer/measurement.rs:133-167): the measurement
+    /// lines, drawn by the library with depth write before the splats of every frame from then on (`gsx.h`, the overlay block) — no
+    /// depth attachment has to be handed over for them.  An empty slice clears them.
+    pub fn update_hit_pairs(&mut self, hit_pairs: &[sys::gsx_overlay_line]) -> Result<(), Error> {
+        let p = if hit_pairs.is_empty() { std::ptr::null() } else { hit_pairs.as_ptr() };
+        check(unsafe { sys::gsx_viewer_set_overlay_lines(self.handle.0, p, hit_pairs.len() as u32) })
+    }
+    /// Last frame's overlay: premultiplied rgba `[height][width][4]` and the effective depth `[height][width]` the splats were tested against.
+    pub fn download_overlay(&mut self, size: (u32, u32)) -> Result<(Vec<f32>, Vec<f32>), Error> {
+        let n = size.0 as usize * size.1 as usize;
+        let (mut rgba, mut depth) = (vec![0f32; 4 * n], vec![0f32; n]);
+        check(unsafe { sys::gsx_download_overlay(self.handle.0, rgba.as_mut_ptr(), depth.as_mut_ptr()) })?;
+        Ok((rgba, depth))
+    }
     /// `GaussianBuffers::new_empty(&device, count)` + `BindGroups::new(..)` + `models.insert(key, ..)` (scene.rs:2111-2139)
     pub fn insert_model(&mut self, key: &str, count: usize) -> Result<(), Error> {
         let k = CString::new(key).unwrap();

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """What the depth test (gsx_viewer_set_depth_test) costs on cfg4's orbit (10 M Gaussians, SH-3, 1920x1080), one process, one GPU.
 
-Four modes, in alternating blocks of --block frames so that drift of the box hits them alike:
+Five modes, in alternating blocks of --block frames so that drift of the box hits them alike:
   off              no depth test (the headline schedule)
   cleared          GSX_DEPTH_LESS against a cleared buffer (all 1.0): the same pixels, the extra work of the test
   occluder         GSX_DEPTH_LESS against a box at view depth --box-depth over the middle quarter of the screen (half the width, half the height)
   occluder_upload  the same box, handed over from host memory EVERY frame (gsx_viewer_upload_depth_buffer: a copy and a wait)
+  lines16          GSX_DEPTH_LESS against 16 measurement lines drawn by the library (gsx_viewer_set_overlay_lines), no caller buffer: what
+                   a host that shows measurement lines does instead of occluder_upload.  On a viewer of its own (a second copy of the
+                   model): an uploaded buffer stays with its viewer, and this row is the one without any
 cleared and occluder read a device buffer in place (gsx_viewer_set_depth_buffer_device, set once), as an app whose depth attachment is
 device memory does: the buffer is read by every frame's first preprocess whether or not it changed.
 The host waits for every frame (gsx_render_frame + gsx_sync), as the app does.  Prints ONE JSON line: fps per mode (median of its
@@ -32,7 +35,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from wgpu_3dgs_viewer_app_amd import camera, scene  # noqa: E402
-from wgpu_3dgs_viewer_app_amd.viewer import DepthCompare, GaussianDisplayMode, GaussianShDegree, MultiModelViewer  # noqa: E402
+from wgpu_3dgs_viewer_app_amd.viewer import DepthCompare, GaussianDisplayMode, GaussianShDegree, HitPair, MultiModelViewer  # noqa: E402
 
 
 def main() -> None:
@@ -52,11 +55,17 @@ def main() -> None:
     torch.zeros(1, device="cuda")   # (torch's lazy device initialisation fails behind gigabytes of libgsx allocations: first)
     n, sh, w, h, seed = scene.CONFIGS[a.config]
     g = scene.synthetic_gaussians(n, seed, sh)
-    v = MultiModelViewer()
-    v.add_model("m", n)
-    v.models["m"].gaussian_buffers.gaussians_buffer.update_range(0, g)
+    viewers = []
+    for _ in range(1 if a.inflight_only else 2):   # (the second one is the lines16 row's)
+        v = MultiModelViewer()
+        v.add_model("m", n)
+        v.models["m"].gaussian_buffers.gaussians_buffer.update_range(0, g)
+        v.update_gaussian_transform(1.0, GaussianDisplayMode.Splat, GaussianShDegree.new(sh), False)
+        viewers.append(v)
     del g
-    v.update_gaussian_transform(1.0, GaussianDisplayMode.Splat, GaussianShDegree.new(sh), False)
+    v, vl = viewers[0], viewers[-1]
+    rng = np.random.default_rng(16)
+    lines16 = np.concatenate([HitPair(p, p + rng.uniform(-1.5, 1.5, 3), rng.integers(60, 256, 4), 30.0) for p in rng.uniform(-2.0, 2.0, (16, 3))])
     orbit = [camera.PrecomputedCamera(camera.orbit_pose(k), w / h) for k in range(240)]
     p = np.asarray(orbit[0].projection(w / h), np.float32).reshape(16)
     box = np.float32(np.float32(p[14]) / np.float32(a.box_depth) - np.float32(p[10]))   # the NDC depth a surface there writes
@@ -65,20 +74,25 @@ def main() -> None:
     occluder[h // 4: 3 * h // 4, w // 4: 3 * w // 4] = box
     dev = {"cleared": torch.from_numpy(cleared).cuda(), "occluder": torch.from_numpy(occluder).cuda()}
     torch.cuda.synchronize()
-    modes = {"off": None, "cleared": cleared, "occluder": occluder, "occluder_upload": occluder}
+    modes = {"off": None, "cleared": cleared, "occluder": occluder, "occluder_upload": occluder, "lines16": None}
     buffers = dict(modes)
     frame = [0]
 
-    def select(mode: str) -> None:
+    def select(mode: str):
+        if mode == "lines16":
+            vl.set_depth_test(DepthCompare.Less)
+            vl.update_hit_pairs(lines16)
+            return vl
         v.set_depth_test(DepthCompare.Always if buffers[mode] is None else DepthCompare.Less)
         if mode in dev:
             v.set_depth_buffer_device(dev[mode].data_ptr(), w, h, 4 * w)
         elif buffers[mode] is not None:
             v.update_depth_buffer(buffers[mode])
+        return v
 
     def run(mode: str, frames: int) -> float:
-        v.set_render_options(frames_in_flight=1)   # (the --inflight rows leave two)
-        select(mode)
+        viewers[0].set_render_options(frames_in_flight=1)   # (the --inflight rows leave two)
+        v = select(mode)
         upload = mode == "occluder_upload"
         v.poll()
         t0 = time.perf_counter()
@@ -92,8 +106,8 @@ def main() -> None:
         return frames / (time.perf_counter() - t0)
 
     def run_unsync(mode: str, fif: int, frames: int) -> float:
-        v.set_render_options(frames_in_flight=fif)
-        select(mode)
+        viewers[0].set_render_options(frames_in_flight=fif)
+        v = select(mode)
         v.poll()
         t0 = time.perf_counter()
         for _ in range(frames):
@@ -117,16 +131,17 @@ def main() -> None:
             fps[m].append(run(m, a.block))
         for m, fif in unsync:
             fps_u[f"{m}_unsync_fif{fif}"].append(run_unsync(m, fif, a.block))
-    v.set_render_options(frames_in_flight=1)
+    viewers[0].set_render_options(frames_in_flight=1)
     stats = {}
     for m in modes:
-        select(m)
-        v.update_camera(orbit[0], (w, h))
-        v.render_frame(["m"])
-        v.poll()
-        stats[m] = v.frame_stats("m")
-    v.set_depth_buffer_device(None, 0, 0, 0)
-    v.close()
+        sv = select(m)
+        sv.update_camera(orbit[0], (w, h))
+        sv.render_frame(["m"])
+        sv.poll()
+        stats[m] = sv.frame_stats("m")
+    viewers[0].set_depth_buffer_device(None, 0, 0, 0)
+    for v in viewers:
+        v.close()
     med = {m: statistics.median(x) for m, x in fps.items()}
     out = {
         "tool": "bench_depth", "config": a.config, "gaussians": n, "size": [w, h], "host_waits_per_frame": True,
@@ -134,6 +149,8 @@ def main() -> None:
         "fps": {m: round(x, 1) for m, x in med.items()},
         "fps_blocks": {m: [round(y, 1) for y in x] for m, x in fps.items()},
         "ratio_to_off": {m: round(med[m] / med["off"], 4) for m in modes},
+        "lines16_over_cleared": round(med["lines16"] / med["cleared"], 4) if "lines16" in med else None,
+        "lines16_over_occluder_upload": round(med["lines16"] / med["occluder_upload"], 4) if "lines16" in med else None,
         "pose0_stats": stats,
     }
     if unsync:

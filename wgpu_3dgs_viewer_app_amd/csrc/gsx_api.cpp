@@ -102,10 +102,11 @@ static gsx_status lane_create(gsx_viewer* v, gsx_viewer** out) {
 // may this frame go to a lane?  (a frame with a query — its flags feed gsx_postprocess — and everything multi-GPU stays on the
 // viewer; selections, edits and the highlight travel: a lane's shadow models view the owner's selection and edit buffers, which
 // the owner prepares before the frame is dealt out, prepare_edits_for_lanes; a depth-tested frame travels too: the lane takes its
-// own snapshot of the depth buffer, lane_sync / depth_snapshot — unless GSX_DEPTH_LANES=0 keeps it on the viewer)
+// own snapshot of the depth buffer, lane_sync / depth_snapshot — unless GSX_DEPTH_LANES=0 keeps it on the viewer; a frame with overlay
+// lines stays on the viewer, which owns the overlay's buffers)
 static bool frame_may_overlap(gsx_viewer* v, const char* const* keys, uint32_t n_keys) {
     if (v->parent || v->options.frames_in_flight < 2 || v->query.kind != GSX_QUERY_NONE || v->ext_fb || v->band_lo != 0 ||
-        v->band_hi != 0xFFFFFFFFu || (v->depth_compare != GSX_DEPTH_ALWAYS && !v->depth_lanes))
+        v->band_hi != 0xFFFFFFFFu || (v->depth_compare != GSX_DEPTH_ALWAYS && !v->depth_lanes) || v->overlay_n)
         return false;
     for (uint32_t i = 0; i < n_keys; ++i) {
         Model* m = find_model(v, keys ? keys[i] : nullptr);
@@ -758,7 +759,11 @@ gsx_status gsx_download_rgba8(gsx_viewer* v, const float bg[3], uint8_t* rgba, u
     if ((st = ensure_fb(v))) return st;
     if ((st = finish_frame(v))) return st;
     HIPCHK(v->scratch.ensure(4 * npx));
-    HIPCHK(launch_resolve_rgba8(v->stream, fb_ptr(v), (uint32_t)npx, bg[0], bg[1], bg[2], v->scratch.as<uint32_t>()));
+    if (overlay_resolves(v))
+        HIPCHK(launch_resolve_rgba8_overlay(v->stream, fb_ptr(v), 0u, (uint32_t)npx, v->width, bg[0], bg[1], bg[2], v->overlay_rgba.as<float4>(),
+                                            v->overlay_flags.as<uint32_t>(), v->scratch.as<uint32_t>()));
+    else
+        HIPCHK(launch_resolve_rgba8(v->stream, fb_ptr(v), (uint32_t)npx, bg[0], bg[1], bg[2], v->scratch.as<uint32_t>()));
     HIPCHK(gsx::op::StreamSynchronize(v->stream));
     HIPCHK(gsx::op::Memcpy(rgba, v->scratch.p, 4 * npx, hipMemcpyDeviceToHost));
     return GSX_OK;

@@ -386,27 +386,53 @@ static gsx_status ensure_msd(gsx_viewer* v, Model* m, DevBuf& ws);
 // viewport or P22 / P23 (recorded with it; gsx_update_camera ends it as well), the end of a frame (gsx_render / gsx_render_frame; every
 // gsx_render_frame starts with a fresh one), and a model preprocessed a second time against it (a new frame whose predecessor failed or
 // was never rendered).  Nothing is ever composited against another frame's snapshot.
+// Overlay lines (gsx_viewer_set_overlay_lines): while lines are set the same snapshot draws them — with either compare — and the limits are
+// made from the effective depth E(p) in the raster launch itself (kernels_overlay.hip); without a caller buffer D = 1.
 static gsx_status depth_snapshot(gsx_viewer* v, const Model* m) {
+    const bool test = v->depth_compare == GSX_DEPTH_LESS, lines = v->overlay_n != 0;
     // z_ndc = z_c / w_c < D  <=>  view depth < P23 / (D + P22) needs the third and fourth rows to depend on view z alone, and
     // z_ndc = P23 / d - P22 to grow with d towards 1 (P23 < 0, P22 <= -1: D + P22 < 0 for every D < 1).  A reversed-Z projection
     // (P23 > 0) turns the inequality round: the limit would show exactly the splats the test hides.
     const float* P = v->proj;  // column-major: P[col * 4 + row]
-    if (!(P[2] == 0.0f && P[6] == 0.0f && P[3] == 0.0f && P[7] == 0.0f && P[15] == 0.0f && P[11] == -1.0f && P[14] < 0.0f && P[10] <= -1.0f))
+    if (test && !(P[2] == 0.0f && P[6] == 0.0f && P[3] == 0.0f && P[7] == 0.0f && P[15] == 0.0f && P[11] == -1.0f && P[14] < 0.0f && P[10] <= -1.0f))
         return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: the depth test needs a perspective projection (P20 = P21 = P30 = P31 = P33 = 0, "
                     "P32 = -1, P23 < 0, P22 <= -1, as perspective_rh); this one is not");
     const float* src = v->depth_dev ? v->depth_dev : v->depth_owned.as<float>();
-    if (!src || !v->depth_w) return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: the depth test is on and no depth buffer was given "
-                                         "(gsx_viewer_upload_depth_buffer / gsx_viewer_set_depth_buffer_device)");
-    if (v->depth_w != v->width || v->depth_h != v->height)
+    if (!src || !v->depth_w) {
+        if (!lines) return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: the depth test is on and no depth buffer was given "
+                                "(gsx_viewer_upload_depth_buffer / gsx_viewer_set_depth_buffer_device)");
+        src = nullptr;  // (lines and no caller buffer: D = 1)
+    }
+    if (src && (v->depth_w != v->width || v->depth_h != v->height))
         return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: the depth buffer is %ux%u, the viewport %ux%u", v->depth_w, v->depth_h, v->width, v->height);
     if (v->depth_snap && !v->depth_frame_closed && v->depth_snap_cfg == v->depth_cfg && v->depth_snap_w == v->width &&
-        v->depth_snap_h == v->height && v->depth_snap_p22 == P[10] && v->depth_snap_p23 == P[14] && m->depth_snap != v->depth_snap)
+        v->depth_snap_h == v->height && v->depth_snap_p22 == P[10] && v->depth_snap_p23 == P[14] &&
+        (test ? m->depth_snap : m->overlay_snap) != v->depth_snap)
         return GSX_OK;
     const uint32_t tiles_x = (v->width + GSX_TILE - 1) / GSX_TILE, tiles_y = (v->height + GSX_TILE - 1) / GSX_TILE;
-    HIPCHK(v->depth_lim.ensure(4 * ((size_t)v->width * v->height + (size_t)tiles_x * tiles_y)));  // (+ one word per tile: "no pixel has a limit")
-    HIPCHK(v->depth_win.ensure(sizeof(uint2) * (size_t)tiles_x * tiles_y));
-    HIPCHK(launch_depth_limits(v->stream, src, v->depth_dev ? v->depth_pitch : 4ull * v->depth_w, v->width, v->height, P[10], P[14],
-                               v->depth_lim.as<uint32_t>(), v->depth_win.as<uint2>()));
+    if (test) {
+        HIPCHK(v->depth_lim.ensure(4 * ((size_t)v->width * v->height + (size_t)tiles_x * tiles_y)));  // (+ one word per tile: "no pixel has a limit")
+        HIPCHK(v->depth_win.ensure(sizeof(uint2) * (size_t)tiles_x * tiles_y));
+    }
+    const uint64_t pitch = v->depth_dev ? v->depth_pitch : 4ull * v->depth_w;
+    if (lines) {
+        const size_t npx = (size_t)v->width * v->height;
+        HIPCHK(v->overlay_rec.ensure(sizeof(OverlayRec) * (size_t)v->overlay_n));
+        HIPCHK(v->overlay_rgba.ensure(sizeof(float4) * npx));
+        HIPCHK(v->overlay_eff.ensure(4 * npx));
+        HIPCHK(v->overlay_flags.ensure(4 * (size_t)tiles_x * tiles_y));
+        OverlayCamera cam;
+        memcpy(cam.view, v->view, sizeof cam.view);
+        memcpy(cam.proj, v->proj, sizeof cam.proj);
+        HIPCHK(launch_overlay(v->stream, v->overlay_lines.as<gsx_overlay_line>(), v->overlay_n, cam, src, pitch, v->width, v->height, P[10], P[14],
+                              v->overlay_rec.as<OverlayRec>(), v->overlay_rgba.as<float4>(), v->overlay_flags.as<uint32_t>(),
+                              v->overlay_eff.as<float>(), test ? v->depth_lim.as<uint32_t>() : nullptr, test ? v->depth_win.as<uint2>() : nullptr));
+        v->overlay_valid = true;
+        v->overlay_w = v->width;
+        v->overlay_h = v->height;
+    } else {
+        HIPCHK(launch_depth_limits(v->stream, src, pitch, v->width, v->height, P[10], P[14], v->depth_lim.as<uint32_t>(), v->depth_win.as<uint2>()));
+    }
     v->depth_snap += 1;
     v->depth_snap_cfg = v->depth_cfg;
     v->depth_snap_w = v->width;
@@ -486,13 +512,22 @@ gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
     // depth test: every tile's window ends at its depth bound — on plain frames too: a record hidden on every tile of its rectangle
     // never enters the depth sort (exact, not speculative: it could not be blended anyway)
     const bool depth = v->depth_compare == GSX_DEPTH_LESS;
-    if (depth) {
-        if (shard_lazy || m->use_imported) return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess('%s'): sharded frames do not support the depth test", m->key.c_str());
+    const bool lines = v->overlay_n != 0;  // overlay lines: drawn by the same snapshot, with either compare
+    if (lines) {
+        if (shard_lazy || m->use_imported) return overlay_refuses(v, "gsx_preprocess", "sharded frames do");
+        if (v->band_lo != 0 || v->band_hi != 0xFFFFFFFFu) return overlay_refuses(v, "gsx_preprocess", "band frames (gsx_viewer_set_band) do");
+        if (v->ext_fb) return overlay_refuses(v, "gsx_preprocess", "frames into an external framebuffer do");
+    } else {
+        v->overlay_valid = false;
+    }
+    if (depth || lines) {
+        if (depth && (shard_lazy || m->use_imported)) return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess('%s'): sharded frames do not support the depth test", m->key.c_str());
         st = depth_snapshot(v, m);   // (reads which snapshot this model was preprocessed against last)
-        m->depth_snap = st ? 0 : v->depth_snap;
+        m->depth_snap = st || !depth ? 0 : v->depth_snap;
+        m->overlay_snap = st || !lines ? 0 : v->depth_snap;
         if (st) return st;
     } else {
-        m->depth_snap = 0;
+        m->depth_snap = m->overlay_snap = 0;
     }
     if (m->spec_round1 && depth) {  // last frame's windows capped by this frame's depth bounds, and their pyramids
         const uint32_t n_tiles = m->fc.tiles_x * m->fc.tiles_y;
@@ -835,6 +870,11 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
         return fail(GSX_ERR_INVALID_ARG, "gsx_render: viewport changed since gsx_preprocess('%s')", m->key.c_str());
     // depth test: the model's admission was made against a depth snapshot; it must be the one this frame composites with
     const bool depth = m->depth_snap != 0;
+    // ... and so are the overlay lines it was preprocessed with
+    if ((v->overlay_n || m->overlay_snap) && (m->overlay_snap != v->depth_snap || v->depth_snap_cfg != v->depth_cfg || v->depth_snap_w != m->fc.w_px ||
+                                              v->depth_snap_h != m->fc.h_px))
+        return fail(GSX_ERR_INVALID_ARG, "gsx_render: the overlay lines, the depth test or its depth buffer changed since gsx_preprocess('%s'); call "
+                    "gsx_preprocess + gsx_sort('%s') again", m->key.c_str(), m->key.c_str());
     if (v->depth_compare == GSX_DEPTH_LESS ? (m->depth_snap != v->depth_snap || v->depth_snap_cfg != v->depth_cfg || v->depth_snap_w != m->fc.w_px ||
                                               v->depth_snap_h != m->fc.h_px) : depth)
         return fail(GSX_ERR_INVALID_ARG, "gsx_render: the depth test or its depth buffer changed since gsx_preprocess('%s'); call gsx_preprocess + "

@@ -742,6 +742,38 @@ hipError_t launch_spec_next(hipStream_t s, const uint32_t* tile_sat, const uint3
 // a limit (the compositors read it: lim holds w * h + tiles words); window: per tile {0, max of its pixels' limits}.
 hipError_t launch_depth_limits(hipStream_t s, const float* depth, uint64_t pitch_bytes, uint32_t w, uint32_t h, float p22, float p23,
                                uint32_t* lim, uint2* window);
+constexpr uint32_t kDepthNoLimit = 0xFFFFFFFFu;
+// D >= 1 (a cleared buffer): no limit.  D <= 0 or NaN: every splat hidden (`Less` against NaN is false).
+__device__ __forceinline__ uint32_t depth_limit_key(float d, float p22, float p23) {
+    if (!(d > 0.0f)) return 0u;
+    if (d >= 1.0f) return kDepthNoLimit;
+    const float lim = p23 / (d + p22);
+    return lim > 0.0f ? __float_as_uint(lim) : 0u;
+}
+
+// Overlay lines (kernels_overlay.hip; spec section 9): the reference's measurement pass, drawn where the depth snapshot is taken.
+// One record per line, written by the set-up launch and walked in array order by the raster launch.
+struct alignas(16) OverlayRec {
+    float cx[4], cy[4];          // pixel-space corners: end 1 -, end 1 +, end 0 -, end 0 +
+    float z0, z1;                // NDC depth of end 0 / end 1 (the corners of an end carry its depth)
+    float gx, gy;                // depth(p) = z1 + gx (p.x - cx[0]) + gy (p.y - cy[0]): the affine function both triangles interpolate
+    int32_t bx0, by0, bx1, by1;  // pixel box of the pixel centres the corners enclose, clamped to the viewport, max exclusive
+    float r, g, b, a;            // straight colour
+    uint32_t drawn, pad[3];
+};
+static_assert(sizeof(OverlayRec) == 96, "OverlayRec is staged through LDS as six uint4");
+struct OverlayCamera {
+    float view[16], proj[16];    // column-major, as gsx_update_camera takes them
+};
+// lines: n x gsx_overlay_line (device).  rec: n records.  depth (nullable: D = 1) / pitch_bytes: the caller's depth buffer.
+// rgba: float4 per pixel, written only for tiles whose flag word is 1 (some drawn line's box touches the tile); eff: E(p) per pixel.
+// lim / window (both null or both set): what launch_depth_limits writes, made from E(p) in the same launch.
+hipError_t launch_overlay(hipStream_t s, const gsx_overlay_line* lines, uint32_t n, const OverlayCamera& cam, const float* depth,
+                          uint64_t pitch_bytes, uint32_t w, uint32_t h, float p22, float p23, OverlayRec* rec, float4* rgba,
+                          uint32_t* tile_flags, float* eff, uint32_t* lim, uint2* window);
+// the RGBA8 resolve over an overlay: out.rgb = rgb + T (C + (1 - A) background), alpha = 1 - T (1 - A); pixels [first, first + n_px)
+hipError_t launch_resolve_rgba8_overlay(hipStream_t s, const float4* fb, uint32_t first, uint32_t n_px, uint32_t w, float bg_r, float bg_g,
+                                        float bg_b, const float4* overlay_rgba, const uint32_t* tile_flags, uint32_t* out_rgba8);
 // out[t] = {spec[t].x, min(spec[t].y, bound[t].y)} and, in the same launch, the max-pyramid (data) and the min-pyramid (min_ends) of `out`
 // as launch_window_pyramid builds them (kernels_spec.hip)
 hipError_t launch_depth_cap_pyramid(hipStream_t s, const uint2* spec, const uint2* bound, uint2* out, uint32_t tiles_x, uint32_t tiles_y,

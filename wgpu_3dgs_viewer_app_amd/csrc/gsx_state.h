@@ -177,6 +177,8 @@ struct Model {
     // depth test (gsx_viewer_set_depth_test): the viewer's depth snapshot this model was preprocessed against (0: none, the test was
     // off), and a speculated frame's windows capped by the depth bounds with their [max | min] pyramids
     uint64_t depth_snap = 0;
+    // overlay lines (gsx_viewer_set_overlay_lines): the snapshot this model was preprocessed against while lines were set (0: none were)
+    uint64_t overlay_snap = 0;
     DevBuf spec_dwin, spec_dpyr;
     // speculation that keeps repairing does not pay (sparse scenes whose tiles hover around saturation): the lazily read
     // statistics keep a history of "this frame needed the repair round"; too many -> unspeculated frames for a while
@@ -462,6 +464,12 @@ struct gsx_viewer {
     float depth_snap_p22 = 0.0f, depth_snap_p23 = 0.0f;
     hipEvent_t depth_event = nullptr;    // lane: its last snapshot has read the depth buffer (the owner's stream waits for it: depth_snapshot)
     bool depth_lanes = true;             // GSX_DEPTH_LANES=0: depth-tested frames run on the viewer itself, one at a time (A/B)
+    // overlay lines (gsx_viewer_set_overlay_lines, kernels_overlay.hip; owner only: a frame with lines runs on the viewer itself).  Drawn by
+    // depth_snapshot — with either compare — in place of k_depth_limits; a change of the lines bumps depth_cfg.  overlay_valid: the last frame
+    // preprocessed on this viewer drew them (the resolve and gsx_download_overlay read overlay_rgba / _flags / _eff of overlay_w x overlay_h)
+    uint32_t overlay_n = 0, overlay_w = 0, overlay_h = 0;
+    bool overlay_valid = false;
+    DevBuf overlay_lines, overlay_rec, overlay_rgba, overlay_flags, overlay_eff;
     gsx_render_options options{1u, 16u, 131072u, 2u, 1u, 0.25f, 3u, 0u, 1u, 1u};  // = gsx_render_options_default (a CPU test compares the two: gsx_viewer_get_render_options)
     bool host_waited = false;  // the host has waited for this viewer's device work (gsx_sync, a blocking readback) since its last frame was enqueued:
                                // the app synchronises per frame, so asking for a speculated frame's verdict costs it nothing (host_verify = 2)
@@ -595,11 +603,21 @@ inline gsx_status ensure_fb(gsx_viewer* v) {
 }
 // readback entry points refer to the newest frame, whichever lane rendered it
 inline gsx_viewer* result_lane(gsx_viewer* v) { return v->latest ? v->latest : v; }
+// the overlay lines are part of neither the sharded frames nor band frames nor frames into an external framebuffer (gsx_preprocess checks the latter two)
+inline gsx_status overlay_refuses(const gsx_viewer* v, const char* fn, const char* what) {
+    if (v && v->overlay_n)
+        return fail(GSX_ERR_INVALID_ARG, "%s: %s not support the overlay lines (gsx_viewer_set_overlay_lines(v, NULL, 0) first)", fn, what);
+    return GSX_OK;
+}
 // the depth test is not part of the sharded (multi-GPU) frames yet: every entry point of theirs refuses while it is on
 inline gsx_status depth_refuses_shard(const gsx_viewer* v, const char* fn) {
     if (v && v->depth_compare != GSX_DEPTH_ALWAYS)
         return fail(GSX_ERR_INVALID_ARG, "%s: sharded frames do not support the depth test (gsx_viewer_set_depth_test(v, GSX_DEPTH_ALWAYS) first)", fn);
-    return GSX_OK;
+    return overlay_refuses(v, fn, "sharded frames do");
+}
+// does the RGBA8 resolve of this viewer's frame go over an overlay?  (lines are set and its last frame drew them, at this viewport)
+inline bool overlay_resolves(const gsx_viewer* v) {
+    return v->overlay_n && v->overlay_valid && !v->parent && !v->ext_fb && v->overlay_w == v->width && v->overlay_h == v->height;
 }
 inline float4* fb_ptr(gsx_viewer* v) { return v->ext_fb ? static_cast<float4*>(v->ext_fb) : reinterpret_cast<float4*>(v->fb.p); }
 

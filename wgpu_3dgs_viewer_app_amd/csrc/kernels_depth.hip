@@ -15,15 +15,7 @@
 
 namespace gsx {
 
-constexpr uint32_t kDepthNoLimit = 0xFFFFFFFFu;
-
-// D >= 1 (a cleared buffer): no limit.  D <= 0 or NaN: every splat hidden (`Less` against NaN is false).
-__device__ __forceinline__ uint32_t depth_limit_key(float d, float p22, float p23) {
-    if (!(d > 0.0f)) return 0u;
-    if (d >= 1.0f) return kDepthNoLimit;
-    const float lim = p23 / (d + p22);
-    return lim > 0.0f ? __float_as_uint(lim) : 0u;
-}
+// (kDepthNoLimit and depth_limit_key live in gsx_internal.h: the overlay raster, kernels_overlay.hip, makes the same keys from E(p))
 
 // one 256-lane workgroup per tile, one pixel per lane.  Behind the w x h limits, one word per tile: 1 when no pixel of the tile has a
 // limit (the minimum of its pixels' limits is "none") — the compositors take such a tile through their loop without the compare.

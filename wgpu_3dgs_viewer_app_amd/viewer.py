@@ -78,6 +78,22 @@ class Cov3dKind(enum.IntEnum):
     Half = 1
 
 
+#: ``gsx_overlay_line``: the reference's measurement ``HitPair`` (src/renderer/measurement.rs:177-184), 32 bytes
+HIT_PAIR_DTYPE = np.dtype([("p0", "<f4", 3), ("color", "u1", 4), ("p1", "<f4", 3), ("line_width", "<f4")])
+
+
+def HitPair(p0, p1, color=(255, 255, 255, 255), line_width: float = 1.0) -> np.ndarray:
+    """One measurement line as a 32-byte record: world-space ends ``p0`` / ``p1``, an RGBA8 colour, a width (its on-screen
+    half-width at an end is ``0.01 * line_width * height / (2 * distance from the eye)``).  Concatenate records (or pass a
+    list of them) to ``MultiModelViewer.update_hit_pairs``."""
+    r = np.zeros(1, HIT_PAIR_DTYPE)
+    r["p0"] = np.asarray(p0, np.float32)
+    r["p1"] = np.asarray(p1, np.float32)
+    r["color"] = np.asarray(color, np.uint8)
+    r["line_width"] = np.float32(line_width)
+    return r
+
+
 def _f32p(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
@@ -444,6 +460,34 @@ class MultiModelViewer:
         were dealt before the call keep reading the buffer they were dealt with (each lane's snapshot is its own)."""
         _lib.check(self._L.gsx_viewer_set_depth_buffer_device(self._h, C.c_void_p(ptr) if ptr else None, int(width), int(height),
                                                               int(row_pitch_bytes)))
+
+    # -- overlay lines: the app's measurement pass, drawn by the library with depth write (src/renderer/measurement.rs) --
+    def update_hit_pairs(self, lines) -> None:
+        """``MeasurementRenderer::update_hit_pairs``: ``HitPair`` records (an array of ``HIT_PAIR_DTYPE``, or a sequence of them);
+        empty or ``None`` clears.  The lines are drawn by the first ``preprocess`` of every frame from then on, `Less` with depth
+        write against the caller's depth buffer (1 where there is none); with ``DepthCompare.Less`` the splats are tested against
+        the result (``gsx.h``, the overlay block)."""
+        if lines is None or len(lines) == 0:
+            _lib.check(self._L.gsx_viewer_set_overlay_lines(self._h, None, 0))
+            return
+        if not isinstance(lines, np.ndarray):
+            lines = np.concatenate([np.asarray(x, HIT_PAIR_DTYPE).reshape(-1) for x in lines])
+        a = np.ascontiguousarray(lines, HIT_PAIR_DTYPE).reshape(-1)
+        _lib.check(self._L.gsx_viewer_set_overlay_lines(self._h, a.ctypes.data, int(a.shape[0])))
+
+    def download_overlay(self):
+        """``(rgba, depth)`` of the last frame's overlay: premultiplied float32 [H, W, 4] (zeros where no line is) and the effective
+        depth float32 [H, W] the splats were (or would be) tested against."""
+        w, h = self.size
+        rgba, depth = np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32)
+        _lib.check(self._L.gsx_download_overlay(self._h, _f32p(rgba), _f32p(depth)))
+        return rgba, depth
+
+    def overlay_device_ptrs(self):
+        """Device addresses ``(rgba, tile_flags, depth)`` of the last frame's overlay (zero-copy consumers)."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(self._L.gsx_overlay_device_ptrs(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def set_render_options(self, **kw) -> None:
         """``gsx_render_options``: progressive depth slabs (default on), first_slab_divisor, min_slab, growth."""
