@@ -75,7 +75,7 @@ def test_block_lists_layered_models_and_display_modes(monkeypatch):
 @pytest.mark.parametrize("speculative", [0, 1])
 def test_dispatch_order_is_a_schedule_not_data(monkeypatch, speculative):
     """The block compositor takes its tiles expensive-first (tile_order_job: last frame's cost per tile, two classes, made by one more
-    workgroup of the first slab's k_block_counts); GSX_TILE_ORDER=0 keeps index order.  Same pixels bit for bit — a scene whose cost
+    workgroup of the first slab's k_block_bin); GSX_TILE_ORDER=0 keeps index order.  Same pixels bit for bit — a scene whose cost
     is concentrated in part of the screen so that both classes are populated, a viewport change (the order is rebuilt), layered
     models (tiles that return early under `carry`), frames in flight (every lane has an order of its own)."""
     rng = np.random.default_rng(77)

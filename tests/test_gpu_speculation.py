@@ -528,6 +528,28 @@ def test_speculation_steps_aside_when_it_does_not_pay():
     plain.close()
 
 
+def test_tuner_cycle_before_any_timing_matters():
+    """The part of the speculation tuner's cycle that depends on no timing (csrc/spec_tuner.h; tests/test_spec_tuner_cpu.py plays the rest
+    on the CPU): default options, one frame in flight, gsx_render_frame + gsx_sync per frame.  Frame 1 has no windows yet, frames 2-32
+    speculate, 33-37 are the probe of plain frames, frame 38 speculates again while the probe's timings settle."""
+    from wgpu_3dgs_viewer_app_amd import scene
+
+    n, w, h = 4096, 160, 120   # the shape of smoke()
+    g = scene.synthetic_gaussians(n, 99, 3)
+    g["scale"] *= np.float32(6.0)
+    with MultiModelViewer() as v:
+        v.set_render_options(frames_in_flight=1)
+        _load(v, "m", g)
+        flags = []
+        for k in range(40):
+            v.update_camera(camera.orbit_pose(k), (w, h))
+            v.update_gaussian_transform(1.0, GaussianDisplayMode.Splat, GaussianShDegree.new(3), False)
+            v.render_frame(["m"])
+            v.poll()
+            flags.append(int(v.frame_stats("m")["speculated"]))
+    assert flags[:38] == [0] + [1] * 31 + [0] * 5 + [1], flags
+
+
 def test_viewport_resizes_with_validation(monkeypatch):
     """Viewport sizes going up and down (the tile tables are allocated with slack and reused): every frame equals the frame
     of a fresh viewer, and the library's own pre-composite validation (GSX_VALIDATE, read when a viewer is created) finds

@@ -6,4 +6,6 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('value', d['value'], 'one lane', d.get('value_one_frame_in_flight'), 'unspeculated', d.get('value_unspeculated'), 'synchronised', d.get('value_synchronised'))
 for sch in (('speculated','unspeculated') if 'passes' in d else ()):
     print(sch, {k:(v['us_per_frame'] if isinstance(v,dict) else v) for k,v in d['passes'][sch].items()})
+if 'cfg5' in d:
+    print('cfg5 value', d['cfg5']['fps_two_frames_in_flight'], 'one lane', d['cfg5']['fps_one_frame_in_flight'], 'unspeculated', d['cfg5']['fps_unspeculated'])
 "; done

@@ -67,7 +67,6 @@ static gsx_status lane_create(gsx_viewer* v, gsx_viewer** out) {
     l->blocks_adaptive = v->blocks_adaptive;
     l->tile_order_on = v->tile_order_on;
     l->bucket_sort = v->bucket_sort;
-    l->bin_fused = v->bin_fused;
     l->short_chain = v->short_chain;
     l->sorted_records = v->sorted_records;
     l->tile_profile = v->tile_profile;
@@ -282,7 +281,6 @@ gsx_status gsx_viewer_create(const gsx_viewer_desc* desc, gsx_viewer** out) {
     v->tile_profile = getenv("GSX_TILE_PROFILE") != nullptr;
     if (const char* e = getenv("GSX_TILE_ORDER")) v->tile_order_on = atoi(e) != 0;
     if (const char* e = getenv("GSX_BUCKET_SORT")) v->bucket_sort = atoi(e) != 0;
-    if (const char* e = getenv("GSX_BIN_FUSED")) v->bin_fused = atoi(e) != 0;
     if (const char* e = getenv("GSX_SHORT_CHAIN")) v->short_chain = atoi(e) != 0;
     if (const char* e = getenv("GSX_DEPTH_LANES")) v->depth_lanes = atoi(e) != 0;
     if (const char* e = getenv("GSX_BIN_BIG_SLAB")) block_bin_set_big_slab((uint32_t)atoi(e));   // tests: smaller slabs take the eight-per-lane tiles

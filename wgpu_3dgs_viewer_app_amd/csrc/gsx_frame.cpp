@@ -23,16 +23,6 @@ gsx_status fail(gsx_status st, const char* fmt, ...) {
     return st;
 }
 
-gsx_status ply_fail(gsx_status st, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return st;
-}
-
 
 // host_verify: spin on the pinned verdict word until k_spec_verify of this frame has posted {seq, need}.  The wait is
 // bounded by the stream itself: if the stream drains (or fails) and the word still is not there, something upstream
@@ -68,16 +58,6 @@ static gsx_status wait_verdict(gsx_viewer* v, uint32_t seq, uint32_t* need) {
 }
 
 
-// ---- does speculating pay on THIS scene, along THIS camera path?  Measured, not guessed. ----
-// Temporal occlusion speculation wins when frames are coherent and the scene occludes (cfg4: 2x), and loses when most frames
-// need the repair round anyway (cfg2: 1 M sparse Gaussians, 90 % of the frames repair; random camera poses).  Either path
-// gives the same pixels, so the viewer simply times them: some frames are bracketed by a pair of HIP events (recorded on the
-// stream, read back when they have completed; the host waits for none of them except a probe's, eight frames after it —
-// kSettleWait), one running mean per mode, and a four-phase cycle per model:
-//   SPEC (len_spec frames) -> PROBE_PLAIN (5 frames, unspeculated; the windows keep being updated) -> SETTLE (speculated
-//   frames until the probe's timings have arrived) -> decide;   PLAIN -> PROBE_SPEC -> SETTLE -> decide likewise.
-// A decision that confirms the current mode doubles its phase — quadruples it when the verdict is clear — (64 ... 2048
-// frames: the probes then cost < 1 %), one that flips it starts over at 64.  By construction the result stays within a few per cent of the better of the two paths.
 // chunks of 128 candidates: finer blocks above kWalkFineOn / coarse blocks again below kWalkFineOff (measured under the finer ones).
 // Round 6: 220 / 70 (160 / 30 before).  cfg4's orbit walks 10-15 chunks a frame with rare poses of 130-170 under coarse blocks and 6-14
 // with spikes of 50 under fine ones — either state held itself and the first spike chose: - 10 % with one frame in flight whenever the
@@ -85,12 +65,9 @@ static gsx_status wait_verdict(gsx_viewer* v, uint32_t seq, uint32_t* need) {
 constexpr uint32_t kWalkFineOn = 220, kWalkFineOff = 70;
 constexpr uint32_t kSlabShadingMaxPercent = 35;  // slab shading pays while the slabs shade less than this share of the visible records (break-even ~45 % on cfg4)
 constexpr uint32_t kBucketSortMax = 1500000;  // pairs: above, the LSD depth sort (256 buckets of 8192 pairs fit the LDS; at 1 M the bucket sort takes half the LSD sort's time)
-constexpr uint32_t kProbeFrames = 5;   // the first is not timed (the switch itself is atypical), the other four are
-constexpr uint32_t kSettleWait = 8;    // frames enqueued behind a probe before the host waits for its timings
-constexpr uint32_t kSettleFrames = 64; // at most this many frames between a probe and the decision it feeds (normally: until its timings are in)
 
-static void tuner_collect(Model* m) {
-    SpecTuner& t = m->tuner_ref ? *m->tuner_ref : m->tuner;
+// ---- the speculation tuner's shell: event pairs in, timings out.  Every rule is SpecTunerRules' (spec_tuner.h). ----
+static void tuner_collect(SpecTuner& t) {
     for (auto& s : t.slots) {
         if (s.state < 2 || hipEventQuery(s.stop) != hipSuccess) continue;
         if (s.state == 3) {  // bracketed before a reset()
@@ -98,109 +75,58 @@ static void tuner_collect(Model* m) {
             continue;
         }
         float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, s.start, s.stop) == hipSuccess && ms > 0.0f) {
-            double& mean = s.spec ? t.mean_spec : t.mean_plain;
-            uint32_t& n = s.spec ? t.n_spec : t.n_plain;
-            mean = n == 0 ? ms : mean + 0.25 * (ms - mean);
-            n += 1;
-        }
-        if (s.probe && t.probe_pending) t.probe_pending -= 1;
+        if (hipEventElapsedTime(&ms, s.start, s.stop) != hipSuccess) ms = 0.0f;
+        t.rules.timing(s.spec, s.probe, ms);
         s.state = 0;
     }
 }
 
 // called once per gsx_preprocess of a model that could speculate; returns whether this frame should
 static bool tuner_wants_speculation(Model* m) {
-    SpecTuner& t = m->tuner_ref ? *m->tuner_ref : m->tuner;
-    tuner_collect(m);
-    static const bool debug = spec_debug_level() >= 1;
-    // a settle phase ends as soon as the probe's timings are in.  Eight frames after the probe the host stops running ahead
-    // until they are: it waits for the probe's last event — with eight frames queued behind it the device never idles, and a
-    // host that is dozens of short frames ahead (a 1 M-Gaussian scene on two lanes) would otherwise spend that long in the
-    // mode it is about to leave
-    const bool settling = t.phase == SpecTuner::SETTLE_SPEC || t.phase == SpecTuner::SETTLE_PLAIN;
-    if (settling && t.probe_pending && kSettleFrames - t.left >= kSettleWait) {
+    SpecTuner& t = m->own_tuner();
+    tuner_collect(t);
+    if (t.rules.must_wait_for_probe()) {
         for (auto& s : t.slots)
             if (s.state == 2 && s.probe) (void)gsx::op::EventSynchronize(s.stop);
-        tuner_collect(m);
+        tuner_collect(t);
     }
-    if (settling && t.probe_pending == 0) t.left = 0;
-    if (t.left == 0) {
-        switch (t.phase) {
-            case SpecTuner::SPEC:
-                t.phase = SpecTuner::PROBE_PLAIN; t.left = kProbeFrames;
-                break;
-            case SpecTuner::PLAIN:
-                t.phase = SpecTuner::PROBE_SPEC; t.left = kProbeFrames;
-                break;
-            // a host that does not wait for the device is several frames ahead of it: the probe's timings arrive while the
-            // frames after it are being enqueued, so the decision is taken a dozen frames later, in the old mode meanwhile
-            case SpecTuner::PROBE_PLAIN:
-                t.phase = SpecTuner::SETTLE_SPEC; t.left = kSettleFrames;
-                break;
-            case SpecTuner::PROBE_SPEC:
-                t.phase = SpecTuner::SETTLE_PLAIN; t.left = kSettleFrames;
-                break;
-            case SpecTuner::SETTLE_SPEC:
-            case SpecTuner::SETTLE_PLAIN: {
-                const bool was_spec = t.phase == SpecTuner::SETTLE_SPEC;
-                const bool have = t.n_spec >= 2 && t.n_plain >= 2;  // (running means over every bracketed frame so far, newest weighted most)
-                const bool spec_better = have ? (was_spec ? t.mean_spec <= 1.03 * t.mean_plain : t.mean_spec < 0.97 * t.mean_plain) : was_spec;
-                if (debug) fprintf(stderr, "[gsx spec] model '%s' frame %u: speculated %.3f ms (%u samples), plain %.3f ms (%u) -> %s\n", m->key.c_str(),
-                                   t.frame_no, t.mean_spec, t.n_spec, t.mean_plain, t.n_plain, spec_better ? "speculate" : "plain");
-                // a clear verdict (the other path costs half as much again, or more) is asked for again four times later, a close
-                // one twice later: on cfg4 a probe is five frames at twice the cost, on cfg2 the two paths are within 5 %
-                const double ratio = !have ? 1.0 : (spec_better ? t.mean_plain / std::max(t.mean_spec, 1e-6) : t.mean_spec / std::max(t.mean_plain, 1e-6));
-                const uint32_t grow = ratio >= 1.5 ? 4u : 2u;
-                if (spec_better) {
-                    t.len_spec = was_spec ? std::min<uint32_t>(grow * t.len_spec, 2048u) : 64u;
-                    t.len_plain = 64;
-                    t.phase = SpecTuner::SPEC; t.left = t.len_spec;
-                } else {
-                    t.len_plain = was_spec ? 64u : std::min<uint32_t>(grow * t.len_plain, 2048u);
-                    t.len_spec = 64;
-                    t.phase = SpecTuner::PLAIN; t.left = t.len_plain;
-                }
-                break;
-            }
-        }
-    }
-    t.left -= 1;
-    t.frame_no += 1;
-    return t.phase == SpecTuner::SPEC || t.phase == SpecTuner::PROBE_SPEC || t.phase == SpecTuner::SETTLE_SPEC;
+    bool decided = false;
+    const bool speculate = t.rules.next_frame(&decided);
+    static const bool debug = spec_debug_level() >= 1;
+    if (debug && decided)
+        fprintf(stderr, "[gsx spec] model '%s' frame %u: speculated %.3f ms (%u samples), plain %.3f ms (%u) -> %s\n", m->key.c_str(), t.rules.frame_no - 1,
+                t.rules.mean_spec, t.rules.n_spec, t.rules.mean_plain, t.rules.n_plain, speculate ? "speculate" : "plain");
+    return speculate;
 }
 
-// bracket this model's frame with events?  every frame of a probe but its first (the switch itself is atypical), every
-// fourth frame otherwise (an event pair costs a few microseconds of stream gap)
 static void tuner_frame_begin(gsx_viewer* v, Model* m, bool speculated) {
-    SpecTuner& t = m->tuner_ref ? *m->tuner_ref : m->tuner;
+    SpecTuner& t = m->own_tuner();
     if (t.active) {  // the last bracket was never closed (a gsx_preprocess without its gsx_render): take the slot back
         if (t.active->state == 1) {
             t.active->state = 0;
-            if (t.active->probe && t.probe_pending) t.probe_pending -= 1;
+            if (t.active->probe) t.rules.probe_dropped();
         }
         t.active = nullptr;
     }
-    const bool probe = t.phase == SpecTuner::PROBE_PLAIN || t.phase == SpecTuner::PROBE_SPEC;
-    if (probe ? t.left == kProbeFrames - 1 : (t.frame_no & 3u) != 0) return;
+    if (!t.rules.bracketed()) return;
     for (auto& s : t.slots) {
         if (s.state != 0) continue;
         if (!s.start && (hipEventCreate(&s.start) != hipSuccess || hipEventCreate(&s.stop) != hipSuccess)) return;
         if (gsx::op::EventRecord(s.start, v->stream) != hipSuccess) return;
         s.spec = speculated;
-        s.probe = probe;
+        s.probe = t.rules.probing();
         s.state = 1;
-        if (probe) t.probe_pending += 1;
+        if (s.probe) t.rules.probe_opened();
         t.active = &s;
         return;
     }
 }
 
 static void tuner_frame_end(gsx_viewer* v, Model* m) {
-    SpecTuner& t = m->tuner_ref ? *m->tuner_ref : m->tuner;
+    SpecTuner& t = m->own_tuner();
     if (!t.active) return;
     t.active->state = gsx::op::EventRecord(t.active->stop, v->stream) == hipSuccess ? 2 : 0;
-    if (t.active->state == 0 && t.active->probe && t.probe_pending) t.probe_pending -= 1;
+    if (t.active->state == 0 && t.active->probe) t.rules.probe_dropped();
     t.active = nullptr;
 }
 
@@ -217,6 +143,25 @@ static void note_overflow(Model* m) {
                 m->key.c_str(), ev, m->h_counters->max_needed_ever, (unsigned long long)m->tile_cap, m->h_counters->n_sorted, m->h_counters->n_sorted2,
                 m->h_counters->n_entries_total, (int)m->stats_copy_speculated);
     m->tile_cap = std::max<uint64_t>(2 * m->tile_cap, (uint64_t)m->h_counters->max_needed_ever + 1024);
+}
+
+// What the host learns from a copy of the model's Counters, whichever way it came (finish_frame's blocking copy, the asynchronous
+// one of do_bin_and_composite): the sizes of the sorts to come, whether slab shading still pays, pair buffers that spilled, the slab
+// plan's hint.  speculated / slab_shaded: the kind of frame the copy was taken behind; plain_slabs: that frame's slabs_used speaks for
+// a plain frame's plan (each caller says when).
+static void absorb_counters(Model* m, bool speculated, bool slab_shaded, bool plain_slabs) {
+    const Counters& c = *m->h_counters;
+    if (speculated) {
+        m->last_spec_sorted = c.n_sorted;
+        m->last_repair_sorted = c.n_sorted2;
+    }
+    if (slab_shaded) m->slab_shading_off = (uint64_t)c.n_shaded_total * 100u > (uint64_t)c.n_visible * kSlabShadingMaxPercent;
+    // (the slab plan of the next PLAIN frame — a probe of the speculation tuner — from the last plain frame: a speculated frame is ONE
+    //  slab and says nothing about how many a plain frame needs; taken from it the hint merged everything behind the second slab into
+    //  one, 11 M entries where four slabs make 1.5 M)
+    if (plain_slabs && !speculated) m->slabs_hint = c.slabs_used;
+    m->stats_copy_inflight = false;
+    note_overflow(m);  // a free-running loop learns here that some earlier frame spilled: larger pair buffers from now on
 }
 
 // Frames are enqueued without any host round trip; this is where the host catches up: wait for the
@@ -238,20 +183,14 @@ gsx_status finish_frame(gsx_viewer* v) {
             Model* m = kv.second.get();
             if (!m->stats_pending) continue;
             m->stats_pending = false;
+            // (only here: the host has waited, so these are THIS frame's counts — what the readbacks and gsx_model_frame_stats report)
             m->n_visible = m->h_counters->n_visible;
             m->n_sorted = m->h_counters->n_sorted;
             m->n_sorted2 = m->h_counters->n_sorted2;
-
             m->n_entries = m->h_counters->n_entries_total;
             m->counters_valid = true;
-            if (m->spec_round1) {
-                m->last_spec_sorted = m->h_counters->n_sorted;
-                m->last_repair_sorted = m->h_counters->n_sorted2;
-            }
-            if (m->slab_shading && m->binned) m->slab_shading_off = (uint64_t)m->h_counters->n_shaded_total * 100u > (uint64_t)m->h_counters->n_visible * kSlabShadingMaxPercent;
-            if (m->binned && !m->spec_round1) m->slabs_hint = m->h_counters->slabs_used;   // (a speculated frame is ONE slab: it says nothing about how many a plain frame needs)
-            m->stats_copy_inflight = false;
-            note_overflow(m);
+            // (a model that was only preprocessed or sorted so far has no slabs of this frame to learn from)
+            absorb_counters(m, m->spec_round1, m->slab_shading && m->binned, m->binned);
             // The pixels of a frame that spilled are complete (k_composite_spill); only its tile LISTS are not, and only a
             // single-slab frame promises those (gsx_model_download_tile_lists): that one is redone with the grown buffers.
             if (m->h_counters->overflow && m->binned && m->lists_complete && !v->tile_cap_fixed && !v->last_render_cont && m->rec_n == m->n)
@@ -304,7 +243,7 @@ gsx_status ensure_sortbin_capacity(Model* m, uint64_t count) {
         }
     }
     HIPCHK(m->srect.ensure(16 * n));  // uint2 tile rectangles (tile lists) or uint4 {rect, key, index} (block lists)
-    // (cnt / block_sums — per-record counts and their chunk sums — belong to the three-launch binning: per-tile lists, GSX_BIN_FUSED=0;
+    // (cnt / block_sums — per-record counts and their chunk sums — belong to the three-launch binning of the per-tile lists;
     //  the slabs that take that path ask for them: ensure_count_buffers)
     m->sortbin_cap = n;
     return GSX_OK;
@@ -462,6 +401,23 @@ static gsx_status depth_pyramid(gsx_viewer* v) {
     return GSX_OK;
 }
 
+// a texture query reads one texel per pixel: the texture must be the viewport's size
+static gsx_status check_query_texture(const gsx_viewer* v) {
+    if (v->query.kind == GSX_QUERY_TEXTURE && (v->query_tex_w != v->width || v->query_tex_h != v->height))
+        return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: texture query without a viewport-sized query texture (gsx_update_query_texture)");
+    return GSX_OK;
+}
+
+// the frame's colour ops (stored edits, highlight) on the projection's records: all n of them, or (late) the listed ones
+static hipError_t apply_edits(gsx_viewer* v, Model* m, bool edits, bool highlight, const LateProjection* late = nullptr) {
+    const uint32_t* selected = highlight ? m->selection.as<uint32_t>() : nullptr;
+    const uint32_t* edited = edits ? m->edited.as<uint32_t>() : nullptr;
+    if (late)
+        return launch_edit_apply_list(v->stream, (uint32_t)m->n, m->proj_rec(), late->pairs, late->d_n, late->shaded, selected, edited,
+                                      m->edit_a.as<float4>(), m->edit_b.as<float4>(), v->highlight);
+    return launch_edit_apply(v->stream, (uint32_t)m->n, m->proj_rec(), selected, edited, m->edit_a.as<float4>(), m->edit_b.as<float4>(), v->highlight);
+}
+
 gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
     frame_consts_setup(v->view, v->proj, v->width, v->height, m->mt, v->size, v->display_mode, v->sh_deg, v->no_sh0,
                        v->params, &m->fc);
@@ -497,13 +453,8 @@ gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
     // ... and whether speculating pays here is measured (SpecTuner): plain frames while it does not, windows kept up to date
     const bool could_speculate = v->options.progressive && v->options.speculative && !(m->shard_win_set && m->shard_tiles_x == m->fc.tiles_x && m->shard_tiles_y == m->fc.tiles_y);
     if (could_speculate && !tuner_wants_speculation(m)) m->spec_round1 = false;
-    // deep inside a plain phase nobody reads the windows this frame would leave behind (its last frame does: a probe follows)
-    {
-        // (with frames in flight every lane needs ITS windows for the probe: the last L frames of the phase keep them)
-        const SpecTuner& tn = m->tuner_ref ? *m->tuner_ref : m->tuner;
-        const uint32_t lanes = v->parent ? v->parent->options.frames_in_flight : v->options.frames_in_flight;
-        m->windows_unwanted = could_speculate && tn.phase == SpecTuner::PLAIN && tn.left >= lanes;
-    }
+    // deep inside a plain phase nobody reads the windows this frame would leave behind (SpecTunerRules::leaves_windows)
+    m->windows_unwanted = could_speculate && !m->own_tuner().rules.leaves_windows((v->parent ? v->parent : v)->options.frames_in_flight);
     ProjectAdmission adm{};
     HIPCHK(m->adm_ballots.ensure(8 * ((std::max<size_t>(m->n, 1) + 63) / 64 + 4)));
     HIPCHK(m->adm_counts.ensure(4 * (std::max<size_t>(std::max(admit_blocks(m->n), (size_t)(m->n + 255) / 256), 1) + 4)));
@@ -554,7 +505,7 @@ gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
     // exactly the records some block of tiles still takes (k_block_bin's list).  Only frames that bin by blocks, slab by slab:
     // a model small enough for ONE slab keeps complete per-tile lists and its full records (gsx_model_download_tile_lists).
     // (a depth-tested frame has windows: its admission already dropped the hidden records, and it projects the admitted ones in full)
-    m->slab_shading = v->options.slab_shading && v->options.progressive && v->bin_mode == 1 && v->bin_fused && !m->spec_round1 && !shard_lazy &&
+    m->slab_shading = v->options.slab_shading && v->options.progressive && v->bin_mode == 1 && !m->spec_round1 && !shard_lazy &&
                       !depth && m->n > v->options.min_slab && v->options.first_slab_divisor > 1 && m->pod().sh_aos != nullptr;
     // (first_slab_divisor == 1: plan_slabs makes the first slab the whole model, one slab whatever min_slab says)
     // ... and only while it pays: a scene where next to nothing saturates (translucent) has every visible record taken by some block — then
@@ -573,8 +524,7 @@ gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
     }
     if (m->lazy && geometric_query) {
         HIPCHK(m->query_flags.ensure(4 * std::max<size_t>(words, 1)));
-        if (v->query.kind == GSX_QUERY_TEXTURE && (v->query_tex_w != v->width || v->query_tex_h != v->height))
-            return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: texture query without a viewport-sized query texture (gsx_update_query_texture)");
+        if ((st = check_query_texture(v))) return st;
         adm.query = ProjectQuery{v->query, v->query_texture.as<uint8_t>(), v->query_tex_w, v->query_tex_h, m->query_flags.as<uint32_t>()};
     }
     m->frame_edits = edits_on;
@@ -621,10 +571,7 @@ gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
         if (m->lazy && (st = shade_admitted(v, m, LateProjection{m->adm_pairs.as<uint2>(), &dcx->n_candidates, nullptr, m->rect8_active}))) return st;
         m->cand_valid = true;
     }
-    if ((edits_on || highlight_on) && !m->lazy)
-        HIPCHK(launch_edit_apply(v->stream, n32, m->proj_rec(), highlight_on ? m->selection.as<uint32_t>() : nullptr,
-                                 edits_on ? m->edited.as<uint32_t>() : nullptr, m->edit_a.as<float4>(), m->edit_b.as<float4>(),
-                                 v->highlight));
+    if ((edits_on || highlight_on) && !m->lazy) HIPCHK(apply_edits(v, m, edits_on, highlight_on));
     m->flags_kind = GSX_QUERY_NONE;
     if (adm.query.flags) {  // answered by the projection kernel
         m->flags_kind = v->query.kind;
@@ -636,8 +583,7 @@ gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
             HIPCHK(gsx::op::MemsetAsync(m->hit_count.p, 0, 4, v->stream));
         } else {
             HIPCHK(m->query_flags.ensure(4 * std::max<size_t>(words, 1)));
-            if (v->query.kind == GSX_QUERY_TEXTURE && (v->query_tex_w != v->width || v->query_tex_h != v->height))
-                return fail(GSX_ERR_INVALID_ARG, "gsx_preprocess: texture query without a viewport-sized query texture (gsx_update_query_texture)");
+            if ((st = check_query_texture(v))) return st;
         }
         HIPCHK(launch_query(v->stream, n32, m->proj_rec(), v->query, v->query_texture.as<uint8_t>(), v->query_tex_w, v->query_tex_h,
                             m->fc, m->query_flags.as<uint32_t>(), m->hits.as<gsx_query_hit>(), m->hit_count.as<uint32_t>(),
@@ -666,9 +612,7 @@ gsx_status complete_records(gsx_viewer* v, Model* m) {
     HIPCHK(launch_project(v->stream, m->fc, (uint32_t)m->n, pod, m->proj_rec(), m->block_vis.as<uint32_t>(), adm));
     m->lazy = false;
     if (m->frame_edits || m->frame_highlight)  // every record was written again: the frame's colour ops on all of them
-        HIPCHK(launch_edit_apply(v->stream, (uint32_t)m->n, m->proj_rec(), m->frame_highlight ? m->selection.as<uint32_t>() : nullptr,
-                                 m->frame_edits ? m->edited.as<uint32_t>() : nullptr, m->edit_a.as<float4>(), m->edit_b.as<float4>(),
-                                 v->highlight));
+        HIPCHK(apply_edits(v, m, m->frame_edits, m->frame_highlight));
     return GSX_OK;
 }
 
@@ -688,11 +632,7 @@ gsx_status shade_admitted(gsx_viewer* v, Model* m, const LateProjection& late) {
     pod.mask = m->last_pod_mask;
     const uint32_t n = (uint32_t)m->n;
     HIPCHK(launch_shade(v->stream, m->fc, n, pod, m->proj_rec(), late));
-    if (m->frame_edits || m->frame_highlight)
-        HIPCHK(launch_edit_apply_list(v->stream, n, m->proj_rec(), late.pairs, late.d_n, late.shaded,
-                                      m->frame_highlight ? m->selection.as<uint32_t>() : nullptr,
-                                      m->frame_edits ? m->edited.as<uint32_t>() : nullptr, m->edit_a.as<float4>(), m->edit_b.as<float4>(),
-                                      v->highlight));
+    if (m->frame_edits || m->frame_highlight) HIPCHK(apply_edits(v, m, m->frame_edits, m->frame_highlight, &late));
     return GSX_OK;
 }
 
@@ -715,6 +655,27 @@ static ShadeRide shade_ride(Model* m, const LateProjection& late) {
     r.skip = late.shaded;
     r.write_a = late.write_a ? 1u : 0u;
     return r;
+}
+
+// The depth sort of the records an admission pass let in — the main round's (do_sort) and the repair round's alike: their (key, index)
+// pairs lie compacted in adm_pairs, *d_count of them (n: an upper bound).  A geometry-only projection left them unshaded: shaded here, in
+// a launch in front of the sort or as riders of the bucket sort's own launches (shading_rides).  msd_ws: the bucket sort's workspace, whose
+// histogram of sort `seq` the admission launch counted; nullptr: four full digit passes.
+static gsx_status sort_admitted(gsx_viewer* v, Model* m, uint32_t n, uint32_t* d_count, DevBuf* msd_ws, uint32_t seq, const LateProjection& late) {
+    const bool rides = msd_ws && shading_rides(v, m);   // (the sort's launches shade beside their own work)
+    if (m->lazy && !rides) {
+        const gsx_status sst = shade_admitted(v, m, late);
+        if (sst) return sst;
+    }
+    RadixBuffers rb{nullptr, nullptr, m->adm_pairs.as<uint2>(), m->sk_out.as<uint32_t>(), m->sv_out.as<uint32_t>(),
+                    m->dp_a.as<uint2>(), m->dp_b.as<uint2>(), m->sort_ws.as<uint32_t>()};
+    if (msd_ws) {
+        const ShadeRide ride = rides ? shade_ride(m, late) : ShadeRide{};
+        HIPCHK(launch_bucket_sort(v->stream, rb, n, d_count, false, msd_ws->as<uint32_t>(), seq, true, rides ? &ride : nullptr));
+    } else {
+        HIPCHK(launch_radix_sort(v->stream, rb, n, d_count, 32, false));
+    }
+    return GSX_OK;
 }
 
 // (A single-launch depth sort for the ~0.3 M pairs of a speculated frame — one persistent grid, device-wide barriers between
@@ -792,21 +753,10 @@ gsx_status do_sort(gsx_viewer* v, Model* m, bool force_full) {
                                                      m->visible_count_pending ? m->block_vis.as<uint32_t>() : nullptr, &dc->n_visible));
                 }
                 m->visible_count_pending = false;
-                const LateProjection late{m->adm_pairs.as<uint2>(), &dc->n_sorted, nullptr, m->rect8_active};
-                const bool rides = bucket && shading_rides(v, m);   // (the sort's launches shade beside their own work)
-                if (m->lazy && !rides) {  // the projection pass was geometry only: shade what it admitted
-                    gsx_status sst = shade_admitted(v, m, late);
-                    if (sst) return sst;
-                }
-                RadixBuffers rb{nullptr, nullptr, m->adm_pairs.as<uint2>(), m->sk_out.as<uint32_t>(), m->sv_out.as<uint32_t>(),
-                                m->dp_a.as<uint2>(), m->dp_b.as<uint2>(), m->sort_ws.as<uint32_t>()};
-                if (bucket) {
-                    const ShadeRide ride = rides ? shade_ride(m, late) : ShadeRide{};
-                    HIPCHK(launch_bucket_sort(v->stream, rb, n, &dc->n_sorted, false, m->msd_ws.as<uint32_t>(), seq, true, rides ? &ride : nullptr));
-                    launches_sort = 2;
-                } else {
-                    HIPCHK(launch_radix_sort(v->stream, rb, n, &dc->n_sorted, 32, false));
-                }
+                const gsx_status sst = sort_admitted(v, m, n, &dc->n_sorted, bucket ? &m->msd_ws : nullptr, seq,
+                                                     LateProjection{m->adm_pairs.as<uint2>(), &dc->n_sorted, nullptr, m->rect8_active});
+                if (sst) return sst;
+                if (bucket) launches_sort = 2;
             }
         }
         m->sorted_idx = m->sv_out.as<uint32_t>();
@@ -854,6 +804,365 @@ static void merge_tail_slabs(std::vector<uint32_t>* bounds, uint32_t used) {
     }
 }
 
+// What one model's frame derives, once, from the viewer, the model and its slab plan: the values its steps below share.  Values, not an
+// interface: the steps are the static functions that take it (run_slab alone changes it: the zero job and the order build are spent by
+// the first block-table kernel that takes them along).
+struct SlabFrame {
+    Counters* dc;
+    bool progressive, blocks, clear_ranges;
+    uint32_t n_tiles, row_words, row_lo, row_hi, owned_tiles;
+    uint32_t cap;                       // pair capacity (Model::tile_cap, this frame)
+    int bits;                           // of a tile id: the per-tile lists' sort key
+    uint32_t bsx, bsy, blocks_max;      // block lists: 2^bsx x 2^bsy tiles a block, at most blocks_max blocks
+    uint32_t *done, *done_count;        // the frame's saturated-tile bitmap (word 0 of the buffer: their count)
+    uint32_t *tile_sat, *row_work;      // [count | bitmap | saturation keys | row work]
+    const uint32_t* done_before;        // the bitmap as the nearer models left it (carry; nullptr otherwise)
+    const uint32_t* depth_lim;          // depth test: per-pixel limit keys
+    const uint2* depth_bound;           //             per-tile windows {0, depth bound}
+    const uint2* window;                // every tile's depth-key window of the main round (nullptr: none)
+    uint32_t* order_buf;                // block compositor's dispatch order (nullptr: index order)
+    bool order_build;                   // ... to be made by this frame's first block-table kernel
+    ZeroJob zero;                       // the per-frame totals (and the frame's saturation state) to zero before anything reads them
+    bool zero_pending;
+};
+
+// What the asynchronous copy of the Counters says, when it has arrived (enqueued every fourth frame, below: the host waits for none)
+static void absorb_stats_copy(gsx_viewer* v, Model* m, bool progressive, uint32_t n_tiles) {
+    if (!m->stats_copy_inflight || hipEventQuery(m->stats_event) != hipSuccess) return;
+    if (progressive) {
+        if (spec_debug_level() >= 3)
+            fprintf(stderr, "[gsx stats] viewer %p: copy of a %s frame: slabs_used %u, n_sorted %u, entries %u, max_needed %u, walk_max %u chunks (fine blocks: speculated %d, plain %d)\n", (void*)v, m->stats_copy_speculated ? "speculated" : "plain",
+                    m->h_counters->slabs_used, m->h_counters->n_sorted, m->h_counters->n_entries_total, m->h_counters->max_needed, m->h_counters->walk_max, (int)m->blocks_fine_spec, (int)m->blocks_fine_plain);
+        m->n_sorted = m->h_counters->n_sorted;
+    }
+    // (the copy was taken behind the frame's binning; only a progressive viewer's slab plan reads the hint)
+    absorb_counters(m, m->stats_copy_speculated, m->stats_copy_slab_shading, progressive);
+    // (only here — these choose the NEXT frames' block size and list layout from whatever frame's statistics arrived last, with hysteresis;
+    //  finish_frame's copy may belong to a frame that was not binned, and must not change which frames use fine blocks)
+    // long block lists (a scene where little saturates): the block sort carries the lists' records along (k_composite_blocks
+    // SORTED); with hysteresis, from whatever frame's statistics arrived last — either way the pixels are the same
+    const uint64_t per_tile = (uint64_t)m->h_counters->n_entries_total / std::max<uint32_t>(n_tiles, 1u);
+    m->lists_long = m->lists_long ? per_tile > 500u : per_tile > 900u;
+    // a tile that never saturates walks its block's whole list, 128 candidates per ~1.5 us, and the launch is as slow as that tile
+    // (an open horizon: 425 chunks for 1900 takers with blocks of 8 x 4 tiles).  Blocks of a quarter the size cut the walk ~3.5x
+    // and cost a second digit in the block sort and ~2x the entries: - 12 % on cfg4's orbit, + 16 % under an open sky
+    // (tools/ab_blocks.py, round 5).  So the block size follows the longest walk of an earlier frame (SlabStats::walk_max, left
+    // by tile_order_job), with hysteresis; either way the pixels are the same.
+    // (one flag per schedule: an unspeculated frame — a probe of the tuner among speculated ones — walks its first slab's whole lists,
+    //  several times the walk of the speculated frames around it; its statistic used to put THEM into fine blocks, where the walk
+    //  then stayed above the way-back threshold: the same bench command read 2040 or 1830 fps with one frame in flight, 20.0 or 21.6
+    //  launches a frame, depending on whether a stats copy happened to catch a probe frame — round 6)
+    const uint32_t walk = m->h_counters->walk_max;
+    bool& fine = m->stats_copy_speculated ? m->blocks_fine_spec : m->blocks_fine_plain;
+    fine = fine ? walk > kWalkFineOff : walk > kWalkFineOn;
+}
+
+// plan the slabs: bounds[i] .. bounds[i + 1] of the depth order
+static void plan_frame_slabs(gsx_viewer* v, Model* m, bool one_slab, std::vector<uint32_t>* bounds) {
+    if (one_slab) {
+        // a speculated round is ONE slab: the windows already bound what every tile takes to little more than it needs,
+        // and the compositor stops a saturated tile by itself; more slabs only add launches (measured on cfg4: 551 fps
+        // with one slab, 487 with three).  The kernels stride over what exists on the device, so the bound is free.
+        // (Same for the imported records of an index-sharded frame whose exchange was windowed.)
+        *bounds = {0u, (uint32_t)m->rec_n};
+    } else {
+        plan_slabs(v->options, (uint32_t)m->rec_n, bounds);
+        if (v->options.progressive) merge_tail_slabs(bounds, m->slabs_hint);
+    }
+    if (spec_debug_level() >= 3) {
+        fprintf(stderr, "[gsx slabs] viewer %p model '%s': speculated %d, slab shading %d, hint %u, slabs", (void*)v, m->key.c_str(), (int)m->spec_round1, (int)m->slab_shading, m->slabs_hint);
+        for (uint32_t b : *bounds) fprintf(stderr, " %u", b);
+        fprintf(stderr, "\n");
+    }
+}
+
+// size the pair buffers: Model::tile_cap entries (f.cap) and what sorts and consumes them
+static gsx_status size_pair_buffers(gsx_viewer* v, Model* m, SlabFrame& f) {
+    // pair capacity to begin with: 16 entries per record for small models (per-tile lists), 6 for large ones (block lists need
+    // ~3 per record on speculated frames, 0.2 on depth slabs; a frame that wants more spills on the device and the host grows
+    // the buffers when it learns of it) — 32 bytes of pair / sort buffers per entry
+    // (a frame without depth slabs keeps per-tile lists of the whole model: 16 as well)
+    {
+        // (round 6: large progressive models start at TWO entries per record — cfg4's largest slab makes 0.2, 32 bytes of pair / sort buffers an
+        //  entry were 192 bytes a Gaussian and lane at the 6 entries of rounds 2-5; a scene that wants more — large splats, nothing saturating —
+        //  spills on the device for the few frames it takes the host to learn of it: note_overflow doubles, or jumps to what was needed)
+        const uint64_t per_record = (!f.progressive || m->rec_n <= (1u << 18)) ? 16u : 2u;
+        m->tile_cap = std::max<uint64_t>(m->tile_cap, std::max<uint64_t>(1u << 20, per_record * m->rec_n));
+    }
+    if (v->tile_cap_fixed) m->tile_cap = v->tile_cap_fixed;  // GSX_TILE_CAP (tests): a capacity that overflows on purpose
+    m->tile_cap = std::min<uint64_t>(m->tile_cap, 0xFFFFF000ull);
+    f.cap = (uint32_t)m->tile_cap;
+    const size_t bytes = sizeof(uint32_t) * (size_t)f.cap;
+    HIPCHK(m->tp_src.ensure(2 * bytes));
+    HIPCHK(m->tk_out.ensure(bytes));
+    HIPCHK(m->tv_out.ensure(bytes));
+    const size_t ws = 4 * radix_workspace_words(f.cap);
+    if (ws > m->tsort_ws.bytes) {
+        HIPCHK(m->tsort_ws.ensure(ws));
+        HIPCHK(gsx::op::MemsetAsync(m->tsort_ws.p, 0, m->tsort_ws.bytes, v->stream));
+    }
+    if (sizeof(uint2) * (size_t)f.n_tiles > m->ranges.bytes) m->ranges_clean = false;
+    HIPCHK(m->ranges.ensure(sizeof(uint2) * (size_t)std::max<uint32_t>(f.n_tiles, 1024u)));  // (block lists: up to 1024 block ranges)
+    if (f.blocks) {
+        HIPCHK(m->block_table.ensure(sizeof(uint4) * 1024));
+        if (v->tile_profile) HIPCHK(v->tile_prof.ensure(sizeof(uint4) * (size_t)f.n_tiles));
+    }
+    // the pair sort's ping-pong buffers: only a sort of two digits has an intermediate, only one of three a second (block lists of
+    // <= 256 blocks — every slab of a large model — are ONE digit: emitted pairs -> sorted keys / values, 32 bytes a Gaussian and lane less)
+    const int pair_bits = f.blocks ? (int)std::max<uint32_t>(1u, ceil_log2(f.blocks_max)) : f.bits;
+    if (pair_bits > 8) HIPCHK(m->tp_a.ensure(2 * bytes));
+    if (pair_bits > 16) HIPCHK(m->tp_b.ensure(2 * bytes));
+    return GSX_OK;
+}
+
+// one depth slab [j0, j1) of the current depth order: bin -> tile sort -> ranges -> composite
+static gsx_status run_slab(gsx_viewer* v, Model* m, SlabFrame& f, uint32_t j0, uint32_t j1, bool later, const uint2* win, const uint32_t* d_n,
+                           uint32_t slab_index, const WindowPyramid* min_ends = nullptr, bool table_ready = false) {
+    // the very first slab of the frame sees no saturated tile: plain rectangle areas
+    const uint32_t* done_in = later ? f.done : nullptr;
+    bool sorted_records = false;  // block lists: the compositor's candidates travel through the block sort (long lists)
+    // a slab of S splats can produce at most S * n_tiles entries; size the sort launch by the smaller bound
+    const uint32_t slab_cap = (uint32_t)std::min<uint64_t>(f.cap, (uint64_t)(j1 - j0) * std::min<uint64_t>(f.owned_tiles, 1u << 16));
+    if (f.blocks) {
+        // (the block sort's one-digit histogram — entries per block — counted by the emit kernel on its way instead of by a launch of
+        //  its own was measured, round 4: two launches less per frame, and slower — every emit workgroup flushes up to 256 bins to
+        //  the same 256 addresses: binning 69 -> 86 us against block sort 37 -> 25 on a speculated cfg4 frame, 218 -> 327 against
+        //  69 -> 45 unspeculated.  Not kept.)
+        const int block_bits = (int)std::max<uint32_t>(1u, ceil_log2(f.blocks_max));
+        ZeroJob jobs = f.zero_pending ? f.zero : ZeroJob{};
+        if (f.order_build && !table_ready) {
+            jobs.order_buf = f.order_buf;
+            jobs.order_tiles = f.n_tiles;
+            m->tile_order_valid = true;
+            f.order_build = false;
+        }
+        const bool slab_shade = m->slab_shading && m->lazy && !m->spec_round1;
+        if (slab_shade) HIPCHK(m->adm_pairs.ensure(8 * std::max<size_t>(m->rec_n, 1)));
+        {
+            ScopedPass t(v, GSX_PASS_BIN);
+            const size_t bw = 4 * bin_workspace_words(m->sortbin_cap);
+            if (m->bin_ws.bytes < bw) {
+                HIPCHK(m->bin_ws.ensure(bw));
+                HIPCHK(gsx::op::MemsetAsync(m->bin_ws.p, 0, m->bin_ws.bytes, v->stream));
+            }
+            HIPCHK(launch_block_bin_fused(v->stream, j0, j1, d_n, m->sorted_idx, m->rec(), m->sk_out.as<uint32_t>(), m->srect.as<uint4>(), f.dc, f.cap,
+                                          f.row_lo, f.row_hi, done_in, f.row_words, (f.progressive && later) ? f.done_count : nullptr, f.owned_tiles, slab_index,
+                                          win, m->fc.tiles_x, m->fc.tiles_y, f.bsx, f.bsy, m->block_table.as<uint4>(), m->tp_src.as<uint2>(),
+                                          m->ranges.as<uint2>(), jobs, table_ready, m->bin_ws.as<uint32_t>(), m->tsort_ws.as<uint32_t>(), block_bits,
+                                          slab_shade ? m->adm_pairs.as<uint2>() : nullptr,
+                                          (slab_shade && m->sorted_code_valid) ? m->sorted_code.as<uint8_t>() : nullptr));
+            // slab shading: conic / colour records for exactly the records of this slab some block takes (and the frame's colour ops on them)
+            if (slab_shade) {
+                const gsx_status sst = shade_admitted(v, m, LateProjection{m->adm_pairs.as<uint2>(), &f.dc->n_slab_shade, nullptr, m->rect8_active});
+                if (sst) return sst;
+            }
+            f.zero_pending = false;
+            v->pass_launches[GSX_PASS_BIN] += 1;
+        }
+        {
+            ScopedPass t(v, GSX_PASS_TILE_SORT);
+            RadixBuffers rb{nullptr, nullptr, m->tp_src.as<uint2>(), m->tk_out.as<uint32_t>(), m->tv_out.as<uint32_t>(),
+                            m->tp_a.as<uint2>(), m->tp_b.as<uint2>(), m->tsort_ws.as<uint32_t>()};
+            const uint32_t block_cap = (uint32_t)std::min<uint64_t>(f.cap, (uint64_t)(j1 - j0) * 256u);
+            // (<= 256 blocks: ONE digit, and the block ranges are the scan of its histogram — no k_tile_ranges launch;
+            //  k_block_table zeroed the ranges, which is what stays when the slab made no entry at all)
+            // sorted_records: the write-out also carries every entry's {rect, key, index} record along
+            sorted_records = v->sorted_records >= 0 ? v->sorted_records == 1 : m->lists_long;  // (the LAST digit pass carries them)
+            if (sorted_records) HIPCHK(m->brec_sorted.ensure(sizeof(uint4) * (size_t)f.cap));
+            HIPCHK(launch_radix_sort(v->stream, rb, block_cap, &f.dc->n_entries, block_bits, false, false, block_bits <= 8 ? m->ranges.as<uint2>() : nullptr,
+                                     sorted_records ? m->srect.as<uint4>() : nullptr, sorted_records ? m->brec_sorted.as<uint4>() : nullptr, true /* k_block_bin counted the digit histogram */));
+            m->tile_keys = m->tk_out.as<uint32_t>();
+            m->tile_list = m->tv_out.as<uint32_t>();
+            v->pass_launches[GSX_PASS_TILE_SORT] += 1;
+            if (block_bits > 8) {  // GSX_BLOCKS_MAX above 256: two digits, ranges from the sorted keys
+                ScopedPass t2(v, GSX_PASS_BIN);
+                HIPCHK(launch_tile_ranges(v->stream, block_cap, &f.dc->n_entries, m->tile_keys, 1024u, m->ranges.as<uint2>(), true));
+            }
+            m->ranges_clean = false;
+        }
+    } else {
+        {
+            ScopedPass t(v, GSX_PASS_BIN);
+            gsx_status cst = ensure_count_buffers(m);
+            if (cst) return cst;
+            HIPCHK(launch_tile_counts(v->stream, j0, j1, d_n, m->sorted_idx, m->rec(), m->srect.as<uint2>(),
+                                      m->cnt.as<uint32_t>(), m->block_sums.as<uint32_t>(), f.dc, f.cap, f.row_lo, f.row_hi, done_in,
+                                      f.row_words, (f.progressive && later) ? f.done_count : nullptr, f.owned_tiles, slab_index,
+                                      win, m->sk_out.as<uint32_t>(), m->fc.tiles_x, min_ends));
+            HIPCHK(launch_tile_emit(v->stream, j0, j1, m->sorted_idx, m->srect.as<uint2>(), m->cnt.as<uint32_t>(),
+                                    m->block_sums.as<uint32_t>(), m->fc.tiles_x, m->tp_src.as<uint2>(), f.row_lo, f.row_hi,
+                                    done_in, f.row_words, d_n, &f.dc->n_entries, f.cap, win, m->sk_out.as<uint32_t>(), &f.dc->slab_cut));
+            v->pass_launches[GSX_PASS_BIN] += 1;
+        }
+        {
+            ScopedPass t(v, GSX_PASS_TILE_SORT);
+            RadixBuffers rb{nullptr, nullptr, m->tp_src.as<uint2>(), m->tk_out.as<uint32_t>(), m->tv_out.as<uint32_t>(),
+                            m->tp_a.as<uint2>(), m->tp_b.as<uint2>(), m->tsort_ws.as<uint32_t>()};
+            HIPCHK(launch_radix_sort(v->stream, rb, slab_cap, &f.dc->n_entries, f.bits, false));
+            m->tile_keys = m->tk_out.as<uint32_t>();
+            m->tile_list = m->tv_out.as<uint32_t>();
+            v->pass_launches[GSX_PASS_TILE_SORT] += (f.bits + 7) / 8;
+        }
+        {
+            ScopedPass t(v, GSX_PASS_BIN);
+            HIPCHK(launch_tile_ranges(v->stream, slab_cap, &f.dc->n_entries, m->tile_keys, (uint32_t)(m->ranges.bytes / sizeof(uint2)),
+                                      m->ranges.as<uint2>(), m->ranges_clean));
+        }
+    }
+    if (v->validate) {  // debug: check what the compositor will dereference, on the host, before it runs
+        HIPCHK(v->scratch.ensure(64));
+        HIPCHK(gsx::op::MemsetAsync(v->scratch.p, 0, 64, v->stream));
+        // (block lists: one range per block, list values are positions in the slab)
+        const uint32_t n_ranges = f.blocks ? block_grid(f.bsx, f.bsy, m->fc.tiles_x, f.row_lo, f.row_hi).blocks_x * block_grid(f.bsx, f.bsy, m->fc.tiles_x, f.row_lo, f.row_hi).blocks_y : f.n_tiles;
+        HIPCHK(launch_validate_tiles(v->stream, m->ranges.as<uint2>(), n_ranges, m->tile_list, &f.dc->n_entries, f.blocks ? f.cap : slab_cap,
+                                     f.blocks ? j1 - j0 : (uint32_t)m->rec_n, v->scratch.as<uint32_t>()));
+        uint32_t rep[8];
+        HIPCHK(gsx::op::MemcpyAsync(rep, v->scratch.p, 32, hipMemcpyDeviceToHost, v->stream));
+        HIPCHK(gsx::op::StreamSynchronize(v->stream));
+        if (rep[0])
+            return fail(GSX_ERR_HIP, "GSX_VALIDATE: model '%s' slab %u: %s (tile %u: %u, %u, %u); n_tiles %u, tiles %ux%u, ranges_clean %d, "
+                        "clear_ranges %d, speculated %d, later %d, slab_cap %u, rec_n %llu", m->key.c_str(), slab_index,
+                        rep[0] == 1 ? "tile range outside the sorted entries" : "list index outside the records", rep[1], rep[2], rep[3], rep[4],
+                        f.n_tiles, m->fc.tiles_x, m->fc.tiles_y, (int)m->ranges_clean, (int)f.clear_ranges, (int)m->spec_round1, (int)later, slab_cap,
+                        (unsigned long long)m->rec_n);
+    }
+    {
+        ScopedPass t(v, GSX_PASS_COMPOSITE);
+        if (f.blocks) {
+            // (a slab whose entries did not fit the pair buffers — decided on the device — has its tail composited pair-free by the
+            //  same launch: the frame is complete without a host round trip)
+            HIPCHK(launch_composite_blocks(v->stream, m->fc, m->ranges.as<uint2>(), sorted_records ? nullptr : m->tile_list,
+                                           sorted_records ? m->brec_sorted.as<uint4>() : m->srect.as<uint4>(), m->rec(), fb_ptr(v),
+                                           later, f.done, f.row_words, f.done_count, f.tile_sat, win, f.row_lo, f.row_hi, f.bsx, f.bsy, f.row_work, f.dc, j1,
+                                           d_n, m->sorted_idx, m->sk_out.as<uint32_t>(),
+                                           (v->tile_profile && slab_index == 0) ? v->tile_prof.as<uint4>() : nullptr,
+                                           (f.order_buf && m->tile_order_valid) ? f.order_buf + 1 + f.n_tiles : nullptr,
+                                           f.order_buf ? f.order_buf + 1 : nullptr, m->rec().rect8 /* (null for imported records) */, f.depth_lim));
+        } else {
+            HIPCHK(launch_composite(v->stream, m->fc, m->ranges.as<uint2>(), m->tile_list, m->rec(), fb_ptr(v),
+                                    later, f.done, f.row_words, f.done_count, f.clear_ranges, f.tile_sat, f.row_work, f.depth_lim));
+            m->ranges_clean = f.clear_ranges;  // the compositor zeroed every range it consumed
+        }
+        v->pass_launches[GSX_PASS_COMPOSITE] += 1;
+        // per-tile lists: the slab's entries did not fit the pair buffers (decided on the device): its tail is composited
+        // pair-free, so the frame is complete without a host round trip; otherwise this launch falls through
+        if (!f.blocks)
+            HIPCHK(launch_composite_spill(v->stream, m->fc, f.dc, j1, d_n, m->sorted_idx, m->sk_out.as<uint32_t>(), m->rec(), fb_ptr(v),
+                                          f.done, f.row_words, f.done_count, f.tile_sat, f.row_lo, f.row_hi, win, f.depth_lim));
+    }
+    return GSX_OK;
+}
+
+// this model's windows for its next frame
+static gsx_status enqueue_next_windows(gsx_viewer* v, Model* m, const SlabFrame& f) {
+    ScopedPass t(v, GSX_PASS_COMPOSITE);
+    HIPCHK(launch_spec_next(v->stream, f.tile_sat, f.done, f.done_before, f.row_words, m->fc.tiles_x, m->fc.tiles_y,
+                            v->options.spec_margin, v->options.spec_radius, m->spec_win.as<uint2>(), f.row_lo, f.row_hi, f.depth_bound));
+    // [max-pyramid of the window ends: admission in k_project | min-pyramid: "every tile takes it" in the binning]
+    // (the two as ONE launch — the last workgroup of k_spec_next building the pyramids — was measured, round 4: 20 us against
+    //  4.9 + 7.2: the device-scope fence in front of the ticket writes back what the compositor has just left dirty in the L2)
+    const size_t pw = window_pyramid_words(m->fc.tiles_x, m->fc.tiles_y);
+    HIPCHK(m->spec_coarse.ensure(8 * pw));
+    HIPCHK(launch_window_pyramid(v->stream, m->spec_win.as<uint2>(), m->fc.tiles_x, m->fc.tiles_y, m->spec_coarse.as<uint32_t>(), false,
+                                 nullptr, m->spec_coarse.as<uint32_t>() + pw));
+    m->spec_valid = true;
+    m->spec_tiles_x = m->fc.tiles_x;
+    m->spec_tiles_y = m->fc.tiles_y;
+    return GSX_OK;
+}
+
+// verify and repair, behind a speculated round's one slab.  Verification on the device: tiles with a bounded window that are still
+// open get, in one more round, exactly the records they were refused, composited behind what they hold.
+// *windows_enqueued: the next frame's windows are on the stream already (they went ahead of the host's wait for the verdict).
+static gsx_status verify_and_repair(gsx_viewer* v, Model* m, SlabFrame& f, uint32_t repair_slab_index, bool* windows_enqueued) {
+    const uint32_t n = (uint32_t)m->rec_n;
+    gsx_status st = GSX_OK;
+    bool repair = true;
+    {
+        ScopedPass t(v, GSX_PASS_DEPTH_SORT);
+        // auto (2): ask while repairs are rare AND the host waits for its frames anyway (it has called gsx_sync or a blocking readback
+        // since the frame before: the app's protocol, scene.rs:614, 873).  A host that streams frames without waiting is better off with
+        // the repair round always enqueued and decided on the device — eight launches that fall through, ~38 us of stream time since
+        // round 6 (22 launches, ~100 us, when this rule was made): cfg4, two / one frames in flight streaming / waiting per frame,
+        // always-device 2350 / 2064 / 1902 fps, always-ask 1980 / 2089 / 1950, the round-5 rule (ask whenever repairs are rare)
+        // 2200 / 1836 / 1955 — the worst of both while streaming (tools/ab_host_verify.py, profiles/r06_ab_host_verify.txt).
+        // While repairs are not rare, the verdicts are still posted and the host merely
+        // LOOKS at the latest one each frame (it lags by the frames in flight, and costs nothing): eight repair-free
+        // verdicts in a row and the host asks again.  (A blocking probe here cost milliseconds: a host that does not wait
+        // is ~10 frames ahead of the device.)
+        const bool automatic = v->options.host_verify == 2;
+        if (automatic && !m->hv_active && v->h_verdict) {
+            const unsigned long long w = __atomic_load_n(v->h_verdict, __ATOMIC_ACQUIRE);
+            const uint32_t wseq = (uint32_t)(w >> 32);
+            if (wseq != 0 && wseq != m->hv_seen_seq) {
+                m->hv_seen_seq = wseq;
+                m->hv_quiet = (uint32_t)w == 0u ? m->hv_quiet + 1u : 0u;
+                if (m->hv_quiet >= 8) m->hv_active = true;
+            }
+        }
+        const bool ask = v->options.host_verify == 1 || (automatic && m->hv_active && (v->parent ? v->parent : v)->host_waited);
+        const bool post = ask || automatic;
+        if (post && !v->h_verdict) {
+            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&v->h_verdict), 64, hipHostMallocDefault));
+            *v->h_verdict = 0;
+        }
+        const uint32_t seq = post ? ++v->verify_seq : 0;
+        HIPCHK(m->spec_need.ensure(4 * (size_t)f.row_words * m->fc.tiles_y));
+        // ... and in the same launch, when something needs repair: the min-pyramid of the repair windows' starts (the repair
+        // round's conservative admission test: four loads per record; an exact per-tile scan of every visible record cost
+        // 260-350 us here) and the repair slab's block table
+        HIPCHK(m->spec_coarse2.ensure(4 * window_pyramid_words(m->fc.tiles_x, m->fc.tiles_y)));
+        const BlockGrid grid = block_grid(f.bsx, f.bsy, m->fc.tiles_x, f.row_lo, f.row_hi);
+        HIPCHK(launch_spec_verify(v->stream, f.window, f.done, f.row_words, m->fc.tiles_x, m->fc.tiles_y,
+                                  m->spec_win2.as<uint2>(), m->spec_need.as<uint32_t>(), &f.dc->spec_need, f.row_lo, f.row_hi,
+                                  post ? v->h_verdict : nullptr, seq, m->spec_coarse2.as<uint32_t>(), f.blocks ? &grid : nullptr,
+                                  f.blocks ? m->block_table.as<uint4>() : nullptr, f.blocks ? m->ranges.as<uint2>() : nullptr, f.depth_bound));
+        if (ask) {
+            // Nothing to repair (most frames): the ~20 launches of the second round would all fall through, at a few
+            // microseconds of stream time each.  So the verdict comes to the host: one pinned word, written by the
+            // verification kernel.  The next frame's windows are enqueued first — they are what follows when there is
+            // nothing to repair, and they keep the stream busy while the word travels; after a repair they are redone.
+            if ((st = enqueue_next_windows(v, m, f))) return st;
+            uint32_t need = 0;
+            if ((st = wait_verdict(v, seq, &need))) return st;
+            repair = need != 0;
+            *windows_enqueued = !repair;
+            // auto: a frame that repairs costs more with the wait than without (the host enqueues the second round
+            // while the device idles); stop asking when half of the last eight frames repaired
+            m->hv_history = (m->hv_history << 1) | (repair ? 1u : 0u);
+            if (automatic && __builtin_popcount(m->hv_history & 0xFFu) >= 6) {
+                m->hv_active = false;
+                m->hv_history = 0;
+                m->hv_quiet = 0;
+            }
+        }
+    }
+    if (!repair) return GSX_OK;
+    {
+        ScopedPass t(v, GSX_PASS_DEPTH_SORT);
+        HIPCHK(m->adm_ballots2.ensure(8 * ((std::max<size_t>(n, 1) + 63) / 64)));
+        HIPCHK(m->adm_counts2.ensure(4 * (std::max<size_t>(admit_blocks(n), 1) + 4)));
+        // conservative admission against the min-pyramid of the repair windows' starts (launch_spec_verify built it; the
+        // binning applies the exact windows)
+        WindowPyramid pyr2 = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, m->spec_coarse2.as<uint32_t>());
+        pyr2.min_of_starts = 1;
+        uint32_t seq2 = 0;
+        const bool bucket2 = v->bucket_sort && !(m->last_repair_sorted > kBucketSortMax);
+        if (bucket2) {  // (the repair round's keys lie behind the windows: a population, and a key range, of their own)
+            if ((st = ensure_msd(v, m, m->msd_ws2))) return st;
+            seq2 = m->msd_seq2++;
+        }
+        HIPCHK(launch_admit(v->stream, m->proj_rec(), n, nullptr, m->fc.tiles_x, nullptr,
+                            f.row_words, pyr2, &f.dc->spec_need,
+                            m->adm_ballots2.as<unsigned long long>(), m->adm_counts2.as<uint32_t>(), &f.dc->n_sorted2,
+                            m->adm_pairs.as<uint2>(), bucket2 ? m->msd_ws2.as<uint32_t>() : nullptr, seq2));
+        if ((st = sort_admitted(v, m, n, &f.dc->n_sorted2, bucket2 ? &m->msd_ws2 : nullptr, seq2,
+                                LateProjection{m->adm_pairs.as<uint2>(), &f.dc->n_sorted2, m->adm_ballots.as<unsigned long long>(), m->rect8_active})))
+            return st;
+    }
+    return run_slab(v, m, f, 0, n, true, m->spec_win2.as<uint2>(), &f.dc->n_sorted2, repair_slab_index, nullptr, f.blocks);
+}
+
 // One model: bin + tile-sort + composite, front to back in depth slabs, enqueued without host syncs.
 // Slab bounds are planned on the record count (an upper bound of N_vis; kernels clamp to the device-side
 // N_vis), slab entry counts stay on the device, and once every tile this rank owns is saturated the
@@ -879,335 +1188,100 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
                                               v->depth_snap_h != m->fc.h_px) : depth)
         return fail(GSX_ERR_INVALID_ARG, "gsx_render: the depth test or its depth buffer changed since gsx_preprocess('%s'); call gsx_preprocess + "
                     "gsx_sort('%s') again", m->key.c_str(), m->key.c_str());
-    const uint32_t* depth_lim = depth ? v->depth_lim.as<uint32_t>() : nullptr;
-    const uint2* depth_bound = depth ? v->depth_win.as<uint2>() : nullptr;
-    const uint32_t n_tiles = m->fc.tiles_x * m->fc.tiles_y;
-    const uint32_t row_words = (m->fc.tiles_x + 31) / 32;
-    const bool progressive = v->options.progressive != 0;
-    uint32_t* done = progressive ? v->done_bits.as<uint32_t>() + 1 : nullptr;  // word 0 is the saturated-tile counter
-    uint32_t* done_count = v->done_bits.as<uint32_t>();
-    const bool speculate = progressive && v->options.speculative && !m->use_imported;
-    if (m->stats_copy_inflight && hipEventQuery(m->stats_event) == hipSuccess) {
-        m->stats_copy_inflight = false;
-        if (progressive) {
-            // (the slab plan of the next PLAIN frame — a probe of the speculation tuner — from the last plain frame: taken from a speculated
-            //  frame's single slab the hint merged everything behind the second slab into one, 11 M entries where four slabs make 1.5 M)
-            if (!m->stats_copy_speculated) m->slabs_hint = m->h_counters->slabs_used;
-            if (spec_debug_level() >= 3)
-                fprintf(stderr, "[gsx stats] viewer %p: copy of a %s frame: slabs_used %u, n_sorted %u, entries %u, max_needed %u, walk_max %u chunks (fine blocks: speculated %d, plain %d)\n", (void*)v, m->stats_copy_speculated ? "speculated" : "plain",
-                        m->h_counters->slabs_used, m->h_counters->n_sorted, m->h_counters->n_entries_total, m->h_counters->max_needed, m->h_counters->walk_max, (int)m->blocks_fine_spec, (int)m->blocks_fine_plain);
-            m->n_sorted = m->h_counters->n_sorted;
-        }
-        if (m->stats_copy_speculated) {
-            m->last_spec_sorted = m->h_counters->n_sorted;
-            m->last_repair_sorted = m->h_counters->n_sorted2;
-        }
-        if (m->stats_copy_slab_shading) m->slab_shading_off = (uint64_t)m->h_counters->n_shaded_total * 100u > (uint64_t)m->h_counters->n_visible * kSlabShadingMaxPercent;
-        note_overflow(m);  // a free-running loop learns here that some earlier frame spilled: larger pair buffers from now on
-        // long block lists (a scene where little saturates): the block sort carries the lists' records along (k_composite_blocks
-        // SORTED); with hysteresis, from whatever frame's statistics arrived last — either way the pixels are the same
-        const uint64_t per_tile = (uint64_t)m->h_counters->n_entries_total / std::max<uint32_t>(n_tiles, 1u);
-        m->lists_long = m->lists_long ? per_tile > 500u : per_tile > 900u;
-        // a tile that never saturates walks its block's whole list, 128 candidates per ~1.5 us, and the launch is as slow as that tile
-        // (an open horizon: 425 chunks for 1900 takers with blocks of 8 x 4 tiles).  Blocks of a quarter the size cut the walk ~3.5x
-        // and cost a second digit in the block sort and ~2x the entries: - 12 % on cfg4's orbit, + 16 % under an open sky
-        // (tools/ab_blocks.py, round 5).  So the block size follows the longest walk of an earlier frame (SlabStats::walk_max, left
-        // by tile_order_job), with hysteresis; either way the pixels are the same.
-        // (one flag per schedule: an unspeculated frame — a probe of the tuner among speculated ones — walks its first slab's whole lists,
-        //  several times the walk of the speculated frames around it; its statistic used to put THEM into fine blocks, where the walk
-        //  then stayed above the way-back threshold: the same bench command read 2040 or 1830 fps with one frame in flight, 20.0 or 21.6
-        //  launches a frame, depending on whether a stats copy happened to catch a probe frame — round 6)
-        const uint32_t walk = m->h_counters->walk_max;
-        bool& fine = m->stats_copy_speculated ? m->blocks_fine_spec : m->blocks_fine_plain;
-        fine = fine ? walk > kWalkFineOff : walk > kWalkFineOn;
-    }
+    SlabFrame f{};
+    f.progressive = v->options.progressive != 0;
+    f.n_tiles = m->fc.tiles_x * m->fc.tiles_y;
+    f.row_words = (m->fc.tiles_x + 31) / 32;
+    absorb_stats_copy(v, m, f.progressive, f.n_tiles);
     std::vector<uint32_t> bounds;
-    const bool imported_windows = m->use_imported && m->has_window && progressive;
-    if (m->spec_round1 || imported_windows) {
-        // a speculated round is ONE slab: the windows already bound what every tile takes to little more than it needs,
-        // and the compositor stops a saturated tile by itself; more slabs only add launches (measured on cfg4: 551 fps
-        // with one slab, 487 with three).  The kernels stride over what exists on the device, so the bound is free.
-        // (Same for the imported records of an index-sharded frame whose exchange was windowed.)
-        bounds = {0u, (uint32_t)m->rec_n};
-    } else {
-        plan_slabs(v->options, (uint32_t)m->rec_n, &bounds);
-        if (progressive) merge_tail_slabs(&bounds, m->slabs_hint);
-    }
-    if (spec_debug_level() >= 3) {
-        fprintf(stderr, "[gsx slabs] viewer %p model '%s': speculated %d, slab shading %d, hint %u, slabs", (void*)v, m->key.c_str(), (int)m->spec_round1, (int)m->slab_shading, m->slabs_hint);
-        for (uint32_t b : bounds) fprintf(stderr, " %u", b);
-        fprintf(stderr, "\n");
-    }
-    Counters* dc = m->counters.as<Counters>();
-    const uint32_t row_lo = std::min(m->row_lo, m->fc.tiles_y), row_hi = std::min(m->row_hi, m->fc.tiles_y);
-    const uint32_t owned_tiles = (row_hi > row_lo ? row_hi - row_lo : 0) * m->fc.tiles_x;
-    const uint2* window = (m->use_imported && m->has_window) ? (m->window_ptr ? m->window_ptr : m->window.as<uint2>()) : nullptr;
-    if (m->spec_round1) window = depth ? m->spec_dwin.as<uint2>() : m->spec_win.as<uint2>();
-    else if (depth) window = depth_bound;
-    uint32_t* tile_sat = progressive ? done + row_words * m->fc.tiles_y : nullptr;  // [count | bitmap | saturation keys | row work]
-    // multi-GPU: what the tiles of every tile row walked, summed — the next frame's bands are balanced by it (gsx_shard_frame.cpp)
-    uint32_t* row_work = (progressive && m->use_imported) ? tile_sat + (size_t)n_tiles : nullptr;
-
-    // pair capacity to begin with: 16 entries per record for small models (per-tile lists), 6 for large ones (block lists need
-    // ~3 per record on speculated frames, 0.2 on depth slabs; a frame that wants more spills on the device and the host grows
-    // the buffers when it learns of it) — 32 bytes of pair / sort buffers per entry
-    // (a frame without depth slabs keeps per-tile lists of the whole model: 16 as well)
-    {
-        // (round 6: large progressive models start at TWO entries per record — cfg4's largest slab makes 0.2, 32 bytes of pair / sort buffers an
-        //  entry were 192 bytes a Gaussian and lane at the 6 entries of rounds 2-5; a scene that wants more — large splats, nothing saturating —
-        //  spills on the device for the few frames it takes the host to learn of it: note_overflow doubles, or jumps to what was needed)
-        const uint64_t per_record = (!progressive || m->rec_n <= (1u << 18)) ? 16u : 2u;
-        m->tile_cap = std::max<uint64_t>(m->tile_cap, std::max<uint64_t>(1u << 20, per_record * m->rec_n));
-    }
-    if (v->tile_cap_fixed) m->tile_cap = v->tile_cap_fixed;  // GSX_TILE_CAP (tests): a capacity that overflows on purpose
-    m->tile_cap = std::min<uint64_t>(m->tile_cap, 0xFFFFF000ull);
-    const uint32_t cap = (uint32_t)m->tile_cap;
-    {
-        const size_t bytes = sizeof(uint32_t) * (size_t)cap;
-        HIPCHK(m->tp_src.ensure(2 * bytes));
-        HIPCHK(m->tk_out.ensure(bytes));
-        HIPCHK(m->tv_out.ensure(bytes));
-        const size_t ws = 4 * radix_workspace_words(cap);
-        if (ws > m->tsort_ws.bytes) {
-            HIPCHK(m->tsort_ws.ensure(ws));
-            HIPCHK(gsx::op::MemsetAsync(m->tsort_ws.p, 0, m->tsort_ws.bytes, v->stream));
-        }
-        if (sizeof(uint2) * (size_t)n_tiles > m->ranges.bytes) m->ranges_clean = false;
-        HIPCHK(m->ranges.ensure(sizeof(uint2) * (size_t)std::max<uint32_t>(n_tiles, 1024u)));  // (block lists: up to 1024 block ranges)
-    }
-    // reset this model's per-frame totals (n_visible and n_sorted stay) — and, for the frame's first model, the frame's saturation
-    // state: one launch, or none where the first slab's block-table kernel can do it on its way (below)
-    ZeroJob zero{&dc->n_entries, (uint32_t)((sizeof(Counters) - offsetof(Counters, n_entries)) / 4), nullptr, 0};
-    if (frame_zero) {
-        zero.b = frame_zero->a;
-        zero.nb = frame_zero->na;
-    }
-    bool zero_pending = true;
-    const uint32_t* done_before = nullptr;
-    uint32_t keep_done_words = 0;
-    if (speculate) {
-        const size_t bm = 4 * (size_t)row_words * m->fc.tiles_y;
-        HIPCHK(m->spec_win.ensure(sizeof(uint2) * (size_t)n_tiles));
-        HIPCHK(m->spec_win2.ensure(sizeof(uint2) * (size_t)n_tiles));
-        if (carry) {  // nearer models already saturated some tiles: remember which, they say nothing about this model
-            HIPCHK(m->spec_done_before.ensure(bm));
-            done_before = m->spec_done_before.as<uint32_t>();
-            keep_done_words = (uint32_t)(bm / 4);
-        }
-    }
-    const int bits = std::max<int>(1, (int)ceil_log2(n_tiles));
-    // Progressive frames bin by BLOCKS of tiles (<= 256 of them: one 8-bit sort pass) and let the compositor decide per tile
-    // (kernels_bin.hip "block lists").
+    const bool imported_windows = m->use_imported && m->has_window && f.progressive;
+    plan_frame_slabs(v, m, m->spec_round1 || imported_windows, &bounds);
+    const bool first_slab = bounds.size() >= 2 && bounds[1] > bounds[0];
     // a single-slab front model keeps complete per-tile lists (gsx_model_download_tile_lists): that frame bins by tile
     const bool lists_wanted = bounds.size() == 2 && !carry && !m->spec_round1 && !imported_windows;
-    const bool blocks = progressive && v->bin_mode == 1 && !lists_wanted;
-    // gsx_preprocess left the conic / colour records (and, in rect8 mode, the `a` records) to the depth slabs' shading lists, and the
-    // frame bins by tile after all: min_slab, first_slab_divisor or growth changed between gsx_preprocess and gsx_render so that one
-    // slab remains (gsx_viewer_set_render_options does not send the model back through gsx_preprocess for them).
-    // The per-tile kernels read every visible record whole: complete them (same values as the full projection)
-    if (m->slab_shading && m->lazy && !blocks) {
-        const gsx_status cst = complete_records(v, m);
-        if (cst) return cst;
-    }
-    if (!blocks || bounds.size() < 2 || bounds[1] == bounds[0]) {  // no block-table kernel ahead (or no slab at all): zero here
-        HIPCHK(launch_zero_words(v->stream, zero.a, zero.na, zero.b, zero.nb));
-        zero_pending = false;
-        if (keep_done_words)
-            HIPCHK(gsx::op::MemcpyAsync(m->spec_done_before.p, done, 4 * (size_t)keep_done_words, hipMemcpyDeviceToDevice, v->stream));
-    } else if (keep_done_words) {   // ... the first slab's block-table kernel copies the bitmap on its way (it runs before anything sets a bit)
-        zero.copy_src = done;
-        zero.copy_dst = m->spec_done_before.as<uint32_t>();
-        zero.n_copy = keep_done_words;
-    }
-    uint32_t bsx = 0, bsy = 0;
+    f.dc = m->counters.as<Counters>();
+    f.depth_lim = depth ? v->depth_lim.as<uint32_t>() : nullptr;
+    f.depth_bound = depth ? v->depth_win.as<uint2>() : nullptr;
+    f.done = f.progressive ? v->done_bits.as<uint32_t>() + 1 : nullptr;  // word 0 is the saturated-tile counter
+    f.done_count = v->done_bits.as<uint32_t>();
+    f.row_lo = std::min(m->row_lo, m->fc.tiles_y);
+    f.row_hi = std::min(m->row_hi, m->fc.tiles_y);
+    f.owned_tiles = (f.row_hi > f.row_lo ? f.row_hi - f.row_lo : 0) * m->fc.tiles_x;
+    f.window = (m->use_imported && m->has_window) ? (m->window_ptr ? m->window_ptr : m->window.as<uint2>()) : nullptr;
+    if (m->spec_round1) f.window = depth ? m->spec_dwin.as<uint2>() : m->spec_win.as<uint2>();
+    else if (depth) f.window = f.depth_bound;
+    f.tile_sat = f.progressive ? f.done + f.row_words * m->fc.tiles_y : nullptr;  // [count | bitmap | saturation keys | row work]
+    // multi-GPU: what the tiles of every tile row walked, summed — the next frame's bands are balanced by it (gsx_shard_frame.cpp)
+    f.row_work = (f.progressive && m->use_imported) ? f.tile_sat + (size_t)f.n_tiles : nullptr;
+    f.bits = std::max<int>(1, (int)ceil_log2(f.n_tiles));
+    // Progressive frames bin by BLOCKS of tiles (<= 256 of them: one 8-bit sort pass) and let the compositor decide per tile
+    // (kernels_bin.hip "block lists").
+    f.blocks = f.progressive && v->bin_mode == 1 && !lists_wanted;
+    f.clear_ranges = f.progressive && !lists_wanted;
     // most blocks of this frame: GSX_BLOCKS_MAX when it was given, otherwise 256 (one 8-bit sort pass) — or 1024 while some tile's walk is long
-    const uint32_t blocks_max = v->blocks_adaptive && (m->spec_round1 ? m->blocks_fine_spec : m->blocks_fine_plain) ? 1024u : v->blocks_max;
-    if (blocks) {
+    f.blocks_max = v->blocks_adaptive && (m->spec_round1 ? m->blocks_fine_spec : m->blocks_fine_plain) ? 1024u : v->blocks_max;
+    if (f.blocks) {
         // The grid covers the rows this viewer composites (block_grid).  An index-sharded rank sizes its blocks for the taller of its
         // own band and an EQUAL band: every rank whose band is no taller than that bins by the same block size, so what a tile row
         // costs — the figure the next frame's bands are balanced by — does not change with the band it happens to lie in (sized by
         // the own band alone, a row was cheaper in a short band than in a tall one and the balance settled at 1.46 x the mean).
-        const uint32_t grid_rows = std::max(row_hi > row_lo ? row_hi - row_lo : 1u, m->use_imported ? m->rows_nominal : 0u);
-        auto count = [&]() { const BlockGrid g = block_grid(bsx, bsy, m->fc.tiles_x, 0, grid_rows); return (uint64_t)g.blocks_x * g.blocks_y; };
-        while (count() > blocks_max) (bsx <= bsy ? bsx : bsy) += 1;
-        HIPCHK(m->block_table.ensure(sizeof(uint4) * 1024));
-        if (v->tile_profile) HIPCHK(v->tile_prof.ensure(sizeof(uint4) * (size_t)n_tiles));
+        const uint32_t grid_rows = std::max(f.row_hi > f.row_lo ? f.row_hi - f.row_lo : 1u, m->use_imported ? m->rows_nominal : 0u);
+        for (;;) {
+            const BlockGrid g = block_grid(f.bsx, f.bsy, m->fc.tiles_x, 0, grid_rows);
+            if ((uint64_t)g.blocks_x * g.blocks_y <= f.blocks_max) break;
+            (f.bsx <= f.bsy ? f.bsx : f.bsy) += 1;
+        }
     }
-    {   // the pair sort's ping-pong buffers: only a sort of two digits has an intermediate, only one of three a second (block lists of
-        // <= 256 blocks — every slab of a large model — are ONE digit: emitted pairs -> sorted keys / values, 32 bytes a Gaussian and lane less)
-        const int pair_bits = blocks ? (int)std::max<uint32_t>(1u, ceil_log2(blocks_max)) : bits;
-        const size_t pair_bytes = 2 * sizeof(uint32_t) * (size_t)cap;
-        if (pair_bits > 8) HIPCHK(m->tp_a.ensure(pair_bytes));
-        if (pair_bits > 16) HIPCHK(m->tp_b.ensure(pair_bytes));
+    gsx_status st = size_pair_buffers(v, m, f);
+    if (st) return st;
+    // reset this model's per-frame totals (n_visible and n_sorted stay) — and, for the frame's first model, the frame's saturation
+    // state: one launch, or none where the first slab's block-table kernel can do it on its way (below)
+    f.zero = ZeroJob{&f.dc->n_entries, (uint32_t)((sizeof(Counters) - offsetof(Counters, n_entries)) / 4), nullptr, 0};
+    if (frame_zero) {
+        f.zero.b = frame_zero->a;
+        f.zero.nb = frame_zero->na;
+    }
+    f.zero_pending = true;
+    const bool speculate = f.progressive && v->options.speculative && !m->use_imported;
+    uint32_t keep_done_words = 0;
+    if (speculate) {
+        const size_t bm = 4 * (size_t)f.row_words * m->fc.tiles_y;
+        HIPCHK(m->spec_win.ensure(sizeof(uint2) * (size_t)f.n_tiles));
+        HIPCHK(m->spec_win2.ensure(sizeof(uint2) * (size_t)f.n_tiles));
+        if (carry) {  // nearer models already saturated some tiles: remember which, they say nothing about this model
+            HIPCHK(m->spec_done_before.ensure(bm));
+            f.done_before = m->spec_done_before.as<uint32_t>();
+            keep_done_words = (uint32_t)(bm / 4);
+        }
+    }
+    // gsx_preprocess left the conic / colour records (and, in rect8 mode, the `a` records) to the depth slabs' shading lists, and the
+    // frame bins by tile after all: min_slab, first_slab_divisor or growth changed between gsx_preprocess and gsx_render so that one
+    // slab remains (gsx_viewer_set_render_options does not send the model back through gsx_preprocess for them).
+    // The per-tile kernels read every visible record whole: complete them (same values as the full projection)
+    if (m->slab_shading && m->lazy && !f.blocks && (st = complete_records(v, m))) return st;
+    if (!f.blocks || !first_slab) {  // no block-table kernel ahead (or no slab at all): zero here
+        HIPCHK(launch_zero_words(v->stream, f.zero.a, f.zero.na, f.zero.b, f.zero.nb));
+        f.zero_pending = false;
+        if (keep_done_words)
+            HIPCHK(gsx::op::MemcpyAsync(m->spec_done_before.p, f.done, 4 * (size_t)keep_done_words, hipMemcpyDeviceToDevice, v->stream));
+    } else if (keep_done_words) {   // ... the first slab's block-table kernel copies the bitmap on its way (it runs before anything sets a bit)
+        f.zero.copy_src = f.done;
+        f.zero.copy_dst = m->spec_done_before.as<uint32_t>();
+        f.zero.n_copy = keep_done_words;
     }
     // Block compositor: the tiles that were expensive in the model's frame before are dispatched first (k_composite_blocks; a
     // schedule, not data).  The order is made by one more workgroup of the frame's first block-table kernel; a second round of the
     // same frame (cont) keeps the first round's, and what it costs counts towards the next frame's.
-    uint32_t* order_buf = nullptr;
-    bool order_build = false;
-    if (blocks && v->tile_order_on && n_tiles <= kTileOrderMax && bounds.size() >= 2 && bounds[1] > bounds[0]) {
-        if (m->tile_order_tiles != n_tiles) {
-            HIPCHK(m->tile_order.ensure(4 * (1 + 2 * (size_t)n_tiles)));
-            HIPCHK(gsx::op::MemsetAsync(m->tile_order.p, 0, 4 * (1 + (size_t)n_tiles), v->stream));
-            m->tile_order_tiles = n_tiles;
+    if (f.blocks && v->tile_order_on && f.n_tiles <= kTileOrderMax && first_slab) {
+        if (m->tile_order_tiles != f.n_tiles) {
+            HIPCHK(m->tile_order.ensure(4 * (1 + 2 * (size_t)f.n_tiles)));
+            HIPCHK(gsx::op::MemsetAsync(m->tile_order.p, 0, 4 * (1 + (size_t)f.n_tiles), v->stream));
+            m->tile_order_tiles = f.n_tiles;
             m->tile_order_valid = false;
         }
-        order_buf = m->tile_order.as<uint32_t>();
-        order_build = !cont || !m->tile_order_valid;
+        f.order_buf = m->tile_order.as<uint32_t>();
+        f.order_build = !cont || !m->tile_order_valid;
     }
-    // a single-slab front model keeps its complete tile lists for gsx_model_download_tile_lists
-    const bool clear_ranges = progressive && !(bounds.size() == 2 && !carry && !m->spec_round1 && !imported_windows);
-    // one depth slab [j0, j1) of the current depth order: bin -> tile sort -> ranges -> composite
-    auto run_slab = [&](uint32_t j0, uint32_t j1, bool later, const uint2* win, const uint32_t* d_n, uint32_t slab_index,
-                        const WindowPyramid* min_ends = nullptr, bool table_ready = false) -> gsx_status {
-        // the very first slab of the frame sees no saturated tile: plain rectangle areas
-        const uint32_t* done_in = later ? done : nullptr;
-        bool sorted_records = false;  // block lists: the compositor's candidates travel through the block sort (long lists)
-        // a slab of S splats can produce at most S * n_tiles entries; size the sort launch by the smaller bound
-        const uint32_t slab_cap = (uint32_t)std::min<uint64_t>(cap, (uint64_t)(j1 - j0) * std::min<uint64_t>(owned_tiles, 1u << 16));
-        if (blocks) {
-            // (the block sort's one-digit histogram — entries per block — counted by the emit kernel on its way instead of by a launch of
-            //  its own was measured, round 4: two launches less per frame, and slower — every emit workgroup flushes up to 256 bins to
-            //  the same 256 addresses: binning 69 -> 86 us against block sort 37 -> 25 on a speculated cfg4 frame, 218 -> 327 against
-            //  69 -> 45 unspeculated.  Not kept.)
-            const int block_bits = (int)std::max<uint32_t>(1u, ceil_log2(blocks_max));
-            ZeroJob jobs = zero_pending ? zero : ZeroJob{};
-            if (order_build && !table_ready) {
-                jobs.order_buf = order_buf;
-                jobs.order_tiles = n_tiles;
-                m->tile_order_valid = true;
-                order_build = false;
-            }
-            const bool fused = v->bin_fused;
-            const bool slab_shade = fused && m->slab_shading && m->lazy && !m->spec_round1;
-            if (slab_shade) HIPCHK(m->adm_pairs.ensure(8 * std::max<size_t>(m->rec_n, 1)));
-            {
-                ScopedPass t(v, GSX_PASS_BIN);
-                if (fused) {
-                    const size_t bw = 4 * bin_workspace_words(m->sortbin_cap);
-                    if (m->bin_ws.bytes < bw) {
-                        HIPCHK(m->bin_ws.ensure(bw));
-                        HIPCHK(gsx::op::MemsetAsync(m->bin_ws.p, 0, m->bin_ws.bytes, v->stream));
-                    }
-                    HIPCHK(launch_block_bin_fused(v->stream, j0, j1, d_n, m->sorted_idx, m->rec(), m->sk_out.as<uint32_t>(), m->srect.as<uint4>(), dc, cap,
-                                                  row_lo, row_hi, done_in, row_words, (progressive && later) ? done_count : nullptr, owned_tiles, slab_index,
-                                                  win, m->fc.tiles_x, m->fc.tiles_y, bsx, bsy, m->block_table.as<uint4>(), m->tp_src.as<uint2>(),
-                                                  m->ranges.as<uint2>(), jobs, table_ready, m->bin_ws.as<uint32_t>(), m->tsort_ws.as<uint32_t>(), block_bits,
-                                                  slab_shade ? m->adm_pairs.as<uint2>() : nullptr,
-                                                  (slab_shade && m->sorted_code_valid) ? m->sorted_code.as<uint8_t>() : nullptr));
-                    // slab shading: conic / colour records for exactly the records of this slab some block takes (and the frame's colour ops on them)
-                    if (slab_shade) {
-                        const gsx_status sst = shade_admitted(v, m, LateProjection{m->adm_pairs.as<uint2>(), &dc->n_slab_shade, nullptr, m->rect8_active});
-                        if (sst) return sst;
-                    }
-                } else {
-                    gsx_status cst = ensure_count_buffers(m);
-                    if (cst) return cst;
-                    HIPCHK(launch_block_bin(v->stream, j0, j1, d_n, m->sorted_idx, m->rec(), m->sk_out.as<uint32_t>(), m->srect.as<uint4>(),
-                                            m->cnt.as<uint32_t>(), m->block_sums.as<uint32_t>(), dc, cap, row_lo, row_hi, done_in, row_words,
-                                            (progressive && later) ? done_count : nullptr, owned_tiles, slab_index, win, m->fc.tiles_x,
-                                            m->fc.tiles_y, bsx, bsy, m->block_table.as<uint4>(), m->tp_src.as<uint2>(), m->ranges.as<uint2>(),
-                                            jobs, table_ready));
-                }
-                zero_pending = false;
-                v->pass_launches[GSX_PASS_BIN] += 1;
-            }
-            {
-                ScopedPass t(v, GSX_PASS_TILE_SORT);
-                RadixBuffers rb{nullptr, nullptr, m->tp_src.as<uint2>(), m->tk_out.as<uint32_t>(), m->tv_out.as<uint32_t>(),
-                                m->tp_a.as<uint2>(), m->tp_b.as<uint2>(), m->tsort_ws.as<uint32_t>()};
-                const uint32_t block_cap = (uint32_t)std::min<uint64_t>(cap, (uint64_t)(j1 - j0) * 256u);
-                // (<= 256 blocks: ONE digit, and the block ranges are the scan of its histogram — no k_tile_ranges launch;
-                //  k_block_table zeroed the ranges, which is what stays when the slab made no entry at all)
-                // (<= 256 blocks: ONE digit, and the block ranges are the scan of its histogram — no k_tile_ranges launch;
-                //  k_block_table zeroed the ranges, which is what stays when the slab made no entry at all)
-                // sorted_records: the write-out also carries every entry's {rect, key, index} record along
-                sorted_records = v->sorted_records >= 0 ? v->sorted_records == 1 : m->lists_long;  // (the LAST digit pass carries them)
-                if (sorted_records) HIPCHK(m->brec_sorted.ensure(sizeof(uint4) * (size_t)cap));
-                HIPCHK(launch_radix_sort(v->stream, rb, block_cap, &dc->n_entries, block_bits, false, false, block_bits <= 8 ? m->ranges.as<uint2>() : nullptr,
-                                         sorted_records ? m->srect.as<uint4>() : nullptr, sorted_records ? m->brec_sorted.as<uint4>() : nullptr, fused));
-                m->tile_keys = m->tk_out.as<uint32_t>();
-                m->tile_list = m->tv_out.as<uint32_t>();
-                v->pass_launches[GSX_PASS_TILE_SORT] += 1;
-                if (block_bits > 8) {  // GSX_BLOCKS_MAX above 256: two digits, ranges from the sorted keys
-                    ScopedPass t2(v, GSX_PASS_BIN);
-                    HIPCHK(launch_tile_ranges(v->stream, block_cap, &dc->n_entries, m->tile_keys, 1024u, m->ranges.as<uint2>(), true));
-                }
-                m->ranges_clean = false;
-            }
-        } else {
-            {
-                ScopedPass t(v, GSX_PASS_BIN);
-                gsx_status cst = ensure_count_buffers(m);
-                if (cst) return cst;
-                HIPCHK(launch_tile_counts(v->stream, j0, j1, d_n, m->sorted_idx, m->rec(), m->srect.as<uint2>(),
-                                          m->cnt.as<uint32_t>(), m->block_sums.as<uint32_t>(), dc, cap, row_lo, row_hi, done_in,
-                                          row_words, (progressive && later) ? done_count : nullptr, owned_tiles, slab_index,
-                                          win, m->sk_out.as<uint32_t>(), m->fc.tiles_x, min_ends));
-                HIPCHK(launch_tile_emit(v->stream, j0, j1, m->sorted_idx, m->srect.as<uint2>(), m->cnt.as<uint32_t>(),
-                                        m->block_sums.as<uint32_t>(), m->fc.tiles_x, m->tp_src.as<uint2>(), row_lo, row_hi,
-                                        done_in, row_words, d_n, &dc->n_entries, cap, win, m->sk_out.as<uint32_t>(), &dc->slab_cut));
-                v->pass_launches[GSX_PASS_BIN] += 1;
-            }
-            {
-                ScopedPass t(v, GSX_PASS_TILE_SORT);
-                RadixBuffers rb{nullptr, nullptr, m->tp_src.as<uint2>(), m->tk_out.as<uint32_t>(), m->tv_out.as<uint32_t>(),
-                                m->tp_a.as<uint2>(), m->tp_b.as<uint2>(), m->tsort_ws.as<uint32_t>()};
-                HIPCHK(launch_radix_sort(v->stream, rb, slab_cap, &dc->n_entries, bits, false));
-                m->tile_keys = m->tk_out.as<uint32_t>();
-                m->tile_list = m->tv_out.as<uint32_t>();
-                v->pass_launches[GSX_PASS_TILE_SORT] += (bits + 7) / 8;
-            }
-            {
-                ScopedPass t(v, GSX_PASS_BIN);
-                HIPCHK(launch_tile_ranges(v->stream, slab_cap, &dc->n_entries, m->tile_keys, (uint32_t)(m->ranges.bytes / sizeof(uint2)),
-                                          m->ranges.as<uint2>(), m->ranges_clean));
-            }
-        }
-        if (v->validate) {  // debug: check what the compositor will dereference, on the host, before it runs
-            HIPCHK(v->scratch.ensure(64));
-            HIPCHK(gsx::op::MemsetAsync(v->scratch.p, 0, 64, v->stream));
-            // (block lists: one range per block, list values are positions in the slab)
-            const uint32_t n_ranges = blocks ? block_grid(bsx, bsy, m->fc.tiles_x, row_lo, row_hi).blocks_x * block_grid(bsx, bsy, m->fc.tiles_x, row_lo, row_hi).blocks_y : n_tiles;
-            HIPCHK(launch_validate_tiles(v->stream, m->ranges.as<uint2>(), n_ranges, m->tile_list, &dc->n_entries, blocks ? cap : slab_cap,
-                                         blocks ? j1 - j0 : (uint32_t)m->rec_n, v->scratch.as<uint32_t>()));
-            uint32_t rep[8];
-            HIPCHK(gsx::op::MemcpyAsync(rep, v->scratch.p, 32, hipMemcpyDeviceToHost, v->stream));
-            HIPCHK(gsx::op::StreamSynchronize(v->stream));
-            if (rep[0])
-                return fail(GSX_ERR_HIP, "GSX_VALIDATE: model '%s' slab %u: %s (tile %u: %u, %u, %u); n_tiles %u, tiles %ux%u, ranges_clean %d, "
-                            "clear_ranges %d, speculated %d, later %d, slab_cap %u, rec_n %llu", m->key.c_str(), slab_index,
-                            rep[0] == 1 ? "tile range outside the sorted entries" : "list index outside the records", rep[1], rep[2], rep[3], rep[4],
-                            n_tiles, m->fc.tiles_x, m->fc.tiles_y, (int)m->ranges_clean, (int)clear_ranges, (int)m->spec_round1, (int)later, slab_cap,
-                            (unsigned long long)m->rec_n);
-        }
-        {
-            ScopedPass t(v, GSX_PASS_COMPOSITE);
-            if (blocks) {
-                // (a slab whose entries did not fit the pair buffers — decided on the device — has its tail composited pair-free by the
-                //  same launch: the frame is complete without a host round trip)
-                HIPCHK(launch_composite_blocks(v->stream, m->fc, m->ranges.as<uint2>(), sorted_records ? nullptr : m->tile_list,
-                                               sorted_records ? m->brec_sorted.as<uint4>() : m->srect.as<uint4>(), m->rec(), fb_ptr(v),
-                                               later, done, row_words, done_count, tile_sat, win, row_lo, row_hi, bsx, bsy, row_work, dc, j1,
-                                               d_n, m->sorted_idx, m->sk_out.as<uint32_t>(),
-                                               (v->tile_profile && slab_index == 0) ? v->tile_prof.as<uint4>() : nullptr,
-                                               (order_buf && m->tile_order_valid) ? order_buf + 1 + n_tiles : nullptr,
-                                               order_buf ? order_buf + 1 : nullptr, m->rec().rect8 /* (null for imported records) */, depth_lim));
-            } else {
-                HIPCHK(launch_composite(v->stream, m->fc, m->ranges.as<uint2>(), m->tile_list, m->rec(), fb_ptr(v),
-                                        later, done, row_words, done_count, clear_ranges, tile_sat, row_work, depth_lim));
-                m->ranges_clean = clear_ranges;  // the compositor zeroed every range it consumed
-            }
-            v->pass_launches[GSX_PASS_COMPOSITE] += 1;
-            // per-tile lists: the slab's entries did not fit the pair buffers (decided on the device): its tail is composited
-            // pair-free, so the frame is complete without a host round trip; otherwise this launch falls through
-            if (!blocks)
-                HIPCHK(launch_composite_spill(v->stream, m->fc, dc, j1, d_n, m->sorted_idx, m->sk_out.as<uint32_t>(), m->rec(), fb_ptr(v),
-                                              done, row_words, done_count, tile_sat, row_lo, row_hi, win, depth_lim));
-        }
-        return GSX_OK;
-    };
-    gsx_status st = GSX_OK;
     // a speculated round's windows all start at 0 and come with the min-pyramid of their ends (enqueue_next_windows)
     WindowPyramid min_ends{};
     bool have_min_ends = false;
@@ -1224,128 +1298,15 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
         have_min_ends = true;
     }
     for (size_t sl = 0; sl + 1 < bounds.size(); ++sl)
-        if ((st = run_slab(bounds[sl], bounds[sl + 1], carry || sl > 0, window, &dc->n_sorted, (uint32_t)sl,
-                           have_min_ends ? &min_ends : nullptr)))
+        if ((st = run_slab(v, m, f, bounds[sl], bounds[sl + 1], carry || sl > 0, f.window, &f.dc->n_sorted, (uint32_t)sl, have_min_ends ? &min_ends : nullptr)))
             return st;
     bool windows_enqueued = false;
-    auto enqueue_next_windows = [&]() -> gsx_status {  // this model's windows for its next frame
-        ScopedPass t(v, GSX_PASS_COMPOSITE);
-        HIPCHK(launch_spec_next(v->stream, tile_sat, done, done_before, row_words, m->fc.tiles_x, m->fc.tiles_y,
-                                v->options.spec_margin, v->options.spec_radius, m->spec_win.as<uint2>(), row_lo, row_hi, depth_bound));
-        // [max-pyramid of the window ends: admission in k_project | min-pyramid: "every tile takes it" in the binning]
-        // (the two as ONE launch — the last workgroup of k_spec_next building the pyramids — was measured, round 4: 20 us against
-        //  4.9 + 7.2: the device-scope fence in front of the ticket writes back what the compositor has just left dirty in the L2)
-        const size_t pw = window_pyramid_words(m->fc.tiles_x, m->fc.tiles_y);
-        HIPCHK(m->spec_coarse.ensure(8 * pw));
-        HIPCHK(launch_window_pyramid(v->stream, m->spec_win.as<uint2>(), m->fc.tiles_x, m->fc.tiles_y, m->spec_coarse.as<uint32_t>(), false,
-                                     nullptr, m->spec_coarse.as<uint32_t>() + pw));
-        m->spec_valid = true;
-        m->spec_tiles_x = m->fc.tiles_x;
-        m->spec_tiles_y = m->fc.tiles_y;
-        return GSX_OK;
-    };
     if (m->spec_round1) {
-        // verification on the device: tiles with a bounded window that are still open get, in one more round, exactly
-        // the records they were refused, composited behind what they hold.
-        const uint32_t n = (uint32_t)m->rec_n;
-        bool repair = true;
-        {
-            ScopedPass t(v, GSX_PASS_DEPTH_SORT);
-            // auto (2): ask while repairs are rare AND the host waits for its frames anyway (it has called gsx_sync or a blocking readback
-            // since the frame before: the app's protocol, scene.rs:614, 873).  A host that streams frames without waiting is better off with
-            // the repair round always enqueued and decided on the device — eight launches that fall through, ~38 us of stream time since
-            // round 6 (22 launches, ~100 us, when this rule was made): cfg4, two / one frames in flight streaming / waiting per frame,
-            // always-device 2350 / 2064 / 1902 fps, always-ask 1980 / 2089 / 1950, the round-5 rule (ask whenever repairs are rare)
-            // 2200 / 1836 / 1955 — the worst of both while streaming (tools/ab_host_verify.py, profiles/r06_ab_host_verify.txt).
-            // While repairs are not rare, the verdicts are still posted and the host merely
-            // LOOKS at the latest one each frame (it lags by the frames in flight, and costs nothing): eight repair-free
-            // verdicts in a row and the host asks again.  (A blocking probe here cost milliseconds: a host that does not wait
-            // is ~10 frames ahead of the device.)
-            const bool automatic = v->options.host_verify == 2;
-            if (automatic && !m->hv_active && v->h_verdict) {
-                const unsigned long long w = __atomic_load_n(v->h_verdict, __ATOMIC_ACQUIRE);
-                const uint32_t wseq = (uint32_t)(w >> 32);
-                if (wseq != 0 && wseq != m->hv_seen_seq) {
-                    m->hv_seen_seq = wseq;
-                    m->hv_quiet = (uint32_t)w == 0u ? m->hv_quiet + 1u : 0u;
-                    if (m->hv_quiet >= 8) m->hv_active = true;
-                }
-            }
-            const bool ask = v->options.host_verify == 1 || (automatic && m->hv_active && (v->parent ? v->parent : v)->host_waited);
-            const bool post = ask || automatic;
-            if (post && !v->h_verdict) {
-                HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&v->h_verdict), 64, hipHostMallocDefault));
-                *v->h_verdict = 0;
-            }
-            const uint32_t seq = post ? ++v->verify_seq : 0;
-            HIPCHK(m->spec_need.ensure(4 * (size_t)row_words * m->fc.tiles_y));
-            // ... and in the same launch, when something needs repair: the min-pyramid of the repair windows' starts (the repair
-            // round's conservative admission test: four loads per record; an exact per-tile scan of every visible record cost
-            // 260-350 us here) and the repair slab's block table
-            HIPCHK(m->spec_coarse2.ensure(4 * window_pyramid_words(m->fc.tiles_x, m->fc.tiles_y)));
-            const BlockGrid grid = block_grid(bsx, bsy, m->fc.tiles_x, row_lo, row_hi);
-                HIPCHK(launch_spec_verify(v->stream, window, done, row_words, m->fc.tiles_x, m->fc.tiles_y,
-                                      m->spec_win2.as<uint2>(), m->spec_need.as<uint32_t>(), &dc->spec_need, row_lo, row_hi,
-                                      post ? v->h_verdict : nullptr, seq, m->spec_coarse2.as<uint32_t>(), blocks ? &grid : nullptr,
-                                      blocks ? m->block_table.as<uint4>() : nullptr, blocks ? m->ranges.as<uint2>() : nullptr, depth_bound));
-            if (ask) {
-                // Nothing to repair (most frames): the ~20 launches of the second round would all fall through, at a few
-                // microseconds of stream time each.  So the verdict comes to the host: one pinned word, written by the
-                // verification kernel.  The next frame's windows are enqueued first — they are what follows when there is
-                // nothing to repair, and they keep the stream busy while the word travels; after a repair they are redone.
-                if ((st = enqueue_next_windows())) return st;
-                uint32_t need = 0;
-                if ((st = wait_verdict(v, seq, &need))) return st;
-                repair = need != 0;
-                windows_enqueued = !repair;
-                // auto: a frame that repairs costs more with the wait than without (the host enqueues the second round
-                // while the device idles); stop asking when half of the last eight frames repaired
-                m->hv_history = (m->hv_history << 1) | (repair ? 1u : 0u);
-                if (automatic && __builtin_popcount(m->hv_history & 0xFFu) >= 6) {
-                    m->hv_active = false;
-                    m->hv_history = 0;
-                    m->hv_quiet = 0;
-                }
-            }
-        }
-        if (repair) {
-            ScopedPass t(v, GSX_PASS_DEPTH_SORT);
-            HIPCHK(m->adm_ballots2.ensure(8 * ((std::max<size_t>(n, 1) + 63) / 64)));
-            HIPCHK(m->adm_counts2.ensure(4 * (std::max<size_t>(admit_blocks(n), 1) + 4)));
-            // conservative admission against the min-pyramid of the repair windows' starts (launch_spec_verify built it; the
-            // binning applies the exact windows)
-            WindowPyramid pyr2 = window_pyramid_layout(m->fc.tiles_x, m->fc.tiles_y, m->spec_coarse2.as<uint32_t>());
-            pyr2.min_of_starts = 1;
-            uint32_t seq2 = 0;
-            const bool bucket2 = v->bucket_sort && !(m->last_repair_sorted > kBucketSortMax);
-            if (bucket2) {  // (the repair round's keys lie behind the windows: a population, and a key range, of their own)
-                if ((st = ensure_msd(v, m, m->msd_ws2))) return st;
-                seq2 = m->msd_seq2++;
-            }
-            HIPCHK(launch_admit(v->stream, m->proj_rec(), n, nullptr, m->fc.tiles_x, nullptr,
-                                row_words, pyr2, &dc->spec_need,
-                                m->adm_ballots2.as<unsigned long long>(), m->adm_counts2.as<uint32_t>(), &dc->n_sorted2,
-                                m->adm_pairs.as<uint2>(), bucket2 ? m->msd_ws2.as<uint32_t>() : nullptr, seq2));
-            const LateProjection late2{m->adm_pairs.as<uint2>(), &dc->n_sorted2, m->adm_ballots.as<unsigned long long>(), m->rect8_active};
-            const bool rides2 = bucket2 && shading_rides(v, m);
-            if (m->lazy && !rides2) {  // the repair round needs records the lazy projection did not shade
-                gsx_status sst = shade_admitted(v, m, late2);
-                if (sst) return sst;
-            }
-            RadixBuffers rb{nullptr, nullptr, m->adm_pairs.as<uint2>(), m->sk_out.as<uint32_t>(), m->sv_out.as<uint32_t>(),
-                            m->dp_a.as<uint2>(), m->dp_b.as<uint2>(), m->sort_ws.as<uint32_t>()};
-            if (bucket2) {
-                const ShadeRide ride2 = rides2 ? shade_ride(m, late2) : ShadeRide{};
-                HIPCHK(launch_bucket_sort(v->stream, rb, n, &dc->n_sorted2, false, m->msd_ws2.as<uint32_t>(), seq2, true, rides2 ? &ride2 : nullptr));
-            } else {
-                HIPCHK(launch_radix_sort(v->stream, rb, n, &dc->n_sorted2, 32, false));
-            }
-        }
-        if (repair && (st = run_slab(0, n, true, m->spec_win2.as<uint2>(), &dc->n_sorted2, (uint32_t)bounds.size(), nullptr, blocks))) return st;
+        if ((st = verify_and_repair(v, m, f, (uint32_t)bounds.size(), &windows_enqueued))) return st;
         m->order_consumed = true;
     }
     if (speculate && m->windows_unwanted) m->spec_valid = false;
-    else if (speculate && !windows_enqueued && (st = enqueue_next_windows())) return st;
+    else if (speculate && !windows_enqueued && (st = enqueue_next_windows(v, m, f))) return st;
     // feed the next frames' slab plan without waiting — every fourth frame is plenty (the copy is two runtime kernels)
     if (!m->stats_copy_inflight && (m->stats_copy_tick++ & 3u) == 0) {
         if (!m->stats_event) HIPCHK(hipEventCreateWithFlags(&m->stats_event, hipEventDisableTiming));
@@ -1358,7 +1319,7 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
     tuner_frame_end(v, m);
     m->binned = true;
     m->stats_pending = true;
-    m->lists_complete = bounds.size() == 2 && !carry && !m->spec_round1 && !imported_windows;
+    m->lists_complete = lists_wanted;
     return GSX_OK;
 }
 

@@ -435,7 +435,7 @@ struct ZeroJob {
     uint32_t na = 0;
     uint32_t* b = nullptr;
     uint32_t nb = 0;
-    // ... and the block compositor's dispatch order, as one more workgroup of the slab's k_block_counts (tile_order_job):
+    // ... and the block compositor's dispatch order, as one more workgroup of the slab's k_block_bin (tile_order_job):
     // order_buf = {threshold, tile_cost[order_tiles], tile_order[order_tiles]}
     uint32_t* order_buf = nullptr;
     uint32_t order_tiles = 0;
@@ -447,7 +447,7 @@ struct ZeroJob {
 };
 // Frames of more tiles keep index order: at 3840 x 2160 (32 400 tiles: ten dispatch rounds, the tail is a smaller share of the launch) the
 // order gains little and the job's one workgroup takes ~20 us per model — cfg5 (four models) measured 6 % slower with it.
-// (tile_order_job keeps 3 words of LDS per 64 tiles: within k_block_counts' 4096)
+// (tile_order_job keeps 3 words of LDS per 64 tiles: within the 4096 of k_block_bin's block table)
 constexpr uint32_t kTileOrderMax = 16384;
 constexpr uint32_t tile_order_lds_words(uint32_t n_tiles) { return 3u * ((n_tiles + 63u) / 64u) + 32u; }
 
@@ -646,8 +646,10 @@ size_t scan_blocks(uint64_t n);
 // Block lists (progressive frames): bin by blocks of 2^bsx x 2^bsy tiles (<= 256 blocks), one 8-bit sort pass, and
 // k_composite_blocks applies the exact per-tile decision.  brec: uint4 per slab record; table: 1024 uint4; ranges: the block
 // range table (zeroed here, filled by launch_tile_ranges).
-// the same as ONE launch behind the block table (k_block_bin: counts, slots by decoupled look-back, entries, and the block sort's digit
+// ONE launch behind the block table (k_block_bin: counts, slots by decoupled look-back, entries, and the block sort's digit
 // histograms into sort_ghist = the block sort's workspace): launch_radix_sort(..., hist_done = true) follows.  bin_ws: bin_workspace_words(records) u32, zeroed once.
+// zero: words the table kernel zeroes on the way.  table_ready: table and ranges are in place already (the repair round of a speculated
+// frame: launch_spec_verify built the table and zeroed the ranges).
 size_t bin_workspace_words(uint64_t n_records);
 hipError_t launch_block_bin_fused(hipStream_t s, uint32_t j0, uint32_t j1, const uint32_t* d_n_vis, const uint32_t* sorted_idx,
                                   const Records& rec, const uint32_t* sorted_keys, uint4* brec, SlabStats* stats, uint32_t capacity,
@@ -658,13 +660,6 @@ hipError_t launch_block_bin_fused(hipStream_t s, uint32_t j0, uint32_t j1, const
                                   uint2* shade_pairs = nullptr /* slab shading: (key, index) of the slab's records some block takes -> stats->n_slab_shade; the
                                                                   rectangles are then read from rec.rect8 (the records are not shaded yet) */,
                                   const uint8_t* sorted_code = nullptr /* Records::code8 in depth order: later slabs skip records whose coarse cells hold no open tile */);
-hipError_t launch_block_bin(hipStream_t s, uint32_t j0, uint32_t j1, const uint32_t* d_n_vis, const uint32_t* sorted_idx,
-                            const Records& rec, const uint32_t* sorted_keys, uint4* brec, uint32_t* cnt, uint32_t* block_sums,
-                            SlabStats* stats, uint32_t capacity, uint32_t row_lo, uint32_t row_hi, const uint32_t* done,
-                            uint32_t row_words, const uint32_t* d_done_count, uint32_t owned_tiles, uint32_t slab_index,
-                            const uint2* window, uint32_t tiles_x, uint32_t tiles_y, uint32_t bsx, uint32_t bsy, uint4* table,
-                            uint2* pairs, uint2* ranges, const ZeroJob& zero = ZeroJob{} /* words the table kernel zeroes on the way */,
-                            bool table_ready = false /* table and ranges are in place already (launch_spec_verify built them) */);
 hipError_t launch_composite_blocks(hipStream_t s, const FrameConsts& f, const uint2* ranges, const uint32_t* list /* nullptr: brec is in list order */, const uint4* brec,
                                    const Records& rec, float4* fb, bool carry, uint32_t* done, uint32_t row_words,
                                    uint32_t* d_done_count, uint32_t* tile_sat, const uint2* window, uint32_t row_lo,

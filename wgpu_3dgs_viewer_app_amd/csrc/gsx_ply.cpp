@@ -17,7 +17,7 @@
 #include "edit_math.h"
 
 namespace gsx {
-gsx_status ply_fail(gsx_status st, const char* fmt, ...);
+gsx_status fail(gsx_status st, const char* fmt, ...);
 }
 
 namespace {
@@ -81,8 +81,8 @@ void gaussian_to_vertex(const gsx_gaussian* g, float v[62]) {
 extern "C" {
 
 gsx_status gsx_ply_read_header(const void* data, uint64_t size, gsx_ply_header* out) {
-    using gsx::ply_fail;
-    if (!data || !out) return ply_fail(GSX_ERR_INVALID_ARG, "gsx_ply_read_header: null argument");
+    using gsx::fail;
+    if (!data || !out) return fail(GSX_ERR_INVALID_ARG, "gsx_ply_read_header: null argument");
     const char* p = static_cast<const char*>(data);
     memset(out, 0, sizeof *out);
     for (int i = 0; i < 62; ++i) out->offsets[i] = -1;
@@ -98,11 +98,11 @@ gsx_status gsx_ply_read_header(const void* data, uint64_t size, gsx_ply_header* 
         return true;
     };
     std::string line;
-    if (!next_line(line) || line != "ply") return ply_fail(GSX_ERR_PLY, "not a PLY file (missing 'ply' magic)");
+    if (!next_line(line) || line != "ply") return fail(GSX_ERR_PLY, "not a PLY file (missing 'ply' magic)");
     bool have_format = false, in_vertex = false, have_vertex = false;
     uint32_t stride = 0, column = 0;
     while (true) {
-        if (!next_line(line)) return ply_fail(GSX_ERR_PLY, "PLY header is not terminated by end_header");
+        if (!next_line(line)) return fail(GSX_ERR_PLY, "PLY header is not terminated by end_header");
         if (line == "end_header") break;
         char a[64] = {0}, b[64] = {0}, c[64] = {0};
         int k = sscanf(line.c_str(), "%63s %63s %63s", a, b, c);
@@ -110,35 +110,35 @@ gsx_status gsx_ply_read_header(const void* data, uint64_t size, gsx_ply_header* 
         if (!strcmp(a, "format")) {
             if (!strcmp(b, "binary_little_endian")) out->is_ascii = 0;
             else if (!strcmp(b, "ascii")) out->is_ascii = 1;
-            else return ply_fail(GSX_ERR_PLY, "unsupported PLY format '%s'", b);
+            else return fail(GSX_ERR_PLY, "unsupported PLY format '%s'", b);
             have_format = true;
         } else if (!strcmp(a, "element")) {
             in_vertex = !strcmp(b, "vertex");
             if (in_vertex) {
-                if (have_vertex) return ply_fail(GSX_ERR_PLY, "duplicate vertex element");
+                if (have_vertex) return fail(GSX_ERR_PLY, "duplicate vertex element");
                 out->count = strtoull(c, nullptr, 10);
                 have_vertex = true;
             } else if (!have_vertex) {
-                return ply_fail(GSX_ERR_PLY, "element '%s' precedes the vertex element (unsupported)", b);
+                return fail(GSX_ERR_PLY, "element '%s' precedes the vertex element (unsupported)", b);
             }
         } else if (!strcmp(a, "property") && in_vertex) {
-            if (!strcmp(b, "list")) return ply_fail(GSX_ERR_PLY, "list property in the vertex element");
+            if (!strcmp(b, "list")) return fail(GSX_ERR_PLY, "list property in the vertex element");
             int ts = type_size(b);
-            if (ts < 0) return ply_fail(GSX_ERR_PLY, "unknown property type '%s'", b);
+            if (ts < 0) return fail(GSX_ERR_PLY, "unknown property type '%s'", b);
             for (int i = 0; i < 62; ++i)
                 if (!strcmp(c, kProps[i])) {
                     if (ts != 4 || (strcmp(b, "float") && strcmp(b, "float32")))
-                        return ply_fail(GSX_ERR_PLY, "property '%s' must be float32", c);
+                        return fail(GSX_ERR_PLY, "property '%s' must be float32", c);
                     out->offsets[i] = out->is_ascii ? (int32_t)column : (int32_t)stride;
                 }
             stride += (uint32_t)ts;
             ++column;
         }
     }
-    if (!have_format || !have_vertex) return ply_fail(GSX_ERR_PLY, "PLY header lacks format or vertex element");
+    if (!have_format || !have_vertex) return fail(GSX_ERR_PLY, "PLY header lacks format or vertex element");
     const int required[] = {0, 1, 2, 6, 7, 8, 54, 55, 56, 57, 58, 59, 60, 61};
     for (int r : required)
-        if (out->offsets[r] < 0) return ply_fail(GSX_ERR_PLY, "PLY vertex lacks property '%s'", kProps[r]);
+        if (out->offsets[r] < 0) return fail(GSX_ERR_PLY, "PLY vertex lacks property '%s'", kProps[r]);
     out->header_bytes = pos;
     out->vertex_bytes = out->is_ascii ? 0 : stride;
     if (out->is_ascii) out->vertex_bytes = column;  // columns per line for ascii
@@ -147,14 +147,14 @@ gsx_status gsx_ply_read_header(const void* data, uint64_t size, gsx_ply_header* 
 
 gsx_status gsx_ply_read_gaussians(const void* data, uint64_t size, const gsx_ply_header* h, uint64_t start, uint64_t n,
                                   gsx_gaussian* out) {
-    using gsx::ply_fail;
-    if (!data || !h || (n && !out)) return ply_fail(GSX_ERR_INVALID_ARG, "gsx_ply_read_gaussians: null argument");
-    if (start > h->count || n > h->count - start) return ply_fail(GSX_ERR_INVALID_ARG, "gsx_ply_read_gaussians: range exceeds vertex count");
+    using gsx::fail;
+    if (!data || !h || (n && !out)) return fail(GSX_ERR_INVALID_ARG, "gsx_ply_read_gaussians: null argument");
+    if (start > h->count || n > h->count - start) return fail(GSX_ERR_INVALID_ARG, "gsx_ply_read_gaussians: range exceeds vertex count");
     const char* p = static_cast<const char*>(data);
     float v[62];
     if (!h->is_ascii) {
         const uint64_t need = h->header_bytes + (start + n) * (uint64_t)h->vertex_bytes;
-        if (need > size) return ply_fail(GSX_ERR_IO, "PLY data truncated: need %llu bytes, have %llu", (unsigned long long)need, (unsigned long long)size);
+        if (need > size) return fail(GSX_ERR_IO, "PLY data truncated: need %llu bytes, have %llu", (unsigned long long)need, (unsigned long long)size);
         auto convert = [&](uint64_t i0, uint64_t i1) {
             float w[62];
             for (uint64_t i = i0; i < i1; ++i) {
@@ -192,10 +192,10 @@ gsx_status gsx_ply_read_gaussians(const void* data, uint64_t size, const gsx_ply
     for (uint64_t i = 0; i < start + n; ++i) {
         for (uint32_t c = 0; c < h->vertex_bytes; ++c) {
             while (pos < size && (p[pos] == ' ' || p[pos] == '\n' || p[pos] == '\r' || p[pos] == '\t')) ++pos;
-            if (pos >= size) return ply_fail(GSX_ERR_IO, "ascii PLY data truncated at vertex %llu", (unsigned long long)i);
+            if (pos >= size) return fail(GSX_ERR_IO, "ascii PLY data truncated at vertex %llu", (unsigned long long)i);
             char* end = nullptr;
             cols[c] = strtof(p + pos, &end);
-            if (end == p + pos) return ply_fail(GSX_ERR_PLY, "ascii PLY: bad number at vertex %llu", (unsigned long long)i);
+            if (end == p + pos) return fail(GSX_ERR_PLY, "ascii PLY: bad number at vertex %llu", (unsigned long long)i);
             pos = (uint64_t)(end - p);
         }
         if (i >= start) {
@@ -208,8 +208,8 @@ gsx_status gsx_ply_read_gaussians(const void* data, uint64_t size, const gsx_ply
 
 gsx_status gsx_ply_write(const gsx_gaussian* g, uint64_t n, const uint32_t* mask, const gsx_gaussian_edit* edits, void* out,
                          uint64_t capacity, uint64_t* out_size) {
-    using gsx::ply_fail;
-    if ((n && !g) || !out_size) return ply_fail(GSX_ERR_INVALID_ARG, "gsx_ply_write: null argument");
+    using gsx::fail;
+    if ((n && !g) || !out_size) return fail(GSX_ERR_INVALID_ARG, "gsx_ply_write: null argument");
     auto keep = [&](uint64_t i) {
         if (mask && !((mask[i >> 5] >> (i & 31)) & 1u)) return false;
         return !(edits && (edits[i].flag & GSX_EDIT_ENABLED) && (edits[i].flag & GSX_EDIT_HIDDEN));
@@ -221,7 +221,7 @@ gsx_status gsx_ply_write(const gsx_gaussian* g, uint64_t n, const uint32_t* mask
     header += "end_header\n";
     *out_size = header.size() + kept * 248ull;
     if (!out) return GSX_OK;
-    if (capacity < *out_size) return ply_fail(GSX_ERR_INVALID_ARG, "gsx_ply_write: buffer too small (%llu < %llu)", (unsigned long long)capacity, (unsigned long long)*out_size);
+    if (capacity < *out_size) return fail(GSX_ERR_INVALID_ARG, "gsx_ply_write: buffer too small (%llu < %llu)", (unsigned long long)capacity, (unsigned long long)*out_size);
     char* p = static_cast<char*>(out);
     memcpy(p, header.data(), header.size());
     p += header.size();

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "gsx_internal.h"
+#include "spec_tuner.h"
 
 namespace gsx {
 
@@ -76,13 +77,10 @@ struct DevBuf {
 
 using Counters = SlabStats;  // device copy + pinned host mirror
 
-// Per model: which of the two equivalent schedules (speculated / plain progressive) is faster here — see gsx_frame.cpp.
+// Per model: which of the two equivalent schedules (speculated / plain progressive) is faster here.  The rules are SpecTunerRules
+// (spec_tuner.h); this is their shell: the event pairs that time the bracketed frames (fed to the rules by gsx_frame.cpp).
 struct SpecTuner {
-    enum Phase { SPEC, PROBE_PLAIN, SETTLE_SPEC, PLAIN, PROBE_SPEC, SETTLE_PLAIN } phase = SPEC;
-    uint32_t left = 32;                 // frames left in the phase (the first SPEC phase is short: decide early)
-    uint32_t len_spec = 64, len_plain = 64, frame_no = 0;
-    double mean_spec = 0.0, mean_plain = 0.0;  // running means of the bracketed frames, milliseconds
-    uint32_t n_spec = 0, n_plain = 0;
+    SpecTunerRules rules;
     struct Slot {
         hipEvent_t start = nullptr, stop = nullptr;
         bool spec = false;
@@ -90,11 +88,9 @@ struct SpecTuner {
         bool probe = false;  // a frame of a probe phase: the decision waits for these
     } slots[16];
     Slot* active = nullptr;
-    uint32_t probe_pending = 0;         // probe frames whose timings have not arrived yet
     // the scene changed under the model (another mask, new Gaussians): what was measured belongs to the old scene
     void reset() {
-        phase = SPEC; left = 32; len_spec = len_plain = 64;
-        n_spec = n_plain = 0; mean_spec = mean_plain = 0.0; probe_pending = 0;
+        rules.reset();
         for (auto& s : slots) {
             if (s.state == 2) s.state = 3;
             if (s.state == 1) s.state = 0;  // bracket opened, never closed (the frame was not rendered): nothing in flight
@@ -186,6 +182,10 @@ struct Model {
     bool windows_unwanted = false;     // this frame need not leave windows for the next (SpecTuner: a plain phase)
     SpecTuner* tuner_ref = nullptr;    // a lane's shadow model: the owner's tuner decides for every lane (one phase cycle per model)
     SpecTuner tuner;                   // speculate or not? decided by timing both paths (gsx_frame.cpp)
+    SpecTuner& own_tuner() {           // this model's tuner: the owner's for a lane's shadow model
+        if (tuner_ref) return *tuner_ref;
+        return tuner;
+    }
     // host_verify = 2 (auto): ask the device for its verdict only while repairs are rare
     bool hv_active = true;             // currently asking
     uint32_t hv_history = 0;           // bit k: the k-th latest verdict needed the repair round
@@ -482,7 +482,6 @@ struct gsx_viewer {
     DevBuf tile_prof;                    // GSX_TILE_PROFILE: what every tile of the LAST block-compositor launch of a frame's first slab cost
     bool tile_profile = false;
     bool short_chain = true;             // GSX_SHORT_CHAIN=0: a speculated frame's shading is a launch of its own in front of the depth sort (A/B)
-    bool bin_fused = true;               // GSX_BIN_FUSED=0: block binning as count + scan + emit + histogram launches (A/B)
     bool bucket_sort = true;             // GSX_BUCKET_SORT=0: speculated frames, repair rounds and imported bands keep the five-launch LSD depth sort (A/B)
     bool tile_order_on = true;           // GSX_TILE_ORDER=0: the block compositor takes its tiles in index order (A/B)
     int sorted_records = -1;             // GSX_SORTED_RECORDS=0 / 1: never / always carry the block lists' records through the block sort (-1: by list length)

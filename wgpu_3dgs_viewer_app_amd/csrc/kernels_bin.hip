@@ -428,102 +428,6 @@ __device__ inline bool block_rect(const BlockGrid& g, uint32_t rx, uint32_t ry, 
     return true;
 }
 
-__global__ __launch_bounds__(kBinThreads) void k_block_counts(const uint32_t* __restrict__ d_n_vis, uint32_t j0, uint32_t j1,
-                                                               const uint32_t* __restrict__ sorted_idx,
-                                                               const float4* __restrict__ rec_a,
-                                                               const uint32_t* __restrict__ sorted_keys, uint4* __restrict__ brec,
-                                                               uint32_t* __restrict__ cnt, uint32_t* __restrict__ block_sums,
-                                                               uint32_t row_lo, uint32_t row_hi,
-                                                               const uint32_t* __restrict__ d_done_count, uint32_t owned_tiles,
-                                                               BlockGrid g, const uint4* __restrict__ table, int keyed,
-                                                               uint32_t* __restrict__ order_buf, uint32_t order_tiles, uint32_t* __restrict__ walk_max_out) {
-    __shared__ uint32_t red[4];
-    __shared__ uint4 tab[1024];
-    // the launch's one extra workgroup (the first, so that it starts at once): the block compositor's dispatch order, made while the
-    // others count (tile_order_job, gsx_internal.h — ~8 us of one workgroup's latency chain, hidden here; as a launch of its own: 11)
-    const uint32_t extra = order_buf ? 1u : 0u, workers = gridDim.x - extra, worker = blockIdx.x - extra;
-    if (extra && blockIdx.x == 0u) {
-        tile_order_job<kBinThreads>(order_buf, order_tiles, reinterpret_cast<uint32_t*>(tab), walk_max_out);
-        return;
-    }
-    const uint32_t n_vis = min(*d_n_vis, j1);
-    const uint32_t chunks = n_vis > j0 ? (n_vis - j0 + kBinThreads - 1) / kBinThreads : 0u;
-    const bool all_done = d_done_count && *d_done_count >= owned_tiles;
-    if (!all_done && worker < chunks) {
-        for (uint32_t b = threadIdx.x; b < g.blocks_x * g.blocks_y; b += kBinThreads) tab[b] = table[b];
-        __syncthreads();
-    }
-    for (uint32_t chunk = worker; chunk < chunks; chunk += workers) {
-        if (all_done) {
-            if (threadIdx.x == 0) block_sums[chunk] = 0;
-            continue;
-        }
-        const uint32_t j = j0 + chunk * kBinThreads + threadIdx.x;
-        uint32_t c = 0;
-        if (j < n_vis) {
-            const uint32_t idx = sorted_idx[j];
-            const float4 a = rec_a[idx];
-            const uint32_t rx = __float_as_uint(a.z), ry = __float_as_uint(a.w);
-            const uint32_t key = sorted_keys[j];
-            uint32_t bx0, bx1, by0, by1;
-            if (block_rect(g, rx, ry, row_lo, row_hi, bx0, bx1, by0, by1))
-                for (uint32_t by = by0; by < by1; ++by)
-                    for (uint32_t bx = bx0; bx < bx1; ++bx) c += block_takes(tab, by * g.blocks_x + bx, key, keyed != 0) ? 1u : 0u;
-            if (c)  // (only records that make an entry are ever looked up: later slabs mostly hit saturated blocks)
-                brec[j - j0] = make_uint4(rx, ry, key, idx);
-            cnt[j - j0] = c;
-        }
-        const uint32_t tot = block_reduce_sum(c, red);
-        if (threadIdx.x == 0) block_sums[chunk] = tot;
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(kBinThreads) void k_block_emit(uint32_t jbase, uint32_t j1, const uint4* __restrict__ brec,
-                                                             const uint32_t* __restrict__ cnt,
-                                                             const uint32_t* __restrict__ block_offs, uint2* __restrict__ pairs,
-                                                             uint32_t row_lo, uint32_t row_hi, const uint32_t* __restrict__ d_n_vis,
-                                                             const uint32_t* __restrict__ d_entries, uint32_t capacity,
-                                                             const uint32_t* __restrict__ d_cut, BlockGrid g,
-                                                             const uint4* __restrict__ table, int keyed) {
-    __shared__ uint32_t wsum[4];
-    __shared__ uint4 tab[1024];
-    if (*d_entries == 0) return;
-    const uint32_t n_vis = min(min(j1, *d_n_vis), *d_cut);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t chunks = n_vis > jbase ? (n_vis - jbase + kBinThreads - 1) / kBinThreads : 0u;
-    if (blockIdx.x < chunks)
-        for (uint32_t b = tid; b < g.blocks_x * g.blocks_y; b += kBinThreads) tab[b] = table[b];
-    __syncthreads();
-    for (uint32_t chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
-        const uint32_t j = jbase + chunk * kBinThreads + tid;
-        const uint32_t mine = j < n_vis ? cnt[j - jbase] : 0u;
-        uint32_t x = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(x, o, 64);
-            if (lane >= (uint32_t)o) x += y;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        uint32_t o = block_offs[chunk] + x - mine;
-        for (uint32_t w = 0; w < wave; ++w) o += wsum[w];
-        if (mine) {
-            const uint4 r = brec[j - jbase];
-            uint32_t bx0, bx1, by0, by1;
-            if (block_rect(g, r.x, r.y, row_lo, row_hi, bx0, bx1, by0, by1))
-                for (uint32_t by = by0; by < by1; ++by)
-                    for (uint32_t bx = bx0; bx < bx1; ++bx) {
-                        const uint32_t b = by * g.blocks_x + bx;
-                        if (!block_takes(tab, b, r.z, keyed != 0)) continue;
-                        if (o < capacity) pairs[o] = make_uint2(b, j - jbase);
-                        ++o;
-                    }
-        }
-        __syncthreads();
-    }
-}
-
 // ---- k_block_counts + k_scan_block_sums + k_block_emit + the block sort's histogram as ONE launch (round 6) ----
 // Persistent 1024-lane workgroups take 2048-record tiles of the slab in ticket order.  A tile: every lane gathers two records
 // (both loads in flight), counts the blocks each touches, the tile's total is published as one 64-bit {epoch, flag, count} word and
@@ -857,29 +761,6 @@ hipError_t launch_block_bin_fused(hipStream_t s, uint32_t j0, uint32_t j1, const
                    stats, capacity, row_lo, row_hi, d_done_count, owned_tiles, slab_index, g, table, window ? 1 : 0, zero.order_buf, zero.order_tiles,
                    zero.order_buf ? &stats->walk_max : nullptr, bin_ws, reinterpret_cast<u64b*>(bin_ws + 8), next_sort_epoch(), sort_ghist, passes, dbits,
                    shade_pairs ? rec.rect8 : nullptr, shade_pairs, live ? sorted_code : nullptr, live, g_big_slab.load(), kBigRect);
-    return hipGetLastError();
-}
-
-hipError_t launch_block_bin(hipStream_t s, uint32_t j0, uint32_t j1, const uint32_t* d_n_vis, const uint32_t* sorted_idx,
-                            const Records& rec, const uint32_t* sorted_keys, uint4* brec, uint32_t* cnt, uint32_t* block_sums,
-                            SlabStats* stats, uint32_t capacity, uint32_t row_lo, uint32_t row_hi, const uint32_t* done,
-                            uint32_t row_words, const uint32_t* d_done_count, uint32_t owned_tiles, uint32_t slab_index,
-                            const uint2* window, uint32_t tiles_x, uint32_t tiles_y, uint32_t bsx, uint32_t bsy, uint4* table,
-                            uint2* pairs, uint2* ranges, const ZeroJob& zero, bool table_ready) {
-    const uint32_t nb = std::min<uint32_t>((uint32_t)scan_blocks(j1 > j0 ? j1 - j0 : 0), kBinGrid);
-    const BlockGrid g = block_grid(bsx, bsy, tiles_x, row_lo, row_hi);
-    if (!table_ready)  // (the repair round of a speculated frame: k_spec_verify_fused has built the table and zeroed the ranges)
-        GSX_LAUNCH(k_block_table, dim3((g.blocks_x * g.blocks_y + 3u) / 4u), dim3(256), 0, s, g, tiles_x, tiles_y, row_lo, row_hi, done,
-                   row_words, window, table, ranges, zero.a, zero.na, zero.b, zero.nb, (uint32_t*)nullptr, zero.copy_src, zero.copy_dst, zero.n_copy);
-    if (nb)
-        GSX_LAUNCH(k_block_counts, dim3(nb + (zero.order_buf ? 1u : 0u)), dim3(kBinThreads), 0, s, d_n_vis, j0, j1, sorted_idx, rec.a, sorted_keys,
-                   brec, cnt, block_sums, row_lo, row_hi, d_done_count, owned_tiles, g, table, window ? 1 : 0, zero.order_buf, zero.order_tiles,
-                   zero.order_buf ? &stats->walk_max : nullptr);
-    GSX_LAUNCH(k_scan_block_sums, dim3(1), dim3(1024), 0, s, block_sums, j0, j1, d_n_vis, stats, capacity, d_done_count,
-                       owned_tiles, slab_index);
-    if (nb)
-        GSX_LAUNCH(k_block_emit, dim3(nb), dim3(kBinThreads), 0, s, j0, j1, brec, cnt, block_sums, pairs, row_lo, row_hi,
-                           d_n_vis, &stats->n_entries, capacity, &stats->slab_cut, g, table, window ? 1 : 0);
     return hipGetLastError();
 }
 
