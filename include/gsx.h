@@ -397,6 +397,58 @@ gsx_status gsx_query_hit_pos_by_alpha_range(const gsx_query_hit* hits, uint64_t 
                                             uint32_t width, uint32_t height, const float coords[2], float range,
                                             uint32_t* out_index, float* out_alpha, float out_pos[3]);
 
+/* ---- the query toolset: gs::QueryToolset, gs::QueryTextureOverlay and gs::QueryCursor (src/tab/scene.rs:740, 766-791, 2003-2014,
+ *      2317-2325), in the library.  While the pointer is dragged the app calls query_toolset.update_pos + query_toolset.render(queue,
+ *      &mut encoder, &query_texture) every frame and shows the texture over the splats; end() turns the painted texture into ONE texture
+ *      query.  One toolset per viewer; the rule it paints by is spec/RENDER_SPEC.md §7, "Toolset".
+ *  - State (host only, no device call): use_texture (default 1; 0 = immediate mode: nothing is painted, every frame's query is the live
+ *    Rect / Brush segment), brush_radius (default 40), the active tool with its selection op, start, previous and current position.
+ *    gsx_toolset_start clears the texture and paints the first shape (Rect: the rectangle start..pos, replaced by every repaint; Brush: a
+ *    disc, then one capsule prev -> pos per gsx_toolset_update_pos, of the radius in force at that call, accumulating until the next
+ *    start).  gsx_toolset_update_pos without an active tool only records the position, for the cursor.  gsx_toolset_query is
+ *    query_toolset.query(), once per frame, and the caller passes what it returns to gsx_update_query: None while a texture stroke is
+ *    drawn, the one Texture query after gsx_toolset_end, then None again; in immediate mode the live query, None after gsx_toolset_end.
+ *  - gsx_toolset_start and gsx_toolset_update_pos QUEUE their paints (up to 64 brush segments; a full queue is enqueued at once by the
+ *    call that filled it — nothing is dropped).  gsx_toolset_render enqueues everything queued as ONE kernel launch over the tiles the
+ *    pending shapes touch, on the viewer's stream, and returns: no host copy, no host wait, and — unlike gsx_update_query_texture — no
+ *    wait for the frames in flight on the lanes.
+ *  - Ordering is stream order on the viewer's stream.  Frames on lanes never read the texture (their query is None: a frame with a query
+ *    runs on the viewer itself, see gsx_render_options); the texture-query frame and the RGBA8 resolve run on the viewer's stream, after
+ *    every paint enqueued before them — the resolve that draws the stroke also when the frame it resolves was rendered by a lane
+ *    (gsx_download_rgba8 then runs it on the viewer's stream, behind that lane's frame).  A paint enqueued while a texture-query frame is
+ *    in flight comes after that frame's read.
+ *  - Size: the texture follows the viewport.  gsx_toolset_render (or a full queue) allocates and zero-fills it when gsx_update_camera has
+ *    changed the size since the texture was made — what was painted is gone, as after viewer.update_query_texture_size (scene.rs:740) —
+ *    and from then on a texture query finds a viewport-sized texture.  A texture painted for another viewport and not rendered again is
+ *    refused by gsx_preprocess like any wrongly sized one.  gsx_update_query_texture still replaces the contents with the caller's.
+ *    (A viewer whose camera was never set has the default 1 x 1 viewport: a render there makes a one-texel texture — harmless, and
+ *    replaced by the first render after gsx_update_camera.)
+ *  - Drawn by gsx_download_rgba8 and gsx_resolve_rgba8_device, on top of splats over overlay lines over background (gsx_download_framebuffer
+ *    keeps returning the splats' (rgb, T)): while a texture stroke is drawn — from gsx_toolset_start to the gsx_toolset_query that hands
+ *    out the Texture query — every pixel whose texel is non-zero is blended with texture_rgba (straight alpha: rgb' = rgb (1 - a) + c a,
+ *    alpha' = alpha (1 - a) + a, applied to the resolved colour before the 8-bit rounding).  Until the first gsx_toolset_render after
+ *    gsx_toolset_start the texture still holds what was there before — the stroke before, a host upload — and a resolve in between draws
+ *    nothing of it.  While no texture stroke is drawn, once a position has been reported,
+ *    the cursor with cursor_rgba: a ring of radius brush_radius at the position (pixel centres at distance d, |d - brush_radius| <=
+ *    cursor_thickness / 2) or, during an immediate-mode Rect stroke, the outline of the rectangle start..pos (pixel centres within
+ *    cursor_thickness / 2 of its boundary, Chebyshev, inside or outside).  One or the other, never both.  Both colours default to alpha 0
+ *    and neither exists until its alpha is > 0: the same launches, the same bits. */
+typedef enum gsx_toolset_tool { GSX_TOOL_RECT = 0, GSX_TOOL_BRUSH = 1 } gsx_toolset_tool;
+gsx_status gsx_toolset_set_use_texture(gsx_viewer* v, uint32_t on);
+gsx_status gsx_toolset_update_brush_radius(gsx_viewer* v, float radius); /* > 0, finite */
+gsx_status gsx_toolset_start(gsx_viewer* v, uint32_t tool, uint32_t selection_op, const float pos[2]);
+gsx_status gsx_toolset_update_pos(gsx_viewer* v, const float pos[2]);
+gsx_status gsx_toolset_end(gsx_viewer* v);
+gsx_status gsx_toolset_query(gsx_viewer* v, gsx_query* out);
+/* active: 0 no tool (the other outputs are not written), 1 a stroke is under way; any output may be NULL */
+gsx_status gsx_toolset_state(gsx_viewer* v, uint32_t* active, uint32_t* tool, uint32_t* selection_op, float start[2], float pos[2]);
+/* query_toolset.render(queue, &mut encoder, &query_texture), scene.rs:791 */
+gsx_status gsx_toolset_render(gsx_viewer* v);
+/* straight-alpha colours in [0, 1] of the stroke overlay and of the cursor, the cursor's line thickness in pixels (>= 0) */
+gsx_status gsx_toolset_set_overlay(gsx_viewer* v, const float texture_rgba[4], const float cursor_rgba[4], float cursor_thickness);
+/* the query texture as the device holds it (width x height bytes = its size, the viewport's once rendered). Synchronises. */
+gsx_status gsx_download_query_texture(gsx_viewer* v, uint8_t* texels, uint32_t width, uint32_t height);
+
 /* ---- ref-counted buffer handles for readback off the owner's thread.  gs:: buffers are cheaply `Clone`: the export path clones
  *      every model's edit and mask buffer, moves the clones into two spawned threads and downloads there while the UI thread
  *      keeps rendering (app.rs:769-816, scene.rs:635-648).  gsx_model_buffer_retain (owner thread; enqueues a device-side

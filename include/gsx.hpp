@@ -266,6 +266,16 @@ public:
         h.resize((size_t)n);
         return h;
     }
+    // QueryTextureOverlay / QueryCursor (scene.rs:2003-2014, 2317-2325): the colours the RGBA8 resolve draws the stroke and the cursor
+    // with (straight alpha; alpha 0, the default, draws nothing); the query texture as the device holds it
+    void set_toolset_overlay(std::array<float, 4> texture_rgba, std::array<float, 4> cursor_rgba, float cursor_thickness) {
+        check(gsx_toolset_set_overlay(v_, texture_rgba.data(), cursor_rgba.data(), cursor_thickness));
+    }
+    std::vector<uint8_t> download_query_texture() {
+        std::vector<uint8_t> t((size_t)size.x * size.y);
+        check(gsx_download_query_texture(v_, t.data(), size.x, size.y));
+        return t;
+    }
     void poll() { check(gsx_sync(v_)); }  // device.poll(Maintain::Wait)
     std::vector<float> download_framebuffer() {
         std::vector<float> fb((size_t)size.x * size.y * 4);
@@ -277,6 +287,38 @@ public:
         check(gsx_model_frame_stats(v_, key.c_str(), &st));
         return st;
     }
+};
+
+enum class QueryToolsetTool : uint32_t { Rect = GSX_TOOL_RECT, Brush = GSX_TOOL_BRUSH };  // gs::QueryToolsetTool, scene.rs:1258-1264
+
+// gs::QueryToolset (scene.rs:766-791) of a viewer, inside the library: start / update_pos queue what they paint, render() enqueues it on
+// the viewer's stream as one launch — the query texture never crosses the host (gsx.h, the toolset block).  The viewer must outlive it.
+class QueryToolset {
+    gsx_viewer* v_;
+public:
+    struct State { QueryToolsetTool tool; gsx_selection_op op; std::array<float, 2> start, pos; };
+    explicit QueryToolset(MultiModelViewer& viewer) : v_(viewer.raw()) {}
+    void set_use_texture(bool on) { check(gsx_toolset_set_use_texture(v_, on ? 1u : 0u)); }
+    void update_brush_radius(float r) { check(gsx_toolset_update_brush_radius(v_, r)); }
+    void start(QueryToolsetTool tool, gsx_selection_op op, std::array<float, 2> pos) { check(gsx_toolset_start(v_, (uint32_t)tool, (uint32_t)op, pos.data())); }
+    void update_pos(std::array<float, 2> pos) { check(gsx_toolset_update_pos(v_, pos.data())); }
+    void end() { check(gsx_toolset_end(v_)); }
+    gsx_query query() {  // query_toolset.query(): hand it to MultiModelViewer::update_query
+        gsx_query q{};
+        check(gsx_toolset_query(v_, &q));
+        return q;
+    }
+    bool state(State* out) {  // query_toolset.state(): false = no tool in use
+        uint32_t active = 0, tool = 0, op = 0;
+        State s{};
+        check(gsx_toolset_state(v_, &active, &tool, &op, s.start.data(), s.pos.data()));
+        if (!active) return false;
+        s.tool = (QueryToolsetTool)tool;
+        s.op = (gsx_selection_op)op;
+        if (out) *out = s;
+        return true;
+    }
+    void render() { check(gsx_toolset_render(v_)); }  // query_toolset.render(queue, &mut encoder, &query_texture), scene.rs:791
 };
 
 }  // namespace gs

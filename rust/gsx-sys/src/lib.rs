@@ -124,6 +124,9 @@ pub enum gsx_buffer_kind { Mask = 0, Edits = 1, Selection = 2 }
 #[repr(i32)]
 #[derive(Clone, Copy, PartialEq, Eq)]
 pub enum gsx_depth_compare { Always = 0, Less = 1 } // the compare of new_with's depth_stencil, src/tab/scene.rs:1969-1980
+#[repr(u32)]
+#[derive(Clone, Copy, PartialEq, Eq)]
+pub enum gsx_toolset_tool { Rect = 0, Brush = 1 } // gs::QueryToolsetTool, src/tab/scene.rs:1258-1264 (the functions take it as u32)
 /// the app's measurement `HitPair` (src/renderer/measurement.rs:177-184), 32 bytes: world-space ends, RGBA8 colour, width
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -207,6 +210,16 @@ extern "C" {
     pub fn gsx_query_download_hits(v: *mut gsx_viewer, key: *const c_char, out: *mut gsx_query_hit, capacity: u64, out_n: *mut u64) -> gsx_status;
     pub fn gsx_query_hit_pos_by_closest(hits: *const gsx_query_hit, n: u64, view: *const f32, proj: *const f32, width: u32, height: u32, coords: *const f32, out_index: *mut u32, out_pos: *mut f32) -> gsx_status;
     pub fn gsx_query_hit_pos_by_alpha_range(hits: *const gsx_query_hit, n: u64, view: *const f32, proj: *const f32, width: u32, height: u32, coords: *const f32, range: f32, out_index: *mut u32, out_alpha: *mut f32, out_pos: *mut f32) -> gsx_status;
+    pub fn gsx_toolset_set_use_texture(v: *mut gsx_viewer, on: u32) -> gsx_status;
+    pub fn gsx_toolset_update_brush_radius(v: *mut gsx_viewer, radius: f32) -> gsx_status;
+    pub fn gsx_toolset_start(v: *mut gsx_viewer, tool: u32, selection_op: u32, pos: *const f32) -> gsx_status;
+    pub fn gsx_toolset_update_pos(v: *mut gsx_viewer, pos: *const f32) -> gsx_status;
+    pub fn gsx_toolset_end(v: *mut gsx_viewer) -> gsx_status;
+    pub fn gsx_toolset_query(v: *mut gsx_viewer, out: *mut gsx_query) -> gsx_status;
+    pub fn gsx_toolset_state(v: *mut gsx_viewer, active: *mut u32, tool: *mut u32, selection_op: *mut u32, start: *mut f32, pos: *mut f32) -> gsx_status;
+    pub fn gsx_toolset_render(v: *mut gsx_viewer) -> gsx_status;
+    pub fn gsx_toolset_set_overlay(v: *mut gsx_viewer, texture_rgba: *const f32, cursor_rgba: *const f32, cursor_thickness: f32) -> gsx_status;
+    pub fn gsx_download_query_texture(v: *mut gsx_viewer, texels: *mut u8, width: u32, height: u32) -> gsx_status;
     pub fn gsx_model_buffer_retain(v: *mut gsx_viewer, key: *const c_char, kind: gsx_buffer_kind, out: *mut *mut gsx_buffer) -> gsx_status;
     pub fn gsx_buffer_retain(b: *mut gsx_buffer) -> gsx_status;
     pub fn gsx_buffer_release(b: *mut gsx_buffer);

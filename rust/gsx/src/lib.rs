@@ -315,6 +315,55 @@ impl<G: GaussianPod> MultiModelViewer<G> {
     }
     pub fn comm_init_group(&mut self, group: *mut sys::gsx_comm_group, rank: u32) -> Result<(), Error> { check(unsafe { sys::gsx_viewer_comm_init_group(self.handle.0, group, rank) }) }
 }
+/// `gs::QueryToolsetTool` (scene.rs:1258-1264)
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum QueryToolsetTool { Rect = 0, Brush = 1 }
+
+/// `gs::QueryToolset` (scene.rs:766-791) of a viewer, inside the library: `start` / `update_pos` queue what they paint and `render`
+/// enqueues it on the viewer's stream as one launch — the query texture never crosses the host (include/gsx.h, the toolset block).
+/// Borrowed from the viewer: `viewer.query_toolset()`.
+pub struct QueryToolset<'a> { v: *mut sys::gsx_viewer, _viewer: PhantomData<&'a mut ()> }
+impl<'a> QueryToolset<'a> {
+    pub fn set_use_texture(&mut self, on: bool) { check(unsafe { sys::gsx_toolset_set_use_texture(self.v, on as u32) }).expect("set_use_texture") }
+    pub fn update_brush_radius(&mut self, radius: f32) -> Result<(), Error> { check(unsafe { sys::gsx_toolset_update_brush_radius(self.v, radius) }) }
+    pub fn start(&mut self, tool: QueryToolsetTool, op: u32, pos: [f32; 2]) -> Result<(), Error> { check(unsafe { sys::gsx_toolset_start(self.v, tool as u32, op, pos.as_ptr()) }) }
+    pub fn update_pos(&mut self, pos: [f32; 2]) -> Result<(), Error> { check(unsafe { sys::gsx_toolset_update_pos(self.v, pos.as_ptr()) }) }
+    pub fn end(&mut self) { check(unsafe { sys::gsx_toolset_end(self.v) }).expect("end") }
+    /// `query_toolset.query()`: this frame's query, for `viewer.update_query`
+    pub fn query(&mut self) -> sys::gsx_query {
+        let mut q = sys::gsx_query { kind: 0, selection_op: 0, p0: [0.0; 2], p1: [0.0; 2], radius: 0.0, reserved: 0 };
+        check(unsafe { sys::gsx_toolset_query(self.v, &mut q) }).expect("query");
+        q
+    }
+    /// `query_toolset.state()`: `Some((tool, op, start, pos))` while a stroke is under way
+    pub fn state(&self) -> Option<(QueryToolsetTool, u32, [f32; 2], [f32; 2])> {
+        let (mut active, mut tool, mut op, mut start, mut pos) = (0u32, 0u32, 0u32, [0f32; 2], [0f32; 2]);
+        check(unsafe { sys::gsx_toolset_state(self.v, &mut active, &mut tool, &mut op, start.as_mut_ptr(), pos.as_mut_ptr()) }).expect("state");
+        if active == 0 { return None; }
+        let tool = match tool {
+            0 => QueryToolsetTool::Rect,
+            1 => QueryToolsetTool::Brush,
+            t => unreachable!("gsx_toolset_state: tool {t} (gsx_toolset_start takes GSX_TOOL_RECT and GSX_TOOL_BRUSH only)"),
+        };
+        Some((tool, op, start, pos))
+    }
+    /// `query_toolset.render(&queue, &mut encoder, &query_texture)` (scene.rs:791)
+    pub fn render(&mut self) -> Result<(), Error> { check(unsafe { sys::gsx_toolset_render(self.v) }) }
+}
+impl<G: GaussianPod> MultiModelViewer<G> {
+    pub fn query_toolset(&mut self) -> QueryToolset<'_> { QueryToolset { v: self.handle.0, _viewer: PhantomData } }
+    /// `QueryTextureOverlay` / `QueryCursor` (scene.rs:2003-2014, 2317-2325): the straight-alpha colours `download_rgba8` draws the stroke
+    /// and the cursor with; alpha 0 (the default) draws nothing
+    pub fn set_toolset_overlay(&mut self, texture_rgba: [f32; 4], cursor_rgba: [f32; 4], cursor_thickness: f32) -> Result<(), Error> {
+        check(unsafe { sys::gsx_toolset_set_overlay(self.handle.0, texture_rgba.as_ptr(), cursor_rgba.as_ptr(), cursor_thickness) })
+    }
+    /// the query texture as the device holds it (the viewport's size once the toolset has rendered)
+    pub fn download_query_texture(&self, width: u32, height: u32) -> Result<Vec<u8>, Error> {
+        let mut t = vec![0u8; width as usize * height as usize];
+        check(unsafe { sys::gsx_download_query_texture(self.handle.0, t.as_mut_ptr(), width, height) })?;
+        Ok(t)
+    }
+}
 pub fn comm_unique_id() -> Result<[u8; 128], Error> {
     let mut id = [0u8; 128];
     check(unsafe { sys::gsx_comm_unique_id(id.as_mut_ptr()) })?;

@@ -121,6 +121,33 @@ int main(int argc, char** argv) {
             printf("frame_driver clones=%s\n", ok ? "ok" : "MISMATCH");
             if (!ok) return 6;
         }
+        // the app's default selection drag (texture mode, app.rs:1454; scene.rs:766-791) through gs::QueryToolset: the stroke is painted
+        // on the device, the one texture query after end() selects what lies under it
+        {
+            gs::QueryToolset toolset(viewer);
+            toolset.update_brush_radius(14.5f);
+            toolset.start(gs::QueryToolsetTool::Brush, GSX_SELECTION_SET, {70.25f, 50.5f});
+            const float path[3][2] = {{120.0f, 90.25f}, {200.5f, 110.0f}, {260.0f, 150.75f}};
+            for (auto& p : path) {
+                toolset.update_pos({p[0], p[1]});
+                toolset.render();
+                viewer.update_query(toolset.query());  // None while the stroke is drawn
+            }
+            toolset.end();
+            viewer.update_query(toolset.query());      // the texture query
+            for (auto& m : models) {
+                viewer.preprocessor.preprocess(m.key);
+                viewer.radix_sorter.sort(m.key);
+            }
+            viewer.renderer.render(keys);
+            for (auto& m : models) viewer.postprocessor.postprocess(m.key);
+            viewer.update_query(toolset.query());      // None again
+            size_t texels = 0, drag_selected = 0;
+            for (uint8_t t : viewer.download_query_texture()) texels += t != 0;
+            for (auto& m : models)
+                for (uint32_t word : viewer.models.at(m.key).gaussian_buffers.selection_buffer.download(m.g->size())) drag_selected += (size_t)__builtin_popcount(word);
+            printf("frame_driver drag texels=%zu selected=%zu active=%d\n", texels, drag_selected, toolset.state(nullptr) ? 1 : 0);
+        }
         // error convention: a missing model is a gs::Error, not a crash
         try { viewer.preprocessor.preprocess("missing"); return 2; } catch (const gs::Error& e) { if (e.status != GSX_ERR_NOT_FOUND) return 3; }
         if (gs::GaussianShDegree::new_(4)) return 4;

@@ -173,6 +173,9 @@ pub enum gsx_buffer_kind { Mask = 0, Edits = 1, Selection = 2 }
 #[repr(i32)]
 #[derive(Clone, Copy, PartialEq, Eq)]
 pub enum gsx_depth_compare { Always = 0, Less = 1 } // the compare of new_with's depth_stencil, src/tab/scene.rs:1969-1980
+#[repr(u32)]
+#[derive(Clone, Copy, PartialEq, Eq)]
+pub enum gsx_toolset_tool { Rect = 0, Brush = 1 } // gs::QueryToolsetTool, src/tab/scene.rs:1258-1264 (the functions take it as u32)
 /// the app's measurement `HitPair` (src/renderer/measurement.rs:177-184), 32 bytes: world-space ends, RGBA8 colour, width
 #[repr(C)]
 #[derive(Clone, Copy)]

@@ -41,6 +41,8 @@ EXPORTS = (
     "gsx_update_selection_edit", "gsx_model_show_unedited", "gsx_postprocess", "gsx_model_upload_selection",
     "gsx_model_download_selection", "gsx_model_download_edits", "gsx_model_upload_edits", "gsx_query_download_hits",
     "gsx_query_hit_pos_by_closest", "gsx_query_hit_pos_by_alpha_range",
+    "gsx_toolset_set_use_texture", "gsx_toolset_update_brush_radius", "gsx_toolset_start", "gsx_toolset_update_pos", "gsx_toolset_end",
+    "gsx_toolset_query", "gsx_toolset_state", "gsx_toolset_render", "gsx_toolset_set_overlay", "gsx_download_query_texture",
     "gsx_debug_set_launch_graphs", "gsx_debug_launch_count", "gsx_debug_device_bytes", "gsx_debug_download_lane_framebuffer", "gsx_viewer_launch_stats", "gsx_debug_tile_profile",
     "gsx_viewer_comm_init_custom_v", "gsx_shard_set_band_edges", "gsx_shard_get_band_edges", "gsx_shard_set_balance",
     "gsx_viewer_comm_info",
@@ -141,6 +143,9 @@ class GsxError(RuntimeError):
 
 
 _lib = None
+#: names load() lets a library lack.  Empty: a library exports every declared name.  tools/bench_drag.py names the toolset's calls here,
+#: before the first load(), when it runs its host rows on a build from before the toolset (GSX_LIB); nothing else may.
+MAY_LACK: frozenset = frozenset()
 
 
 def load() -> C.CDLL:
@@ -189,6 +194,16 @@ def load() -> C.CDLL:
         "gsx_query_download_hits": ([vp, cp, vp, u64, C.POINTER(u64)], C.c_int32),
         "gsx_query_hit_pos_by_closest": ([vp, u64, f32p, f32p, u32, u32, f32p, u32p, f32p], C.c_int32),
         "gsx_query_hit_pos_by_alpha_range": ([vp, u64, f32p, f32p, u32, u32, f32p, C.c_float, u32p, f32p, f32p], C.c_int32),
+        "gsx_toolset_set_use_texture": ([vp, u32], C.c_int32),
+        "gsx_toolset_update_brush_radius": ([vp, C.c_float], C.c_int32),
+        "gsx_toolset_start": ([vp, u32, u32, f32p], C.c_int32),
+        "gsx_toolset_update_pos": ([vp, f32p], C.c_int32),
+        "gsx_toolset_end": ([vp], C.c_int32),
+        "gsx_toolset_query": ([vp, C.POINTER(Query)], C.c_int32),
+        "gsx_toolset_state": ([vp, u32p, u32p, u32p, f32p, f32p], C.c_int32),
+        "gsx_toolset_render": ([vp], C.c_int32),
+        "gsx_toolset_set_overlay": ([vp, f32p, f32p, C.c_float], C.c_int32),
+        "gsx_download_query_texture": ([vp, vp, u32, u32], C.c_int32),
         "gsx_preprocess": ([vp, cp], C.c_int32),
         "gsx_sort": ([vp, cp], C.c_int32),
         "gsx_sync": ([vp], C.c_int32),
@@ -268,6 +283,8 @@ def load() -> C.CDLL:
     }
     assert set(sig) == set(EXPORTS)
     for name, (args, res) in sig.items():
+        if name in MAY_LACK and not hasattr(L, name):
+            continue
         fn = getattr(L, name)  # AttributeError here = the library does not export what gsx.h declares
         fn.argtypes = args
         fn.restype = res

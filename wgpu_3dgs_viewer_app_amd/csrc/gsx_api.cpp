@@ -751,13 +751,23 @@ gsx_status gsx_debug_download_lane_framebuffer(gsx_viewer* v, uint32_t lane, flo
 gsx_status gsx_download_rgba8(gsx_viewer* v, const float bg[3], uint8_t* rgba, uint64_t n_bytes) {
     gsx_status st = viewer_bind(v);
     if (st) return st;
+    const gsx_viewer* owner = v;
     v = result_lane(v);  // the newest frame may be a lane's
     const uint64_t npx = (uint64_t)v->width * v->height;
     if (!bg || !rgba || n_bytes != 4 * npx) return fail(GSX_ERR_INVALID_ARG, "gsx_download_rgba8: expected %llu bytes", (unsigned long long)(4 * npx));
     if ((st = ensure_fb(v))) return st;
     if ((st = finish_frame(v))) return st;
     HIPCHK(v->scratch.ensure(4 * npx));
-    if (overlay_resolves(v))
+    ToolsetDraw draw;
+    if (toolset_draws(owner, v, &draw)) {  // the stroke overlay or the cursor on top (a viewer that never set their colours: never)
+        // On the OWNER's stream, whichever lane rendered the frame: the query texture is painted (and cleared) there, and a lane's stream
+        // is ordered after it only at that lane's next frame.  viewer_bind above has put the owner's stream behind the lane's frame
+        // (and finish_frame has waited for whatever it enqueued on the lane itself).
+        const bool lines = overlay_resolves(v);
+        HIPCHK(launch_resolve_rgba8_toolset(owner->stream, fb_ptr(v), 0u, (uint32_t)npx, v->width, bg[0], bg[1], bg[2], lines ? v->overlay_rgba.as<float4>() : nullptr,
+                                            lines ? v->overlay_flags.as<uint32_t>() : nullptr, owner->query_texture.as<uint8_t>(), draw, v->scratch.as<uint32_t>()));
+        HIPCHK(gsx::op::StreamSynchronize(owner->stream));
+    } else if (overlay_resolves(v))
         HIPCHK(launch_resolve_rgba8_overlay(v->stream, fb_ptr(v), 0u, (uint32_t)npx, v->width, bg[0], bg[1], bg[2], v->overlay_rgba.as<float4>(),
                                             v->overlay_flags.as<uint32_t>(), v->scratch.as<uint32_t>()));
     else

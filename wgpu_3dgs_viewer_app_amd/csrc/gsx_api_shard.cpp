@@ -113,7 +113,13 @@ gsx_status gsx_resolve_rgba8_device(gsx_viewer* v, const float bg[3], uint32_t y
     const uint64_t rows_avail = src->ext_fb ? src->ext_fb_bytes / (sizeof(float4) * (uint64_t)src->width) : src->height;
     if (y1 > rows_avail) return fail(GSX_ERR_INVALID_ARG, "gsx_resolve_rgba8_device: rows [%u, %u) of a %llu-row framebuffer", y0, y1, (unsigned long long)rows_avail);
     const uint64_t npx = (uint64_t)(y1 - y0) * src->width;
-    if (overlay_resolves(src))  // (a frame with lines ran on the viewer itself: src == v)
+    ToolsetDraw draw;
+    if (toolset_draws(v, src, &draw)) {  // the stroke overlay or the cursor on top (the query texture is painted on this stream)
+        const bool lines = overlay_resolves(src);
+        HIPCHK(launch_resolve_rgba8_toolset(v->stream, fb_ptr(src), y0 * src->width, (uint32_t)npx, src->width, bg[0], bg[1], bg[2],
+                                            lines ? src->overlay_rgba.as<float4>() : nullptr, lines ? src->overlay_flags.as<uint32_t>() : nullptr,
+                                            v->query_texture.as<uint8_t>(), draw, static_cast<uint32_t*>(d_rgba)));
+    } else if (overlay_resolves(src))  // (a frame with lines ran on the viewer itself: src == v)
         HIPCHK(launch_resolve_rgba8_overlay(v->stream, fb_ptr(src), y0 * src->width, (uint32_t)npx, src->width, bg[0], bg[1], bg[2],
                                             src->overlay_rgba.as<float4>(), src->overlay_flags.as<uint32_t>(), static_cast<uint32_t*>(d_rgba)));
     else

@@ -6,6 +6,7 @@
 
 #include "../../include/gsx.h"
 #include "gsx_launch.h"
+#include "toolset_math.h"
 
 namespace gsx {
 
@@ -769,6 +770,21 @@ hipError_t launch_overlay(hipStream_t s, const gsx_overlay_line* lines, uint32_t
 // the RGBA8 resolve over an overlay: out.rgb = rgb + T (C + (1 - A) background), alpha = 1 - T (1 - A); pixels [first, first + n_px)
 hipError_t launch_resolve_rgba8_overlay(hipStream_t s, const float4* fb, uint32_t first, uint32_t n_px, uint32_t w, float bg_r, float bg_g,
                                         float bg_b, const float4* overlay_rgba, const uint32_t* tile_flags, uint32_t* out_rgba8);
+// Query toolset (kernels_toolset.hip; spec section 7, "Toolset").  The paint: every pending shape by value (toolset_math.h), over the tiles
+// of `cover` only; tex: w x h bytes, rows tightly packed.
+hipError_t launch_toolset_paint(hipStream_t s, const ToolsetPaint& p, const ToolsetBox& cover, uint32_t w, uint32_t h, uint8_t* tex);
+// What the RGBA8 resolve draws on top of the frame: the stroke overlay (every pixel whose texel is non-zero), the cursor ring at (x0, y0),
+// or the outline of the rectangle (x0, y0) .. (x1, y1), corners sorted; rgba: the straight-alpha colour it is blended with.
+enum : uint32_t { kToolsetDrawStroke = 1, kToolsetDrawRing = 2, kToolsetDrawRectOutline = 3 };
+struct ToolsetDraw {
+    uint32_t mode, tex_h;
+    float rgba[4];
+    float x0, y0, x1, y1, radius, half_thickness;
+};
+// the resolve of launch_resolve_rgba8 (overlay_rgba == nullptr) / launch_resolve_rgba8_overlay, with `d` blended on top before the rounding
+hipError_t launch_resolve_rgba8_toolset(hipStream_t s, const float4* fb, uint32_t first, uint32_t n_px, uint32_t w, float bg_r, float bg_g,
+                                        float bg_b, const float4* overlay_rgba, const uint32_t* tile_flags, const uint8_t* tex,
+                                        const ToolsetDraw& d, uint32_t* out_rgba8);
 // out[t] = {spec[t].x, min(spec[t].y, bound[t].y)} and, in the same launch, the max-pyramid (data) and the min-pyramid (min_ends) of `out`
 // as launch_window_pyramid builds them (kernels_spec.hip)
 hipError_t launch_depth_cap_pyramid(hipStream_t s, const uint2* spec, const uint2* bound, uint2* out, uint32_t tiles_x, uint32_t tiles_y,

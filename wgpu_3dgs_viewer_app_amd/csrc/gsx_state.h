@@ -15,6 +15,7 @@
 
 #include "gsx_internal.h"
 #include "spec_tuner.h"
+#include "toolset_state.h"
 
 namespace gsx {
 
@@ -412,6 +413,9 @@ struct gsx_viewer {
     gsx_query query{};                   // GSX_QUERY_NONE
     DevBuf query_texture;
     uint32_t query_tex_w = 0, query_tex_h = 0;
+    // the query toolset (gsx_toolset_*, gsx_api_toolset.cpp; owner only): its state machine and the paints it has queued; the texture it
+    // paints is query_texture above, on this viewer's stream
+    gsx::ToolsetState toolset;
     float highlight[4]{0, 0, 0, 0};
     gsx_gaussian_edit sel_edit{0u, {0.0f, 1.0f, 1.0f}, 0.0f, 0.0f, 1.0f, 1.0f};
     unsigned long long* h_shard_verdict = nullptr;  // pinned, 2 words: {seq | need}, {busiest pair's records | overflow} (k_shard_verify / k_shard_post_counts)
@@ -617,6 +621,36 @@ inline gsx_status depth_refuses_shard(const gsx_viewer* v, const char* fn) {
 // does the RGBA8 resolve of this viewer's frame go over an overlay?  (lines are set and its last frame drew them, at this viewport)
 inline bool overlay_resolves(const gsx_viewer* v) {
     return v->overlay_n && v->overlay_valid && !v->parent && !v->ext_fb && v->overlay_w == v->width && v->overlay_h == v->height;
+}
+// Does the RGBA8 resolve of `src`'s frame (the owner's newest: src is the owner or one of its lanes) draw the toolset's stroke overlay or
+// its cursor on top?  One or the other, never both; neither until its colour has an alpha > 0 (spec section 7, "Toolset").
+inline bool toolset_draws(const gsx_viewer* owner, const gsx_viewer* src, ToolsetDraw* d) {
+    const ToolsetState& t = owner->toolset;
+    memset(d, 0, sizeof *d);
+    if (t.stroke_shown()) {
+        // (pend_clear: start() has not been rendered yet — the texture still holds the stroke before, or a host upload: nothing is shown)
+        if (t.pend_clear || !(t.texture_rgba[3] > 0.0f) || !owner->query_texture.p || owner->query_tex_w != src->width || owner->query_tex_h != src->height) return false;
+        d->mode = kToolsetDrawStroke;
+        d->tex_h = owner->query_tex_h;
+        memcpy(d->rgba, t.texture_rgba, sizeof d->rgba);
+        return true;
+    }
+    if (!t.cursor_known || !(t.cursor_rgba[3] > 0.0f)) return false;
+    memcpy(d->rgba, t.cursor_rgba, sizeof d->rgba);
+    d->half_thickness = 0.5f * t.cursor_thickness;
+    if (t.active() && t.tool == GSX_TOOL_RECT) {  // (an immediate-mode stroke: a texture-mode one shows its texture)
+        d->mode = kToolsetDrawRectOutline;
+        d->x0 = std::min(t.start_pos[0], t.pos[0]);
+        d->y0 = std::min(t.start_pos[1], t.pos[1]);
+        d->x1 = std::max(t.start_pos[0], t.pos[0]);
+        d->y1 = std::max(t.start_pos[1], t.pos[1]);
+    } else {
+        d->mode = kToolsetDrawRing;
+        d->x0 = t.cursor[0];
+        d->y0 = t.cursor[1];
+        d->radius = t.brush_radius;
+    }
+    return true;
 }
 inline float4* fb_ptr(gsx_viewer* v) { return v->ext_fb ? static_cast<float4*>(v->ext_fb) : reinterpret_cast<float4*>(v->fb.p); }
 

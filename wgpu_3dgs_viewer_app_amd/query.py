@@ -198,6 +198,55 @@ class QueryToolset:
         return QueryPod.brush(self._prev, self._pos, self.brush_radius, self._op)
 
 
+class DeviceQueryToolset:
+    """``gs::QueryToolset`` inside libgsx.so, bound to a viewer: :class:`QueryToolset`'s interface, with the strokes painted on the device
+    into the viewer's query texture (``gsx_toolset_*``).  ``render()`` is ``query_toolset.render(queue, &mut encoder, &query_texture)``
+    (scene.rs:791): it enqueues what ``start`` / ``update_pos`` queued and returns.  The texture never crosses the host; ``texture``
+    downloads it (tests)."""
+
+    def __init__(self, viewer):
+        self._v, self._L = viewer, _lib.load()
+
+    @staticmethod
+    def _pos(pos):
+        return (C.c_float * 2)(float(pos[0]), float(pos[1]))
+
+    def set_use_texture(self, on: bool) -> None:
+        _lib.check(self._L.gsx_toolset_set_use_texture(self._v._h, 1 if on else 0))
+
+    def update_brush_radius(self, r) -> None:
+        _lib.check(self._L.gsx_toolset_update_brush_radius(self._v._h, float(r)))
+
+    def start(self, tool, op, pos) -> None:
+        _lib.check(self._L.gsx_toolset_start(self._v._h, int(tool), int(op), self._pos(pos)))
+
+    def update_pos(self, pos) -> None:
+        _lib.check(self._L.gsx_toolset_update_pos(self._v._h, self._pos(pos)))
+
+    def end(self) -> None:
+        _lib.check(self._L.gsx_toolset_end(self._v._h))
+
+    def render(self) -> None:
+        _lib.check(self._L.gsx_toolset_render(self._v._h))
+
+    def state(self):
+        active, tool, op = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        start, pos = (C.c_float * 2)(), (C.c_float * 2)()
+        _lib.check(self._L.gsx_toolset_state(self._v._h, C.byref(active), C.byref(tool), C.byref(op), start, pos))
+        if not active.value:
+            return None
+        return QueryToolsetTool(tool.value), QuerySelectionOp(op.value), (start[0], start[1]), (pos[0], pos[1])
+
+    def query(self) -> QueryPod:
+        q = _lib.Query()
+        _lib.check(self._L.gsx_toolset_query(self._v._h, C.byref(q)))
+        return QueryPod(q.kind, q.selection_op, tuple(q.p0), tuple(q.p1), q.radius)
+
+    @property
+    def texture(self) -> np.ndarray:
+        return self._v.download_query_texture()
+
+
 def _cam_args(camera, size):
     w, h = int(size[0]), int(size[1])
     v = np.ascontiguousarray(camera.view(), np.float32).reshape(16)

@@ -406,6 +406,20 @@ class MultiModelViewer:
         t = np.ascontiguousarray(texels, np.uint8)
         _lib.check(self._L.gsx_update_query_texture(self._h, t.ctypes.data, t.shape[1], t.shape[0]))
 
+    def download_query_texture(self) -> np.ndarray:
+        """uint8 [H, W]: the query texture as the device holds it (the viewport's size once the toolset has rendered)."""
+        w, h = self.size
+        out = np.empty((h, w), np.uint8)
+        _lib.check(self._L.gsx_download_query_texture(self._h, out.ctypes.data, w, h))
+        return out
+
+    def set_toolset_overlay(self, texture_rgba=(0.0, 0.0, 0.0, 0.0), cursor_rgba=(0.0, 0.0, 0.0, 0.0), cursor_thickness: float = 1.0) -> None:
+        """``QueryTextureOverlay`` / ``QueryCursor`` (src/tab/scene.rs:2003-2014, 2317-2325): the straight-alpha colours the RGBA8 resolve
+        draws the stroke and the cursor with; alpha 0 (the default) draws nothing."""
+        t = np.ascontiguousarray(texture_rgba, np.float32).reshape(4)
+        c = np.ascontiguousarray(cursor_rgba, np.float32).reshape(4)
+        _lib.check(self._L.gsx_toolset_set_overlay(self._h, _f32p(t), _f32p(c), float(cursor_thickness)))
+
     def update_selection_highlight(self, rgba) -> None:
         """``viewer.update_selection_highlight(queue, vec4)`` / ``_with_pod`` (src/tab/scene.rs:816-829)."""
         c = np.ascontiguousarray(rgba, np.float32).reshape(4)
