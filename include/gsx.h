@@ -226,7 +226,9 @@ gsx_status gsx_render_frame(gsx_viewer* v, const char* const* keys_far_to_near, 
 /* ---- depth test against the caller's depth buffer: the `depth_stencil` of gs::MultiModelViewer::new_with,
  *      DepthStencilState { Depth32Float, depth_write_enabled: false, Less } (scene.rs:1969-1980).  The app draws the mask
  *      gizmos and the measurement lines with depth write on first (scene.rs:2145-2160, renderer/measurement.rs:110-115); a
- *      splat behind them is hidden at that pixel (spec §6, "Depth test").
+ *      splat behind them is hidden at that pixel (spec §6, "Depth test").  The library draws both itself
+ *      (gsx_viewer_set_mask_gizmos, gsx_viewer_set_overlay_lines below), so the app needs no caller buffer for them: this block is
+ *      for a host that draws something else of its own into the depth attachment.
  *  - The buffer is float32 [height][width] (row 0 at the top, like the framebuffer) of NDC depth in [0, 1], viewport-sized.
  *    A splat's fragments carry the depth of its centre; with GSX_DEPTH_LESS it is blended at pixel p only if it lies in front
  *    of D(p).  Nothing is written to the buffer.  Every model of a frame is tested against the same buffer.  D >= 1 (a cleared
@@ -288,11 +290,34 @@ typedef struct gsx_overlay_line { float p0[3]; uint8_t color[4]; float p1[3]; fl
 #define GSX_OVERLAY_MAX_LINES 4096u
 /* MeasurementRenderer::update_hit_pairs (measurement.rs:133-167); host array, copied; n = 0 clears */
 gsx_status gsx_viewer_set_overlay_lines(gsx_viewer* v, const gsx_overlay_line* lines, uint32_t n);
+
+/* ---- mask gizmos: the wireframes of the mask shapes (gs::MaskGizmo; scene.rs:2141-2166 the pass, :2211-2247 its update, :2283-2293
+ *      the draws), which SceneCallback::paint draws first of all, with the lines' depth state.  Drawn by the library (spec §10, "Mask
+ *      gizmos"); with the lines above, the library then makes all the depth the app's splats are tested against.
+ *  - A record is a mask shape in WORLD space — kind, pos, rotation quaternion (x, y, z, w), scale, as gsx_mask_shape — with a straight
+ *    RGBA colour in [0, 1] (gs::MaskShape.color) and a width in gsx_overlay_line.line_width units.  The host passes, for each key of
+ *    the frame's render keys, that model's visible boxes and then its visible ellipsoids.
+ *  - The wireframe is the boundary of the set the mask tests (spec §2c): the 12 edges of the box, or the three circles of the
+ *    ellipsoid in the shape's coordinate planes, GSX_GIZMO_CIRCLE_SEGMENTS chords each.  Every segment is clipped against the near
+ *    plane (clip z >= 0) — the camera may sit inside a shape — and is then drawn as an overlay line is: the same trapezoid, `Less`,
+ *    depth write, straight alpha blending into the same overlay and effective depth E.
+ *  - Order: every gizmo segment, in record order then segment order, before the first overlay line.
+ *  - Everything else is as for the lines: when they are drawn, E, the resolve, gsx_render's refusal of a frame preprocessed before
+ *    the call, frames on the viewer itself while any are set, and the refusal of gsx_shard_* frames, gsx_render_more, band frames and
+ *    an external framebuffer.  With none set nothing of this exists.
+ *  - GSX_OVERLAY_BATCH_BOXES=0 (read when the viewer is created; A/B) makes the raster walk every batch of 64 records in every tile
+ *    instead of culling batches by their pixel boxes; no result changes. */
+typedef struct gsx_mask_gizmo { uint32_t kind; float pos[3]; float quat_xyzw[4]; float scale[3]; float color[4]; float line_width; } gsx_mask_gizmo; /* 64 B */
+#define GSX_GIZMO_MAX_SHAPES 256u
+#define GSX_GIZMO_CIRCLE_SEGMENTS 64u
+/* gs::MaskGizmo::update + render_box_with_pass / render_ellipsoid_with_pass (scene.rs:2230-2246, :2283-2293); host array, copied;
+ * n = 0 clears.  kind: gsx_mask_shape_kind; an unknown kind or a field that is not finite: GSX_ERR_INVALID_ARG */
+gsx_status gsx_viewer_set_mask_gizmos(gsx_viewer* v, const gsx_mask_gizmo* gizmos, uint32_t n);
 /* last frame's overlay: premultiplied rgba float [h][w][4] (zeros where nothing), effective depth [h][w]; either nullable; synchronises.
- * A frame without lines has no overlay: zeros, and the caller's depth buffer (1 where there is none). */
+ * A frame without lines or gizmos has no overlay: zeros, and the caller's depth buffer (1 where there is none). */
 gsx_status gsx_download_overlay(gsx_viewer* v, float* rgba, float* depth);
 /* zero-copy: colour (float4 per pixel, meaningful only in tiles whose flag is 1), per-tile flags (u32 per 16x16 tile, row-major),
- * effective depth (float per pixel) — of the last frame rendered with lines set; GSX_ERR_INVALID_ARG when there is none */
+ * effective depth (float per pixel) — of the last frame rendered with lines or gizmos set; GSX_ERR_INVALID_ARG when there is none */
 gsx_status gsx_overlay_device_ptrs(gsx_viewer* v, void** rgba, void** tile_flags, void** depth);
 
 /* ---- readback (buffer.download(&device,&queue), app.rs:789, app.rs:806) ---- */

@@ -221,6 +221,12 @@ public:
     void update_hit_pairs(const std::vector<gsx_overlay_line>& lines) {
         check(gsx_viewer_set_overlay_lines(v_, lines.empty() ? nullptr : lines.data(), (uint32_t)lines.size()));
     }
+    // gs::MaskGizmo (src/tab/scene.rs:2211-2247, 2283-2293): the mask shapes' wireframes, drawn by the library before the measurement
+    // lines with their depth state (gsx.h, the gizmo block): per render key the model's visible boxes, then its visible ellipsoids, in
+    // world space; an empty vector clears them
+    void set_mask_gizmos(const std::vector<gsx_mask_gizmo>& gizmos) {
+        check(gsx_viewer_set_mask_gizmos(v_, gizmos.empty() ? nullptr : gizmos.data(), (uint32_t)gizmos.size()));
+    }
     // last frame's overlay: premultiplied rgba [size.y][size.x][4] and the effective depth [size.y][size.x]; either may be null
     void download_overlay(float* rgba, float* depth) { check(gsx_download_overlay(v_, rgba, depth)); }
     MultiModelViewer(int device, UVec2 sz, ShCompression sh_, Cov3dCompression cov_) : sh(sh_), cov3d(cov_), size(sz) {

@@ -17,6 +17,8 @@ pub const GSX_MASK_MAX_OPS: u32 = 64;
 pub const GSX_MASK_MAX_SHAPES: u32 = 32;
 pub const GSX_QUERY_MAX_HITS: u32 = 65536;
 pub const GSX_OVERLAY_MAX_LINES: u32 = 4096;
+pub const GSX_GIZMO_MAX_SHAPES: u32 = 256;
+pub const GSX_GIZMO_CIRCLE_SEGMENTS: u32 = 64;
 pub const GSX_EDIT_ENABLED: u32 = 1;
 pub const GSX_EDIT_HIDDEN: u32 = 2;
 pub const GSX_EDIT_OVERRIDE_COLOR: u32 = 4;
@@ -131,6 +133,11 @@ pub enum gsx_toolset_tool { Rect = 0, Brush = 1 } // gs::QueryToolsetTool, src/t
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_overlay_line { pub p0: [f32; 3], pub color: [u8; 4], pub p1: [f32; 3], pub line_width: f32 }
+/// a mask shape's gizmo (gs::MaskGizmo; src/tab/scene.rs:2211-2247), 64 bytes: a world-space `gs::MaskShape` (kind 0 box / 1 ellipsoid),
+/// its straight RGBA colour in [0, 1] and a width in `gsx_overlay_line::line_width` units
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gsx_mask_gizmo { pub kind: u32, pub pos: [f32; 3], pub quat_xyzw: [f32; 4], pub scale: [f32; 3], pub color: [f32; 4], pub line_width: f32 }
 /// the two collectives of a caller-supplied transport: they ENQUEUE on `hip_stream` and return 0 or a gsx_status
 pub type gsx_comm_all_to_all_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, d_send: *const c_void, d_recv: *mut c_void, bytes_per_peer: u64, hip_stream: *mut c_void) -> gsx_status>;
 pub type gsx_comm_all_gather_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, d_send: *const c_void, d_recv: *mut c_void, bytes_per_rank: u64, hip_stream: *mut c_void) -> gsx_status>;
@@ -186,6 +193,7 @@ extern "C" {
     pub fn gsx_viewer_set_depth_buffer_device(v: *mut gsx_viewer, d_ptr: *const f32, width: u32, height: u32, row_pitch_bytes: u64) -> gsx_status;
     pub fn gsx_viewer_upload_depth_buffer(v: *mut gsx_viewer, host: *const f32, width: u32, height: u32) -> gsx_status;
     pub fn gsx_viewer_set_overlay_lines(v: *mut gsx_viewer, lines: *const gsx_overlay_line, n: u32) -> gsx_status;
+    pub fn gsx_viewer_set_mask_gizmos(v: *mut gsx_viewer, gizmos: *const gsx_mask_gizmo, n: u32) -> gsx_status;
     pub fn gsx_download_overlay(v: *mut gsx_viewer, rgba: *mut f32, depth: *mut f32) -> gsx_status;
     pub fn gsx_overlay_device_ptrs(v: *mut gsx_viewer, rgba: *mut *mut c_void, tile_flags: *mut *mut c_void, depth: *mut *mut c_void) -> gsx_status;
     pub fn gsx_download_framebuffer(v: *mut gsx_viewer, rgbt: *mut f32, n_floats: u64) -> gsx_status;

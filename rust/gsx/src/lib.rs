@@ -221,6 +221,13 @@ impl<G: GaussianPod> MultiModelViewer<G> {
         let p = if hit_pairs.is_empty() { std::ptr::null() } else { hit_pairs.as_ptr() };
         check(unsafe { sys::gsx_viewer_set_overlay_lines(self.handle.0, p, hit_pairs.len() as u32) })
     }
+    /// `gs::MaskGizmo::update` + `render_box_with_pass` / `render_ellipsoid_with_pass` (src/tab/scene.rs:2211-2247, 2283-2293): the mask
+    /// shapes' wireframes, drawn by the library before the measurement lines, with their depth state (`gsx.h`, the gizmo block).  Pass, for
+    /// each render key, that model's visible boxes and then its visible ellipsoids, in world space.  An empty slice clears them.
+    pub fn set_mask_gizmos(&mut self, gizmos: &[sys::gsx_mask_gizmo]) -> Result<(), Error> {
+        let p = if gizmos.is_empty() { std::ptr::null() } else { gizmos.as_ptr() };
+        check(unsafe { sys::gsx_viewer_set_mask_gizmos(self.handle.0, p, gizmos.len() as u32) })
+    }
     /// Last frame's overlay: premultiplied rgba `[height][width][4]` and the effective depth `[height][width]` the splats were tested against.
     pub fn download_overlay(&mut self, size: (u32, u32)) -> Result<(Vec<f32>, Vec<f32>), Error> {
         let n = size.0 as usize * size.1 as usize;

@@ -29,7 +29,7 @@ EXPORTS = (
     "gsx_mask_evaluate", "gsx_ply_read_header", "gsx_ply_read_gaussians", "gsx_ply_write", "gsx_render_options_default", "gsx_viewer_set_render_options", "gsx_shard_layout", "gsx_viewer_set_external_framebuffer", "gsx_shard_pack", "gsx_shard_import", "gsx_shard_feedback_words", "gsx_shard_feedback", "gsx_shard_set_windows", "gsx_viewer_set_band", "gsx_resolve_rgba8_device",
     "gsx_render_more", "gsx_debug_set_radix_rank_mode",
     "gsx_viewer_set_depth_test", "gsx_viewer_set_depth_buffer_device", "gsx_viewer_upload_depth_buffer",
-    "gsx_viewer_set_overlay_lines", "gsx_download_overlay", "gsx_overlay_device_ptrs",
+    "gsx_viewer_set_overlay_lines", "gsx_viewer_set_mask_gizmos", "gsx_download_overlay", "gsx_overlay_device_ptrs",
     "gsx_shard_frame_begin", "gsx_shard_slot_records", "gsx_shard_pack_slots", "gsx_shard_import_slots", "gsx_shard_verify",
     "gsx_shard_wait_verdict", "gsx_shard_repair_count", "gsx_shard_post_counts", "gsx_shard_frame_end",
     "gsx_shard_next_windows", "gsx_shard_download_limits", "gsx_comm_unique_id", "gsx_viewer_comm_init", "gsx_viewer_comm_destroy",
@@ -55,6 +55,16 @@ GSX_OVERLAY_MAX_LINES = 4096
 class OverlayLine(C.Structure):
     """``gsx_overlay_line`` = the reference's measurement ``HitPair`` (32 bytes)."""
     _fields_ = [("p0", C.c_float * 3), ("color", C.c_uint8 * 4), ("p1", C.c_float * 3), ("line_width", C.c_float)]
+
+
+GSX_GIZMO_MAX_SHAPES = 256
+GSX_GIZMO_CIRCLE_SEGMENTS = 64
+
+
+class MaskGizmo(C.Structure):
+    """``gsx_mask_gizmo``: a world-space mask shape, its straight RGBA colour and a line width (64 bytes)."""
+    _fields_ = [("kind", C.c_uint32), ("pos", C.c_float * 3), ("quat_xyzw", C.c_float * 4), ("scale", C.c_float * 3),
+                ("color", C.c_float * 4), ("line_width", C.c_float)]
 
 
 class GaussianEdit(C.Structure):
@@ -144,7 +154,8 @@ class GsxError(RuntimeError):
 
 _lib = None
 #: names load() lets a library lack.  Empty: a library exports every declared name.  tools/bench_drag.py names the toolset's calls here,
-#: before the first load(), when it runs its host rows on a build from before the toolset (GSX_LIB); nothing else may.
+#: before the first load(), when it runs its host rows on a build from before the toolset (GSX_LIB), and tools/bench_depth.py names
+#: gsx_viewer_set_mask_gizmos for its rows on a build from before the gizmos; nothing else may.
 MAY_LACK: frozenset = frozenset()
 
 
@@ -226,6 +237,7 @@ def load() -> C.CDLL:
         "gsx_viewer_set_depth_buffer_device": ([vp, vp, u32, u32, u64], C.c_int32),
         "gsx_viewer_upload_depth_buffer": ([vp, f32p, u32, u32], C.c_int32),
         "gsx_viewer_set_overlay_lines": ([vp, vp, u32], C.c_int32),
+        "gsx_viewer_set_mask_gizmos": ([vp, vp, u32], C.c_int32),
         "gsx_download_overlay": ([vp, f32p, f32p], C.c_int32),
         "gsx_overlay_device_ptrs": ([vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)], C.c_int32),
         "gsx_shard_pack": ([vp, cp, u32, vp, vp, u64, C.POINTER(u64)], C.c_int32),

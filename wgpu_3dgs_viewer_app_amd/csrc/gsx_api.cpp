@@ -102,10 +102,10 @@ static gsx_status lane_create(gsx_viewer* v, gsx_viewer** out) {
 // viewer; selections, edits and the highlight travel: a lane's shadow models view the owner's selection and edit buffers, which
 // the owner prepares before the frame is dealt out, prepare_edits_for_lanes; a depth-tested frame travels too: the lane takes its
 // own snapshot of the depth buffer, lane_sync / depth_snapshot — unless GSX_DEPTH_LANES=0 keeps it on the viewer; a frame with overlay
-// lines stays on the viewer, which owns the overlay's buffers)
+// lines or mask gizmos stays on the viewer, which owns the overlay's buffers)
 static bool frame_may_overlap(gsx_viewer* v, const char* const* keys, uint32_t n_keys) {
     if (v->parent || v->options.frames_in_flight < 2 || v->query.kind != GSX_QUERY_NONE || v->ext_fb || v->band_lo != 0 ||
-        v->band_hi != 0xFFFFFFFFu || (v->depth_compare != GSX_DEPTH_ALWAYS && !v->depth_lanes) || v->overlay_n)
+        v->band_hi != 0xFFFFFFFFu || (v->depth_compare != GSX_DEPTH_ALWAYS && !v->depth_lanes) || overlay_set(v))
         return false;
     for (uint32_t i = 0; i < n_keys; ++i) {
         Model* m = find_model(v, keys ? keys[i] : nullptr);
@@ -283,6 +283,7 @@ gsx_status gsx_viewer_create(const gsx_viewer_desc* desc, gsx_viewer** out) {
     if (const char* e = getenv("GSX_BUCKET_SORT")) v->bucket_sort = atoi(e) != 0;
     if (const char* e = getenv("GSX_SHORT_CHAIN")) v->short_chain = atoi(e) != 0;
     if (const char* e = getenv("GSX_DEPTH_LANES")) v->depth_lanes = atoi(e) != 0;
+    if (const char* e = getenv("GSX_OVERLAY_BATCH_BOXES")) v->overlay_batch_boxes = atoi(e) != 0;
     if (const char* e = getenv("GSX_BIN_BIG_SLAB")) block_bin_set_big_slab((uint32_t)atoi(e));   // tests: smaller slabs take the eight-per-lane tiles
     if (const char* e = getenv("GSX_BUCKET_CAP")) bucket_sort_set_cap((uint32_t)atoi(e));   // tests: buckets above this take the global-memory path
     if (const char* e = getenv("GSX_SORTED_RECORDS")) v->sorted_records = atoi(e) != 0 ? 1 : 0;

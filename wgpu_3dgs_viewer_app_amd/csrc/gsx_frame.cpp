@@ -325,10 +325,11 @@ static gsx_status ensure_msd(gsx_viewer* v, Model* m, DevBuf& ws);
 // viewport or P22 / P23 (recorded with it; gsx_update_camera ends it as well), the end of a frame (gsx_render / gsx_render_frame; every
 // gsx_render_frame starts with a fresh one), and a model preprocessed a second time against it (a new frame whose predecessor failed or
 // was never rendered).  Nothing is ever composited against another frame's snapshot.
-// Overlay lines (gsx_viewer_set_overlay_lines): while lines are set the same snapshot draws them — with either compare — and the limits are
-// made from the effective depth E(p) in the raster launch itself (kernels_overlay.hip); without a caller buffer D = 1.
+// Overlay lines and mask gizmos (gsx_viewer_set_overlay_lines, gsx_viewer_set_mask_gizmos; `lines` below is either): while any are set the
+// same snapshot draws them — with either compare; a set-up launch for each kind that is set, then one raster launch over all records — and
+// the limits are made from the effective depth E(p) in the raster launch itself (kernels_overlay.hip); without a caller buffer D = 1.
 static gsx_status depth_snapshot(gsx_viewer* v, const Model* m) {
-    const bool test = v->depth_compare == GSX_DEPTH_LESS, lines = v->overlay_n != 0;
+    const bool test = v->depth_compare == GSX_DEPTH_LESS, lines = overlay_set(v);
     // z_ndc = z_c / w_c < D  <=>  view depth < P23 / (D + P22) needs the third and fourth rows to depend on view z alone, and
     // z_ndc = P23 / d - P22 to grow with d towards 1 (P23 < 0, P22 <= -1: D + P22 < 0 for every D < 1).  A reversed-Z projection
     // (P23 > 0) turns the inequality round: the limit would show exactly the splats the test hides.
@@ -356,15 +357,19 @@ static gsx_status depth_snapshot(gsx_viewer* v, const Model* m) {
     const uint64_t pitch = v->depth_dev ? v->depth_pitch : 4ull * v->depth_w;
     if (lines) {
         const size_t npx = (size_t)v->width * v->height;
-        HIPCHK(v->overlay_rec.ensure(sizeof(OverlayRec) * (size_t)v->overlay_n));
+        const size_t n_rec = (size_t)v->gizmo_rec + v->overlay_n;
+        HIPCHK(v->overlay_rec.ensure(sizeof(OverlayRec) * n_rec));
+        if (v->overlay_batch_boxes) HIPCHK(v->overlay_boxes.ensure(sizeof(int4) * ((n_rec + 63) / 64)));
         HIPCHK(v->overlay_rgba.ensure(sizeof(float4) * npx));
         HIPCHK(v->overlay_eff.ensure(4 * npx));
         HIPCHK(v->overlay_flags.ensure(4 * (size_t)tiles_x * tiles_y));
         OverlayCamera cam;
         memcpy(cam.view, v->view, sizeof cam.view);
         memcpy(cam.proj, v->proj, sizeof cam.proj);
-        HIPCHK(launch_overlay(v->stream, v->overlay_lines.as<gsx_overlay_line>(), v->overlay_n, cam, src, pitch, v->width, v->height, P[10], P[14],
-                              v->overlay_rec.as<OverlayRec>(), v->overlay_rgba.as<float4>(), v->overlay_flags.as<uint32_t>(),
+        const OverlayGizmos gz{v->gizmo_buf.as<uint8_t>(), v->gizmo_n, v->gizmo_segs, v->gizmo_rec};
+        HIPCHK(launch_overlay(v->stream, gz, v->overlay_lines.as<gsx_overlay_line>(), v->overlay_n, cam, src, pitch, v->width, v->height, P[10], P[14],
+                              v->overlay_rec.as<OverlayRec>(), v->overlay_batch_boxes ? v->overlay_boxes.as<int4>() : nullptr,
+                              v->overlay_rgba.as<float4>(), v->overlay_flags.as<uint32_t>(),
                               v->overlay_eff.as<float>(), test ? v->depth_lim.as<uint32_t>() : nullptr, test ? v->depth_win.as<uint2>() : nullptr));
         v->overlay_valid = true;
         v->overlay_w = v->width;
@@ -463,7 +468,7 @@ gsx_status do_preprocess(gsx_viewer* v, Model* m, bool defer_visible_count) {
     // depth test: every tile's window ends at its depth bound — on plain frames too: a record hidden on every tile of its rectangle
     // never enters the depth sort (exact, not speculative: it could not be blended anyway)
     const bool depth = v->depth_compare == GSX_DEPTH_LESS;
-    const bool lines = v->overlay_n != 0;  // overlay lines: drawn by the same snapshot, with either compare
+    const bool lines = overlay_set(v);  // overlay lines, mask gizmos: drawn by the same snapshot, with either compare
     if (lines) {
         if (shard_lazy || m->use_imported) return overlay_refuses(v, "gsx_preprocess", "sharded frames do");
         if (v->band_lo != 0 || v->band_hi != 0xFFFFFFFFu) return overlay_refuses(v, "gsx_preprocess", "band frames (gsx_viewer_set_band) do");
@@ -1180,9 +1185,9 @@ static gsx_status do_bin_and_composite(gsx_viewer* v, Model* m, bool carry, cons
     // depth test: the model's admission was made against a depth snapshot; it must be the one this frame composites with
     const bool depth = m->depth_snap != 0;
     // ... and so are the overlay lines it was preprocessed with
-    if ((v->overlay_n || m->overlay_snap) && (m->overlay_snap != v->depth_snap || v->depth_snap_cfg != v->depth_cfg || v->depth_snap_w != m->fc.w_px ||
+    if ((overlay_set(v) || m->overlay_snap) && (m->overlay_snap != v->depth_snap || v->depth_snap_cfg != v->depth_cfg || v->depth_snap_w != m->fc.w_px ||
                                               v->depth_snap_h != m->fc.h_px))
-        return fail(GSX_ERR_INVALID_ARG, "gsx_render: the overlay lines, the depth test or its depth buffer changed since gsx_preprocess('%s'); call "
+        return fail(GSX_ERR_INVALID_ARG, "gsx_render: the overlay lines, the mask gizmos, the depth test or its depth buffer changed since gsx_preprocess('%s'); call "
                     "gsx_preprocess + gsx_sort('%s') again", m->key.c_str(), m->key.c_str());
     if (v->depth_compare == GSX_DEPTH_LESS ? (m->depth_snap != v->depth_snap || v->depth_snap_cfg != v->depth_cfg || v->depth_snap_w != m->fc.w_px ||
                                               v->depth_snap_h != m->fc.h_px) : depth)

@@ -6,6 +6,7 @@
 
 #include "../../include/gsx.h"
 #include "gsx_launch.h"
+#include "gizmo_math.h"
 #include "toolset_math.h"
 
 namespace gsx {
@@ -747,8 +748,8 @@ __device__ __forceinline__ uint32_t depth_limit_key(float d, float p22, float p2
     return lim > 0.0f ? __float_as_uint(lim) : 0u;
 }
 
-// Overlay lines (kernels_overlay.hip; spec section 9): the reference's measurement pass, drawn where the depth snapshot is taken.
-// One record per line, written by the set-up launch and walked in array order by the raster launch.
+// Overlay lines and mask gizmos (kernels_overlay.hip; spec sections 9 and 10): the reference's gizmo and measurement passes, drawn where
+// the depth snapshot is taken.  One record per line or gizmo segment, written by the set-up launch and walked in array order by the raster launch.
 struct alignas(16) OverlayRec {
     float cx[4], cy[4];          // pixel-space corners: end 1 -, end 1 +, end 0 -, end 0 +
     float z0, z1;                // NDC depth of end 0 / end 1 (the corners of an end carry its depth)
@@ -761,12 +762,22 @@ static_assert(sizeof(OverlayRec) == 96, "OverlayRec is staged through LDS as six
 struct OverlayCamera {
     float view[16], proj[16];    // column-major, as gsx_update_camera takes them
 };
-// lines: n x gsx_overlay_line (device).  rec: n records.  depth (nullable: D = 1) / pitch_bytes: the caller's depth buffer.
-// rgba: float4 per pixel, written only for tiles whose flag word is 1 (some drawn line's box touches the tile); eff: E(p) per pixel.
+// Mask gizmos (spec section 10) in one device buffer: the (cos, sin) circle table, the shapes' first-record offsets (n_shapes + 1 words)
+// and the n_shapes gsx_mask_gizmo records.  n_segs: records the shapes make; n_rec: n_segs padded with undrawn records to whole batches of 64.
+constexpr size_t kGizmoOffsetsAt = sizeof(GizmoCircle);                                              // 512
+constexpr size_t kGizmoShapesAt = kGizmoOffsetsAt + 4 * ((GSX_GIZMO_MAX_SHAPES + 1 + 3) / 4 * 4);    // 16-byte aligned
+struct OverlayGizmos {
+    const uint8_t* buf;
+    uint32_t n_shapes, n_segs, n_rec;
+};
+// gz: the gizmos (n_rec == 0: none).  lines: n x gsx_overlay_line (device).  rec: gz.n_rec + n records, the gizmos' first.
+// boxes (nullable: the raster walks every batch): one int4 per batch of 64 records.  depth (nullable: D = 1) / pitch_bytes: the caller's
+// depth buffer.
+// rgba: float4 per pixel, written only for tiles whose flag word is 1 (some drawn record's box touches the tile); eff: E(p) per pixel.
 // lim / window (both null or both set): what launch_depth_limits writes, made from E(p) in the same launch.
-hipError_t launch_overlay(hipStream_t s, const gsx_overlay_line* lines, uint32_t n, const OverlayCamera& cam, const float* depth,
-                          uint64_t pitch_bytes, uint32_t w, uint32_t h, float p22, float p23, OverlayRec* rec, float4* rgba,
-                          uint32_t* tile_flags, float* eff, uint32_t* lim, uint2* window);
+hipError_t launch_overlay(hipStream_t s, const OverlayGizmos& gz, const gsx_overlay_line* lines, uint32_t n, const OverlayCamera& cam,
+                          const float* depth, uint64_t pitch_bytes, uint32_t w, uint32_t h, float p22, float p23, OverlayRec* rec, int4* boxes,
+                          float4* rgba, uint32_t* tile_flags, float* eff, uint32_t* lim, uint2* window);
 // the RGBA8 resolve over an overlay: out.rgb = rgb + T (C + (1 - A) background), alpha = 1 - T (1 - A); pixels [first, first + n_px)
 hipError_t launch_resolve_rgba8_overlay(hipStream_t s, const float4* fb, uint32_t first, uint32_t n_px, uint32_t w, float bg_r, float bg_g,
                                         float bg_b, const float4* overlay_rgba, const uint32_t* tile_flags, uint32_t* out_rgba8);

@@ -474,6 +474,12 @@ struct gsx_viewer {
     uint32_t overlay_n = 0, overlay_w = 0, overlay_h = 0;
     bool overlay_valid = false;
     DevBuf overlay_lines, overlay_rec, overlay_rgba, overlay_flags, overlay_eff;
+    // mask gizmos (gsx_viewer_set_mask_gizmos; spec section 10): drawn with the lines and in front of them, under the same rules.  gizmo_buf:
+    // circle table, offsets, shapes (OverlayGizmos, gsx_internal.h); gizmo_segs records, padded to gizmo_rec.  overlay_boxes: one pixel box
+    // per batch of 64 records of either kind, unless GSX_OVERLAY_BATCH_BOXES=0 (overlay_batch_boxes; A/B) keeps the raster's flat walk
+    uint32_t gizmo_n = 0, gizmo_segs = 0, gizmo_rec = 0;
+    bool overlay_batch_boxes = true;
+    DevBuf gizmo_buf, overlay_boxes;
     gsx_render_options options{1u, 16u, 131072u, 2u, 1u, 0.25f, 3u, 0u, 1u, 1u};  // = gsx_render_options_default (a CPU test compares the two: gsx_viewer_get_render_options)
     bool host_waited = false;  // the host has waited for this viewer's device work (gsx_sync, a blocking readback) since its last frame was enqueued:
                                // the app synchronises per frame, so asking for a speculated frame's verdict costs it nothing (host_verify = 2)
@@ -606,10 +612,14 @@ inline gsx_status ensure_fb(gsx_viewer* v) {
 }
 // readback entry points refer to the newest frame, whichever lane rendered it
 inline gsx_viewer* result_lane(gsx_viewer* v) { return v->latest ? v->latest : v; }
-// the overlay lines are part of neither the sharded frames nor band frames nor frames into an external framebuffer (gsx_preprocess checks the latter two)
+// is anything set that the depth snapshot draws: overlay lines, mask gizmos?
+inline bool overlay_set(const gsx_viewer* v) { return v->overlay_n != 0 || v->gizmo_n != 0; }
+// the overlay lines and the mask gizmos are part of neither the sharded frames nor band frames nor frames into an external framebuffer
+// (gsx_preprocess checks the latter two)
 inline gsx_status overlay_refuses(const gsx_viewer* v, const char* fn, const char* what) {
-    if (v && v->overlay_n)
-        return fail(GSX_ERR_INVALID_ARG, "%s: %s not support the overlay lines (gsx_viewer_set_overlay_lines(v, NULL, 0) first)", fn, what);
+    if (v && overlay_set(v))
+        return fail(GSX_ERR_INVALID_ARG, "%s: %s not support the overlay lines or the mask gizmos (gsx_viewer_set_overlay_lines(v, NULL, 0) and "
+                    "gsx_viewer_set_mask_gizmos(v, NULL, 0) first)", fn, what);
     return GSX_OK;
 }
 // the depth test is not part of the sharded (multi-GPU) frames yet: every entry point of theirs refuses while it is on
@@ -618,9 +628,9 @@ inline gsx_status depth_refuses_shard(const gsx_viewer* v, const char* fn) {
         return fail(GSX_ERR_INVALID_ARG, "%s: sharded frames do not support the depth test (gsx_viewer_set_depth_test(v, GSX_DEPTH_ALWAYS) first)", fn);
     return overlay_refuses(v, fn, "sharded frames do");
 }
-// does the RGBA8 resolve of this viewer's frame go over an overlay?  (lines are set and its last frame drew them, at this viewport)
+// does the RGBA8 resolve of this viewer's frame go over an overlay?  (lines or gizmos are set and its last frame drew them, at this viewport)
 inline bool overlay_resolves(const gsx_viewer* v) {
-    return v->overlay_n && v->overlay_valid && !v->parent && !v->ext_fb && v->overlay_w == v->width && v->overlay_h == v->height;
+    return overlay_set(v) && v->overlay_valid && !v->parent && !v->ext_fb && v->overlay_w == v->width && v->overlay_h == v->height;
 }
 // Does the RGBA8 resolve of `src`'s frame (the owner's newest: src is the owner or one of its lanes) draw the toolset's stroke overlay or
 // its cursor on top?  One or the other, never both; neither until its colour has an alpha > 0 (spec section 7, "Toolset").

@@ -29,12 +29,37 @@ class MaskShapeKind(enum.IntEnum):
 
 @dataclass
 class MaskShape:
-    """``gs::MaskShape {kind, pos, rotation, scale, color}`` (src/app.rs:1620-1640; colour is gizmo-only)."""
+    """``gs::MaskShape {kind, pos, rotation, scale, color}`` (src/app.rs:1620-1640; colour is gizmo-only: straight RGBA in [0, 1])."""
 
     kind: MaskShapeKind = MaskShapeKind.Box
     pos: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
     rotation: np.ndarray = field(default_factory=lambda: np.array([0, 0, 0, 1], np.float32))  # quaternion x,y,z,w
     scale: np.ndarray = field(default_factory=lambda: np.ones(3, np.float32))
+    color: np.ndarray = field(default_factory=lambda: np.ones(4, np.float32))
+
+    def to_mask_gizmo_pod(self, line_width: float = 1.0) -> np.ndarray:
+        """This shape's gizmo as one ``viewer.MASK_GIZMO_DTYPE`` record (``gs::MaskGizmoPod``; ``MultiModelViewer.set_mask_gizmos``)."""
+        from .viewer import MASK_GIZMO_DTYPE
+
+        r = np.zeros(1, MASK_GIZMO_DTYPE)
+        r["kind"] = int(self.kind)
+        r["pos"] = np.asarray(self.pos, np.float32)
+        r["quat_xyzw"] = np.asarray(self.rotation, np.float32)
+        r["scale"] = np.asarray(self.scale, np.float32)
+        r["color"] = np.asarray(self.color, np.float32)
+        r["line_width"] = np.float32(line_width)
+        return r
+
+
+def gizmo_records(models_in_render_order, line_width: float = 1.0) -> np.ndarray:
+    """The records ``SceneCallback::paint`` draws (src/tab/scene.rs:2213-2227, 2283-2293): for each model of the frame's render keys, in
+    their order, its visible boxes and then its visible ellipsoids.  ``models_in_render_order``: one sequence of visible ``MaskShape`` per
+    model."""
+    from .viewer import MASK_GIZMO_DTYPE
+
+    recs = [s.to_mask_gizmo_pod(line_width) for shapes in models_in_render_order
+            for kind in (MaskShapeKind.Box, MaskShapeKind.Ellipsoid) for s in shapes if s.kind == kind]
+    return np.concatenate(recs) if recs else np.zeros(0, MASK_GIZMO_DTYPE)
 
 
 class MaskOpError(ValueError):

@@ -94,6 +94,11 @@ def HitPair(p0, p1, color=(255, 255, 255, 255), line_width: float = 1.0) -> np.n
     return r
 
 
+#: ``gsx_mask_gizmo``: a world-space mask shape, its straight RGBA colour in [0, 1] and a width in ``HitPair.line_width`` units, 64 bytes
+MASK_GIZMO_DTYPE = np.dtype([("kind", "<u4"), ("pos", "<f4", 3), ("quat_xyzw", "<f4", 4), ("scale", "<f4", 3), ("color", "<f4", 4),
+                             ("line_width", "<f4")])
+
+
 def _f32p(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
@@ -488,6 +493,20 @@ class MultiModelViewer:
             lines = np.concatenate([np.asarray(x, HIT_PAIR_DTYPE).reshape(-1) for x in lines])
         a = np.ascontiguousarray(lines, HIT_PAIR_DTYPE).reshape(-1)
         _lib.check(self._L.gsx_viewer_set_overlay_lines(self._h, a.ctypes.data, int(a.shape[0])))
+
+    # -- mask gizmos: the mask shapes' wireframes (gs::MaskGizmo, src/tab/scene.rs:2211-2247, 2283-2293), drawn before the lines --
+    def set_mask_gizmos(self, gizmos) -> None:
+        """Records of ``MASK_GIZMO_DTYPE`` (an array, or a sequence of them: ``mask.gizmo_records``) in draw order: for each render
+        key that model's visible boxes, then its visible ellipsoids, in world space; empty or ``None`` clears.  Drawn by the first
+        ``preprocess`` of every frame from then on, before the measurement lines and with their depth state (``gsx.h``, the gizmo
+        block)."""
+        if gizmos is None or len(gizmos) == 0:
+            _lib.check(self._L.gsx_viewer_set_mask_gizmos(self._h, None, 0))
+            return
+        if not isinstance(gizmos, np.ndarray):
+            gizmos = np.concatenate([np.asarray(x, MASK_GIZMO_DTYPE).reshape(-1) for x in gizmos])
+        a = np.ascontiguousarray(gizmos, MASK_GIZMO_DTYPE).reshape(-1)
+        _lib.check(self._L.gsx_viewer_set_mask_gizmos(self._h, a.ctypes.data, int(a.shape[0])))
 
     def download_overlay(self):
         """``(rgba, depth)`` of the last frame's overlay: premultiplied float32 [H, W, 4] (zeros where no line is) and the effective
