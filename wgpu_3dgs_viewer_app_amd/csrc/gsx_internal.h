@@ -293,8 +293,11 @@ constexpr uint32_t kMsdCells = 2048, kMsdTicket = 2056, kMsdRanges = 2064, kMsdS
 constexpr uint32_t kCompactWordsPerTile = 1024;  // ballot words (64 Gaussians each) per k_admit_compact workgroup — 256 for models of fewer than
 constexpr uint32_t kCompactSmallWords = 65536;   // ... this many ballot words (4.2 M Gaussians)
 inline size_t msd_workspace_words(uint64_t n_gaussians) {
+    // status words for the FINER tiling at every count: a workspace sized for one count serves every launch of a smaller one, whichever
+    // tiling that launch picks from its own n (sized by the launch's tiling it shrank at kCompactSmallWords: 256 tiles just below, 64 at
+    // it).  At most 16 bytes per 16 384 Gaussians.
     const uint64_t words = (n_gaussians + 63) / 64;
-    const uint64_t tiles = words < kCompactSmallWords ? (words + 255) / 256 : (words + kCompactWordsPerTile - 1) / kCompactWordsPerTile;
+    const uint64_t tiles = (words + 255) / 256;
     return kMsdStatus + 4 * (size_t)(tiles + 1);
 }
 #ifdef __HIPCC__
