@@ -359,6 +359,40 @@ gsx_status gsx_model_download_tile_lists(gsx_viewer* v, const char* key, uint32_
 gsx_status gsx_model_download_pod(gsx_viewer* v, const char* key, float* pos, uint32_t* color, float* sh,
                                   float* cov3d);
 
+/* ---- model bounds: the box, the centre and the centroid of a model's Gaussian centres, computed on the device from the resident
+ *      positions (spec/RENDER_SPEC.md §11 [BUILD-SPEC]).  `center` is GaussianSplattingModel::center, "the center of the bounding
+ *      box" (src/app.rs:1019-1046): what world_center() and the far -> near model order (src/tab/scene.rs:533-558) are computed
+ *      from, and what the reference leaves at Vec3::ZERO.
+ *      Space and extent: model space (what world_center multiplies by the model transform); Gaussian CENTRES only, not their extent.
+ *      Filter: any combination of the flags below; a Gaussian is counted if it passes every one that is set.  The stored buffers are
+ *      read as they are: gsx_model_show_unedited does not change what GSX_BOUNDS_SKIP_HIDDEN means.
+ *      Non-finite: a Gaussian that passes the filter and has a NaN or infinite coordinate is counted in n_nonfinite and left out of
+ *      everything else.
+ *      Trimming: k = count * trim_permille / 1000 (integer arithmetic).  Per axis, [trim_min, trim_max] leaves at most k counted
+ *      Gaussians below it and at most k above it, and each end is within (max - min) / 2048 of the k-th value from its side; an
+ *      axis whose range is zero, not a finite float32, or too small to divide into 2048 float32 bins returns min / max.
+ *      With trim_permille = 0, trim_* equal min / max bit for bit.
+ *      Empty result: count == 0 gives GSX_OK with every float field 0.0f.
+ *      Errors: unknown filter bits or trim_permille >= 500: GSX_ERR_INVALID_ARG; unknown key: GSX_ERR_NOT_FOUND.
+ *      Ordering: the call runs on the viewer's stream, behind the frames in flight and every upload enqueued before it, then
+ *      synchronises and returns.  The result is the same bits from call to call.  It writes nothing a frame reads.
+ *      Sharded viewers: the result covers the resident shard; a caller combines min / max / count across ranks itself.
+ *      (The struct is gsx_model_bounds_t, as gsx_shard_layout_t is: C has one name space for a typedef and a function.) ---- */
+#define GSX_BOUNDS_MASKED      1u  /* only Gaussians the model's mask keeps (bit set = kept; no mask = all) */
+#define GSX_BOUNDS_SKIP_HIDDEN 2u  /* drop Gaussians whose stored edit has ENABLED and HIDDEN */
+#define GSX_BOUNDS_SELECTED    4u  /* only selected Gaussians (no selection = none) */
+typedef struct gsx_bounds_desc { uint32_t filter; uint32_t trim_permille; } gsx_bounds_desc; /* trim_permille < 500 */
+typedef struct gsx_model_bounds_t {
+    uint64_t count;       /* Gaussians that passed the filter and have a finite position */
+    uint64_t n_nonfinite; /* passed the filter, some coordinate NaN or +-inf: left out of everything else */
+    float min[3], max[3]; /* exact */
+    float center[3];      /* 0.5f * (min + max), float32: GaussianSplattingModel::center */
+    float mean[3];        /* centroid of the counted positions (summed in float64, rounded once) */
+    float trim_min[3], trim_max[3];
+} gsx_model_bounds_t; /* 88 bytes */
+void gsx_bounds_desc_default(gsx_bounds_desc* d); /* filter 0, trim_permille 0 */
+gsx_status gsx_model_bounds(gsx_viewer* v, const char* key, const gsx_bounds_desc* desc, gsx_model_bounds_t* out);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

@@ -172,7 +172,20 @@ struct MultiModelViewerGaussianBuffers {
     SelectionBuffer selection_buffer;
     GaussiansEditBuffer gaussians_edit_buffer;
 };
-struct MultiModelViewerModel { MultiModelViewerGaussianBuffers gaussian_buffers; };
+using ModelBounds = gsx_model_bounds_t;  // box, centre (GaussianSplattingModel::center, app.rs:1019-1046), centroid, trimmed box
+struct MultiModelViewerModel {
+    MultiModelViewerGaussianBuffers gaussian_buffers;
+    gsx_viewer* v_ = nullptr;
+    std::string key_;
+    // gsx_model_bounds: model space, Gaussian centres; filter = GSX_BOUNDS_* flags, trim_permille < 500.  After the last
+    // update_range of a load: model.center = viewer.models.at(key).bounds().center
+    ModelBounds bounds(uint32_t filter = 0, uint32_t trim_permille = 0) const {
+        const gsx_bounds_desc d{filter, trim_permille};
+        ModelBounds b;
+        check(gsx_model_bounds(v_, key_.c_str(), &d, &b));
+        return b;
+    }
+};
 
 class MultiModelViewer {
     gsx_viewer* v_ = nullptr;
@@ -241,7 +254,7 @@ public:
     MultiModelViewerModel& add_model(const std::string& key, size_t count) {  // new_empty + BindGroups::new + insert
         check(gsx_model_create(v_, key.c_str(), count, (gsx_sh_kind)sh, (gsx_cov3d_kind)cov3d));
         return models.emplace(key, MultiModelViewerModel{{GaussiansBuffer(v_, key), MaskBuffer(v_, key), SelectionBuffer(v_, key),
-                                                            GaussiansEditBuffer(v_, key)}}).first->second;
+                                                            GaussiansEditBuffer(v_, key)}, v_, key}).first->second;
     }
     void remove_model(const std::string& key) {  // scene.rs:2176
         check(gsx_model_remove(v_, key.c_str()));

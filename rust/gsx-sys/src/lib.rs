@@ -22,6 +22,9 @@ pub const GSX_GIZMO_CIRCLE_SEGMENTS: u32 = 64;
 pub const GSX_EDIT_ENABLED: u32 = 1;
 pub const GSX_EDIT_HIDDEN: u32 = 2;
 pub const GSX_EDIT_OVERRIDE_COLOR: u32 = 4;
+pub const GSX_BOUNDS_MASKED: u32 = 1;
+pub const GSX_BOUNDS_SKIP_HIDDEN: u32 = 2;
+pub const GSX_BOUNDS_SELECTED: u32 = 4;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -92,6 +95,17 @@ pub struct gsx_frame_stats {
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_gaussian_edit { pub flag: u32, pub color: [f32; 3], pub contrast: f32, pub exposure: f32, pub gamma: f32, pub alpha: f32 } // gs::GaussianEditPod
+/// which Gaussians gsx_model_bounds counts (GSX_BOUNDS_*), and the share (< 500) the trimmed box may leave outside at each end
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_bounds_desc { pub filter: u32, pub trim_permille: u32 }
+/// the result of gsx_model_bounds, 88 bytes; model space, Gaussian centres; `center` is GaussianSplattingModel::center (src/app.rs:1019-1046)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_model_bounds_t {
+    pub count: u64, pub n_nonfinite: u64, pub min: [f32; 3], pub max: [f32; 3],
+    pub center: [f32; 3], pub mean: [f32; 3], pub trim_min: [f32; 3], pub trim_max: [f32; 3],
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }
@@ -204,6 +218,8 @@ extern "C" {
     pub fn gsx_model_download_sorted(v: *mut gsx_viewer, key: *const c_char, indices: *mut u32, capacity: u64, out_n_visible: *mut u64) -> gsx_status;
     pub fn gsx_model_download_tile_lists(v: *mut gsx_viewer, key: *const c_char, tile_offsets: *mut u32, n_offsets: u64, list: *mut u32, capacity: u64) -> gsx_status;
     pub fn gsx_model_download_pod(v: *mut gsx_viewer, key: *const c_char, pos: *mut f32, color: *mut u32, sh: *mut f32, cov3d: *mut f32) -> gsx_status;
+    pub fn gsx_bounds_desc_default(d: *mut gsx_bounds_desc);
+    pub fn gsx_model_bounds(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_bounds_desc, out: *mut gsx_model_bounds_t) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

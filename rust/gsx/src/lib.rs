@@ -149,7 +149,20 @@ pub struct MultiModelViewerGaussianBuffers {
     pub gaussians_edit_buffer: GaussiansEditBuffer,
 }
 /// `gs::MultiModelViewerModel { gaussian_buffers, bind_groups }` (scene.rs:2133-2139); bind groups have no counterpart.
-pub struct MultiModelViewerModel { pub gaussian_buffers: MultiModelViewerGaussianBuffers }
+pub struct MultiModelViewerModel { pub gaussian_buffers: MultiModelViewerGaussianBuffers, v: *mut sys::gsx_viewer, key: CString }
+/// The result of `MultiModelViewerModel::bounds`: `center` is `GaussianSplattingModel::center` (app.rs:1019-1046).
+pub type ModelBounds = sys::gsx_model_bounds_t;
+impl MultiModelViewerModel {
+    /// `gsx_model_bounds`: box, centre, centroid and trimmed box of the model's Gaussian centres, in model space, computed on the
+    /// device.  `filter`: `sys::GSX_BOUNDS_*` flags; `trim_permille` < 500.  After the last `update_range` of a load:
+    /// `model.center = viewer.models[key].bounds(0, 0)?.center.into()` (the reference leaves it `Vec3::ZERO`).
+    pub fn bounds(&self, filter: u32, trim_permille: u32) -> Result<ModelBounds, Error> {
+        let desc = sys::gsx_bounds_desc { filter, trim_permille };
+        let mut out = ModelBounds::default();
+        check(unsafe { sys::gsx_model_bounds(self.v, self.key.as_ptr(), &desc, &mut out) })?;
+        Ok(out)
+    }
+}
 
 pub struct Preprocessor(*mut sys::gsx_viewer);
 impl Preprocessor {
@@ -243,8 +256,8 @@ impl<G: GaussianPod> MultiModelViewer<G> {
         self.models.insert(key.to_owned(), MultiModelViewerModel { gaussian_buffers: MultiModelViewerGaussianBuffers {
             gaussians_buffer: GaussiansBuffer { v, key: k.clone() },
             mask_buffer: MaskBuffer { v, key: k.clone(), words: (count + 31) / 32 },
-            gaussians_edit_buffer: GaussiansEditBuffer { v, key: k, n: count },
-        } });
+            gaussians_edit_buffer: GaussiansEditBuffer { v, key: k.clone(), n: count },
+        }, v, key: k });
         Ok(())
     }
     /// `viewer.remove_model(&key)` (scene.rs:2176)

@@ -71,6 +71,9 @@ pub const GSX_GIZMO_CIRCLE_SEGMENTS: u32 = 64;
 pub const GSX_EDIT_ENABLED: u32 = 1;
 pub const GSX_EDIT_HIDDEN: u32 = 2;
 pub const GSX_EDIT_OVERRIDE_COLOR: u32 = 4;
+pub const GSX_BOUNDS_MASKED: u32 = 1;
+pub const GSX_BOUNDS_SKIP_HIDDEN: u32 = 2;
+pub const GSX_BOUNDS_SELECTED: u32 = 4;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -141,6 +144,17 @@ pub struct gsx_frame_stats {
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_gaussian_edit { pub flag: u32, pub color: [f32; 3], pub contrast: f32, pub exposure: f32, pub gamma: f32, pub alpha: f32 } // gs::GaussianEditPod
+/// which Gaussians gsx_model_bounds counts (GSX_BOUNDS_*), and the share (< 500) the trimmed box may leave outside at each end
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_bounds_desc { pub filter: u32, pub trim_permille: u32 }
+/// the result of gsx_model_bounds, 88 bytes; model space, Gaussian centres; `center` is GaussianSplattingModel::center (src/app.rs:1019-1046)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_model_bounds_t {
+    pub count: u64, pub n_nonfinite: u64, pub min: [f32; 3], pub max: [f32; 3],
+    pub center: [f32; 3], pub mean: [f32; 3], pub trim_min: [f32; 3], pub trim_max: [f32; 3],
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }

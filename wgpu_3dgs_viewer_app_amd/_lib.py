@@ -46,6 +46,7 @@ EXPORTS = (
     "gsx_debug_set_launch_graphs", "gsx_debug_launch_count", "gsx_debug_device_bytes", "gsx_debug_download_lane_framebuffer", "gsx_viewer_launch_stats", "gsx_debug_tile_profile",
     "gsx_viewer_comm_init_custom_v", "gsx_shard_set_band_edges", "gsx_shard_get_band_edges", "gsx_shard_set_balance",
     "gsx_viewer_comm_info",
+    "gsx_bounds_desc_default", "gsx_model_bounds",
 )
 
 
@@ -65,6 +66,21 @@ class MaskGizmo(C.Structure):
     """``gsx_mask_gizmo``: a world-space mask shape, its straight RGBA colour and a line width (64 bytes)."""
     _fields_ = [("kind", C.c_uint32), ("pos", C.c_float * 3), ("quat_xyzw", C.c_float * 4), ("scale", C.c_float * 3),
                 ("color", C.c_float * 4), ("line_width", C.c_float)]
+
+
+#: gsx_bounds_desc.filter
+GSX_BOUNDS_MASKED, GSX_BOUNDS_SKIP_HIDDEN, GSX_BOUNDS_SELECTED = 1, 2, 4
+
+
+class BoundsDesc(C.Structure):
+    """``gsx_bounds_desc`` (8 bytes): which Gaussians count, and how much of them the trimmed box may leave outside."""
+    _fields_ = [("filter", C.c_uint32), ("trim_permille", C.c_uint32)]
+
+
+class ModelBounds(C.Structure):
+    """``gsx_model_bounds_t`` (88 bytes)."""
+    _fields_ = [("count", C.c_uint64), ("n_nonfinite", C.c_uint64), ("min", C.c_float * 3), ("max", C.c_float * 3),
+                ("center", C.c_float * 3), ("mean", C.c_float * 3), ("trim_min", C.c_float * 3), ("trim_max", C.c_float * 3)]
 
 
 class GaussianEdit(C.Structure):
@@ -292,6 +308,8 @@ def load() -> C.CDLL:
         "gsx_viewer_launch_stats": ([vp, C.POINTER(LaunchStats), u32], C.c_int32),
         "gsx_set_pass_timing": ([vp, u32], C.c_int32),
         "gsx_get_pass_timing": ([vp, f32p, u32p], C.c_int32),
+        "gsx_bounds_desc_default": ([C.POINTER(BoundsDesc)], None),
+        "gsx_model_bounds": ([vp, cp, C.POINTER(BoundsDesc), C.POINTER(ModelBounds)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)
     for name, (args, res) in sig.items():

@@ -164,6 +164,28 @@ def orbit_pose(index: int, poses: int = 240, radius: float = 6.0, height: float 
     return CameraOrbitControl(target=np.zeros(3, f32), pos=pos)
 
 
+def frame_bounds(lo, hi, vertical_fov: float, aspect_ratio: float, direction=(0.0, 0.0, 1.0)) -> CameraOrbitControl:
+    """The "fit view" of a box (``MultiModelViewerModel.bounds``: ``min`` / ``max``, or the trimmed box; in world space: apply
+    the model transform to the box first): an orbit camera that looks along ``direction`` at the box centre from the distance at
+    which the box's bounding sphere fits both fields of view.
+
+        c = (lo + hi) / 2        r = |hi - lo| / 2        half_v = vertical_fov / 2        half_h = atan(aspect_ratio * tan(half_v))
+        d = r / sin(min(half_v, half_h))        target = c        pos = c - d * direction / |direction|
+
+    A sphere of radius r at distance d subtends the half-angle asin(r / d), so it touches the narrower of the two frusta's side
+    planes; every corner of the box lies on or in the sphere.  A box of zero size has no distance of its own (r = 0): the camera
+    then stands at d = 1, a finite pose.  ``direction`` must not be parallel to the up vector (0, 1, 0) of ``view()``."""
+    lo64, hi64 = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    c = 0.5 * (lo64 + hi64)
+    r = 0.5 * float(np.linalg.norm(hi64 - lo64))
+    half_v = 0.5 * float(vertical_fov)
+    half_h = math.atan(float(aspect_ratio) * math.tan(half_v))
+    d = r / math.sin(min(half_v, half_h)) if r > 0.0 else 1.0
+    u = np.asarray(direction, np.float64).reshape(3)
+    u = u / np.linalg.norm(u)
+    return CameraOrbitControl(target=c.astype(f32), pos=(c - d * u).astype(f32), vertical_fov=float(vertical_fov))
+
+
 class PrecomputedCamera:
     """A camera whose view / projection matrices were evaluated once (``CameraTrait`` as the viewer sees it: two
     matrices).  The frame loop of bench.py prepares the orbit's 240 cameras before it starts the clock."""

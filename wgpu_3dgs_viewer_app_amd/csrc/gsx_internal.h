@@ -6,6 +6,7 @@
 
 #include "../../include/gsx.h"
 #include "gsx_launch.h"
+#include "bounds_math.h"
 #include "gizmo_math.h"
 #include "toolset_math.h"
 
@@ -891,6 +892,29 @@ struct MaskProgram {
 };
 hipError_t launch_mask_evaluate(hipStream_t s, const float4* pc, uint32_t n, const MaskProgram& prog, uint32_t* mask);
 void quat_to_rows(const float q[4], float r[9]);
+
+// Model bounds (kernels_bounds.hip; gsx_model_bounds).  The filter: the bit planes a Gaussian must pass, nullptr = absent = passes
+// (mask: bit set = kept; selection: bit set = selected; edited + edit_a: dropped where the stored flag has ENABLED and HIDDEN).
+struct BoundsFilter {
+    const uint32_t* mask;
+    const uint32_t* selection;
+    const uint32_t* edited;
+    const float4* edit_a;
+};
+struct BoundsPartial {  // one per workgroup of k_bounds_reduce; 64 bytes
+    float mn[3], mx[3];
+    uint64_t count, nonfinite;
+    double sum[3];
+};
+constexpr uint32_t kBoundsMaxGroups = 2048;   // most workgroups (= partials) of k_bounds_reduce: eight per CU
+constexpr uint32_t kBoundsHistGroups = 1024;  // ... of k_bounds_hist
+uint32_t bounds_reduce_groups(uint64_t n);    // the partials launch_bounds_reduce leaves for a model of n Gaussians
+hipError_t launch_bounds_reduce(hipStream_t s, const float4* pc, uint64_t n, const BoundsFilter& f, BoundsPartial* partials);  // n > 0
+hipError_t launch_bounds_finish(hipStream_t s, const BoundsPartial* partials, uint32_t n_partials, bool clear_hist, gsx_model_bounds_t* out,
+                                uint32_t* hist);
+// the histogram over [out->min, out->max] and its scan: writes out->trim_min / trim_max (n > 0; hist: 3 * kBoundsBins words, cleared)
+hipError_t launch_bounds_trim(hipStream_t s, const float4* pc, uint64_t n, const BoundsFilter& f, uint32_t trim_permille,
+                              gsx_model_bounds_t* out, uint32_t* hist);
 
 // Compositing and resolve.
 // carry: continue from the (C, T) already in fb (later slabs / models behind); done: saturated-tile bitmap

@@ -496,6 +496,9 @@ struct gsx_viewer {
     bool tile_order_on = true;           // GSX_TILE_ORDER=0: the block compositor takes its tiles in index order (A/B)
     int sorted_records = -1;             // GSX_SORTED_RECORDS=0 / 1: never / always carry the block lists' records through the block sort (-1: by list length)
     gsx::LaunchTrace* trace = nullptr;  // owned; created by the first TraceScope on this viewer (gsx_graph.cpp)
+    // gsx_model_bounds (gsx_api_bounds.cpp; owner only): the 88-byte result, the partials of k_bounds_reduce and the trimmed box's
+    // histograms, allocated by the first call and reused.  Nothing a frame reads
+    DevBuf bounds_ws;
 };
 
 namespace gsx {

@@ -19,6 +19,7 @@ Every call goes into libgsx.so (HIP kernels); nothing here computes pixels.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import enum
 from typing import Iterable, Sequence
 
@@ -269,11 +270,41 @@ class MultiModelViewerGaussianBuffers:
         self.gaussians_edit_buffer = GaussiansEditBuffer(viewer, key)
 
 
+@dataclasses.dataclass
+class ModelBounds:
+    """``gsx_model_bounds_t``: what ``MultiModelViewerModel.bounds`` returns.  Model space, Gaussian centres only; the vectors
+    are float32[3].  ``center`` is ``GaussianSplattingModel::center`` (src/app.rs:1019-1046)."""
+
+    count: int
+    n_nonfinite: int
+    min: np.ndarray
+    max: np.ndarray
+    center: np.ndarray
+    mean: np.ndarray
+    trim_min: np.ndarray
+    trim_max: np.ndarray
+
+
 class MultiModelViewerModel:
     """``gs::MultiModelViewerModel {gaussian_buffers, bind_groups}`` (src/tab/scene.rs:2133-2139)."""
 
     def __init__(self, viewer: "MultiModelViewer", key: str):
         self.gaussian_buffers = MultiModelViewerGaussianBuffers(viewer, key)
+        self._v, self._key = viewer, key
+
+    def bounds(self, masked: bool = False, skip_hidden: bool = False, selected: bool = False, trim_permille: int = 0) -> ModelBounds:
+        """``gsx_model_bounds``: the box, its centre, the centroid and the trimmed box of the model's Gaussian centres, computed on
+        the device from the resident positions.  ``masked``: only what the model's mask keeps; ``skip_hidden``: without the
+        Gaussians whose stored edit hides them; ``selected``: only the selection; ``trim_permille`` (< 500): per axis the trimmed box
+        leaves at most ``count * trim_permille // 1000`` of the counted Gaussians below it and as many above.  After the last
+        ``update_range`` of a load, ``model.center = viewer.models[key].bounds().center`` (the reference leaves it zero)."""
+        desc = _lib.BoundsDesc((_lib.GSX_BOUNDS_MASKED if masked else 0) | (_lib.GSX_BOUNDS_SKIP_HIDDEN if skip_hidden else 0)
+                               | (_lib.GSX_BOUNDS_SELECTED if selected else 0), int(trim_permille))
+        out = _lib.ModelBounds()
+        _lib.check(self._v._L.gsx_model_bounds(self._v._h, self._key.encode(), C.byref(desc), C.byref(out)))
+        vec = lambda a: np.array(a[:], np.float32)  # noqa: E731
+        return ModelBounds(int(out.count), int(out.n_nonfinite), vec(out.min), vec(out.max), vec(out.center), vec(out.mean),
+                           vec(out.trim_min), vec(out.trim_max))
 
 
 class _Preprocessor:
