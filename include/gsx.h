@@ -393,6 +393,35 @@ typedef struct gsx_model_bounds_t {
 void gsx_bounds_desc_default(gsx_bounds_desc* d); /* filter 0, trim_permille 0 */
 gsx_status gsx_model_bounds(gsx_viewer* v, const char* key, const gsx_bounds_desc* desc, gsx_model_bounds_t* out);
 
+/* ---- model extract: part of a model becomes a new model, on the device (spec/RENDER_SPEC.md §12 [BUILD-SPEC]; the reference has no
+ *      counterpart).  A stable stream compaction of src's resident planes: what a host does with a mask, a selection or hidden edits
+ *      beyond hiding Gaussians every frame ("separate selection into a model", "apply the mask").
+ *      Kept set: a Gaussian passes if it passes every GSX_BOUNDS_* flag set in `filter`, with gsx_model_bounds' exact meaning: no
+ *      mask = all pass, no selection = none pass, GSX_BOUNDS_SKIP_HIDDEN reads the stored edit flag whatever gsx_model_show_unedited
+ *      says.  GSX_EXTRACT_INVERT complements that conjunction over [0, n).  Bits of the last mask or selection word at or above n
+ *      never count (a host may leave garbage there).  Non-finite positions are copied like any other.
+ *      Order: kept Gaussians keep their relative order: the Gaussian at dst index j is the j-th kept one of src.  The result is the
+ *      same bits on every call.
+ *      Carried: every resident pod plane as stored bits (positions and colours, the covariance planes, the SH planes of the model's
+ *      kind, the shade records): nothing is dequantised or requantised, dst has src's sh and cov3d kinds.  dst gets src's model
+ *      transform.  Unless GSX_EXTRACT_DROP_EDITS is set, and if src has edit records, dst gets the kept Gaussians' stored edit records
+ *      and edited bits; it gets no edit buffers if src has none.  dst has no mask (everything kept) and no selection, show_unedited is
+ *      off, and it starts without speculation windows, like any new model.
+ *      src is not written: its planes, mask, selection, edits and next frame are what they were.
+ *      Empty result: if nothing is kept the call returns GSX_OK with *out_count == 0 and creates no model.
+ *      Errors: a null viewer, key, desc or out, unknown filter or flag bits, a dst_key that exists or equals src_key:
+ *      GSX_ERR_INVALID_ARG; unknown src_key: GSX_ERR_NOT_FOUND; a viewer with a communicator initialised, or a sharded src:
+ *      GSX_ERR_UNSUPPORTED (index sharding assumes every rank knows the global count); allocation failure: GSX_ERR_OOM, with no dst
+ *      left behind.
+ *      Ordering: the call runs on the viewer's stream, behind every frame in flight on the lanes and every upload enqueued before it
+ *      (as every call that touches model data: "frames in flight" above).  It waits once, for the kept count that sizes dst, then
+ *      enqueues the copy.  When it returns, dst can be preprocessed, sorted and rendered, on lanes too. ---- */
+#define GSX_EXTRACT_INVERT     1u  /* keep exactly the Gaussians the filter rejects */
+#define GSX_EXTRACT_DROP_EDITS 2u  /* the new model starts without edit records */
+typedef struct gsx_extract_desc { uint32_t filter; uint32_t flags; } gsx_extract_desc; /* filter: GSX_BOUNDS_* bits */
+void gsx_extract_desc_default(gsx_extract_desc* d); /* filter 0, flags 0: a copy of the whole model */
+gsx_status gsx_model_extract(gsx_viewer* v, const char* src_key, const char* dst_key, const gsx_extract_desc* desc, uint64_t* out_count);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

@@ -256,6 +256,18 @@ public:
         return models.emplace(key, MultiModelViewerModel{{GaussiansBuffer(v_, key), MaskBuffer(v_, key), SelectionBuffer(v_, key),
                                                             GaussiansEditBuffer(v_, key)}, v_, key}).first->second;
     }
+    // gsx_model_extract: the Gaussians of `src_key` that pass `filter` (GSX_BOUNDS_* flags; flags: GSX_EXTRACT_INVERT, _DROP_EDITS) become
+    // the new model `dst_key`, in their order, on the device, as stored bits.  Returns the number kept; 0 creates no model.
+    // "Separate selection into a model": extract(k, a, GSX_BOUNDS_SELECTED), extract(k, b, GSX_BOUNDS_SELECTED, GSX_EXTRACT_INVERT).
+    uint64_t extract(const std::string& src_key, const std::string& dst_key, uint32_t filter = 0, uint32_t flags = 0) {
+        const gsx_extract_desc d{filter, flags};
+        uint64_t count = 0;
+        check(gsx_model_extract(v_, src_key.c_str(), dst_key.c_str(), &d, &count));
+        if (count)
+            models.emplace(dst_key, MultiModelViewerModel{{GaussiansBuffer(v_, dst_key), MaskBuffer(v_, dst_key), SelectionBuffer(v_, dst_key),
+                                                           GaussiansEditBuffer(v_, dst_key)}, v_, dst_key});
+        return count;
+    }
     void remove_model(const std::string& key) {  // scene.rs:2176
         check(gsx_model_remove(v_, key.c_str()));
         models.erase(key);

@@ -260,6 +260,24 @@ impl<G: GaussianPod> MultiModelViewer<G> {
         }, v, key: k });
         Ok(())
     }
+    /// `gsx_model_extract`: the Gaussians of `src_key` that pass `filter` (`sys::GSX_BOUNDS_*`; `flags`: `sys::GSX_EXTRACT_INVERT`,
+    /// `sys::GSX_EXTRACT_DROP_EDITS`) become the new model `dst_key`, in their order, on the device, as stored bits.  Returns the
+    /// number kept; 0 creates no model.  "Apply the mask": `extract(k, a, GSX_BOUNDS_MASKED | GSX_BOUNDS_SKIP_HIDDEN, 0)`, `remove_model(k)`.
+    pub fn extract(&mut self, src_key: &str, dst_key: &str, filter: u32, flags: u32) -> Result<u64, Error> {
+        let (s, k) = (CString::new(src_key).unwrap(), CString::new(dst_key).unwrap());
+        let desc = sys::gsx_extract_desc { filter, flags };
+        let mut count = 0u64;
+        check(unsafe { sys::gsx_model_extract(self.handle.0, s.as_ptr(), k.as_ptr(), &desc, &mut count) })?;
+        if count > 0 {
+            let (v, n) = (self.handle.0, count as usize);
+            self.models.insert(dst_key.to_owned(), MultiModelViewerModel { gaussian_buffers: MultiModelViewerGaussianBuffers {
+                gaussians_buffer: GaussiansBuffer { v, key: k.clone() },
+                mask_buffer: MaskBuffer { v, key: k.clone(), words: (n + 31) / 32 },
+                gaussians_edit_buffer: GaussiansEditBuffer { v, key: k.clone(), n },
+            }, v, key: k });
+        }
+        Ok(count)
+    }
     /// `viewer.remove_model(&key)` (scene.rs:2176)
     pub fn remove_model(&mut self, key: &str) {
         let k = CString::new(key).unwrap();

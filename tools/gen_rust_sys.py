@@ -74,6 +74,8 @@ pub const GSX_EDIT_OVERRIDE_COLOR: u32 = 4;
 pub const GSX_BOUNDS_MASKED: u32 = 1;
 pub const GSX_BOUNDS_SKIP_HIDDEN: u32 = 2;
 pub const GSX_BOUNDS_SELECTED: u32 = 4;
+pub const GSX_EXTRACT_INVERT: u32 = 1;
+pub const GSX_EXTRACT_DROP_EDITS: u32 = 2;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -155,6 +157,10 @@ pub struct gsx_model_bounds_t {
     pub count: u64, pub n_nonfinite: u64, pub min: [f32; 3], pub max: [f32; 3],
     pub center: [f32; 3], pub mean: [f32; 3], pub trim_min: [f32; 3], pub trim_max: [f32; 3],
 }
+/// which Gaussians gsx_model_extract keeps (filter: GSX_BOUNDS_*) and how (flags: GSX_EXTRACT_*)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_extract_desc { pub filter: u32, pub flags: u32 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }

@@ -47,6 +47,7 @@ EXPORTS = (
     "gsx_viewer_comm_init_custom_v", "gsx_shard_set_band_edges", "gsx_shard_get_band_edges", "gsx_shard_set_balance",
     "gsx_viewer_comm_info",
     "gsx_bounds_desc_default", "gsx_model_bounds",
+    "gsx_extract_desc_default", "gsx_model_extract",
 )
 
 
@@ -81,6 +82,15 @@ class ModelBounds(C.Structure):
     """``gsx_model_bounds_t`` (88 bytes)."""
     _fields_ = [("count", C.c_uint64), ("n_nonfinite", C.c_uint64), ("min", C.c_float * 3), ("max", C.c_float * 3),
                 ("center", C.c_float * 3), ("mean", C.c_float * 3), ("trim_min", C.c_float * 3), ("trim_max", C.c_float * 3)]
+
+
+#: gsx_extract_desc.flags (its filter takes the GSX_BOUNDS_* bits)
+GSX_EXTRACT_INVERT, GSX_EXTRACT_DROP_EDITS = 1, 2
+
+
+class ExtractDesc(C.Structure):
+    """``gsx_extract_desc`` (8 bytes): which Gaussians the new model keeps (``GSX_BOUNDS_*``), and ``GSX_EXTRACT_*`` flags."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class GaussianEdit(C.Structure):
@@ -310,6 +320,8 @@ def load() -> C.CDLL:
         "gsx_get_pass_timing": ([vp, f32p, u32p], C.c_int32),
         "gsx_bounds_desc_default": ([C.POINTER(BoundsDesc)], None),
         "gsx_model_bounds": ([vp, cp, C.POINTER(BoundsDesc), C.POINTER(ModelBounds)], C.c_int32),
+        "gsx_extract_desc_default": ([C.POINTER(ExtractDesc)], None),
+        "gsx_model_extract": ([vp, cp, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)
     for name, (args, res) in sig.items():

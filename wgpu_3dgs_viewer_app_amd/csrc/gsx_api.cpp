@@ -402,9 +402,12 @@ gsx_status gsx_viewer_set_spec_params(gsx_viewer* v, const gsx_spec_params* p) {
     return GSX_OK;
 }
 
-gsx_status gsx_model_create(gsx_viewer* v, const char* key, uint64_t count, gsx_sh_kind sh, gsx_cov3d_kind cov3d) {
-    gsx_status st = viewer_bind(v);
-    if (st) return st;
+}  // extern "C"
+// gsx_model_create's body, shared with gsx_model_extract (gsx_api_extract.cpp): the caller has bound the viewer.  zero_planes: a
+// fresh model is all-zero Gaussians; a caller that writes every plane of every Gaussian itself skips the fill.  The model is
+// inserted last: a failure leaves none behind.
+namespace gsx {
+gsx_status model_create(gsx_viewer* v, const char* key, uint64_t count, gsx_sh_kind sh, gsx_cov3d_kind cov3d, bool zero_planes, Model** out) {
     if (!key) return fail(GSX_ERR_INVALID_ARG, "gsx_model_create: key is null");
     if (count >= 0xFFFFFFF0ull) return fail(GSX_ERR_INVALID_ARG, "gsx_model_create: count %llu too large", (unsigned long long)count);
     if (v->models.count(key)) return fail(GSX_ERR_INVALID_ARG, "gsx_model_create: model '%s' exists", key);
@@ -449,10 +452,20 @@ gsx_status gsx_model_create(gsx_viewer* v, const char* key, uint64_t count, gsx_
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&m->h_counters), sizeof(Counters), hipHostMallocDefault));
     HIPCHK(gsx::op::MemsetAsync(m->counters.p, 0, sizeof(Counters), v->stream));
     // a fresh model is all-zero Gaussians (new_empty) and fully unmasked (MaskOpTree::Reset, scene.rs:2124-2131)
-    for (DevBuf* b : {&m->pc, &m->cov_a, &m->cov_b, &m->cov_h, &m->cov_h2, &m->sh4, &m->sh1, &m->sh_h, &m->sh_q, &m->sh_aos})
-        if (b->p) HIPCHK(gsx::op::MemsetAsync(b->p, 0, b->bytes, v->stream));
+    if (zero_planes)
+        for (DevBuf* b : {&m->pc, &m->cov_a, &m->cov_b, &m->cov_h, &m->cov_h2, &m->sh4, &m->sh1, &m->sh_h, &m->sh_q, &m->sh_aos})
+            if (b->p) HIPCHK(gsx::op::MemsetAsync(b->p, 0, b->bytes, v->stream));
+    if (out) *out = m.get();
     v->models[key] = std::move(m);
     return GSX_OK;
+}
+}  // namespace gsx
+extern "C" {
+
+gsx_status gsx_model_create(gsx_viewer* v, const char* key, uint64_t count, gsx_sh_kind sh, gsx_cov3d_kind cov3d) {
+    gsx_status st = viewer_bind(v);
+    if (st) return st;
+    return model_create(v, key, count, sh, cov3d, true, nullptr);
 }
 
 gsx_status gsx_model_remove(gsx_viewer* v, const char* key) {

@@ -7,6 +7,7 @@
 #include "../../include/gsx.h"
 #include "gsx_launch.h"
 #include "bounds_math.h"
+#include "extract_math.h"
 #include "gizmo_math.h"
 #include "toolset_math.h"
 
@@ -915,6 +916,40 @@ hipError_t launch_bounds_finish(hipStream_t s, const BoundsPartial* partials, ui
 // the histogram over [out->min, out->max] and its scan: writes out->trim_min / trim_max (n > 0; hist: 3 * kBoundsBins words, cleared)
 hipError_t launch_bounds_trim(hipStream_t s, const float4* pc, uint64_t n, const BoundsFilter& f, uint32_t trim_permille,
                               gsx_model_bounds_t* out, uint32_t* hist);
+
+// Model extract (kernels_extract.hip; gsx_model_extract).  The filter, with gsx_model_bounds' meaning: the bit planes a Gaussian must
+// pass, nullptr = absent = passes — but for `select_none` (SELECTED asked of a model without a selection: none pass); `invert` keeps
+// exactly the Gaussians that do not pass.
+struct ExtractFilter {
+    const uint32_t* mask;
+    const uint32_t* selection;
+    const uint32_t* edited;
+    const float4* edit_a;
+    uint32_t select_none, invert;
+};
+// Everything that is carried, as stored bits: the planes of the model's pod kind (the others nullptr), the shade records, and the
+// edit planes (all three, or none when no edit records are carried).
+struct ExtractPlanes {
+    uint4* pc;
+    uint4* cov_a;
+    uint2* cov_b;
+    uint2* cov_h;
+    uint32_t* cov_h2;
+    uint4* sh4;
+    uint32_t* sh1;
+    uint4* sh_h;
+    uint4* sh_q;
+    uint4* sh_aos;
+    uint32_t* edited;
+    uint4* edit_a;
+    uint4* edit_b;
+};
+// keep: ceil(n / 32) words; partials, bases: extract_groups(n) words; total: one 64-bit word, written by the scan (n > 0)
+hipError_t launch_extract_keep(hipStream_t s, uint64_t n, const ExtractFilter& f, uint32_t* keep, uint32_t* partials);
+hipError_t launch_extract_scan(hipStream_t s, const uint32_t* partials, uint64_t n_partials, uint32_t* bases, uint64_t* total);
+// src is only read.  dst's planes hold n_dst = the scan's total Gaussians; dst.edited (when carried) is zeroed
+hipError_t launch_extract_scatter(hipStream_t s, int sh_kind, int cov_kind, uint64_t n_src, uint64_t n_dst, const uint32_t* keep, const uint32_t* bases,
+                                  const ExtractPlanes& src, const ExtractPlanes& dst);
 
 // Compositing and resolve.
 // carry: continue from the (C, T) already in fb (later slabs / models behind); done: saturated-tile bitmap

@@ -499,6 +499,9 @@ struct gsx_viewer {
     // gsx_model_bounds (gsx_api_bounds.cpp; owner only): the 88-byte result, the partials of k_bounds_reduce and the trimmed box's
     // histograms, allocated by the first call and reused.  Nothing a frame reads
     DevBuf bounds_ws;
+    // gsx_model_extract (gsx_api_extract.cpp; owner only): the total, the keep words (n / 8 bytes) and two words per 1024 Gaussians
+    // (popcount partials, their scan), allocated by the first call and grown when a larger model is extracted from.  Nothing a frame reads
+    DevBuf extract_ws;
 };
 
 namespace gsx {
@@ -689,6 +692,8 @@ gsx_status shade_admitted(gsx_viewer* v, Model* m, const LateProjection& late);
 gsx_status ensure_record_capacity(Model* m, uint64_t count);
 gsx_status ensure_sortbin_capacity(Model* m, uint64_t count);
 gsx_status ensure_import_capacity(Model* m, uint64_t count);
+// gsx_api.cpp: gsx_model_create's body (the viewer is bound): the new model, zero-filled or not, inserted under `key` and returned in *out
+gsx_status model_create(gsx_viewer* v, const char* key, uint64_t count, gsx_sh_kind sh, gsx_cov3d_kind cov3d, bool zero_planes, Model** out);
 gsx_status ensure_selection(gsx_viewer* v, Model* m);
 gsx_status ensure_edit_buffers(gsx_viewer* v, Model* m);
 

@@ -306,6 +306,20 @@ class MultiModelViewerModel:
         return ModelBounds(int(out.count), int(out.n_nonfinite), vec(out.min), vec(out.max), vec(out.center), vec(out.mean),
                            vec(out.trim_min), vec(out.trim_max))
 
+    def extract(self, dst_key: str, filter: int = 0, invert: bool = False, drop_edits: bool = False) -> int:  # noqa: A002
+        """``gsx_model_extract``: the Gaussians of this model that pass ``filter`` (``_lib.GSX_BOUNDS_*`` bits, with ``bounds``'
+        meaning; ``invert``: exactly those that do not) become the new model ``dst_key``, in their order, on the device: every
+        resident plane as stored bits, the model transform, and the stored edit records unless ``drop_edits``.  Returns the number
+        kept; 0 creates no model.  The new model is ``viewer.models[dst_key]``.  "Separate selection into a model" is
+        ``extract(a, SELECTED)`` and ``extract(b, SELECTED, invert=True)``; "apply the mask" is ``extract(a, MASKED | SKIP_HIDDEN)``
+        and ``viewer.remove_model`` of this one."""
+        desc = _lib.ExtractDesc(int(filter), (_lib.GSX_EXTRACT_INVERT if invert else 0) | (_lib.GSX_EXTRACT_DROP_EDITS if drop_edits else 0))
+        count = C.c_uint64()
+        _lib.check(self._v._L.gsx_model_extract(self._v._h, self._key.encode(), dst_key.encode(), C.byref(desc), C.byref(count)))
+        if count.value:
+            self._v.models[dst_key] = MultiModelViewerModel(self._v, dst_key)
+        return int(count.value)
+
 
 class _Preprocessor:
     def __init__(self, v):
