@@ -422,6 +422,40 @@ typedef struct gsx_extract_desc { uint32_t filter; uint32_t flags; } gsx_extract
 void gsx_extract_desc_default(gsx_extract_desc* d); /* filter 0, flags 0: a copy of the whole model */
 gsx_status gsx_model_extract(gsx_viewer* v, const char* src_key, const char* dst_key, const gsx_extract_desc* desc, uint64_t* out_count);
 
+/* ---- model merge: several models become one new model, on the device, their model transforms baked into the Gaussians
+ *      (spec/RENDER_SPEC.md §13 [BUILD-SPEC]; the reference has no counterpart: it layers models by centre distance and never merges
+ *      them).  The way back from gsx_model_extract: pieces that were split off and moved with gsx_update_model_transform become one
+ *      model again, which sorts Gaussian by Gaussian where the pieces interpenetrate and pays one frame pipeline.
+ *      Kept set: per source exactly gsx_model_extract's: desc->filter and desc->flags (GSX_EXTRACT_INVERT, GSX_EXTRACT_DROP_EDITS)
+ *      apply to every source with that call's meaning (no mask = all pass, no selection = none pass, bits at or above n ignored).
+ *      Order: the sources in the order given, inside a source the kept Gaussians in ascending index.  out_counts[s] (nullable) is the
+ *      kept count of source s, *out_total their sum.  A key may appear twice: the model is then instantiated twice.  The result is
+ *      the same bits on every call.
+ *      Identity sources: a source whose model transform is exactly pos 0, scale 1, quat (0,0,0,1) or (0,0,0,-1) contributes its planes
+ *      as stored bits, as gsx_model_extract would.
+ *      Baked sources: every other source is dequantised exactly, baked and quantised again into the pod kind (§2b), so a Half or
+ *      Norm8 source is quantised twice.  Positions p' = R_m (s_m * p) + t_m and covariances S' = M S M^T, M = R_m diag(s_m), in
+ *      float32 with the float32 R_m the frame uses; the SH coefficients of bands 1..3 are multiplied by the band's rotation matrix
+ *      of R_m (computed on the host in float64 from the normalised quaternion, rounded to float32) — the library evaluates SH in model
+ *      space, so a rotation that is baked has to turn the coefficients too; a scale, negative components included, needs nothing.
+ *      The colour word (DC and alpha) is carried.  The shade records are written to agree with the planes word for word.
+ *      Pod kinds: every source must have the first source's sh and cov3d kinds, and dst takes them (GSX_ERR_INVALID_ARG otherwise).
+ *      Edits: unless GSX_EXTRACT_DROP_EDITS is set, dst gets edit buffers if any source has edit records; kept Gaussians of such a
+ *      source carry their stored records and edited bits (edits are colour operations), those of the other sources read as never
+ *      edited.  dst has the identity transform, no mask, no selection, show_unedited off and no speculation windows.
+ *      The sources are not written: their planes, masks, selections, edits, transforms and next frames are what they were.
+ *      Empty result: if nothing is kept anywhere the call returns GSX_OK with *out_total == 0 and creates no model.
+ *      Errors: a null viewer, key array, key, desc or out_total, n_src of 0 or above GSX_MERGE_MAX_SOURCES, unknown filter or flag
+ *      bits, a dst_key that exists or equals a source, mixed pod kinds, a source transform with a non-finite component or a zero
+ *      quaternion: GSX_ERR_INVALID_ARG; an unknown source: GSX_ERR_NOT_FOUND (the message names it); a viewer with a communicator, or
+ *      a sharded source: GSX_ERR_UNSUPPORTED; allocation failure: GSX_ERR_OOM, with no dst left behind.
+ *      Ordering: as gsx_model_extract, on the viewer's stream behind the lanes' frames.  The keep and scan passes of all sources are
+ *      enqueued first; the call waits once, for the n_src counts that size dst, then enqueues the copies.  When it returns, dst can
+ *      be preprocessed, sorted and rendered, on lanes too. ---- */
+#define GSX_MERGE_MAX_SOURCES 64u
+gsx_status gsx_model_merge(gsx_viewer* v, const char* const* src_keys, uint32_t n_src, const char* dst_key,
+                           const gsx_extract_desc* desc, uint64_t* out_counts /* n_src entries, nullable */, uint64_t* out_total);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

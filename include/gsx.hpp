@@ -268,6 +268,23 @@ public:
                                                            GaussiansEditBuffer(v_, dst_key)}, v_, dst_key});
         return count;
     }
+    // gsx_model_merge: the Gaussians of the models `src_keys` that pass `filter` become the one new model `dst_key`, source after source,
+    // each source's model transform baked into its Gaussians (an identity source travels as stored bits); dst has the identity transform.
+    // Returns the total kept (0 creates no model); counts (optional) receives one kept count per source.
+    uint64_t merge(const std::vector<std::string>& src_keys, const std::string& dst_key, uint32_t filter = 0, uint32_t flags = 0,
+                   std::vector<uint64_t>* counts = nullptr) {
+        const gsx_extract_desc d{filter, flags};
+        std::vector<const char*> keys;
+        for (const std::string& k : src_keys) keys.push_back(k.c_str());
+        std::vector<uint64_t> per(src_keys.size() ? src_keys.size() : 1);
+        uint64_t total = 0;
+        check(gsx_model_merge(v_, keys.data(), (uint32_t)keys.size(), dst_key.c_str(), &d, per.data(), &total));
+        if (total)
+            models.emplace(dst_key, MultiModelViewerModel{{GaussiansBuffer(v_, dst_key), MaskBuffer(v_, dst_key), SelectionBuffer(v_, dst_key),
+                                                           GaussiansEditBuffer(v_, dst_key)}, v_, dst_key});
+        if (counts) counts->assign(per.begin(), per.begin() + src_keys.size());
+        return total;
+    }
     void remove_model(const std::string& key) {  // scene.rs:2176
         check(gsx_model_remove(v_, key.c_str()));
         models.erase(key);

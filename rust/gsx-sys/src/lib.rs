@@ -27,6 +27,7 @@ pub const GSX_BOUNDS_SKIP_HIDDEN: u32 = 2;
 pub const GSX_BOUNDS_SELECTED: u32 = 4;
 pub const GSX_EXTRACT_INVERT: u32 = 1;
 pub const GSX_EXTRACT_DROP_EDITS: u32 = 2;
+pub const GSX_MERGE_MAX_SOURCES: u32 = 64;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -228,6 +229,7 @@ extern "C" {
     pub fn gsx_model_bounds(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_bounds_desc, out: *mut gsx_model_bounds_t) -> gsx_status;
     pub fn gsx_extract_desc_default(d: *mut gsx_extract_desc);
     pub fn gsx_model_extract(v: *mut gsx_viewer, src_key: *const c_char, dst_key: *const c_char, desc: *const gsx_extract_desc, out_count: *mut u64) -> gsx_status;
+    pub fn gsx_model_merge(v: *mut gsx_viewer, src_keys: *const *const c_char, n_src: u32, dst_key: *const c_char, desc: *const gsx_extract_desc, out_counts: *mut u64, out_total: *mut u64) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

@@ -278,6 +278,27 @@ impl<G: GaussianPod> MultiModelViewer<G> {
         }
         Ok(count)
     }
+    /// `gsx_model_merge`: the Gaussians of the models `src_keys` that pass `filter` become the one new model `dst_key`, source after
+    /// source, each source's model transform baked into its Gaussians (an identity source travels as stored bits); `dst_key` has the
+    /// identity transform.  Returns the total kept and one kept count per source; a total of 0 creates no model.
+    pub fn merge(&mut self, src_keys: &[&str], dst_key: &str, filter: u32, flags: u32) -> Result<(u64, Vec<u64>), Error> {
+        let keys: Vec<CString> = src_keys.iter().map(|s| CString::new(*s).unwrap()).collect();
+        let ptrs: Vec<*const std::os::raw::c_char> = keys.iter().map(|k| k.as_ptr()).collect();
+        let k = CString::new(dst_key).unwrap();
+        let desc = sys::gsx_extract_desc { filter, flags };
+        let (mut counts, mut total) = (vec![0u64; keys.len().max(1)], 0u64);
+        check(unsafe { sys::gsx_model_merge(self.handle.0, ptrs.as_ptr(), ptrs.len() as u32, k.as_ptr(), &desc, counts.as_mut_ptr(), &mut total) })?;
+        counts.truncate(keys.len());
+        if total > 0 {
+            let (v, n) = (self.handle.0, total as usize);
+            self.models.insert(dst_key.to_owned(), MultiModelViewerModel { gaussian_buffers: MultiModelViewerGaussianBuffers {
+                gaussians_buffer: GaussiansBuffer { v, key: k.clone() },
+                mask_buffer: MaskBuffer { v, key: k.clone(), words: (n + 31) / 32 },
+                gaussians_edit_buffer: GaussiansEditBuffer { v, key: k.clone(), n },
+            }, v, key: k });
+        }
+        Ok((total, counts))
+    }
     /// `viewer.remove_model(&key)` (scene.rs:2176)
     pub fn remove_model(&mut self, key: &str) {
         let k = CString::new(key).unwrap();

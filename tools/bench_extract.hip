@@ -144,7 +144,7 @@ int main(int argc, char** argv) {
             fprintf(stderr, "pattern %s: the scan counted %llu, the host %llu\n", names[pat], (unsigned long long)count, (unsigned long long)want);
             return 1;
         }
-        const double scatter_us = time_us(reps, [&] { CK(launch_extract_scatter(0, sh, cov, n, count, keep, bases, src, dst)); });
+        const double scatter_us = time_us(reps, [&] { CK(launch_extract_scatter(0, sh, cov, n, count, 0, keep, bases, src, dst)); });
         const double bytes = 2.0 * (double)per_gaussian * (double)count;
         char row[512];
         snprintf(row, sizeof row, ", \"%s\": {\"kept\": %llu, \"keep_us\": %.2f, \"scan_us\": %.2f, \"scatter_us\": %.2f, \"scatter_bytes\": %.0f, \"scatter_TBps\": %.4f}",

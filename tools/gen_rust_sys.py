@@ -76,6 +76,7 @@ pub const GSX_BOUNDS_SKIP_HIDDEN: u32 = 2;
 pub const GSX_BOUNDS_SELECTED: u32 = 4;
 pub const GSX_EXTRACT_INVERT: u32 = 1;
 pub const GSX_EXTRACT_DROP_EDITS: u32 = 2;
+pub const GSX_MERGE_MAX_SOURCES: u32 = 64;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;

@@ -47,7 +47,7 @@ EXPORTS = (
     "gsx_viewer_comm_init_custom_v", "gsx_shard_set_band_edges", "gsx_shard_get_band_edges", "gsx_shard_set_balance",
     "gsx_viewer_comm_info",
     "gsx_bounds_desc_default", "gsx_model_bounds",
-    "gsx_extract_desc_default", "gsx_model_extract",
+    "gsx_extract_desc_default", "gsx_model_extract", "gsx_model_merge",
 )
 
 
@@ -86,6 +86,8 @@ class ModelBounds(C.Structure):
 
 #: gsx_extract_desc.flags (its filter takes the GSX_BOUNDS_* bits)
 GSX_EXTRACT_INVERT, GSX_EXTRACT_DROP_EDITS = 1, 2
+#: most sources one gsx_model_merge call takes
+GSX_MERGE_MAX_SOURCES = 64
 
 
 class ExtractDesc(C.Structure):
@@ -322,6 +324,7 @@ def load() -> C.CDLL:
         "gsx_model_bounds": ([vp, cp, C.POINTER(BoundsDesc), C.POINTER(ModelBounds)], C.c_int32),
         "gsx_extract_desc_default": ([C.POINTER(ExtractDesc)], None),
         "gsx_model_extract": ([vp, cp, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_model_merge": ([vp, C.POINTER(C.c_char_p), C.c_uint32, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)
     for name, (args, res) in sig.items():

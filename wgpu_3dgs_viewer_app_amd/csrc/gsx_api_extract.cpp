@@ -6,27 +6,7 @@ using namespace gsx;
 namespace {
 // the workspace: [total, padded to 128 B | keep words, padded to 128 B | partials | bases]
 constexpr size_t kWsKeep = 128;
-inline size_t pad128(size_t b) { return (b + 127u) & ~size_t(127); }
 
-ExtractPlanes planes_of(const Model* m, bool edits) {
-    ExtractPlanes p{};
-    p.pc = m->pc.as<uint4>();
-    p.cov_a = m->cov_a.as<uint4>();
-    p.cov_b = m->cov_b.as<uint2>();
-    p.cov_h = m->cov_h.as<uint2>();
-    p.cov_h2 = m->cov_h2.as<uint32_t>();
-    p.sh4 = m->sh4.as<uint4>();
-    p.sh1 = m->sh1.as<uint32_t>();
-    p.sh_h = m->sh_h.as<uint4>();
-    p.sh_q = m->sh_q.as<uint4>();
-    p.sh_aos = m->sh_aos.as<uint4>();
-    if (edits) {
-        p.edited = m->edited.as<uint32_t>();
-        p.edit_a = m->edit_a.as<uint4>();
-        p.edit_b = m->edit_b.as<uint4>();
-    }
-    return p;
-}
 }  // namespace
 
 extern "C" {
@@ -56,7 +36,7 @@ gsx_status gsx_model_extract(gsx_viewer* v, const char* src_key, const char* dst
     if (n == 0) return GSX_OK;
 
     const uint64_t groups = extract_groups(n);
-    const size_t ws_partials = kWsKeep + pad128(4 * (size_t)((n + 31) / 32)), ws_bases = ws_partials + pad128(4 * (size_t)groups);
+    const size_t ws_partials = kWsKeep + extract_pad128(4 * (size_t)((n + 31) / 32)), ws_bases = ws_partials + extract_pad128(4 * (size_t)groups);
     HIPCHK(v->extract_ws.ensure(ws_bases + 4 * (size_t)groups));
     char* ws = v->extract_ws.as<char>();
     uint64_t* d_total = reinterpret_cast<uint64_t*>(ws);
@@ -91,7 +71,7 @@ gsx_status gsx_model_extract(gsx_viewer* v, const char* src_key, const char* dst
     if (edits && (st = ensure_edit_buffers(v, d)) == GSX_OK)  // (zeroes dst's `edited` plane)
         d->edit_epoch += 1;
     if (st == GSX_OK) {
-        e = launch_extract_scatter(v->stream, (int)m->sh_kind, (int)m->cov_kind, n, count, keep, bases, planes_of(m, edits), planes_of(d, edits));
+        e = launch_extract_scatter(v->stream, (int)m->sh_kind, (int)m->cov_kind, n, count, 0, keep, bases, extract_planes(m, edits), extract_planes(d, edits));
         if (e != hipSuccess) st = fail(e == hipErrorOutOfMemory ? GSX_ERR_OOM : GSX_ERR_HIP, "gsx_model_extract: the scatter failed: %s", hipGetErrorString(e));
     }
     if (st) {  // no dst left behind

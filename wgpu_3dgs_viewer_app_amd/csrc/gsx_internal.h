@@ -9,6 +9,7 @@
 #include "bounds_math.h"
 #include "extract_math.h"
 #include "gizmo_math.h"
+#include "merge_math.h"
 #include "toolset_math.h"
 
 namespace gsx {
@@ -944,12 +945,48 @@ struct ExtractPlanes {
     uint4* edit_a;
     uint4* edit_b;
 };
+// The start of both scatters (k_extract_scatter, k_merge_bake): wave 0 loads the workgroup's 32 keep words
+// and scans their popcounts; s_before[w] = kept Gaussians of the workgroup's words before word w, s_before[32] = all of them.  Ends
+// with a barrier.  A Gaussian's rank in its workgroup is s_before[word] + extract_rank(word, bit): from the keep words alone.
+__device__ inline void extract_group_ranks(const uint32_t* __restrict__ keep, uint64_t n_src, uint64_t base, uint32_t* s_keep, uint32_t* s_before) {
+    const uint32_t t = threadIdx.x;
+    if (t < 64u) {  // (one whole wave: the shuffles below need every lane of it)
+        const uint64_t w = (base >> 5) + t;
+        const uint32_t word = (t < kExtractGroupWords && w * 32u < n_src) ? keep[w] : 0u;
+        uint32_t incl = extract_popc(word);
+#pragma unroll
+        for (uint32_t off = 1; off < kExtractGroupWords; off <<= 1) {
+            const uint32_t up = __shfl_up(incl, off);
+            if (t >= off) incl += up;
+        }
+        if (t < kExtractGroupWords) {
+            s_keep[t] = word;
+            s_before[t + 1] = incl;
+            if (t == 0) s_before[0] = 0u;
+        }
+    }
+    __syncthreads();
+}
+// a workspace region's size: whole 128-byte lines (gsx_api_extract.cpp, gsx_api_merge.cpp)
+inline size_t extract_pad128(size_t b) { return (b + 127u) & ~size_t(127); }
 // keep: ceil(n / 32) words; partials, bases: extract_groups(n) words; total: one 64-bit word, written by the scan (n > 0)
 hipError_t launch_extract_keep(hipStream_t s, uint64_t n, const ExtractFilter& f, uint32_t* keep, uint32_t* partials);
 hipError_t launch_extract_scan(hipStream_t s, const uint32_t* partials, uint64_t n_partials, uint32_t* bases, uint64_t* total);
-// src is only read.  dst's planes hold n_dst = the scan's total Gaussians; dst.edited (when carried) is zeroed
-hipError_t launch_extract_scatter(hipStream_t s, int sh_kind, int cov_kind, uint64_t n_src, uint64_t n_dst, const uint32_t* keep, const uint32_t* bases,
-                                  const ExtractPlanes& src, const ExtractPlanes& dst);
+// src is only read.  dst's planes hold n_dst Gaussians, of which this launch writes [dst_offset, dst_offset + the scan's total)
+// (gsx_model_extract: dst_offset 0, n_dst the total); dst.edited (when carried) is zeroed
+hipError_t launch_extract_scatter(hipStream_t s, int sh_kind, int cov_kind, uint64_t n_src, uint64_t n_dst, uint64_t dst_offset, const uint32_t* keep,
+                                  const uint32_t* bases, const ExtractPlanes& src, const ExtractPlanes& dst);
+
+// Model merge (kernels_merge.hip; gsx_model_merge): a source whose model transform is not the identity is dequantised, baked and
+// quantised again on its way into dst.  The per-source constants, passed by value (wave-uniform: they sit in scalar registers).
+struct MergeBake {
+    float R[9];                 // R_m, row-major: quat_to_rows(mt.quat), the float32 matrix frame_consts_setup uses
+    float s[3], t[3];           // s_m, t_m
+    float sh[kMergeShFloats];   // merge_math.h: the SH matrices of bands 1, 2, 3, float64 rounded to float32
+};
+// as launch_extract_scatter, baking: src's edit planes may be absent while dst's are present (a source without edit records)
+hipError_t launch_merge_bake(hipStream_t s, int sh_kind, int cov_kind, uint64_t n_src, uint64_t n_dst, uint64_t dst_offset, const uint32_t* keep,
+                             const uint32_t* bases, const ExtractPlanes& src, const ExtractPlanes& dst, const MergeBake& bake);
 
 // Compositing and resolve.
 // carry: continue from the (C, T) already in fb (later slabs / models behind); done: saturated-tile bitmap

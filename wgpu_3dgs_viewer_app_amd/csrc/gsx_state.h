@@ -500,7 +500,8 @@ struct gsx_viewer {
     // histograms, allocated by the first call and reused.  Nothing a frame reads
     DevBuf bounds_ws;
     // gsx_model_extract (gsx_api_extract.cpp; owner only): the total, the keep words (n / 8 bytes) and two words per 1024 Gaussians
-    // (popcount partials, their scan), allocated by the first call and grown when a larger model is extracted from.  Nothing a frame reads
+    // (popcount partials, their scan), allocated by the first call and grown when a larger model is extracted from.  gsx_model_merge
+    // (gsx_api_merge.cpp) lays one such region per source behind its array of totals.  Nothing a frame reads
     DevBuf extract_ws;
 };
 
@@ -694,6 +695,26 @@ gsx_status ensure_sortbin_capacity(Model* m, uint64_t count);
 gsx_status ensure_import_capacity(Model* m, uint64_t count);
 // gsx_api.cpp: gsx_model_create's body (the viewer is bound): the new model, zero-filled or not, inserted under `key` and returned in *out
 gsx_status model_create(gsx_viewer* v, const char* key, uint64_t count, gsx_sh_kind sh, gsx_cov3d_kind cov3d, bool zero_planes, Model** out);
+// the planes gsx_model_extract and gsx_model_merge carry (gsx_api_extract.cpp, gsx_api_merge.cpp); edits: with the three edit planes
+inline ExtractPlanes extract_planes(const Model* m, bool edits) {
+    ExtractPlanes p{};
+    p.pc = m->pc.as<uint4>();
+    p.cov_a = m->cov_a.as<uint4>();
+    p.cov_b = m->cov_b.as<uint2>();
+    p.cov_h = m->cov_h.as<uint2>();
+    p.cov_h2 = m->cov_h2.as<uint32_t>();
+    p.sh4 = m->sh4.as<uint4>();
+    p.sh1 = m->sh1.as<uint32_t>();
+    p.sh_h = m->sh_h.as<uint4>();
+    p.sh_q = m->sh_q.as<uint4>();
+    p.sh_aos = m->sh_aos.as<uint4>();
+    if (edits) {
+        p.edited = m->edited.as<uint32_t>();
+        p.edit_a = m->edit_a.as<uint4>();
+        p.edit_b = m->edit_b.as<uint4>();
+    }
+    return p;
+}
 gsx_status ensure_selection(gsx_viewer* v, Model* m);
 gsx_status ensure_edit_buffers(gsx_viewer* v, Model* m);
 

@@ -97,32 +97,17 @@ __device__ inline void ex_copy_planes(const T* __restrict__ src, uint64_t n_src,
 }
 
 template <int SH, int COV>
-__global__ __launch_bounds__(256) void k_extract_scatter(uint64_t n_src, uint64_t n_dst, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ bases,
-                                                          ExtractPlanes src, ExtractPlanes dst) {
+__global__ __launch_bounds__(256) void k_extract_scatter(uint64_t n_src, uint64_t n_dst, uint64_t dst_offset, const uint32_t* __restrict__ keep,
+                                                          const uint32_t* __restrict__ bases, ExtractPlanes src, ExtractPlanes dst) {
     constexpr uint32_t kStride = SH == GSX_SH_SINGLE ? 16u : SH == GSX_SH_HALF ? (COV == GSX_COV3D_SINGLE ? 12u : 8u) : SH == GSX_SH_NORM8 ? 8u : 0u;
     __shared__ uint32_t s_keep[kExtractGroupWords], s_before[kExtractGroupWords + 1];
     __shared__ uint16_t s_list[kExtractGroup];  // the workgroup's kept Gaussians, by rank: index inside the workgroup
     const uint32_t t = threadIdx.x;
     const uint64_t base = (uint64_t)blockIdx.x * kExtractGroup;
-    if (t < 64u) {  // (one whole wave: the shuffles below need every lane of it)
-        const uint64_t w = (base >> 5) + t;
-        const uint32_t word = (t < kExtractGroupWords && w * 32u < n_src) ? keep[w] : 0u;
-        uint32_t incl = extract_popc(word);
-#pragma unroll
-        for (uint32_t off = 1; off < kExtractGroupWords; off <<= 1) {
-            const uint32_t up = __shfl_up(incl, off);
-            if (t >= off) incl += up;
-        }
-        if (t < kExtractGroupWords) {
-            s_keep[t] = word;
-            s_before[t + 1] = incl;
-            if (t == 0) s_before[0] = 0u;
-        }
-    }
-    __syncthreads();
+    extract_group_ranks(keep, n_src, base, s_keep, s_before);
     const uint32_t kept = s_before[kExtractGroupWords];
     if (kept == 0) return;  // (uniform)
-    const uint64_t j0 = bases[blockIdx.x];
+    const uint64_t j0 = dst_offset + bases[blockIdx.x];  // (dst_offset: 0 for extract; gsx_model_merge lands a source anywhere in dst)
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
         const uint32_t local = k * 256u + t, w = local >> 5, bit = local & 31u, word = s_keep[w];
@@ -150,7 +135,8 @@ __global__ __launch_bounds__(256) void k_extract_scatter(uint64_t n_src, uint64_
             dst.edit_a[j] = src.edit_a[i];
             dst.edit_b[j] = src.edit_b[i];
             // dst's `edited` plane starts zeroed; an OR whose result nobody reads gives the same word in any order
-            if ((src.edited[i >> 5] >> bit) & 1u) atomicOr(&dst.edited[j >> 5], 1u << (uint32_t)(j & 31u));
+            // (merge_math.h: with an offset the first and last word of a source are shared with its neighbours)
+            if ((src.edited[i >> 5] >> bit) & 1u) atomicOr(&dst.edited[merge_bit_word(j0, r)], merge_bit_mask(j0, r));
         }
     }
     if (kStride == 0u) return;
@@ -183,12 +169,12 @@ hipError_t launch_extract_scan(hipStream_t s, const uint32_t* partials, uint64_t
     GSX_LAUNCH(k_extract_scan, dim3(1), dim3(kExtractScanPass), 0, s, partials, n_partials, bases, total);
     return hipGetLastError();
 }
-hipError_t launch_extract_scatter(hipStream_t s, int sh_kind, int cov_kind, uint64_t n_src, uint64_t n_dst, const uint32_t* keep, const uint32_t* bases,
-                                  const ExtractPlanes& src, const ExtractPlanes& dst) {
+hipError_t launch_extract_scatter(hipStream_t s, int sh_kind, int cov_kind, uint64_t n_src, uint64_t n_dst, uint64_t dst_offset, const uint32_t* keep,
+                                  const uint32_t* bases, const ExtractPlanes& src, const ExtractPlanes& dst) {
     const dim3 grid((uint32_t)extract_groups(n_src)), block(256);
 #define GSX_EX_CASE(SH, COV)                                                                                   \
     if (sh_kind == SH && cov_kind == COV) {                                                                    \
-        GSX_LAUNCH((k_extract_scatter<SH, COV>), grid, block, 0, s, n_src, n_dst, keep, bases, src, dst);      \
+        GSX_LAUNCH((k_extract_scatter<SH, COV>), grid, block, 0, s, n_src, n_dst, dst_offset, keep, bases, src, dst); \
         return hipGetLastError();                                                                              \
     }
     GSX_EX_CASE(GSX_SH_SINGLE, GSX_COV3D_SINGLE) GSX_EX_CASE(GSX_SH_SINGLE, GSX_COV3D_HALF)

@@ -13,6 +13,7 @@
 
 #include "edit_math.h"
 #include "gsx_internal.h"
+#include "pod_quant.h"
 #include "project_math.h"
 #include "shade_quads.h"
 #include "window_scan.h"
@@ -94,15 +95,7 @@ __device__ inline float ddot3(float a0, float a1, float a2, float b0, float b1, 
 }
 
 // ---- quantisation (spec/RENDER_SPEC.md §2b) ----
-// f16: IEEE binary16, round to nearest even (what `half::f16::from_f32` does; v_cvt_f16_f32).
-// snorm8: q = floor(clamp(v,-1,1) * 127 + 0.5) as int8; decode = max(q / 127, -1) (WGSL unpack4x8snorm).
-__device__ inline uint32_t pack_h2(float a, float b) {
-    return (uint32_t)__half_as_ushort(__float2half_rn(a)) | ((uint32_t)__half_as_ushort(__float2half_rn(b)) << 16);
-}
-__device__ inline uint32_t q_snorm8(float v) {
-    float c = fminf(fmaxf(v, -1.0f), 1.0f);
-    return (uint32_t)(int)floorf(c * 127.0f + 0.5f) & 0xFFu;
-}
+// pack_h2, q_snorm8 and their decoders: pod_quant.h (shared with kernels_merge.hip)
 
 __device__ inline void store_sh(const PodPlanes& pod, uint64_t model_n, uint64_t i, const float* s45) {
     if (pod.sh_kind == GSX_SH_SINGLE) {

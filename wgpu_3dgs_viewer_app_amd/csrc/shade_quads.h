@@ -8,16 +8,10 @@
 #include <hip/hip_fp16.h>
 
 #include "gsx_internal.h"
+#include "pod_quant.h"  // h_lo, h_hi, dq_snorm8
 #include "project_math.h"
 
 namespace gsx {
-
-__device__ inline float h_lo(uint32_t u) { return __half2float(__ushort_as_half((unsigned short)(u & 0xFFFFu))); }
-__device__ inline float h_hi(uint32_t u) { return __half2float(__ushort_as_half((unsigned short)(u >> 16))); }
-__device__ inline float dq_snorm8(uint32_t word, int byte) {
-    int q = (int)(signed char)((word >> (8 * byte)) & 0xFFu);
-    return fmaxf((float)q * (1.0f / 127.0f), -1.0f);
-}
 
 // k_shade for the 256-byte record copy (f32 SH + f32 covariance), four lanes to a record.  One record per lane meant sixteen 16-byte
 // loads 256 bytes apart from lane to lane: every load instruction touched 64 different lines, a wave's working set was 16 KB of a

@@ -416,6 +416,21 @@ class MultiModelViewer:
         self.models[key] = MultiModelViewerModel(self, key)
         return self.models[key]
 
+    def merge(self, dst_key: str, src_keys, filter: int = 0, invert: bool = False, drop_edits: bool = False):  # noqa: A002
+        """``gsx_model_merge``: the Gaussians of the models ``src_keys`` that pass ``filter`` (``_lib.GSX_BOUNDS_*`` bits, applied to
+        every source with ``extract``'s meaning) become the one new model ``dst_key`` on the device, source after source in the order
+        given, with each source's model transform baked into its Gaussians (positions, covariances and SH coefficients; a source
+        under the identity transform travels as stored bits).  ``dst_key`` has the identity transform.  A key may appear twice.
+        Returns ``(total, counts)``; a total of 0 creates no model.  The way back from ``extract`` + ``update_model_transform``."""
+        keys = [k.encode() for k in src_keys]
+        arr = (C.c_char_p * max(len(keys), 1))(*keys)
+        desc = _lib.ExtractDesc(int(filter), (_lib.GSX_EXTRACT_INVERT if invert else 0) | (_lib.GSX_EXTRACT_DROP_EDITS if drop_edits else 0))
+        counts, total = (C.c_uint64 * max(len(keys), 1))(), C.c_uint64()
+        _lib.check(self._L.gsx_model_merge(self._h, arr, len(keys), dst_key.encode(), C.byref(desc), counts, C.byref(total)))
+        if total.value:
+            self.models[dst_key] = MultiModelViewerModel(self, dst_key)
+        return int(total.value), [int(c) for c in counts[: len(keys)]]
+
     def remove_model(self, key: str) -> None:
         """``viewer.remove_model(&key)`` (src/tab/scene.rs:2176)."""
         _lib.check(self._L.gsx_model_remove(self._h, key.encode()))
