@@ -456,6 +456,53 @@ gsx_status gsx_model_extract(gsx_viewer* v, const char* src_key, const char* dst
 gsx_status gsx_model_merge(gsx_viewer* v, const char* const* src_keys, uint32_t n_src, const char* dst_key,
                            const gsx_extract_desc* desc, uint64_t* out_counts /* n_src entries, nullable */, uint64_t* out_total);
 
+/* ---- model export: a resident model as gsx_gaussian records or as an INRIA PLY file, built on the device (spec/RENDER_SPEC.md §14
+ *      [BUILD-SPEC]; the app's export modal and write_ply, src/app.rs:753-817 and 897-947, work on host Gaussians).  The way out for
+ *      a model that exists only in device memory (gsx_model_extract, gsx_model_merge), and the way from one pod kind to another: the
+ *      records can be uploaded with gsx_model_upload_range into a model of any kind.
+ *      Kept set and order: exactly gsx_model_extract's, from `filter` (GSX_BOUNDS_* bits) and GSX_EXTRACT_INVERT: no mask = all pass,
+ *      no selection = none pass, bits at or above n ignored; kept Gaussians appear in ascending index order.
+ *      Space: model space.  The model transform is NOT applied; a caller who wants it baked calls gsx_model_merge first.
+ *      pos: the stored bits, non-finite values included.  sh[15][3]: the exact dequantisation (§2b) of the resident planes, zeros for
+ *      an Sh None model.  color: the stored colour word unless edits are baked.  Uploading the records into a model of the same pod
+ *      kind therefore reproduces the position, colour and SH planes bit for bit.
+ *      rot and scale: from the stored covariance, dequantised exactly, by a cyclic Jacobi eigen-solve in float32 with a fixed number
+ *      of sweeps in a fixed pair order (the same bits on every call).  scale_k = sqrtf(max(lambda_k, 0)), scale_0 >= scale_1 >=
+ *      scale_2; the eigenvector matrix is made a proper rotation (last column flipped if the determinant is negative); the quaternion
+ *      is normalised and has w >= 0 (w == 0: the first non-zero of x, y, z is positive).  The covariance that the upload conversion
+ *      makes of (rot, scale) differs from the stored one by at most 4 x what a float64 eigen-solve rounded to float32 gives (§14).
+ *      Special cases: an all-zero covariance gives rot (0,0,0,1) and scale 0; a non-finite entry (a Half covariance that overflowed)
+ *      gives rot (0,0,0,1) and scale_k = sqrtf(fmaxf(S_kk, 0)), unsorted; a negative eigenvalue (Half rounding) gives scale 0.
+ *      Edits: with GSX_EXPORT_BAKE_EDITS on a model that has edit records, a Gaussian whose `edited` bit is set and whose record has
+ *      ENABLED gets spec §7 Export's arithmetic, as gsx_ply_write applies it: PLY rows f_dc = (c - 0.5) / C0 from the edited float
+ *      colour and opacity = logit(clamp(a, 1e-6, 1 - 1e-6)); records color = floor(255 * clamp(x, 0, 1) + 0.5) per channel.  HIDDEN
+ *      Gaussians are dropped only if `filter` has GSX_BOUNDS_SKIP_HIDDEN; gsx_model_show_unedited changes nothing here.  Without the
+ *      flag, or on a model without edit records, the stored colour word is exported.
+ *      PLY rows: 62 float32 in gsx_ply_write's property order, exactly its conversion of the record: normals 0, f_rest channel-major,
+ *      rot as w, x, y, z, scale_k = logf(scale_k) (a zero scale writes -inf).
+ *      gsx_model_export: `out` NULL returns only the kept count in *out_count.  Otherwise capacity_bytes must hold count x row bytes;
+ *      if it does not, GSX_ERR_INVALID_ARG with *out_count the needed count and nothing written.  A count of 0 is GSX_OK and writes
+ *      nothing.
+ *      gsx_model_export_ply: the whole file: gsx_ply_write's header for the kept count, byte for byte, then the rows; desc->format is
+ *      ignored.  `out` NULL returns the size in *out_size; a capacity below it is GSX_ERR_INVALID_ARG with *out_size set.  The
+ *      reference's write_ply(edits, mask) is filter = MASKED | SKIP_HIDDEN, flags = BAKE_EDITS.
+ *      Staging: rows are produced into one of two device staging buffers of staging_bytes each (0: the library's default, 32 MiB;
+ *      raised to 1024 rows) and copied to `out` chunk by chunk, the kernel of a chunk running while the chunk before it is copied.
+ *      The buffers belong to the viewer, are counted by gsx_debug_device_bytes and are freed with it.
+ *      Errors: a null viewer, key, desc or count / size pointer, unknown filter bits, flag bits (2u included), format, a non-zero
+ *      `reserved`: GSX_ERR_INVALID_ARG; unknown key: GSX_ERR_NOT_FOUND; a viewer with a communicator, or a sharded model:
+ *      GSX_ERR_UNSUPPORTED.
+ *      Ordering: as gsx_model_extract, on the viewer's stream behind the lanes' frames in flight and earlier uploads.  The call
+ *      returns when `out` is complete.  The model is not written: its planes, mask, selection, edits and next frame are what they
+ *      were. ---- */
+#define GSX_EXPORT_GAUSSIANS    0u /* gsx_gaussian records, 224 B each */
+#define GSX_EXPORT_PLY_VERTICES 1u /* INRIA rows, 62 f32 = 248 B each, property order of gsx_ply_write */
+#define GSX_EXPORT_BAKE_EDITS   4u /* flag; GSX_EXTRACT_INVERT (1u) is the other legal flag, 2u is not legal here */
+typedef struct gsx_export_desc { uint32_t filter; uint32_t flags; uint32_t format; uint32_t reserved; uint64_t staging_bytes; } gsx_export_desc; /* 24 B */
+void gsx_export_desc_default(gsx_export_desc* d); /* all zero: whole model, gsx_gaussian records, library-chosen staging */
+gsx_status gsx_model_export(gsx_viewer* v, const char* key, const gsx_export_desc* desc, void* out, uint64_t capacity_bytes, uint64_t* out_count);
+gsx_status gsx_model_export_ply(gsx_viewer* v, const char* key, const gsx_export_desc* desc, void* out, uint64_t capacity, uint64_t* out_size);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

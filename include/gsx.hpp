@@ -285,6 +285,27 @@ public:
         if (counts) counts->assign(per.begin(), per.begin() + src_keys.size());
         return total;
     }
+    // gsx_model_export: the Gaussians of `key` that pass `filter` (flags: GSX_EXTRACT_INVERT, GSX_EXPORT_BAKE_EDITS) as gsx_gaussian
+    // records in model space: rotation and scale solved from the stored covariance on the device, positions, colours and SH as stored.
+    // The way out for a model that only the device holds (extract, merge); upload the records into a model of any pod kind.
+    std::vector<gsx_gaussian> export_gaussians(const std::string& key, uint32_t filter = 0, uint32_t flags = 0, uint64_t staging_bytes = 0) {
+        const gsx_export_desc d{filter, flags, GSX_EXPORT_GAUSSIANS, 0u, staging_bytes};
+        uint64_t count = 0;
+        check(gsx_model_export(v_, key.c_str(), &d, nullptr, 0, &count));
+        std::vector<gsx_gaussian> out(count);
+        if (count) check(gsx_model_export(v_, key.c_str(), &d, out.data(), count * sizeof(gsx_gaussian), &count));
+        return out;
+    }
+    // gsx_model_export_ply: the same Gaussians as a binary INRIA PLY file (gsx_ply_write's header and rows).  The reference's
+    // write_ply(edits, mask) is export_ply(key, GSX_BOUNDS_MASKED | GSX_BOUNDS_SKIP_HIDDEN, GSX_EXPORT_BAKE_EDITS).
+    std::vector<uint8_t> export_ply(const std::string& key, uint32_t filter = 0, uint32_t flags = 0, uint64_t staging_bytes = 0) {
+        const gsx_export_desc d{filter, flags, GSX_EXPORT_PLY_VERTICES, 0u, staging_bytes};
+        uint64_t size = 0;
+        check(gsx_model_export_ply(v_, key.c_str(), &d, nullptr, 0, &size));
+        std::vector<uint8_t> out(size);
+        check(gsx_model_export_ply(v_, key.c_str(), &d, out.data(), out.size(), &size));
+        return out;
+    }
     void remove_model(const std::string& key) {  // scene.rs:2176
         check(gsx_model_remove(v_, key.c_str()));
         models.erase(key);

@@ -28,6 +28,9 @@ pub const GSX_BOUNDS_SELECTED: u32 = 4;
 pub const GSX_EXTRACT_INVERT: u32 = 1;
 pub const GSX_EXTRACT_DROP_EDITS: u32 = 2;
 pub const GSX_MERGE_MAX_SOURCES: u32 = 64;
+pub const GSX_EXPORT_GAUSSIANS: u32 = 0;
+pub const GSX_EXPORT_PLY_VERTICES: u32 = 1;
+pub const GSX_EXPORT_BAKE_EDITS: u32 = 4;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -113,6 +116,10 @@ pub struct gsx_model_bounds_t {
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_extract_desc { pub filter: u32, pub flags: u32 }
+/// what gsx_model_export writes (filter: GSX_BOUNDS_*; flags: GSX_EXTRACT_INVERT, GSX_EXPORT_BAKE_EDITS; format: GSX_EXPORT_*)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_export_desc { pub filter: u32, pub flags: u32, pub format: u32, pub reserved: u32, pub staging_bytes: u64 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }
@@ -230,6 +237,9 @@ extern "C" {
     pub fn gsx_extract_desc_default(d: *mut gsx_extract_desc);
     pub fn gsx_model_extract(v: *mut gsx_viewer, src_key: *const c_char, dst_key: *const c_char, desc: *const gsx_extract_desc, out_count: *mut u64) -> gsx_status;
     pub fn gsx_model_merge(v: *mut gsx_viewer, src_keys: *const *const c_char, n_src: u32, dst_key: *const c_char, desc: *const gsx_extract_desc, out_counts: *mut u64, out_total: *mut u64) -> gsx_status;
+    pub fn gsx_export_desc_default(d: *mut gsx_export_desc);
+    pub fn gsx_model_export(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_export_desc, out: *mut c_void, capacity_bytes: u64, out_count: *mut u64) -> gsx_status;
+    pub fn gsx_model_export_ply(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_export_desc, out: *mut c_void, capacity: u64, out_size: *mut u64) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

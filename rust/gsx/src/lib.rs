@@ -299,6 +299,33 @@ impl<G: GaussianPod> MultiModelViewer<G> {
         }
         Ok((total, counts))
     }
+    /// `gsx_model_export`: the Gaussians of `key` that pass `filter` (`flags`: `sys::GSX_EXTRACT_INVERT`, `sys::GSX_EXPORT_BAKE_EDITS`)
+    /// as `gsx_gaussian` records in model space, rotation and scale solved from the stored covariance on the device.  The way out
+    /// for a model that only the device holds (`extract`, `merge`).
+    pub fn export(&mut self, key: &str, filter: u32, flags: u32) -> Result<Vec<sys::gsx_gaussian>, Error> {
+        let k = CString::new(key).unwrap();
+        let desc = sys::gsx_export_desc { filter, flags, format: sys::GSX_EXPORT_GAUSSIANS, reserved: 0, staging_bytes: 0 };
+        let mut count = 0u64;
+        check(unsafe { sys::gsx_model_export(self.handle.0, k.as_ptr(), &desc, std::ptr::null_mut(), 0, &mut count) })?;
+        let mut out: Vec<sys::gsx_gaussian> = Vec::with_capacity(count as usize);
+        if count > 0 {
+            let bytes = count * std::mem::size_of::<sys::gsx_gaussian>() as u64;
+            check(unsafe { sys::gsx_model_export(self.handle.0, k.as_ptr(), &desc, out.as_mut_ptr() as *mut std::os::raw::c_void, bytes, &mut count) })?;
+            unsafe { out.set_len(count as usize) };  // every byte of every record is written by the library
+        }
+        Ok(out)
+    }
+    /// `gsx_model_export_ply`: the same Gaussians as a binary INRIA PLY file.  The reference's `write_ply(edits, mask)` is
+    /// `export_ply(key, GSX_BOUNDS_MASKED | GSX_BOUNDS_SKIP_HIDDEN, GSX_EXPORT_BAKE_EDITS)`.
+    pub fn export_ply(&mut self, key: &str, filter: u32, flags: u32) -> Result<Vec<u8>, Error> {
+        let k = CString::new(key).unwrap();
+        let desc = sys::gsx_export_desc { filter, flags, format: sys::GSX_EXPORT_PLY_VERTICES, reserved: 0, staging_bytes: 0 };
+        let mut size = 0u64;
+        check(unsafe { sys::gsx_model_export_ply(self.handle.0, k.as_ptr(), &desc, std::ptr::null_mut(), 0, &mut size) })?;
+        let mut out = vec![0u8; size as usize];
+        check(unsafe { sys::gsx_model_export_ply(self.handle.0, k.as_ptr(), &desc, out.as_mut_ptr() as *mut std::os::raw::c_void, size, &mut size) })?;
+        Ok(out)
+    }
     /// `viewer.remove_model(&key)` (scene.rs:2176)
     pub fn remove_model(&mut self, key: &str) {
         let k = CString::new(key).unwrap();

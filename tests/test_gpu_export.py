@@ -1,0 +1,578 @@
+"""GPU: gsx_model_export and gsx_model_export_ply (spec/RENDER_SPEC.md §14; csrc/kernels_export.hip, csrc/gsx_api_export.cpp).
+Positions, colours and SH are compared bit for bit with the kept rows of gsx_model_download_pod (the exact dequantisation of the
+stored values).  Rotation and scale are compared through the covariance they give back under spec §2's upload conversion, against
+the float64 path of tests/export_ref.py: the worst error over a fixture is at most 4 x that path's.  Kept sets come from
+tests/extract_ref.py, PLY files from the host writer (Gaussians.write_ply), frames from re-uploaded models (spec §8's 1e-3)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import common
+from tests import export_ref as E
+from tests import extract_ref as X
+from wgpu_3dgs_viewer_app_amd import _lib, camera, ply, query, scene
+from wgpu_3dgs_viewer_app_amd import viewer as viewer_mod
+from wgpu_3dgs_viewer_app_amd.query import GaussianEditFlag as F
+from wgpu_3dgs_viewer_app_amd.viewer import (CommGroup, Cov3dKind, DepthCompare, GaussianDisplayMode, GaussianShDegree, GsxError, MultiModelViewer,
+                                             ShKind)
+
+pytestmark = pytest.mark.gpu
+W, H = 96, 64
+FRAME_TOL = 1e-3  # spec §8
+KINDS = [(sh, cov) for sh in ShKind for cov in Cov3dKind]
+KIND_IDS = [f"{sh.name}-{cov.name}" for sh, cov in KINDS]
+SRC = "src"
+BAKE = _lib.GSX_EXPORT_BAKE_EDITS
+ROW = {_lib.GSX_EXPORT_GAUSSIANS: 224, _lib.GSX_EXPORT_PLY_VERTICES: 248}
+C0 = 0.28209479177387814
+HALF_STEP = 2.0 ** -10  # one binary16 step of a normal value is at most this times the value; of a subnormal one it is 2^-24
+
+
+def _load(v, g, key=SRC, mt=None):
+    v.add_model(key, g.shape[0])
+    v.models[key].gaussian_buffers.gaussians_buffer.update_range(0, g)
+    if mt is not None:
+        v.update_model_transform(key, *mt)
+
+
+def _pod(v, key=SRC):
+    """the resident planes, dequantised: pos, color, sh, cov3d (sh: zeros for a viewer without SH planes)"""
+    if v.sh != ShKind.Remove:
+        return v.models[key].gaussian_buffers.gaussians_buffer.download_pod()
+    n = C.c_uint64()
+    _lib.check(v._L.gsx_model_len(v._h, key.encode(), C.byref(n)))
+    n = int(n.value)
+    pos, color, cov = np.empty((n, 3), np.float32), np.empty(n, np.uint32), np.empty((n, 6), np.float32)
+    f32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    _lib.check(v._L.gsx_model_download_pod(v._h, key.encode(), f32p(pos), color.ctypes.data_as(C.POINTER(C.c_uint32)), None, f32p(cov)))
+    return pos, color, np.zeros((n, 45), np.float32), cov
+
+
+def _frames(v, keys, poses=(5, 6, 7), sh_deg=3):
+    out = []
+    for pose in poses:
+        v.update_camera(camera.orbit_pose(pose), (W, H))
+        v.update_gaussian_transform(1.0, GaussianDisplayMode.Splat, GaussianShDegree.new(sh_deg), False)
+        v.render_frame(list(keys))
+        out.append(v.download_framebuffer())
+    return out
+
+
+def _export_raw(v, key, filter=0, flags=0, fmt=0, staging=0, reserved=0, capacity=None):  # noqa: A002
+    """gsx_model_export through ctypes: (status, count, the output buffer with 64 sentinel bytes behind the rows)"""
+    desc = _lib.ExportDesc(filter, flags, fmt, reserved, staging)
+    count = C.c_uint64(0xDEAD)
+    st = v._L.gsx_model_export(v._h, key.encode(), C.byref(desc), None, 0, C.byref(count))
+    if st != _lib.GSX_OK:
+        return st, int(count.value), None
+    rows = ROW.get(fmt, 224) * int(count.value)
+    buf = np.full(rows + 64, 0xA5, np.uint8)
+    st = v._L.gsx_model_export(v._h, key.encode(), C.byref(desc), buf.ctypes.data, rows if capacity is None else capacity, C.byref(count))
+    return st, int(count.value), buf
+
+
+def _split_ply(data, n):
+    """the header bytes and the (n, 62) uint32 rows of a PLY file"""
+    data = np.frombuffer(data, np.uint8)
+    head = data.size - 248 * n
+    return data[:head].tobytes(), data[head:].copy().view(np.uint32).reshape(n, 62)
+
+
+def _rows_of_ply(rows):
+    """(n, 62) uint32 PLY rows -> pos bits, sh bits (n, 45), rot x y z w, linear scale"""
+    f = rows.view(np.float32)
+    sh = rows[:, 9:54].reshape(-1, 3, 15).transpose(0, 2, 1).reshape(-1, 45)  # channel-major on disk
+    with np.errstate(all="ignore"):
+        return rows[:, 0:3], sh, np.concatenate([f[:, 59:62], f[:, 58:59]], axis=1), np.exp(f[:, 55:58].astype(np.float64))
+
+
+def _check_against_pod(g, pod, kept, what=""):
+    """exported records against the kept rows of download_pod: pos, colour word and sh bit for bit"""
+    pos, color, sh, _ = pod
+    assert g.shape[0] == kept.size, what
+    assert g["pos"].tobytes() == np.ascontiguousarray(pos[kept]).tobytes(), (what, "pos")
+    assert np.array_equal(g["color"].view(np.uint32).reshape(-1), color[kept]), (what, "color")
+    assert g["sh"].reshape(-1, 45).tobytes() == np.ascontiguousarray(sh[kept]).tobytes(), (what, "sh")
+
+
+def _check_cov(cov, rot, scale, what="", through_log=False):
+    """the covariance bound and the canonical form over one fixture of finite covariances; returns (worst, the float64 path's worst).
+    through_log: the scales were read from PLY rows; the float64 path's scales then go through the float32 logarithm too"""
+    E.check_canonical(rot, scale)
+    r64, s64 = E.solve_f64(cov)
+    if through_log:
+        s64 = E.through_log(s64)
+    mine, yard = float(E.cov_err(cov, rot, scale).max()), float(E.cov_err(cov, r64, s64).max())
+    print(f"{what}: worst covariance error {mine * 2 ** 24:.1f} x 2^-24, float64 path {yard * 2 ** 24:.1f} x 2^-24")
+    assert mine <= E.FACTOR * yard, (what, mine, yard)
+    return mine, yard
+
+
+def _check_fdc(fdc_bits, c32, extra=0.0):
+    """f_dc = (c - 0.5) / C0 of the float32 colour c: within 2 ulp of the float64 value (the difference and the quotient round once each)"""
+    want = (c32.astype(np.float64) - 0.5) / np.float64(np.float32(C0))
+    got = fdc_bits.view(np.float32).astype(np.float64)
+    assert (np.abs(got - want) <= 2 * np.spacing(np.abs(want).astype(np.float32)).astype(np.float64) + extra).all()
+
+
+def _check_opacity(op_bits, a32):
+    """opacity = logit(clamp(a, 1e-6, 1 - 1e-6)) of the float32 alpha a: within 2^-22 max(1, |x|) of the float64 value (the quotient carries
+    two roundings and the log one ulp); the clamp's bounds are the float32 constants"""
+    a = np.clip(a32.astype(np.float32), np.float32(1e-6), np.float32(1.0) - np.float32(1e-6)).astype(np.float64)
+    want = np.log(a / (1.0 - a))
+    got = op_bits.view(np.float32).astype(np.float64)
+    assert (np.abs(got - want) <= 2.0 ** -22 * np.maximum(1.0, np.abs(want))).all()
+
+
+# ---- 1. sizes ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def big():
+    g = common.small_scene(70001, 61)
+    g.setflags(write=False)
+    return g
+
+
+@pytest.fixture(scope="module")
+def big_reference(big):
+    """the scene's covariances as an upload makes them, and the float64 path's worst error over them: computed once"""
+    cov = E.upload_cov(big["rot"], big["scale"])
+    r64, s64 = E.solve_f64(cov)
+    return cov, float(E.cov_err(cov, r64, s64).max())
+
+
+@pytest.mark.parametrize("n", [1, 33, 257, 1023, 1024, 1025, 70001])
+def test_sizes_both_formats(big, big_reference, n):
+    g = big[:n]
+    big_cov, big_yard = big_reference
+    with MultiModelViewer() as v:
+        _load(v, g)
+        m = v.models[SRC]
+        pod = _pod(v)
+        out = m.export().gaussians
+        _check_against_pod(out, pod, np.arange(n), n)
+        # a float32 pod holds what was uploaded
+        assert out["pos"].tobytes() == g["pos"].tobytes() and out["color"].tobytes() == g["color"].tobytes() and out["sh"].tobytes() == g["sh"].tobytes()
+        # the fixture is the scene: every size is a prefix of it, judged with the float64 path's worst over the whole of it
+        E.check_canonical(out["rot"], out["scale"])
+        assert np.array_equal(pod[3], big_cov[:n])  # (the device's upload conversion is the restatement's, bit for bit)
+        worst = float(E.cov_err(pod[3], out["rot"], out["scale"]).max())
+        print(f"n={n}: worst covariance error {worst * 2 ** 24:.1f} x 2^-24, float64 path over the scene {big_yard * 2 ** 24:.1f} x 2^-24")
+        assert worst <= E.FACTOR * big_yard
+        assert m.export().gaussians.tobytes() == out.tobytes()  # the same bits on every call
+        data = m.export_ply()
+        assert m.export_ply() == data
+        header, rows = _split_ply(data, n)
+        want_header, want = _split_ply(ply.Gaussians(g).write_ply(), n)  # the host writer on the Gaussians that were uploaded
+        assert header == want_header
+        pos_bits, sh_bits, rot, scale = _rows_of_ply(rows)
+        assert np.array_equal(rows[:, 0:6], want[:, 0:6]) and np.array_equal(rows[:, 9:54], want[:, 9:54])  # x y z, normals 0, f_rest
+        assert pos_bits.tobytes() == g["pos"].tobytes() and sh_bits.tobytes() == g["sh"].tobytes() and not rows[:, 3:6].any()
+        # rot is the record's, w first; scale its logarithm: logf is within 1 ulp of a value below 16, that is 2^-20, and rounds once more
+        assert np.array_equal(rot.view(np.uint32), out["rot"].view(np.uint32))
+        assert (out["scale"] > np.exp(-16.0)).all() and (out["scale"] < np.exp(16.0)).all()
+        assert np.allclose(scale, out["scale"].astype(np.float64), rtol=2 * 2.0 ** -20, atol=0)
+        # f_dc and opacity of the stored colour word: against the float64 value of gaussian_to_vertex's arithmetic
+        c32 = g["color"].astype(np.float32) / np.float32(255.0)
+        _check_fdc(rows[:, 6:9], c32[:, :3])
+        _check_opacity(rows[:, 54], c32[:, 3])
+        # the file loads back
+        back = ply.Gaussians.read_ply(data).gaussians
+        assert back["pos"].tobytes() == g["pos"].tobytes() and back["sh"].tobytes() == g["sh"].tobytes()
+        assert np.array_equal(back["color"], g["color"])
+
+
+# ---- 2. chunks --------------------------------------------------------------------------------------------------------------------
+def test_chunks_are_invisible(big):
+    n = 70001
+    keep = np.random.default_rng(62).random(n) < 0.5
+    keep[3 * 1024:6 * 1024] = False       # three workgroups that keep nothing
+    keep[4 * 1024 + 17] = True            # ... but for one Gaussian
+    keep[20 * 1024:21 * 1024] = True      # a full workgroup
+    keep[68 * 1024:] = False              # an empty tail, the partial last workgroup in it
+    kept = np.nonzero(keep)[0]
+    with MultiModelViewer() as v:
+        _load(v, big)
+        v.models[SRC].gaussian_buffers.mask_buffer.upload(X.words(keep, True))
+        pod = _pod(v)
+        for fmt in (_lib.GSX_EXPORT_GAUSSIANS, _lib.GSX_EXPORT_PLY_VERTICES):
+            outs = []
+            for staging in (1, 3 * 1024 * ROW[fmt], 0):
+                st, count, buf = _export_raw(v, SRC, X.MASKED, 0, fmt, staging)
+                assert st == _lib.GSX_OK and count == kept.size
+                assert (buf[-64:] == 0xA5).all()  # nothing behind the rows
+                outs.append(buf[:-64].tobytes())
+            assert outs[0] == outs[1] == outs[2], fmt
+            if fmt == _lib.GSX_EXPORT_GAUSSIANS:
+                _check_against_pod(np.frombuffer(outs[0], scene.GAUSSIAN_DTYPE), pod, kept, "chunks")
+        assert v.models[SRC].export_ply(X.MASKED, staging_bytes=1) == v.models[SRC].export_ply(X.MASKED)
+
+
+# ---- 3. all eight pod kinds: export, upload again -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("sh,cov", KINDS, ids=KIND_IDS)
+def test_all_eight_pod_kinds_round_trip(sh, cov):
+    """Observed frame distance of the re-uploaded model: see the printed value."""
+    n = 2049
+    g = common.small_scene(n, 63)
+    with MultiModelViewer(sh=sh, cov3d=cov) as v:
+        _load(v, g)
+        pod = _pod(v)
+        out = v.models[SRC].export().gaussians
+        _check_against_pod(out, pod, np.arange(n), (sh, cov))
+        mine, yard = _check_cov(pod[3], out["rot"], out["scale"], f"{sh.name}/{cov.name}")
+        _load(v, out, "again")
+        back = _pod(v, "again")
+        for name, a, b in zip(("pos", "color", "sh"), back, pod):
+            assert a.tobytes() == b.tobytes(), name  # the same pod kind: the same planes, bit for bit
+        den = np.abs(pod[3].astype(np.float64)).max(axis=1)
+        diff = np.abs(back[3].astype(np.float64) - pod[3].astype(np.float64)).max(axis=1)
+        if cov == Cov3dKind.Single:
+            assert (diff <= E.FACTOR * yard * den).all()
+        else:  # requantised: one binary16 step of an entry (at most 2^-10 of the largest) on top of the bound
+            step = np.maximum(HALF_STEP * np.abs(pod[3].astype(np.float64)), 2.0 ** -24)  # per entry
+            assert (np.abs(back[3].astype(np.float64) - pod[3].astype(np.float64)) <= (E.FACTOR * yard * den)[:, None] + step).all()
+        if (sh, cov) in ((ShKind.Single, Cov3dKind.Single), (ShKind.Norm8, Cov3dKind.Half)):
+            want = _frames(v, [SRC])
+            assert want[0][..., :3].max() > 0
+            worst = max(float(np.abs(a - b).max()) for a, b in zip(_frames(v, ["again"]), want))
+            print(f"{sh.name}/{cov.name}: re-uploaded frame L-inf {worst:.2e}")
+            assert worst <= FRAME_TOL
+
+
+def test_recompress_norm8_half_into_f32():
+    n = 2049
+    g = common.small_scene(n, 64)
+    with MultiModelViewer(sh=ShKind.Norm8, cov3d=Cov3dKind.Half) as v, MultiModelViewer() as f32:
+        _load(v, g)
+        out = v.models[SRC].export().gaussians
+        _load(f32, out)
+        want = _frames(v, [SRC])
+        assert want[0][..., :3].max() > 0
+        worst = max(float(np.abs(a - b).max()) for a, b in zip(_frames(f32, [SRC]), want))
+        print(f"Norm8/Half exported into f32: frame L-inf {worst:.2e}")
+        assert worst <= FRAME_TOL
+        # the f32 model holds the dequantised values exactly
+        a, b = _pod(f32), _pod(v)
+        assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes() and a[2].tobytes() == b[2].tobytes()
+
+
+# ---- 4. filters -------------------------------------------------------------------------------------------------------------------
+def _filter_model(v, n, seed=65):
+    rng = np.random.default_rng(seed)
+    g = common.small_scene(n, seed)
+    mask, sel = rng.random(n) < 0.6, rng.random(n) < 0.5
+    edits = query.default_edits(n)
+    edits["flag"][0::3] = int(F.ENABLED | F.HIDDEN)
+    edits["flag"][1::3] = int(F.ENABLED | F.OVERRIDE_COLOR)
+    edits["flag"][5::7] |= int(F.HIDDEN)  # (HIDDEN without ENABLED hides nothing)
+    edits["color"] = rng.random((n, 3)).astype(np.float32)
+    edits["alpha"] = rng.choice(np.float32([1.0, 0.5, 0.25]), n)
+    _load(v, g)
+    bufs = v.models[SRC].gaussian_buffers
+    bufs.mask_buffer.upload(X.words(mask, True))  # garbage in the last word's high bits
+    bufs.selection_buffer.upload(X.words(sel, True))
+    bufs.gaussians_edit_buffer.upload(edits)
+    return g, mask, sel, edits
+
+
+def test_filters_against_the_restatement():
+    n = 4097
+    with MultiModelViewer() as v:
+        g, mask, sel, edits = _filter_model(v, n)
+        m = v.models[SRC]
+        pod = _pod(v)
+        stored = m.gaussian_buffers.gaussians_edit_buffer.download()["flag"]
+        for flt in (X.MASKED, X.SKIP_HIDDEN, X.SELECTED, X.MASKED | X.SKIP_HIDDEN, X.MASKED | X.SKIP_HIDDEN | X.SELECTED, 0):
+            for invert in (False, True):
+                kept = X.kept(n, flt, X.INVERT if invert else 0, mask, sel, stored)
+                out = m.export(flt, invert=invert).gaussians
+                _check_against_pod(out, pod, kept, (flt, invert))
+                header, rows = _split_ply(m.export_ply(flt, invert=invert), kept.size)
+                assert f"element vertex {kept.size}\n".encode() in header
+                assert rows[:, 0:3].tobytes() == np.ascontiguousarray(pod[0][kept]).tobytes()
+        # SKIP_HIDDEN reads the stored flag, whatever gsx_model_show_unedited says
+        v.show_unedited(SRC, True)
+        assert m.export(X.SKIP_HIDDEN).gaussians.shape[0] == X.kept(n, X.SKIP_HIDDEN, 0, edit_flags=stored).size
+        v.show_unedited(SRC, False)
+    # absent planes: no mask = all, no edit records = none hidden, no selection = none (and all of them when inverted)
+    with MultiModelViewer() as v:
+        _load(v, g)
+        m = v.models[SRC]
+        assert m.export(X.MASKED | X.SKIP_HIDDEN).gaussians.shape[0] == n
+        assert m.export(X.SELECTED).gaussians.shape[0] == 0
+        assert m.export(X.SELECTED, invert=True).gaussians.shape[0] == n
+        assert m.export(X.MASKED, bake_edits=True).gaussians.tobytes() == m.export().gaussians.tobytes()  # no edit records: nothing to bake
+
+
+# ---- 5. edits and PLY -------------------------------------------------------------------------------------------------------------
+def test_edits_and_ply_against_the_host_writer():
+    n = 3000
+    with MultiModelViewer() as v:
+        g, mask, sel, edits = _filter_model(v, n, 66)
+        edits["flag"][2::9] = 0  # HSV edits too (ENABLED without OVERRIDE_COLOR), with contrast, exposure and gamma
+        edits["flag"][2::9] = int(F.ENABLED)
+        edits["color"][2::9] = np.float32([0.3, 0.8, 1.1])
+        edits["contrast"][2::9] = np.float32(0.2)
+        edits["exposure"][2::9] = np.float32(-0.5)
+        edits["gamma"][2::9] = np.float32(2.2)
+        m = v.models[SRC]
+        m.gaussian_buffers.gaussians_edit_buffer.upload(edits)
+        flt = X.MASKED | X.SKIP_HIDDEN
+        kept = X.kept(n, flt, 0, mask, sel, edits["flag"])
+        want_file = ply.Gaussians(g).write_ply(X.words(mask), edits)
+        got_file = m.export_ply(flt, bake_edits=True)
+        assert len(got_file) == len(want_file)
+        (wh, want), (gh, got) = _split_ply(want_file, kept.size), _split_ply(got_file, kept.size)
+        assert gh == wh  # the header bytes, the count in them
+        assert np.array_equal(got[:, 0:6], want[:, 0:6]) and np.array_equal(got[:, 9:54], want[:, 9:54])  # x y z, normals, f_rest
+        # f_dc within 2 ulp, opacity within 2^-22 max(1, |x|): both sides against the float64 value, from the edited float32 colour
+        e = edits[kept]
+        on = (e["flag"] & 1) != 0
+        ov = on & ((e["flag"] & int(F.OVERRIDE_COLOR)) != 0)
+        hsv = on & ~ov
+        assert ov.any() and hsv.any() and (~on).any()
+        f32 = np.float32
+        c32 = g["color"][kept].astype(f32) / f32(255.0)
+        rgb32 = c32[:, :3].copy()
+        rgb32[ov] = e["color"][ov]
+        a32 = c32[:, 3].copy()
+        a32[on] = np.clip(a32[on] * e["alpha"][on], f32(0), f32(1))  # em_apply_edit's last line, in float32
+        known = ~hsv  # stored and overridden colours are float32 values the test knows exactly
+        # the HSV rows: the float64 restatement of spec §7 (tests/test_edit_cpu.py), with the tolerance that file gives the float32
+        # chain of colour ops (rtol 2e-5, atol 2e-6 on the colour), carried through the division by C0
+        from tests.test_edit_cpu import edit_f64
+
+        hsv_rows = np.nonzero(hsv)[0]
+        rgb64 = np.array([edit_f64(query.GaussianEditPod(int(e["flag"][i]), tuple(float(x) for x in e["color"][i]), float(e["contrast"][i]),
+                                                         float(e["exposure"][i]), float(e["gamma"][i]), float(e["alpha"][i])),
+                                   c32[i, :3].astype(np.float64), float(c32[i, 3]))[0] for i in hsv_rows])
+        for side in (got, want):
+            _check_fdc(side[known, 6:9], rgb32[known])
+            _check_opacity(side[:, 54], a32)
+            fdc = side[hsv, 6:9].view(np.float32).astype(np.float64)
+            assert (np.abs(fdc - (rgb64 - 0.5) / C0) <= (2e-5 * np.abs(rgb64) + 2e-6) / C0 + 2 * np.spacing(np.abs(fdc).astype(np.float32))).all()
+        # scale and rot columns: through the covariance bound
+        _, _, rot, scale = _rows_of_ply(got)
+        pod = _pod(v)
+        _check_cov(pod[3][kept], rot, scale.astype(np.float32), "ply rows", through_log=True)
+        # the gsx_gaussian format: the UNORM8 rule on the same edited float colour
+        rec = m.export(flt, bake_edits=True).gaussians
+        stored = m.export(flt).gaussians
+        assert np.array_equal(stored["color"], g["color"][kept])  # without the flag: the stored colour, edited or not
+        assert rec["pos"].tobytes() == stored["pos"].tobytes() and rec["sh"].tobytes() == stored["sh"].tobytes()
+        assert rec["rot"].tobytes() == stored["rot"].tobytes() and rec["scale"].tobytes() == stored["scale"].tobytes()
+        assert np.array_equal(rec["color"][~on], g["color"][kept][~on])
+        unorm8 = lambda x: np.floor(np.clip(x, f32(0), f32(1)) * f32(255.0) + f32(0.5)).astype(np.uint8)  # noqa: E731  (float32, as the library)
+        assert np.array_equal(rec["color"][ov][:, :3], unorm8(e["color"][ov]))
+        assert np.array_equal(rec["color"][on][:, 3], unorm8(a32[on]))
+        assert (np.abs(rec["color"][hsv][:, :3].astype(np.float64) - np.floor(255.0 * np.clip(rgb64, 0, 1) + 0.5)) <= 1).all()
+        assert (rec["color"] != stored["color"]).any()
+        # hidden Gaussians are dropped only by SKIP_HIDDEN
+        assert m.export(X.MASKED, bake_edits=True).gaussians.shape[0] == int(mask.sum()) > kept.size
+
+
+# ---- 6. degenerates ---------------------------------------------------------------------------------------------------------------
+def test_degenerates_on_the_device():
+    n = 1100
+    g = common.small_scene(n, 67)
+    g["scale"][0:100] = g["scale"][0:100, :1]                      # spheres
+    g["scale"][100:200, 2] = 0                                      # one zero scale
+    g["scale"][200:300] = 0                                         # all-zero covariance
+    g["pos"][300] = [np.nan, np.inf, -0.0]                          # carried as bits
+    with MultiModelViewer() as v:
+        _load(v, g)
+        pod = _pod(v)
+        out = v.models[SRC].export().gaussians
+        _check_against_pod(out, pod, np.arange(n))
+        assert out["pos"][300].tobytes() == g["pos"][300].tobytes()
+        E.check_canonical(out["rot"], out["scale"])
+        _, yard = _check_cov(pod[3], out["rot"], out["scale"], "degenerates")
+        assert (out["scale"][200:300] == 0).all() and np.array_equal(out["rot"][200:300], np.tile(np.float32([0, 0, 0, 1]), (100, 1)))
+        flat = out["scale"][100:200].astype(np.float64)
+        assert (flat[:, 2] ** 2 <= E.FACTOR * yard * flat[:, 0] ** 2).all()  # (0, or the root of a rounding-sized eigenvalue)
+        rows = _split_ply(v.models[SRC].export_ply(), n)[1].view(np.float32)
+        assert (rows[200:300, 55:58] == -np.inf).all()  # a zero scale writes -inf
+    # a Half covariance that overflowed to inf: no solve, the identity rotation, the diagonal's roots
+    with MultiModelViewer(sh=ShKind.Remove, cov3d=Cov3dKind.Half) as v:
+        h = g[:64].copy()
+        h["scale"][:8] = np.float32([300.0, 2.0, 0.5])  # 300^2 > 65504
+        h["rot"][:8] = np.float32([0, 0, 0, 1])
+        h["scale"][8:24] = np.float32([1.0, 1.0, 0.001])  # thin and turned: binary16 rounding (2^-11) outweighs the smallest eigenvalue (1e-6)
+        _load(v, h)
+        pod = _pod(v)
+        assert np.isinf(pod[3][:8, 0]).all() and np.isfinite(pod[3][8:]).all()
+        out = v.models[SRC].export().gaussians
+        assert np.array_equal(out["rot"][:8], np.tile(np.float32([0, 0, 0, 1]), (8, 1)))
+        assert np.isinf(out["scale"][:8, 0]).all() and np.array_equal(out["scale"][:8, 1:], np.tile(np.float32([2.0, 0.5]), (8, 1)))
+        assert not out["sh"].any()
+        E.check_canonical(out["rot"][8:], out["scale"][8:])
+        # the comparison is made on the dequantised stored covariance; an indefinite one (Half rounding) gives scale 0 and is left out
+        S = np.zeros((56, 3, 3))
+        c = pod[3][8:].astype(np.float64)
+        S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2] = (c[:, k] for k in range(6))
+        lam_min = np.linalg.eigvalsh(S + S.transpose(0, 2, 1) - S * np.eye(3))[:, 0]
+        definite = lam_min > 0
+        assert definite.sum() > 8
+        _, yard = _check_cov(pod[3][8:][definite], out["rot"][8:][definite], out["scale"][8:][definite], "Half, definite")
+        # an eigenvalue that is negative beyond the solve's own error gives scale 0
+        indefinite = lam_min < -E.FACTOR * yard * np.abs(c).max(axis=1)
+        assert indefinite.any() and (out["scale"][8:][indefinite][:, 2] == 0).all()
+
+
+# ---- 7. after merge ---------------------------------------------------------------------------------------------------------------
+def test_export_of_a_merged_model():
+    """The case the feature exists for: a merged model has baked planes no host array ever held."""
+    n = 1500
+    q = np.random.default_rng(68).normal(size=4)
+    mt = (np.float32([0.3, -0.2, 0.5]), (q / np.linalg.norm(q)).astype(np.float32), np.float32([1.3, 0.7, 0.9]))
+    with MultiModelViewer() as v:
+        _load(v, common.small_scene(n, 68), "a")
+        _load(v, common.small_scene(n, 69), "b", mt)
+        assert v.merge("m", ["a", "b"])[0] == 2 * n
+        assert v.models["a"].extract("x", 0) == n
+        want = _frames(v, ["m"])
+        assert want[0][..., :3].max() > 0
+        data = v.models["m"].export_ply()
+        back = ply.Gaussians.read_ply(data).gaussians
+        assert back.shape[0] == 2 * n
+        _load(v, back, "again")
+        worst = max(float(np.abs(a - b).max()) for a, b in zip(_frames(v, ["again"]), want))
+        print(f"merged model through export_ply and read_ply: frame L-inf {worst:.2e}")
+        # (the PLY route rounds the colour through f_dc and the scales through log / exp; the records route below does not)
+        assert worst <= FRAME_TOL
+        out = v.models["m"].export().gaussians
+        _check_against_pod(out, _pod(v, "m"), np.arange(2 * n), "merged")
+        _load(v, out, "records")
+        worst = max(float(np.abs(a - b).max()) for a, b in zip(_frames(v, ["records"]), want))
+        print(f"merged model through export and update_range: frame L-inf {worst:.2e}")
+        assert worst <= FRAME_TOL
+        # an extracted model exports its source's kept rows
+        assert v.models["x"].export().gaussians.tobytes() == v.models["a"].export().gaussians.tobytes()
+
+
+# ---- 8. contract ------------------------------------------------------------------------------------------------------------------
+def test_count_capacity_and_errors():
+    n = 2 * X.GROUP + 77
+    with MultiModelViewer() as v, MultiModelViewer() as other:
+        g, mask, sel, edits = _filter_model(v, n, 70)
+        L = v._L
+        kept = X.kept(n, X.MASKED, 0, mask, sel, edits["flag"])
+        desc, count = _lib.ExportDesc(X.MASKED, 0, 0, 0, 0), C.c_uint64()
+        # the count-only call
+        assert L.gsx_model_export(v._h, SRC.encode(), C.byref(desc), None, 0, C.byref(count)) == _lib.GSX_OK and count.value == kept.size
+        # a capacity one byte short: the status, the needed count, nothing written
+        st, needed, buf = _export_raw(v, SRC, X.MASKED, capacity=224 * kept.size - 1)
+        assert st == _lib.GSX_ERR_INVALID_ARG and needed == kept.size and (buf == 0xA5).all()
+        assert b"gsx_model_export" in L.gsx_last_error_string()
+        size = C.c_uint64()
+        assert L.gsx_model_export_ply(v._h, SRC.encode(), C.byref(desc), None, 0, C.byref(size)) == _lib.GSX_OK
+        full = np.full(size.value, 0xA5, np.uint8)
+        assert L.gsx_model_export_ply(v._h, SRC.encode(), C.byref(desc), full.ctypes.data, size.value - 1, C.byref(size)) == _lib.GSX_ERR_INVALID_ARG
+        assert (full == 0xA5).all() and size.value == full.size
+        # `format` is ignored by export_ply
+        desc.format = 77
+        assert L.gsx_model_export_ply(v._h, SRC.encode(), C.byref(desc), full.ctypes.data, full.size, C.byref(size)) == _lib.GSX_OK
+        assert full.tobytes() == v.models[SRC].export_ply(X.MASKED)
+        # a count of 0: GSX_OK, nothing written
+        st, zero, buf = _export_raw(v, SRC, 0, X.INVERT)
+        assert st == _lib.GSX_OK and zero == 0 and (buf == 0xA5).all()
+        assert v.models[SRC].export(0, invert=True).gaussians.shape[0] == 0
+        empty = v.models[SRC].export_ply(0, invert=True)
+        assert empty == ply.Gaussians(g[:0]).write_ply() and ply.Gaussians.read_ply(empty).gaussians.shape[0] == 0
+        # errors
+        for kw, status in ((dict(filter=8), _lib.GSX_ERR_INVALID_ARG), (dict(flags=2), _lib.GSX_ERR_INVALID_ARG), (dict(flags=8), _lib.GSX_ERR_INVALID_ARG),
+                           (dict(fmt=2), _lib.GSX_ERR_INVALID_ARG), (dict(reserved=1), _lib.GSX_ERR_INVALID_ARG)):
+            st, _, _ = _export_raw(v, SRC, **kw)
+            assert st == status and b"gsx_model_export" in L.gsx_last_error_string(), kw
+        assert _export_raw(v, "nope")[0] == _lib.GSX_ERR_NOT_FOUND
+        desc = _lib.ExportDesc(0, 0, 0, 0, 0)
+        for fn in (L.gsx_model_export, L.gsx_model_export_ply):
+            assert fn(v._h, None, C.byref(desc), None, 0, C.byref(count)) == _lib.GSX_ERR_INVALID_ARG
+            assert fn(v._h, SRC.encode(), None, None, 0, C.byref(count)) == _lib.GSX_ERR_INVALID_ARG
+            assert fn(v._h, SRC.encode(), C.byref(desc), None, 0, None) == _lib.GSX_ERR_INVALID_ARG
+            assert fn(v._h, b"nope", C.byref(desc), None, 0, C.byref(count)) == _lib.GSX_ERR_NOT_FOUND
+        bad = _lib.ExportDesc(0, 2, 0, 0, 0)
+        assert L.gsx_model_export_ply(v._h, SRC.encode(), C.byref(bad), None, 0, C.byref(count)) == _lib.GSX_ERR_INVALID_ARG
+        # a sharded model; a viewer with a communicator
+        _frames(v, [SRC], poses=(5,))
+        _load(v, g[:50], "b")
+        v.shard_set_limits("b", np.full((H + 15) // 16 * ((W + 15) // 16), 0x40400000, np.uint32))
+        with pytest.raises(GsxError) as e:
+            v.models["b"].export()
+        assert e.value.status == _lib.GSX_ERR_UNSUPPORTED and "shard" in str(e.value)
+        _load(other, g[:50], "a")
+        other.comm_init_group(CommGroup(1), 0)
+        for call in (other.models["a"].export, other.models["a"].export_ply):
+            with pytest.raises(GsxError) as e:
+                call()
+            assert e.value.status == _lib.GSX_ERR_UNSUPPORTED and "communicator" in str(e.value)
+
+
+def test_the_source_is_untouched():
+    n = 3000
+    with MultiModelViewer() as v, MultiModelViewer() as twin:
+        for vv in (v, twin):
+            g, mask, sel, edits = _filter_model(vv, n, 71)
+
+        def state(vv):
+            bufs = vv.models[SRC].gaussian_buffers
+            return [a.tobytes() for a in _pod(vv)] + [bufs.mask_buffer.download().tobytes(), bufs.selection_buffer.download().tobytes(),
+                                                      bufs.gaussians_edit_buffer.download().tobytes()]
+
+        before = state(v)
+        assert np.array_equal(_frames(v, [SRC], poses=(5,))[0], _frames(twin, [SRC], poses=(5,))[0])
+        m = v.models[SRC]
+        assert m.export(X.MASKED | X.SKIP_HIDDEN, bake_edits=True).gaussians.shape[0] > 0
+        assert len(m.export_ply(X.SELECTED, invert=True, staging_bytes=1)) > 0
+        assert state(v) == before == state(twin)
+        # src's next, speculated frames are the frames of the twin that was never exported from
+        for a, b in zip(_frames(v, [SRC], poses=(6, 7)), _frames(twin, [SRC], poses=(6, 7))):
+            assert np.array_equal(a, b)
+
+
+def _depth_lane_sequence(g, export_at):
+    """depth-tested frames on two lanes; at `export_at` two frames are in flight (rendered, not downloaded) when the export is issued"""
+    frames, exported = [], None
+    with MultiModelViewer() as v:
+        v.set_render_options(frames_in_flight=2)
+        _load(v, g)
+        v.set_depth_test(DepthCompare.Less)
+        depth = np.ones((H, W), np.float32)
+        depth[:, : W // 2] = 0.9
+        v.update_depth_buffer(depth)
+        for pose in range(1, 9):
+            v.update_camera(camera.orbit_pose(pose), (W, H))
+            v.update_gaussian_transform(1.0, GaussianDisplayMode.Splat, GaussianShDegree.new(3), False)
+            v.render_frame([SRC])
+            if pose in (4, 5):  # left in flight, one on each lane
+                if pose == 5 and export_at:
+                    exported = v.models[SRC].export_ply(staging_bytes=1)
+                continue
+            frames.append(v.download_framebuffer())
+        idle = v.models[SRC].export_ply()
+    return frames, exported, idle
+
+
+def test_export_behind_depth_tested_frames_in_flight():
+    g = common.small_scene(2500, 72)
+    with_export, exported, idle = _depth_lane_sequence(g, True)
+    without, _, idle2 = _depth_lane_sequence(g, False)
+    assert exported == idle == idle2
+    assert len(with_export) == 6 and with_export[0][..., :3].max() > 0
+    for k, (a, b) in enumerate(zip(with_export, without)):
+        assert np.array_equal(a, b), k
+
+
+# ---- 9. memory --------------------------------------------------------------------------------------------------------------------
+def test_device_memory_returns_after_close():
+    start = viewer_mod.device_bytes()
+    g = common.small_scene(5000, 73)
+    with MultiModelViewer() as v:
+        _load(v, g)
+        loaded = viewer_mod.device_bytes()
+        v.models[SRC].export()
+        held = viewer_mod.device_bytes() - loaded
+        assert held >= 2 * 224 * 5000  # the two staging buffers (and the keep workspace) are counted
+        v.models[SRC].export_ply(staging_bytes=1)
+        assert len(v.models[SRC].export_ply()) > 248 * 5000
+    assert viewer_mod.device_bytes() == start

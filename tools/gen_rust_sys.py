@@ -77,6 +77,9 @@ pub const GSX_BOUNDS_SELECTED: u32 = 4;
 pub const GSX_EXTRACT_INVERT: u32 = 1;
 pub const GSX_EXTRACT_DROP_EDITS: u32 = 2;
 pub const GSX_MERGE_MAX_SOURCES: u32 = 64;
+pub const GSX_EXPORT_GAUSSIANS: u32 = 0;
+pub const GSX_EXPORT_PLY_VERTICES: u32 = 1;
+pub const GSX_EXPORT_BAKE_EDITS: u32 = 4;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -162,6 +165,10 @@ pub struct gsx_model_bounds_t {
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_extract_desc { pub filter: u32, pub flags: u32 }
+/// what gsx_model_export writes (filter: GSX_BOUNDS_*; flags: GSX_EXTRACT_INVERT, GSX_EXPORT_BAKE_EDITS; format: GSX_EXPORT_*)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_export_desc { pub filter: u32, pub flags: u32, pub format: u32, pub reserved: u32, pub staging_bytes: u64 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }

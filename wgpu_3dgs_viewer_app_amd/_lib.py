@@ -48,6 +48,7 @@ EXPORTS = (
     "gsx_viewer_comm_info",
     "gsx_bounds_desc_default", "gsx_model_bounds",
     "gsx_extract_desc_default", "gsx_model_extract", "gsx_model_merge",
+    "gsx_export_desc_default", "gsx_model_export", "gsx_model_export_ply",
 )
 
 
@@ -88,6 +89,17 @@ class ModelBounds(C.Structure):
 GSX_EXTRACT_INVERT, GSX_EXTRACT_DROP_EDITS = 1, 2
 #: most sources one gsx_model_merge call takes
 GSX_MERGE_MAX_SOURCES = 64
+
+
+#: gsx_export_desc.format, and the flag that gsx_model_export takes beside GSX_EXTRACT_INVERT
+GSX_EXPORT_GAUSSIANS, GSX_EXPORT_PLY_VERTICES = 0, 1
+GSX_EXPORT_BAKE_EDITS = 4
+
+
+class ExportDesc(C.Structure):
+    """``gsx_export_desc`` (24 bytes): which Gaussians are exported (``GSX_BOUNDS_*``), ``GSX_EXTRACT_INVERT | GSX_EXPORT_BAKE_EDITS``,
+    the row format (``GSX_EXPORT_*``) and the size of one device staging buffer (0: the library's default)."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("format", C.c_uint32), ("reserved", C.c_uint32), ("staging_bytes", C.c_uint64)]
 
 
 class ExtractDesc(C.Structure):
@@ -324,6 +336,9 @@ def load() -> C.CDLL:
         "gsx_model_bounds": ([vp, cp, C.POINTER(BoundsDesc), C.POINTER(ModelBounds)], C.c_int32),
         "gsx_extract_desc_default": ([C.POINTER(ExtractDesc)], None),
         "gsx_model_extract": ([vp, cp, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_export_desc_default": ([C.POINTER(ExportDesc)], None),
+        "gsx_model_export": ([vp, cp, C.POINTER(ExportDesc), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_model_export_ply": ([vp, cp, C.POINTER(ExportDesc), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int32),
         "gsx_model_merge": ([vp, C.POINTER(C.c_char_p), C.c_uint32, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)

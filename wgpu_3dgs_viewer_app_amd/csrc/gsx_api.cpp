@@ -336,6 +336,14 @@ void gsx_viewer_destroy(gsx_viewer* v) {
     if (v->lane_event) (void)hipEventDestroy(v->lane_event);
     if (v->depth_event) (void)hipEventDestroy(v->depth_event);
     for (hipStream_t ps : v->parked_streams) (void)hipStreamDestroy(ps);
+    if (v->export_stream) {  // gsx_model_export's copy stream and events (the staging buffers go with the viewer's other DevBufs)
+        (void)gsx::op::StreamSynchronize(v->export_stream);
+        for (int b = 0; b < 2; ++b) {
+            if (v->export_written[b]) (void)hipEventDestroy(v->export_written[b]);
+            if (v->export_copied[b]) (void)hipEventDestroy(v->export_copied[b]);
+        }
+        (void)hipStreamDestroy(v->export_stream);
+    }
     if (v->h_shard_verdict) (void)hipHostFree(v->h_shard_verdict);
     if (v->h_verdict_ring) (void)hipHostFree(v->h_verdict_ring);
     for (auto& t : v->timers) {

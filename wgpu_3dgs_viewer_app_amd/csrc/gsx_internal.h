@@ -988,6 +988,13 @@ struct MergeBake {
 hipError_t launch_merge_bake(hipStream_t s, int sh_kind, int cov_kind, uint64_t n_src, uint64_t n_dst, uint64_t dst_offset, const uint32_t* keep,
                              const uint32_t* bases, const ExtractPlanes& src, const ExtractPlanes& dst, const MergeBake& bake);
 
+// Model export (kernels_export.hip; gsx_model_export): the rows of the kept Gaussians of the source workgroups [group0, group0 +
+// n_groups), in `format` (GSX_EXPORT_*), into `out` starting at the chunk's first kept Gaussian: row_base = bases[group0].  `out`
+// holds at least bases[group0 + n_groups] - row_base rows (the total in place of bases[] past the last group).  src is only read;
+// its edit planes are present exactly when edits are to be baked.
+hipError_t launch_export_rows(hipStream_t s, int sh_kind, int cov_kind, uint32_t format, uint64_t n_src, uint32_t group0, uint32_t n_groups, uint32_t row_base,
+                              const uint32_t* keep, const uint32_t* bases, const ExtractPlanes& src, void* out);
+
 // Compositing and resolve.
 // carry: continue from the (C, T) already in fb (later slabs / models behind); done: saturated-tile bitmap
 // (read to skip tiles when carrying, updated when a tile saturates; nullable).

@@ -18,6 +18,7 @@
 
 namespace gsx {
 gsx_status fail(gsx_status st, const char* fmt, ...);
+std::string ply_header(uint64_t count);
 }
 
 namespace {
@@ -77,6 +78,14 @@ void gaussian_to_vertex(const gsx_gaussian* g, float v[62]) {
 }
 
 }  // namespace
+
+// the header of a binary INRIA file of `count` vertices: the one writer (gsx_ply_write here, gsx_model_export_ply in gsx_api_export.cpp)
+std::string gsx::ply_header(uint64_t count) {
+    std::string header = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(count) + "\n";
+    for (int k = 0; k < 62; ++k) header += std::string("property float ") + kProps[k] + "\n";
+    header += "end_header\n";
+    return header;
+}
 
 extern "C" {
 
@@ -216,9 +225,7 @@ gsx_status gsx_ply_write(const gsx_gaussian* g, uint64_t n, const uint32_t* mask
     };
     uint64_t kept = 0;
     for (uint64_t i = 0; i < n; ++i) kept += keep(i);
-    std::string header = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(kept) + "\n";
-    for (int k = 0; k < 62; ++k) header += std::string("property float ") + kProps[k] + "\n";
-    header += "end_header\n";
+    const std::string header = gsx::ply_header(kept);
     *out_size = header.size() + kept * 248ull;
     if (!out) return GSX_OK;
     if (capacity < *out_size) return fail(GSX_ERR_INVALID_ARG, "gsx_ply_write: buffer too small (%llu < %llu)", (unsigned long long)capacity, (unsigned long long)*out_size);

@@ -503,6 +503,12 @@ struct gsx_viewer {
     // (popcount partials, their scan), allocated by the first call and grown when a larger model is extracted from.  gsx_model_merge
     // (gsx_api_merge.cpp) lays one such region per source behind its array of totals.  Nothing a frame reads
     DevBuf extract_ws;
+    // gsx_model_export (gsx_api_export.cpp; owner only): two staging buffers of rows, so that the kernel of one chunk runs while the
+    // chunk before it is copied to the host on export_stream; an event per buffer for "rows written" and one for "rows copied".
+    // Allocated by the first call that writes rows, grown when a call asks for larger staging, freed with the viewer
+    DevBuf export_stage[2];
+    hipStream_t export_stream = nullptr;
+    hipEvent_t export_written[2]{}, export_copied[2]{};
 };
 
 namespace gsx {

@@ -320,6 +320,38 @@ class MultiModelViewerModel:
             self._v.models[dst_key] = MultiModelViewerModel(self._v, dst_key)
         return int(count.value)
 
+    def _export_desc(self, filter, invert, bake_edits, fmt, staging_bytes):  # noqa: A002
+        return _lib.ExportDesc(int(filter), (_lib.GSX_EXTRACT_INVERT if invert else 0) | (_lib.GSX_EXPORT_BAKE_EDITS if bake_edits else 0),
+                               fmt, 0, int(staging_bytes))
+
+    def export(self, filter: int = 0, invert: bool = False, bake_edits: bool = False, staging_bytes: int = 0):  # noqa: A002
+        """``gsx_model_export``: the Gaussians of this model that pass ``filter`` (``_lib.GSX_BOUNDS_*`` bits, ``extract``'s meaning;
+        ``invert``: exactly those that do not) as ``ply.Gaussians``, built on the device from the resident planes: positions, colours
+        and SH as stored (dequantised exactly), rotation and scale solved from the stored covariance.  Model space: the model
+        transform is not applied (``viewer.merge`` bakes it).  ``bake_edits``: enabled edit records are baked into the colours as
+        ``write_ply`` does.  The way out for a model that only the device holds, and from one pod kind to another."""
+        from .ply import Gaussians
+        from .scene import GAUSSIAN_DTYPE
+
+        desc = self._export_desc(filter, invert, bake_edits, _lib.GSX_EXPORT_GAUSSIANS, staging_bytes)
+        count = C.c_uint64()
+        _lib.check(self._v._L.gsx_model_export(self._v._h, self._key.encode(), C.byref(desc), None, 0, C.byref(count)))
+        out = np.empty(count.value, GAUSSIAN_DTYPE)  # every byte is written by the library
+        if count.value:
+            _lib.check(self._v._L.gsx_model_export(self._v._h, self._key.encode(), C.byref(desc), out.ctypes.data, out.nbytes, C.byref(count)))
+        return Gaussians(out)
+
+    def export_ply(self, filter: int = 0, invert: bool = False, bake_edits: bool = False, staging_bytes: int = 0) -> bytes:  # noqa: A002
+        """``gsx_model_export_ply``: the same Gaussians as a binary INRIA PLY file, ``Gaussians.write_ply``'s header and rows.  The
+        reference's ``write_ply(edits, mask)`` is ``export_ply(MASKED | SKIP_HIDDEN, bake_edits=True)``; ``Gaussians.read_ply`` loads
+        the result back."""
+        desc = self._export_desc(filter, invert, bake_edits, _lib.GSX_EXPORT_PLY_VERTICES, staging_bytes)
+        size = C.c_uint64()
+        _lib.check(self._v._L.gsx_model_export_ply(self._v._h, self._key.encode(), C.byref(desc), None, 0, C.byref(size)))
+        out = np.empty(size.value, np.uint8)
+        _lib.check(self._v._L.gsx_model_export_ply(self._v._h, self._key.encode(), C.byref(desc), out.ctypes.data, out.size, C.byref(size)))
+        return out.tobytes()
+
 
 class _Preprocessor:
     def __init__(self, v):
