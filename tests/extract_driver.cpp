@@ -3,6 +3,8 @@
 // stdin:  "n <N>", "filter <GSX_BOUNDS_* bits>", "invert <0|1>", then the planes that exist, each on one line:
 //         "mask <ceil(N/32) hex words>", "sel <hex words>", "edited <hex words>" with "flags <N stored edit flags>".
 // stdout: "count <kept>", then "kept <source index of dst 0> <of dst 1> ...": the new model's Gaussians in dst order.
+// Or stdin "layout <N of source 0> <N of source 1> ...": stdout "size <workspace bytes>", then per source "source<s> <byte offset
+// of its bases> <of its partials> <of its keep words>" (extract_ws_layout; the totals lie at 8 s).
 // The three steps are the kernels': a keep word per 32 Gaussians, a popcount partial per kExtractGroup, their exclusive scan, and
 // dst index = group base + ranks of the group's preceding words + rank in the word.  Every dst index must be written exactly once.
 #include <stdio.h>
@@ -26,6 +28,21 @@ static std::vector<uint32_t> numbers(const char* s, int base) {
     return v;
 }
 
+// the workspace of the kept-set pass over sources of these sizes: the total size, then every source's three byte offsets
+static int layout(const char* sizes) {
+    std::vector<uint64_t> n;
+    char* end = nullptr;
+    for (const char* s = sizes;; s = end) {
+        const unsigned long long x = strtoull(s, &end, 10);
+        if (end == s) break;
+        n.push_back(x);
+    }
+    std::vector<gsx::ExtractRegion> r(n.size());
+    printf("size %zu\n", gsx::extract_ws_layout(n.data(), (uint32_t)n.size(), r.data()));
+    for (size_t s = 0; s < n.size(); ++s) printf("source%zu %zu %zu %zu\n", s, r[s].bases, r[s].partials, r[s].keep);
+    return 0;
+}
+
 int main() {
     uint64_t n = 0;
     uint32_t filter = 0, invert = 0;
@@ -45,6 +62,7 @@ int main() {
         else if (!strncmp(s, "sel ", 4)) sel = numbers(s + 4, 16), have_sel = true;
         else if (!strncmp(s, "edited ", 7)) edited = numbers(s + 7, 16), have_edits = true;
         else if (!strncmp(s, "flags ", 6)) flags = numbers(s + 6, 10);
+        else if (!strncmp(s, "layout ", 7)) return layout(s + 7);
         line.clear();
     }
     const uint64_t n_words = (n + 31) / 32, groups = gsx::extract_groups(n);

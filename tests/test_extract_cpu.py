@@ -138,3 +138,27 @@ def test_patterns_across_words_and_groups(driver):
         for invert in (False, True):
             got = _play(driver, n, X.MASKED, invert, X.words(mask, True))
             assert np.array_equal(got, np.nonzero(~mask if invert else mask)[0]), (name, invert)
+
+
+# ---- the workspace of the kept-set pass (extract_ws_layout) ----
+LAYOUTS = [[0], [1], [32], [33], [1024], [1025], [263169], [1, 0, 1025], [1024] * 16]
+
+
+@pytest.mark.parametrize("sizes", LAYOUTS, ids=lambda s: "x".join(map(str, s)) if len(s) < 4 else f"{s[0]}x{len(s)}")
+def test_workspace_layout(driver, sizes):
+    r = subprocess.run([driver], input="layout " + " ".join(map(str, sizes)) + "\n", capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stderr == "", r.stderr
+    lines = [ln.split() for ln in r.stdout.splitlines()]
+    assert lines[0][0] == "size" and [ln[0] for ln in lines[1:]] == [f"source{s}" for s in range(len(sizes))]
+    size = int(lines[0][1])
+    regions = [("totals", 0, 8 * len(sizes))]  # (name, start, bytes needed)
+    for s, (n, ln) in enumerate(zip(sizes, lines[1:])):
+        bases, partials, keep = map(int, ln[1:])
+        groups = -(-n // X.GROUP)
+        regions += [(f"bases{s}", bases, 4 * groups), (f"partials{s}", partials, 4 * groups), (f"keep{s}", keep, 4 * (-(-n // 32)))]
+    regions.sort(key=lambda reg: reg[1])
+    for (name, start, need), nxt in zip(regions, regions[1:] + [("end", size, 0)]):
+        assert start % 128 == 0, name  # whole 128-byte lines
+        assert start + need <= nxt[1], (name, nxt[0])  # as large as its kernel needs, disjoint from the next, inside the workspace
+    if len(sizes) == 1:  # the total and the bases are one copy to the host
+        assert dict((name, start) for name, start, _ in regions)["bases0"] == 128

@@ -11,6 +11,8 @@ import pytest
 from tests import common
 from tests import export_ref as E
 from tests import extract_ref as X
+from tests import model_ops
+from tests.model_ops import H, KIND_IDS, KINDS, W, frames as _frames, load as _load
 from wgpu_3dgs_viewer_app_amd import _lib, camera, ply, query, scene
 from wgpu_3dgs_viewer_app_amd import viewer as viewer_mod
 from wgpu_3dgs_viewer_app_amd.query import GaussianEditFlag as F
@@ -18,10 +20,7 @@ from wgpu_3dgs_viewer_app_amd.viewer import (CommGroup, Cov3dKind, DepthCompare,
                                              ShKind)
 
 pytestmark = pytest.mark.gpu
-W, H = 96, 64
 FRAME_TOL = 1e-3  # spec §8
-KINDS = [(sh, cov) for sh in ShKind for cov in Cov3dKind]
-KIND_IDS = [f"{sh.name}-{cov.name}" for sh, cov in KINDS]
 SRC = "src"
 BAKE = _lib.GSX_EXPORT_BAKE_EDITS
 ROW = {_lib.GSX_EXPORT_GAUSSIANS: 224, _lib.GSX_EXPORT_PLY_VERTICES: 248}
@@ -29,34 +28,9 @@ C0 = 0.28209479177387814
 HALF_STEP = 2.0 ** -10  # one binary16 step of a normal value is at most this times the value; of a subnormal one it is 2^-24
 
 
-def _load(v, g, key=SRC, mt=None):
-    v.add_model(key, g.shape[0])
-    v.models[key].gaussian_buffers.gaussians_buffer.update_range(0, g)
-    if mt is not None:
-        v.update_model_transform(key, *mt)
-
-
 def _pod(v, key=SRC):
     """the resident planes, dequantised: pos, color, sh, cov3d (sh: zeros for a viewer without SH planes)"""
-    if v.sh != ShKind.Remove:
-        return v.models[key].gaussian_buffers.gaussians_buffer.download_pod()
-    n = C.c_uint64()
-    _lib.check(v._L.gsx_model_len(v._h, key.encode(), C.byref(n)))
-    n = int(n.value)
-    pos, color, cov = np.empty((n, 3), np.float32), np.empty(n, np.uint32), np.empty((n, 6), np.float32)
-    f32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
-    _lib.check(v._L.gsx_model_download_pod(v._h, key.encode(), f32p(pos), color.ctypes.data_as(C.POINTER(C.c_uint32)), None, f32p(cov)))
-    return pos, color, np.zeros((n, 45), np.float32), cov
-
-
-def _frames(v, keys, poses=(5, 6, 7), sh_deg=3):
-    out = []
-    for pose in poses:
-        v.update_camera(camera.orbit_pose(pose), (W, H))
-        v.update_gaussian_transform(1.0, GaussianDisplayMode.Splat, GaussianShDegree.new(sh_deg), False)
-        v.render_frame(list(keys))
-        out.append(v.download_framebuffer())
-    return out
+    return model_ops.pod(v, key, sh_zeros=True)
 
 
 def _export_raw(v, key, filter=0, flags=0, fmt=0, staging=0, reserved=0, capacity=None):  # noqa: A002

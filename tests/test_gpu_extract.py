@@ -8,14 +8,14 @@ import pytest
 
 from tests import common
 from tests import extract_ref as X
-from wgpu_3dgs_viewer_app_amd import _lib, camera, query, scene
+from tests.model_ops import KINDS, frames as _frames, load as _load, model_len as _len, pod as _pod
+from wgpu_3dgs_viewer_app_amd import _lib, query, scene
 from wgpu_3dgs_viewer_app_amd import viewer as viewer_mod
 from wgpu_3dgs_viewer_app_amd.query import GaussianEditFlag as F
-from wgpu_3dgs_viewer_app_amd.viewer import BufferHandle, Cov3dKind, GaussianDisplayMode, GaussianShDegree, GsxError, MultiModelViewer, ShKind
+from wgpu_3dgs_viewer_app_amd.viewer import BufferHandle, Cov3dKind, GsxError, MultiModelViewer, ShKind
 
 pytestmark = pytest.mark.gpu
 SRC, DST = "src", "dst"
-W, H = 96, 64
 # word, wave and workgroup tails; one below, at and one above the Gaussians of a scatter workgroup; a few dozen workgroups; and one
 # model just past what the scan's one workgroup takes in a pass (X.SCAN_PASS partials of X.GROUP Gaussians each)
 EDGE_SIZES = [1, 31, 32, 33, 63, 64, 65, 255, 256, 257, X.GROUP - 1, X.GROUP, X.GROUP + 1, 70001, X.SCAN_PASS * X.GROUP + X.GROUP + 1]
@@ -29,31 +29,10 @@ def big():
     return g
 
 
-def _load(v, g, key=SRC):
-    v.add_model(key, g.shape[0])
-    v.models[key].gaussian_buffers.gaussians_buffer.update_range(0, g)
-
-
-def _pod(v, key):
-    """the resident planes, dequantised: pos, color, sh, cov3d (sh: an empty array for a viewer without SH planes)"""
-    if v.sh != ShKind.Remove:
-        return v.models[key].gaussian_buffers.gaussians_buffer.download_pod()
-    n = _len(v, key)[1]
-    pos, color, cov = np.empty((n, 3), np.float32), np.empty(n, np.uint32), np.empty((n, 6), np.float32)
-    f32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
-    _lib.check(v._L.gsx_model_download_pod(v._h, key.encode(), f32p(pos), color.ctypes.data_as(C.POINTER(C.c_uint32)), None, f32p(cov)))
-    return pos, color, np.empty((n, 0), np.float32), cov
-
-
 def _same_rows(got, src, kept, what=""):
     """the four downloaded planes of dst are src's kept rows, bit for bit (bytes: a NaN equals itself)"""
     for name, a, b in zip(("pos", "color", "sh", "cov3d"), got, src):
         assert a.shape[0] == kept.size and a.tobytes() == np.ascontiguousarray(b[kept]).tobytes(), (what, name)
-
-
-def _len(v, key):
-    n = C.c_uint64()
-    return v._L.gsx_model_len(v._h, key.encode(), C.byref(n)), int(n.value)
 
 
 def _extract_raw(v, src, dst, flt=0, flags=0):
@@ -98,20 +77,6 @@ def test_edges_of_the_compaction(big, n):
             m.gaussian_buffers.mask_buffer.upload(X.words(np.zeros(n, bool), garbage))
             assert m.extract(DST, X.MASKED) == 0 and DST not in v.models
             assert _len(v, DST)[0] == _lib.GSX_ERR_NOT_FOUND
-
-
-def _frames(v, keys, poses=(5, 6, 7), sh_deg=3):
-    """one frame per pose (a camera path: the later ones are speculated), each downloaded"""
-    out = []
-    for pose in poses:
-        v.update_camera(camera.orbit_pose(pose), (W, H))
-        v.update_gaussian_transform(1.0, GaussianDisplayMode.Splat, GaussianShDegree.new(sh_deg), False)
-        v.render_frame(list(keys))
-        out.append(v.download_framebuffer())
-    return out
-
-
-KINDS = [(sh, cov) for sh in ShKind for cov in Cov3dKind]
 
 
 @pytest.mark.parametrize("sh,cov", KINDS, ids=[f"{sh.name}-{cov.name}" for sh, cov in KINDS])

@@ -13,19 +13,16 @@ from oracle import spec_f64
 from tests import common
 from tests import extract_ref as X
 from tests import merge_ref as R
+from tests.model_ops import H, KIND_IDS, KINDS, W, frames as _frames, load as _load, model_len as _len, pod as _pod
 from wgpu_3dgs_viewer_app_amd import _lib, camera, query, scene
 from wgpu_3dgs_viewer_app_amd.query import GaussianEditFlag as F
-from wgpu_3dgs_viewer_app_amd.viewer import (BufferHandle, CommGroup, Cov3dKind, GaussianDisplayMode, GaussianShDegree, GsxError, MultiModelViewer,
-                                             ShKind)
+from wgpu_3dgs_viewer_app_amd.viewer import BufferHandle, CommGroup, Cov3dKind, GsxError, MultiModelViewer, ShKind
 
 pytestmark = pytest.mark.gpu
-W, H = 96, 64
 OW, OH = 80, 48  # the frames that are compared with the float64 spec
 FRAME_TOL = 1e-3  # spec §8
 AMBIGUITY_TOL = 1e-3  # as the golden fixtures: support decisions |q - k^2| < this go into the oracle's per-pixel allowance
 U = 2.0 ** -24
-KINDS = [(sh, cov) for sh in ShKind for cov in Cov3dKind]
-KIND_IDS = [f"{sh.name}-{cov.name}" for sh, cov in KINDS]
 BIG = 263169  # the size tests/test_gpu_extract.py's edge test ends with: the scan of the partials takes more than one pass
 
 
@@ -35,42 +32,8 @@ def fixture_transform(seed, pos=(0.3, -0.2, 0.5), scale=(1.3, -0.7, 0.9)):
     return np.float32(pos), (q / np.linalg.norm(q)).astype(np.float32), np.float32(scale)
 
 
-def _load(v, g, key, mt=None):
-    v.add_model(key, g.shape[0])
-    v.models[key].gaussian_buffers.gaussians_buffer.update_range(0, g)
-    if mt is not None:
-        v.update_model_transform(key, *mt)
-
-
-def _len(v, key):
-    n = C.c_uint64()
-    return v._L.gsx_model_len(v._h, key.encode(), C.byref(n)), int(n.value)
-
-
-def _pod(v, key):
-    """the resident planes, dequantised: pos, color, sh, cov3d (sh: an empty array for a viewer without SH planes)"""
-    if v.sh != ShKind.Remove:
-        return v.models[key].gaussian_buffers.gaussians_buffer.download_pod()
-    n = _len(v, key)[1]
-    pos, color, cov = np.empty((n, 3), np.float32), np.empty(n, np.uint32), np.empty((n, 6), np.float32)
-    f32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
-    _lib.check(v._L.gsx_model_download_pod(v._h, key.encode(), f32p(pos), color.ctypes.data_as(C.POINTER(C.c_uint32)), None, f32p(cov)))
-    return pos, color, np.empty((n, 0), np.float32), cov
-
-
 def _edits(v, key):
     return v.models[key].gaussian_buffers.gaussians_edit_buffer.download()
-
-
-def _frames(v, keys, poses=(5, 6, 7), size=(W, H), sh_deg=3):
-    """one frame per pose (a camera path: the later ones are speculated), each downloaded"""
-    out = []
-    for pose in poses:
-        v.update_camera(camera.orbit_pose(pose), size)
-        v.update_gaussian_transform(1.0, GaussianDisplayMode.Splat, GaussianShDegree.new(sh_deg), False)
-        v.render_frame(list(keys))
-        out.append(v.download_framebuffer())
-    return out
 
 
 def _same_bytes(a, b, what=""):

@@ -109,8 +109,8 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    const BoundsFilter none{};
-    const BoundsFilter all{mask, sel, edited, edit_a};
+    const ModelFilter none{};
+    const ModelFilter all{mask, sel, edited, edit_a};
     const uint32_t groups = bounds_reduce_groups(n);
     auto row = [&](int r) {
         switch (r) {

@@ -43,7 +43,7 @@ def build_kernels() -> None:
     """the native half, on first use (a profiling tool must not fail the product's build)"""
     src = os.path.join(ROOT, "tools", "bench_bounds.hip")
     csrc = os.path.join(ROOT, "wgpu_3dgs_viewer_app_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in ("kernels_bounds.hip", "kernels_mask.hip", "bounds_math.h", "gsx_internal.h")]
+    deps = [src] + [os.path.join(csrc, f) for f in ("kernels_bounds.hip", "kernels_mask.hip", "bounds_math.h", "extract_math.h", "gsx_internal.h")]
     if os.path.exists(KERNELS) and all(os.path.getmtime(KERNELS) >= os.path.getmtime(d) for d in deps):
         return
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950", src, "-I" + csrc,

@@ -165,7 +165,7 @@ int main(int argc, char** argv) {
             h_mask[w] = word;
         }
         CK(hipMemcpy(mask, h_mask.data(), 4 * words, hipMemcpyHostToDevice));
-        ExtractFilter f{};
+        ModelFilter f{};
         f.mask = mask;
         CK(launch_extract_keep(0, n, f, keep, partials));
         CK(launch_extract_scan(0, partials, groups, bases, total));

@@ -46,7 +46,7 @@ FORMATS = {"gaussians": (_lib.GSX_EXPORT_GAUSSIANS, 224), "ply": (_lib.GSX_EXPOR
 def build_native() -> None:
     """the native halves, on first use (a profiling tool must not fail the product's build)"""
     csrc = os.path.join(ROOT, "wgpu_3dgs_viewer_app_amd", "csrc")
-    deps = [os.path.join(csrc, f) for f in ("kernels_extract.hip", "kernels_export.hip", "extract_math.h", "export_math.h", "edit_math.h", "pod_quant.h",
+    deps = [os.path.join(csrc, f) for f in ("kernels_extract.hip", "kernels_export.hip", "extract_math.h", "export_math.h", "edit_math.h", "pod_quant.h", "pod_planes.h",
                                             "gsx_internal.h")]
     for exe, src, dep in ((KERNELS, os.path.join(ROOT, "tools", "bench_export.hip"), deps), (EXTRACT, os.path.join(ROOT, "tools", "bench_extract.hip"), deps),
                           (HBM, os.path.join(ROOT, "tools", "bench_hbm.hip"), [])):

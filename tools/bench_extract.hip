@@ -134,7 +134,7 @@ int main(int argc, char** argv) {
             h_mask[w] = word;  // (pattern `all` leaves bits above n set: the kernel clears them)
         }
         CK(hipMemcpy(mask, h_mask.data(), 4 * words, hipMemcpyHostToDevice));
-        ExtractFilter f{};
+        ModelFilter f{};
         f.mask = mask;
         const double keep_us = time_us(reps, [&] { CK(launch_extract_keep(0, n, f, keep, partials)); });
         const double scan_us = time_us(reps, [&] { CK(launch_extract_scan(0, partials, groups, bases, total)); });

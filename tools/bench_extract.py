@@ -44,7 +44,7 @@ PATTERNS = ("all", "first_half", "p50", "p03")
 def build_native() -> None:
     """the native halves, on first use (a profiling tool must not fail the product's build)"""
     csrc = os.path.join(ROOT, "wgpu_3dgs_viewer_app_amd", "csrc")
-    jobs = ((KERNELS, os.path.join(ROOT, "tools", "bench_extract.hip"), [os.path.join(csrc, f) for f in ("kernels_extract.hip", "extract_math.h", "merge_math.h", "gsx_internal.h")]),
+    jobs = ((KERNELS, os.path.join(ROOT, "tools", "bench_extract.hip"), [os.path.join(csrc, f) for f in ("kernels_extract.hip", "extract_math.h", "merge_math.h", "pod_planes.h", "gsx_internal.h")]),
             (HBM, os.path.join(ROOT, "tools", "bench_hbm.hip"), []))
     for exe, src, deps in jobs:
         if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in [src] + deps):

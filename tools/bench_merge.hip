@@ -130,7 +130,7 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&partials_w, 4 * extract_groups(n)));
     CK(hipMalloc(&bases_w, 4 * extract_groups(n)));
 
-    ExtractFilter f{};  // no mask: all pass
+    ModelFilter f{};  // no mask: all pass
     const double keep_us = time_us(reps, [&] {
         for (int s = 0; s < kSources; ++s) CK(launch_extract_keep(0, counts[s], f, keep[s], partials[s]));
     });

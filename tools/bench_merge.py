@@ -60,7 +60,7 @@ SH_C3 = (-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.37317633
 def build_native() -> None:
     """the native halves, on first use (a profiling tool must not fail the product's build)"""
     csrc = os.path.join(ROOT, "wgpu_3dgs_viewer_app_amd", "csrc")
-    deps = [os.path.join(csrc, f) for f in ("kernels_extract.hip", "kernels_merge.hip", "extract_math.h", "merge_math.h", "pod_quant.h", "gsx_internal.h")]
+    deps = [os.path.join(csrc, f) for f in ("kernels_extract.hip", "kernels_merge.hip", "extract_math.h", "merge_math.h", "pod_quant.h", "pod_planes.h", "gsx_internal.h")]
     for exe, src, dep in ((KERNELS, os.path.join(ROOT, "tools", "bench_merge.hip"), deps), (EXTRACT, os.path.join(ROOT, "tools", "bench_extract.hip"), deps),
                           (HBM, os.path.join(ROOT, "tools", "bench_hbm.hip"), [])):
         if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in [src] + dep):

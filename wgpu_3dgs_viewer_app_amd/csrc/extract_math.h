@@ -1,9 +1,11 @@
 // extract_math.h — the word arithmetic of gsx_model_extract (spec/RENDER_SPEC.md §12, "Model extract"), written once: the kernels
 // of kernels_extract.hip and the host restatement of tests/extract_driver.cpp both include it, so the two cannot drift.
 // It holds the keep word of 32 Gaussians composed from their mask, selection and hidden words, its inversion, the bits of a
-// plane's last word that lie at or above n, and a Gaussian's rank among the kept ones of its word.
+// plane's last word that lie at or above n, a Gaussian's rank among the kept ones of its word, and the layout of the workspace the
+// keep and scan passes of every model operation share (gsx_model_extract, gsx_model_merge, gsx_model_export).
 // Plain integer arithmetic; no HIP include (the functions are __host__ __device__ under hipcc).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -52,5 +54,26 @@ GSX_EX_HD inline uint32_t extract_rank(uint32_t keep_word, uint32_t bit) { retur
 
 // workgroups (= popcount partials) of a model of n Gaussians
 GSX_EX_HD inline uint64_t extract_groups(uint64_t n) { return (n + kExtractGroup - 1u) / kExtractGroup; }
+
+// a workspace region's size: whole 128-byte lines
+inline size_t extract_pad128(size_t b) { return (b + 127u) & ~size_t(127); }
+
+// The workspace of the kept-set pass over n_src sources: the 64-bit totals of all sources first (source s at byte 8 s), then per
+// source its bases, partials (extract_groups(n) words each) and keep words (ceil(n / 32)), every region padded to 128 bytes.  With
+// one source the total lies at 0 and the bases at 128: total and bases are one contiguous copy.  Returns the workspace's bytes.
+struct ExtractRegion {
+    size_t bases, partials, keep;  // byte offsets
+};
+inline size_t extract_ws_layout(const uint64_t* n, uint32_t n_src, ExtractRegion* out) {
+    size_t at = extract_pad128(sizeof(uint64_t) * n_src);
+    for (uint32_t s = 0; s < n_src; ++s) {
+        const size_t group_bytes = extract_pad128(4 * (size_t)extract_groups(n[s]));
+        out[s].bases = at;
+        out[s].partials = at + group_bytes;
+        out[s].keep = at + 2 * group_bytes;
+        at = out[s].keep + extract_pad128(4 * (size_t)((n[s] + 31u) / 32u));
+    }
+    return at;
+}
 
 }  // namespace gsx

@@ -109,6 +109,8 @@ static bool frame_may_overlap(gsx_viewer* v, const char* const* keys, uint32_t n
         return false;
     for (uint32_t i = 0; i < n_keys; ++i) {
         Model* m = find_model(v, keys ? keys[i] : nullptr);
+        // (not model_is_shard: a limits override that waits for the model's next sharded frame, shard_override_tiles, is neither read
+        // nor cleared by an ordinary frame, so it keeps no frame off the lanes; the three below are state a sharded frame left)
         if (!m || m->shard_win_set || m->shard_limit_valid || m->shard_next_valid) return false;
     }
     return n_keys > 0;

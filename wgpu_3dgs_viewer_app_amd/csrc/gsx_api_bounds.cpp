@@ -21,8 +21,7 @@ void gsx_bounds_desc_default(gsx_bounds_desc* d) {
 
 gsx_status gsx_model_bounds(gsx_viewer* v, const char* key, const gsx_bounds_desc* desc, gsx_model_bounds_t* out) {
     if (!v || !desc || !out) return fail(GSX_ERR_INVALID_ARG, "gsx_model_bounds: null argument");
-    if (desc->filter & ~(GSX_BOUNDS_MASKED | GSX_BOUNDS_SKIP_HIDDEN | GSX_BOUNDS_SELECTED))
-        return fail(GSX_ERR_INVALID_ARG, "gsx_model_bounds: unknown filter bits 0x%x", desc->filter);
+    if (desc->filter & ~kModelFilterBits) return fail(GSX_ERR_INVALID_ARG, "gsx_model_bounds: unknown filter bits 0x%x", desc->filter);
     if (desc->trim_permille >= 500u) return fail(GSX_ERR_INVALID_ARG, "gsx_model_bounds: trim_permille %u is not below 500", desc->trim_permille);
     gsx_status st = viewer_bind(v);
     if (st) return st;
@@ -33,16 +32,9 @@ gsx_status gsx_model_bounds(gsx_viewer* v, const char* key, const gsx_bounds_des
     gsx_model_bounds_t* d_out = reinterpret_cast<gsx_model_bounds_t*>(ws);
     BoundsPartial* partials = reinterpret_cast<BoundsPartial*>(ws + kWsPartials);
     uint32_t* hist = reinterpret_cast<uint32_t*>(ws + kWsHist);
-    BoundsFilter f{};
-    if ((desc->filter & GSX_BOUNDS_MASKED) && m->has_mask) f.mask = m->mask.as<uint32_t>();
-    if ((desc->filter & GSX_BOUNDS_SKIP_HIDDEN) && m->has_edits) {
-        f.edited = m->edited.as<uint32_t>();
-        f.edit_a = m->edit_a.as<float4>();
-    }
+    const ModelFilter f = model_filter(m, desc->filter, false);
     // selected Gaussians of a model without a selection: none — no Gaussian is looked at
-    const bool none = (desc->filter & GSX_BOUNDS_SELECTED) && !m->has_selection;
-    if (desc->filter & GSX_BOUNDS_SELECTED) f.selection = m->selection.as<uint32_t>();
-    const uint64_t n = none ? 0 : m->n;
+    const uint64_t n = f.select_none ? 0 : m->n;
     const bool trim = desc->trim_permille > 0 && n > 0;
     if (n) HIPCHK(launch_bounds_reduce(v->stream, m->pc.as<float4>(), n, f, partials));
     HIPCHK(launch_bounds_finish(v->stream, partials, n ? bounds_reduce_groups(n) : 0u, trim, d_out, hist));

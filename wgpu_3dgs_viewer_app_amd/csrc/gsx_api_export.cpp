@@ -11,24 +11,19 @@ std::string ply_header(uint64_t count);  // gsx_ply.cpp: the one header writer
 }
 
 namespace {
-// the workspace: [total, padded to 128 B | bases | partials | keep words]: the total and the bases are one copy to the host
-constexpr size_t kWsBases = 128;
 constexpr uint64_t kDefaultStagingBytes = 32ull << 20;  // one staging buffer when the desc says 0
 
 constexpr uint64_t row_bytes(uint32_t format) { return format == GSX_EXPORT_GAUSSIANS ? sizeof(gsx_gaussian) : 248u; }
 
 // what the keep and scan passes of one call leave behind
-struct Kept {
-    Model* m = nullptr;
-    uint64_t groups = 0, total = 0;
-    const uint32_t* d_keep = nullptr;
-    const uint32_t* d_bases = nullptr;
+struct Kept : KeptSet {
     std::vector<uint32_t> bases;  // host copy, groups + 1 entries (the last: the total); only with `want_bases`
 };
 
-// validation, viewer_bind, the keep and scan passes, the one wait
+// validation, viewer_bind, then the kept set (kept_sets: the keep and scan passes, the one wait before the rows: the kept count
+// sizes the output, the bases cut the source into chunks)
 gsx_status export_keep(gsx_viewer* v, const char* key, const gsx_export_desc* desc, const char* who, bool check_format, bool want_bases, Kept* k) {
-    if (desc->filter & ~(GSX_BOUNDS_MASKED | GSX_BOUNDS_SKIP_HIDDEN | GSX_BOUNDS_SELECTED)) return fail(GSX_ERR_INVALID_ARG, "%s: unknown filter bits 0x%x", who, desc->filter);
+    if (desc->filter & ~kModelFilterBits) return fail(GSX_ERR_INVALID_ARG, "%s: unknown filter bits 0x%x", who, desc->filter);
     if (desc->flags & ~(GSX_EXTRACT_INVERT | GSX_EXPORT_BAKE_EDITS)) return fail(GSX_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x", who, desc->flags);
     if (check_format && desc->format != GSX_EXPORT_GAUSSIANS && desc->format != GSX_EXPORT_PLY_VERTICES) return fail(GSX_ERR_INVALID_ARG, "%s: unknown format %u", who, desc->format);
     if (desc->reserved) return fail(GSX_ERR_INVALID_ARG, "%s: reserved is %u, not 0", who, desc->reserved);
@@ -37,48 +32,10 @@ gsx_status export_keep(gsx_viewer* v, const char* key, const gsx_export_desc* de
     Model* m = find_model(v, key);
     if (!m) return fail(GSX_ERR_NOT_FOUND, "%s: no model '%s'", who, key);
     if (has_comm(v)) return fail(GSX_ERR_UNSUPPORTED, "%s: the viewer has a communicator (export before gsx_viewer_comm_init, or on one GPU)", who);
-    if (m->shard_win_set || m->shard_limit_valid || m->shard_next_valid || m->shard_override_tiles)
-        return fail(GSX_ERR_UNSUPPORTED, "%s: model '%s' is a shard of a multi-GPU frame", who, key);
+    if (model_is_shard(m)) return fail(GSX_ERR_UNSUPPORTED, "%s: model '%s' is a shard of a multi-GPU frame", who, key);
     k->m = m;
-    const uint64_t n = m->n;
-    if (n == 0) return GSX_OK;
-
-    const uint64_t groups = k->groups = extract_groups(n);
-    const size_t ws_partials = kWsBases + extract_pad128(4 * (size_t)groups), ws_keep = ws_partials + extract_pad128(4 * (size_t)groups);
-    HIPCHK(v->extract_ws.ensure(ws_keep + 4 * (size_t)((n + 31) / 32)));
-    char* ws = v->extract_ws.as<char>();
-    uint64_t* d_total = reinterpret_cast<uint64_t*>(ws);
-    uint32_t* bases = reinterpret_cast<uint32_t*>(ws + kWsBases);
-    uint32_t* partials = reinterpret_cast<uint32_t*>(ws + ws_partials);
-    uint32_t* keep = reinterpret_cast<uint32_t*>(ws + ws_keep);
-
-    ExtractFilter f{};
-    if ((desc->filter & GSX_BOUNDS_MASKED) && m->has_mask) f.mask = m->mask.as<uint32_t>();
-    if ((desc->filter & GSX_BOUNDS_SKIP_HIDDEN) && m->has_edits) {
-        f.edited = m->edited.as<uint32_t>();
-        f.edit_a = m->edit_a.as<float4>();
-    }
-    if (desc->filter & GSX_BOUNDS_SELECTED) {
-        if (m->has_selection) f.selection = m->selection.as<uint32_t>();
-        else f.select_none = 1u;
-    }
-    f.invert = (desc->flags & GSX_EXTRACT_INVERT) ? 1u : 0u;
-    HIPCHK(launch_extract_keep(v->stream, n, f, keep, partials));
-    HIPCHK(launch_extract_scan(v->stream, partials, groups, bases, d_total));
-    // the one wait before the rows: the kept count sizes the output, the bases cut the source into chunks
-    HIPCHK(gsx::op::StreamSynchronize(v->stream));
-    if (want_bases) {
-        std::vector<uint32_t> host((kWsBases / 4) + groups);
-        HIPCHK(gsx::op::Memcpy(host.data(), ws, 4 * host.size(), hipMemcpyDeviceToHost));
-        memcpy(&k->total, host.data(), sizeof k->total);
-        k->bases.assign(host.begin() + kWsBases / 4, host.end());
-        k->bases.push_back((uint32_t)k->total);
-    } else {
-        HIPCHK(gsx::op::Memcpy(&k->total, d_total, sizeof k->total, hipMemcpyDeviceToHost));
-    }
-    k->d_keep = keep;
-    k->d_bases = bases;
-    return GSX_OK;
+    if (m->n == 0) return GSX_OK;
+    return kept_sets(v, k, 1, desc->filter, (desc->flags & GSX_EXTRACT_INVERT) != 0, want_bases ? &k->bases : nullptr);
 }
 
 gsx_status export_streams(gsx_viewer* v) {

@@ -129,7 +129,7 @@ struct PodPlanes {
 };
 
 // words per shade record and the word that holds pc, by pod kind (PodPlanes::sh_aos)
-inline void aos_layout(int sh_kind, int cov_kind, uint32_t* stride, uint32_t* geo) {
+constexpr void aos_layout(int sh_kind, int cov_kind, uint32_t* stride, uint32_t* geo) {
     switch (sh_kind) {
         case GSX_SH_SINGLE: *stride = 16u; *geo = 12u; break;
         case GSX_SH_HALF: *stride = cov_kind == GSX_COV3D_SINGLE ? 12u : 8u; *geo = 6u; break;
@@ -895,14 +895,19 @@ struct MaskProgram {
 hipError_t launch_mask_evaluate(hipStream_t s, const float4* pc, uint32_t n, const MaskProgram& prog, uint32_t* mask);
 void quat_to_rows(const float q[4], float r[9]);
 
-// Model bounds (kernels_bounds.hip; gsx_model_bounds).  The filter: the bit planes a Gaussian must pass, nullptr = absent = passes
-// (mask: bit set = kept; selection: bit set = selected; edited + edit_a: dropped where the stored flag has ENABLED and HIDDEN).
-struct BoundsFilter {
+// The filter of the model operations (bounds, extract, merge, export), built by model_filter (gsx_state.h) alone: the bit planes a
+// Gaussian must pass, nullptr = absent = passes (mask: bit set = kept; selection: bit set = selected; edited + edit_a: dropped where
+// the stored flag hides, extract_flag_hides) — but for `select_none` (SELECTED asked of a model without a selection: none pass);
+// `invert` keeps exactly the Gaussians that do not pass.  k_extract_keep reads all of it.  The bounds kernels read the four planes
+// only: gsx_model_bounds has no invert, and looks at no Gaussian when `select_none` is set.
+struct ModelFilter {
     const uint32_t* mask;
     const uint32_t* selection;
     const uint32_t* edited;
     const float4* edit_a;
+    uint32_t select_none, invert;
 };
+// Model bounds (kernels_bounds.hip; gsx_model_bounds).
 struct BoundsPartial {  // one per workgroup of k_bounds_reduce; 64 bytes
     float mn[3], mx[3];
     uint64_t count, nonfinite;
@@ -911,23 +916,14 @@ struct BoundsPartial {  // one per workgroup of k_bounds_reduce; 64 bytes
 constexpr uint32_t kBoundsMaxGroups = 2048;   // most workgroups (= partials) of k_bounds_reduce: eight per CU
 constexpr uint32_t kBoundsHistGroups = 1024;  // ... of k_bounds_hist
 uint32_t bounds_reduce_groups(uint64_t n);    // the partials launch_bounds_reduce leaves for a model of n Gaussians
-hipError_t launch_bounds_reduce(hipStream_t s, const float4* pc, uint64_t n, const BoundsFilter& f, BoundsPartial* partials);  // n > 0
+hipError_t launch_bounds_reduce(hipStream_t s, const float4* pc, uint64_t n, const ModelFilter& f, BoundsPartial* partials);  // n > 0
 hipError_t launch_bounds_finish(hipStream_t s, const BoundsPartial* partials, uint32_t n_partials, bool clear_hist, gsx_model_bounds_t* out,
                                 uint32_t* hist);
 // the histogram over [out->min, out->max] and its scan: writes out->trim_min / trim_max (n > 0; hist: 3 * kBoundsBins words, cleared)
-hipError_t launch_bounds_trim(hipStream_t s, const float4* pc, uint64_t n, const BoundsFilter& f, uint32_t trim_permille,
+hipError_t launch_bounds_trim(hipStream_t s, const float4* pc, uint64_t n, const ModelFilter& f, uint32_t trim_permille,
                               gsx_model_bounds_t* out, uint32_t* hist);
 
-// Model extract (kernels_extract.hip; gsx_model_extract).  The filter, with gsx_model_bounds' meaning: the bit planes a Gaussian must
-// pass, nullptr = absent = passes — but for `select_none` (SELECTED asked of a model without a selection: none pass); `invert` keeps
-// exactly the Gaussians that do not pass.
-struct ExtractFilter {
-    const uint32_t* mask;
-    const uint32_t* selection;
-    const uint32_t* edited;
-    const float4* edit_a;
-    uint32_t select_none, invert;
-};
+// Model extract (kernels_extract.hip; gsx_model_extract).
 // Everything that is carried, as stored bits: the planes of the model's pod kind (the others nullptr), the shade records, and the
 // edit planes (all three, or none when no edit records are carried).
 struct ExtractPlanes {
@@ -945,7 +941,7 @@ struct ExtractPlanes {
     uint4* edit_a;
     uint4* edit_b;
 };
-// The start of both scatters (k_extract_scatter, k_merge_bake): wave 0 loads the workgroup's 32 keep words
+// The start of every reader of a kept set (k_extract_scatter, k_merge_bake, k_export_rows): wave 0 loads the workgroup's 32 keep words
 // and scans their popcounts; s_before[w] = kept Gaussians of the workgroup's words before word w, s_before[32] = all of them.  Ends
 // with a barrier.  A Gaussian's rank in its workgroup is s_before[word] + extract_rank(word, bit): from the keep words alone.
 __device__ inline void extract_group_ranks(const uint32_t* __restrict__ keep, uint64_t n_src, uint64_t base, uint32_t* s_keep, uint32_t* s_before) {
@@ -967,10 +963,43 @@ __device__ inline void extract_group_ranks(const uint32_t* __restrict__ keep, ui
     }
     __syncthreads();
 }
-// a workspace region's size: whole 128-byte lines (gsx_api_extract.cpp, gsx_api_merge.cpp)
-inline size_t extract_pad128(size_t b) { return (b + 127u) & ~size_t(127); }
+// After extract_group_ranks: the workgroup's kept Gaussians by rank, each as its index inside the workgroup (k_export_rows;
+// k_extract_scatter writes the same entries inside its copy loop, where the rank is at hand: measured faster there).
+// s_list holds kExtractGroup entries; 256 lanes, four Gaussians a lane.  No barrier at its end.
+__device__ inline void extract_group_list(const uint32_t* s_keep, const uint32_t* s_before, uint16_t* s_list) {
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+        const uint32_t local = k * 256u + threadIdx.x, w = local >> 5, bit = local & 31u, word = s_keep[w];
+        if ((word >> bit) & 1u) s_list[s_before[w] + extract_rank(word, bit)] = (uint16_t)local;  // (the keep words are clear at and above n)
+    }
+}
+// The staged writer (k_merge_bake's records, k_export_rows' rows): up to 256 lanes each hold one row of ROW_VECS vectors in registers,
+// the rows are contiguous at d_rows, and they leave as runs of consecutive vector stores: CHUNK vectors of every row at a time pass
+// through LDS (s_stage: CHUNK * kStagePitch vectors).  Lane `slot` of the `kept` lanes that are `on` gives vector q of its row as
+// vec(q); kept is uniform.  Between two vectors of the staging area lie kStagePitch vectors, one more than the lanes, so the copy's
+// reads (CHUNK lanes a row, a vector apart) spread over the banks.
+constexpr uint32_t kStagePitch = 257;
+template <class Vec, uint32_t CHUNK, uint32_t ROW_VECS, class F>
+__device__ inline void stage_rows_out(Vec* s_stage, Vec* __restrict__ d_rows, bool on, uint32_t slot, uint32_t kept, F&& vec) {
+#pragma unroll
+    for (uint32_t v0 = 0; v0 < ROW_VECS; v0 += CHUNK) {
+        const uint32_t chunk = ROW_VECS - v0 < CHUNK ? ROW_VECS - v0 : CHUNK;  // (the last pass of a row may be shorter)
+        __syncthreads();  // the copy of the pass before has read the staging area
+        if (on) {
+#pragma unroll
+            for (uint32_t q = 0; q < CHUNK; ++q)
+                if (q < chunk) s_stage[q * kStagePitch + slot] = vec(v0 + q < ROW_VECS ? v0 + q : 0u);
+        }
+        __syncthreads();
+        const uint32_t vecs = kept * chunk;
+        for (uint32_t q = threadIdx.x; q < vecs; q += 256u) {
+            const uint32_t g = q / chunk, ww = q % chunk;
+            d_rows[(uint64_t)g * ROW_VECS + v0 + ww] = s_stage[ww * kStagePitch + g];
+        }
+    }
+}
 // keep: ceil(n / 32) words; partials, bases: extract_groups(n) words; total: one 64-bit word, written by the scan (n > 0)
-hipError_t launch_extract_keep(hipStream_t s, uint64_t n, const ExtractFilter& f, uint32_t* keep, uint32_t* partials);
+hipError_t launch_extract_keep(hipStream_t s, uint64_t n, const ModelFilter& f, uint32_t* keep, uint32_t* partials);
 hipError_t launch_extract_scan(hipStream_t s, const uint32_t* partials, uint64_t n_partials, uint32_t* bases, uint64_t* total);
 // src is only read.  dst's planes hold n_dst Gaussians, of which this launch writes [dst_offset, dst_offset + the scan's total)
 // (gsx_model_extract: dst_offset 0, n_dst the total); dst.edited (when carried) is zeroed

@@ -721,6 +721,35 @@ inline ExtractPlanes extract_planes(const Model* m, bool edits) {
     }
     return p;
 }
+// The filter of gsx_model_bounds, _extract, _merge and _export: the only copy of its rules.  No mask, or MASKED not asked for: every
+// Gaussian passes the mask.  SKIP_HIDDEN counts only on a model with edit records.  SELECTED without a selection: none pass.
+constexpr uint32_t kModelFilterBits = GSX_BOUNDS_MASKED | GSX_BOUNDS_SKIP_HIDDEN | GSX_BOUNDS_SELECTED;  // the bits a desc may set
+inline ModelFilter model_filter(const Model* m, uint32_t filter_bits, bool invert) {
+    ModelFilter f{};
+    if ((filter_bits & GSX_BOUNDS_MASKED) && m->has_mask) f.mask = m->mask.as<uint32_t>();
+    if ((filter_bits & GSX_BOUNDS_SKIP_HIDDEN) && m->has_edits) {
+        f.edited = m->edited.as<uint32_t>();
+        f.edit_a = m->edit_a.as<float4>();
+    }
+    if (filter_bits & GSX_BOUNDS_SELECTED) {
+        if (m->has_selection) f.selection = m->selection.as<uint32_t>();
+        else f.select_none = 1u;
+    }
+    f.invert = invert ? 1u : 0u;
+    return f;
+}
+// does the model carry the shard state of a multi-GPU frame?  (gsx_model_extract, _merge and _export refuse such a model)
+inline bool model_is_shard(const Model* m) { return m->shard_win_set || m->shard_limit_valid || m->shard_next_valid || m->shard_override_tiles; }
+// The kept sets of n_src models under one filter (gsx_api_extract.cpp; the workspace is extract_ws_layout's, in v->extract_ws): the
+// keep and scan passes of every non-empty source, then the ONE wait of the call, then the totals on the host.
+struct KeptSet {
+    const Model* m = nullptr;          // in
+    uint64_t groups = 0, total = 0;    // out: extract_groups(m->n), the kept count
+    const uint32_t* d_keep = nullptr;  // out: the keep words and the groups' bases on the device (nullptr for an empty source)
+    const uint32_t* d_bases = nullptr;
+};
+// host_bases (nullable; one source): the source's bases and, as the last entry, its total — groups + 1 entries, copied with the total
+gsx_status kept_sets(gsx_viewer* v, KeptSet* src, uint32_t n_src, uint32_t filter_bits, bool invert, std::vector<uint32_t>* host_bases = nullptr);
 gsx_status ensure_selection(gsx_viewer* v, Model* m);
 gsx_status ensure_edit_buffers(gsx_viewer* v, Model* m);
 

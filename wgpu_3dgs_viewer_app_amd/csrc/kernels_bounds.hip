@@ -29,7 +29,7 @@ struct BoundsLoads {
     float4 p[kBoundsPerLane];
     uint32_t mask[kBoundsPerLane], sel[kBoundsPerLane], edited[kBoundsPerLane];
 };
-__device__ inline void bd_load(const float4* __restrict__ pc, uint64_t n, const BoundsFilter& f, uint64_t base, BoundsLoads* L) {
+__device__ inline void bd_load(const float4* __restrict__ pc, uint64_t n, const ModelFilter& f, uint64_t base, BoundsLoads* L) {
 #pragma unroll
     for (uint32_t k = 0; k < kBoundsPerLane; ++k) {
         const uint64_t i = base + k * 256u;
@@ -41,14 +41,11 @@ __device__ inline void bd_load(const float4* __restrict__ pc, uint64_t n, const 
     }
 }
 // does Gaussian i = base + k * 256 pass the filter?  (the edit flag word is read only where the `edited` bit is set)
-__device__ inline bool bd_keep(const BoundsFilter& f, uint64_t n, uint64_t base, uint32_t k, const BoundsLoads& L) {
+__device__ inline bool bd_keep(const ModelFilter& f, uint64_t n, uint64_t base, uint32_t k, const BoundsLoads& L) {
     const uint64_t i = base + k * 256u;
     const uint32_t b = (uint32_t)i & 31u;
     bool keep = i < n && ((L.mask[k] >> b) & 1u) && ((L.sel[k] >> b) & 1u);
-    if (keep && ((L.edited[k] >> b) & 1u)) {
-        const uint32_t flag = __float_as_uint(f.edit_a[i].x);
-        keep = !((flag & GSX_EDIT_ENABLED) && (flag & GSX_EDIT_HIDDEN));
-    }
+    if (keep && ((L.edited[k] >> b) & 1u)) keep = !extract_flag_hides(__float_as_uint(f.edit_a[i].x));
     return keep;
 }
 
@@ -73,7 +70,7 @@ __device__ inline BoundsPartial bd_identity() {
     return a;
 }
 
-__global__ __launch_bounds__(256) void k_bounds_reduce(const float4* __restrict__ pc, uint64_t n, BoundsFilter f,
+__global__ __launch_bounds__(256) void k_bounds_reduce(const float4* __restrict__ pc, uint64_t n, ModelFilter f,
                                                         BoundsPartial* __restrict__ partials) {
     BoundsPartial acc = bd_identity();
     const uint64_t chunks = (n + kBoundsChunk - 1) / kBoundsChunk;
@@ -167,7 +164,7 @@ __global__ __launch_bounds__(256) void k_bounds_finish(const BoundsPartial* __re
 }
 
 // The histogram pass: the same stream and the same verdicts as k_bounds_reduce; the bins live in LDS (24 KiB per workgroup).
-__global__ __launch_bounds__(256) void k_bounds_hist(const float4* __restrict__ pc, uint64_t n, BoundsFilter f,
+__global__ __launch_bounds__(256) void k_bounds_hist(const float4* __restrict__ pc, uint64_t n, ModelFilter f,
                                                       const gsx_model_bounds_t* __restrict__ res, uint32_t* __restrict__ hist) {
     __shared__ uint32_t bins[3u * kBoundsBins];
     if (res->count == 0) return;  // (uniform)
@@ -235,7 +232,7 @@ uint32_t bounds_reduce_groups(uint64_t n) {
     return rounds ? (uint32_t)((chunks + rounds - 1) / rounds) : 0u;
 }
 
-hipError_t launch_bounds_reduce(hipStream_t s, const float4* pc, uint64_t n, const BoundsFilter& f, BoundsPartial* partials) {
+hipError_t launch_bounds_reduce(hipStream_t s, const float4* pc, uint64_t n, const ModelFilter& f, BoundsPartial* partials) {
     GSX_LAUNCH(k_bounds_reduce, dim3(bounds_reduce_groups(n)), dim3(256), 0, s, pc, n, f, partials);
     return hipGetLastError();
 }
@@ -244,7 +241,7 @@ hipError_t launch_bounds_finish(hipStream_t s, const BoundsPartial* partials, ui
     GSX_LAUNCH(k_bounds_finish, dim3(1), dim3(256), 0, s, partials, n_partials, clear_hist ? 1u : 0u, out, hist);
     return hipGetLastError();
 }
-hipError_t launch_bounds_trim(hipStream_t s, const float4* pc, uint64_t n, const BoundsFilter& f, uint32_t trim_permille,
+hipError_t launch_bounds_trim(hipStream_t s, const float4* pc, uint64_t n, const ModelFilter& f, uint32_t trim_permille,
                               gsx_model_bounds_t* out, uint32_t* hist) {
     // fewer, longer-lived workgroups than the reduction: each flushes up to 3 x 2048 bins with global atomics
     const uint32_t groups = (uint32_t)std::min<uint64_t>((n + kBoundsChunk - 1) / kBoundsChunk, kBoundsHistGroups);

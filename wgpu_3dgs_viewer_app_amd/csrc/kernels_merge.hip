@@ -1,17 +1,17 @@
 // kernels_merge.hip — the baked path of gsx_model_merge for gfx950 (spec/RENDER_SPEC.md §13, "Model merge").  A source whose model
 // transform is the identity goes through k_extract_scatter with a destination offset (kernels_extract.hip); every other source goes
 // through k_merge_bake here: the same keep words, bases and destination arithmetic, but each kept Gaussian is dequantised exactly
-// (§2b), moved into world space and quantised again into the destination's kind (pod_quant.h: the one implementation of §2b).
+// (§2b; pod_planes.h), moved into world space and quantised again into the destination's kind (pod_quant.h).
 //   position     p' = R_m (s_m * p) + t_m, each row ((R0 a0 + R1 a1) + R2 a2) + t in float32 (§3's dot product);
 //   covariance   S' = M S M^T with M = R_m diag(s_m): A = M S, then S' = A M^T, every entry a §3 dot product;
 //   SH           per band and channel c' = M_l c, the float32 matrices of merge_math.h, accumulated with fmaf in column order;
 //   colour word  carried.
 // The per-source constants arrive by value (MergeBake, 98 floats): wave-uniform, read with scalar loads.  One lane per source
 // Gaussian, four rounds of 256 per workgroup as in k_extract_scatter.  The shade records of a round are staged in LDS, eight words
-// of every record at a time, and leave as whole 128-byte runs: consecutive lanes write consecutive uint4s.
+// of every record at a time, and leave as whole 128-byte runs: consecutive lanes write consecutive uint4s (stage_rows_out).
 // Built with -ffp-contract=off; the only fused operations are the fmaf calls of the SH product.  Plane offsets are 64-bit.
 #include "gsx_internal.h"
-#include "pod_quant.h"
+#include "pod_planes.h"
 
 namespace gsx {
 
@@ -19,9 +19,7 @@ static_assert(kMergeMaxSources == GSX_MERGE_MAX_SOURCES, "merge_math.h restates 
 static_assert(sizeof(MergeBake) == 4 * (15 + kMergeShFloats), "98 floats by value");
 
 namespace {
-constexpr uint32_t kRecChunk = 8;     // words of a record staged per pass
-constexpr uint32_t kRecPitch = 257;   // uint4s between two words of the staging area: one more than the lanes, so the copy's reads
-                                      // (eight lanes a record, a word apart) spread over the banks
+constexpr uint32_t kRecChunk = 8;  // words of a record staged per pass (stage_rows_out)
 
 __device__ inline float mg_dot3(float a0, float a1, float a2, float b0, float b1, float b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
 __device__ inline uint4 mg_u4(float a, float b, float c, float d) {
@@ -50,11 +48,10 @@ __device__ inline void mg_rotate_band(const MergeBake& b, float* s) {
 template <int SH, int COV>
 __global__ __launch_bounds__(256) void k_merge_bake(uint64_t n_src, uint64_t n_dst, uint64_t dst_offset, const uint32_t* __restrict__ keep,
                                                      const uint32_t* __restrict__ bases, ExtractPlanes src, ExtractPlanes dst, MergeBake b) {
-    constexpr uint32_t kShWords = SH == GSX_SH_SINGLE ? 12u : SH == GSX_SH_HALF ? 6u : SH == GSX_SH_NORM8 ? 3u : 0u;
-    constexpr uint32_t kStride = SH == GSX_SH_SINGLE ? 16u : SH == GSX_SH_HALF ? (COV == GSX_COV3D_SINGLE ? 12u : 8u) : SH == GSX_SH_NORM8 ? 8u : 0u;
+    constexpr uint32_t kShWords = PodKind<SH, COV>::kShWords, kStride = PodKind<SH, COV>::kStride;
     constexpr uint32_t kRecWords = kStride ? kStride : 1u;
     __shared__ uint32_t s_keep[kExtractGroupWords], s_before[kExtractGroupWords + 1];
-    __shared__ uint4 s_rec[kStride ? kRecChunk * kRecPitch : 1u];
+    __shared__ uint4 s_rec[kStride ? kRecChunk * kStagePitch : 1u];
     const uint32_t t = threadIdx.x;
     const uint64_t base = (uint64_t)blockIdx.x * kExtractGroup;
     extract_group_ranks(keep, n_src, base, s_keep, s_before);
@@ -72,45 +69,8 @@ __global__ __launch_bounds__(256) void k_merge_bake(uint64_t n_src, uint64_t n_d
             // ---- load, dequantised exactly ----
             const uint4 pc = src.pc[i];
             float c[6], s[48];
-            if (COV == GSX_COV3D_SINGLE) {
-                const uint4 a = src.cov_a[i];
-                const uint2 bb = src.cov_b[i];
-                c[0] = __uint_as_float(a.x); c[1] = __uint_as_float(a.y); c[2] = __uint_as_float(a.z); c[3] = __uint_as_float(a.w);
-                c[4] = __uint_as_float(bb.x); c[5] = __uint_as_float(bb.y);
-            } else {
-                const uint2 a = src.cov_h[i];
-                const uint32_t bb = src.cov_h2[i];
-                c[0] = h_lo(a.x); c[1] = h_hi(a.x); c[2] = h_lo(a.y); c[3] = h_hi(a.y); c[4] = h_lo(bb); c[5] = h_hi(bb);
-            }
-            if (SH == GSX_SH_SINGLE) {
-#pragma unroll
-                for (int p = 0; p < kShPlanes4; ++p) {
-                    const uint4 v = src.sh4[(uint64_t)p * n_src + i];
-                    s[4 * p] = __uint_as_float(v.x); s[4 * p + 1] = __uint_as_float(v.y); s[4 * p + 2] = __uint_as_float(v.z); s[4 * p + 3] = __uint_as_float(v.w);
-                }
-                s[44] = __uint_as_float(src.sh1[i]);
-            } else if (SH == GSX_SH_HALF) {
-#pragma unroll
-                for (int p = 0; p < 6; ++p) {
-                    const uint4 v = src.sh_h[(uint64_t)p * n_src + i];
-                    const uint32_t ww[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        s[8 * p + 2 * q] = h_lo(ww[q]);
-                        s[8 * p + 2 * q + 1] = h_hi(ww[q]);
-                    }
-                }
-            } else if (SH == GSX_SH_NORM8) {
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    const uint4 v = src.sh_q[(uint64_t)p * n_src + i];
-                    const uint32_t ww[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) s[16 * p + 4 * q + e] = dq_snorm8(ww[q], e);
-                }
-            }
+            pod_load_cov<COV>(src, i, c);
+            pod_load_sh<SH>(src, n_src, i, s);
             // ---- bake ----
             const float sx = b.s[0] * __uint_as_float(pc.x), sy = b.s[1] * __uint_as_float(pc.y), sz = b.s[2] * __uint_as_float(pc.z);
             const float px = mg_dot3(b.R[0], b.R[1], b.R[2], sx, sy, sz) + b.t[0];
@@ -207,41 +167,18 @@ __global__ __launch_bounds__(256) void k_merge_bake(uint64_t n_src, uint64_t n_d
         }
         if (kStride == 0u) continue;
         // ---- the round's records: staged kRecChunk words at a time, written as consecutive uint4s ----
-        const uint32_t kept = r_hi - r_lo;  // (uniform)
-        uint4* __restrict__ d_aos = dst.sh_aos + (j0 + r_lo) * kStride;
-#pragma unroll
-        for (uint32_t w0 = 0; w0 < kStride; w0 += kRecChunk) {
-            const uint32_t chunk = kStride - w0 < kRecChunk ? kStride - w0 : kRecChunk;  // (8, or 4 for the 12-word record's second pass)
-            __syncthreads();  // the copy of the pass before has read the staging area
-            if (on) {
-#pragma unroll
-                for (uint32_t q = 0; q < kRecChunk; ++q)
-                    if (q < chunk) s_rec[q * kRecPitch + (r - r_lo)] = rec[w0 + q < kRecWords ? w0 + q : 0u];
-            }
-            __syncthreads();
-            const uint32_t words = kept * chunk;
-            for (uint32_t q = t; q < words; q += 256u) {
-                const uint32_t g = q / chunk, ww = q % chunk;
-                d_aos[(uint64_t)g * kStride + w0 + ww] = s_rec[ww * kRecPitch + g];
-            }
-        }
+        // (passes of 8 words; 4 for the 12-word record's second pass)
+        stage_rows_out<uint4, kRecChunk, kStride>(s_rec, dst.sh_aos + (j0 + r_lo) * kStride, on, r - r_lo, r_hi - r_lo, [&](uint32_t q) { return rec[q]; });
     }
 }
 
 hipError_t launch_merge_bake(hipStream_t s, int sh_kind, int cov_kind, uint64_t n_src, uint64_t n_dst, uint64_t dst_offset, const uint32_t* keep,
                              const uint32_t* bases, const ExtractPlanes& src, const ExtractPlanes& dst, const MergeBake& bake) {
     const dim3 grid((uint32_t)extract_groups(n_src)), block(256);
-#define GSX_MG_CASE(SH, COV)                                                                                                  \
-    if (sh_kind == SH && cov_kind == COV) {                                                                                   \
-        GSX_LAUNCH((k_merge_bake<SH, COV>), grid, block, 0, s, n_src, n_dst, dst_offset, keep, bases, src, dst, bake);       \
-        return hipGetLastError();                                                                                             \
-    }
-    GSX_MG_CASE(GSX_SH_SINGLE, GSX_COV3D_SINGLE) GSX_MG_CASE(GSX_SH_SINGLE, GSX_COV3D_HALF)
-    GSX_MG_CASE(GSX_SH_HALF, GSX_COV3D_SINGLE) GSX_MG_CASE(GSX_SH_HALF, GSX_COV3D_HALF)
-    GSX_MG_CASE(GSX_SH_NORM8, GSX_COV3D_SINGLE) GSX_MG_CASE(GSX_SH_NORM8, GSX_COV3D_HALF)
-    GSX_MG_CASE(GSX_SH_NONE, GSX_COV3D_SINGLE) GSX_MG_CASE(GSX_SH_NONE, GSX_COV3D_HALF)
-#undef GSX_MG_CASE
-    return hipErrorInvalidValue;
+    return dispatch_pod_kind(sh_kind, cov_kind, [&](auto sh, auto cov) {
+        GSX_LAUNCH((k_merge_bake<decltype(sh)::value, decltype(cov)::value>), grid, block, 0, s, n_src, n_dst, dst_offset, keep, bases, src, dst, bake);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace gsx

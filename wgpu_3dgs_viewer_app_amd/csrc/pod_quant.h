@@ -1,6 +1,7 @@
-// pod_quant.h — the quantisation of compressed pods (spec/RENDER_SPEC.md §2b), written once: the upload conversion and the projection
-// pass (kernels_project.hip), the shading of shade records (shade_quads.h) and the bake of gsx_model_merge (kernels_merge.hip) all
-// store and read Half and Norm8 values through these.  Build-internal, device code.
+// pod_quant.h — the scalar conversions of compressed pods (spec/RENDER_SPEC.md §2b), written once: the upload conversion and the
+// projection pass (kernels_project.hip), the shading of shade records (shade_quads.h), the bake of gsx_model_merge (kernels_merge.hip)
+// and the per-kind plane decode of the model operations (pod_planes.h: pod_load_cov, pod_load_sh) all store and read Half and Norm8
+// values through these.  Build-internal, device code.
 //   f16: IEEE binary16, round to nearest even (what `half::f16::from_f32` does; v_cvt_f16_f32); decoding is exact.
 //   snorm8: q = floor(clamp(v,-1,1) * 127 + 0.5) as int8; decode = max(q / 127, -1) (WGSL unpack4x8snorm).
 #pragma once
