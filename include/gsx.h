@@ -503,6 +503,38 @@ void gsx_export_desc_default(gsx_export_desc* d); /* all zero: whole model, gsx_
 gsx_status gsx_model_export(gsx_viewer* v, const char* key, const gsx_export_desc* desc, void* out, uint64_t capacity_bytes, uint64_t* out_count);
 gsx_status gsx_model_export_ply(gsx_viewer* v, const char* key, const gsx_export_desc* desc, void* out, uint64_t capacity, uint64_t* out_size);
 
+/* ---- PLY import on the device (spec/RENDER_SPEC.md §15 [BUILD-SPEC]): the load path of the app, read_ply_header -> read_ply_gaussians
+ *      -> Gaussian::from -> update_range (src/app.rs:1053-1096), without a gsx_gaussian record in between.  Binary vertex rows are
+ *      copied into device staging and decoded there straight into the resident planes; the bits a model holds afterwards are those
+ *      gsx_model_upload_range leaves for the §15 records of the rows.  Against gsx_ply_read_gaussians (which goes through the host's
+ *      float32 expf): pos, rot, sh and the rgb bytes are the same bits for finite inputs, scale is within 1 float32 ulp, alpha within 1.
+ *      gsx_model_upload_ply_rows: the streaming form.  `rows` are n binary rows of header->vertex_bytes each (the file's data +
+ *      header_bytes + first_row * vertex_bytes), in host memory; they become the Gaussians [start, start + n) of model `key`.  Keys,
+ *      ranges, shards and ordering are gsx_model_upload_range's: wherever that call is legal, this one is.  n == 0 is GSX_OK and does
+ *      nothing.  The header is the caller's and is checked before a row is read: not ascii, 0 < vertex_bytes <= 1024, every offset -1
+ *      or inside the row (offset + 4 <= vertex_bytes), the fourteen properties gsx_ply_read_header requires present; a header that
+ *      fails is GSX_ERR_INVALID_ARG, but an ascii one or a stride above 1024 is GSX_ERR_UNSUPPORTED (gsx_ply_read_gaussians reads
+ *      those).  Offsets and strides need not be multiples of 4.
+ *      gsx_model_import_ply: the whole file.  Runs gsx_ply_read_header, creates model `key` with the header's count and the given pod
+ *      kinds, decodes every row; *out_count receives the count.  A count of 0 is GSX_OK with *out_count 0 and no model.
+ *      Staging: rows pass through the two device staging buffers the export uses, of staging_bytes each (0: the library's default,
+ *      32 MiB; raised to 1024 rows, never more rows than the call has); the kernel of a chunk runs while the next chunk is copied.  The
+ *      buffers belong to the viewer, are counted by gsx_debug_device_bytes and are freed with it.
+ *      Errors: a null viewer, key, data / header, desc or count pointer, a key that exists, flag bits (none are defined), a non-zero
+ *      reserved: GSX_ERR_INVALID_ARG.  Header errors: GSX_ERR_PLY as gsx_ply_read_header returns them.  size below header_bytes +
+ *      count x vertex_bytes: GSX_ERR_IO.  ascii, a stride above 1024, a viewer with a communicator: GSX_ERR_UNSUPPORTED.  Allocation
+ *      failure: GSX_ERR_OOM.  After an error of gsx_model_import_ply no model `key` exists and the viewer's device bytes are what they
+ *      were, the staging buffers apart.
+ *      Ordering: as gsx_model_extract, on the viewer's stream behind the lanes' frames in flight and earlier uploads.  Both calls
+ *      return when the caller's memory is no longer read and the kernels are complete. ---- */
+typedef struct gsx_ply_header gsx_ply_header; /* defined with the PLY I/O block below */
+typedef struct gsx_import_desc { uint32_t flags; uint32_t reserved; uint64_t staging_bytes; } gsx_import_desc; /* 16 B */
+void gsx_import_desc_default(gsx_import_desc* d); /* all zero */
+gsx_status gsx_model_upload_ply_rows(gsx_viewer* v, const char* key, uint64_t start, const void* rows, uint64_t n,
+                                     const gsx_ply_header* header, const gsx_import_desc* desc);
+gsx_status gsx_model_import_ply(gsx_viewer* v, const char* key, const void* data, uint64_t size, gsx_sh_kind sh,
+                                gsx_cov3d_kind cov3d, const gsx_import_desc* desc, uint64_t* out_count);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

@@ -105,6 +105,12 @@ public:
         check(gsx_model_upload_range(v_, key_.c_str(), start, gaussians, n));
     }
     void update_range(size_t start, const std::vector<Gaussian>& g) { update_range(start, g.data(), g.size()); }
+    // gsx_model_upload_ply_rows: n binary PLY vertex rows of header.vertex_bytes each, decoded on the device into the Gaussians from
+    // `start` on (spec section 15): update_range of the rows' Gaussians without the records in between
+    void update_range_ply(size_t start, const void* rows, size_t n, const gsx_ply_header& header, uint64_t staging_bytes = 0) {
+        const gsx_import_desc d{0u, 0u, staging_bytes};
+        check(gsx_model_upload_ply_rows(v_, key_.c_str(), start, rows, n, &header, &d));
+    }
 };
 // A cloned buffer (`edit_buffer.clone()` / `mask_buffer.clone()`, app.rs:769-780): copyable, shares one device-side snapshot
 // taken at clone time; download() may run on any thread while the viewer renders (gsx_buffer_*).
@@ -305,6 +311,18 @@ public:
         std::vector<uint8_t> out(size);
         check(gsx_model_export_ply(v_, key.c_str(), &d, out.data(), out.size(), &size));
         return out;
+    }
+    // gsx_model_import_ply: the app's load path read_ply_header -> read_ply_gaussians -> Gaussian::from -> update_range (app.rs:1053-1096)
+    // in one call, the rows decoded on the device: a binary INRIA PLY file becomes the new model `key` of this viewer's pod kinds.
+    // Returns the count; a file of 0 vertices creates no model.
+    uint64_t import_ply(const std::string& key, const void* data, uint64_t size, uint64_t staging_bytes = 0) {
+        const gsx_import_desc d{0u, 0u, staging_bytes};
+        uint64_t count = 0;
+        check(gsx_model_import_ply(v_, key.c_str(), data, size, (gsx_sh_kind)sh, (gsx_cov3d_kind)cov3d, &d, &count));
+        if (count)
+            models.emplace(key, MultiModelViewerModel{{GaussiansBuffer(v_, key), MaskBuffer(v_, key), SelectionBuffer(v_, key),
+                                                       GaussiansEditBuffer(v_, key)}, v_, key});
+        return count;
     }
     void remove_model(const std::string& key) {  // scene.rs:2176
         check(gsx_model_remove(v_, key.c_str()));

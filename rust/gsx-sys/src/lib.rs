@@ -120,6 +120,10 @@ pub struct gsx_extract_desc { pub filter: u32, pub flags: u32 }
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_export_desc { pub filter: u32, pub flags: u32, pub format: u32, pub reserved: u32, pub staging_bytes: u64 }
+/// how gsx_model_import_ply and gsx_model_upload_ply_rows stage their rows (flags: none are defined; staging_bytes 0: the default)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_import_desc { pub flags: u32, pub reserved: u32, pub staging_bytes: u64 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }
@@ -240,6 +244,9 @@ extern "C" {
     pub fn gsx_export_desc_default(d: *mut gsx_export_desc);
     pub fn gsx_model_export(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_export_desc, out: *mut c_void, capacity_bytes: u64, out_count: *mut u64) -> gsx_status;
     pub fn gsx_model_export_ply(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_export_desc, out: *mut c_void, capacity: u64, out_size: *mut u64) -> gsx_status;
+    pub fn gsx_import_desc_default(d: *mut gsx_import_desc);
+    pub fn gsx_model_upload_ply_rows(v: *mut gsx_viewer, key: *const c_char, start: u64, rows: *const c_void, n: u64, header: *const gsx_ply_header, desc: *const gsx_import_desc) -> gsx_status;
+    pub fn gsx_model_import_ply(v: *mut gsx_viewer, key: *const c_char, data: *const c_void, size: u64, sh: gsx_sh_kind, cov3d: gsx_cov3d_kind, desc: *const gsx_import_desc, out_count: *mut u64) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

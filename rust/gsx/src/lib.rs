@@ -90,6 +90,13 @@ impl GaussiansBuffer {
         check(unsafe { sys::gsx_model_upload_range(self.v, self.key.as_ptr(), start as u64, gaussians.as_ptr(), gaussians.len() as u64) })
             .expect("update_range"); // infallible in the crate's signature: panics like the reference (scene.rs:2078-2081)
     }
+    /// `gsx_model_upload_ply_rows`: binary PLY vertex rows (`header.vertex_bytes` each) decoded on the device into the Gaussians from
+    /// `start` on: `update_range` of the rows' Gaussians without the records in between (spec section 15).
+    pub fn update_range_ply<Q>(&self, _queue: &Q, start: usize, rows: &[u8], header: &sys::gsx_ply_header) -> Result<(), Error> {
+        let desc = sys::gsx_import_desc { flags: 0, reserved: 0, staging_bytes: 0 };
+        let n = if header.vertex_bytes > 0 { rows.len() as u64 / header.vertex_bytes as u64 } else { 0 };
+        check(unsafe { sys::gsx_model_upload_ply_rows(self.v, self.key.as_ptr(), start as u64, rows.as_ptr() as *const std::os::raw::c_void, n, header, &desc) })
+    }
     pub fn len(&self) -> usize {
         let mut n = 0u64;
         check(unsafe { sys::gsx_model_len(self.v, self.key.as_ptr(), &mut n) }).expect("len");
@@ -325,6 +332,24 @@ impl<G: GaussianPod> MultiModelViewer<G> {
         let mut out = vec![0u8; size as usize];
         check(unsafe { sys::gsx_model_export_ply(self.handle.0, k.as_ptr(), &desc, out.as_mut_ptr() as *mut std::os::raw::c_void, size, &mut size) })?;
         Ok(out)
+    }
+    /// `gsx_model_import_ply`: the app's load path `read_ply_header -> read_ply_gaussians -> Gaussian::from -> update_range`
+    /// (app.rs:1053-1096) in one call, the rows decoded on the device: a binary INRIA PLY file becomes the new model `key` of pod `G`.
+    /// Returns the count; a file of 0 vertices creates no model.
+    pub fn import_ply(&mut self, key: &str, data: &[u8]) -> Result<u64, Error> {
+        let k = CString::new(key).unwrap();
+        let desc = sys::gsx_import_desc { flags: 0, reserved: 0, staging_bytes: 0 };
+        let mut count = 0u64;
+        check(unsafe { sys::gsx_model_import_ply(self.handle.0, k.as_ptr(), data.as_ptr() as *const std::os::raw::c_void, data.len() as u64, G::SH, G::COV3D, &desc, &mut count) })?;
+        if count > 0 {
+            let (v, n) = (self.handle.0, count as usize);
+            self.models.insert(key.to_owned(), MultiModelViewerModel { gaussian_buffers: MultiModelViewerGaussianBuffers {
+                gaussians_buffer: GaussiansBuffer { v, key: k.clone() },
+                mask_buffer: MaskBuffer { v, key: k.clone(), words: (n + 31) / 32 },
+                gaussians_edit_buffer: GaussiansEditBuffer { v, key: k.clone(), n },
+            }, v, key: k });
+        }
+        Ok(count)
     }
     /// `viewer.remove_model(&key)` (scene.rs:2176)
     pub fn remove_model(&mut self, key: &str) {

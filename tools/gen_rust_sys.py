@@ -169,6 +169,10 @@ pub struct gsx_extract_desc { pub filter: u32, pub flags: u32 }
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_export_desc { pub filter: u32, pub flags: u32, pub format: u32, pub reserved: u32, pub staging_bytes: u64 }
+/// how gsx_model_import_ply and gsx_model_upload_ply_rows stage their rows (flags: none are defined; staging_bytes 0: the default)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_import_desc { pub flags: u32, pub reserved: u32, pub staging_bytes: u64 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }

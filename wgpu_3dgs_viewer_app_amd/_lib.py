@@ -49,6 +49,7 @@ EXPORTS = (
     "gsx_bounds_desc_default", "gsx_model_bounds",
     "gsx_extract_desc_default", "gsx_model_extract", "gsx_model_merge",
     "gsx_export_desc_default", "gsx_model_export", "gsx_model_export_ply",
+    "gsx_import_desc_default", "gsx_model_upload_ply_rows", "gsx_model_import_ply",
 )
 
 
@@ -100,6 +101,11 @@ class ExportDesc(C.Structure):
     """``gsx_export_desc`` (24 bytes): which Gaussians are exported (``GSX_BOUNDS_*``), ``GSX_EXTRACT_INVERT | GSX_EXPORT_BAKE_EDITS``,
     the row format (``GSX_EXPORT_*``) and the size of one device staging buffer (0: the library's default)."""
     _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("format", C.c_uint32), ("reserved", C.c_uint32), ("staging_bytes", C.c_uint64)]
+
+
+class ImportDesc(C.Structure):
+    """``gsx_import_desc`` (16 bytes): flags (none are defined), and the size of one device staging buffer (0: the library's default)."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("staging_bytes", C.c_uint64)]
 
 
 class ExtractDesc(C.Structure):
@@ -339,6 +345,9 @@ def load() -> C.CDLL:
         "gsx_export_desc_default": ([C.POINTER(ExportDesc)], None),
         "gsx_model_export": ([vp, cp, C.POINTER(ExportDesc), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int32),
         "gsx_model_export_ply": ([vp, cp, C.POINTER(ExportDesc), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_import_desc_default": ([C.POINTER(ImportDesc)], None),
+        "gsx_model_upload_ply_rows": ([vp, cp, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(PlyHeader), C.POINTER(ImportDesc)], C.c_int32),
+        "gsx_model_import_ply": ([vp, cp, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(ImportDesc), C.POINTER(C.c_uint64)], C.c_int32),
         "gsx_model_merge": ([vp, C.POINTER(C.c_char_p), C.c_uint32, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)

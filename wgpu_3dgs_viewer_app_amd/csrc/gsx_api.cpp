@@ -338,13 +338,13 @@ void gsx_viewer_destroy(gsx_viewer* v) {
     if (v->lane_event) (void)hipEventDestroy(v->lane_event);
     if (v->depth_event) (void)hipEventDestroy(v->depth_event);
     for (hipStream_t ps : v->parked_streams) (void)hipStreamDestroy(ps);
-    if (v->export_stream) {  // gsx_model_export's copy stream and events (the staging buffers go with the viewer's other DevBufs)
-        (void)gsx::op::StreamSynchronize(v->export_stream);
+    if (v->row_stream) {  // the copy stream and events of the model export and import (the staging buffers go with the viewer's other DevBufs)
+        (void)gsx::op::StreamSynchronize(v->row_stream);
         for (int b = 0; b < 2; ++b) {
-            if (v->export_written[b]) (void)hipEventDestroy(v->export_written[b]);
-            if (v->export_copied[b]) (void)hipEventDestroy(v->export_copied[b]);
+            if (v->row_kernel_done[b]) (void)hipEventDestroy(v->row_kernel_done[b]);
+            if (v->row_copy_done[b]) (void)hipEventDestroy(v->row_copy_done[b]);
         }
-        (void)hipStreamDestroy(v->export_stream);
+        (void)hipStreamDestroy(v->row_stream);
     }
     if (v->h_shard_verdict) (void)hipHostFree(v->h_shard_verdict);
     if (v->h_verdict_ring) (void)hipHostFree(v->h_verdict_ring);

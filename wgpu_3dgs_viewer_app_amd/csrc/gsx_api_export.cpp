@@ -10,6 +10,16 @@ namespace gsx {
 std::string ply_header(uint64_t count);  // gsx_ply.cpp: the one header writer
 }
 
+gsx_status gsx::row_streams(gsx_viewer* v) {
+    if (v->row_stream) return GSX_OK;
+    HIPCHK(hipStreamCreateWithFlags(&v->row_stream, hipStreamNonBlocking));
+    for (int b = 0; b < 2; ++b) {
+        HIPCHK(hipEventCreateWithFlags(&v->row_kernel_done[b], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&v->row_copy_done[b], hipEventDisableTiming));
+    }
+    return GSX_OK;
+}
+
 namespace {
 constexpr uint64_t kDefaultStagingBytes = 32ull << 20;  // one staging buffer when the desc says 0
 
@@ -38,16 +48,6 @@ gsx_status export_keep(gsx_viewer* v, const char* key, const gsx_export_desc* de
     return kept_sets(v, k, 1, desc->filter, (desc->flags & GSX_EXTRACT_INVERT) != 0, want_bases ? &k->bases : nullptr);
 }
 
-gsx_status export_streams(gsx_viewer* v) {
-    if (v->export_stream) return GSX_OK;
-    HIPCHK(hipStreamCreateWithFlags(&v->export_stream, hipStreamNonBlocking));
-    for (int b = 0; b < 2; ++b) {
-        HIPCHK(hipEventCreateWithFlags(&v->export_written[b], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&v->export_copied[b], hipEventDisableTiming));
-    }
-    return GSX_OK;
-}
-
 // the chunk loop: k->total rows of `format` into out (k->total > 0, out holds them)
 gsx_status export_rows(gsx_viewer* v, const gsx_export_desc* desc, uint32_t format, const Kept& k, char* out) {
     const Model* m = k.m;
@@ -56,9 +56,9 @@ gsx_status export_rows(gsx_viewer* v, const gsx_export_desc* desc, uint32_t form
     uint64_t stage_rows = (desc->staging_bytes ? desc->staging_bytes : kDefaultStagingBytes) / rb;
     if (stage_rows < kExtractGroup) stage_rows = kExtractGroup;
     if (stage_rows > k.total) stage_rows = k.total;  // (no chunk has more rows than the call)
-    gsx_status st = export_streams(v);
+    gsx_status st = row_streams(v);
     if (st) return st;
-    for (int b = 0; b < 2; ++b) HIPCHK(v->export_stage[b].ensure((size_t)(stage_rows * rb)));
+    for (int b = 0; b < 2; ++b) HIPCHK(v->row_stage[b].ensure((size_t)(stage_rows * rb)));
     const bool bake = (desc->flags & GSX_EXPORT_BAKE_EDITS) && m->has_edits;
     const ExtractPlanes src = extract_planes(m, bake);
 
@@ -83,11 +83,11 @@ gsx_status export_rows(gsx_viewer* v, const gsx_export_desc* desc, uint32_t form
     auto rows_kernel = [&](size_t c) {
         const int b = (int)(c & 1u);
         const Chunk& ch = chunks[c];
-        hipError_t r = c >= 2 ? gsx::op::StreamWaitEvent(v->stream, v->export_copied[b], 0) : hipSuccess;
+        hipError_t r = c >= 2 ? gsx::op::StreamWaitEvent(v->stream, v->row_copy_done[b], 0) : hipSuccess;
         if (r == hipSuccess)
             r = launch_export_rows(v->stream, (int)m->sh_kind, (int)m->cov_kind, format, m->n, (uint32_t)ch.g0, (uint32_t)(ch.g1 - ch.g0), k.bases[ch.g0], k.d_keep,
-                                   k.d_bases, src, v->export_stage[b].p);
-        if (r == hipSuccess) r = gsx::op::EventRecord(v->export_written[b], v->stream);
+                                   k.d_bases, src, v->row_stage[b].p);
+        if (r == hipSuccess) r = gsx::op::EventRecord(v->row_kernel_done[b], v->stream);
         return r;
     };
     if (!chunks.empty()) e = rows_kernel(0);
@@ -96,14 +96,14 @@ gsx_status export_rows(gsx_viewer* v, const gsx_export_desc* desc, uint32_t form
         const Chunk& ch = chunks[c];
         if (c + 1 < chunks.size()) e = rows_kernel(c + 1);
         const uint64_t rows = (uint64_t)k.bases[ch.g1] - k.bases[ch.g0];
-        if (e == hipSuccess) e = gsx::op::StreamWaitEvent(v->export_stream, v->export_written[b], 0);
-        if (e == hipSuccess) e = gsx::op::MemcpyAsync(out + (uint64_t)k.bases[ch.g0] * rb, v->export_stage[b].p, (size_t)(rows * rb), hipMemcpyDeviceToHost, v->export_stream);
-        if (e == hipSuccess) e = gsx::op::EventRecord(v->export_copied[b], v->export_stream);
+        if (e == hipSuccess) e = gsx::op::StreamWaitEvent(v->row_stream, v->row_kernel_done[b], 0);
+        if (e == hipSuccess) e = gsx::op::MemcpyAsync(out + (uint64_t)k.bases[ch.g0] * rb, v->row_stage[b].p, (size_t)(rows * rb), hipMemcpyDeviceToHost, v->row_stream);
+        if (e == hipSuccess) e = gsx::op::EventRecord(v->row_copy_done[b], v->row_stream);
     }
     gsx_status err = GSX_OK;
     if (e != hipSuccess) err = fail(e == hipErrorOutOfMemory ? GSX_ERR_OOM : GSX_ERR_HIP, "gsx_model_export: a chunk failed: %s", hipGetErrorString(e));
     // the call returns when `out` is complete (and, after an error, when nothing of it is in flight any more)
-    hipError_t e1 = gsx::op::StreamSynchronize(v->export_stream), e2 = gsx::op::StreamSynchronize(v->stream);
+    hipError_t e1 = gsx::op::StreamSynchronize(v->row_stream), e2 = gsx::op::StreamSynchronize(v->stream);
     if (err) return err;
     HIPCHK(e1);
     HIPCHK(e2);

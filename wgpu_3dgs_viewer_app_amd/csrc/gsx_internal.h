@@ -9,6 +9,7 @@
 #include "bounds_math.h"
 #include "extract_math.h"
 #include "gizmo_math.h"
+#include "import_math.h"
 #include "merge_math.h"
 #include "toolset_math.h"
 
@@ -1023,6 +1024,16 @@ hipError_t launch_merge_bake(hipStream_t s, int sh_kind, int cov_kind, uint64_t 
 // its edit planes are present exactly when edits are to be baked.
 hipError_t launch_export_rows(hipStream_t s, int sh_kind, int cov_kind, uint32_t format, uint64_t n_src, uint32_t group0, uint32_t n_groups, uint32_t row_base,
                               const uint32_t* keep, const uint32_t* bases, const ExtractPlanes& src, void* out);
+
+// PLY import (kernels_import.hip; gsx_model_import_ply, gsx_model_upload_ply_rows): n binary rows of `lay` at d_rows (device memory,
+// 16-byte aligned, n * lay.stride bytes: nothing outside them is read) become the Gaussians [start, start + n) of the planes, as
+// launch_convert would write the records of spec section 15.  One lane a Gaussian, kImportGroup rows a workgroup.  `read` picks the
+// read side: kImportAuto = the slab kernel for the canonical layout and the general kernel for every other; kImportSlab and
+// kImportDirect take the canonical layout only (the second exists for tools/bench_import.py: DESIGN section 4).
+constexpr uint32_t kImportGroup = 128;  // (256 rows, 62 KiB of LDS and two workgroups a CU, was measured 4 to 11 % slower: DESIGN section 4)
+enum { kImportAuto = 0, kImportSlab = 1, kImportDirect = 2, kImportGeneral = 3 };
+hipError_t launch_import_rows(hipStream_t s, const void* d_rows, uint64_t n, uint64_t start, uint64_t model_n, const PodPlanes& pod,
+                              const ImportLayout& lay, int read = kImportAuto);
 
 // Compositing and resolve.
 // carry: continue from the (C, T) already in fb (later slabs / models behind); done: saturated-tile bitmap

@@ -503,12 +503,14 @@ struct gsx_viewer {
     // (popcount partials, their scan), allocated by the first call and grown when a larger model is extracted from.  gsx_model_merge
     // (gsx_api_merge.cpp) lays one such region per source behind its array of totals.  Nothing a frame reads
     DevBuf extract_ws;
-    // gsx_model_export (gsx_api_export.cpp; owner only): two staging buffers of rows, so that the kernel of one chunk runs while the
-    // chunk before it is copied to the host on export_stream; an event per buffer for "rows written" and one for "rows copied".
-    // Allocated by the first call that writes rows, grown when a call asks for larger staging, freed with the viewer
-    DevBuf export_stage[2];
-    hipStream_t export_stream = nullptr;
-    hipEvent_t export_written[2]{}, export_copied[2]{};
+    // gsx_model_export and gsx_model_import_ply (gsx_api_export.cpp, gsx_api_import.cpp; owner only): two staging buffers of rows, so
+    // that the kernel of one chunk runs while the chunk before it (export) or after it (import) is copied on row_stream; an event per
+    // buffer for "the kernel is done with the buffer" and one for "the copy is done with it".  Both calls wait for both streams before
+    // they return, so the buffers never serve two calls at once.  Allocated by the first call that moves rows (row_streams), grown when
+    // a call asks for larger staging, freed with the viewer
+    DevBuf row_stage[2];
+    hipStream_t row_stream = nullptr;
+    hipEvent_t row_kernel_done[2]{}, row_copy_done[2]{};
 };
 
 namespace gsx {
@@ -738,6 +740,8 @@ inline ModelFilter model_filter(const Model* m, uint32_t filter_bits, bool inver
     f.invert = invert ? 1u : 0u;
     return f;
 }
+// the copy stream and the events of the row staging buffers, created on first use (gsx_api_export.cpp)
+gsx_status row_streams(gsx_viewer* v);
 // does the model carry the shard state of a multi-GPU frame?  (gsx_model_extract, _merge and _export refuse such a model)
 inline bool model_is_shard(const Model* m) { return m->shard_win_set || m->shard_limit_valid || m->shard_next_valid || m->shard_override_tiles; }
 // The kept sets of n_src models under one filter (gsx_api_extract.cpp; the workspace is extract_ws_layout's, in v->extract_ws): the

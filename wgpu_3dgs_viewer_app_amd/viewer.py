@@ -126,6 +126,18 @@ class GaussiansBuffer:
         g = np.ascontiguousarray(gaussians, dtype=GAUSSIAN_DTYPE)
         _lib.check(self._v._L.gsx_model_upload_range(self._v._h, self._key.encode(), int(start), g.ctypes.data, g.shape[0]))
 
+    def update_range_ply(self, start: int, rows, header, staging_bytes: int = 0) -> None:
+        """``gsx_model_upload_ply_rows``: binary PLY vertex rows (a bytes-like object of ``header.raw.vertex_bytes`` each; ``header`` a
+        ``ply.PlyHeader`` or a ``_lib.PlyHeader``) decoded on the device into the Gaussians from ``start`` on: ``update_range`` of the
+        rows' Gaussians without the records in between (spec §15)."""
+        raw = getattr(header, "raw", header)
+        buf = np.frombuffer(rows, dtype=np.uint8)
+        if raw.vertex_bytes == 0 or buf.size % raw.vertex_bytes:
+            raise ValueError("rows must be whole vertices of header.vertex_bytes bytes")
+        desc = _lib.ImportDesc(0, 0, int(staging_bytes))
+        _lib.check(self._v._L.gsx_model_upload_ply_rows(self._v._h, self._key.encode(), int(start), buf.ctypes.data if buf.size else None,
+                                                        buf.size // raw.vertex_bytes, C.byref(raw), C.byref(desc)))
+
     def update_range_pod_device(self, start: int, n: int, d_pos: int, d_color: int, d_sh: int, d_cov3d: int) -> None:
         """Zero-copy upload of pod planes that already live in device memory (raw device pointers)."""
         _lib.check(self._v._L.gsx_model_upload_pod_device(self._v._h, self._key.encode(), int(start), int(n), d_pos,
@@ -447,6 +459,19 @@ class MultiModelViewer:
         _lib.check(self._L.gsx_model_create(self._h, key.encode(), int(count), int(self.sh), int(self.cov3d)))
         self.models[key] = MultiModelViewerModel(self, key)
         return self.models[key]
+
+    def import_ply(self, key: str, data, staging_bytes: int = 0) -> int:
+        """``gsx_model_import_ply``: the app's load path ``read_ply_header -> read_ply_gaussians -> Gaussian::from -> update_range``
+        (src/app.rs:1053-1096) in one call, the rows decoded on the device: the binary INRIA PLY file ``data`` (bytes-like) becomes the
+        new model ``key`` of this viewer's pod kinds.  Returns the count; a file of 0 vertices creates no model."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        desc = _lib.ImportDesc(0, 0, int(staging_bytes))
+        count = C.c_uint64()
+        _lib.check(self._L.gsx_model_import_ply(self._h, key.encode(), buf.ctypes.data if buf.size else None, buf.size, int(self.sh), int(self.cov3d),
+                                                C.byref(desc), C.byref(count)))
+        if count.value:
+            self.models[key] = MultiModelViewerModel(self, key)
+        return int(count.value)
 
     def merge(self, dst_key: str, src_keys, filter: int = 0, invert: bool = False, drop_edits: bool = False):  # noqa: A002
         """``gsx_model_merge``: the Gaussians of the models ``src_keys`` that pass ``filter`` (``_lib.GSX_BOUNDS_*`` bits, applied to
