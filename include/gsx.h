@@ -440,6 +440,7 @@ gsx_status gsx_model_extract(gsx_viewer* v, const char* src_key, const char* dst
  *      space, so a rotation that is baked has to turn the coefficients too; a scale, negative components included, needs nothing.
  *      The colour word (DC and alpha) is carried.  The shade records are written to agree with the planes word for word.
  *      Pod kinds: every source must have the first source's sh and cov3d kinds, and dst takes them (GSX_ERR_INVALID_ARG otherwise).
+ *      Sources of mixed kinds are converted first (gsx_model_convert, below), then merged.
  *      Edits: unless GSX_EXTRACT_DROP_EDITS is set, dst gets edit buffers if any source has edit records; kept Gaussians of such a
  *      source carry their stored records and edited bits (edits are colour operations), those of the other sources read as never
  *      edited.  dst has the identity transform, no mask, no selection, show_unedited off and no speculation windows.
@@ -534,6 +535,38 @@ gsx_status gsx_model_upload_ply_rows(gsx_viewer* v, const char* key, uint64_t st
                                      const gsx_ply_header* header, const gsx_import_desc* desc);
 gsx_status gsx_model_import_ply(gsx_viewer* v, const char* key, const void* data, uint64_t size, gsx_sh_kind sh,
                                 gsx_cov3d_kind cov3d, const gsx_import_desc* desc, uint64_t* out_count);
+
+/* ---- model convert: a resident model into another pod kind, on the device (spec/RENDER_SPEC.md §16 [BUILD-SPEC]).  The app's
+ *      Compression Settings (src/app.rs:152-177: SH Single / Half / Norm8 / Remove, covariance Single / Half) take effect when a file
+ *      is loaded; these calls apply them to a model that is resident, an extracted or merged one included.
+ *      gsx_model_pod_kind: the kinds the model's planes are stored in (those it was created with, or of the last
+ *      gsx_model_set_pod_kind).  A null argument: GSX_ERR_INVALID_ARG; an unknown key: GSX_ERR_NOT_FOUND.
+ *      gsx_model_convert is gsx_model_extract into a model of the kind (desc->sh, desc->cov3d).  The kept set and its order
+ *      (desc->filter: GSX_BOUNDS_* bits; desc->flags: GSX_EXTRACT_INVERT | GSX_EXTRACT_DROP_EDITS), what dst gets and lacks (src's
+ *      transform, the kept edit records and edited bits unless dropped; no mask, no selection, no speculation windows), the empty
+ *      result (GSX_OK, *out_count == 0, no model), the ordering (on the viewer's stream behind the lanes' frames, one wait for the
+ *      count), "src is not written" and every error case are gsx_model_extract's; in addition desc->sh or desc->cov3d out of range is
+ *      GSX_ERR_INVALID_ARG.
+ *      Planes: position and colour word are carried as stored bits.  Covariance and SH are dequantised exactly (§2b) and quantised
+ *      once into the destination kind (f16: round to nearest even, overflow to infinity; snorm8: clamp, floor(v * 127 + 0.5)); the
+ *      spare slots at SH floats 45 and above are zero; the shade records agree with the planes word for word, spare words zero.
+ *      That is: dst holds the bits gsx_model_upload_pod_device leaves in a fresh model of the destination kind for the four planes
+ *      gsx_model_download_pod returns of the kept Gaussians of src.  A source of Sh None stands for 45 zeros; a destination of Sh None
+ *      drops the SH and has no shade records.  When the kinds equal src's the call IS gsx_model_extract, bit for bit.  The same bits
+ *      on every call.
+ *      gsx_model_set_pod_kind: the menu entry applied to a loaded model, which keeps its key.  Its planes become what
+ *      gsx_model_convert with filter 0 makes.  It keeps its length, its transform, its mask (with the mask program's hash), its
+ *      selection, its edit records and edited bits and show_unedited: those buffers are moved, not copied.  What a frame caches starts
+ *      again as for a new model: no speculation windows, the tuner reset, the next frame an unspeculated one, on lanes too.  Handles
+ *      retained before the call keep their snapshots.  The same kind returns GSX_OK and does nothing.  Old and new planes exist side
+ *      by side during the call; on GSX_ERR_OOM the model is what it was.  Unknown key: GSX_ERR_NOT_FOUND; kind out of range:
+ *      GSX_ERR_INVALID_ARG; a viewer with a communicator, or a sharded model: GSX_ERR_UNSUPPORTED.  Ordering as gsx_model_extract;
+ *      when it returns the model can be preprocessed, sorted and rendered, on lanes too. ---- */
+gsx_status gsx_model_pod_kind(gsx_viewer* v, const char* key, gsx_sh_kind* out_sh, gsx_cov3d_kind* out_cov3d);
+typedef struct gsx_convert_desc { uint32_t filter; uint32_t flags; uint32_t sh; uint32_t cov3d; } gsx_convert_desc; /* 16 B */
+void gsx_convert_desc_default(gsx_convert_desc* d); /* all zero: the whole model, Sh Single, Cov3d Single */
+gsx_status gsx_model_convert(gsx_viewer* v, const char* src_key, const char* dst_key, const gsx_convert_desc* desc, uint64_t* out_count);
+gsx_status gsx_model_set_pod_kind(gsx_viewer* v, const char* key, gsx_sh_kind sh, gsx_cov3d_kind cov3d);
 
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,

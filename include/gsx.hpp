@@ -20,6 +20,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gsx.h"
@@ -191,6 +192,18 @@ struct MultiModelViewerModel {
         check(gsx_model_bounds(v_, key_.c_str(), &d, &b));
         return b;
     }
+    // gsx_model_pod_kind: the kinds this model's planes are stored in (a viewer may hold models of several kinds after convert)
+    std::pair<ShCompression, Cov3dCompression> pod_kind() const {
+        gsx_sh_kind s = GSX_SH_SINGLE;
+        gsx_cov3d_kind c = GSX_COV3D_SINGLE;
+        check(gsx_model_pod_kind(v_, key_.c_str(), &s, &c));
+        return {(ShCompression)s, (Cov3dCompression)c};
+    }
+    // gsx_model_set_pod_kind: the Compression Settings menu (app.rs:152-177) applied to this loaded model: same key, length, transform,
+    // mask, selection and edits; the planes requantised on the device; the next frame unspeculated.  The same kind does nothing.
+    void set_pod_kind(ShCompression sh, Cov3dCompression cov3d) {
+        check(gsx_model_set_pod_kind(v_, key_.c_str(), (gsx_sh_kind)sh, (gsx_cov3d_kind)cov3d));
+    }
 };
 
 class MultiModelViewer {
@@ -269,6 +282,19 @@ public:
         const gsx_extract_desc d{filter, flags};
         uint64_t count = 0;
         check(gsx_model_extract(v_, src_key.c_str(), dst_key.c_str(), &d, &count));
+        if (count)
+            models.emplace(dst_key, MultiModelViewerModel{{GaussiansBuffer(v_, dst_key), MaskBuffer(v_, dst_key), SelectionBuffer(v_, dst_key),
+                                                           GaussiansEditBuffer(v_, dst_key)}, v_, dst_key});
+        return count;
+    }
+    // gsx_model_convert: extract into a model of the pod kind (sh, cov3d): position and colour word carried, covariance and SH
+    // dequantised exactly and quantised once into the new kind, on the device.  The same kind is extract.  Returns the number kept; 0
+    // creates no model.  Models of different kinds are merged by converting first.
+    uint64_t convert(const std::string& src_key, const std::string& dst_key, ShCompression sh, Cov3dCompression cov3d, uint32_t filter = 0,
+                     uint32_t flags = 0) {
+        const gsx_convert_desc d{filter, flags, (uint32_t)sh, (uint32_t)cov3d};
+        uint64_t count = 0;
+        check(gsx_model_convert(v_, src_key.c_str(), dst_key.c_str(), &d, &count));
         if (count)
             models.emplace(dst_key, MultiModelViewerModel{{GaussiansBuffer(v_, dst_key), MaskBuffer(v_, dst_key), SelectionBuffer(v_, dst_key),
                                                            GaussiansEditBuffer(v_, dst_key)}, v_, dst_key});

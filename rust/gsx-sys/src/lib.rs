@@ -124,6 +124,10 @@ pub struct gsx_export_desc { pub filter: u32, pub flags: u32, pub format: u32, p
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_import_desc { pub flags: u32, pub reserved: u32, pub staging_bytes: u64 }
+/// gsx_model_convert: gsx_extract_desc's filter and flags, and the pod kind of the new model (gsx_sh_kind / gsx_cov3d_kind as u32)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_convert_desc { pub filter: u32, pub flags: u32, pub sh: u32, pub cov3d: u32 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }
@@ -247,6 +251,10 @@ extern "C" {
     pub fn gsx_import_desc_default(d: *mut gsx_import_desc);
     pub fn gsx_model_upload_ply_rows(v: *mut gsx_viewer, key: *const c_char, start: u64, rows: *const c_void, n: u64, header: *const gsx_ply_header, desc: *const gsx_import_desc) -> gsx_status;
     pub fn gsx_model_import_ply(v: *mut gsx_viewer, key: *const c_char, data: *const c_void, size: u64, sh: gsx_sh_kind, cov3d: gsx_cov3d_kind, desc: *const gsx_import_desc, out_count: *mut u64) -> gsx_status;
+    pub fn gsx_model_pod_kind(v: *mut gsx_viewer, key: *const c_char, out_sh: *mut gsx_sh_kind, out_cov3d: *mut gsx_cov3d_kind) -> gsx_status;
+    pub fn gsx_convert_desc_default(d: *mut gsx_convert_desc);
+    pub fn gsx_model_convert(v: *mut gsx_viewer, src_key: *const c_char, dst_key: *const c_char, desc: *const gsx_convert_desc, out_count: *mut u64) -> gsx_status;
+    pub fn gsx_model_set_pod_kind(v: *mut gsx_viewer, key: *const c_char, sh: gsx_sh_kind, cov3d: gsx_cov3d_kind) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

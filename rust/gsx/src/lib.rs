@@ -169,6 +169,18 @@ impl MultiModelViewerModel {
         check(unsafe { sys::gsx_model_bounds(self.v, self.key.as_ptr(), &desc, &mut out) })?;
         Ok(out)
     }
+    /// `gsx_model_pod_kind`: the kinds this model's planes are stored in (after `convert` a viewer holds models of several kinds).
+    pub fn pod_kind(&self) -> Result<(sys::gsx_sh_kind, sys::gsx_cov3d_kind), Error> {
+        let (mut sh, mut cov3d) = (sys::gsx_sh_kind::Single, sys::gsx_cov3d_kind::Single);
+        check(unsafe { sys::gsx_model_pod_kind(self.v, self.key.as_ptr(), &mut sh, &mut cov3d) })?;
+        Ok((sh, cov3d))
+    }
+    /// `gsx_model_set_pod_kind`: the Compression Settings menu (app.rs:152-177) applied to this loaded model: same key, length,
+    /// transform, mask, selection and edits; the planes requantised on the device; the next frame unspeculated.  The same kind does
+    /// nothing.
+    pub fn set_pod_kind(&mut self, sh: sys::gsx_sh_kind, cov3d: sys::gsx_cov3d_kind) -> Result<(), Error> {
+        check(unsafe { sys::gsx_model_set_pod_kind(self.v, self.key.as_ptr(), sh, cov3d) })
+    }
 }
 
 pub struct Preprocessor(*mut sys::gsx_viewer);
@@ -275,6 +287,24 @@ impl<G: GaussianPod> MultiModelViewer<G> {
         let desc = sys::gsx_extract_desc { filter, flags };
         let mut count = 0u64;
         check(unsafe { sys::gsx_model_extract(self.handle.0, s.as_ptr(), k.as_ptr(), &desc, &mut count) })?;
+        if count > 0 {
+            let (v, n) = (self.handle.0, count as usize);
+            self.models.insert(dst_key.to_owned(), MultiModelViewerModel { gaussian_buffers: MultiModelViewerGaussianBuffers {
+                gaussians_buffer: GaussiansBuffer { v, key: k.clone() },
+                mask_buffer: MaskBuffer { v, key: k.clone(), words: (n + 31) / 32 },
+                gaussians_edit_buffer: GaussiansEditBuffer { v, key: k.clone(), n },
+            }, v, key: k });
+        }
+        Ok(count)
+    }
+    /// `gsx_model_convert`: `extract` into a model of the pod kind `(sh, cov3d)`: position and colour word carried, covariance and SH
+    /// dequantised exactly and quantised once into the new kind, on the device.  The same kind is `extract`.  Returns the number kept;
+    /// 0 creates no model.  Models of different kinds are merged by converting first.
+    pub fn convert(&mut self, src_key: &str, dst_key: &str, sh: sys::gsx_sh_kind, cov3d: sys::gsx_cov3d_kind, filter: u32, flags: u32) -> Result<u64, Error> {
+        let (s, k) = (CString::new(src_key).unwrap(), CString::new(dst_key).unwrap());
+        let desc = sys::gsx_convert_desc { filter, flags, sh: sh as u32, cov3d: cov3d as u32 };
+        let mut count = 0u64;
+        check(unsafe { sys::gsx_model_convert(self.handle.0, s.as_ptr(), k.as_ptr(), &desc, &mut count) })?;
         if count > 0 {
             let (v, n) = (self.handle.0, count as usize);
             self.models.insert(dst_key.to_owned(), MultiModelViewerModel { gaussian_buffers: MultiModelViewerGaussianBuffers {

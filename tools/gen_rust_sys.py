@@ -173,6 +173,10 @@ pub struct gsx_export_desc { pub filter: u32, pub flags: u32, pub format: u32, p
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_import_desc { pub flags: u32, pub reserved: u32, pub staging_bytes: u64 }
+/// gsx_model_convert: gsx_extract_desc's filter and flags, and the pod kind of the new model (gsx_sh_kind / gsx_cov3d_kind as u32)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_convert_desc { pub filter: u32, pub flags: u32, pub sh: u32, pub cov3d: u32 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }

@@ -50,6 +50,7 @@ EXPORTS = (
     "gsx_extract_desc_default", "gsx_model_extract", "gsx_model_merge",
     "gsx_export_desc_default", "gsx_model_export", "gsx_model_export_ply",
     "gsx_import_desc_default", "gsx_model_upload_ply_rows", "gsx_model_import_ply",
+    "gsx_model_pod_kind", "gsx_convert_desc_default", "gsx_model_convert", "gsx_model_set_pod_kind",
 )
 
 
@@ -106,6 +107,12 @@ class ExportDesc(C.Structure):
 class ImportDesc(C.Structure):
     """``gsx_import_desc`` (16 bytes): flags (none are defined), and the size of one device staging buffer (0: the library's default)."""
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("staging_bytes", C.c_uint64)]
+
+
+class ConvertDesc(C.Structure):
+    """``gsx_convert_desc`` (16 bytes): ``ExtractDesc``'s filter and flags, and the pod kind of the new model (``gsx_sh_kind``,
+    ``gsx_cov3d_kind``)."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("sh", C.c_uint32), ("cov3d", C.c_uint32)]
 
 
 class ExtractDesc(C.Structure):
@@ -348,6 +355,10 @@ def load() -> C.CDLL:
         "gsx_import_desc_default": ([C.POINTER(ImportDesc)], None),
         "gsx_model_upload_ply_rows": ([vp, cp, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(PlyHeader), C.POINTER(ImportDesc)], C.c_int32),
         "gsx_model_import_ply": ([vp, cp, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(ImportDesc), C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_model_pod_kind": ([vp, cp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int32),
+        "gsx_convert_desc_default": ([C.POINTER(ConvertDesc)], None),
+        "gsx_model_convert": ([vp, cp, cp, C.POINTER(ConvertDesc), C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_model_set_pod_kind": ([vp, cp, C.c_int32, C.c_int32], C.c_int32),
         "gsx_model_merge": ([vp, C.POINTER(C.c_char_p), C.c_uint32, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)

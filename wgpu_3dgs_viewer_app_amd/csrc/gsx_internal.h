@@ -1018,6 +1018,12 @@ struct MergeBake {
 hipError_t launch_merge_bake(hipStream_t s, int sh_kind, int cov_kind, uint64_t n_src, uint64_t n_dst, uint64_t dst_offset, const uint32_t* keep,
                              const uint32_t* bases, const ExtractPlanes& src, const ExtractPlanes& dst, const MergeBake& bake);
 
+// Model convert (kernels_convert.hip; gsx_model_convert, gsx_model_set_pod_kind): as launch_extract_scatter, but dst is of the kind
+// (dst_sh, dst_cov) and src of (src_sh, src_cov): covariance and SH are dequantised exactly and quantised once into dst's kind, the
+// position and the colour word are carried.  The two kinds differ: the same kind is launch_extract_scatter's (hipErrorInvalidValue).
+hipError_t launch_convert_kind(hipStream_t s, int src_sh, int src_cov, int dst_sh, int dst_cov, uint64_t n_src, uint64_t n_dst, uint64_t dst_offset,
+                               const uint32_t* keep, const uint32_t* bases, const ExtractPlanes& src, const ExtractPlanes& dst);
+
 // Model export (kernels_export.hip; gsx_model_export): the rows of the kept Gaussians of the source workgroups [group0, group0 +
 // n_groups), in `format` (GSX_EXPORT_*), into `out` starting at the chunk's first kept Gaussian: row_base = bases[group0].  `out`
 // holds at least bases[group0 + n_groups] - row_base rows (the total in place of bases[] past the last group).  src is only read;

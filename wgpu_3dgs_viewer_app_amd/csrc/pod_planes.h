@@ -1,7 +1,8 @@
 // pod_planes.h — a stored Gaussian by pod kind, written once for the model operations that read the resident planes back
-// (k_extract_scatter, k_merge_bake, k_export_rows): the record sizes of a kind, the exact dequantisation of a Gaussian's covariance
-// and SH planes (spec/RENDER_SPEC.md §2b; the scalar conversions are pod_quant.h's), and the launch dispatch over the eight
-// (sh_kind, cov_kind) pairs.  Build-internal.
+// (k_extract_scatter, k_merge_bake, k_export_rows, k_convert_kind): the record sizes of a kind, the exact dequantisation of a
+// Gaussian's covariance and SH planes (spec/RENDER_SPEC.md §2b; the scalar conversions are pod_quant.h's), the encoders that turn
+// decoded values in registers into the words of a kind (pod_encode_cov, pod_encode_sh: k_convert_kind), and the launch dispatch over
+// the eight (sh_kind, cov_kind) pairs.  Build-internal.
 #pragma once
 #include <type_traits>
 
@@ -69,6 +70,61 @@ __device__ inline void pod_load_sh(const ExtractPlanes& src, uint64_t n_src, uin
             for (int q = 0; q < 4; ++q)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) s[16 * p + 4 * q + e] = dq_snorm8(ww[q], e);
+        }
+    }
+}
+
+// ---- the write side, in registers (k_convert_kind): the words a pod of the kind stores for decoded values, quantised once ----
+// The covariance c[0 .. 5] as the words of kind COV.  Single: g1 = {xx, xy, xz, yy} (cov_a), g2 = {yz, zz, 0, 0} (cov_b = its first
+// two words); Half: g1 = {xx|xy, xz|yy, yz|zz, 0} (cov_h = its first two words, cov_h2 the third), g2 zero.  g1, then for Single g2,
+// are also the covariance words of a shade record.
+template <int COV>
+__device__ inline void pod_encode_cov(const float c[6], uint4& g1, uint4& g2) {
+    if (COV == GSX_COV3D_SINGLE) {
+        g1 = make_uint4(__float_as_uint(c[0]), __float_as_uint(c[1]), __float_as_uint(c[2]), __float_as_uint(c[3]));
+        g2 = make_uint4(__float_as_uint(c[4]), __float_as_uint(c[5]), 0u, 0u);
+    } else {
+        g1 = make_uint4(pack_h2(c[0], c[1]), pack_h2(c[2], c[3]), pack_h2(c[4], c[5]), 0u);
+        g2 = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+// The SH floats s[0 .. 44] as the words of kind SH: rec[p] is plane p's word of the Gaussian and word p of its shade record (Single:
+// rec[0 .. 10] the sh4 planes, rec[11] = {float 44, 0, 0, 0}, whose first word is the sh1 plane's; Half: rec[0 .. 5]; Norm8:
+// rec[0 .. 2]).  The spare slots at floats 45 and above are zero whatever s holds there.  None: nothing is written.
+template <int SH>
+__device__ inline void pod_encode_sh(const float s[48], uint4* rec) {
+    if (SH == GSX_SH_SINGLE) {
+#pragma unroll
+        for (int p = 0; p < kShPlanes4; ++p)
+            rec[p] = make_uint4(__float_as_uint(s[4 * p]), __float_as_uint(s[4 * p + 1]), __float_as_uint(s[4 * p + 2]), __float_as_uint(s[4 * p + 3]));
+        rec[11] = make_uint4(__float_as_uint(s[44]), 0u, 0u, 0u);
+    } else if (SH == GSX_SH_HALF) {
+#pragma unroll
+        for (int p = 0; p < 6; ++p) {
+            uint32_t ww[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int f0 = 8 * p + 2 * q, f1 = f0 + 1;
+                ww[q] = pack_h2(f0 < 45 ? s[f0] : 0.0f, f1 < 45 ? s[f1] : 0.0f);
+            }
+            rec[p] = make_uint4(ww[0], ww[1], ww[2], ww[3]);
+        }
+    } else if (SH == GSX_SH_NORM8) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            uint32_t ww[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                uint32_t v = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int f = 16 * p + 4 * q + e;
+                    v |= (f < 45 ? q_snorm8(s[f]) : 0u) << (8 * e);
+                }
+                ww[q] = v;
+            }
+            rec[p] = make_uint4(ww[0], ww[1], ww[2], ww[3]);
         }
     }
 }

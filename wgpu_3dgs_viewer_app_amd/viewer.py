@@ -332,6 +332,33 @@ class MultiModelViewerModel:
             self._v.models[dst_key] = MultiModelViewerModel(self._v, dst_key)
         return int(count.value)
 
+    @property
+    def pod_kind(self):
+        """``gsx_model_pod_kind``: the ``(ShKind, Cov3dKind)`` this model's planes are stored in: the kinds it was created with, or
+        those of the last ``set_pod_kind``."""
+        sh, cov = C.c_int32(), C.c_int32()
+        _lib.check(self._v._L.gsx_model_pod_kind(self._v._h, self._key.encode(), C.byref(sh), C.byref(cov)))
+        return ShKind(sh.value), Cov3dKind(cov.value)
+
+    def convert(self, dst_key: str, sh, cov3d, filter: int = 0, invert: bool = False, drop_edits: bool = False) -> int:  # noqa: A002
+        """``gsx_model_convert``: ``extract`` into a model of the pod kind ``(sh, cov3d)``: the same kept set, order, transform and
+        edit records; position and colour word carried, covariance and SH dequantised exactly and quantised once into the new kind
+        (what an upload of this model's ``download_pod`` into a model of that kind stores), on the device.  The same kind is
+        ``extract``.  Returns the number kept; 0 creates no model.  "Convert, then merge" joins models of different kinds."""
+        desc = _lib.ConvertDesc(int(filter), (_lib.GSX_EXTRACT_INVERT if invert else 0) | (_lib.GSX_EXTRACT_DROP_EDITS if drop_edits else 0),
+                                int(sh), int(cov3d))
+        count = C.c_uint64()
+        _lib.check(self._v._L.gsx_model_convert(self._v._h, self._key.encode(), dst_key.encode(), C.byref(desc), C.byref(count)))
+        if count.value:
+            self._v.models[dst_key] = MultiModelViewerModel(self._v, dst_key)
+        return int(count.value)
+
+    def set_pod_kind(self, sh, cov3d) -> None:
+        """``gsx_model_set_pod_kind``: the app's Compression Settings applied to this loaded model: its planes become what
+        ``convert`` makes, under the same key; length, transform, mask, selection, edit records and ``show_unedited`` stay (the
+        buffers are moved).  The next frame is an unspeculated one.  The same kind does nothing."""
+        _lib.check(self._v._L.gsx_model_set_pod_kind(self._v._h, self._key.encode(), int(sh), int(cov3d)))
+
     def _export_desc(self, filter, invert, bake_edits, fmt, staging_bytes):  # noqa: A002
         return _lib.ExportDesc(int(filter), (_lib.GSX_EXTRACT_INVERT if invert else 0) | (_lib.GSX_EXPORT_BAKE_EDITS if bake_edits else 0),
                                fmt, 0, int(staging_bytes))
