@@ -568,6 +568,58 @@ void gsx_convert_desc_default(gsx_convert_desc* d); /* all zero: the whole model
 gsx_status gsx_model_convert(gsx_viewer* v, const char* src_key, const char* dst_key, const gsx_convert_desc* desc, uint64_t* out_count);
 gsx_status gsx_model_set_pod_kind(gsx_viewer* v, const char* key, gsx_sh_kind sh, gsx_cov3d_kind cov3d);
 
+/* ---- model properties: one float32 per Gaussian, its histogram, and a selection by range, on the device (spec/RENDER_SPEC.md §17
+ *      [BUILD-SPEC]).  The reference's Selection tab stops at screen-space tools; "the near-transparent splats", "the huge ones",
+ *      "everything above a height", "everything of one colour" are choices by a stored property, made here without a Gaussian
+ *      crossing to the host.
+ *      Properties (gsx_property): POS_X/Y/Z the stored position bits in model space — with GSX_PROP_WORLD the model transform applied
+ *      as gsx_model_merge bakes a position, p' = R_m (s_m * p) + t_m in float32, an identity transform giving the stored bits;
+ *      RED/GREEN/BLUE/OPACITY the bytes of the stored colour word / 255.0f; HUE/SATURATION/VALUE the HSV of those three (spec §7's
+ *      conversion); SCALE_MAX/MID/MIN scale[0..2] as gsx_model_export solves them from the stored covariance (spec §14), special cases
+ *      included.  Stored values are read as they are: edits are not applied, gsx_model_show_unedited changes nothing.
+ *      GSX_PROP_WORLD with a property that is no position is GSX_ERR_INVALID_ARG.
+ *      gsx_model_property_values: out[i] = the property of Gaussian i, non-finite values as they come; n must be the model's length.
+ *      gsx_model_histogram: a Gaussian that passes desc->filter (GSX_BOUNDS_* bits, gsx_model_bounds' meaning) and has a finite value
+ *      is counted in `count`; min / max are exact over those (-0 below +0); counted values below lo / above hi go to `below` /
+ *      `above`, the others into desc->bins (1 .. 4096) equal bins over [lo, hi], written to out_bins[0 .. bins): their sum is count -
+ *      below - above.  NaN and +-inf go to n_nonfinite only.  The bin of a value: edge(0) = lo, edge(bins) = hi, edge(b) = min(hi, lo
+ *      + b * width) with width = (hi - lo) / bins; b is the bin with edge(b) <= v <= edge(b + 1) reached from floor((v - lo) * (bins /
+ *      (hi - lo))); a range that is zero, not finite, or too small for `bins` float32 bins puts every in-range value into bin 0.
+ *      GSX_HIST_AUTO_RANGE: desc->lo / hi are ignored, [min, max] is the range and is returned in out->lo / hi (otherwise they echo
+ *      the desc).  count == 0 is GSX_OK with zeros.  lo > hi or a non-finite lo / hi without AUTO_RANGE: GSX_ERR_INVALID_ARG.  The
+ *      same bits on every call; nothing a frame reads is written.
+ *      gsx_model_select_range: a Gaussian is hit if it passes desc->filter, its value is finite, lo <= value <= hi and, when
+ *      desc->bins > 0, its bin under (lo, hi, bins) lies in [bin_lo, bin_hi] — so the hit count is the sum of the bins bin_lo ..
+ *      bin_hi of the histogram with the same property, flags, filter, bins, lo and hi, and selecting each bin in turn partitions the
+ *      in-range set.  selection_op (gsx_selection_op): Set, the selection becomes the hit set; Add, |=; Remove, &= ~.
+ *      GSX_BOUNDS_SELECTED in the filter reads the selection as it was before the call.  A model without a selection gets one (none
+ *      = none selected); bits at or above n are written 0.  *out_hit (nullable): the hit count; *out_selected (nullable): the
+ *      selected count afterwards.  GSX_HIST_AUTO_RANGE is not legal here.  Ordering and frame consistency are
+ *      gsx_model_upload_selection's: on the viewer's stream behind the lanes' frames in flight, the next frame sees the selection.
+ *      Errors of all three: a null viewer, key, desc or required out pointer, an unknown property, flag, filter bit or op, bins out
+ *      of range, bin_lo > bin_hi, bin_hi >= bins, reserved != 0: GSX_ERR_INVALID_ARG; unknown key: GSX_ERR_NOT_FOUND; a viewer with a
+ *      communicator, or a sharded model: GSX_ERR_UNSUPPORTED.  A model of 0 Gaussians: GSX_OK with zeros. ---- */
+typedef enum gsx_property {
+    GSX_PROP_POS_X = 0, GSX_PROP_POS_Y = 1, GSX_PROP_POS_Z = 2,
+    GSX_PROP_RED = 3, GSX_PROP_GREEN = 4, GSX_PROP_BLUE = 5, GSX_PROP_OPACITY = 6,
+    GSX_PROP_HUE = 7, GSX_PROP_SATURATION = 8, GSX_PROP_VALUE = 9,
+    GSX_PROP_SCALE_MAX = 10, GSX_PROP_SCALE_MID = 11, GSX_PROP_SCALE_MIN = 12,
+    GSX_PROP_COUNT = 13
+} gsx_property;
+#define GSX_PROP_WORLD      1u  /* positions in world space (the model transform applied as gsx_model_merge bakes it) */
+#define GSX_HIST_AUTO_RANGE 4u  /* gsx_model_histogram: the range is [min, max] of the counted values */
+#define GSX_HIST_MAX_BINS   4096u
+typedef struct gsx_histogram_desc { uint32_t property; uint32_t flags; uint32_t filter; uint32_t bins; float lo; float hi; } gsx_histogram_desc; /* 24 B */
+typedef struct gsx_histogram_t { uint64_t count; uint64_t below; uint64_t above; uint64_t n_nonfinite; float lo; float hi; float min; float max; } gsx_histogram_t; /* 48 B */
+typedef struct gsx_select_desc {
+    uint32_t property; uint32_t flags; uint32_t filter; uint32_t selection_op; /* gsx_property, GSX_PROP_WORLD, GSX_BOUNDS_*, gsx_selection_op */
+    float lo; float hi;
+    uint32_t bins; uint32_t bin_lo; uint32_t bin_hi; uint32_t reserved; /* bins 0: the range alone; reserved: 0 */
+} gsx_select_desc; /* 40 B */
+gsx_status gsx_model_property_values(gsx_viewer* v, const char* key, uint32_t property, uint32_t flags, float* out, uint64_t n);
+gsx_status gsx_model_histogram(gsx_viewer* v, const char* key, const gsx_histogram_desc* desc, uint64_t* out_bins, gsx_histogram_t* out);
+gsx_status gsx_model_select_range(gsx_viewer* v, const char* key, const gsx_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

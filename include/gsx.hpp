@@ -204,6 +204,31 @@ struct MultiModelViewerModel {
     void set_pod_kind(ShCompression sh, Cov3dCompression cov3d) {
         check(gsx_model_set_pod_kind(v_, key_.c_str(), (gsx_sh_kind)sh, (gsx_cov3d_kind)cov3d));
     }
+    // gsx_model_property_values: one float32 per Gaussian, computed on the device from the stored values (edits are not applied): the
+    // stored position (flags = GSX_PROP_WORLD: the model transform applied as merge bakes it), the bytes of the colour word / 255, their
+    // HSV, or the scales export solves from the covariance.
+    std::vector<float> property_values(gsx_property property, uint32_t flags = 0) const {
+        uint64_t n = 0;
+        check(gsx_model_len(v_, key_.c_str(), &n));
+        std::vector<float> out((size_t)n);
+        check(gsx_model_property_values(v_, key_.c_str(), (uint32_t)property, flags, out.data(), n));
+        return out;
+    }
+    // gsx_model_histogram: desc.bins equal bins of the property over [lo, hi] (GSX_HIST_AUTO_RANGE: over [min, max], returned in the
+    // result's lo / hi) among the Gaussians that pass desc.filter and have a finite value.  bins receives the counts.
+    gsx_histogram_t histogram(const gsx_histogram_desc& desc, std::vector<uint64_t>& bins) const {
+        bins.assign(desc.bins ? desc.bins : 1u, 0);
+        gsx_histogram_t h{};
+        check(gsx_model_histogram(v_, key_.c_str(), &desc, bins.data(), &h));
+        return h;
+    }
+    // gsx_model_select_range: the Gaussians that pass desc.filter, have a finite value in [lo, hi] and (desc.bins > 0) a bin in [bin_lo,
+    // bin_hi] are the hit set; desc.selection_op sets, adds or removes it, on the device.  Returns {hit, selected afterwards}.
+    std::pair<uint64_t, uint64_t> select_range(const gsx_select_desc& desc) {
+        uint64_t hit = 0, selected = 0;
+        check(gsx_model_select_range(v_, key_.c_str(), &desc, &hit, &selected));
+        return {hit, selected};
+    }
 };
 
 class MultiModelViewer {

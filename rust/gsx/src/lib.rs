@@ -181,6 +181,31 @@ impl MultiModelViewerModel {
     pub fn set_pod_kind(&mut self, sh: sys::gsx_sh_kind, cov3d: sys::gsx_cov3d_kind) -> Result<(), Error> {
         check(unsafe { sys::gsx_model_set_pod_kind(self.v, self.key.as_ptr(), sh, cov3d) })
     }
+    /// `gsx_model_property_values`: one `f32` per Gaussian, computed on the device from the stored values (edits are not applied):
+    /// the stored position (`flags = GSX_PROP_WORLD`: the model transform applied as `merge` bakes it), the bytes of the colour word
+    /// / 255, their HSV, or the scales `export` solves from the covariance.
+    pub fn property_values(&self, property: sys::gsx_property, flags: u32) -> Result<Vec<f32>, Error> {
+        let mut n = 0u64;
+        check(unsafe { sys::gsx_model_len(self.v, self.key.as_ptr(), &mut n) })?;
+        let mut out = vec![0f32; n as usize];
+        check(unsafe { sys::gsx_model_property_values(self.v, self.key.as_ptr(), property as u32, flags, out.as_mut_ptr(), n) })?;
+        Ok(out)
+    }
+    /// `gsx_model_histogram`: `desc.bins` equal bins of the property over `[lo, hi]` (`GSX_HIST_AUTO_RANGE`: over `[min, max]`,
+    /// returned in the result's `lo` / `hi`) among the Gaussians that pass `desc.filter` and have a finite value.
+    pub fn histogram(&self, desc: &sys::gsx_histogram_desc) -> Result<(sys::gsx_histogram_t, Vec<u64>), Error> {
+        let mut bins = vec![0u64; desc.bins.max(1) as usize];
+        let mut out = sys::gsx_histogram_t::default();
+        check(unsafe { sys::gsx_model_histogram(self.v, self.key.as_ptr(), desc, bins.as_mut_ptr(), &mut out) })?;
+        Ok((out, bins))
+    }
+    /// `gsx_model_select_range`: the Gaussians that pass `desc.filter`, have a finite value in `[lo, hi]` and (`desc.bins > 0`) a bin
+    /// in `[bin_lo, bin_hi]` are the hit set; `desc.selection_op` sets, adds or removes it, on the device.  Returns `(hit, selected)`.
+    pub fn select_range(&mut self, desc: &sys::gsx_select_desc) -> Result<(u64, u64), Error> {
+        let (mut hit, mut selected) = (0u64, 0u64);
+        check(unsafe { sys::gsx_model_select_range(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected) })?;
+        Ok((hit, selected))
+    }
 }
 
 pub struct Preprocessor(*mut sys::gsx_viewer);

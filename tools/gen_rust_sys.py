@@ -80,6 +80,9 @@ pub const GSX_MERGE_MAX_SOURCES: u32 = 64;
 pub const GSX_EXPORT_GAUSSIANS: u32 = 0;
 pub const GSX_EXPORT_PLY_VERTICES: u32 = 1;
 pub const GSX_EXPORT_BAKE_EDITS: u32 = 4;
+pub const GSX_PROP_WORLD: u32 = 1;
+pub const GSX_HIST_AUTO_RANGE: u32 = 4;
+pub const GSX_HIST_MAX_BINS: u32 = 4096;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -177,6 +180,27 @@ pub struct gsx_import_desc { pub flags: u32, pub reserved: u32, pub staging_byte
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_convert_desc { pub filter: u32, pub flags: u32, pub sh: u32, pub cov3d: u32 }
+/// one float32 per Gaussian (the functions take it as u32): stored position (world space with GSX_PROP_WORLD), the bytes of the colour
+/// word / 255, their HSV, the scales gsx_model_export solves from the stored covariance
+#[repr(u32)]
+#[derive(Clone, Copy, PartialEq, Eq)]
+pub enum gsx_property { PosX = 0, PosY = 1, PosZ = 2, Red = 3, Green = 4, Blue = 5, Opacity = 6, Hue = 7, Saturation = 8, Value = 9, ScaleMax = 10, ScaleMid = 11, ScaleMin = 12 }
+pub const GSX_PROP_COUNT: u32 = 13;
+/// gsx_model_histogram: the property, GSX_PROP_WORLD | GSX_HIST_AUTO_RANGE, the GSX_BOUNDS_* filter, 1..=4096 bins over [lo, hi]; 24 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_histogram_desc { pub property: u32, pub flags: u32, pub filter: u32, pub bins: u32, pub lo: f32, pub hi: f32 }
+/// the result of gsx_model_histogram, 48 bytes: counted (finite, passing the filter), below lo, above hi, NaN / inf; the range used; exact min / max
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_histogram_t { pub count: u64, pub below: u64, pub above: u64, pub n_nonfinite: u64, pub lo: f32, pub hi: f32, pub min: f32, pub max: f32 }
+/// gsx_model_select_range, 40 bytes: hit = passes the filter, finite, lo <= value <= hi and (bins > 0) its bin in [bin_lo, bin_hi]
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_select_desc {
+    pub property: u32, pub flags: u32, pub filter: u32, pub selection_op: u32, pub lo: f32, pub hi: f32,
+    pub bins: u32, pub bin_lo: u32, pub bin_hi: u32, pub reserved: u32,
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }

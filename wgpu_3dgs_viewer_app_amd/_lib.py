@@ -51,6 +51,7 @@ EXPORTS = (
     "gsx_export_desc_default", "gsx_model_export", "gsx_model_export_ply",
     "gsx_import_desc_default", "gsx_model_upload_ply_rows", "gsx_model_import_ply",
     "gsx_model_pod_kind", "gsx_convert_desc_default", "gsx_model_convert", "gsx_model_set_pod_kind",
+    "gsx_model_property_values", "gsx_model_histogram", "gsx_model_select_range",
 )
 
 
@@ -113,6 +114,35 @@ class ConvertDesc(C.Structure):
     """``gsx_convert_desc`` (16 bytes): ``ExtractDesc``'s filter and flags, and the pod kind of the new model (``gsx_sh_kind``,
     ``gsx_cov3d_kind``)."""
     _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("sh", C.c_uint32), ("cov3d", C.c_uint32)]
+
+
+#: gsx_property: one float32 per Gaussian (spec section 17)
+(GSX_PROP_POS_X, GSX_PROP_POS_Y, GSX_PROP_POS_Z, GSX_PROP_RED, GSX_PROP_GREEN, GSX_PROP_BLUE, GSX_PROP_OPACITY, GSX_PROP_HUE,
+ GSX_PROP_SATURATION, GSX_PROP_VALUE, GSX_PROP_SCALE_MAX, GSX_PROP_SCALE_MID, GSX_PROP_SCALE_MIN, GSX_PROP_COUNT) = range(14)
+#: flags of the property calls: positions in world space; gsx_model_histogram takes [min, max] as its range
+GSX_PROP_WORLD, GSX_HIST_AUTO_RANGE = 1, 4
+GSX_HIST_MAX_BINS = 4096
+#: gsx_selection_op
+GSX_SELECTION_SET, GSX_SELECTION_ADD, GSX_SELECTION_REMOVE = 0, 1, 2
+
+
+class HistogramDesc(C.Structure):
+    """``gsx_histogram_desc`` (24 bytes): the property, ``GSX_PROP_WORLD | GSX_HIST_AUTO_RANGE``, the ``GSX_BOUNDS_*`` filter, 1..4096
+    bins over ``[lo, hi]``."""
+    _fields_ = [("property", C.c_uint32), ("flags", C.c_uint32), ("filter", C.c_uint32), ("bins", C.c_uint32), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+class Histogram(C.Structure):
+    """``gsx_histogram_t`` (48 bytes)."""
+    _fields_ = [("count", C.c_uint64), ("below", C.c_uint64), ("above", C.c_uint64), ("n_nonfinite", C.c_uint64),
+                ("lo", C.c_float), ("hi", C.c_float), ("min", C.c_float), ("max", C.c_float)]
+
+
+class SelectDesc(C.Structure):
+    """``gsx_select_desc`` (40 bytes): the property, ``GSX_PROP_WORLD``, the filter, the ``gsx_selection_op``, the range, and
+    (``bins`` > 0) the bins ``[bin_lo, bin_hi]`` of the histogram over that range."""
+    _fields_ = [("property", C.c_uint32), ("flags", C.c_uint32), ("filter", C.c_uint32), ("selection_op", C.c_uint32), ("lo", C.c_float),
+                ("hi", C.c_float), ("bins", C.c_uint32), ("bin_lo", C.c_uint32), ("bin_hi", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class ExtractDesc(C.Structure):
@@ -359,6 +389,9 @@ def load() -> C.CDLL:
         "gsx_convert_desc_default": ([C.POINTER(ConvertDesc)], None),
         "gsx_model_convert": ([vp, cp, cp, C.POINTER(ConvertDesc), C.POINTER(C.c_uint64)], C.c_int32),
         "gsx_model_set_pod_kind": ([vp, cp, C.c_int32, C.c_int32], C.c_int32),
+        "gsx_model_property_values": ([vp, cp, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64], C.c_int32),
+        "gsx_model_histogram": ([vp, cp, C.POINTER(HistogramDesc), C.POINTER(C.c_uint64), C.POINTER(Histogram)], C.c_int32),
+        "gsx_model_select_range": ([vp, cp, C.POINTER(SelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
         "gsx_model_merge": ([vp, C.POINTER(C.c_char_p), C.c_uint32, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)

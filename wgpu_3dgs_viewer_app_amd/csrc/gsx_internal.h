@@ -1024,6 +1024,38 @@ hipError_t launch_merge_bake(hipStream_t s, int sh_kind, int cov_kind, uint64_t 
 hipError_t launch_convert_kind(hipStream_t s, int src_sh, int src_cov, int dst_sh, int dst_cov, uint64_t n_src, uint64_t n_dst, uint64_t dst_offset,
                                const uint32_t* keep, const uint32_t* bases, const ExtractPlanes& src, const ExtractPlanes& dst);
 
+// Model properties (kernels_property.hip; gsx_model_property_values, gsx_model_histogram, gsx_model_select_range): one frame over
+// the model in four modes, each but the first followed by a one-workgroup finish over the workgroups' partials.  The result block
+// (kPropResultWords words; the finish of a mode writes that mode's words):
+//   [0] count  [1] below  [2] above  [3] non-finite  [4] min key  [5] max key  (the histogram pass; property_math.h: prop_key)
+//   [6] hit    [7] selected afterwards                                            (the select pass)
+//   [8] count  [9] non-finite  [10] min key  [11] max key                         (the reduction in front of an AUTO_RANGE histogram)
+enum : uint32_t { kPropValues = 0, kPropReduce = 1, kPropHist = 2, kPropSelect = 3 };
+enum : uint32_t { kPropCount = 0, kPropBelowAt = 1, kPropAboveAt = 2, kPropNonfiniteAt = 3, kPropMinKey = 4, kPropMaxKey = 5, kPropHit = 6, kPropSelected = 7,
+                  kPropAutoCount = 8, kPropAutoNonfinite = 9, kPropAutoMinKey = 10, kPropAutoMaxKey = 11, kPropResultWords = 32 };
+constexpr uint32_t kPropMaxGroups = 2048;   // most workgroups (= partials) of a launch
+constexpr uint32_t kPropPartialWords = 8;   // count | below or selected | above | non-finite | min key | max key | 0 | 0
+struct PropertyJob {
+    uint32_t property;        // gsx_property
+    uint32_t world;           // positions: apply the transform below (never set for an identity transform)
+    float R[9], s[3], t[3];   // MergeBake's R_m, s_m, t_m
+    float lo, hi;             // histogram (unless auto_range) and select
+    uint32_t bins;            // histogram: 1 .. 4096; select: 0 = the range alone
+    uint32_t bin_lo, bin_hi;  // select with bins
+    uint32_t op;              // select: gsx_selection_op
+    uint32_t auto_range;      // histogram: [lo, hi] = the reduction's [min, max] (result[kPropAutoMinKey / MaxKey]; count 0: [0, 0])
+    uint32_t selection_valid; // select: 0 = the selection buffer stands for "none selected" whatever it holds
+    float* values;            // values mode: n floats
+    uint32_t* result;         // kPropResultWords words
+    uint32_t* partials;       // kPropMaxGroups x kPropPartialWords words: one partial per workgroup
+    uint32_t* hist;           // histogram: `bins` words, zeroed
+    uint32_t* selection;      // select: ceil(n / 32) words, read and written
+};
+// the histogram's zeros (and the result block's identities), in front of a histogram
+hipError_t launch_property_reset(hipStream_t s, uint32_t* result, uint32_t* hist, uint32_t bins);
+// cov_kind is read for the scale properties only; src is only read
+hipError_t launch_property(hipStream_t s, uint32_t mode, int cov_kind, uint64_t n, const ModelFilter& f, const ExtractPlanes& src, const PropertyJob& job);
+
 // Model export (kernels_export.hip; gsx_model_export): the rows of the kept Gaussians of the source workgroups [group0, group0 +
 // n_groups), in `format` (GSX_EXPORT_*), into `out` starting at the chunk's first kept Gaussian: row_base = bases[group0].  `out`
 // holds at least bases[group0 + n_groups] - row_base rows (the total in place of bases[] past the last group).  src is only read;

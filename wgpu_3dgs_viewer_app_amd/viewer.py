@@ -297,6 +297,23 @@ class ModelBounds:
     trim_max: np.ndarray
 
 
+@dataclasses.dataclass
+class PropertyHistogram:
+    """``gsx_histogram_t`` and its bins: what ``MultiModelViewerModel.histogram`` returns.  ``count``: Gaussians that pass the filter
+    and have a finite value; ``below`` / ``above``: those of them outside ``[lo, hi]``; ``bins`` (uint64) holds the others;
+    ``n_nonfinite``: NaN and infinities; ``min`` / ``max``: exact over the counted values."""
+
+    bins: np.ndarray
+    count: int
+    below: int
+    above: int
+    n_nonfinite: int
+    lo: np.float32
+    hi: np.float32
+    min: np.float32
+    max: np.float32
+
+
 class MultiModelViewerModel:
     """``gs::MultiModelViewerModel {gaussian_buffers, bind_groups}`` (src/tab/scene.rs:2133-2139)."""
 
@@ -358,6 +375,44 @@ class MultiModelViewerModel:
         ``convert`` makes, under the same key; length, transform, mask, selection, edit records and ``show_unedited`` stay (the
         buffers are moved).  The next frame is an unspeculated one.  The same kind does nothing."""
         _lib.check(self._v._L.gsx_model_set_pod_kind(self._v._h, self._key.encode(), int(sh), int(cov3d)))
+
+    def property_values(self, prop: int, world: bool = False) -> np.ndarray:
+        """``gsx_model_property_values``: the property ``prop`` (``_lib.GSX_PROP_*``) of every Gaussian as float32, computed on the
+        device from the stored values (edits are not applied): the stored position (``world``: with the model transform applied as
+        ``merge`` bakes it), the bytes of the colour word / 255, their HSV, or the scales ``export`` solves from the covariance."""
+        n = self.gaussian_buffers.gaussians_buffer.len()
+        out = np.empty(n, np.float32)
+        _lib.check(self._v._L.gsx_model_property_values(self._v._h, self._key.encode(), int(prop), _lib.GSX_PROP_WORLD if world else 0,
+                                                        out.ctypes.data, n))
+        return out
+
+    def histogram(self, prop: int, bins: int, lo: float | None = None, hi: float | None = None, filter: int = 0,  # noqa: A002
+                  world: bool = False) -> PropertyHistogram:
+        """``gsx_model_histogram``: ``bins`` (1..4096) equal bins of the property over ``[lo, hi]`` — or, with both ``None``, over
+        the ``[min, max]`` of the counted values — among the Gaussians that pass ``filter`` (``_lib.GSX_BOUNDS_*``) and have a finite
+        value.  Returns the bins, ``count``, ``below``, ``above``, ``n_nonfinite``, the range used and the exact ``min`` / ``max``;
+        ``bins.sum() == count - below - above``.  Pass the returned ``lo`` / ``hi`` to ``select_range``."""
+        auto = lo is None and hi is None
+        desc = _lib.HistogramDesc(int(prop), (_lib.GSX_PROP_WORLD if world else 0) | (_lib.GSX_HIST_AUTO_RANGE if auto else 0), int(filter),
+                                  int(bins), 0.0 if auto else float(lo), 0.0 if auto else float(hi))
+        counts = np.zeros(max(int(bins), 1), np.uint64)
+        out = _lib.Histogram()
+        _lib.check(self._v._L.gsx_model_histogram(self._v._h, self._key.encode(), C.byref(desc), counts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                  C.byref(out)))
+        return PropertyHistogram(counts, int(out.count), int(out.below), int(out.above), int(out.n_nonfinite), np.float32(out.lo),
+                                 np.float32(out.hi), np.float32(out.min), np.float32(out.max))
+
+    def select_range(self, prop: int, lo: float, hi: float, op: int = 0, filter: int = 0, world: bool = False,  # noqa: A002
+                     bins: int = 0, bin_lo: int = 0, bin_hi: int = 0) -> tuple[int, int]:
+        """``gsx_model_select_range``: the Gaussians that pass ``filter``, have a finite value and ``lo <= value <= hi`` — and, with
+        ``bins`` > 0, whose bin of the histogram over ``(lo, hi, bins)`` lies in ``[bin_lo, bin_hi]`` — are the hit set; ``op``
+        (``_lib.GSX_SELECTION_*``) makes it the selection, adds it or removes it, on the device.  Returns ``(hit, selected)``: the
+        hit count and the selected count afterwards.  The next frame highlights it; ``extract(dst, SELECTED)`` splits it off."""
+        desc = _lib.SelectDesc(int(prop), _lib.GSX_PROP_WORLD if world else 0, int(filter), int(op), float(lo), float(hi), int(bins),
+                               int(bin_lo), int(bin_hi), 0)
+        hit, selected = C.c_uint64(), C.c_uint64()
+        _lib.check(self._v._L.gsx_model_select_range(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected)))
+        return int(hit.value), int(selected.value)
 
     def _export_desc(self, filter, invert, bake_edits, fmt, staging_bytes):  # noqa: A002
         return _lib.ExportDesc(int(filter), (_lib.GSX_EXTRACT_INVERT if invert else 0) | (_lib.GSX_EXPORT_BAKE_EDITS if bake_edits else 0),
