@@ -620,6 +620,42 @@ gsx_status gsx_model_property_values(gsx_viewer* v, const char* key, uint32_t pr
 gsx_status gsx_model_histogram(gsx_viewer* v, const char* key, const gsx_histogram_desc* desc, uint64_t* out_bins, gsx_histogram_t* out);
 gsx_status gsx_model_select_range(gsx_viewer* v, const char* key, const gsx_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected);
 
+/* ---- model neighbours: how many other Gaussians lie within a radius of each one, and a selection by that count, on the device
+ *      (spec/RENDER_SPEC.md §18 [BUILD-SPEC]).  Floaters, the isolated splats of a capture, are the Gaussians with few neighbours:
+ *      gsx_model_select_neighbors with max_count = k, count_lo = 0, count_hi = k - 1, then gsx_model_extract with
+ *      GSX_BOUNDS_SELECTED and GSX_EXTRACT_INVERT.  No Gaussian crosses to the host.
+ *      Participants: a Gaussian participates if it passes desc->filter (GSX_BOUNDS_* bits, gsx_model_bounds' meaning) and its three
+ *      stored position coordinates are finite; stats.count is their number.  One that passes the filter with a NaN or infinite
+ *      coordinate goes to n_nonfinite.  Who does not participate is nobody's neighbour and has count 0.
+ *      Distance: model space, the stored position bits as they are — the model transform, the edits and gsx_model_show_unedited change
+ *      nothing.  d2(i, j) = (dx*dx + dy*dy) + dz*dz in float32, every operation rounded, dx dy dz the float32 coordinate
+ *      differences; r2 = radius * radius in float32.  j is a neighbour of i iff j != i, both participate and d2 <= r2: symmetric;
+ *      coincident Gaussians are neighbours of one another; a difference that overflows gives d2 = inf and no neighbour.
+ *      Counts: out_counts[i] (nullable; the model's length) = min(neighbours of i, max_count) for a participant, 0 otherwise, 1 <=
+ *      max_count <= GSX_NEIGHBOR_MAX_COUNT.  out_hist[c] (nullable; max_count + 1 entries) = the participants with saturated count
+ *      c; its sum is stats.count.  The same bits on every call; nothing a frame reads is written.
+ *      gsx_model_select_neighbors: a Gaussian is hit iff it participates and count_lo <= its saturated count <= count_hi (count_hi
+ *      <= max_count), so *out_hit is the sum of out_hist[count_lo .. count_hi] of gsx_model_neighbors with the same filter, radius
+ *      and max_count.  selection_op, a model without a selection, the tail bits, GSX_BOUNDS_SELECTED reading the selection as it was
+ *      before the call, *out_hit / *out_selected (nullable), ordering and frame consistency: gsx_model_select_range's.
+ *      grid_bits: 0 lets the library choose its hash table, 1 .. 24 forces 2^grid_bits buckets; no value changes a result;
+ *      stats.grid_bits returns the value used.
+ *      Errors: a null viewer, key, desc or stats pointer, unknown filter bits or op, flags != 0 (none are defined), a radius that is
+ *      not finite or not above 0 or whose float32 square is 0 or inf, max_count 0 or above 4095, grid_bits > 24, count_lo > count_hi,
+ *      count_hi > max_count, a reserved word != 0: GSX_ERR_INVALID_ARG; unknown key: GSX_ERR_NOT_FOUND; a viewer with a communicator,
+ *      or a sharded model: GSX_ERR_UNSUPPORTED; an allocation failure: GSX_ERR_OOM, the model and its selection as they were.  A
+ *      model of 0 Gaussians, or 0 participants: GSX_OK with zeros (a select with Set then clears the selection). ---- */
+#define GSX_NEIGHBOR_MAX_COUNT 4095u
+typedef struct gsx_neighbor_desc { uint32_t filter; uint32_t flags; float radius; uint32_t max_count; uint32_t grid_bits; uint32_t reserved; } gsx_neighbor_desc; /* 24 B */
+typedef struct gsx_neighbor_stats_t { uint64_t count; uint64_t n_nonfinite; uint32_t grid_bits; uint32_t reserved; } gsx_neighbor_stats_t; /* 24 B */
+typedef struct gsx_neighbor_select_desc {
+    uint32_t filter; uint32_t flags; uint32_t selection_op; uint32_t max_count; /* GSX_BOUNDS_*, 0, gsx_selection_op, 1 .. 4095 */
+    float radius; uint32_t count_lo; uint32_t count_hi; uint32_t grid_bits; uint32_t reserved[2];
+} gsx_neighbor_select_desc; /* 40 B */
+void gsx_neighbor_desc_default(gsx_neighbor_desc* d); /* no filter, radius 1, max_count 4095, the library's table */
+gsx_status gsx_model_neighbors(gsx_viewer* v, const char* key, const gsx_neighbor_desc* desc, uint32_t* out_counts, uint64_t* out_hist, gsx_neighbor_stats_t* out);
+gsx_status gsx_model_select_neighbors(gsx_viewer* v, const char* key, const gsx_neighbor_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

@@ -229,6 +229,26 @@ struct MultiModelViewerModel {
         check(gsx_model_select_range(v_, key_.c_str(), &desc, &hit, &selected));
         return {hit, selected};
     }
+    // gsx_model_neighbors: for every Gaussian, how many others lie within desc.radius of it in model space (d2 <= r2 in float32),
+    // saturated at desc.max_count, among the Gaussians that pass desc.filter and have a finite position; computed on the device with a
+    // hashed grid.  counts receives one count per Gaussian, hist[c] the number of participants with count c.
+    gsx_neighbor_stats_t neighbors(const gsx_neighbor_desc& desc, std::vector<uint32_t>& counts, std::vector<uint64_t>& hist) const {
+        uint64_t n = 0;
+        check(gsx_model_len(v_, key_.c_str(), &n));
+        counts.assign((size_t)n, 0u);
+        hist.assign((size_t)(desc.max_count < GSX_NEIGHBOR_MAX_COUNT ? desc.max_count : GSX_NEIGHBOR_MAX_COUNT) + 1u, 0);
+        gsx_neighbor_stats_t out{};
+        check(gsx_model_neighbors(v_, key_.c_str(), &desc, counts.data(), hist.data(), &out));
+        return out;
+    }
+    // gsx_model_select_neighbors: the participants whose saturated count lies in [count_lo, count_hi] are the hit set;
+    // desc.selection_op sets, adds or removes it, on the device.  Floaters with fewer than k neighbours: max_count = k, [0, k - 1].
+    // Returns {hit, selected afterwards}.
+    std::pair<uint64_t, uint64_t> select_neighbors(const gsx_neighbor_select_desc& desc) {
+        uint64_t hit = 0, selected = 0;
+        check(gsx_model_select_neighbors(v_, key_.c_str(), &desc, &hit, &selected));
+        return {hit, selected};
+    }
 };
 
 class MultiModelViewer {

@@ -34,6 +34,7 @@ pub const GSX_EXPORT_BAKE_EDITS: u32 = 4;
 pub const GSX_PROP_WORLD: u32 = 1;
 pub const GSX_HIST_AUTO_RANGE: u32 = 4;
 pub const GSX_HIST_MAX_BINS: u32 = 4096;
+pub const GSX_NEIGHBOR_MAX_COUNT: u32 = 4095;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -151,6 +152,22 @@ pub struct gsx_histogram_t { pub count: u64, pub below: u64, pub above: u64, pub
 pub struct gsx_select_desc {
     pub property: u32, pub flags: u32, pub filter: u32, pub selection_op: u32, pub lo: f32, pub hi: f32,
     pub bins: u32, pub bin_lo: u32, pub bin_hi: u32, pub reserved: u32,
+}
+/// gsx_model_neighbors, 24 bytes: the GSX_BOUNDS_* filter, flags (0), the radius (model space), the cap 1..=4095 a count saturates at,
+/// grid_bits (0: the library's hash table; 1..=24 forces 2^grid_bits buckets, no result changes)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_neighbor_desc { pub filter: u32, pub flags: u32, pub radius: f32, pub max_count: u32, pub grid_bits: u32, pub reserved: u32 }
+/// the result of gsx_model_neighbors, 24 bytes: participants (pass the filter, finite position), those with a NaN / inf coordinate, the table used
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_neighbor_stats_t { pub count: u64, pub n_nonfinite: u64, pub grid_bits: u32, pub reserved: u32 }
+/// gsx_model_select_neighbors, 40 bytes: hit = participates and count_lo <= min(neighbours, max_count) <= count_hi
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_neighbor_select_desc {
+    pub filter: u32, pub flags: u32, pub selection_op: u32, pub max_count: u32, pub radius: f32,
+    pub count_lo: u32, pub count_hi: u32, pub grid_bits: u32, pub reserved: [u32; 2],
 }
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -282,6 +299,9 @@ extern "C" {
     pub fn gsx_model_property_values(v: *mut gsx_viewer, key: *const c_char, property: u32, flags: u32, out: *mut f32, n: u64) -> gsx_status;
     pub fn gsx_model_histogram(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_histogram_desc, out_bins: *mut u64, out: *mut gsx_histogram_t) -> gsx_status;
     pub fn gsx_model_select_range(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_select_desc, out_hit: *mut u64, out_selected: *mut u64) -> gsx_status;
+    pub fn gsx_neighbor_desc_default(d: *mut gsx_neighbor_desc);
+    pub fn gsx_model_neighbors(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_neighbor_desc, out_counts: *mut u32, out_hist: *mut u64, out: *mut gsx_neighbor_stats_t) -> gsx_status;
+    pub fn gsx_model_select_neighbors(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_neighbor_select_desc, out_hit: *mut u64, out_selected: *mut u64) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

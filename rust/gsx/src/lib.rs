@@ -206,6 +206,26 @@ impl MultiModelViewerModel {
         check(unsafe { sys::gsx_model_select_range(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected) })?;
         Ok((hit, selected))
     }
+    /// `gsx_model_neighbors`: for every Gaussian, how many others lie within `desc.radius` of it in model space (`d2 <= r2` in `f32`),
+    /// saturated at `desc.max_count`, among the Gaussians that pass `desc.filter` and have a finite position; computed on the device
+    /// with a hashed grid.  Returns `(counts, hist, stats)`: `hist[c]` is the number of participants with count `c`.
+    pub fn neighbors(&self, desc: &sys::gsx_neighbor_desc) -> Result<(Vec<u32>, Vec<u64>, sys::gsx_neighbor_stats_t), Error> {
+        let mut n = 0u64;
+        check(unsafe { sys::gsx_model_len(self.v, self.key.as_ptr(), &mut n) })?;
+        let mut counts = vec![0u32; n as usize];
+        let mut hist = vec![0u64; desc.max_count.min(sys::GSX_NEIGHBOR_MAX_COUNT) as usize + 1];
+        let mut out = sys::gsx_neighbor_stats_t::default();
+        check(unsafe { sys::gsx_model_neighbors(self.v, self.key.as_ptr(), desc, counts.as_mut_ptr(), hist.as_mut_ptr(), &mut out) })?;
+        Ok((counts, hist, out))
+    }
+    /// `gsx_model_select_neighbors`: the participants whose saturated count lies in `[count_lo, count_hi]` are the hit set;
+    /// `desc.selection_op` sets, adds or removes it, on the device.  Floaters with fewer than `k` neighbours: `max_count = k`,
+    /// `[0, k - 1]`.  Returns `(hit, selected)`.
+    pub fn select_neighbors(&mut self, desc: &sys::gsx_neighbor_select_desc) -> Result<(u64, u64), Error> {
+        let (mut hit, mut selected) = (0u64, 0u64);
+        check(unsafe { sys::gsx_model_select_neighbors(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected) })?;
+        Ok((hit, selected))
+    }
 }
 
 pub struct Preprocessor(*mut sys::gsx_viewer);

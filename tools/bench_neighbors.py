@@ -1,0 +1,212 @@
+#!/usr/bin/env python3
+"""What the neighbour counts cost on cfg4's model (10 M Gaussians), one process tree, one GPU: gsx_model_neighbors and
+gsx_model_select_neighbors whole, their passes alone, and the host route of today.
+
+  radii         three radii derived from the scene, so that the median saturated count is about 2, 16 and 128: a coarse
+                gsx_model_neighbors sweep (a bisection on the radius, the median read off the histogram); each printed with its median
+  calls/*       per radius, host to host followed by a device synchronise, median of --reps with every sample listed:
+                gsx_model_neighbors with counts and histogram (4 n bytes to the host), without the counts, with max_count 8, and
+                gsx_model_select_neighbors with the floaters recipe (max_count 8, counts 0..7)
+  bits/*        gsx_model_neighbors without the counts at the library's table size and two sizes either side of it (24 at most)
+  passes        tools/bench_neighbors_kernels (tools/bench_neighbors.hip: the kernel files compiled as source, a HIP event between
+                every two passes) on the scene's position elements: reset, reduce, cell, scan, scatter, query, select per radius, the
+                query with max_count 4095 and with 8, and the table sizes of bits/*
+  host/*        the host route at --host-n Gaussians (the first of the scene), in the same process on the same box:
+                gsx_model_download_pod + tests/neighbors_ref.py: grid + gsx_model_upload_selection, beside both device calls on a model
+                of those same Gaussians with the same radius (median count about 2)
+Every GPU child is wrapped in `timeout`.  Prints ONE JSON line; `bars` holds host_ms / call_ms per host row (the bar: each device
+call is faster than its host route in every row).
+
+    python tools/bench_neighbors.py [--config cfg4] [--reps 5] [--host-n 200000:5,1000000:1]
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from tests import neighbors_ref as N  # noqa: E402
+from wgpu_3dgs_viewer_app_amd import _lib, scene  # noqa: E402
+from wgpu_3dgs_viewer_app_amd.viewer import Cov3dKind, MultiModelViewer, ShKind  # noqa: E402
+
+KERNELS = os.path.join(ROOT, "tools", "bench_neighbors_kernels")
+TARGETS = (2, 16, 128)
+
+
+def build_native() -> None:
+    """the native half, on first use (a profiling tool must not fail the product's build)"""
+    csrc = os.path.join(ROOT, "wgpu_3dgs_viewer_app_amd", "csrc")
+    src = os.path.join(ROOT, "tools", "bench_neighbors.hip")
+    deps = [src] + [os.path.join(csrc, f) for f in ("kernels_neighbors.hip", "kernels_extract.hip", "neighbors_math.h", "extract_math.h", "pod_planes.h",
+                                                    "gsx_internal.h")]
+    if os.path.exists(KERNELS) and all(os.path.getmtime(KERNELS) >= os.path.getmtime(d) for d in deps):
+        return
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950", src, "-I" + csrc,
+                           "-I" + os.path.join(ROOT, "include"), "-o", KERNELS])
+
+
+def note(*what) -> None:
+    print("[bench_neighbors]", *what, file=sys.stderr, flush=True)
+
+
+def run_native(cmd, timeout_s: int) -> str:
+    r = subprocess.run(["timeout", "-k", "10", str(timeout_s), *cmd], capture_output=True, text=True)
+    if r.returncode != 0:
+        raise SystemExit(f"{cmd[0]} exited with {r.returncode}: {r.stderr.strip()}")
+    return r.stdout
+
+
+def timed(v, reps, call):
+    ms = []
+    for _ in range(reps):
+        v.poll()
+        t0 = time.perf_counter()
+        call()
+        v.poll()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return dict(ms=round(statistics.median(ms), 4), ms_all=[round(x, 4) for x in ms])
+
+
+def stats_only(v, key, radius, cap, bits=0):
+    """gsx_model_neighbors with the histogram and without the counts: nothing of n bytes crosses"""
+    desc = _lib.NeighborDesc(0, 0, float(radius), int(cap), int(bits), 0)
+    hist, out = np.zeros(cap + 1, np.uint64), _lib.NeighborStats()
+    _lib.check(v._L.gsx_model_neighbors(v._h, key, C.byref(desc), None, hist.ctypes.data, C.byref(out)))
+    return hist, out
+
+
+def median_of(hist):
+    return int(np.searchsorted(np.cumsum(hist), (int(hist.sum()) + 1) // 2))
+
+
+def find_radius(v, key, start, target, steps=12):
+    """the radius whose median saturated count is nearest `target`: a bisection in log(radius), cap 8 x target"""
+    cap = min(8 * target, N.MAX_COUNT)
+    lo, hi, r = None, None, float(start)
+    best = None
+    for _ in range(steps):
+        med = median_of(stats_only(v, key, r, cap)[0])
+        if best is None or abs(med - target) < abs(best[1] - target):
+            best = (r, med)
+        if med == target:
+            break
+        if med < target:
+            lo = r
+            r = r * 1.6 if hi is None else (r * hi) ** 0.5
+        else:
+            hi = r
+            r = r / 1.6 if lo is None else (r * lo) ** 0.5
+    return best
+
+
+def download_positions(v, key, n):
+    pos, color, cov = np.empty((n, 3), np.float32), np.empty(n, np.uint32), np.empty((n, 6), np.float32)
+    f32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    _lib.check(v._L.gsx_model_download_pod(v._h, key, f32p(pos), color.ctypes.data_as(C.POINTER(C.c_uint32)), None, f32p(cov)))
+    return pos, color
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="cfg4")
+    ap.add_argument("--reps", type=int, default=5, help="timed calls per row")
+    ap.add_argument("--host-n", default="200000:5,1000000:1", help="n:reps of the host route, comma separated")
+    ap.add_argument("--kernel-timeout", type=int, default=300, help="seconds the native half may take")
+    a = ap.parse_args()
+    build_native()
+    n, sh_deg, w, h, seed = scene.CONFIGS[a.config]
+    g = scene.synthetic_gaussians(n, seed, sh_deg)
+    out = dict(tool="bench_neighbors", config=a.config, n=n, reps=a.reps, radii={}, calls={}, bits={}, host={})
+    key = b"m"
+    with MultiModelViewer(sh=ShKind.Remove, cov3d=Cov3dKind.Half) as v:  # raises without a GPU: there is nothing to measure then
+        v.add_model("m", n)
+        m = v.models["m"]
+        m.gaussian_buffers.gaussians_buffer.update_range(0, g)
+        pos, color = download_positions(v, key, n)
+        fin = pos[np.isfinite(pos).all(axis=1)]
+        extent = np.percentile(fin, 95, axis=0) - np.percentile(fin, 5, axis=0)
+        start = float(np.cbrt(np.prod(extent.astype(np.float64)) / n))  # the spacing of a uniform fill of the middle of the scene
+        radii = {}
+        for target in TARGETS:
+            r, med = find_radius(v, key, start * (target / 4.0) ** (1.0 / 3.0), target)
+            radii[target] = r
+            out["radii"][str(target)] = dict(radius=r, median=med)
+            note(f"target median {target}: radius {r:.6g}, median saturated count {med}")
+        auto = N.auto_bits(n)
+        out["grid_bits_auto"] = auto
+        for target, r in radii.items():
+            row = {}
+            row["neighbors/counts+hist/4095"] = timed(v, a.reps, lambda: m.neighbors(r))
+            row["neighbors/hist/4095"] = timed(v, a.reps, lambda: stats_only(v, key, r, N.MAX_COUNT))
+            row["neighbors/hist/8"] = timed(v, a.reps, lambda: stats_only(v, key, r, 8))
+            row["select/floaters/8"] = timed(v, a.reps, lambda: m.select_neighbors(r, 0, 7))
+            out["calls"][str(target)] = row
+            note(target, row)
+            out["bits"][str(target)] = {str(b): timed(v, a.reps, lambda: stats_only(v, key, r, N.MAX_COUNT, b))
+                                        for b in range(auto - 2, auto + 3) if 1 <= b <= N.MAX_BITS}
+            note(target, "bits", out["bits"][str(target)])
+        # ---- the passes alone ----
+        with tempfile.TemporaryDirectory() as tmp:
+            path = os.path.join(tmp, "pc.bin")
+            np.concatenate([pos.view(np.uint32), color[:, None]], axis=1).astype(np.uint32).tofile(path)
+            jobs = []
+            for target, r in radii.items():
+                jobs += [f"{r:.9g}:{N.MAX_COUNT}:0", f"{r:.9g}:8:0"] + [f"{r:.9g}:{N.MAX_COUNT}:{b}" for b in range(auto - 2, auto + 3)
+                                                                      if 1 <= b <= N.MAX_BITS and b != auto]
+            out["passes"] = json.loads(run_native([KERNELS, path, str(n), str(a.reps), *jobs], a.kernel_timeout).strip().splitlines()[-1])
+        # ---- the host route, and the device calls at its n ----
+        for spec in a.host_n.split(","):
+            hn, hreps = (int(x) for x in spec.split(":"))
+            hk = f"h{hn}"
+            v.add_model(hk, hn)
+            hm = v.models[hk]
+            hm.gaussian_buffers.gaussians_buffer.update_range(0, g[:hn])
+            hr, hmed = find_radius(v, hk.encode(), start * (n / hn) ** (1.0 / 3.0) * 0.8, 2)
+            k = 3  # floaters: fewer than 3 neighbours
+
+            last = {}
+
+            def host_counts():
+                p, _ = download_positions(v, hk.encode(), hn)
+                last["counts"] = N.grid(p, N.participates(p), hr)
+                return p, last["counts"]
+
+            def host_select():
+                p, counts = host_counts()
+                pad = np.zeros(((hn + 31) // 32) * 32, bool)
+                pad[:hn] = N.participates(p) & (counts < k)
+                hm.gaussian_buffers.selection_buffer.upload(np.packbits(pad, bitorder="little").view(np.uint32))
+
+            row = dict(n=hn, radius=hr, median=hmed)
+            row["host/neighbors"] = timed(v, hreps, host_counts)
+            row["host/select"] = timed(v, hreps, host_select)
+            host_words = hm.gaussian_buffers.selection_buffer.download()
+            row["neighbors/counts+hist/4095"] = timed(v, a.reps, lambda: hm.neighbors(hr))
+            row["select/floaters"] = timed(v, a.reps, lambda: hm.select_neighbors(hr, 0, k - 1))
+            # the device's answer and the host's agree
+            row["counts_equal_host"] = bool(np.array_equal(hm.neighbors(hr).counts, last["counts"]))
+            row["selection_equals_host"] = bool(np.array_equal(hm.gaussian_buffers.selection_buffer.download(), host_words))
+            out["host"][str(hn)] = row
+            note("host", row)
+    ratios = {}
+    for hn, row in out["host"].items():
+        ratios[f"{hn}/neighbors"] = round(row["host/neighbors"]["ms"] / row["neighbors/counts+hist/4095"]["ms"], 1)
+        ratios[f"{hn}/select"] = round(row["host/select"]["ms"] / row["select/floaters"]["ms"], 1)
+    out["bars"] = {"call_vs_host": dict(ratio=ratios, smallest=min(ratios.values()), met=bool(min(ratios.values()) > 1.0),
+                                        missed=[k for k, x in ratios.items() if x <= 1.0])}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -52,6 +52,7 @@ EXPORTS = (
     "gsx_import_desc_default", "gsx_model_upload_ply_rows", "gsx_model_import_ply",
     "gsx_model_pod_kind", "gsx_convert_desc_default", "gsx_model_convert", "gsx_model_set_pod_kind",
     "gsx_model_property_values", "gsx_model_histogram", "gsx_model_select_range",
+    "gsx_neighbor_desc_default", "gsx_model_neighbors", "gsx_model_select_neighbors",
 )
 
 
@@ -143,6 +144,29 @@ class SelectDesc(C.Structure):
     (``bins`` > 0) the bins ``[bin_lo, bin_hi]`` of the histogram over that range."""
     _fields_ = [("property", C.c_uint32), ("flags", C.c_uint32), ("filter", C.c_uint32), ("selection_op", C.c_uint32), ("lo", C.c_float),
                 ("hi", C.c_float), ("bins", C.c_uint32), ("bin_lo", C.c_uint32), ("bin_hi", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+#: the most a neighbour count saturates at
+GSX_NEIGHBOR_MAX_COUNT = 4095
+
+
+class NeighborDesc(C.Structure):
+    """``gsx_neighbor_desc`` (24 bytes): the ``GSX_BOUNDS_*`` filter, flags (0), the radius in model space, the cap 1..4095 a count
+    saturates at, ``grid_bits`` (0: the library's hash table; 1..24 forces ``2**grid_bits`` buckets and changes no result)."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("radius", C.c_float), ("max_count", C.c_uint32), ("grid_bits", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class NeighborStats(C.Structure):
+    """``gsx_neighbor_stats_t`` (24 bytes)."""
+    _fields_ = [("count", C.c_uint64), ("n_nonfinite", C.c_uint64), ("grid_bits", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class NeighborSelectDesc(C.Structure):
+    """``gsx_neighbor_select_desc`` (40 bytes): the filter, flags (0), the ``gsx_selection_op``, the cap, the radius, the counts
+    ``[count_lo, count_hi]`` that are hit, ``grid_bits``."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("selection_op", C.c_uint32), ("max_count", C.c_uint32), ("radius", C.c_float),
+                ("count_lo", C.c_uint32), ("count_hi", C.c_uint32), ("grid_bits", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class ExtractDesc(C.Structure):
@@ -392,6 +416,9 @@ def load() -> C.CDLL:
         "gsx_model_property_values": ([vp, cp, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64], C.c_int32),
         "gsx_model_histogram": ([vp, cp, C.POINTER(HistogramDesc), C.POINTER(C.c_uint64), C.POINTER(Histogram)], C.c_int32),
         "gsx_model_select_range": ([vp, cp, C.POINTER(SelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_neighbor_desc_default": ([C.POINTER(NeighborDesc)], None),
+        "gsx_model_neighbors": ([vp, cp, C.POINTER(NeighborDesc), C.c_void_p, C.c_void_p, C.POINTER(NeighborStats)], C.c_int32),
+        "gsx_model_select_neighbors": ([vp, cp, C.POINTER(NeighborSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
         "gsx_model_merge": ([vp, C.POINTER(C.c_char_p), C.c_uint32, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)

@@ -908,6 +908,24 @@ struct ModelFilter {
     const float4* edit_a;
     uint32_t select_none, invert;
 };
+// Does Gaussian i (lane t of the workgroup, i < n or not) pass the filter?  (k_property; k_nb_reduce and k_nb_cell.)  Every lane of a
+// 32-lane half composes the same keep word from the same plane words (one request a word); the hidden word is the half's part of
+// the wave's ballot over the stored edit flags, which are read only where `edited` is set.  Must be called by all 64 lanes of the
+// wave.
+__device__ inline bool prop_keep(const ModelFilter& f, uint64_t n, uint64_t i, uint32_t t) {
+    const bool in = i < n;
+    const uint64_t w = i >> 5;
+    const uint32_t edited = (in && f.edited) ? f.edited[w] : 0u;
+    bool hidden = false;
+    if ((edited >> (t & 31u)) & 1u) hidden = extract_flag_hides(__float_as_uint(f.edit_a[i].x));
+    const unsigned long long hidden64 = __ballot(hidden);
+    if (!in) return false;
+    ExtractWords x;
+    x.mask = f.mask ? f.mask[w] : 0xFFFFFFFFu;
+    x.selection = f.selection ? f.selection[w] : (f.select_none ? 0u : 0xFFFFFFFFu);
+    x.hidden = (uint32_t)(hidden64 >> (t & 32u));
+    return (extract_keep_word(x, f.invert != 0, n, w) >> (t & 31u)) & 1u;
+}
 // Model bounds (kernels_bounds.hip; gsx_model_bounds).
 struct BoundsPartial {  // one per workgroup of k_bounds_reduce; 64 bytes
     float mn[3], mx[3];
@@ -1055,6 +1073,37 @@ struct PropertyJob {
 hipError_t launch_property_reset(hipStream_t s, uint32_t* result, uint32_t* hist, uint32_t bins);
 // cov_kind is read for the scale properties only; src is only read
 hipError_t launch_property(hipStream_t s, uint32_t mode, int cov_kind, uint64_t n, const ModelFilter& f, const ExtractPlanes& src, const PropertyJob& job);
+
+// Model neighbours (kernels_neighbors.hip; gsx_model_neighbors, gsx_model_select_neighbors): a hashed uniform grid built by a
+// counting sort, one launch_neighbors_* per pass, in this order on one stream; every workgroup of the passes in index order takes
+// kExtractGroup consecutive Gaussians and leaves one partial of kNbPartialWords words.  The result block (kNbResultWords words):
+//   [0] participants  [1] non-finite  [2..4] the grid origin (float bits: the participants' minimum)  [5] hit  [6] selected afterwards
+enum : uint32_t { kNbCount = 0, kNbNonfinite = 1, kNbOrigin = 2, kNbHit = 5, kNbSelected = 6, kNbResultWords = 32 };
+constexpr uint32_t kNbPartialWords = 8;    // reduce: count | non-finite | min x | min y | min z; select: hit | selected
+constexpr uint32_t kNbScanBlock = 1024;    // table words a workgroup of the scan takes
+struct NeighborJob {
+    float r2, inv_h;          // neighbors_math.h: nb_grid
+    uint32_t bits;            // the table has 2^bits buckets
+    uint32_t max_count;       // 1 .. 4095: a lane stops counting there
+    uint32_t count_lo, count_hi, op, selection_valid;  // select (selection_valid 0: the buffer stands for "none selected")
+    uint32_t* result;         // kNbResultWords words, zeroed
+    uint32_t* hist;           // max_count + 1 words, zeroed
+    uint32_t* partials;       // extract_groups(n) x kNbPartialWords words
+    uint32_t* participants;   // ceil(n / 32) words: bit set = passes the filter and has a finite position (written by the cell pass)
+    uint32_t* table;          // 2^bits words, zeroed: bucket sizes (cell pass), starts (scan), ends (scatter)
+    uint32_t* scan_sums;      // ceil(2^bits / kNbScanBlock) words, and as many bases
+    uint32_t* scan_bases;
+    uint64_t* scan_total;
+    uint32_t* counts;         // n words: the saturated counts by original index (0 for a Gaussian that does not participate)
+    uint4* records;           // n records in bucket order: x, y, z bits and the original index
+    uint32_t* selection;      // select: ceil(n / 32) words, read and written
+};
+hipError_t launch_neighbors_reduce(hipStream_t s, uint64_t n, const ModelFilter& f, const uint4* pc, const NeighborJob& job);   // result[0..4]
+hipError_t launch_neighbors_cell(hipStream_t s, uint64_t n, const ModelFilter& f, const uint4* pc, const NeighborJob& job);     // participants, table, counts = 0
+hipError_t launch_neighbors_scan(hipStream_t s, const NeighborJob& job);                                                        // table: sizes -> starts
+hipError_t launch_neighbors_scatter(hipStream_t s, uint64_t n, const uint4* pc, const NeighborJob& job);                        // records; table: starts -> ends
+hipError_t launch_neighbors_query(hipStream_t s, uint64_t n, const NeighborJob& job);                                           // counts, hist
+hipError_t launch_neighbors_select(hipStream_t s, uint64_t n, const NeighborJob& job);                                          // selection, result[5..6]
 
 // Model export (kernels_export.hip; gsx_model_export): the rows of the kept Gaussians of the source workgroups [group0, group0 +
 // n_groups), in `format` (GSX_EXPORT_*), into `out` starting at the chunk's first kept Gaussian: row_base = bases[group0].  `out`

@@ -36,24 +36,6 @@ __device__ inline uint4 prop_ld_stream(const uint4* p) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-// Does Gaussian i (lane t of the workgroup, i < n or not) pass the filter?  Every lane of a 32-lane half composes the same keep
-// word from the same plane words (one request a word); the hidden word is the half's part of the wave's ballot over the stored
-// edit flags, which are read only where `edited` is set.  Must be called by all 64 lanes of the wave.
-__device__ inline bool prop_keep(const ModelFilter& f, uint64_t n, uint64_t i, uint32_t t) {
-    const bool in = i < n;
-    const uint64_t w = i >> 5;
-    const uint32_t edited = (in && f.edited) ? f.edited[w] : 0u;
-    bool hidden = false;
-    if ((edited >> (t & 31u)) & 1u) hidden = extract_flag_hides(__float_as_uint(f.edit_a[i].x));
-    const unsigned long long hidden64 = __ballot(hidden);
-    if (!in) return false;
-    ExtractWords x;
-    x.mask = f.mask ? f.mask[w] : 0xFFFFFFFFu;
-    x.selection = f.selection ? f.selection[w] : (f.select_none ? 0u : 0xFFFFFFFFu);
-    x.hidden = (uint32_t)(hidden64 >> (t & 32u));
-    return (extract_keep_word(x, f.invert != 0, n, w) >> (t & 31u)) & 1u;
-}
-
 // The planes a property reads, of ExtractPlanes' thirteen: the kernel's arguments live in scalar registers for the whole loop.
 struct PropPlanes {
     const uint4* pc;

@@ -314,6 +314,20 @@ class PropertyHistogram:
     max: np.float32
 
 
+@dataclasses.dataclass
+class ModelNeighbors:
+    """What ``MultiModelViewerModel.neighbors`` returns.  ``counts`` (uint32, one per Gaussian): neighbours within the radius,
+    saturated at the cap, 0 for a Gaussian that does not participate; ``hist`` (uint64, cap + 1): participants per count; ``count``:
+    participants (pass the filter, finite position); ``n_nonfinite``: passed the filter with a NaN or infinite coordinate;
+    ``grid_bits``: the hash table used."""
+
+    counts: np.ndarray
+    hist: np.ndarray
+    count: int
+    n_nonfinite: int
+    grid_bits: int
+
+
 class MultiModelViewerModel:
     """``gs::MultiModelViewerModel {gaussian_buffers, bind_groups}`` (src/tab/scene.rs:2133-2139)."""
 
@@ -412,6 +426,33 @@ class MultiModelViewerModel:
                                int(bin_lo), int(bin_hi), 0)
         hit, selected = C.c_uint64(), C.c_uint64()
         _lib.check(self._v._L.gsx_model_select_range(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected)))
+        return int(hit.value), int(selected.value)
+
+    def neighbors(self, radius: float, max_count: int = _lib.GSX_NEIGHBOR_MAX_COUNT, filter: int = 0,  # noqa: A002
+                  grid_bits: int = 0) -> ModelNeighbors:
+        """``gsx_model_neighbors``: for every Gaussian, how many others lie within ``radius`` of it in model space (stored positions,
+        ``d2 <= r2`` in float32), saturated at ``max_count`` (1..4095), among the Gaussians that pass ``filter``
+        (``_lib.GSX_BOUNDS_*``) and have a finite position; computed on the device with a hashed grid.  ``hist.sum() == count``.
+        ``grid_bits`` forces the table size and changes no result."""
+        n = self.gaussian_buffers.gaussians_buffer.len()
+        desc = _lib.NeighborDesc(int(filter), 0, float(radius), int(max_count), int(grid_bits), 0)
+        counts = np.zeros(n, np.uint32)
+        hist = np.zeros(min(max(int(max_count), 0), _lib.GSX_NEIGHBOR_MAX_COUNT) + 1, np.uint64)
+        out = _lib.NeighborStats()
+        _lib.check(self._v._L.gsx_model_neighbors(self._v._h, self._key.encode(), C.byref(desc), counts.ctypes.data, hist.ctypes.data,
+                                                  C.byref(out)))
+        return ModelNeighbors(counts, hist, int(out.count), int(out.n_nonfinite), int(out.grid_bits))
+
+    def select_neighbors(self, radius: float, count_lo: int, count_hi: int, max_count: int | None = None, op: int = 0,
+                         filter: int = 0, grid_bits: int = 0) -> tuple[int, int]:  # noqa: A002
+        """``gsx_model_select_neighbors``: the participants whose neighbour count, saturated at ``max_count`` (default: ``count_hi``
+        + 1, the cheapest cap that still tells the range apart), lies in ``[count_lo, count_hi]`` are the hit set; ``op``
+        (``_lib.GSX_SELECTION_*``) makes it the selection, adds it or removes it, on the device.  Floaters with fewer than ``k``
+        neighbours: ``select_neighbors(r, 0, k - 1)``, then ``extract(dst, SELECTED, invert=True)``.  Returns ``(hit, selected)``."""
+        cap = min(int(count_hi) + 1, _lib.GSX_NEIGHBOR_MAX_COUNT) if max_count is None else int(max_count)
+        desc = _lib.NeighborSelectDesc(int(filter), 0, int(op), cap, float(radius), int(count_lo), int(count_hi), int(grid_bits))
+        hit, selected = C.c_uint64(), C.c_uint64()
+        _lib.check(self._v._L.gsx_model_select_neighbors(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected)))
         return int(hit.value), int(selected.value)
 
     def _export_desc(self, filter, invert, bake_edits, fmt, staging_bytes):  # noqa: A002
