@@ -656,6 +656,47 @@ void gsx_neighbor_desc_default(gsx_neighbor_desc* d); /* no filter, radius 1, ma
 gsx_status gsx_model_neighbors(gsx_viewer* v, const char* key, const gsx_neighbor_desc* desc, uint32_t* out_counts, uint64_t* out_hist, gsx_neighbor_stats_t* out);
 gsx_status gsx_model_select_neighbors(gsx_viewer* v, const char* key, const gsx_neighbor_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected);
 
+/* ---- model clusters: the connected pieces of a model under "within a radius of one another", and a selection by them, on the
+ *      device (spec/RENDER_SPEC.md §19 [BUILD-SPEC]).  Keep the object, drop the debris: gsx_model_select_clusters in mode
+ *      GSX_CLUSTER_LARGEST, then gsx_model_extract with GSX_BOUNDS_SELECTED; or mode GSX_CLUSTER_BY_SIZE with (1, k - 1), then
+ *      extract with GSX_EXTRACT_INVERT.  Select linked: brush a few Gaussians, then mode GSX_CLUSTER_SEEDED with GSX_SELECTION_ADD.
+ *      Participants, distance and radius are gsx_model_neighbors' word for word: a Gaussian participates if it passes desc->filter
+ *      and its three stored coordinates are finite; d2 in float32, every operation rounded; r2 = radius * radius; i ~ j iff i != j,
+ *      both participate and d2 <= r2.  The model transform, the edits and gsx_model_show_unedited change nothing.
+ *      A cluster is an equivalence class of the transitive closure of ~ over the participants; a participant without a neighbour is
+ *      a cluster of size 1.  out_labels[i] (nullable; the model's length) is the smallest Gaussian index of i's cluster,
+ *      GSX_CLUSTER_NONE for a Gaussian that does not participate; out_sizes[i] (nullable) the size of i's cluster, 0 for one that
+ *      does not participate.  stats: count participants, n_nonfinite, n_clusters, largest_size, largest_label the label of the
+ *      largest cluster (the smallest such label on a tie; GSX_CLUSTER_NONE without participants), grid_bits the table used.  The same
+ *      bits on every call; nothing a frame reads is written.
+ *      gsx_model_select_clusters, the hit set by mode: GSX_CLUSTER_BY_SIZE participates and size_lo <= the size of its cluster <=
+ *      size_hi (1 <= size_lo <= size_hi); GSX_CLUSTER_LARGEST its label is largest_label; GSX_CLUSTER_SEEDED participates and its
+ *      cluster holds a seed, a participant whose selection bit was set before the call (a model without a selection has none).  In
+ *      the last two modes size_lo and size_hi are 0.  *out_hit is what gsx_model_clusters with the same filter and radius implies.
+ *      selection_op, a model without a selection, the tail bits, GSX_BOUNDS_SELECTED reading the selection as it was before the
+ *      call, *out_hit / *out_selected (nullable), ordering and frame consistency: gsx_model_select_range's.  grid_bits: as in
+ *      gsx_model_neighbors.
+ *      Errors: a null viewer, key, desc or stats pointer, unknown filter bits, op or mode, flags != 0 (none are defined), a radius
+ *      gsx_model_neighbors refuses, grid_bits > 24, sizes that the mode does not allow, a reserved word != 0: GSX_ERR_INVALID_ARG;
+ *      unknown key: GSX_ERR_NOT_FOUND; a viewer with a communicator, or a sharded model: GSX_ERR_UNSUPPORTED; an allocation failure:
+ *      GSX_ERR_OOM, the model and its selection as they were.  A model of 0 Gaussians, or 0 participants: GSX_OK with zeros (a
+ *      select with Set then clears the selection). ---- */
+#define GSX_CLUSTER_NONE 0xFFFFFFFFu
+#define GSX_CLUSTER_BY_SIZE 0u
+#define GSX_CLUSTER_LARGEST 1u
+#define GSX_CLUSTER_SEEDED 2u
+typedef struct gsx_cluster_desc { uint32_t filter; uint32_t flags; float radius; uint32_t grid_bits; uint32_t reserved[2]; } gsx_cluster_desc; /* 24 B */
+typedef struct gsx_cluster_stats_t {
+    uint64_t count; uint64_t n_nonfinite; uint64_t n_clusters; uint64_t largest_size; uint32_t largest_label; uint32_t grid_bits;
+} gsx_cluster_stats_t; /* 40 B */
+typedef struct gsx_cluster_select_desc {
+    uint32_t filter; uint32_t flags; uint32_t selection_op; uint32_t mode; /* GSX_BOUNDS_*, 0, gsx_selection_op, GSX_CLUSTER_* */
+    float radius; uint32_t size_lo; uint32_t size_hi; uint32_t grid_bits; uint32_t reserved[2];
+} gsx_cluster_select_desc; /* 40 B */
+void gsx_cluster_desc_default(gsx_cluster_desc* d); /* no filter, radius 1, the library's table */
+gsx_status gsx_model_clusters(gsx_viewer* v, const char* key, const gsx_cluster_desc* desc, uint32_t* out_labels, uint32_t* out_sizes, gsx_cluster_stats_t* out);
+gsx_status gsx_model_select_clusters(gsx_viewer* v, const char* key, const gsx_cluster_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

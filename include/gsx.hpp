@@ -249,6 +249,27 @@ struct MultiModelViewerModel {
         check(gsx_model_select_neighbors(v_, key_.c_str(), &desc, &hit, &selected));
         return {hit, selected};
     }
+    // gsx_model_clusters: the connected pieces of the model under "within desc.radius of one another" (d2 <= r2 in float32, model
+    // space), among the Gaussians that pass desc.filter and have a finite position; computed on the device by a union-find over a
+    // hashed grid.  labels receives the smallest Gaussian index of each Gaussian's cluster (GSX_CLUSTER_NONE for one that does not
+    // participate), sizes the size of its cluster.
+    gsx_cluster_stats_t clusters(const gsx_cluster_desc& desc, std::vector<uint32_t>& labels, std::vector<uint32_t>& sizes) const {
+        uint64_t n = 0;
+        check(gsx_model_len(v_, key_.c_str(), &n));
+        labels.assign((size_t)n, GSX_CLUSTER_NONE);
+        sizes.assign((size_t)n, 0u);
+        gsx_cluster_stats_t out{};
+        check(gsx_model_clusters(v_, key_.c_str(), &desc, labels.data(), sizes.data(), &out));
+        return out;
+    }
+    // gsx_model_select_clusters: the hit set is, by desc.mode, the clusters with a size in [size_lo, size_hi], the largest cluster, or
+    // the clusters that hold a selected Gaussian; desc.selection_op sets, adds or removes it, on the device.  Returns {hit, selected
+    // afterwards}.
+    std::pair<uint64_t, uint64_t> select_clusters(const gsx_cluster_select_desc& desc) {
+        uint64_t hit = 0, selected = 0;
+        check(gsx_model_select_clusters(v_, key_.c_str(), &desc, &hit, &selected));
+        return {hit, selected};
+    }
 };
 
 class MultiModelViewer {

@@ -35,6 +35,10 @@ pub const GSX_PROP_WORLD: u32 = 1;
 pub const GSX_HIST_AUTO_RANGE: u32 = 4;
 pub const GSX_HIST_MAX_BINS: u32 = 4096;
 pub const GSX_NEIGHBOR_MAX_COUNT: u32 = 4095;
+pub const GSX_CLUSTER_NONE: u32 = 0xFFFF_FFFF;
+pub const GSX_CLUSTER_BY_SIZE: u32 = 0;
+pub const GSX_CLUSTER_LARGEST: u32 = 1;
+pub const GSX_CLUSTER_SEEDED: u32 = 2;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -169,6 +173,24 @@ pub struct gsx_neighbor_select_desc {
     pub filter: u32, pub flags: u32, pub selection_op: u32, pub max_count: u32, pub radius: f32,
     pub count_lo: u32, pub count_hi: u32, pub grid_bits: u32, pub reserved: [u32; 2],
 }
+/// gsx_model_clusters, 24 bytes: the GSX_BOUNDS_* filter, flags (0), the radius (model space), grid_bits (0: the library's hash table)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_cluster_desc { pub filter: u32, pub flags: u32, pub radius: f32, pub grid_bits: u32, pub reserved: [u32; 2] }
+/// the result of gsx_model_clusters, 40 bytes: participants, those with a NaN / inf coordinate, the clusters, the largest one's size and
+/// label (the smallest such label on a tie; GSX_CLUSTER_NONE without participants), the table used
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_cluster_stats_t {
+    pub count: u64, pub n_nonfinite: u64, pub n_clusters: u64, pub largest_size: u64, pub largest_label: u32, pub grid_bits: u32,
+}
+/// gsx_model_select_clusters, 40 bytes: mode GSX_CLUSTER_BY_SIZE (size_lo <= the cluster's size <= size_hi), _LARGEST or _SEEDED (both 0)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_cluster_select_desc {
+    pub filter: u32, pub flags: u32, pub selection_op: u32, pub mode: u32, pub radius: f32,
+    pub size_lo: u32, pub size_hi: u32, pub grid_bits: u32, pub reserved: [u32; 2],
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }
@@ -302,6 +324,9 @@ extern "C" {
     pub fn gsx_neighbor_desc_default(d: *mut gsx_neighbor_desc);
     pub fn gsx_model_neighbors(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_neighbor_desc, out_counts: *mut u32, out_hist: *mut u64, out: *mut gsx_neighbor_stats_t) -> gsx_status;
     pub fn gsx_model_select_neighbors(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_neighbor_select_desc, out_hit: *mut u64, out_selected: *mut u64) -> gsx_status;
+    pub fn gsx_cluster_desc_default(d: *mut gsx_cluster_desc);
+    pub fn gsx_model_clusters(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_cluster_desc, out_labels: *mut u32, out_sizes: *mut u32, out: *mut gsx_cluster_stats_t) -> gsx_status;
+    pub fn gsx_model_select_clusters(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_cluster_select_desc, out_hit: *mut u64, out_selected: *mut u64) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

@@ -226,6 +226,27 @@ impl MultiModelViewerModel {
         check(unsafe { sys::gsx_model_select_neighbors(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected) })?;
         Ok((hit, selected))
     }
+    /// `gsx_model_clusters`: the connected pieces of the model under "within `desc.radius` of one another" (`d2 <= r2` in `f32`, model
+    /// space), among the Gaussians that pass `desc.filter` and have a finite position; computed on the device by a union-find over a
+    /// hashed grid.  Returns `(labels, sizes, stats)`: `labels[i]` is the smallest Gaussian index of `i`'s cluster
+    /// (`GSX_CLUSTER_NONE` for one that does not participate), `sizes[i]` the size of its cluster.
+    pub fn clusters(&self, desc: &sys::gsx_cluster_desc) -> Result<(Vec<u32>, Vec<u32>, sys::gsx_cluster_stats_t), Error> {
+        let mut n = 0u64;
+        check(unsafe { sys::gsx_model_len(self.v, self.key.as_ptr(), &mut n) })?;
+        let mut labels = vec![sys::GSX_CLUSTER_NONE; n as usize];
+        let mut sizes = vec![0u32; n as usize];
+        let mut out = sys::gsx_cluster_stats_t::default();
+        check(unsafe { sys::gsx_model_clusters(self.v, self.key.as_ptr(), desc, labels.as_mut_ptr(), sizes.as_mut_ptr(), &mut out) })?;
+        Ok((labels, sizes, out))
+    }
+    /// `gsx_model_select_clusters`: the hit set is, by `desc.mode`, the clusters with a size in `[size_lo, size_hi]`, the largest
+    /// cluster, or the clusters that hold a selected Gaussian; `desc.selection_op` sets, adds or removes it, on the device.  Returns
+    /// `(hit, selected)`.
+    pub fn select_clusters(&mut self, desc: &sys::gsx_cluster_select_desc) -> Result<(u64, u64), Error> {
+        let (mut hit, mut selected) = (0u64, 0u64);
+        check(unsafe { sys::gsx_model_select_clusters(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected) })?;
+        Ok((hit, selected))
+    }
 }
 
 pub struct Preprocessor(*mut sys::gsx_viewer);

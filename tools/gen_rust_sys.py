@@ -84,6 +84,10 @@ pub const GSX_PROP_WORLD: u32 = 1;
 pub const GSX_HIST_AUTO_RANGE: u32 = 4;
 pub const GSX_HIST_MAX_BINS: u32 = 4096;
 pub const GSX_NEIGHBOR_MAX_COUNT: u32 = 4095;
+pub const GSX_CLUSTER_NONE: u32 = 0xFFFF_FFFF;
+pub const GSX_CLUSTER_BY_SIZE: u32 = 0;
+pub const GSX_CLUSTER_LARGEST: u32 = 1;
+pub const GSX_CLUSTER_SEEDED: u32 = 2;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -217,6 +221,24 @@ pub struct gsx_neighbor_stats_t { pub count: u64, pub n_nonfinite: u64, pub grid
 pub struct gsx_neighbor_select_desc {
     pub filter: u32, pub flags: u32, pub selection_op: u32, pub max_count: u32, pub radius: f32,
     pub count_lo: u32, pub count_hi: u32, pub grid_bits: u32, pub reserved: [u32; 2],
+}
+/// gsx_model_clusters, 24 bytes: the GSX_BOUNDS_* filter, flags (0), the radius (model space), grid_bits (0: the library's hash table)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_cluster_desc { pub filter: u32, pub flags: u32, pub radius: f32, pub grid_bits: u32, pub reserved: [u32; 2] }
+/// the result of gsx_model_clusters, 40 bytes: participants, those with a NaN / inf coordinate, the clusters, the largest one's size and
+/// label (the smallest such label on a tie; GSX_CLUSTER_NONE without participants), the table used
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_cluster_stats_t {
+    pub count: u64, pub n_nonfinite: u64, pub n_clusters: u64, pub largest_size: u64, pub largest_label: u32, pub grid_bits: u32,
+}
+/// gsx_model_select_clusters, 40 bytes: mode GSX_CLUSTER_BY_SIZE (size_lo <= the cluster's size <= size_hi), _LARGEST or _SEEDED (both 0)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_cluster_select_desc {
+    pub filter: u32, pub flags: u32, pub selection_op: u32, pub mode: u32, pub radius: f32,
+    pub size_lo: u32, pub size_hi: u32, pub grid_bits: u32, pub reserved: [u32; 2],
 }
 #[repr(C)]
 #[derive(Clone, Copy)]

@@ -53,6 +53,7 @@ EXPORTS = (
     "gsx_model_pod_kind", "gsx_convert_desc_default", "gsx_model_convert", "gsx_model_set_pod_kind",
     "gsx_model_property_values", "gsx_model_histogram", "gsx_model_select_range",
     "gsx_neighbor_desc_default", "gsx_model_neighbors", "gsx_model_select_neighbors",
+    "gsx_cluster_desc_default", "gsx_model_clusters", "gsx_model_select_clusters",
 )
 
 
@@ -167,6 +168,31 @@ class NeighborSelectDesc(C.Structure):
     ``[count_lo, count_hi]`` that are hit, ``grid_bits``."""
     _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("selection_op", C.c_uint32), ("max_count", C.c_uint32), ("radius", C.c_float),
                 ("count_lo", C.c_uint32), ("count_hi", C.c_uint32), ("grid_bits", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+#: the label of a Gaussian that does not participate
+GSX_CLUSTER_NONE = 0xFFFFFFFF
+#: ``gsx_cluster_select_desc.mode``
+GSX_CLUSTER_BY_SIZE, GSX_CLUSTER_LARGEST, GSX_CLUSTER_SEEDED = 0, 1, 2
+
+
+class ClusterDesc(C.Structure):
+    """``gsx_cluster_desc`` (24 bytes): the ``GSX_BOUNDS_*`` filter, flags (0), the radius in model space, ``grid_bits`` (0: the
+    library's hash table; 1..24 forces ``2**grid_bits`` buckets and changes no result)."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("radius", C.c_float), ("grid_bits", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class ClusterStats(C.Structure):
+    """``gsx_cluster_stats_t`` (40 bytes)."""
+    _fields_ = [("count", C.c_uint64), ("n_nonfinite", C.c_uint64), ("n_clusters", C.c_uint64), ("largest_size", C.c_uint64),
+                ("largest_label", C.c_uint32), ("grid_bits", C.c_uint32)]
+
+
+class ClusterSelectDesc(C.Structure):
+    """``gsx_cluster_select_desc`` (40 bytes): the filter, flags (0), the ``gsx_selection_op``, the ``GSX_CLUSTER_*`` mode, the radius,
+    the cluster sizes ``[size_lo, size_hi]`` that are hit (mode BY_SIZE; 0, 0 otherwise), ``grid_bits``."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("selection_op", C.c_uint32), ("mode", C.c_uint32), ("radius", C.c_float),
+                ("size_lo", C.c_uint32), ("size_hi", C.c_uint32), ("grid_bits", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class ExtractDesc(C.Structure):
@@ -419,6 +445,9 @@ def load() -> C.CDLL:
         "gsx_neighbor_desc_default": ([C.POINTER(NeighborDesc)], None),
         "gsx_model_neighbors": ([vp, cp, C.POINTER(NeighborDesc), C.c_void_p, C.c_void_p, C.POINTER(NeighborStats)], C.c_int32),
         "gsx_model_select_neighbors": ([vp, cp, C.POINTER(NeighborSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_cluster_desc_default": ([C.POINTER(ClusterDesc)], None),
+        "gsx_model_clusters": ([vp, cp, C.POINTER(ClusterDesc), C.c_void_p, C.c_void_p, C.POINTER(ClusterStats)], C.c_int32),
+        "gsx_model_select_clusters": ([vp, cp, C.POINTER(ClusterSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
         "gsx_model_merge": ([vp, C.POINTER(C.c_char_p), C.c_uint32, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)

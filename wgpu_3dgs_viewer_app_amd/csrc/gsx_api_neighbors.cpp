@@ -1,9 +1,9 @@
 // gsx_api_neighbors.cpp — C ABI of the neighbour counts (spec/RENDER_SPEC.md section 18; kernels_neighbors.hip):
 // gsx_model_neighbors and gsx_model_select_neighbors.  The filter is model_filter's, the workspace the model operations'
-// (v->extract_ws): [result block, 128 B | 4096 histogram words | the scan's total | the workgroups' partials | the participant bits |
-// the bucket table | the scan's block sums and bases | the counts, 4 B a Gaussian | the records, 16 B a Gaussian].
+// (v->extract_ws), laid out by neighbors_host.h, which also holds what the clusters (gsx_api_clusters.cpp) share with these calls.
 #include "gsx_state.h"
 #include "neighbors_math.h"
+#include "neighbors_host.h"
 
 using namespace gsx;
 
@@ -11,56 +11,6 @@ namespace {
 
 static_assert(sizeof(gsx_neighbor_desc) == 24 && sizeof(gsx_neighbor_stats_t) == 24 && sizeof(gsx_neighbor_select_desc) == 40, "spec section 18's layouts");
 static_assert(GSX_NEIGHBOR_MAX_COUNT == kNbMaxCount, "neighbors_math.h restates the cap");
-
-constexpr size_t kWsHist = 4 * kNbResultWords;                 // 128
-constexpr size_t kWsTotal = kWsHist + 4 * (kNbMaxCount + 1u);  // 16 512
-constexpr size_t kWsPartials = kWsTotal + 128;
-static_assert(kWsHist == 128 && kWsPartials % 128 == 0, "the workspace regions are whole 128-byte lines");
-
-// The workspace of a model of n Gaussians under a table of 2^bits buckets; returns its bytes.
-size_t neighbor_ws(char* ws, uint64_t n, uint32_t bits, NeighborJob* job) {
-    const size_t words = size_t(1) << bits, blocks = (words + kNbScanBlock - 1u) / kNbScanBlock;
-    size_t at = kWsPartials;
-    const auto take = [&](size_t bytes) {  // the next region: whole 128-byte lines
-        const size_t here = at;
-        at += extract_pad128(bytes);
-        return reinterpret_cast<uintptr_t>(ws) + here;
-    };
-    const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
-    job->result = reinterpret_cast<uint32_t*>(base);
-    job->hist = reinterpret_cast<uint32_t*>(base + kWsHist);
-    job->scan_total = reinterpret_cast<uint64_t*>(base + kWsTotal);
-    job->partials = reinterpret_cast<uint32_t*>(take(4 * kNbPartialWords * (size_t)extract_groups(n)));
-    job->participants = reinterpret_cast<uint32_t*>(take(4 * (size_t)((n + 31u) / 32u)));
-    job->table = reinterpret_cast<uint32_t*>(take(4 * words));
-    job->scan_sums = reinterpret_cast<uint32_t*>(take(4 * blocks));
-    job->scan_bases = reinterpret_cast<uint32_t*>(take(4 * blocks));
-    job->counts = reinterpret_cast<uint32_t*>(take(4 * (size_t)n));
-    job->records = reinterpret_cast<uint4*>(take(16 * (size_t)n));
-    return at;
-}
-
-// what both calls check about (filter, flags, radius, max_count, grid_bits)
-gsx_status check_desc(const char* fn, uint32_t filter, uint32_t flags, float radius, uint32_t max_count, uint32_t grid_bits) {
-    if (filter & ~kModelFilterBits) return fail(GSX_ERR_INVALID_ARG, "%s: unknown filter bits 0x%x", fn, filter);
-    if (flags) return fail(GSX_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x (none are defined)", fn, flags);
-    if (!nb_radius_ok(radius)) return fail(GSX_ERR_INVALID_ARG, "%s: the radius %g is not finite and above 0, or its float32 square is 0 or inf", fn, (double)radius);
-    if (max_count < 1u || max_count > kNbMaxCount) return fail(GSX_ERR_INVALID_ARG, "%s: max_count %u is not in 1 .. %u", fn, max_count, kNbMaxCount);
-    if (grid_bits > kNbMaxBits) return fail(GSX_ERR_INVALID_ARG, "%s: grid_bits %u is above %u", fn, grid_bits, kNbMaxBits);
-    return GSX_OK;
-}
-
-// bind, find, refuse what gsx_model_extract refuses
-gsx_status neighbor_model(gsx_viewer* v, const char* fn, const char* key, Model** out) {
-    gsx_status st = viewer_bind(v);  // behind the frames in flight on the lanes
-    if (st) return st;
-    Model* m = find_model(v, key);
-    if (!m) return fail(GSX_ERR_NOT_FOUND, "%s: no model '%s'", fn, key);
-    if (has_comm(v)) return fail(GSX_ERR_UNSUPPORTED, "%s: the viewer has a communicator (call it before gsx_viewer_comm_init, or on one GPU)", fn);
-    if (model_is_shard(m)) return fail(GSX_ERR_UNSUPPORTED, "%s: model '%s' is a shard of a multi-GPU frame", fn, key);
-    *out = m;
-    return GSX_OK;
-}
 
 // The workspace (grown if need be: the only step that can fail for memory) and the job of a call; n > 0.
 gsx_status neighbor_job(gsx_viewer* v, const Model* m, float radius, uint32_t max_count, uint32_t grid_bits, NeighborJob* job) {
@@ -79,13 +29,8 @@ gsx_status neighbor_job(gsx_viewer* v, const Model* m, float radius, uint32_t ma
 
 // Every pass up to the query, enqueued: the counts and the histogram are in the workspace when the stream reaches its end.
 gsx_status enqueue_counts(gsx_viewer* v, const Model* m, const ModelFilter& f, const NeighborJob& job) {
-    const uint4* pc = extract_planes(m, false).pc;
-    HIPCHK(gsx::op::MemsetAsync(job.result, 0, kWsTotal + 8, v->stream));  // the result block, the bins, the scan's total
-    HIPCHK(gsx::op::MemsetAsync(job.table, 0, 4 * (size_t(1) << job.bits), v->stream));
-    HIPCHK(launch_neighbors_reduce(v->stream, m->n, f, pc, job));
-    HIPCHK(launch_neighbors_cell(v->stream, m->n, f, pc, job));
-    HIPCHK(launch_neighbors_scan(v->stream, job));
-    HIPCHK(launch_neighbors_scatter(v->stream, m->n, pc, job));
+    const gsx_status st = enqueue_grid(v, m, f, job);
+    if (st) return st;
     HIPCHK(launch_neighbors_query(v->stream, m->n, job));
     return GSX_OK;
 }

@@ -1105,6 +1105,27 @@ hipError_t launch_neighbors_scatter(hipStream_t s, uint64_t n, const uint4* pc, 
 hipError_t launch_neighbors_query(hipStream_t s, uint64_t n, const NeighborJob& job);                                           // counts, hist
 hipError_t launch_neighbors_select(hipStream_t s, uint64_t n, const NeighborJob& job);                                          // selection, result[5..6]
 
+// Model clusters (kernels_clusters.hip; gsx_model_clusters, gsx_model_select_clusters): the connected components of "within the
+// radius" over the grid above (launch_neighbors_reduce / _cell / _scan / _scatter on `nb`), by a lock-free union-find (clusters_math.h)
+// whose parent[] is nb.counts.  One launch_clusters_* per pass, in this order on one stream, after the grid's.  The result block is
+// nb.result; the clusters' words of it:
+//   [5] hit  [6] selected afterwards  [8] clusters  [10..11] the largest cluster's key, (size << 32) | ~label, a 64-bit word
+enum : uint32_t { kClClusters = 8, kClKey = 10 };
+enum : uint32_t { kClBySize = 0, kClLargest = 1, kClSeeded = 2 };  // GSX_CLUSTER_BY_SIZE / _LARGEST / _SEEDED
+struct ClusterJob {
+    NeighborJob nb;           // the grid; nb.counts is parent[]; nb.partials holds one partial a workgroup (kNbPartialWords words)
+    uint32_t* label;          // n words: the cluster's smallest index, or 0xFFFFFFFF
+    uint32_t* size;           // n words, zeroed: size[l] = the Gaussians with label l
+    uint32_t* sizes;          // n words: size[label[i]], 0 for a Gaussian that does not participate
+    uint32_t* seeded;         // n words, zeroed (seeds only): seeded[l] = 1 if a Gaussian with label l is a seed
+    uint32_t seeds;           // 1: k_cl_label marks the labels of the selected participants (nb.selection, nb.selection_valid)
+    uint32_t mode, size_lo, size_hi;  // select; the op is nb.op
+};
+hipError_t launch_clusters_hook(hipStream_t s, uint64_t n, const ClusterJob& job);    // parent[] = i, then every pair united
+hipError_t launch_clusters_label(hipStream_t s, uint64_t n, const ClusterJob& job);   // label, size, seeded
+hipError_t launch_clusters_stats(hipStream_t s, uint64_t n, const ClusterJob& job);   // sizes, result[8], result[10..11]
+hipError_t launch_clusters_select(hipStream_t s, uint64_t n, const ClusterJob& job);  // selection, result[5..6]
+
 // Model export (kernels_export.hip; gsx_model_export): the rows of the kept Gaussians of the source workgroups [group0, group0 +
 // n_groups), in `format` (GSX_EXPORT_*), into `out` starting at the chunk's first kept Gaussian: row_base = bases[group0].  `out`
 // holds at least bases[group0 + n_groups] - row_base rows (the total in place of bases[] past the last group).  src is only read;

@@ -1,0 +1,75 @@
+// neighbors_host.h — the host side that the neighbour counts (gsx_api_neighbors.cpp, spec section 18) and the clusters
+// (gsx_api_clusters.cpp, section 19) share: the grid's workspace inside the model operations' (v->extract_ws), what both check about
+// a desc, how both bind and find their model, and the four passes that build the grid.  The workspace:
+// [result block, 128 B | 4096 histogram words | the scan's total | the workgroups' partials | the participant bits | the bucket table |
+//  the scan's block sums and bases | the counts, 4 B a Gaussian | the records, 16 B a Gaussian]; a caller's own regions follow.
+#pragma once
+#include "gsx_state.h"
+#include "neighbors_math.h"
+
+namespace gsx {
+
+constexpr size_t kNbWsHist = 4 * kNbResultWords;                   // 128
+constexpr size_t kNbWsTotal = kNbWsHist + 4 * (kNbMaxCount + 1u);  // 16 512
+constexpr size_t kNbWsPartials = kNbWsTotal + 128;
+static_assert(kNbWsHist == 128 && kNbWsPartials % 128 == 0, "the workspace regions are whole 128-byte lines");
+
+// The workspace of a model of n Gaussians under a table of 2^bits buckets; returns its bytes.
+inline size_t neighbor_ws(char* ws, uint64_t n, uint32_t bits, NeighborJob* job) {
+    const size_t words = size_t(1) << bits, blocks = (words + kNbScanBlock - 1u) / kNbScanBlock;
+    size_t at = kNbWsPartials;
+    const auto take = [&](size_t bytes) {  // the next region: whole 128-byte lines
+        const size_t here = at;
+        at += extract_pad128(bytes);
+        return reinterpret_cast<uintptr_t>(ws) + here;
+    };
+    const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
+    job->result = reinterpret_cast<uint32_t*>(base);
+    job->hist = reinterpret_cast<uint32_t*>(base + kNbWsHist);
+    job->scan_total = reinterpret_cast<uint64_t*>(base + kNbWsTotal);
+    job->partials = reinterpret_cast<uint32_t*>(take(4 * kNbPartialWords * (size_t)extract_groups(n)));
+    job->participants = reinterpret_cast<uint32_t*>(take(4 * (size_t)((n + 31u) / 32u)));
+    job->table = reinterpret_cast<uint32_t*>(take(4 * words));
+    job->scan_sums = reinterpret_cast<uint32_t*>(take(4 * blocks));
+    job->scan_bases = reinterpret_cast<uint32_t*>(take(4 * blocks));
+    job->counts = reinterpret_cast<uint32_t*>(take(4 * (size_t)n));
+    job->records = reinterpret_cast<uint4*>(take(16 * (size_t)n));
+    return at;
+}
+
+// what the calls check about (filter, flags, radius, max_count, grid_bits)
+inline gsx_status check_desc(const char* fn, uint32_t filter, uint32_t flags, float radius, uint32_t max_count, uint32_t grid_bits) {
+    if (filter & ~kModelFilterBits) return fail(GSX_ERR_INVALID_ARG, "%s: unknown filter bits 0x%x", fn, filter);
+    if (flags) return fail(GSX_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x (none are defined)", fn, flags);
+    if (!nb_radius_ok(radius)) return fail(GSX_ERR_INVALID_ARG, "%s: the radius %g is not finite and above 0, or its float32 square is 0 or inf", fn, (double)radius);
+    if (max_count < 1u || max_count > kNbMaxCount) return fail(GSX_ERR_INVALID_ARG, "%s: max_count %u is not in 1 .. %u", fn, max_count, kNbMaxCount);
+    if (grid_bits > kNbMaxBits) return fail(GSX_ERR_INVALID_ARG, "%s: grid_bits %u is above %u", fn, grid_bits, kNbMaxBits);
+    return GSX_OK;
+}
+
+// bind, find, refuse what gsx_model_extract refuses
+inline gsx_status neighbor_model(gsx_viewer* v, const char* fn, const char* key, Model** out) {
+    gsx_status st = viewer_bind(v);  // behind the frames in flight on the lanes
+    if (st) return st;
+    Model* m = find_model(v, key);
+    if (!m) return fail(GSX_ERR_NOT_FOUND, "%s: no model '%s'", fn, key);
+    if (has_comm(v)) return fail(GSX_ERR_UNSUPPORTED, "%s: the viewer has a communicator (call it before gsx_viewer_comm_init, or on one GPU)", fn);
+    if (model_is_shard(m)) return fail(GSX_ERR_UNSUPPORTED, "%s: model '%s' is a shard of a multi-GPU frame", fn, key);
+    *out = m;
+    return GSX_OK;
+}
+
+// The grid's passes, enqueued: the participant bits, the table (bucket ends) and the records in bucket order are in the workspace
+// when the stream reaches its end; the counts are 0.
+inline gsx_status enqueue_grid(gsx_viewer* v, const Model* m, const ModelFilter& f, const NeighborJob& job) {
+    const uint4* pc = extract_planes(m, false).pc;
+    HIPCHK(gsx::op::MemsetAsync(job.result, 0, kNbWsTotal + 8, v->stream));  // the result block, the bins, the scan's total
+    HIPCHK(gsx::op::MemsetAsync(job.table, 0, 4 * (size_t(1) << job.bits), v->stream));
+    HIPCHK(launch_neighbors_reduce(v->stream, m->n, f, pc, job));
+    HIPCHK(launch_neighbors_cell(v->stream, m->n, f, pc, job));
+    HIPCHK(launch_neighbors_scan(v->stream, job));
+    HIPCHK(launch_neighbors_scatter(v->stream, m->n, pc, job));
+    return GSX_OK;
+}
+
+}  // namespace gsx

@@ -328,6 +328,24 @@ class ModelNeighbors:
     grid_bits: int
 
 
+@dataclasses.dataclass
+class ModelClusters:
+    """What ``MultiModelViewerModel.clusters`` returns.  ``labels`` (uint32, one per Gaussian): the smallest Gaussian index of its
+    cluster, ``_lib.GSX_CLUSTER_NONE`` for a Gaussian that does not participate; ``sizes`` (uint32): the size of its cluster, 0 for
+    one that does not participate; ``count``: participants (pass the filter, finite position); ``n_nonfinite``: passed the filter
+    with a NaN or infinite coordinate; ``n_clusters``; ``largest_size`` and ``largest_label``: the largest cluster (the smallest
+    label on a tie; ``GSX_CLUSTER_NONE`` without participants); ``grid_bits``: the hash table used."""
+
+    labels: np.ndarray
+    sizes: np.ndarray
+    count: int
+    n_nonfinite: int
+    n_clusters: int
+    largest_size: int
+    largest_label: int
+    grid_bits: int
+
+
 class MultiModelViewerModel:
     """``gs::MultiModelViewerModel {gaussian_buffers, bind_groups}`` (src/tab/scene.rs:2133-2139)."""
 
@@ -453,6 +471,32 @@ class MultiModelViewerModel:
         desc = _lib.NeighborSelectDesc(int(filter), 0, int(op), cap, float(radius), int(count_lo), int(count_hi), int(grid_bits))
         hit, selected = C.c_uint64(), C.c_uint64()
         _lib.check(self._v._L.gsx_model_select_neighbors(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected)))
+        return int(hit.value), int(selected.value)
+
+    def clusters(self, radius: float, filter: int = 0, grid_bits: int = 0) -> ModelClusters:  # noqa: A002
+        """``gsx_model_clusters``: the connected pieces of the model under "within ``radius`` of one another" (stored positions,
+        ``d2 <= r2`` in float32, model space), among the Gaussians that pass ``filter`` (``_lib.GSX_BOUNDS_*``) and have a finite
+        position; computed on the device by a union-find over a hashed grid.  ``grid_bits`` forces the table size and changes no
+        result."""
+        n = self.gaussian_buffers.gaussians_buffer.len()
+        desc = _lib.ClusterDesc(int(filter), 0, float(radius), int(grid_bits))
+        labels = np.full(n, _lib.GSX_CLUSTER_NONE, np.uint32)
+        sizes = np.zeros(n, np.uint32)
+        out = _lib.ClusterStats()
+        _lib.check(self._v._L.gsx_model_clusters(self._v._h, self._key.encode(), C.byref(desc), labels.ctypes.data, sizes.ctypes.data,
+                                                 C.byref(out)))
+        return ModelClusters(labels, sizes, int(out.count), int(out.n_nonfinite), int(out.n_clusters), int(out.largest_size),
+                             int(out.largest_label), int(out.grid_bits))
+
+    def select_clusters(self, radius: float, mode: int, size_lo: int = 0, size_hi: int = 0, op: int = 0, filter: int = 0,  # noqa: A002
+                        grid_bits: int = 0) -> tuple[int, int]:
+        """``gsx_model_select_clusters``: the hit set is, by ``mode`` (``_lib.GSX_CLUSTER_*``), the clusters whose size lies in
+        ``[size_lo, size_hi]`` (debris below ``k``: ``(1, k - 1)``), the largest cluster, or the clusters that hold a Gaussian
+        selected before the call; ``op`` (``_lib.GSX_SELECTION_*``) makes it the selection, adds it or removes it, on the device.
+        Keep the object: ``select_clusters(r, GSX_CLUSTER_LARGEST)``, then ``extract(dst, SELECTED)``.  Returns ``(hit, selected)``."""
+        desc = _lib.ClusterSelectDesc(int(filter), 0, int(op), int(mode), float(radius), int(size_lo), int(size_hi), int(grid_bits))
+        hit, selected = C.c_uint64(), C.c_uint64()
+        _lib.check(self._v._L.gsx_model_select_clusters(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected)))
         return int(hit.value), int(selected.value)
 
     def _export_desc(self, filter, invert, bake_edits, fmt, staging_bytes):  # noqa: A002
