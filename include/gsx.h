@@ -697,6 +697,69 @@ void gsx_cluster_desc_default(gsx_cluster_desc* d); /* no filter, radius 1, the 
 gsx_status gsx_model_clusters(gsx_viewer* v, const char* key, const gsx_cluster_desc* desc, uint32_t* out_labels, uint32_t* out_sizes, gsx_cluster_stats_t* out);
 gsx_status gsx_model_select_clusters(gsx_viewer* v, const char* key, const gsx_cluster_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected);
 
+/* ---- model nearest neighbours: every Gaussian's k smallest squared distances to the others, a local-scale score from them, the
+ *      score's statistics, and a selection by the score, on the device (spec/RENDER_SPEC.md §20 [BUILD-SPEC]).  The radius-free
+ *      sibling of the two blocks above: stats.mean of GSX_KNN_SCORE_KTH is the radius to hand to gsx_model_neighbors and
+ *      gsx_model_clusters; gsx_model_select_knn in mode GSX_KNN_SELECT_OUTLIERS is the statistical outlier removal of PCL and Open3D
+ *      (mean distance to the k nearest above mean + std_ratio * std over the model), then gsx_model_extract with GSX_BOUNDS_SELECTED
+ *      and GSX_EXTRACT_INVERT.  No Gaussian crosses to the host.
+ *      Participants and distance are gsx_model_neighbors' word for word: a Gaussian participates if it passes desc->filter
+ *      (GSX_BOUNDS_* bits) and its three stored coordinates are finite; stats.count is their number, one that passes the filter
+ *      with a NaN or infinite coordinate goes to n_nonfinite.  d2(i, j) = (dx*dx + dy*dy) + dz*dz in float32, every operation
+ *      rounded; model space, the stored bits as they are: the model transform, the edits and gsx_model_show_unedited change nothing.
+ *      A coordinate difference that overflows gives d2 = +inf; no NaN arises from finite inputs.
+ *      Rows: for a participant i let D(i) be the multiset { d2(i, j) : j participates, j != i } — self is excluded by index, not by
+ *      value: coincident Gaussians are each other's neighbours at distance 0.  nn(i, q), q = 0 .. k - 1, is the q-th smallest
+ *      element of D(i), ascending, +inf where D(i) has fewer than q + 1 elements; out_d2[i * k + q] (nullable; n * k floats) holds
+ *      it.  A Gaussian that does not participate has a row of +inf.  Values only, no indices: ties cannot make the result
+ *      ambiguous.  1 <= k <= GSX_KNN_MAX_K.
+ *      Score: out_score[i] (nullable; n floats), computed on the device, +inf for a Gaussian that does not participate.
+ *      GSX_KNN_SCORE_KTH: sqrtf(nn(i, k - 1)).  GSX_KNN_SCORE_MEAN: s = sqrtf(nn(i, 0)), then s = s + sqrtf(nn(i, q)) for q = 1 ..
+ *      k - 1 in that ascending order, each add rounded to float32; the score is s / (float)k.  sqrtf and the division are correctly
+ *      rounded.  A row that holds a +inf has an infinite score.
+ *      Statistics, over the m participants with a finite score: n_scored = m; score_min and score_max exact; mean = sum / m in
+ *      double; std = sqrt(sum (score - mean)^2 / (m - 1)) in double, two passes, the sample deviation (0 for m < 2); all five 0 for
+ *      m = 0.  The sums are combined from per-workgroup partials in a fixed order: the same bits on every call, like everything
+ *      else the call returns.
+ *      gsx_model_select_knn, the hit set by mode.  GSX_KNN_SELECT_RANGE: participates and lo <= score <= hi (neither bound NaN, lo
+ *      <= hi; hi may be +inf, which also takes the Gaussians with fewer than k others; std_ratio 0).  GSX_KNN_SELECT_OUTLIERS:
+ *      threshold = (float)(mean + (double)std_ratio * std), the double expression without contraction, rounded to nearest; hit iff
+ *      participates, m >= 1 and score > threshold, so an infinite score is an outlier; std_ratio finite; lo and hi 0.  The
+ *      threshold is returned in stats.threshold, which is 0 in RANGE mode and from gsx_model_knn.  selection_op, a model without a
+ *      selection, the tail bits, GSX_BOUNDS_SELECTED reading the selection as it was before the call, *out_hit / *out_selected
+ *      (nullable), ordering and frame consistency: gsx_model_select_range's.
+ *      Knobs that change no result: radius_hint is the first search radius (0: the library chooses it); grid_bits as in
+ *      gsx_model_neighbors; max_rounds 0 for the library's own rule, or 1 .. 64 grid rounds before the exact fallback (ignored
+ *      while the fallback would exceed the library's work budget).  stats.first_radius, rounds, n_brute (the Gaussians the exact
+ *      fallback answered) and grid_bits report what ran and may differ with the knobs; no row, score, statistic or selection
+ *      word may.
+ *      Errors: a null viewer, key, desc or stats pointer of gsx_model_knn, unknown filter bits, score, mode or op, flags != 0 (none
+ *      are defined), k outside 1 .. 16, a radius_hint that is negative or NaN, or positive and one gsx_model_neighbors refuses,
+ *      grid_bits > 24, max_rounds > 64, bounds the mode does not allow, a reserved word != 0: GSX_ERR_INVALID_ARG; unknown key:
+ *      GSX_ERR_NOT_FOUND; a viewer with a communicator, or a sharded model: GSX_ERR_UNSUPPORTED; an allocation failure:
+ *      GSX_ERR_OOM, the model and its selection as they were.  A model of 0 Gaussians, or 0 participants: GSX_OK with zeros (a
+ *      select with Set then clears the selection). ---- */
+#define GSX_KNN_MAX_K 16u
+#define GSX_KNN_SCORE_KTH 0u
+#define GSX_KNN_SCORE_MEAN 1u
+#define GSX_KNN_SELECT_RANGE 0u
+#define GSX_KNN_SELECT_OUTLIERS 1u
+typedef struct gsx_knn_desc { uint32_t filter; uint32_t flags; uint32_t k; uint32_t score; float radius_hint; uint32_t grid_bits; uint32_t max_rounds; uint32_t reserved; } gsx_knn_desc; /* 32 B */
+typedef struct gsx_knn_stats_t {
+    uint64_t count; uint64_t n_nonfinite; uint64_t n_scored; uint64_t n_brute; double mean; double std;
+    float score_min; float score_max; float first_radius; float threshold; uint32_t rounds; uint32_t grid_bits;
+} gsx_knn_stats_t; /* 72 B */
+typedef struct gsx_knn_select_desc {
+    uint32_t filter; uint32_t flags; uint32_t selection_op; uint32_t mode; /* GSX_BOUNDS_*, 0, gsx_selection_op, GSX_KNN_SELECT_* */
+    uint32_t k; uint32_t score; float radius_hint; uint32_t grid_bits;
+    uint32_t max_rounds; float lo; float hi; float std_ratio;
+} gsx_knn_select_desc; /* 48 B */
+void gsx_knn_desc_default(gsx_knn_desc* d); /* no filter, k 3, SCORE_MEAN, everything else 0 */
+gsx_status gsx_model_knn(gsx_viewer* v, const char* key, const gsx_knn_desc* desc, float* out_d2 /* nullable, n * k, row i at i * k */,
+                         float* out_score /* nullable, n */, gsx_knn_stats_t* out);
+gsx_status gsx_model_select_knn(gsx_viewer* v, const char* key, const gsx_knn_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected,
+                                gsx_knn_stats_t* out_stats /* nullable */);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

@@ -16,6 +16,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <limits>
 #include <map>
 #include <optional>
 #include <stdexcept>
@@ -268,6 +269,27 @@ struct MultiModelViewerModel {
     std::pair<uint64_t, uint64_t> select_clusters(const gsx_cluster_select_desc& desc) {
         uint64_t hit = 0, selected = 0;
         check(gsx_model_select_clusters(v_, key_.c_str(), &desc, &hit, &selected));
+        return {hit, selected};
+    }
+    // gsx_model_knn: every Gaussian's desc.k smallest squared distances to the others (float32, model space), a score from them
+    // (GSX_KNN_SCORE_*) and the score's statistics, among the Gaussians that pass desc.filter and have a finite position; computed on
+    // the device, bit for bit the brute-force answer.  score receives one float a Gaussian, d2 (nullable) n * k floats, row i at i *
+    // k; both +inf for a Gaussian that does not participate.
+    gsx_knn_stats_t knn(const gsx_knn_desc& desc, std::vector<float>& score, std::vector<float>* d2 = nullptr) const {
+        uint64_t n = 0;
+        check(gsx_model_len(v_, key_.c_str(), &n));
+        score.assign((size_t)n, std::numeric_limits<float>::infinity());
+        if (d2) d2->assign((size_t)n * desc.k, std::numeric_limits<float>::infinity());
+        gsx_knn_stats_t out{};
+        check(gsx_model_knn(v_, key_.c_str(), &desc, d2 ? d2->data() : nullptr, score.data(), &out));
+        return out;
+    }
+    // gsx_model_select_knn: the hit set is, by desc.mode, the participants with a score in [lo, hi] or the statistical outliers (score
+    // above mean + std_ratio * std); desc.selection_op sets, adds or removes it, on the device.  Returns {hit, selected afterwards};
+    // stats (nullable) receives the statistics and the threshold.
+    std::pair<uint64_t, uint64_t> select_knn(const gsx_knn_select_desc& desc, gsx_knn_stats_t* stats = nullptr) {
+        uint64_t hit = 0, selected = 0;
+        check(gsx_model_select_knn(v_, key_.c_str(), &desc, &hit, &selected, stats));
         return {hit, selected};
     }
 };

@@ -247,6 +247,29 @@ impl MultiModelViewerModel {
         check(unsafe { sys::gsx_model_select_clusters(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected) })?;
         Ok((hit, selected))
     }
+    /// `gsx_model_knn`: every Gaussian's `desc.k` smallest squared distances to the others (`f32`, model space), a score from them
+    /// (`GSX_KNN_SCORE_*`) and the score's statistics, among the Gaussians that pass `desc.filter` and have a finite position; computed
+    /// on the device, bit for bit the brute-force answer.  Returns `(d2, score, stats)`: `d2` holds `n * k` values, row `i` at `i * k`
+    /// (empty without `rows`), `score` one value a Gaussian; both `+inf` for a Gaussian that does not participate.
+    pub fn knn(&self, desc: &sys::gsx_knn_desc, rows: bool) -> Result<(Vec<f32>, Vec<f32>, sys::gsx_knn_stats_t), Error> {
+        let mut n = 0u64;
+        check(unsafe { sys::gsx_model_len(self.v, self.key.as_ptr(), &mut n) })?;
+        let mut d2 = vec![f32::INFINITY; if rows { n as usize * desc.k as usize } else { 0 }];
+        let mut score = vec![f32::INFINITY; n as usize];
+        let mut out = sys::gsx_knn_stats_t::default();
+        let d2_ptr = if rows { d2.as_mut_ptr() } else { std::ptr::null_mut() };
+        check(unsafe { sys::gsx_model_knn(self.v, self.key.as_ptr(), desc, d2_ptr, score.as_mut_ptr(), &mut out) })?;
+        Ok((d2, score, out))
+    }
+    /// `gsx_model_select_knn`: the hit set is, by `desc.mode`, the participants with a score in `[lo, hi]` or the statistical outliers
+    /// (score above mean + `std_ratio` * std); `desc.selection_op` sets, adds or removes it, on the device.  Returns
+    /// `(hit, selected, stats)`.
+    pub fn select_knn(&mut self, desc: &sys::gsx_knn_select_desc) -> Result<(u64, u64, sys::gsx_knn_stats_t), Error> {
+        let (mut hit, mut selected) = (0u64, 0u64);
+        let mut out = sys::gsx_knn_stats_t::default();
+        check(unsafe { sys::gsx_model_select_knn(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected, &mut out) })?;
+        Ok((hit, selected, out))
+    }
 }
 
 pub struct Preprocessor(*mut sys::gsx_viewer);

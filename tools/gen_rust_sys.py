@@ -88,6 +88,11 @@ pub const GSX_CLUSTER_NONE: u32 = 0xFFFF_FFFF;
 pub const GSX_CLUSTER_BY_SIZE: u32 = 0;
 pub const GSX_CLUSTER_LARGEST: u32 = 1;
 pub const GSX_CLUSTER_SEEDED: u32 = 2;
+pub const GSX_KNN_MAX_K: u32 = 16;
+pub const GSX_KNN_SCORE_KTH: u32 = 0;
+pub const GSX_KNN_SCORE_MEAN: u32 = 1;
+pub const GSX_KNN_SELECT_RANGE: u32 = 0;
+pub const GSX_KNN_SELECT_OUTLIERS: u32 = 1;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -239,6 +244,30 @@ pub struct gsx_cluster_stats_t {
 pub struct gsx_cluster_select_desc {
     pub filter: u32, pub flags: u32, pub selection_op: u32, pub mode: u32, pub radius: f32,
     pub size_lo: u32, pub size_hi: u32, pub grid_bits: u32, pub reserved: [u32; 2],
+}
+/// gsx_model_knn, 32 bytes: the GSX_BOUNDS_* filter, flags (0), k 1..=16, the GSX_KNN_SCORE_* score, and three knobs that change no
+/// result: radius_hint (0: the library's first search radius), grid_bits, max_rounds (0: the library's rule; 1..=64)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_knn_desc {
+    pub filter: u32, pub flags: u32, pub k: u32, pub score: u32, pub radius_hint: f32, pub grid_bits: u32, pub max_rounds: u32, pub reserved: u32,
+}
+/// the result of gsx_model_knn, 72 bytes: participants, those with a NaN / inf coordinate, the finite scores' number, the Gaussians the
+/// exact fallback answered, the scores' double mean and sample deviation, minimum and maximum, the first radius, the outlier threshold
+/// (select, mode OUTLIERS; otherwise 0), the grid rounds, the table used
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_knn_stats_t {
+    pub count: u64, pub n_nonfinite: u64, pub n_scored: u64, pub n_brute: u64, pub mean: f64, pub std: f64,
+    pub score_min: f32, pub score_max: f32, pub first_radius: f32, pub threshold: f32, pub rounds: u32, pub grid_bits: u32,
+}
+/// gsx_model_select_knn, 48 bytes: mode GSX_KNN_SELECT_RANGE (lo <= score <= hi; std_ratio 0) or _OUTLIERS (score > mean + std_ratio *
+/// std; lo and hi 0)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_knn_select_desc {
+    pub filter: u32, pub flags: u32, pub selection_op: u32, pub mode: u32, pub k: u32, pub score: u32, pub radius_hint: f32,
+    pub grid_bits: u32, pub max_rounds: u32, pub lo: f32, pub hi: f32, pub std_ratio: f32,
 }
 #[repr(C)]
 #[derive(Clone, Copy)]

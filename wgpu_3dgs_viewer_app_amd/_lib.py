@@ -54,6 +54,7 @@ EXPORTS = (
     "gsx_model_property_values", "gsx_model_histogram", "gsx_model_select_range",
     "gsx_neighbor_desc_default", "gsx_model_neighbors", "gsx_model_select_neighbors",
     "gsx_cluster_desc_default", "gsx_model_clusters", "gsx_model_select_clusters",
+    "gsx_knn_desc_default", "gsx_model_knn", "gsx_model_select_knn",
 )
 
 
@@ -193,6 +194,40 @@ class ClusterSelectDesc(C.Structure):
     the cluster sizes ``[size_lo, size_hi]`` that are hit (mode BY_SIZE; 0, 0 otherwise), ``grid_bits``."""
     _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("selection_op", C.c_uint32), ("mode", C.c_uint32), ("radius", C.c_float),
                 ("size_lo", C.c_uint32), ("size_hi", C.c_uint32), ("grid_bits", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+#: the largest ``k`` of ``gsx_model_knn``
+GSX_KNN_MAX_K = 16
+#: ``gsx_knn_desc.score``: the distance to the k-th nearest, or the mean distance to the k nearest
+GSX_KNN_SCORE_KTH, GSX_KNN_SCORE_MEAN = 0, 1
+#: ``gsx_knn_select_desc.mode``
+GSX_KNN_SELECT_RANGE, GSX_KNN_SELECT_OUTLIERS = 0, 1
+
+
+class KnnDesc(C.Structure):
+    """``gsx_knn_desc`` (32 bytes): the ``GSX_BOUNDS_*`` filter, flags (0), ``k`` (1..16), the ``GSX_KNN_SCORE_*`` score, and three
+    knobs that change no result: ``radius_hint`` (0: the library's first search radius), ``grid_bits`` (0: the library's hash
+    table), ``max_rounds`` (0: the library's rule; 1..64 grid rounds before the exact fallback)."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("k", C.c_uint32), ("score", C.c_uint32), ("radius_hint", C.c_float),
+                ("grid_bits", C.c_uint32), ("max_rounds", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class KnnStats(C.Structure):
+    """``gsx_knn_stats_t`` (72 bytes): the participants, the non-finite, the finite scores' number, minimum, maximum, double mean and
+    sample deviation, the outlier threshold (select, mode OUTLIERS), and what ran: the first radius, the grid rounds, the Gaussians the
+    exact fallback answered, the table."""
+    _fields_ = [("count", C.c_uint64), ("n_nonfinite", C.c_uint64), ("n_scored", C.c_uint64), ("n_brute", C.c_uint64), ("mean", C.c_double),
+                ("std", C.c_double), ("score_min", C.c_float), ("score_max", C.c_float), ("first_radius", C.c_float), ("threshold", C.c_float),
+                ("rounds", C.c_uint32), ("grid_bits", C.c_uint32)]
+
+
+class KnnSelectDesc(C.Structure):
+    """``gsx_knn_select_desc`` (48 bytes): the filter, flags (0), the ``gsx_selection_op``, the ``GSX_KNN_SELECT_*`` mode, ``k``, the
+    score, the three knobs, the score range ``[lo, hi]`` (mode RANGE) and ``std_ratio`` (mode OUTLIERS: hit above mean + std_ratio *
+    std)."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("selection_op", C.c_uint32), ("mode", C.c_uint32), ("k", C.c_uint32),
+                ("score", C.c_uint32), ("radius_hint", C.c_float), ("grid_bits", C.c_uint32), ("max_rounds", C.c_uint32), ("lo", C.c_float),
+                ("hi", C.c_float), ("std_ratio", C.c_float)]
 
 
 class ExtractDesc(C.Structure):
@@ -448,6 +483,9 @@ def load() -> C.CDLL:
         "gsx_cluster_desc_default": ([C.POINTER(ClusterDesc)], None),
         "gsx_model_clusters": ([vp, cp, C.POINTER(ClusterDesc), C.c_void_p, C.c_void_p, C.POINTER(ClusterStats)], C.c_int32),
         "gsx_model_select_clusters": ([vp, cp, C.POINTER(ClusterSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_knn_desc_default": ([C.POINTER(KnnDesc)], None),
+        "gsx_model_knn": ([vp, cp, C.POINTER(KnnDesc), C.c_void_p, C.c_void_p, C.POINTER(KnnStats)], C.c_int32),
+        "gsx_model_select_knn": ([vp, cp, C.POINTER(KnnSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(KnnStats)], C.c_int32),
         "gsx_model_merge": ([vp, C.POINTER(C.c_char_p), C.c_uint32, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)

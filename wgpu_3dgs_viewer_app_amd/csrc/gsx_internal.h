@@ -1126,6 +1126,40 @@ hipError_t launch_clusters_label(hipStream_t s, uint64_t n, const ClusterJob& jo
 hipError_t launch_clusters_stats(hipStream_t s, uint64_t n, const ClusterJob& job);   // sizes, result[8], result[10..11]
 hipError_t launch_clusters_select(hipStream_t s, uint64_t n, const ClusterJob& job);  // selection, result[5..6]
 
+// Model nearest neighbours (kernels_knn.hip; gsx_model_knn, gsx_model_select_knn): every participant's k smallest squared distances
+// by rounds over the grid above at growing radii (launch_neighbors_reduce / _cell / _scan / _scatter on `nb`, once a round) and an
+// exact fallback over all records (knn_math.h).  The kNN's own regions lie behind the grid's, where the grid's memsets do not reach.
+// Its words (kKnnWords 32-bit words; the doubles at even word offsets):
+//   [0..1] the entries of list 0 / list 1
+//   [10] n_scored  [11] score_min  [12] score_max  [13] threshold (float bits)  [14] hit  [15] selected afterwards
+//   [16] sum  [18] mean  [20] sum of squared deviations  [22] std (doubles)
+enum : uint32_t {
+    kKnnList = 0, kKnnScored = 10, kKnnScoreMin = 11, kKnnScoreMax = 12,
+    kKnnThreshold = 13, kKnnHit = 14, kKnnSelected = 15, kKnnSum = 16, kKnnMean = 18, kKnnSs = 20, kKnnStd = 22, kKnnWords = 32
+};
+constexpr uint32_t kKnnPartialWords = 8;  // 32 B a workgroup: stats (count | min | max | - | the double sum), select (hit | selected)
+struct KnnJob {
+    NeighborJob nb;           // the grid of the round; nb.records holds every participant after any round's scatter
+    uint32_t k, score;        // 1 .. 16; GSX_KNN_SCORE_*
+    uint32_t mode;            // select: GSX_KNN_SELECT_*; the op, the selection and selection_valid are nb's
+    float lo, hi, std_ratio;  // select
+    uint32_t* words;          // kKnnWords words
+    uint32_t* partials;       // extract_groups(n) x kKnnPartialWords words
+    float* scores;            // n floats, filled with +inf before the search
+    float* rows;              // n * k floats, filled with +inf, or nullptr: the rows are not wanted
+    uint4* list[2];           // n records each: the unresolved entries of a round (x, y, z bits, original index), in any order
+    gsx_model_bounds_t* box;  // the participants' count, box and trimmed box (launch_bounds_*), with its partials and histogram
+    BoundsPartial* box_partials;
+    uint32_t* box_hist;
+};
+hipError_t launch_knn_fill(hipStream_t s, uint64_t n, const KnnJob& job);                                           // scores, rows = +inf
+// One grid round: the `count` entries of src (the grid's records, or a list) are answered or appended to list[to] (words[to] zeroed by the caller).
+hipError_t launch_knn_query(hipStream_t s, uint64_t n, const uint4* src, uint32_t count, uint32_t to, const KnnJob& job);
+// The exact fallback: one workgroup an entry of src against all `total` records of the grid.
+hipError_t launch_knn_brute(hipStream_t s, uint64_t n, const uint4* src, uint32_t count, uint32_t total, const KnnJob& job);
+hipError_t launch_knn_stats(hipStream_t s, uint64_t n, const KnnJob& job);   // words[10..13], [16..23]
+hipError_t launch_knn_select(hipStream_t s, uint64_t n, const KnnJob& job);  // selection, words[14..15]
+
 // Model export (kernels_export.hip; gsx_model_export): the rows of the kept Gaussians of the source workgroups [group0, group0 +
 // n_groups), in `format` (GSX_EXPORT_*), into `out` starting at the chunk's first kept Gaussian: row_base = bases[group0].  `out`
 // holds at least bases[group0 + n_groups] - row_base rows (the total in place of bases[] past the last group).  src is only read;

@@ -346,6 +346,37 @@ class ModelClusters:
     grid_bits: int
 
 
+@dataclasses.dataclass
+class ModelKnn:
+    """What ``MultiModelViewerModel.knn`` returns.  ``d2`` (float32, ``(n, k)``, or ``None`` without ``rows=True``): every Gaussian's k
+    smallest squared distances to the other participants, ascending, ``+inf`` where there are fewer and for a Gaussian that does not
+    participate; ``score`` (float32, one per Gaussian): the distance to the k-th nearest or the mean distance to the k nearest,
+    ``+inf`` where the row holds one; ``count``: participants (pass the filter, finite position); ``n_nonfinite``; ``n_scored``,
+    ``score_min``, ``score_max``, ``mean``, ``std`` (the sample deviation): over the finite scores; ``first_radius``, ``rounds``,
+    ``n_brute``, ``grid_bits``: what the search ran (they may differ with the knobs; nothing else does)."""
+
+    d2: np.ndarray | None
+    score: np.ndarray
+    count: int
+    n_nonfinite: int
+    n_scored: int
+    score_min: np.float32
+    score_max: np.float32
+    mean: float
+    std: float
+    threshold: np.float32
+    first_radius: np.float32
+    rounds: int
+    n_brute: int
+    grid_bits: int
+
+
+def _knn_stats(out, d2, score) -> ModelKnn:
+    return ModelKnn(d2, score, int(out.count), int(out.n_nonfinite), int(out.n_scored), np.float32(out.score_min), np.float32(out.score_max),
+                    float(out.mean), float(out.std), np.float32(out.threshold), np.float32(out.first_radius), int(out.rounds),
+                    int(out.n_brute), int(out.grid_bits))
+
+
 class MultiModelViewerModel:
     """``gs::MultiModelViewerModel {gaussian_buffers, bind_groups}`` (src/tab/scene.rs:2133-2139)."""
 
@@ -498,6 +529,39 @@ class MultiModelViewerModel:
         hit, selected = C.c_uint64(), C.c_uint64()
         _lib.check(self._v._L.gsx_model_select_clusters(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected)))
         return int(hit.value), int(selected.value)
+
+    def knn(self, k: int = 3, score: int = _lib.GSX_KNN_SCORE_MEAN, filter: int = 0, radius_hint: float = 0.0,  # noqa: A002
+            grid_bits: int = 0, max_rounds: int = 0, rows: bool = False) -> ModelKnn:
+        """``gsx_model_knn``: for every Gaussian the ``k`` (1..16) smallest squared distances to the others (stored positions, float32,
+        model space; ``rows=True`` downloads them), a score from them (``_lib.GSX_KNN_SCORE_*``) and the score's statistics, among
+        the Gaussians that pass ``filter`` (``_lib.GSX_BOUNDS_*``) and have a finite position; computed on the device, bit for bit
+        the brute-force answer.  ``knn(k, GSX_KNN_SCORE_KTH).mean`` is a radius for ``neighbors`` and ``clusters``.  ``radius_hint``,
+        ``grid_bits`` and ``max_rounds`` steer the search and change no result."""
+        n = self.gaussian_buffers.gaussians_buffer.len()
+        desc = _lib.KnnDesc(int(filter), 0, int(k), int(score), float(radius_hint), int(grid_bits), int(max_rounds), 0)
+        d2 = np.full((n, min(max(int(k), 1), _lib.GSX_KNN_MAX_K)), np.inf, np.float32) if rows else None
+        values = np.full(n, np.inf, np.float32)
+        out = _lib.KnnStats()
+        _lib.check(self._v._L.gsx_model_knn(self._v._h, self._key.encode(), C.byref(desc), d2.ctypes.data if rows else None,
+                                            values.ctypes.data, C.byref(out)))
+        return _knn_stats(out, d2, values)
+
+    def select_knn(self, k: int = 3, score: int = _lib.GSX_KNN_SCORE_MEAN, lo: float = 0.0, hi: float = 0.0,
+                   std_ratio: float | None = None, op: int = 0, filter: int = 0, radius_hint: float = 0.0,  # noqa: A002
+                   grid_bits: int = 0, max_rounds: int = 0) -> tuple[int, int, ModelKnn]:
+        """``gsx_model_select_knn``: the participants whose score lies in ``[lo, hi]`` (``hi`` may be ``inf``) or, with ``std_ratio``
+        given, the statistical outliers (score above mean + ``std_ratio`` * std over the model, as in PCL and Open3D) are the hit
+        set; ``op`` (``_lib.GSX_SELECTION_*``) makes it the selection, adds it or removes it, on the device.  Floaters:
+        ``select_knn(k, std_ratio=2.0)``, then ``extract(dst, SELECTED, invert=True)``.  Returns ``(hit, selected, stats)``; the
+        stats carry the threshold and no arrays."""
+        outliers = std_ratio is not None
+        desc = _lib.KnnSelectDesc(int(filter), 0, int(op), _lib.GSX_KNN_SELECT_OUTLIERS if outliers else _lib.GSX_KNN_SELECT_RANGE, int(k),
+                                  int(score), float(radius_hint), int(grid_bits), int(max_rounds), float(lo), float(hi),
+                                  float(std_ratio) if outliers else 0.0)
+        hit, selected, out = C.c_uint64(), C.c_uint64(), _lib.KnnStats()
+        _lib.check(self._v._L.gsx_model_select_knn(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected),
+                                                   C.byref(out)))
+        return int(hit.value), int(selected.value), _knn_stats(out, None, None)
 
     def _export_desc(self, filter, invert, bake_edits, fmt, staging_bytes):  # noqa: A002
         return _lib.ExportDesc(int(filter), (_lib.GSX_EXTRACT_INVERT if invert else 0) | (_lib.GSX_EXPORT_BAKE_EDITS if bake_edits else 0),
