@@ -760,6 +760,43 @@ gsx_status gsx_model_knn(gsx_viewer* v, const char* key, const gsx_knn_desc* des
 gsx_status gsx_model_select_knn(gsx_viewer* v, const char* key, const gsx_knn_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected,
                                 gsx_knn_stats_t* out_stats /* nullable */);
 
+/* ---- model transform: move, rotate, scale or mirror the kept Gaussians of a resident model where they lie, on the device
+ *      (spec/RENDER_SPEC.md §21 [BUILD-SPEC]).  The edit behind "grab the selection and move it": no copy of the model, the Gaussian
+ *      order, every index, the mask, the selection and the edit records stay.  gsx_update_model_transform moves a whole model
+ *      without touching its data; this call bakes a transform into part of it.
+ *      Kept set: gsx_model_extract's, word for word (desc->filter GSX_BOUNDS_* bits, desc->flags GSX_EXTRACT_INVERT; no mask: all
+ *      pass; GSX_BOUNDS_SELECTED without a selection: none passes; bits at or above the count never count, before or after
+ *      inversion).  A kept Gaussian is rewritten at its own index; every byte of every other Gaussian stays.  *out_count
+ *      (nullable) receives the kept count.
+ *      Position: with c = pivot, q = p - c per axis, a = scale * q and R the float32 matrix of the quaternion AS GIVEN (what a
+ *      model transform's quaternion becomes in a frame): p'_r = (((R_r0 a0 + R_r1 a1) + R_r2 a2) + pos_r) + c_r, every operation
+ *      rounded to float32, no contraction.  With a pivot that is exactly (0, 0, 0) the subtraction and the last addition are not
+ *      performed: p' is then what gsx_model_merge bakes for that model transform, bit for bit.  A non-finite coordinate goes
+ *      through the same formula.
+ *      Covariance and SH: gsx_model_merge's bake (S' = (M S) M^T with M = R diag(scale); per band c' = M_l c with the matrices of
+ *      the normalised quaternion), dequantised exactly and quantised again into the model's pod kind; neither depends on the
+ *      pivot; the colour word is carried.  Every call that rewrites a quantised plane quantises it again: with Half or Norm8
+ *      planes, n calls are not one call with the composed transform.
+ *      Planes that are carried as stored bits: the SH planes under quat (0, 0, 0, +-1) (as float32 values); the covariance planes
+ *      too when scale is also (1, 1, 1) — a translation writes positions only, which is what makes moving a Half or Norm8 model
+ *      lossless; and with pos 0 as well (the identity) nothing is written at all, whatever the pivot, and no frame state is reset.
+ *      A quaternion that is the identity only after normalisation, (0, 0, 0, 2), is not the identity: every plane is rewritten.
+ *      The shade records of the kept Gaussians agree with the planes afterwards.  Not touched: the model transform, the mask and
+ *      selection words (a mask evaluated from shapes is not evaluated again: the bits stay, the positions moved), the edit records,
+ *      gsx_model_show_unedited, the pod kind.  Runs on the viewer's stream behind every frame in flight; the next frames are
+ *      ordered behind it.  The same bits on every call.  No shear, no general matrix.
+ *      Errors: a null viewer, key or desc, unknown filter bits, a flag other than GSX_EXTRACT_INVERT, a non-finite pos, quat,
+ *      scale or pivot component, a zero quaternion, reserved != 0: GSX_ERR_INVALID_ARG; unknown key: GSX_ERR_NOT_FOUND; a viewer
+ *      with a communicator, or a sharded model: GSX_ERR_UNSUPPORTED; an allocation failure: GSX_ERR_OOM, the model as it was.  A
+ *      model of 0 Gaussians or an empty kept set: GSX_OK, count 0, nothing written. ---- */
+typedef struct gsx_transform_desc {
+    uint32_t filter; uint32_t flags;                 /* GSX_BOUNDS_*, GSX_EXTRACT_INVERT */
+    float pos[3]; float quat[4]; float scale[3];     /* as gsx_update_model_transform takes them; quat x, y, z, w */
+    float pivot[3]; uint32_t reserved;               /* rotate and scale about this point (model space); 0 */
+} gsx_transform_desc; /* 64 B */
+void gsx_transform_desc_default(gsx_transform_desc* d); /* no filter, no flags, pos 0, quat (0, 0, 0, 1), scale 1, pivot 0 */
+gsx_status gsx_model_apply_transform(gsx_viewer* v, const char* key, const gsx_transform_desc* desc, uint64_t* out_count /* nullable */);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

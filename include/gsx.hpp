@@ -205,6 +205,15 @@ struct MultiModelViewerModel {
     void set_pod_kind(ShCompression sh, Cov3dCompression cov3d) {
         check(gsx_model_set_pod_kind(v_, key_.c_str(), (gsx_sh_kind)sh, (gsx_cov3d_kind)cov3d));
     }
+    // gsx_model_apply_transform: the Gaussians that pass desc.filter (desc.flags GSX_EXTRACT_INVERT: those that do not) are moved,
+    // rotated, scaled or mirrored about desc.pivot where they lie, on the device: positions, covariances, SH and shade records as
+    // gsx_model_merge bakes a model transform; order, mask, selection and edits stay.  "Rotate the selection about its centre":
+    // pivot = bounds(GSX_BOUNDS_SELECTED).center.  Returns the number of Gaussians moved.
+    uint64_t apply_transform(const gsx_transform_desc& desc) {
+        uint64_t count = 0;
+        check(gsx_model_apply_transform(v_, key_.c_str(), &desc, &count));
+        return count;
+    }
     // gsx_model_property_values: one float32 per Gaussian, computed on the device from the stored values (edits are not applied): the
     // stored position (flags = GSX_PROP_WORLD: the model transform applied as merge bakes it), the bytes of the colour word / 255, their
     // HSV, or the scales export solves from the covariance.

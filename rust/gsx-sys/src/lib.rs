@@ -220,6 +220,13 @@ pub struct gsx_knn_select_desc {
     pub filter: u32, pub flags: u32, pub selection_op: u32, pub mode: u32, pub k: u32, pub score: u32, pub radius_hint: f32,
     pub grid_bits: u32, pub max_rounds: u32, pub lo: f32, pub hi: f32, pub std_ratio: f32,
 }
+/// gsx_model_apply_transform, 64 bytes: the GSX_BOUNDS_* filter, flags (GSX_EXTRACT_INVERT), the transform as
+/// gsx_update_model_transform takes it (quat x, y, z, w), the pivot it rotates and scales about, reserved (0)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gsx_transform_desc {
+    pub filter: u32, pub flags: u32, pub pos: [f32; 3], pub quat: [f32; 4], pub scale: [f32; 3], pub pivot: [f32; 3], pub reserved: u32,
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }
@@ -359,6 +366,8 @@ extern "C" {
     pub fn gsx_knn_desc_default(d: *mut gsx_knn_desc);
     pub fn gsx_model_knn(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_knn_desc, out_d2: *mut f32, out_score: *mut f32, out: *mut gsx_knn_stats_t) -> gsx_status;
     pub fn gsx_model_select_knn(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_knn_select_desc, out_hit: *mut u64, out_selected: *mut u64, out_stats: *mut gsx_knn_stats_t) -> gsx_status;
+    pub fn gsx_transform_desc_default(d: *mut gsx_transform_desc);
+    pub fn gsx_model_apply_transform(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_transform_desc, out_count: *mut u64) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

@@ -181,6 +181,15 @@ impl MultiModelViewerModel {
     pub fn set_pod_kind(&mut self, sh: sys::gsx_sh_kind, cov3d: sys::gsx_cov3d_kind) -> Result<(), Error> {
         check(unsafe { sys::gsx_model_set_pod_kind(self.v, self.key.as_ptr(), sh, cov3d) })
     }
+    /// `gsx_model_apply_transform`: the Gaussians that pass `desc.filter` (`desc.flags` `GSX_EXTRACT_INVERT`: those that do not) are
+    /// moved, rotated, scaled or mirrored about `desc.pivot` where they lie, on the device: positions, covariances, SH and shade
+    /// records as `merge` bakes a model transform; order, mask, selection and edits stay.  "Rotate the selection about its centre":
+    /// `pivot = bounds(GSX_BOUNDS_SELECTED, 0)?.center`.  Returns the number of Gaussians moved.
+    pub fn apply_transform(&mut self, desc: &sys::gsx_transform_desc) -> Result<u64, Error> {
+        let mut count = 0u64;
+        check(unsafe { sys::gsx_model_apply_transform(self.v, self.key.as_ptr(), desc, &mut count) })?;
+        Ok(count)
+    }
     /// `gsx_model_property_values`: one `f32` per Gaussian, computed on the device from the stored values (edits are not applied):
     /// the stored position (`flags = GSX_PROP_WORLD`: the model transform applied as `merge` bakes it), the bytes of the colour word
     /// / 255, their HSV, or the scales `export` solves from the covariance.

@@ -269,6 +269,13 @@ pub struct gsx_knn_select_desc {
     pub filter: u32, pub flags: u32, pub selection_op: u32, pub mode: u32, pub k: u32, pub score: u32, pub radius_hint: f32,
     pub grid_bits: u32, pub max_rounds: u32, pub lo: f32, pub hi: f32, pub std_ratio: f32,
 }
+/// gsx_model_apply_transform, 64 bytes: the GSX_BOUNDS_* filter, flags (GSX_EXTRACT_INVERT), the transform as
+/// gsx_update_model_transform takes it (quat x, y, z, w), the pivot it rotates and scales about, reserved (0)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gsx_transform_desc {
+    pub filter: u32, pub flags: u32, pub pos: [f32; 3], pub quat: [f32; 4], pub scale: [f32; 3], pub pivot: [f32; 3], pub reserved: u32,
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }

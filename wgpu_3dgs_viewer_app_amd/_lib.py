@@ -55,6 +55,7 @@ EXPORTS = (
     "gsx_neighbor_desc_default", "gsx_model_neighbors", "gsx_model_select_neighbors",
     "gsx_cluster_desc_default", "gsx_model_clusters", "gsx_model_select_clusters",
     "gsx_knn_desc_default", "gsx_model_knn", "gsx_model_select_knn",
+    "gsx_transform_desc_default", "gsx_model_apply_transform",
 )
 
 
@@ -228,6 +229,13 @@ class KnnSelectDesc(C.Structure):
     _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("selection_op", C.c_uint32), ("mode", C.c_uint32), ("k", C.c_uint32),
                 ("score", C.c_uint32), ("radius_hint", C.c_float), ("grid_bits", C.c_uint32), ("max_rounds", C.c_uint32), ("lo", C.c_float),
                 ("hi", C.c_float), ("std_ratio", C.c_float)]
+
+
+class TransformDesc(C.Structure):
+    """``gsx_transform_desc`` (64 bytes): the ``GSX_BOUNDS_*`` filter, flags (``GSX_EXTRACT_INVERT``), the transform as
+    ``gsx_update_model_transform`` takes it (``quat`` x, y, z, w), the pivot it rotates and scales about, reserved (0)."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("pos", C.c_float * 3), ("quat", C.c_float * 4), ("scale", C.c_float * 3),
+                ("pivot", C.c_float * 3), ("reserved", C.c_uint32)]
 
 
 class ExtractDesc(C.Structure):
@@ -486,6 +494,8 @@ def load() -> C.CDLL:
         "gsx_knn_desc_default": ([C.POINTER(KnnDesc)], None),
         "gsx_model_knn": ([vp, cp, C.POINTER(KnnDesc), C.c_void_p, C.c_void_p, C.POINTER(KnnStats)], C.c_int32),
         "gsx_model_select_knn": ([vp, cp, C.POINTER(KnnSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(KnnStats)], C.c_int32),
+        "gsx_transform_desc_default": ([C.POINTER(TransformDesc)], None),
+        "gsx_model_apply_transform": ([vp, cp, C.POINTER(TransformDesc), C.POINTER(C.c_uint64)], C.c_int32),
         "gsx_model_merge": ([vp, C.POINTER(C.c_char_p), C.c_uint32, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)

@@ -1042,6 +1042,18 @@ hipError_t launch_merge_bake(hipStream_t s, int sh_kind, int cov_kind, uint64_t 
 hipError_t launch_convert_kind(hipStream_t s, int src_sh, int src_cov, int dst_sh, int dst_cov, uint64_t n_src, uint64_t n_dst, uint64_t dst_offset,
                                const uint32_t* keep, const uint32_t* bases, const ExtractPlanes& src, const ExtractPlanes& dst);
 
+// Model transform (kernels_transform.hip; gsx_model_apply_transform): the kept Gaussians of `m` (keep: launch_extract_keep's words)
+// are dequantised, moved and quantised again at their own index, planes and shade records; nothing else of `m` is written.  The
+// constants go by value, as MergeBake does; `mode` is transform_math.h's (translate, no rotation or full: the identity launches
+// nothing, hipErrorInvalidValue) and decides which planes are read and written at all.  m's edit planes are not used.
+struct TransformBake {
+    MergeBake b;          // R = quat_to_rows(quat), s, t, the SH matrices (read in full mode only)
+    float c[3];           // the pivot
+    uint32_t use_pivot;   // 0: the pivot is exactly zero, p' is §13's
+};
+hipError_t launch_transform_inplace(hipStream_t s, int sh_kind, int cov_kind, int mode, uint64_t n, const uint32_t* keep, const ExtractPlanes& m,
+                                    const TransformBake& bake);
+
 // Model properties (kernels_property.hip; gsx_model_property_values, gsx_model_histogram, gsx_model_select_range): one frame over
 // the model in four modes, each but the first followed by a one-workgroup finish over the workgroups' partials.  The result block
 // (kPropResultWords words; the finish of a mode writes that mode's words):

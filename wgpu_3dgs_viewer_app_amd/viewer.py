@@ -439,6 +439,21 @@ class MultiModelViewerModel:
         buffers are moved).  The next frame is an unspeculated one.  The same kind does nothing."""
         _lib.check(self._v._L.gsx_model_set_pod_kind(self._v._h, self._key.encode(), int(sh), int(cov3d)))
 
+    def apply_transform(self, pos=(0.0, 0.0, 0.0), quat=(0.0, 0.0, 0.0, 1.0), scale=(1.0, 1.0, 1.0), pivot=(0.0, 0.0, 0.0),
+                        filter: int = 0, invert: bool = False) -> int:  # noqa: A002
+        """``gsx_model_apply_transform``: the Gaussians that pass ``filter`` (``_lib.GSX_BOUNDS_*`` bits, ``extract``'s kept set;
+        ``invert``: exactly those that do not) are moved, rotated, scaled or mirrored about ``pivot`` where they lie, on the device:
+        positions, covariances, SH and shade records as ``merge`` bakes a model transform (``quat`` x, y, z, w, taken as given).
+        The Gaussian order, the mask, the selection, the edit records and the model transform stay.  A translation writes
+        positions only; the identity writes nothing.  "Rotate the selection about its centre":
+        ``pivot=model.bounds(selected=True).center, filter=GSX_BOUNDS_SELECTED``.  Returns the number of Gaussians moved."""
+        f3 = lambda a: (C.c_float * 3)(*(float(x) for x in a))  # noqa: E731
+        desc = _lib.TransformDesc(int(filter), _lib.GSX_EXTRACT_INVERT if invert else 0, f3(pos), (C.c_float * 4)(*(float(x) for x in quat)),
+                                  f3(scale), f3(pivot), 0)
+        count = C.c_uint64()
+        _lib.check(self._v._L.gsx_model_apply_transform(self._v._h, self._key.encode(), C.byref(desc), C.byref(count)))
+        return int(count.value)
+
     def property_values(self, prop: int, world: bool = False) -> np.ndarray:
         """``gsx_model_property_values``: the property ``prop`` (``_lib.GSX_PROP_*``) of every Gaussian as float32, computed on the
         device from the stored values (edits are not applied): the stored position (``world``: with the model transform applied as
