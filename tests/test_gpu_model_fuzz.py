@@ -1,0 +1,453 @@
+"""GPU: the device-side model operations against one another and against the frame pipeline's cached state, over long sessions.
+
+Two viewers per seed, in lock-step.  `live`: speculation on, several slabs, 1 to 3 frames in flight, slab shading and the edit cache
+on; every operation goes to it through the Python mirror.  `rebuilt`: speculative = 0, progressive = 0, one lane, GSX_NO_EDIT_CACHE; it
+never receives a model operation: after every step that changes a model the affected models are dropped and created again from the
+host shadow (tests/model_shadow.py) with convert_ref.upload_pod in the shadow's kind, then given the mask, selection, edit records,
+transform and show-unedited.  Every step renders one frame on both with the same camera, viewport, display state and painter's order:
+the two framebuffers (and the RGBA8 resolves, which show the gizmos and lines) must be the same bytes.  After each operation the
+counts, words, rows and positions the shadow knows are asserted; tests/model_shadow.py's docstring lists what it adopts from the
+device instead.  A failure's message names the seed, the step and the ops so far with their drawn parameters.
+
+Conditions that keep this from passing vacuously, asserted by test_conditions_over_the_seed_set: (a) every op kind ran; (b) every
+select variant had a hit set neither empty nor full; (c) every op kind that changes a model was followed, before the next such op, by
+a speculated frame of a model it changed; (d) model-changing ops ran with two frames enqueued and not waited for.  The run of camera
+steps after a model-changing op is model_shadow.POST_OP_RUN = 5: a changed model's first frame on each of up to three lanes is
+unspeculated, the fourth and fifth speculate.
+
+Cost, measured on an MI355X: a seed takes 0.4 to 0.75 s, of which 0.10 to 0.22 s are the hundred frames of both viewers (a seed of
+test_gpu_speculation.py::test_fuzz_operation_sequences, which has no host reference, takes 0.08 to 0.15 s); the rest is the host's
+brute-force restatements and the downloads.  That is why a seed has only two ops beyond its walk through the kinds, and why the
+spatial ops draw a model of at most model_shadow.SPATIAL_N Gaussians when there is one."""
+import os
+import time
+import types
+
+import numpy as np
+import pytest
+
+from tests import bounds_ref as B
+from tests import clusters_ref as CL
+from tests import common
+from tests import convert_ref as CV
+from tests import extract_ref as X
+from tests import knn_ref as K
+from tests import model_shadow as S
+from tests import neighbors_ref as N
+from tests import property_ref as P
+from tests.test_gpu_depth_test import ndc_of
+from wgpu_3dgs_viewer_app_amd import camera, mask as mask_mod, parallel, query
+from wgpu_3dgs_viewer_app_amd.mask import MaskEvaluator, MaskOp
+from wgpu_3dgs_viewer_app_amd.ply import Gaussians
+from wgpu_3dgs_viewer_app_amd.viewer import Cov3dKind, DepthCompare, GaussianDisplayMode, GaussianShDegree, HitPair, MultiModelViewer, ShKind
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+SEEDS = [int(x) for x in os.environ.get("GSX_MODEL_FUZZ_SEEDS", ",".join(str(s) for s in S.DEFAULT_SEEDS)).split(",")]
+MODES = [GaussianDisplayMode.Splat, GaussianDisplayMode.Ellipse, GaussianDisplayMode.Point]
+LINES = np.concatenate([HitPair((-1.5, 0.0, 0.0), (1.5, 0.6, 0.0), (255, 40, 40, 255), 30.0), HitPair((0.0, -1.0, -1.0), (0.3, 1.0, 1.0), (40, 255, 40, 200), 20.0)])
+#: what the seeds of this run saw, for the conditions over the seed set
+SEEN = dict(seeds=[], ran={}, nontrivial=set(), speculated_after=set(), in_flight_ops=0)
+
+
+def _kind(k):
+    return ShKind(k[0]), Cov3dKind(k[1])
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+def _same_f32(a, b, what):
+    assert np.asarray(a).shape == np.asarray(b).shape and _bits(a).tobytes() == _bits(b).tobytes(), what
+
+
+def _depth(size):
+    """a cleared depth buffer with a rectangle at view depth 5.5 in its middle: in front of part of every scene here"""
+    w, h = size
+    d = np.ones((h, w), F)
+    d[h // 4: (3 * h) // 4, w // 3: (2 * w) // 3] = ndc_of(camera.orbit_pose(0).projection(w / h), 5.5)
+    return d
+
+
+class Device:
+    """the two viewers of a seed, and what model_shadow.Session asks of them"""
+
+    def __init__(self, session, monkeypatch):
+        self.s = session
+        sh, cov = _kind(session.kind)
+        self.live = MultiModelViewer(sh=sh, cov3d=cov)
+        self.live.set_render_options(speculative=1, min_slab=512, frames_in_flight=session.lanes, host_verify=session.host_verify)
+        monkeypatch.setenv("GSX_NO_EDIT_CACHE", "1")
+        self.rebuilt = MultiModelViewer(sh=sh, cov3d=cov)
+        monkeypatch.delenv("GSX_NO_EDIT_CACHE")
+        self.rebuilt.set_render_options(speculative=0, progressive=0, frames_in_flight=1)
+        self.speculated, self.frame_s = 0, 0.0
+        self.watch = None  # (op kind, the keys it changed) until a speculated frame of one of them, or the next model-changing op
+
+    def close(self):
+        self.live.close()
+        self.rebuilt.close()
+
+    def both(self, fn):
+        for v in (self.live, self.rebuilt):
+            fn(v)
+
+    # ---- models ----
+    def new_model(self, key, g, mt):
+        self.live.add_model(key, g.shape[0])
+        self.live.models[key].gaussian_buffers.gaussians_buffer.update_range(0, g)
+        self.live.update_model_transform(key, *mt)
+
+    def pod_live(self, key):
+        assert CV.pod_kind(self.live, key) == _kind(self.s.shadow.models[key].kind), key
+        return CV.pod(self.live, key)
+
+    def pod_rebuilt(self, key):
+        return CV.pod(self.rebuilt, key)
+
+    def remove(self, keys):
+        for k in keys:
+            self.live.remove_model(k)
+            if k in self.rebuilt.models:
+                self.rebuilt.remove_model(k)
+
+    def rebuild(self, removed, changed):
+        v = self.rebuilt
+        for k in removed:
+            if k in v.models:
+                v.remove_model(k)
+        for k in changed:
+            m = self.s.shadow.models[k]
+            if k in v.models:
+                v.remove_model(k)
+            CV.upload_pod(v, k, m.planes, kind=_kind(m.kind))
+            bufs = v.models[k].gaussian_buffers
+            if m.mask is not None:
+                bufs.mask_buffer.upload(X.words(m.mask))
+            if m.sel is not None:
+                bufs.selection_buffer.upload(X.words(m.sel))
+            if m.edits is not None:
+                bufs.gaussians_edit_buffer.upload(m.edits)
+            v.update_model_transform(k, *m.mt)
+            v.show_unedited(k, m.unedited)
+
+    def check_state(self, key, m):
+        """what an op carries or must leave alone, as the live viewer holds it"""
+        bufs = self.live.models[key].gaussian_buffers
+        assert CV.model_len(self.live, key) == m.n
+        assert np.array_equal(X.bits(bufs.selection_buffer.download(), m.n), m.selection()), (key, "selection")
+        want = query.default_edits(m.n) if m.edits is None else m.edits
+        assert bufs.gaussians_edit_buffer.download().tobytes() == want.tobytes(), (key, "edit records")
+        if m.mask is not None:
+            assert np.array_equal(X.bits(bufs.mask_buffer.download(), m.n), m.mask), (key, "mask")
+
+    def check_pivot(self, key, pivot):
+        got = self.live.models[key].bounds(selected=True).center
+        _same_f32(got, pivot, "bounds(selected).center")
+
+    def ply_roundtrip(self, key, dst, n):
+        data = self.live.models[key].export_ply()
+        assert self.live.import_ply(dst, data) == n
+
+    # ---- frames ----
+    def _uniforms(self, v, pose):
+        view = self.s.view
+        v.update_camera(camera.orbit_pose(pose), view.size)
+        v.update_gaussian_transform(view.gsize, MODES[view.mode], GaussianShDegree.new(view.deg), False)
+
+    def _order(self, pose):
+        alive = self.s.keys()
+        shown = [k for k in alive if k not in self.s.view.hidden] or alive
+        return parallel.model_render_keys(camera.orbit_pose(pose).pos, {k: types.SimpleNamespace(pos=self.s.shadow.models[k].mt[0]) for k in shown})
+
+    def enqueue_frames(self, count):
+        """frames of the live viewer alone, enqueued and not waited for, in front of the op that follows (a frame writes nothing but
+        the selection edit it persists, which the step's own frame has written already)"""
+        for j in range(1, count + 1):
+            pose = (self.s.view.pose + j) % 240
+            self._uniforms(self.live, pose)
+            self.live.update_query(query.QueryPod.none())
+            self.live.render_frame(self._order(pose))
+
+    def frame(self):
+        t0 = time.perf_counter()
+        try:
+            return self._frame()
+        finally:
+            self.frame_s += time.perf_counter() - t0
+
+    def _frame(self):
+        s, view = self.s, self.s.view
+        keys = self._order(view.pose)
+        q = query.QueryPod.none() if view.rect is None else query.QueryPod.rect(view.rect["p0"], view.rect["p1"], query.QuerySelectionOp(view.rect["op"]))
+        out = []
+        for v in (self.live, self.rebuilt):
+            self._uniforms(v, view.pose)
+            v.update_query(q)
+            v.render_frame(keys)
+            for k in keys:
+                v.postprocessor.postprocess(k)
+            v.poll()
+            out.append((v.download_framebuffer(), v.download_rgba8()))
+        assert np.array_equal(out[0][0], out[1][0]), f"framebuffers differ, L-inf {np.abs(out[0][0] - out[1][0]).max()}, keys {keys}"
+        assert np.array_equal(out[0][1], out[1][1]), f"RGBA8 resolves differ, keys {keys}"
+        # what the frame itself wrote: the selection of a rectangle query, the stored edits of a selection edit that persists
+        for k in keys:
+            m = s.shadow.models[k]
+            a, b = (v.models[k].gaussian_buffers for v in (self.live, self.rebuilt))
+            if view.rect is not None:
+                words = a.selection_buffer.download()
+                assert np.array_equal(X.bits(words, m.n), X.bits(b.selection_buffer.download(), m.n)), (k, "selections differ")
+                m.sel = X.bits(words, m.n)
+            if view.sel_edit_on:
+                edits = a.gaussians_edit_buffer.download()
+                assert edits.tobytes() == b.gaussians_edit_buffer.download().tobytes(), (k, "stored edits differ")
+                m.edits = edits if (edits["flag"] != 0).any() or m.edits is not None else None
+        stats = {k: self.live.frame_stats(k)["speculated"] for k in keys}
+        self.speculated += any(stats.values())
+        if self.watch is not None and any(stats.get(k) for k in self.watch[1]):
+            SEEN["speculated_after"].add(self.watch[0])
+            self.watch = None
+        return out[0][0]
+
+    # ---- ops that both viewers get as they are ----
+    def state_op(self, op):
+        kind, view = op["kind"], self.s.view
+        if kind == "viewport" and view.depth:
+            self.both(lambda v: v.update_depth_buffer(_depth(view.size)))
+        elif kind == "model_transform":
+            self.both(lambda v: v.update_model_transform(op["key"], *op["mt"]))
+        elif kind == "mask_eval":
+            key, m = op["key"], self.s.shadow.models[op["key"]]
+            MaskEvaluator(self.live).evaluate(MaskOp.parse(op["expr"]) if op["expr"] else None, key, self.s.shapes)
+            if m.mask is not None:
+                assert np.array_equal(X.bits(self.live.models[key].gaussian_buffers.mask_buffer.download(), m.n), m.mask), "mask bits"
+            self.rebuilt.models[key].gaussian_buffers.mask_buffer.upload(None if m.mask is None else X.words(m.mask))
+        elif kind == "sel_upload":
+            m = self.s.shadow.models[op["key"]]
+            self.both(lambda v: v.models[op["key"]].gaussian_buffers.selection_buffer.upload(None if m.sel is None else X.words(m.sel, True)))
+        elif kind == "sel_edit":
+            pod = query.GaussianEditPod(op["flag"], tuple(op["color"]), op["contrast"], op["exposure"], op["gamma"], op["alpha"])
+            self.both(lambda v: (v.update_selection_edit_with_pod(pod), v.update_selection_highlight((1.0, 0.0, 1.0, op["highlight"]))))
+        elif kind == "edits_upload":
+            m = self.s.shadow.models[op["key"]]
+            raw = None if op["rseed"] is None else S.random_edits(m.n, op["rseed"])  # (as drawn: the library normalises them itself)
+            self.both(lambda v: v.models[op["key"]].gaussian_buffers.gaussians_edit_buffer.upload(raw))
+            self.check_state(op["key"], m)
+        elif kind == "unedited":
+            self.both(lambda v: v.show_unedited(op["key"], op["on"]))
+        elif kind == "depth_test":
+            self.both(lambda v: (v.set_depth_test(DepthCompare.Less), v.update_depth_buffer(_depth(view.size))) if op["on"] else v.set_depth_test(DepthCompare.Always))
+        elif kind == "hit_pairs":
+            self.both(lambda v: v.update_hit_pairs(LINES if op["on"] else None))
+        elif kind == "gizmos":
+            self.both(lambda v: v.set_mask_gizmos(mask_mod.gizmo_records([self.s.shapes], 20.0) if op["on"] else None))
+
+    # ---- selects ----
+    def upload_selection(self, key, bits):
+        self.both(lambda v: v.models[key].gaussian_buffers.selection_buffer.upload(X.words(bits)))
+
+    def select(self, op):
+        model, kind = self.live.models[op["key"]], op["kind"]
+        a = dict(op=op["op"], filter=op["flt"])
+        if kind == "select_range":
+            return model.select_range(op["prop"], op["lo"], op["hi"], world=op["world"], **a)
+        if kind == "select_neighbors":
+            return model.select_neighbors(op["r"], op["lo"], op["hi"], **a)
+        if kind == "select_clusters":
+            return model.select_clusters(op["r"], op["mode"], op["size_lo"], op["size_hi"], **a)
+        hit, selected, st = model.select_knn(op["k"], op["score"], op["lo"], op["hi"], op["std_ratio"], **a)
+        if op["std_ratio"] is not None:  # the threshold within one unit in the last place of the restatement's (tests/test_gpu_knn.py)
+            part, _, s = self.s.shadow.knn_scores(op["key"], op["k"], op["score"], op["flt"])
+            ks = K.stats(np.where(part, s, K.INF))
+            assert abs(int(_bits(st.threshold)[0]) - int(_bits(K.threshold(ks["mean"], ks["std"], op["std_ratio"]))[0])) <= 1
+        return hit, selected, st.threshold
+
+    def check_selection(self, key, bits):
+        assert np.array_equal(X.bits(self.live.models[key].gaussian_buffers.selection_buffer.download(), bits.size), bits), "selection bits"
+        self.rebuilt.models[key].gaussian_buffers.selection_buffer.upload(X.words(bits))
+
+    # ---- read-only calls ----
+    def read_only(self, op, m):
+        read_only_call(self.live.models[op["key"]], m, op)
+
+
+def read_only_call(model, m, op):
+    """one read-only call of the model against the restatement over the shadow model `m`"""
+    kind, flt = op["kind"], op["flt"]
+    passes, part = m.passes(flt), m.part(flt)
+    if kind == "bounds":
+        got = model.bounds(masked=bool(flt & X.MASKED), skip_hidden=bool(flt & X.SKIP_HIDDEN), selected=bool(flt & X.SELECTED), trim_permille=op["trim"])
+        want = B.reference(m.pos, passes)
+        assert (got.count, got.n_nonfinite) == (want["count"], want["n_nonfinite"])
+        for name in ("min", "max", "center"):
+            _same_f32(getattr(got, name), want[name], ("bounds", name))
+    elif kind == "histogram":
+        vals = m.values(op["prop"], op["world"])
+        lo, hi = (None, None) if op["auto"] else np.quantile(vals[passes & P.finite(vals)], [0.1, 0.9]).astype(F)
+        got = model.histogram(op["prop"], op["bins"], lo, hi, filter=flt, world=op["world"])
+        want = P.histogram(vals, passes, op["bins"], lo, hi)
+        assert np.array_equal(got.bins, want["bins"])
+        assert (got.count, got.below, got.above, got.n_nonfinite) == (want["count"], want["below"], want["above"], want["n_nonfinite"])
+        for name in ("lo", "hi", "min", "max"):
+            _same_f32(getattr(got, name), want[name], ("histogram", name))
+    elif kind == "property_values":
+        _same_f32(model.property_values(op["prop"], op["world"]), m.values(op["prop"], op["world"]), "property_values")
+    elif kind == "neighbors":
+        got = model.neighbors(op["r"], filter=flt)
+        counts = N.brute(m.pos, part, op["r"])
+        assert np.array_equal(got.counts, counts) and np.array_equal(got.hist, N.hist(counts, part)) and got.count == int(part.sum())
+    elif kind == "clusters":
+        got = model.clusters(op["r"], filter=flt)
+        want = CL.clusters(m.pos, part, op["r"])
+        assert np.array_equal(got.labels, want.labels) and np.array_equal(got.sizes, want.sizes)
+        assert (got.count, got.n_clusters, got.largest_size, got.largest_label) == (want.count, want.n_clusters, want.largest_size, want.largest_label)
+    elif kind == "knn":
+        got = model.knn(op["k"], op["score"], filter=flt, rows=True)
+        rows = S.memo(K.brute, m.pos, part, op["k"])
+        score = K.score(rows, op["score"])
+        st = K.stats(np.where(part, score, K.INF))
+        _same_f32(got.d2, rows, "knn rows")
+        _same_f32(got.score, score, "knn scores")
+        assert (got.count, got.n_scored) == (int(part.sum()), st["n_scored"])
+        _same_f32(got.score_min, st["score_min"], "score_min")
+        _same_f32(got.score_max, st["score_max"], "score_max")
+    else:
+        idx = m.kept(flt, op["invert"])
+        g = model.export(flt, op["invert"]).gaussians if kind == "export" else Gaussians.read_ply(model.export_ply(flt, op["invert"])).gaussians
+        assert g.shape[0] == idx.size
+        assert g["pos"].tobytes() == np.ascontiguousarray(m.pos[idx]).tobytes(), (kind, "pos")
+        if kind == "export":
+            assert np.array_equal(g["color"].view(np.uint32).reshape(-1), m.color[idx]), (kind, "color")
+            assert g["sh"].reshape(-1, 45).tobytes() == np.ascontiguousarray(m.planes[2][idx]).tobytes(), (kind, "sh")
+
+
+# ---- 1. the lock-step fuzz ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", SEEDS)
+def test_fuzz_model_operations(seed, monkeypatch):
+    t0 = time.perf_counter()
+    s = S.Session(seed)
+    dev = Device(s, monkeypatch)
+    step = -1
+    try:
+        s.load_start(dev)
+        for step, kind in enumerate(S.plan(seed)):
+            op = {"kind": "cam_step"} if kind == "cam_step" else s.draw(kind)
+            changed = s.apply(op, dev)
+            if kind in S.MODEL_CHANGING:
+                dev.watch = (kind, changed)
+                SEEN["in_flight_ops"] += s.lanes > 1 and op.get("inflight", 0) >= 2
+            dev.frame()
+    except Exception as e:
+        raise AssertionError(f"{type(e).__name__}: {e}\n  at step {step} of {s.replay()}") from e
+    finally:
+        dev.close()
+    SEEN["seeds"].append(seed)
+    for k, c in s.ran.items():
+        SEEN["ran"][k] = SEEN["ran"].get(k, 0) + c
+    SEEN["nontrivial"] |= s.nontrivial
+    print(f"seed {seed}: lanes {s.lanes}, host_verify {s.host_verify}, kind {_kind(s.kind)}, {step + 1} frames, {dev.speculated} speculated, "
+          f"{time.perf_counter() - t0:.2f} s of which {dev.frame_s:.2f} s in the frames of both viewers, ops {dict(sorted(s.ran.items()))}")
+    assert dev.speculated > 0
+
+
+def test_conditions_over_the_seed_set():
+    """(a) to (d) of the module docstring, over the default seed set, which test_fuzz_model_operations ran before this.  A replay of
+    other seeds through GSX_MODEL_FUZZ_SEEDS has no such set to answer for."""
+    if set(SEEDS) != set(S.DEFAULT_SEEDS):
+        pytest.skip("GSX_MODEL_FUZZ_SEEDS names other seeds than the default set the conditions are stated over")
+    unfinished = sorted(set(S.DEFAULT_SEEDS) - set(SEEN["seeds"]))
+    assert not unfinished, f"seeds that did not pass before this test (it is run with the whole file): {unfinished}"
+    missing = [k for k in S.OP_KINDS if k != "cam_step" and not SEEN["ran"].get(k)]
+    assert not missing, f"(a) op kinds that never ran: {missing}"
+    trivial = [k for k in S.SELECT_VARIANTS if k not in SEEN["nontrivial"]]
+    assert not trivial, f"(b) selects that never selected something and not everything: {trivial}"
+    cold = [k for k in S.MODEL_CHANGING if k not in SEEN["speculated_after"]]
+    assert not cold, f"(c) model-changing ops never followed by a speculated frame of the changed model: {cold}"
+    assert SEEN["in_flight_ops"] > 0, "(d) no op ran with two frames enqueued and not waited for"
+
+
+# ---- 2. directed ------------------------------------------------------------------------------------------------------------------------
+def _two_lanes(**kw):
+    v = MultiModelViewer(**kw)
+    v.set_render_options(speculative=1, min_slab=512, frames_in_flight=2)
+    return v
+
+
+def _enqueue(v, pose, keys):
+    v.update_camera(camera.orbit_pose(pose), (S.W, S.H))
+    v.update_gaussian_transform(1.0, GaussianDisplayMode.Splat, GaussianShDegree.new(3), False)
+    v.render_frame(keys)
+
+
+def test_read_only_calls_between_frames_in_flight():
+    """Two identical viewers with two lanes.  One enqueues two frames (one per lane), makes a read-only call, two frames, the next
+    call ... through all eight, with no host wait but the call's own; its twin only renders.  Every frame of both lanes is the
+    twin's, and every answer is the restatement's."""
+    n = 3000
+    g = common.small_scene(n, 91)
+    rng = np.random.default_rng(91)
+    shadow = S.Shadow()
+    with _two_lanes() as v, _two_lanes() as twin:
+        for vv in (v, twin):
+            vv.add_model("m", n)
+            vv.models["m"].gaussian_buffers.gaussians_buffer.update_range(0, g)
+        m = shadow.add("m", S.SINGLE, CV.pod(v, "m"))
+        m.mask, m.sel, m.edits = rng.random(n) < 0.8, rng.random(n) < 0.4, S.normalise_edits(S.random_edits(n, 91))
+        for vv in (v, twin):
+            bufs = vv.models["m"].gaussian_buffers
+            bufs.mask_buffer.upload(X.words(m.mask, True))
+            bufs.selection_buffer.upload(X.words(m.sel, True))
+            bufs.gaussians_edit_buffer.upload(m.edits)
+        r = float(F(K.kth_distance_median(m.pos, m.part(0), 2)))
+        flt = X.MASKED | X.SKIP_HIDDEN
+        calls = [dict(kind="bounds", flt=flt, trim=50), dict(kind="histogram", flt=flt, prop=P.HUE, bins=64, world=False, auto=True),
+                 dict(kind="property_values", flt=0, prop=P.POS_Y, world=True), dict(kind="neighbors", flt=flt, r=r), dict(kind="clusters", flt=X.SELECTED, r=r),
+                 dict(kind="knn", flt=flt, k=3, score=K.SCORE_MEAN), dict(kind="export", flt=X.SELECTED, invert=True), dict(kind="export_ply", flt=flt, invert=False)]
+        assert [c["kind"] for c in calls] == list(S.READ_ONLY)
+        speculated = 0
+        for k, call in enumerate(calls):
+            poses = (10 + 2 * k, 11 + 2 * k)
+            for pose in poses:
+                _enqueue(v, pose, ["m"])
+            read_only_call(v.models["m"], m, call)
+            got = [v.debug_download_lane_framebuffer(lane) for lane in (0, 1)]
+            want = []
+            for pose in poses:
+                _enqueue(twin, pose, ["m"])
+                want.append(twin.download_framebuffer())
+            assert want[0][..., :3].max() > 0 and not np.array_equal(want[0], want[1])
+            assert any(all(np.array_equal(got[a], want[b]) for a, b in zip((0, 1), order)) for order in ((0, 1), (1, 0))), (k, call["kind"])
+            v.poll()
+            speculated += v.frame_stats("m")["speculated"]
+        assert speculated >= 6
+
+
+def test_a_key_removed_and_reused():
+    """Frames in flight on two lanes, remove_model("m"), a model of another length under the same key, another pod kind: every frame
+    that follows is a fresh viewer's (nothing derived from the first "m" survives: windows, shade records, a lane's shadow model)."""
+    n, other_n = 3000, 1700
+    to = (ShKind.Norm8, Cov3dKind.Half)
+    with _two_lanes() as v, MultiModelViewer() as fresh:
+        v.add_model("m", n)
+        v.models["m"].gaussian_buffers.gaussians_buffer.update_range(0, common.small_scene(n, 92))
+        for pose in (5, 6, 7, 8):  # enqueued, not waited for
+            _enqueue(v, pose, ["m"])
+        v.remove_model("m")
+        v.add_model("m", other_n)
+        v.models["m"].gaussian_buffers.gaussians_buffer.update_range(0, common.small_scene(other_n, 93))
+        _enqueue(v, 9, ["m"])  # a frame of the new model in its first kind, in flight under the conversion
+        v.models["m"].set_pod_kind(*to)
+        held = CV.pod(v, "m")
+        CV.upload_pod(fresh, "m", held, kind=to)
+        CV.same_bytes(CV.pod(fresh, "m"), held)
+        speculated = 0
+        for k, pose in enumerate((10, 11, 12, 13, 14, 15)):
+            _enqueue(v, pose, ["m"])
+            a = v.download_framebuffer()
+            _enqueue(fresh, pose, ["m"])
+            b = fresh.download_framebuffer()
+            assert b[..., :3].max() > 0 and np.array_equal(a, b), (k, float(np.abs(a - b).max()))
+            speculated += v.frame_stats("m")["speculated"]
+        assert speculated >= 3
