@@ -797,6 +797,48 @@ typedef struct gsx_transform_desc {
 void gsx_transform_desc_default(gsx_transform_desc* d); /* no filter, no flags, pos 0, quat (0, 0, 0, 1), scale 1, pivot 0 */
 gsx_status gsx_model_apply_transform(gsx_viewer* v, const char* key, const gsx_transform_desc* desc, uint64_t* out_count /* nullable */);
 
+/* ---- model decimate: reduce a resident model's Gaussian count on the device (spec/RENDER_SPEC.md §22 [BUILD-SPEC]).  The
+ *      Gaussians that share a cell of a uniform grid of edge desc->cell become ONE moment-matched Gaussian of a new model: 10 M down
+ *      to 1 M for a web export, a coarse stand-in for a far model, a merged scene whose overlap holds everything twice.  No Gaussian
+ *      crosses to the host.
+ *      Participants: a Gaussian participates if it passes desc->filter / desc->flags (GSX_BOUNDS_* bits and GSX_EXTRACT_INVERT,
+ *      gsx_model_extract's meaning word for word: no mask = all pass, no selection = none pass, tail bits never count) and its three
+ *      stored coordinates are finite; stats.count is their number, stats.n_nonfinite the kept Gaussians with a NaN or infinite
+ *      coordinate, which are dropped.
+ *      Cells: gsx_model_neighbors' grid with the edge given: origin = the participants' minimum per axis, inv_h = 1 / cell in float32,
+ *      a coordinate's cell min(floor((x - origin) * inv_h), 32767) in float32: cells beyond 32767 on an axis are joined.
+ *      dst: one Gaussian per occupied cell.  A cell's representative is its member with the smallest index; dst holds the cells in
+ *      ascending order of representative.  stats.cells = dst's length, stats.singletons the one-member cells, stats.largest_cell the
+ *      largest member count.  out_map[i] (nullable; the model's length) = the dst index Gaussian i went into, 0xFFFFFFFF if it does not
+ *      participate.  A one-member cell is copied as stored bits (a cell so small that every cell has one member IS gsx_model_extract of
+ *      the participants with GSX_EXTRACT_DROP_EDITS).  A cell of two members and more: mean and covariance of the mixture weighted by
+ *      alpha * sqrt(det Sigma) (weight 1 for every member when that sum is not positive and finite), opacity conserving that mass
+ *      (at most 1), colour and SH the weighted means; float32, members in ascending index, quantised once into src's pod kind; the
+ *      same bits on every call.  dst has src's pod kind and model transform, no mask, no selection and no edit records (members'
+ *      edits cannot be averaged: exclude hidden Gaussians with GSX_BOUNDS_SKIP_HIDDEN).  src is not written.
+ *      dst_key NULL: count only: stats and out_map are filled, no model is made.  No participants: GSX_OK, cells 0, no model.
+ *      grid_bits: gsx_model_neighbors'.  Ordering: gsx_model_extract's; the call waits once, for the cell count.
+ *      gsx_model_decimate_edge: an edge for a target count, by 20 count-only bisection steps on log2(edge) between extent / 32767 and
+ *      extent * (1 + 2^-5) (one cell), extent the participants' largest axis extent: *out_cell = the smallest probed edge with at most
+ *      target_cells cells, *out_cells that count (the count is not strictly monotone in the edge: only this rule is promised).  An
+ *      extent of 0: edge 1, one cell.  No participants: edge 0, 0 cells.
+ *      Cost at coarse edges: a bucket of more than 2048 records is ordered by ONE workgroup and a cell is reduced by ONE wave, members
+ *      in order, so the time grows with the largest cell: 10 M Gaussians into about 1 k cells take 44 to 50 ms, and an edge that puts a
+ *      model of millions into one or a few cells runs for seconds inside a single kernel (it is not a hang, and it is not measured).
+ *      gsx_model_decimate_edge with a target of a few cells on a large model converges towards such edges and repeats that count up to
+ *      20 times: for tiny targets choose the edge from gsx_model_bounds instead.
+ *      Errors: a null viewer, src_key / key, desc or out pointer, unknown filter bits, a flag other than GSX_EXTRACT_INVERT, a cell
+ *      that is not finite and above 0 or whose float32 reciprocal is 0 or inf, grid_bits > 24, a reserved word != 0, a dst_key that
+ *      exists or equals src_key, target_cells 0: GSX_ERR_INVALID_ARG; unknown src: GSX_ERR_NOT_FOUND; a viewer with a communicator,
+ *      or a sharded model: GSX_ERR_UNSUPPORTED; an allocation failure: GSX_ERR_OOM, no dst left behind. ---- */
+typedef struct gsx_decimate_desc { uint32_t filter; uint32_t flags; float cell; uint32_t grid_bits; uint32_t reserved[2]; } gsx_decimate_desc; /* 24 B */
+typedef struct gsx_decimate_stats_t { uint64_t count; uint64_t n_nonfinite; uint64_t cells; uint64_t singletons; uint32_t largest_cell; uint32_t grid_bits; } gsx_decimate_stats_t; /* 40 B */
+void gsx_decimate_desc_default(gsx_decimate_desc* d); /* filter 0, flags 0, cell 0 (must be set), grid_bits 0 = the library's */
+gsx_status gsx_model_decimate(gsx_viewer* v, const char* src_key, const char* dst_key /* NULL: count only */, const gsx_decimate_desc* desc,
+                              uint32_t* out_map /* nullable, n words */, gsx_decimate_stats_t* out);
+gsx_status gsx_model_decimate_edge(gsx_viewer* v, const char* key, uint32_t filter, uint32_t flags, uint64_t target_cells,
+                                   float* out_cell, uint64_t* out_cells);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

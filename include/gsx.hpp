@@ -214,6 +214,26 @@ struct MultiModelViewerModel {
         check(gsx_model_apply_transform(v_, key_.c_str(), &desc, &count));
         return count;
     }
+    // gsx_model_decimate without a destination: how a grid of edge desc.cell would divide the model: the statistics, and in map (the
+    // model's length) the cell every Gaussian would go into (0xFFFFFFFF: it does not participate).  Nothing is created.
+    gsx_decimate_stats_t decimate_count(const gsx_decimate_desc& desc, std::vector<uint32_t>* map = nullptr) const {
+        if (map) {
+            uint64_t n = 0;
+            check(gsx_model_len(v_, key_.c_str(), &n));
+            map->assign((size_t)n, 0xFFFFFFFFu);
+        }
+        gsx_decimate_stats_t out{};
+        check(gsx_model_decimate(v_, key_.c_str(), nullptr, &desc, map ? map->data() : nullptr, &out));
+        return out;
+    }
+    // gsx_model_decimate_edge: the smallest probed cell edge that leaves at most target_cells cells, by count-only bisection on the
+    // device.  Returns {edge, cells}.
+    std::pair<float, uint64_t> decimate_edge(uint64_t target_cells, uint32_t filter = 0, uint32_t flags = 0) const {
+        float cell = 0.0f;
+        uint64_t cells = 0;
+        check(gsx_model_decimate_edge(v_, key_.c_str(), filter, flags, target_cells, &cell, &cells));
+        return {cell, cells};
+    }
     // gsx_model_property_values: one float32 per Gaussian, computed on the device from the stored values (edits are not applied): the
     // stored position (flags = GSX_PROP_WORLD: the model transform applied as merge bakes it), the bytes of the colour word / 255, their
     // HSV, or the scales export solves from the covariance.
@@ -383,6 +403,22 @@ public:
             models.emplace(dst_key, MultiModelViewerModel{{GaussiansBuffer(v_, dst_key), MaskBuffer(v_, dst_key), SelectionBuffer(v_, dst_key),
                                                            GaussiansEditBuffer(v_, dst_key)}, v_, dst_key});
         return count;
+    }
+    // gsx_model_decimate: the Gaussians of src_key that share a cell of a grid of edge desc.cell become one moment-matched Gaussian
+    // of the new model dst_key, on the device (one-member cells are copied as stored bits).  map (nullable) receives the dst index
+    // of every source Gaussian.  Returns the statistics; cells == 0 creates no model.
+    gsx_decimate_stats_t decimate(const std::string& src_key, const std::string& dst_key, const gsx_decimate_desc& desc, std::vector<uint32_t>* map = nullptr) {
+        if (map) {
+            uint64_t n = 0;
+            check(gsx_model_len(v_, src_key.c_str(), &n));
+            map->assign((size_t)n, 0xFFFFFFFFu);
+        }
+        gsx_decimate_stats_t out{};
+        check(gsx_model_decimate(v_, src_key.c_str(), dst_key.c_str(), &desc, map ? map->data() : nullptr, &out));
+        if (out.cells)
+            models.emplace(dst_key, MultiModelViewerModel{{GaussiansBuffer(v_, dst_key), MaskBuffer(v_, dst_key), SelectionBuffer(v_, dst_key),
+                                                           GaussiansEditBuffer(v_, dst_key)}, v_, dst_key});
+        return out;
     }
     // gsx_model_convert: extract into a model of the pod kind (sh, cov3d): position and colour word carried, covariance and SH
     // dequantised exactly and quantised once into the new kind, on the device.  The same kind is extract.  Returns the number kept; 0

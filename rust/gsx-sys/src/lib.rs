@@ -227,6 +227,16 @@ pub struct gsx_knn_select_desc {
 pub struct gsx_transform_desc {
     pub filter: u32, pub flags: u32, pub pos: [f32; 3], pub quat: [f32; 4], pub scale: [f32; 3], pub pivot: [f32; 3], pub reserved: u32,
 }
+/// gsx_model_decimate, 24 bytes: the GSX_BOUNDS_* filter, flags (GSX_EXTRACT_INVERT), the cell edge (model space; must be set),
+/// grid_bits (0: the library's hash table; 1..=24 forces 2^grid_bits buckets, no result changes), reserved (0)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_decimate_desc { pub filter: u32, pub flags: u32, pub cell: f32, pub grid_bits: u32, pub reserved: [u32; 2] }
+/// the result of gsx_model_decimate, 40 bytes: participants, kept Gaussians with a NaN / inf coordinate (dropped), occupied cells (the
+/// new model's length), one-member cells, the largest member count, the table used
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_decimate_stats_t { pub count: u64, pub n_nonfinite: u64, pub cells: u64, pub singletons: u64, pub largest_cell: u32, pub grid_bits: u32 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }
@@ -368,6 +378,9 @@ extern "C" {
     pub fn gsx_model_select_knn(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_knn_select_desc, out_hit: *mut u64, out_selected: *mut u64, out_stats: *mut gsx_knn_stats_t) -> gsx_status;
     pub fn gsx_transform_desc_default(d: *mut gsx_transform_desc);
     pub fn gsx_model_apply_transform(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_transform_desc, out_count: *mut u64) -> gsx_status;
+    pub fn gsx_decimate_desc_default(d: *mut gsx_decimate_desc);
+    pub fn gsx_model_decimate(v: *mut gsx_viewer, src_key: *const c_char, dst_key: *const c_char, desc: *const gsx_decimate_desc, out_map: *mut u32, out: *mut gsx_decimate_stats_t) -> gsx_status;
+    pub fn gsx_model_decimate_edge(v: *mut gsx_viewer, key: *const c_char, filter: u32, flags: u32, target_cells: u64, out_cell: *mut f32, out_cells: *mut u64) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

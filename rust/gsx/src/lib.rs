@@ -190,6 +190,23 @@ impl MultiModelViewerModel {
         check(unsafe { sys::gsx_model_apply_transform(self.v, self.key.as_ptr(), desc, &mut count) })?;
         Ok(count)
     }
+    /// `gsx_model_decimate` without a destination: how a grid of edge `desc.cell` would divide the model.  Returns the statistics
+    /// and the cell every Gaussian would go into (`0xFFFF_FFFF`: it does not participate).  Nothing is created.
+    pub fn decimate_count(&self, desc: &sys::gsx_decimate_desc) -> Result<(sys::gsx_decimate_stats_t, Vec<u32>), Error> {
+        let mut n = 0u64;
+        check(unsafe { sys::gsx_model_len(self.v, self.key.as_ptr(), &mut n) })?;
+        let mut map = vec![u32::MAX; n as usize];
+        let mut out = sys::gsx_decimate_stats_t::default();
+        check(unsafe { sys::gsx_model_decimate(self.v, self.key.as_ptr(), std::ptr::null(), desc, map.as_mut_ptr(), &mut out) })?;
+        Ok((out, map))
+    }
+    /// `gsx_model_decimate_edge`: the smallest probed cell edge that leaves at most `target_cells` cells, by count-only bisection on
+    /// the device.  Returns `(edge, cells)`.
+    pub fn decimate_edge(&self, target_cells: u64, filter: u32, flags: u32) -> Result<(f32, u64), Error> {
+        let (mut cell, mut cells) = (0f32, 0u64);
+        check(unsafe { sys::gsx_model_decimate_edge(self.v, self.key.as_ptr(), filter, flags, target_cells, &mut cell, &mut cells) })?;
+        Ok((cell, cells))
+    }
     /// `gsx_model_property_values`: one `f32` per Gaussian, computed on the device from the stored values (edits are not applied):
     /// the stored position (`flags = GSX_PROP_WORLD`: the model transform applied as `merge` bakes it), the bytes of the colour word
     /// / 255, their HSV, or the scales `export` solves from the covariance.
@@ -394,6 +411,26 @@ impl<G: GaussianPod> MultiModelViewer<G> {
             }, v, key: k });
         }
         Ok(count)
+    }
+    /// `gsx_model_decimate`: the Gaussians of `src_key` that share a cell of a grid of edge `desc.cell` become one moment-matched
+    /// Gaussian of the new model `dst_key`, on the device (one-member cells are copied as stored bits).  Returns the statistics and
+    /// the `dst` index of every source Gaussian; `cells == 0` creates no model.
+    pub fn decimate(&mut self, src_key: &str, dst_key: &str, desc: &sys::gsx_decimate_desc) -> Result<(sys::gsx_decimate_stats_t, Vec<u32>), Error> {
+        let (s, k) = (CString::new(src_key).unwrap(), CString::new(dst_key).unwrap());
+        let mut len = 0u64;
+        check(unsafe { sys::gsx_model_len(self.handle.0, s.as_ptr(), &mut len) })?;
+        let mut map = vec![u32::MAX; len as usize];
+        let mut out = sys::gsx_decimate_stats_t::default();
+        check(unsafe { sys::gsx_model_decimate(self.handle.0, s.as_ptr(), k.as_ptr(), desc, map.as_mut_ptr(), &mut out) })?;
+        if out.cells > 0 {
+            let (v, n) = (self.handle.0, out.cells as usize);
+            self.models.insert(dst_key.to_owned(), MultiModelViewerModel { gaussian_buffers: MultiModelViewerGaussianBuffers {
+                gaussians_buffer: GaussiansBuffer { v, key: k.clone() },
+                mask_buffer: MaskBuffer { v, key: k.clone(), words: (n + 31) / 32 },
+                gaussians_edit_buffer: GaussiansEditBuffer { v, key: k.clone(), n },
+            }, v, key: k });
+        }
+        Ok((out, map))
     }
     /// `gsx_model_convert`: `extract` into a model of the pod kind `(sh, cov3d)`: position and colour word carried, covariance and SH
     /// dequantised exactly and quantised once into the new kind, on the device.  The same kind is `extract`.  Returns the number kept;

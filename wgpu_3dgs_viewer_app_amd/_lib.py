@@ -56,6 +56,7 @@ EXPORTS = (
     "gsx_cluster_desc_default", "gsx_model_clusters", "gsx_model_select_clusters",
     "gsx_knn_desc_default", "gsx_model_knn", "gsx_model_select_knn",
     "gsx_transform_desc_default", "gsx_model_apply_transform",
+    "gsx_decimate_desc_default", "gsx_model_decimate", "gsx_model_decimate_edge",
 )
 
 
@@ -236,6 +237,22 @@ class TransformDesc(C.Structure):
     ``gsx_update_model_transform`` takes it (``quat`` x, y, z, w), the pivot it rotates and scales about, reserved (0)."""
     _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("pos", C.c_float * 3), ("quat", C.c_float * 4), ("scale", C.c_float * 3),
                 ("pivot", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+#: ``out_map`` of a Gaussian that does not participate in a decimate
+GSX_DECIMATE_NO_CELL = 0xFFFFFFFF
+
+
+class DecimateDesc(C.Structure):
+    """``gsx_decimate_desc`` (24 bytes): the ``GSX_BOUNDS_*`` filter, flags (``GSX_EXTRACT_INVERT``), the cell edge in model space
+    (must be set), ``grid_bits`` (0: the library's hash table; 1..24 forces ``2**grid_bits`` buckets and changes no result)."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("cell", C.c_float), ("grid_bits", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class DecimateStats(C.Structure):
+    """``gsx_decimate_stats_t`` (40 bytes)."""
+    _fields_ = [("count", C.c_uint64), ("n_nonfinite", C.c_uint64), ("cells", C.c_uint64), ("singletons", C.c_uint64),
+                ("largest_cell", C.c_uint32), ("grid_bits", C.c_uint32)]
 
 
 class ExtractDesc(C.Structure):
@@ -496,6 +513,9 @@ def load() -> C.CDLL:
         "gsx_model_select_knn": ([vp, cp, C.POINTER(KnnSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(KnnStats)], C.c_int32),
         "gsx_transform_desc_default": ([C.POINTER(TransformDesc)], None),
         "gsx_model_apply_transform": ([vp, cp, C.POINTER(TransformDesc), C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_decimate_desc_default": ([C.POINTER(DecimateDesc)], None),
+        "gsx_model_decimate": ([vp, cp, cp, C.POINTER(DecimateDesc), C.c_void_p, C.POINTER(DecimateStats)], C.c_int32),
+        "gsx_model_decimate_edge": ([vp, cp, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_uint64)], C.c_int32),
         "gsx_model_merge": ([vp, C.POINTER(C.c_char_p), C.c_uint32, cp, C.POINTER(ExtractDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
     }
     assert set(sig) == set(EXPORTS)

@@ -1172,6 +1172,40 @@ hipError_t launch_knn_brute(hipStream_t s, uint64_t n, const uint4* src, uint32_
 hipError_t launch_knn_stats(hipStream_t s, uint64_t n, const KnnJob& job);   // words[10..13], [16..23]
 hipError_t launch_knn_select(hipStream_t s, uint64_t n, const KnnJob& job);  // selection, words[14..15]
 
+// Model decimate (kernels_decimate.hip; gsx_model_decimate, gsx_model_decimate_edge): the Gaussians that share a cell of the grid
+// above (launch_neighbors_reduce / _cell / _scan / _scatter on `nb`, the cell edge given instead of a radius) become one
+// moment-matched Gaussian (decimate_math.h).  One launch_decimate_* per pass, in this order on one stream, after the grid's.  The
+// decimate's own regions lie behind the grid's.  Its words: [0] one-member cells  [1] the largest member count  [2] the entries of
+// `big`  [8] participants  [9..11] their minimum  [12..14] their maximum per axis (float bits: launch_decimate_extent).
+enum : uint32_t { kDecSingletons = 0, kDecLargest = 1, kDecBig = 2, kDecExtCount = 8, kDecExtMin = 9, kDecExtMax = 12, kDecWords = 32 };
+struct DecimateJob {
+    NeighborJob nb;            // the grid; nb.records holds every participant in bucket order
+    uint32_t* words;           // kDecWords words.  [0..2] are cleared in front of every count (gsx_api_decimate.cpp: count_cells); [8..14] are
+                               // written by launch_decimate_extent, in gsx_model_decimate_edge alone, and read by nobody else: stale elsewhere
+    uint64_t* totals;          // [0] the cells, from the head bits; [1] the same, from the keep bits (written by the scans)
+    uint4* sorted;             // n records {cell key low, high, original index, 0} in (bucket, cell, index) order
+    uint32_t* heads;           // ceil(n / 32) words over the positions of `sorted`: bit set = the first member of its cell
+    uint32_t* head_partials;   // extract_groups(n) words, and as many bases
+    uint32_t* head_bases;
+    uint32_t* keep;            // ceil(n / 32) words over the model, zeroed: bit set = a cell's representative (its smallest index)
+    uint32_t* keep_partials;   // extract_groups(n) words, and as many bases: k_extract_scatter's inputs
+    uint32_t* keep_bases;
+    uint32_t* run_start;       // n + 1 words: the position in `sorted` of the r-th head; [cells] = the participant count
+    uint32_t* run_dst;         // n words: the destination index of the r-th head's cell
+    uint32_t* cell_start;      // n words, by destination index: where the cell's members start in `sorted`, and how many they are
+    uint32_t* cell_len;
+    uint32_t* map;             // n words, filled with 0xFF: the destination index of every participant's cell
+    uint32_t* big;             // n / 64 + 2 words: the buckets of more than kDecRankBucket records, in any order
+    uint32_t big_cap;
+};
+hipError_t launch_decimate_extent(hipStream_t s, uint64_t n, const ModelFilter& f, const uint4* pc, const DecimateJob& job);  // words[8..14]
+hipError_t launch_decimate_order(hipStream_t s, uint64_t n, const DecimateJob& job);   // sorted, big
+hipError_t launch_decimate_cells(hipStream_t s, uint64_t n, const DecimateJob& job);   // heads, keep, both scans, run_*, cell_*, map, words[0..1]
+// dst holds launch_extract_scatter's copy of every representative (job.keep, job.keep_bases); the cells of two members and more are
+// written over it: planes and shade records of the kind, quantised once
+hipError_t launch_decimate_merge(hipStream_t s, int sh_kind, int cov_kind, uint64_t n_src, uint64_t n_dst, const DecimateJob& job, const ExtractPlanes& src,
+                                 const ExtractPlanes& dst);
+
 // Model export (kernels_export.hip; gsx_model_export): the rows of the kept Gaussians of the source workgroups [group0, group0 +
 // n_groups), in `format` (GSX_EXPORT_*), into `out` starting at the chunk's first kept Gaussian: row_base = bases[group0].  `out`
 // holds at least bases[group0 + n_groups] - row_base rows (the total in place of bases[] past the last group).  src is only read;

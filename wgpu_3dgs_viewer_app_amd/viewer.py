@@ -377,6 +377,23 @@ def _knn_stats(out, d2, score) -> ModelKnn:
                     int(out.n_brute), int(out.grid_bits))
 
 
+@dataclasses.dataclass
+class ModelDecimate:
+    """What ``MultiModelViewerModel.decimate`` and ``decimate_count`` return.  ``count``: participants (pass the filter, finite
+    position); ``n_nonfinite``: passed the filter with a NaN or infinite coordinate (dropped); ``cells``: occupied cells, the new
+    model's length; ``singletons``: one-member cells; ``largest_cell``: the largest member count; ``grid_bits``: the hash table used;
+    ``map`` (uint32, one per source Gaussian, or ``None``): the index in the new model it went into, ``_lib.GSX_DECIMATE_NO_CELL``
+    where it does not participate."""
+
+    count: int
+    n_nonfinite: int
+    cells: int
+    singletons: int
+    largest_cell: int
+    grid_bits: int
+    map: np.ndarray | None
+
+
 class MultiModelViewerModel:
     """``gs::MultiModelViewerModel {gaussian_buffers, bind_groups}`` (src/tab/scene.rs:2133-2139)."""
 
@@ -577,6 +594,40 @@ class MultiModelViewerModel:
         _lib.check(self._v._L.gsx_model_select_knn(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected),
                                                    C.byref(out)))
         return int(hit.value), int(selected.value), _knn_stats(out, None, None)
+
+    def _decimate(self, dst_key, cell, filter, invert, grid_bits, want_map):  # noqa: A002
+        desc = _lib.DecimateDesc(int(filter), _lib.GSX_EXTRACT_INVERT if invert else 0, float(cell), int(grid_bits))
+        out = _lib.DecimateStats()
+        out_map = np.full(self.gaussian_buffers.gaussians_buffer.len(), _lib.GSX_DECIMATE_NO_CELL, np.uint32) if want_map else None
+        _lib.check(self._v._L.gsx_model_decimate(self._v._h, self._key.encode(), None if dst_key is None else dst_key.encode(), C.byref(desc),
+                                                 out_map.ctypes.data if want_map else None, C.byref(out)))
+        if dst_key is not None and out.cells:
+            self._v.models[dst_key] = MultiModelViewerModel(self._v, dst_key)
+        return ModelDecimate(int(out.count), int(out.n_nonfinite), int(out.cells), int(out.singletons), int(out.largest_cell), int(out.grid_bits),
+                             out_map)
+
+    def decimate(self, dst_key: str, cell: float, filter: int = 0, invert: bool = False, grid_bits: int = 0,  # noqa: A002
+                 want_map: bool = False) -> ModelDecimate:
+        """``gsx_model_decimate``: the Gaussians that pass ``filter`` (``extract``'s kept set), have a finite position and share a
+        cell of a uniform grid of edge ``cell`` (model space) become ONE moment-matched Gaussian of the new model ``dst_key``, on the
+        device: mean and covariance of the mixture weighted by opacity times volume, opacity conserving that mass, colour and SH the
+        weighted means; a one-member cell is copied as stored bits.  The new model has this one's pod kind and transform and no mask,
+        selection or edits; it is ``viewer.models[dst_key]``.  ``cells == 0`` creates no model.  ``want_map`` downloads where every
+        Gaussian went.  ``decimate_edge`` finds a ``cell`` for a target count."""
+        return self._decimate(dst_key, cell, filter, invert, grid_bits, want_map)
+
+    def decimate_count(self, cell: float, filter: int = 0, invert: bool = False, grid_bits: int = 0,  # noqa: A002
+                       want_map: bool = False) -> ModelDecimate:
+        """``gsx_model_decimate`` without a destination: the statistics (and the map) ``decimate`` would return; nothing is created."""
+        return self._decimate(None, cell, filter, invert, grid_bits, want_map)
+
+    def decimate_edge(self, target: int, filter: int = 0, invert: bool = False) -> tuple[float, int]:  # noqa: A002
+        """``gsx_model_decimate_edge``: the smallest probed cell edge that leaves at most ``target`` cells, by 20 count-only bisection
+        steps on the device.  Returns ``(cell, cells)``: ``cell`` as a numpy float32, ready for ``decimate``."""
+        cell, cells = C.c_float(), C.c_uint64()
+        _lib.check(self._v._L.gsx_model_decimate_edge(self._v._h, self._key.encode(), int(filter), _lib.GSX_EXTRACT_INVERT if invert else 0,
+                                                      int(target), C.byref(cell), C.byref(cells)))
+        return np.float32(cell.value), int(cells.value)
 
     def _export_desc(self, filter, invert, bake_edits, fmt, staging_bytes):  # noqa: A002
         return _lib.ExportDesc(int(filter), (_lib.GSX_EXTRACT_INVERT if invert else 0) | (_lib.GSX_EXPORT_BAKE_EDITS if bake_edits else 0),
