@@ -15,7 +15,7 @@ from tests import common
 from tests import extract_ref as X
 from tests import neighbors_ref as N
 from tests.model_ops import H, W, frames as _frames, load as _load, pod as _pod
-from tests.test_gpu_neighbors import _filter_model, _passes, _points_model, _radius, _scene_model
+from tests.test_gpu_neighbors import FINISH_N, _filter_model, _finish_lattice, _passes, _points_model, _radius, _scene_model, _selection_is
 from wgpu_3dgs_viewer_app_amd import _lib, camera, query
 from wgpu_3dgs_viewer_app_amd import viewer as viewer_mod
 from wgpu_3dgs_viewer_app_amd.query import GaussianEditFlag as EF
@@ -235,6 +235,15 @@ def test_select_against_the_restatement(n):
         desc = _lib.ClusterSelectDesc(0, 0, K.SET, K.BY_SIZE, float(r), 1, 2, 1)
         assert v._L.gsx_model_select_clusters(v._h, SRC.encode(), C.byref(desc), None, None) == _lib.GSX_OK
         assert np.array_equal(sb.download(), X.words(K.hits(K.clusters(pos, finite, r), K.BY_SIZE, 1, 2)))
+
+
+def test_select_sums_more_partials_than_the_finish_has_lanes():
+    n = FINISH_N
+    with MultiModelViewer(sh=ShKind.Remove) as v:
+        m, _ = _points_model(v, _finish_lattice())
+        got = m.clusters(0.25)
+        assert (got.count, got.n_clusters, got.largest_size) == (n, n, 1)
+        assert m.select_clusters(0.25, K.BY_SIZE, 1, 1, K.SET) == (n, n) and _selection_is(m.gaussian_buffers.selection_buffer, True)
 
 
 def test_keep_the_largest_recipe_then_extract_and_frames():

@@ -22,6 +22,7 @@ from tests import extract_ref as X
 from tests import knn_ref as K
 from tests import neighbors_ref as N
 from tests.model_ops import H, W, frames as _frames, load as _load, pod as _pod
+from tests.test_gpu_neighbors import FINISH_N, _finish_lattice, _selection_is
 from wgpu_3dgs_viewer_app_amd import _lib, query
 from wgpu_3dgs_viewer_app_amd import viewer as viewer_mod
 from wgpu_3dgs_viewer_app_amd.query import GaussianEditFlag as EF
@@ -295,6 +296,16 @@ def test_select_against_the_restatement(n):
         desc = _lib.KnnSelectDesc(0, 0, N.SET, K.SELECT_RANGE, 16, K.SCORE_MEAN, 1e-4, 1, 1, 0.0, np.inf, 0.0)
         assert v._L.gsx_model_select_knn(v._h, SRC.encode(), C.byref(desc), None, None, None) == _lib.GSX_OK
         assert np.array_equal(sb.download(), words)
+
+
+def test_select_sums_more_partials_than_the_finish_has_lanes():
+    n = FINISH_N
+    with MultiModelViewer(sh=ShKind.Remove) as v:
+        m, _ = _points_model(v, _finish_lattice())
+        got = m.knn(1, K.SCORE_KTH)
+        # (sums of ones are exact in double: the mean is exactly 1, the deviation exactly 0)
+        assert (got.n_scored, got.score_min, got.score_max, got.mean, got.std) == (n, 1.0, 1.0, 1.0, 0.0)
+        assert m.select_knn(1, K.SCORE_KTH, lo=1.0, hi=1.0, op=N.SET)[:2] == (n, n) and _selection_is(m.gaussian_buffers.selection_buffer, True)
 
 
 def test_outlier_removal_then_extract_and_frames():

@@ -219,6 +219,31 @@ def test_select_against_the_restatement(n):
         assert np.array_equal(sb.download(), X.words(N.hits(N.brute(pos, finite, r, 3), finite, 0, 2)))
 
 
+FINISH_N = 256 * 1024 + 1  # 257 workgroups' partials: the smallest n at which a lane of the one-workgroup finish takes a second one
+
+
+def _finish_lattice():
+    """FINISH_N points of the integer lattice, Gaussian i at (i mod 64, i / 64 mod 64, i / 4096): every nearest distance is 1"""
+    i = np.arange(FINISH_N)
+    return np.stack([i % 64, (i // 64) % 64, i // 4096], axis=1).astype(F)
+
+
+def _selection_is(sb, on):
+    return np.array_equal(sb.download(), X.words(np.full(FINISH_N, on, bool)))  # (all ones and a cleared tail, or all zeros)
+
+
+def test_select_sums_more_partials_than_the_finish_has_lanes():
+    n = FINISH_N
+    with MultiModelViewer(sh=ShKind.Remove) as v:
+        m, _ = _points_model(v, _finish_lattice())
+        sb = m.gaussian_buffers.selection_buffer
+        got = m.neighbors(0.25, 7)
+        assert got.count == n and got.hist[0] == n and not got.hist[1:].any()
+        assert m.select_neighbors(0.25, 0, 0, 7, N.SET) == (n, n) and _selection_is(sb, True)
+        assert m.select_neighbors(0.25, 0, 0, 7, N.REMOVE) == (n, 0) and _selection_is(sb, False)
+        assert m.select_neighbors(0.25, 1, 7, 7, N.SET) == (0, 0) and _selection_is(sb, False)
+
+
 def test_floaters_recipe_then_extract_and_frames():
     n, k = 2500, 3
     g = common.small_scene(n, 37)

@@ -102,8 +102,6 @@ int main(int argc, char** argv) {
         job.nb.inv_h = g.inv_h;
         job.nb.bits = bits ? bits : nb_auto_bits(n);
         job.nb.max_count = kNbMaxCount;
-        job.nb.op = GSX_SELECTION_ADD;
-        job.nb.selection_valid = 1u;
         job.nb.result = head;
         job.nb.hist = head + kNbResultWords;
         job.nb.scan_total = reinterpret_cast<uint64_t*>(head + kNbResultWords + kNbMaxCount + 1u);
@@ -114,7 +112,7 @@ int main(int argc, char** argv) {
         job.nb.scan_bases = bases;
         job.nb.counts = counts;
         job.nb.records = records;
-        job.nb.selection = selection;
+        job.nb.sel = SelectionWrite{GSX_SELECTION_ADD, 1u, selection, partials};
         job.label = label;
         job.size = size;
         job.sizes = sizes;

@@ -51,7 +51,8 @@ def build_native() -> None:
     csrc = os.path.join(ROOT, "wgpu_3dgs_viewer_app_amd", "csrc")
     src = os.path.join(ROOT, "tools", "bench_clusters.hip")
     deps = [src] + [os.path.join(csrc, f) for f in ("kernels_clusters.hip", "kernels_neighbors.hip", "kernels_extract.hip", "clusters_math.h",
-                                                    "neighbors_math.h", "extract_math.h", "pod_planes.h", "gsx_internal.h")]
+                                                    "neighbors_math.h", "extract_math.h", "pod_planes.h", "gsx_internal.h", "wave_reduce.h",
+                                                    "selection_write.h", "neighbors_grid.h")]
     if os.path.exists(KERNELS) and all(os.path.getmtime(KERNELS) >= os.path.getmtime(d) for d in deps):
         return
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950", src, "-I" + csrc,

@@ -90,8 +90,6 @@ int main(int argc, char** argv) {
         job.max_count = max_count;
         job.count_lo = 0;
         job.count_hi = max_count - 1u;  // the floaters recipe
-        job.op = GSX_SELECTION_SET;
-        job.selection_valid = 1u;
         job.result = head;
         job.hist = head + kNbResultWords;
         job.scan_total = reinterpret_cast<uint64_t*>(head + kNbResultWords + kNbMaxCount + 1u);
@@ -102,7 +100,7 @@ int main(int argc, char** argv) {
         job.scan_bases = bases;
         job.counts = counts;
         job.records = records;
-        job.selection = selection;
+        job.sel = SelectionWrite{GSX_SELECTION_SET, 1u, selection, partials};
         std::vector<double> ms[kPasses];
         uint32_t h_res[kNbResultWords] = {0};
         for (int k = -1; k < samples; ++k) {  // (-1: the warm-up)

@@ -132,13 +132,11 @@ int main(int argc, char** argv) {
         job.lo = r.lo;
         job.hi = r.hi;
         job.bins = r.bins;
-        job.op = GSX_SELECTION_SET;
-        job.selection_valid = 1u;
         job.values = values;
         job.result = ws;
         job.hist = ws + kPropResultWords;
         job.partials = ws + kPropResultWords + kPropMaxBins;
-        job.selection = sel;
+        job.sel = SelectionWrite{GSX_SELECTION_SET, 1u, sel, job.partials};
         CK(launch_property(s, r.mode, r.cov_kind, n, none, src, job));
     };
     printf("{\"tool\": \"bench_property_kernels\", \"n\": %llu, \"samples\": %d, \"reps\": %d, \"rows\": {", (unsigned long long)n, samples, reps);

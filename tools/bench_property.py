@@ -47,7 +47,7 @@ def build_native() -> None:
     csrc = os.path.join(ROOT, "wgpu_3dgs_viewer_app_amd", "csrc")
     src = os.path.join(ROOT, "tools", "bench_property.hip")
     deps = [src] + [os.path.join(csrc, f) for f in ("kernels_property.hip", "property_math.h", "export_math.h", "edit_math.h", "extract_math.h",
-                                                    "pod_planes.h", "gsx_internal.h")]
+                                                    "pod_planes.h", "gsx_internal.h", "wave_reduce.h", "selection_write.h")]
     for suffix, flags in VARIANTS.items():
         exe = KERNELS + suffix
         if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps):

@@ -15,6 +15,12 @@
 
 namespace gsx {
 
+// A selection op on one word of the selection: Set, Add, Remove.  The only spelling: k_selection_op (kernels_edit.hip) and the model
+// operations' selects (selection_write.h) apply it, tests/property_driver.cpp tests it.
+GSX_HD inline uint32_t prop_apply_op(uint32_t op, uint32_t old, uint32_t hits) {
+    return op == (uint32_t)GSX_SELECTION_SET ? hits : (op == (uint32_t)GSX_SELECTION_ADD ? (old | hits) : (old & ~hits));
+}
+
 GSX_HD inline float em_clamp(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
 GSX_HD inline void em_rgb_to_hsv(float r, float g, float b, float& h, float& s, float& v) {

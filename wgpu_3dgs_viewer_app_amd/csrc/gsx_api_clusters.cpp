@@ -16,17 +16,12 @@ static_assert(GSX_CLUSTER_BY_SIZE == kClBySize && GSX_CLUSTER_LARGEST == kClLarg
 
 // The workspace of a model of n Gaussians under a table of 2^bits buckets; returns its bytes.
 size_t cluster_ws(char* ws, uint64_t n, uint32_t bits, ClusterJob* job) {
-    size_t at = neighbor_ws(ws, n, bits, &job->nb);
-    const auto take = [&](size_t bytes) {
-        const size_t here = at;
-        at += extract_pad128(bytes);
-        return reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(ws) + here);
-    };
-    job->label = take(4 * (size_t)n);
-    job->size = take(4 * (size_t)n);
-    job->sizes = take(4 * (size_t)n);
-    job->seeded = take(4 * (size_t)n);
-    return at;
+    WsCursor c{ws, neighbor_ws(ws, n, bits, &job->nb)};
+    job->label = c.take<uint32_t>(4 * (size_t)n);
+    job->size = c.take<uint32_t>(4 * (size_t)n);
+    job->sizes = c.take<uint32_t>(4 * (size_t)n);
+    job->seeded = c.take<uint32_t>(4 * (size_t)n);
+    return c.at;
 }
 
 // The workspace (grown if need be: the only step that can fail for memory) and the job of a call; n > 0.
@@ -98,7 +93,7 @@ gsx_status gsx_model_select_clusters(gsx_viewer* v, const char* key, const gsx_c
     if (!v || !key || !desc) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_clusters: null argument");
     gsx_status st = check_desc("gsx_model_select_clusters", desc->filter, desc->flags, desc->radius, kNbMaxCount, desc->grid_bits);
     if (st) return st;
-    if (desc->selection_op > (uint32_t)GSX_SELECTION_REMOVE) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_clusters: unknown selection op %u", desc->selection_op);
+    if ((st = check_selection_op("gsx_model_select_clusters", desc->selection_op))) return st;
     if (desc->mode > (uint32_t)GSX_CLUSTER_SEEDED) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_clusters: unknown mode %u", desc->mode);
     if (desc->mode == (uint32_t)GSX_CLUSTER_BY_SIZE ? (desc->size_lo < 1u || desc->size_lo > desc->size_hi) : (desc->size_lo != 0u || desc->size_hi != 0u))
         return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_clusters: sizes [%u, %u] in mode %u (by size: 1 <= size_lo <= size_hi; otherwise both 0)", desc->size_lo,
@@ -112,21 +107,16 @@ gsx_status gsx_model_select_clusters(gsx_viewer* v, const char* key, const gsx_c
     if (n == 0) return GSX_OK;
     ClusterJob job;
     if ((st = cluster_job(v, m, desc->radius, desc->grid_bits, &job))) return st;  // (before anything of the model changes)
-    // what gsx_model_select_range does: the epoch, the buffer, the write on the viewer's stream, the wait, then "has a selection"
     const ModelFilter f = model_filter(m, desc->filter, false);  // (before has_selection changes: none selected = none pass)
-    m->edit_epoch += 1;
-    if ((st = ensure_selection(v, m))) return st;
+    if ((st = select_begin(v, m, desc->selection_op, job.nb.partials, &job.nb.sel))) return st;  // (a model without a selection has no seeds)
     job.mode = desc->mode;
     job.size_lo = desc->size_lo;
     job.size_hi = desc->size_hi;
     job.seeds = desc->mode == (uint32_t)GSX_CLUSTER_SEEDED ? 1u : 0u;
-    job.nb.op = desc->selection_op;
-    job.nb.selection_valid = m->has_selection ? 1u : 0u;  // (a model without a selection has no seeds)
-    job.nb.selection = m->selection.as<uint32_t>();
     if ((st = enqueue_clusters(v, m, f, job))) return st;
     HIPCHK(launch_clusters_select(v->stream, n, job));
     HIPCHK(gsx::op::StreamSynchronize(v->stream));
-    m->has_selection = true;
+    select_end(m);
     uint32_t host[kNbResultWords];
     HIPCHK(gsx::op::Memcpy(host, job.nb.result, sizeof host, hipMemcpyDeviceToHost));
     if (out_hit) *out_hit = host[kNbHit];

@@ -16,30 +16,25 @@ static_assert(sizeof(gsx_decimate_desc) == 24 && sizeof(gsx_decimate_stats_t) ==
 
 // The decimate's regions behind the grid's `at` bytes; returns the workspace's bytes.
 size_t decimate_ws(char* ws, size_t at, uint64_t n, DecimateJob* job) {
-    const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
     const size_t groups = (size_t)extract_groups(n), bit_words = (size_t)((n + 31u) / 32u);
-    const auto take = [&](size_t bytes) {  // the next region: whole 128-byte lines
-        const size_t here = at;
-        at += extract_pad128(bytes);
-        return base + here;
-    };
-    job->words = reinterpret_cast<uint32_t*>(take(4 * kDecWords));
-    job->totals = reinterpret_cast<uint64_t*>(take(16));
+    WsCursor c{ws, at};
+    job->words = c.take<uint32_t>(4 * kDecWords);
+    job->totals = c.take<uint64_t>(16);
     job->big_cap = (uint32_t)(n / 64u + 2u);
-    job->big = reinterpret_cast<uint32_t*>(take(4 * (size_t)job->big_cap));
-    job->heads = reinterpret_cast<uint32_t*>(take(4 * bit_words));
-    job->head_partials = reinterpret_cast<uint32_t*>(take(4 * groups));
-    job->head_bases = reinterpret_cast<uint32_t*>(take(4 * groups));
-    job->keep = reinterpret_cast<uint32_t*>(take(4 * bit_words));
-    job->keep_partials = reinterpret_cast<uint32_t*>(take(4 * groups));
-    job->keep_bases = reinterpret_cast<uint32_t*>(take(4 * groups));
-    job->run_start = reinterpret_cast<uint32_t*>(take(4 * ((size_t)n + 1u)));
-    job->run_dst = reinterpret_cast<uint32_t*>(take(4 * (size_t)n));
-    job->cell_start = reinterpret_cast<uint32_t*>(take(4 * (size_t)n));
-    job->cell_len = reinterpret_cast<uint32_t*>(take(4 * (size_t)n));
-    job->map = reinterpret_cast<uint32_t*>(take(4 * (size_t)n));
-    job->sorted = reinterpret_cast<uint4*>(take(16 * (size_t)n));
-    return at;
+    job->big = c.take<uint32_t>(4 * (size_t)job->big_cap);
+    job->heads = c.take<uint32_t>(4 * bit_words);
+    job->head_partials = c.take<uint32_t>(4 * groups);
+    job->head_bases = c.take<uint32_t>(4 * groups);
+    job->keep = c.take<uint32_t>(4 * bit_words);
+    job->keep_partials = c.take<uint32_t>(4 * groups);
+    job->keep_bases = c.take<uint32_t>(4 * groups);
+    job->run_start = c.take<uint32_t>(4 * ((size_t)n + 1u));
+    job->run_dst = c.take<uint32_t>(4 * (size_t)n);
+    job->cell_start = c.take<uint32_t>(4 * (size_t)n);
+    job->cell_len = c.take<uint32_t>(4 * (size_t)n);
+    job->map = c.take<uint32_t>(4 * (size_t)n);
+    job->sorted = c.take<uint4>(16 * (size_t)n);
+    return c.at;
 }
 
 // what both calls check about (filter, flags, grid_bits)
@@ -74,7 +69,7 @@ gsx_status count_cells(gsx_viewer* v, const Model* m, const ModelFilter& f, floa
     job.nb.r2 = 0.0f;
     gsx_status st = enqueue_grid(v, m, f, job.nb);
     if (st) return st;
-    HIPCHK(gsx::op::MemsetAsync(job.words, 0, 4 * (kDecBig + 1u), v->stream));  // (the extent's words stay)
+    HIPCHK(gsx::op::MemsetAsync(job.words, 0, 4 * (kDecBig + 1u), v->stream));
     HIPCHK(gsx::op::MemsetAsync(job.totals, 0, 16, v->stream));
     HIPCHK(gsx::op::MemsetAsync(job.keep, 0, 4 * (size_t)((n + 31u) / 32u), v->stream));
     HIPCHK(gsx::op::MemsetAsync(job.map, 0xFF, 4 * (size_t)n, v->stream));
@@ -169,13 +164,15 @@ gsx_status gsx_model_decimate_edge(gsx_viewer* v, const char* key, uint32_t filt
     DecimateJob job;
     if ((st = decimate_job(v, m, nb_auto_bits(n), &job))) return st;
     const ModelFilter f = model_filter(m, filter, (flags & GSX_EXTRACT_INVERT) != 0);
-    HIPCHK(launch_decimate_extent(v->stream, n, f, extract_planes(m, false).pc, job));
+    // the participants' extent: the grid's reduce alone (count, origin and maximum in its result block)
+    HIPCHK(gsx::op::MemsetAsync(job.nb.result, 0, 4 * kNbResultWords, v->stream));
+    HIPCHK(launch_neighbors_reduce(v->stream, n, f, extract_planes(m, false).pc, job.nb));
     HIPCHK(gsx::op::StreamSynchronize(v->stream));
-    uint32_t words[kDecWords];
-    HIPCHK(gsx::op::Memcpy(words, job.words, sizeof words, hipMemcpyDeviceToHost));
-    if (words[kDecExtCount] == 0u) return GSX_OK;  // nothing participates: edge 0, 0 cells
+    uint32_t words[kNbResultWords];
+    HIPCHK(gsx::op::Memcpy(words, job.nb.result, sizeof words, hipMemcpyDeviceToHost));
+    if (words[kNbCount] == 0u) return GSX_OK;  // nothing participates: edge 0, 0 cells
     float extent = 0.0f;
-    for (int a = 0; a < 3; ++a) extent = fmaxf(extent, nb_from_bits(words[kDecExtMax + a]) - nb_from_bits(words[kDecExtMin + a]));
+    for (int a = 0; a < 3; ++a) extent = fmaxf(extent, nb_from_bits(words[kNbMax + a]) - nb_from_bits(words[kNbOrigin + a]));
     const auto count = [&](float edge, uint64_t* cells) {
         DecimateCount c{};
         const gsx_status e = count_cells(v, m, f, edge, job, &c);

@@ -20,22 +20,17 @@ static_assert(GSX_KNN_SELECT_RANGE == kKnnSelectRange && GSX_KNN_SELECT_OUTLIERS
 
 // The workspace of a model of n Gaussians under a table of 2^bits buckets, with or without rows of k; returns its bytes.
 size_t knn_ws(char* ws, uint64_t n, uint32_t bits, uint32_t k, bool rows, KnnJob* job) {
-    size_t at = neighbor_ws(ws, n, bits, &job->nb);
-    const auto take = [&](size_t bytes) {
-        const size_t here = at;
-        at += extract_pad128(bytes);
-        return reinterpret_cast<uintptr_t>(ws) + here;
-    };
-    job->words = reinterpret_cast<uint32_t*>(take(4 * kKnnWords));
-    job->partials = reinterpret_cast<uint32_t*>(take(4 * kKnnPartialWords * (size_t)extract_groups(n)));
-    job->box = reinterpret_cast<gsx_model_bounds_t*>(take(sizeof(gsx_model_bounds_t)));
-    job->box_partials = reinterpret_cast<BoundsPartial*>(take(sizeof(BoundsPartial) * kBoundsMaxGroups));
-    job->box_hist = reinterpret_cast<uint32_t*>(take(4 * 3u * kBoundsBins));
-    job->scores = reinterpret_cast<float*>(take(4 * (size_t)n));
-    job->list[0] = reinterpret_cast<uint4*>(take(16 * (size_t)n));
-    job->list[1] = reinterpret_cast<uint4*>(take(16 * (size_t)n));
-    job->rows = rows ? reinterpret_cast<float*>(take(4 * (size_t)n * k)) : nullptr;
-    return at;
+    WsCursor c{ws, neighbor_ws(ws, n, bits, &job->nb)};
+    job->words = c.take<uint32_t>(4 * kKnnWords);
+    job->partials = c.take<uint32_t>(4 * kKnnPartialWords * (size_t)extract_groups(n));
+    job->box = c.take<gsx_model_bounds_t>(sizeof(gsx_model_bounds_t));
+    job->box_partials = c.take<BoundsPartial>(sizeof(BoundsPartial) * kBoundsMaxGroups);
+    job->box_hist = c.take<uint32_t>(4 * 3u * kBoundsBins);
+    job->scores = c.take<float>(4 * (size_t)n);
+    job->list[0] = c.take<uint4>(16 * (size_t)n);
+    job->list[1] = c.take<uint4>(16 * (size_t)n);
+    job->rows = rows ? c.take<float>(4 * (size_t)n * k) : nullptr;
+    return c.at;
 }
 
 // what both calls check about (filter, flags, k, score, radius_hint, grid_bits, max_rounds)
@@ -171,7 +166,7 @@ gsx_status gsx_model_select_knn(gsx_viewer* v, const char* key, const gsx_knn_se
     if (!v || !key || !desc) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_knn: null argument");
     gsx_status st = check_knn("gsx_model_select_knn", desc->filter, desc->flags, desc->k, desc->score, desc->radius_hint, desc->grid_bits, desc->max_rounds);
     if (st) return st;
-    if (desc->selection_op > (uint32_t)GSX_SELECTION_REMOVE) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_knn: unknown selection op %u", desc->selection_op);
+    if ((st = check_selection_op("gsx_model_select_knn", desc->selection_op))) return st;
     if (desc->mode > (uint32_t)GSX_KNN_SELECT_OUTLIERS) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_knn: unknown mode %u", desc->mode);
     if (desc->mode == (uint32_t)GSX_KNN_SELECT_RANGE ? !(desc->lo <= desc->hi && desc->std_ratio == 0.0f)  // (a NaN bound compares false)
                                                      : !(nb_finite(desc->std_ratio) && desc->lo == 0.0f && desc->hi == 0.0f))
@@ -188,21 +183,16 @@ gsx_status gsx_model_select_knn(gsx_viewer* v, const char* key, const gsx_knn_se
     if (n == 0) return GSX_OK;
     KnnJob job;
     if ((st = knn_job(v, m, desc->k, desc->score, desc->grid_bits, false, &job))) return st;  // (before anything of the model changes)
-    // what gsx_model_select_range does: the epoch, the buffer, the write on the viewer's stream, the wait, then "has a selection"
     const ModelFilter f = model_filter(m, desc->filter, false);  // (before has_selection changes: none selected = none pass)
-    m->edit_epoch += 1;
-    if ((st = ensure_selection(v, m))) return st;
+    if ((st = select_begin(v, m, desc->selection_op, job.nb.partials, &job.nb.sel))) return st;
     job.mode = desc->mode;
     job.lo = desc->lo;
     job.hi = desc->hi;
     job.std_ratio = desc->std_ratio;
-    job.nb.op = desc->selection_op;
-    job.nb.selection_valid = m->has_selection ? 1u : 0u;
-    job.nb.selection = m->selection.as<uint32_t>();
     if ((st = run_knn(v, m, f, job, desc->radius_hint, desc->max_rounds, &stats))) return st;
     HIPCHK(launch_knn_select(v->stream, n, job));
     HIPCHK(gsx::op::StreamSynchronize(v->stream));
-    m->has_selection = true;
+    select_end(m);
     uint32_t host[kKnnWords];
     HIPCHK(gsx::op::Memcpy(host, job.words, sizeof host, hipMemcpyDeviceToHost));
     read_stats(host, &stats);

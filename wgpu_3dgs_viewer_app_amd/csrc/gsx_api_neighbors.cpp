@@ -77,7 +77,7 @@ gsx_status gsx_model_select_neighbors(gsx_viewer* v, const char* key, const gsx_
     if (!v || !key || !desc) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_neighbors: null argument");
     gsx_status st = check_desc("gsx_model_select_neighbors", desc->filter, desc->flags, desc->radius, desc->max_count, desc->grid_bits);
     if (st) return st;
-    if (desc->selection_op > (uint32_t)GSX_SELECTION_REMOVE) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_neighbors: unknown selection op %u", desc->selection_op);
+    if ((st = check_selection_op("gsx_model_select_neighbors", desc->selection_op))) return st;
     if (desc->count_lo > desc->count_hi || desc->count_hi > desc->max_count)
         return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_neighbors: counts [%u, %u] under max_count %u", desc->count_lo, desc->count_hi, desc->max_count);
     if (desc->reserved[0] != 0u || desc->reserved[1] != 0u) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_neighbors: a reserved word is not 0");
@@ -89,19 +89,14 @@ gsx_status gsx_model_select_neighbors(gsx_viewer* v, const char* key, const gsx_
     if (n == 0) return GSX_OK;
     NeighborJob job;
     if ((st = neighbor_job(v, m, desc->radius, desc->max_count, desc->grid_bits, &job))) return st;  // (before anything of the model changes)
-    // what gsx_model_select_range does: the epoch, the buffer, the write on the viewer's stream, the wait, then "has a selection"
     const ModelFilter f = model_filter(m, desc->filter, false);  // (before has_selection changes: none selected = none pass)
-    m->edit_epoch += 1;
-    if ((st = ensure_selection(v, m))) return st;
+    if ((st = select_begin(v, m, desc->selection_op, job.partials, &job.sel))) return st;
     job.count_lo = desc->count_lo;
     job.count_hi = desc->count_hi;
-    job.op = desc->selection_op;
-    job.selection_valid = m->has_selection ? 1u : 0u;
-    job.selection = m->selection.as<uint32_t>();
     if ((st = enqueue_counts(v, m, f, job))) return st;
     HIPCHK(launch_neighbors_select(v->stream, n, job));
     HIPCHK(gsx::op::StreamSynchronize(v->stream));
-    m->has_selection = true;
+    select_end(m);
     uint32_t host[kNbResultWords];
     HIPCHK(gsx::op::Memcpy(host, job.result, sizeof host, hipMemcpyDeviceToHost));
     if (out_hit) *out_hit = host[kNbHit];

@@ -129,7 +129,7 @@ gsx_status gsx_model_select_range(gsx_viewer* v, const char* key, const gsx_sele
     gsx_status st = check_property("gsx_model_select_range", desc->property, desc->flags, GSX_PROP_WORLD);  // (AUTO_RANGE is not legal here)
     if (st) return st;
     if (desc->filter & ~kModelFilterBits) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_range: unknown filter bits 0x%x", desc->filter);
-    if (desc->selection_op > (uint32_t)GSX_SELECTION_REMOVE) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_range: unknown selection op %u", desc->selection_op);
+    if ((st = check_selection_op("gsx_model_select_range", desc->selection_op))) return st;
     if (desc->reserved != 0u) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_range: reserved is %u, not 0", desc->reserved);
     if (desc->bins > kPropMaxBins) return fail(GSX_ERR_INVALID_ARG, "gsx_model_select_range: bins %u is above %u", desc->bins, kPropMaxBins);
     if (desc->bins && (desc->bin_lo > desc->bin_hi || desc->bin_hi >= desc->bins))
@@ -144,22 +144,17 @@ gsx_status gsx_model_select_range(gsx_viewer* v, const char* key, const gsx_sele
     if (n == 0) return GSX_OK;
     HIPCHK(v->extract_ws.ensure(kWsValues));
     uint32_t* result = v->extract_ws.as<uint32_t>();
-    // what gsx_model_upload_selection does: the epoch, the buffer, the write on the viewer's stream, the wait, then "has a selection"
     const ModelFilter f = model_filter(m, desc->filter, false);  // (before has_selection changes: none selected = none pass)
-    m->edit_epoch += 1;
-    if ((st = ensure_selection(v, m))) return st;
     PropertyJob job = property_job(m, desc->property, desc->flags, result);
+    if ((st = select_begin(v, m, desc->selection_op, job.partials, &job.sel))) return st;
     job.lo = desc->lo;
     job.hi = desc->hi;
     job.bins = desc->bins;
     job.bin_lo = desc->bin_lo;
     job.bin_hi = desc->bin_hi;
-    job.op = desc->selection_op;
-    job.selection_valid = m->has_selection ? 1u : 0u;
-    job.selection = m->selection.as<uint32_t>();
     HIPCHK(launch_property(v->stream, kPropSelect, (int)m->cov_kind, n, f, extract_planes(m, false), job));
     HIPCHK(gsx::op::StreamSynchronize(v->stream));
-    m->has_selection = true;
+    select_end(m);
     uint32_t host[kPropResultWords];
     HIPCHK(gsx::op::Memcpy(host, result, sizeof host, hipMemcpyDeviceToHost));
     if (out_hit) *out_hit = host[kPropHit];

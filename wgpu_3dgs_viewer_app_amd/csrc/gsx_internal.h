@@ -1054,6 +1054,16 @@ struct TransformBake {
 hipError_t launch_transform_inplace(hipStream_t s, int sh_kind, int cov_kind, int mode, uint64_t n, const uint32_t* keep, const ExtractPlanes& m,
                                     const TransformBake& bake);
 
+// What a select call of the model operations writes (gsx_model_select_range / _neighbors / _clusters / _knn): filled by select_begin
+// (gsx_state.h), written by select_write and summed by launch_select_finish (selection_write.h).
+constexpr uint32_t kSelectPartialWords = 8;  // hit | selected | 6 unused: the stride of every operation's partials
+struct SelectionWrite {
+    uint32_t op;              // gsx_selection_op
+    uint32_t valid;           // 0 = the selection buffer stands for "none selected" whatever it holds
+    uint32_t* words;          // ceil(n / 32) words, read and written
+    uint32_t* partials;       // one partial of kSelectPartialWords words per workgroup
+};
+
 // Model properties (kernels_property.hip; gsx_model_property_values, gsx_model_histogram, gsx_model_select_range): one frame over
 // the model in four modes, each but the first followed by a one-workgroup finish over the workgroups' partials.  The result block
 // (kPropResultWords words; the finish of a mode writes that mode's words):
@@ -1064,7 +1074,7 @@ enum : uint32_t { kPropValues = 0, kPropReduce = 1, kPropHist = 2, kPropSelect =
 enum : uint32_t { kPropCount = 0, kPropBelowAt = 1, kPropAboveAt = 2, kPropNonfiniteAt = 3, kPropMinKey = 4, kPropMaxKey = 5, kPropHit = 6, kPropSelected = 7,
                   kPropAutoCount = 8, kPropAutoNonfinite = 9, kPropAutoMinKey = 10, kPropAutoMaxKey = 11, kPropResultWords = 32 };
 constexpr uint32_t kPropMaxGroups = 2048;   // most workgroups (= partials) of a launch
-constexpr uint32_t kPropPartialWords = 8;   // count | below or selected | above | non-finite | min key | max key | 0 | 0
+constexpr uint32_t kPropPartialWords = 8;   // count | below | above | non-finite | min key | max key | 0 | 0; select: SelectionWrite's
 struct PropertyJob {
     uint32_t property;        // gsx_property
     uint32_t world;           // positions: apply the transform below (never set for an identity transform)
@@ -1072,14 +1082,12 @@ struct PropertyJob {
     float lo, hi;             // histogram (unless auto_range) and select
     uint32_t bins;            // histogram: 1 .. 4096; select: 0 = the range alone
     uint32_t bin_lo, bin_hi;  // select with bins
-    uint32_t op;              // select: gsx_selection_op
     uint32_t auto_range;      // histogram: [lo, hi] = the reduction's [min, max] (result[kPropAutoMinKey / MaxKey]; count 0: [0, 0])
-    uint32_t selection_valid; // select: 0 = the selection buffer stands for "none selected" whatever it holds
     float* values;            // values mode: n floats
     uint32_t* result;         // kPropResultWords words
     uint32_t* partials;       // kPropMaxGroups x kPropPartialWords words: one partial per workgroup
     uint32_t* hist;           // histogram: `bins` words, zeroed
-    uint32_t* selection;      // select: ceil(n / 32) words, read and written
+    SelectionWrite sel;       // select (its partials are `partials`)
 };
 // the histogram's zeros (and the result block's identities), in front of a histogram
 hipError_t launch_property_reset(hipStream_t s, uint32_t* result, uint32_t* hist, uint32_t bins);
@@ -1090,14 +1098,16 @@ hipError_t launch_property(hipStream_t s, uint32_t mode, int cov_kind, uint64_t 
 // counting sort, one launch_neighbors_* per pass, in this order on one stream; every workgroup of the passes in index order takes
 // kExtractGroup consecutive Gaussians and leaves one partial of kNbPartialWords words.  The result block (kNbResultWords words):
 //   [0] participants  [1] non-finite  [2..4] the grid origin (float bits: the participants' minimum)  [5] hit  [6] selected afterwards
-enum : uint32_t { kNbCount = 0, kNbNonfinite = 1, kNbOrigin = 2, kNbHit = 5, kNbSelected = 6, kNbResultWords = 32 };
-constexpr uint32_t kNbPartialWords = 8;    // reduce: count | non-finite | min x | min y | min z; select: hit | selected
+//   [12..14] the participants' maximum (float bits: gsx_model_decimate_edge's extent is maximum - origin)
+enum : uint32_t { kNbCount = 0, kNbNonfinite = 1, kNbOrigin = 2, kNbHit = 5, kNbSelected = 6, kNbMax = 12, kNbResultWords = 32 };
+constexpr uint32_t kNbPartialWords = 8;    // reduce: count | non-finite | min x, y, z | max x, y, z; select: SelectionWrite's
+static_assert(kNbPartialWords == kSelectPartialWords, "the grid's partials are the select's");
 constexpr uint32_t kNbScanBlock = 1024;    // table words a workgroup of the scan takes
 struct NeighborJob {
     float r2, inv_h;          // neighbors_math.h: nb_grid
     uint32_t bits;            // the table has 2^bits buckets
     uint32_t max_count;       // 1 .. 4095: a lane stops counting there
-    uint32_t count_lo, count_hi, op, selection_valid;  // select (selection_valid 0: the buffer stands for "none selected")
+    uint32_t count_lo, count_hi;  // select
     uint32_t* result;         // kNbResultWords words, zeroed
     uint32_t* hist;           // max_count + 1 words, zeroed
     uint32_t* partials;       // extract_groups(n) x kNbPartialWords words
@@ -1108,9 +1118,9 @@ struct NeighborJob {
     uint64_t* scan_total;
     uint32_t* counts;         // n words: the saturated counts by original index (0 for a Gaussian that does not participate)
     uint4* records;           // n records in bucket order: x, y, z bits and the original index
-    uint32_t* selection;      // select: ceil(n / 32) words, read and written
+    SelectionWrite sel;       // select (its partials are `partials`)
 };
-hipError_t launch_neighbors_reduce(hipStream_t s, uint64_t n, const ModelFilter& f, const uint4* pc, const NeighborJob& job);   // result[0..4]
+hipError_t launch_neighbors_reduce(hipStream_t s, uint64_t n, const ModelFilter& f, const uint4* pc, const NeighborJob& job);   // result[0..4], [12..14]
 hipError_t launch_neighbors_cell(hipStream_t s, uint64_t n, const ModelFilter& f, const uint4* pc, const NeighborJob& job);     // participants, table, counts = 0
 hipError_t launch_neighbors_scan(hipStream_t s, const NeighborJob& job);                                                        // table: sizes -> starts
 hipError_t launch_neighbors_scatter(hipStream_t s, uint64_t n, const uint4* pc, const NeighborJob& job);                        // records; table: starts -> ends
@@ -1130,8 +1140,8 @@ struct ClusterJob {
     uint32_t* size;           // n words, zeroed: size[l] = the Gaussians with label l
     uint32_t* sizes;          // n words: size[label[i]], 0 for a Gaussian that does not participate
     uint32_t* seeded;         // n words, zeroed (seeds only): seeded[l] = 1 if a Gaussian with label l is a seed
-    uint32_t seeds;           // 1: k_cl_label marks the labels of the selected participants (nb.selection, nb.selection_valid)
-    uint32_t mode, size_lo, size_hi;  // select; the op is nb.op
+    uint32_t seeds;           // 1: k_cl_label marks the labels of the selected participants (nb.sel)
+    uint32_t mode, size_lo, size_hi;  // select; the op is nb.sel.op
 };
 hipError_t launch_clusters_hook(hipStream_t s, uint64_t n, const ClusterJob& job);    // parent[] = i, then every pair united
 hipError_t launch_clusters_label(hipStream_t s, uint64_t n, const ClusterJob& job);   // label, size, seeded
@@ -1149,14 +1159,14 @@ enum : uint32_t {
     kKnnList = 0, kKnnScored = 10, kKnnScoreMin = 11, kKnnScoreMax = 12,
     kKnnThreshold = 13, kKnnHit = 14, kKnnSelected = 15, kKnnSum = 16, kKnnMean = 18, kKnnSs = 20, kKnnStd = 22, kKnnWords = 32
 };
-constexpr uint32_t kKnnPartialWords = 8;  // 32 B a workgroup: stats (count | min | max | - | the double sum), select (hit | selected)
+constexpr uint32_t kKnnPartialWords = 8;  // 32 B a workgroup: count | min | max | - | the double sum
 struct KnnJob {
     NeighborJob nb;           // the grid of the round; nb.records holds every participant after any round's scatter
     uint32_t k, score;        // 1 .. 16; GSX_KNN_SCORE_*
-    uint32_t mode;            // select: GSX_KNN_SELECT_*; the op, the selection and selection_valid are nb's
+    uint32_t mode;            // select: GSX_KNN_SELECT_*; the selection is nb.sel
     float lo, hi, std_ratio;  // select
     uint32_t* words;          // kKnnWords words
-    uint32_t* partials;       // extract_groups(n) x kKnnPartialWords words
+    uint32_t* partials;       // extract_groups(n) x kKnnPartialWords words (the select's partials are nb.partials)
     float* scores;            // n floats, filled with +inf before the search
     float* rows;              // n * k floats, filled with +inf, or nullptr: the rows are not wanted
     uint4* list[2];           // n records each: the unresolved entries of a round (x, y, z bits, original index), in any order
@@ -1176,12 +1186,11 @@ hipError_t launch_knn_select(hipStream_t s, uint64_t n, const KnnJob& job);  // 
 // above (launch_neighbors_reduce / _cell / _scan / _scatter on `nb`, the cell edge given instead of a radius) become one
 // moment-matched Gaussian (decimate_math.h).  One launch_decimate_* per pass, in this order on one stream, after the grid's.  The
 // decimate's own regions lie behind the grid's.  Its words: [0] one-member cells  [1] the largest member count  [2] the entries of
-// `big`  [8] participants  [9..11] their minimum  [12..14] their maximum per axis (float bits: launch_decimate_extent).
-enum : uint32_t { kDecSingletons = 0, kDecLargest = 1, kDecBig = 2, kDecExtCount = 8, kDecExtMin = 9, kDecExtMax = 12, kDecWords = 32 };
+// `big`.
+enum : uint32_t { kDecSingletons = 0, kDecLargest = 1, kDecBig = 2, kDecWords = 32 };
 struct DecimateJob {
     NeighborJob nb;            // the grid; nb.records holds every participant in bucket order
-    uint32_t* words;           // kDecWords words.  [0..2] are cleared in front of every count (gsx_api_decimate.cpp: count_cells); [8..14] are
-                               // written by launch_decimate_extent, in gsx_model_decimate_edge alone, and read by nobody else: stale elsewhere
+    uint32_t* words;           // kDecWords words; [0..2] are cleared in front of every count (gsx_api_decimate.cpp: count_cells)
     uint64_t* totals;          // [0] the cells, from the head bits; [1] the same, from the keep bits (written by the scans)
     uint4* sorted;             // n records {cell key low, high, original index, 0} in (bucket, cell, index) order
     uint32_t* heads;           // ceil(n / 32) words over the positions of `sorted`: bit set = the first member of its cell
@@ -1198,7 +1207,6 @@ struct DecimateJob {
     uint32_t* big;             // n / 64 + 2 words: the buckets of more than kDecRankBucket records, in any order
     uint32_t big_cap;
 };
-hipError_t launch_decimate_extent(hipStream_t s, uint64_t n, const ModelFilter& f, const uint4* pc, const DecimateJob& job);  // words[8..14]
 hipError_t launch_decimate_order(hipStream_t s, uint64_t n, const DecimateJob& job);   // sorted, big
 hipError_t launch_decimate_cells(hipStream_t s, uint64_t n, const DecimateJob& job);   // heads, keep, both scans, run_*, cell_*, map, words[0..1]
 // dst holds launch_extract_scatter's copy of every representative (job.keep, job.keep_bases); the cells of two members and more are

@@ -756,6 +756,23 @@ struct KeptSet {
 gsx_status kept_sets(gsx_viewer* v, KeptSet* src, uint32_t n_src, uint32_t filter_bits, bool invert, std::vector<uint32_t>* host_bases = nullptr);
 gsx_status ensure_selection(gsx_viewer* v, Model* m);
 gsx_status ensure_edit_buffers(gsx_viewer* v, Model* m);
+// The host side of a select call of the model operations (gsx_model_select_range / _neighbors / _clusters / _knn), which does what
+// gsx_model_upload_selection does: the epoch, the buffer, the write on the viewer's stream, the wait, then "has a selection".
+// check_selection_op stands among a call's argument checks; select_begin comes after the call's filter was taken (model_filter looks
+// at has_selection: none selected = none pass) and after its workspace was grown (before anything of the model changes), and fills
+// what the kernels write through; select_end comes after the wait for the stream.
+inline gsx_status check_selection_op(const char* fn, uint32_t op) {
+    if (op > (uint32_t)GSX_SELECTION_REMOVE) return fail(GSX_ERR_INVALID_ARG, "%s: unknown selection op %u", fn, op);
+    return GSX_OK;
+}
+inline gsx_status select_begin(gsx_viewer* v, Model* m, uint32_t op, uint32_t* partials, SelectionWrite* sel) {
+    m->edit_epoch += 1;
+    const gsx_status st = ensure_selection(v, m);
+    if (st) return st;
+    *sel = SelectionWrite{op, m->has_selection ? 1u : 0u, m->selection.as<uint32_t>(), partials};
+    return GSX_OK;
+}
+inline void select_end(Model* m) { m->has_selection = true; }
 
 // tile rows per rank of the multi-GPU layout with equal bands, the layout in force, bytes of a per-tile window map
 inline uint32_t rows_per_rank(const gsx_viewer* v, uint32_t world) {

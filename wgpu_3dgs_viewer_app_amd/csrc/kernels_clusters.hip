@@ -1,19 +1,17 @@
 // kernels_clusters.hip — the model clusters for gfx950 (spec/RENDER_SPEC.md §19, "Model clusters"): gsx_model_clusters and
 // gsx_model_select_clusters.  The grid is section 18's (kernels_neighbors.hip: reduce, cell, scan, scatter), unchanged; on top of it:
 //   k_cl_init    parent[i] = i for every Gaussian (the region section 18 calls counts);
-//   k_cl_hook    one lane per record, in bucket order, walks the 27 cells around its own exactly as k_nb_query does, with the
-//                own-cell test (a record counts only where its own cell IS the visited cell: two of the 27 cells that share a bucket
-//                would otherwise give it twice, and a cell's bucket holds other cells' records).  No cap, no early exit.  A record
-//                within the radius whose original index is below the lane's own is united with the lane's: each unordered pair
-//                once.  The union-find is clusters_math.h's, lock-free: nobody waits for anybody;
+//   k_cl_hook    one lane per record, in bucket order, walks the 27 cells around its own as k_nb_query does (neighbors_grid.h:
+//                nb_walk, with its own-cell test).  No cap, no early exit.  A record within the radius whose original index is
+//                below the lane's own is united with the lane's: each unordered pair once.  The union-find is clusters_math.h's,
+//                lock-free: nobody waits for anybody;
 //   k_cl_label   a separate launch, index order: label[i] = cl_find(i), or 0xFFFFFFFF for a Gaussian that does not participate;
 //                size[label] is counted by non-returning adds, combined first over the wave and, for the workgroup's smallest
 //                label, over the workgroup; with seeds, a plain store of 1 to seeded[label] for a selected participant (every
 //                writer stores the same value);
 //   k_cl_stats   index order: sizes[i] = size[label[i]]; the clusters are the Gaussians with label[i] == i, the largest one the
 //                maximum of (size << 32) | ~label — the smallest label wins a tie; one partial a workgroup, k_cl_finish combines them;
-//   k_cl_select  k_nb_select's shape: 64 hit tests are balloted into the wave's two selection words; lanes 0 and 32 apply the op,
-//                clear the tail, store, and count hit and selected bits: one partial a workgroup, k_cl_finish combines them.
+//   k_cl_select  k_nb_select's shape with the hit test of the mode; the write, the partial and its sum are selection_write.h's.
 // Memory model: every access to parent[] in k_cl_hook and k_cl_label is a relaxed agent-scope atomic (load, compare-and-swap, min),
 // which the L2-private XCDs resolve at the memory side; a CU's L1 is never asked.  No lane polls for another's progress: there is no
 // flag and no spin on a word somebody else must write.  A stale parent value is an older link of the same tree (clusters_math.h), the
@@ -24,13 +22,14 @@
 // indexes size[] or seeded[].
 #include "gsx_internal.h"
 #include "clusters_math.h"
+#include "neighbors_grid.h"
 #include "neighbors_math.h"
+#include "selection_write.h"
+#include "wave_reduce.h"
 
 namespace gsx {
 
 namespace {
-enum : uint32_t { kClModeStats = 0, kClModeSelect = 1 };
-
 // parent[] through relaxed agent-scope atomics: clusters_math.h's three primitives
 struct ClParent {
     uint32_t* parent;
@@ -39,46 +38,14 @@ struct ClParent {
     __device__ void min(uint32_t i, uint32_t v) const { atomicMin(parent + i, v); }  // (the value is not used: non-returning)
 };
 
-__device__ inline uint32_t cl_wave_sum(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ inline uint64_t cl_wave_max(uint64_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t y = ((uint64_t)__shfl_xor((uint32_t)(x >> 32), o, 64) << 32) | __shfl_xor((uint32_t)x, o, 64);
-        x = y > x ? y : x;
-    }
-    return x;
-}
-
-// The workgroup's partial from its lanes' values: sums of a0, a1, the maximum of key.  p[0] a0, p[1] a1, p[2..3] key.
-__device__ inline void cl_store_partial(uint32_t* __restrict__ partial, uint32_t a0, uint32_t a1, uint64_t key) {
-    __shared__ uint32_t s_sum[4][2];
-    __shared__ uint64_t s_key[4];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    a0 = cl_wave_sum(a0);
-    a1 = cl_wave_sum(a1);
-    key = cl_wave_max(key);
-    if (lane == 0u) {
-        s_sum[wave][0] = a0;
-        s_sum[wave][1] = a1;
-        s_key[wave] = key;
-    }
-    __syncthreads();
-    if (t == 0u) {
-        for (uint32_t w = 1; w < 4u; ++w) {
-            a0 += s_sum[w][0];
-            a1 += s_sum[w][1];
-            key = s_key[w] > key ? s_key[w] : key;
-        }
-        // ONE partial per workgroup, plain stores (DESIGN section 4, "Model properties": atomics on a few words cost more than the stream)
-        partial[0] = a0;
-        partial[1] = a1;
-        partial[2] = (uint32_t)key;
-        partial[3] = (uint32_t)(key >> 32);
-    }
+// What k_cl_stats leaves per workgroup and k_cl_finish combines: the clusters' count and the largest one's key, in thread 0.
+struct ClPartial {
+    uint32_t clusters;
+    uint64_t key;
+};
+__device__ inline ClPartial cl_fold(uint32_t clusters, uint64_t key) {
+    return group_fold(ClPartial{wave_sum(clusters), wave_max(key)},
+                      [](ClPartial a, const ClPartial& b) { return ClPartial{a.clusters + b.clusters, b.key > a.key ? b.key : a.key}; });
 }
 }  // namespace
 
@@ -88,35 +55,20 @@ __global__ __launch_bounds__(256) void k_cl_init(uint64_t n, uint32_t* __restric
 }
 
 __global__ __launch_bounds__(256) void k_cl_hook(uint64_t n, NeighborJob job) {
-    const uint32_t total = job.result[kNbCount];
+    const NbFrame g = nb_frame(job);
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= total) return;
-    const float ox = __uint_as_float(job.result[kNbOrigin + 0]), oy = __uint_as_float(job.result[kNbOrigin + 1]),
-                oz = __uint_as_float(job.result[kNbOrigin + 2]);
-    const float r2 = job.r2, inv_h = job.inv_h;
+    if (p >= g.total) return;
+    const float r2 = job.r2;
     const uint4 self = job.records[p];
     if (self.w >= n) return;  // (never: the scatter wrote an index below n)
     const float px = __uint_as_float(self.x), py = __uint_as_float(self.y), pz = __uint_as_float(self.z);
-    const uint32_t cx = nb_cell(px, ox, inv_h), cy = nb_cell(py, oy, inv_h), cz = nb_cell(pz, oz, inv_h);
     ClParent parent{job.counts};
-#pragma unroll 1
-    for (uint32_t c = 0; c < 27u; ++c) {
-        // (a coordinate below 0 wraps above kNbMaxCell: there is no such cell)
-        const uint32_t vx = cx + (c % 3u) - 1u, vy = cy + ((c / 3u) % 3u) - 1u, vz = cz + (c / 9u) - 1u;
-        if (vx > kNbMaxCell || vy > kNbMaxCell || vz > kNbMaxCell) continue;
-        const uint32_t b = nb_bucket(vx, vy, vz, job.bits);
-        uint32_t q = b ? job.table[b - 1u] : 0u;
-        const uint32_t end = min(job.table[b], total);
-#pragma unroll 1
-        for (; q < end; ++q) {
-            const uint4 r = job.records[q];
-            if (r.w >= self.w) continue;  // the pair belongs to the lane with the larger index (and a record is not its own pair)
-            const float rx = __uint_as_float(r.x), ry = __uint_as_float(r.y), rz = __uint_as_float(r.z);
-            if (nb_d2(px, py, pz, rx, ry, rz) <= r2) {
-                if (nb_cell(rx, ox, inv_h) == vx && nb_cell(ry, oy, inv_h) == vy && nb_cell(rz, oz, inv_h) == vz) cl_union(parent, self.w, r.w);
-            }
-        }
-    }
+    nb_walk(g, job, nb_cell3(g, self), [&](const uint4& r, const NbVisit& v) {
+        // the index first: the pair belongs to the lane with the larger index (and a record is not its own pair)
+        if (r.w < self.w && nb_d2(px, py, pz, __uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z)) <= r2 && v.holds(r))
+            cl_union(parent, self.w, r.w);
+        return true;  // (no cap, no early exit)
+    });
 }
 
 // Index order, kExtractGroup Gaussians a workgroup in four rounds.  The sizes are counted in three steps, because the common model is
@@ -144,15 +96,14 @@ __global__ __launch_bounds__(256) void k_cl_label(uint64_t n, ClusterJob job) {
                 const uint32_t root = cl_find(parent, (uint32_t)i);
                 if (root < n) {  // (always)
                     l[k] = root;
-                    if (job.seeds && job.nb.selection_valid && ((job.nb.selection[i >> 5] >> bit) & 1u)) job.seeded[root] = 1u;
+                    if (job.seeds && job.nb.sel.valid && ((job.nb.sel.words[i >> 5] >> bit) & 1u)) job.seeded[root] = 1u;
                 }
             }
             job.label[i] = l[k];
         }
         lowest = min(lowest, l[k]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lowest = min(lowest, (uint32_t)__shfl_xor(lowest, o, 64));
+    lowest = wave_min(lowest);
     if (lane == 0u && lowest != kClNone) atomicMin(&s_lowest, lowest);  // (LDS)
     __syncthreads();
     const uint32_t common = s_lowest;
@@ -195,39 +146,39 @@ __global__ __launch_bounds__(256) void k_cl_stats(uint64_t n, ClusterJob job) {
         }
         job.sizes[i] = s;
     }
-    cl_store_partial(job.nb.partials + (size_t)blockIdx.x * kNbPartialWords, clusters, 0u, key);
+    const ClPartial p = cl_fold(clusters, key);
+    if (t == 0u) {
+        // ONE partial per workgroup, plain stores (DESIGN section 4, "Model properties": atomics on a few words cost more than the stream)
+        uint32_t* out = job.nb.partials + (size_t)blockIdx.x * kNbPartialWords;
+        out[0] = p.clusters;
+        out[2] = (uint32_t)p.key;
+        out[3] = (uint32_t)(p.key >> 32);
+    }
 }
 
-// One workgroup: the partials combined into the result block's words of the mode.
-__global__ __launch_bounds__(256) void k_cl_finish(uint32_t mode, const uint32_t* __restrict__ partials, uint32_t n_partials, uint32_t* __restrict__ result) {
-    __shared__ uint32_t s_out[4];
+// One workgroup: the partials of k_cl_stats combined into the result block.
+__global__ __launch_bounds__(256) void k_cl_finish(const uint32_t* __restrict__ partials, uint32_t n_partials, uint32_t* __restrict__ result) {
     const uint32_t t = threadIdx.x;
-    uint32_t a0 = 0, a1 = 0;
+    uint32_t clusters = 0;
     uint64_t key = 0;
     for (uint32_t j = t; j < n_partials; j += 256u) {
-        const uint32_t* p = partials + (size_t)j * kNbPartialWords;
-        a0 += p[0];
-        a1 += p[1];
-        const uint64_t theirs = ((uint64_t)p[3] << 32) | p[2];
+        const uint32_t* in = partials + (size_t)j * kNbPartialWords;
+        clusters += in[0];
+        const uint64_t theirs = ((uint64_t)in[3] << 32) | in[2];
         key = theirs > key ? theirs : key;
     }
-    cl_store_partial(s_out, a0, a1, key);
+    const ClPartial p = cl_fold(clusters, key);
     if (t != 0u) return;
-    if (mode == kClModeStats) {
-        result[kClClusters] = s_out[0];
-        result[kClKey] = s_out[2];
-        result[kClKey + 1u] = s_out[3];
-    } else {
-        result[kNbHit] = s_out[0];
-        result[kNbSelected] = s_out[1];
-    }
+    result[kClClusters] = p.clusters;
+    result[kClKey] = (uint32_t)p.key;
+    result[kClKey + 1u] = (uint32_t)(p.key >> 32);
 }
 
 __global__ __launch_bounds__(256) void k_cl_select(uint64_t n, ClusterJob job) {
-    const uint32_t t = threadIdx.x, lane = t & 63u;
+    const uint32_t t = threadIdx.x;
     const uint64_t base = (uint64_t)blockIdx.x * kExtractGroup;
     const uint32_t largest = ~job.nb.result[kClKey];  // (0xFFFFFFFF without participants: no label below n equals it)
-    uint32_t hit_count = 0, selected = 0;  // lanes 0 and 32 of a wave
+    SelectCounts counts;
 #pragma unroll 1
     for (uint32_t k = 0; k < 4u; ++k) {
         if (base + k * 256u >= n) break;  // (uniform)
@@ -246,19 +197,9 @@ __global__ __launch_bounds__(256) void k_cl_select(uint64_t n, ClusterJob job) {
                 }
             }
         }
-        const unsigned long long hits64 = __ballot(hit);
-        if ((lane & 31u) == 0u && i < n) {  // this lane reads and writes the word of its 32: no other wave touches it
-            const uint64_t w = i >> 5;
-            const uint32_t hits = (uint32_t)(hits64 >> lane);
-            const uint32_t old = job.nb.selection_valid ? job.nb.selection[w] : 0u;
-            const uint32_t now = (job.nb.op == (uint32_t)GSX_SELECTION_SET ? hits : (job.nb.op == (uint32_t)GSX_SELECTION_ADD ? (old | hits) : (old & ~hits))) &
-                                 extract_tail_mask(n, w);
-            job.nb.selection[w] = now;
-            hit_count += extract_popc(hits);
-            selected += extract_popc(now);
-        }
+        select_write(job.nb.sel, hit, i, n, counts);
     }
-    cl_store_partial(job.nb.partials + (size_t)blockIdx.x * kNbPartialWords, hit_count, selected, 0u);
+    select_store_partial(job.nb.sel, counts);
 }
 
 hipError_t launch_clusters_hook(hipStream_t s, uint64_t n, const ClusterJob& job) {
@@ -274,14 +215,13 @@ hipError_t launch_clusters_label(hipStream_t s, uint64_t n, const ClusterJob& jo
 hipError_t launch_clusters_stats(hipStream_t s, uint64_t n, const ClusterJob& job) {
     const uint32_t groups = (uint32_t)extract_groups(n);
     GSX_LAUNCH(k_cl_stats, dim3(groups), dim3(256), 0, s, n, job);
-    GSX_LAUNCH(k_cl_finish, dim3(1), dim3(256), 0, s, (uint32_t)kClModeStats, job.nb.partials, groups, job.nb.result);
+    GSX_LAUNCH(k_cl_finish, dim3(1), dim3(256), 0, s, job.nb.partials, groups, job.nb.result);
     return hipGetLastError();
 }
 hipError_t launch_clusters_select(hipStream_t s, uint64_t n, const ClusterJob& job) {
     const uint32_t groups = (uint32_t)extract_groups(n);
     GSX_LAUNCH(k_cl_select, dim3(groups), dim3(256), 0, s, n, job);
-    GSX_LAUNCH(k_cl_finish, dim3(1), dim3(256), 0, s, (uint32_t)kClModeSelect, job.nb.partials, groups, job.nb.result);
-    return hipGetLastError();
+    return launch_select_finish(s, job.nb.sel, groups, job.nb.result + kNbHit, job.nb.result + kNbSelected);
 }
 
 }  // namespace gsx

@@ -27,19 +27,19 @@
 // against its capacity.
 #include "decimate_math.h"
 #include "gsx_internal.h"
+#include "neighbors_grid.h"
 #include "pod_planes.h"
+#include "wave_reduce.h"
 
 namespace gsx {
 
 namespace {
-constexpr float kDecInf = __builtin_huge_valf();
 constexpr uint32_t kDecSortGroups = 1024u;  // workgroups of k_dec_sort_big: each takes every 1024th entry of `big`
 
-__device__ inline uint4 dec_key_record(const uint4 rec, float ox, float oy, float oz, float inv_h, uint32_t* bucket, uint32_t bits) {
-    const uint32_t cx = nb_cell(__uint_as_float(rec.x), ox, inv_h), cy = nb_cell(__uint_as_float(rec.y), oy, inv_h),
-                   cz = nb_cell(__uint_as_float(rec.z), oz, inv_h);
-    const uint64_t key = dec_cell_key(cx, cy, cz);
-    if (bucket) *bucket = nb_bucket(cx, cy, cz, bits);
+__device__ inline uint4 dec_key_record(const NbFrame& g, const uint4 rec, uint32_t* bucket = nullptr) {
+    const NbCell c = nb_cell3(g, rec);
+    const uint64_t key = dec_cell_key(c.x, c.y, c.z);
+    if (bucket) *bucket = nb_bucket(g, c);
     return make_uint4((uint32_t)key, (uint32_t)(key >> 32), rec.w, 0u);
 }
 // (cell, index) order of two key records; no two records share an index
@@ -48,27 +48,6 @@ __device__ inline bool dec_less(const uint4 a, const uint4 b) {
     if (a.x != b.x) return a.x < b.x;
     return a.z < b.z;
 }
-__device__ inline uint32_t dec_wave_sum(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ inline uint32_t dec_wave_max(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = max(x, (uint32_t)__shfl_xor(x, o, 64));
-    return x;
-}
-__device__ inline float dec_wave_minf(float x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fminf(x, __shfl_xor(x, o, 64));
-    return x;
-}
-__device__ inline float dec_wave_maxf(float x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
-    return x;
-}
-
 // One compare-exchange network over a[0 .. size): every merge ascending, so the absent records past `size` stand for keys above all
 // others and a pair that reaches one is left alone.  256 lanes; ends with a barrier.
 __device__ inline void dec_bitonic(uint4* a, uint32_t size) {
@@ -112,99 +91,21 @@ __device__ inline float dec_load_sh(const ExtractPlanes& src, uint64_t n_src, ui
 }
 }  // namespace
 
-// The participants' count, minimum and maximum per axis (gsx_model_decimate_edge's extent): one partial a workgroup, then one workgroup.
-__global__ __launch_bounds__(256) void k_dec_extent(uint64_t n, ModelFilter f, const uint4* __restrict__ pc, uint32_t* __restrict__ partials) {
-    __shared__ uint32_t s_part[4][7];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    const uint64_t base = (uint64_t)blockIdx.x * kExtractGroup;
-    uint32_t count = 0;
-    float mn[3] = {kDecInf, kDecInf, kDecInf}, mx[3] = {-kDecInf, -kDecInf, -kDecInf};
-#pragma unroll 1
-    for (uint32_t k = 0; k < 4u; ++k) {
-        if (base + k * 256u >= n) break;  // (uniform)
-        const uint64_t i = base + k * 256u + t;
-        if (prop_keep(f, n, i, t)) {  // (every lane of the wave makes the call)
-            const uint4 e = pc[i];
-            const float x = __uint_as_float(e.x), y = __uint_as_float(e.y), z = __uint_as_float(e.z);
-            if (nb_finite(x) && nb_finite(y) && nb_finite(z)) {
-                count += 1u;
-                mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
-                mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
-            }
-        }
-    }
-    count = dec_wave_sum(count);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        mn[a] = dec_wave_minf(mn[a]);
-        mx[a] = dec_wave_maxf(mx[a]);
-    }
-    if (lane == 0u) {
-        s_part[wave][0] = count;
-        for (int a = 0; a < 3; ++a) {
-            s_part[wave][1 + a] = __float_as_uint(mn[a]);
-            s_part[wave][4 + a] = __float_as_uint(mx[a]);
-        }
-    }
-    __syncthreads();
-    if (t == 0u) {
-        for (uint32_t w = 1; w < 4u; ++w) {
-            count += s_part[w][0];
-            for (int a = 0; a < 3; ++a) {
-                mn[a] = fminf(mn[a], __uint_as_float(s_part[w][1 + a]));
-                mx[a] = fmaxf(mx[a], __uint_as_float(s_part[w][4 + a]));
-            }
-        }
-        uint32_t* p = partials + (size_t)blockIdx.x * kNbPartialWords;
-        p[0] = count;
-        for (int a = 0; a < 3; ++a) {
-            p[1 + a] = __float_as_uint(mn[a]);
-            p[4 + a] = __float_as_uint(mx[a]);
-        }
-    }
-}
-__global__ __launch_bounds__(64) void k_dec_extent_finish(const uint32_t* __restrict__ partials, uint32_t n_partials, uint32_t* __restrict__ words) {
-    const uint32_t lane = threadIdx.x;
-    uint32_t count = 0;
-    float mn[3] = {kDecInf, kDecInf, kDecInf}, mx[3] = {-kDecInf, -kDecInf, -kDecInf};
-    for (uint32_t j = lane; j < n_partials; j += 64u) {
-        const uint32_t* p = partials + (size_t)j * kNbPartialWords;
-        count += p[0];
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = fminf(mn[a], __uint_as_float(p[1 + a]));
-            mx[a] = fmaxf(mx[a], __uint_as_float(p[4 + a]));
-        }
-    }
-    count = dec_wave_sum(count);
-    for (int a = 0; a < 3; ++a) {
-        mn[a] = dec_wave_minf(mn[a]);
-        mx[a] = dec_wave_maxf(mx[a]);
-    }
-    if (lane == 0u) {
-        words[kDecExtCount] = count;
-        for (int a = 0; a < 3; ++a) {
-            words[kDecExtMin + a] = __float_as_uint(mn[a]);
-            words[kDecExtMax + a] = __float_as_uint(mx[a]);
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void k_dec_order(uint64_t n, DecimateJob job) {
     const NeighborJob& nb = job.nb;
-    const uint32_t total = min(nb.result[kNbCount], (uint32_t)n);
+    const NbFrame g = nb_frame(nb);
+    const uint32_t total = min(g.total, (uint32_t)n);
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= total) return;
-    const float ox = __uint_as_float(nb.result[kNbOrigin + 0]), oy = __uint_as_float(nb.result[kNbOrigin + 1]),
-                oz = __uint_as_float(nb.result[kNbOrigin + 2]);
     uint32_t b;
-    const uint4 own = dec_key_record(nb.records[p], ox, oy, oz, nb.inv_h, &b, nb.bits);
+    const uint4 own = dec_key_record(g, nb.records[p], &b);
     const uint32_t start = b ? nb.table[b - 1u] : 0u, end = min(nb.table[b], total);
     if (p < start || p >= end) return;  // (never: the scatter put the record into its bucket's range)
     if (end - start <= kDecRankBucket) {
         uint32_t rank = 0;
 #pragma unroll 1
         for (uint32_t q = start; q < end; ++q) {
-            const uint4 other = dec_key_record(nb.records[q], ox, oy, oz, nb.inv_h, nullptr, 0u);
+            const uint4 other = dec_key_record(g, nb.records[q]);
             rank += dec_less(other, own) ? 1u : 0u;  // (the record itself is not below itself)
         }
         job.sorted[start + rank] = own;  // (rank < end - start: the keys differ, so the ranks are a permutation)
@@ -218,10 +119,9 @@ __global__ __launch_bounds__(256) void k_dec_sort_big(uint64_t n, DecimateJob jo
     __shared__ uint4 s_rec[kDecLdsBucket];
     const NeighborJob& nb = job.nb;
     const uint32_t t = threadIdx.x;
-    const uint32_t total = min(nb.result[kNbCount], (uint32_t)n);
+    const NbFrame g = nb_frame(nb);
+    const uint32_t total = min(g.total, (uint32_t)n);
     const uint32_t n_big = min(job.words[kDecBig], job.big_cap);
-    const float ox = __uint_as_float(nb.result[kNbOrigin + 0]), oy = __uint_as_float(nb.result[kNbOrigin + 1]),
-                oz = __uint_as_float(nb.result[kNbOrigin + 2]);
 #pragma unroll 1
     for (uint32_t e = blockIdx.x; e < n_big; e += gridDim.x) {  // (uniform: the barriers below are reached by every lane)
         const uint32_t b = job.big[e];
@@ -230,7 +130,7 @@ __global__ __launch_bounds__(256) void k_dec_sort_big(uint64_t n, DecimateJob jo
         const uint32_t size = end - start;
         const bool in_lds = size <= kDecLdsBucket;
         uint4* a = in_lds ? s_rec : job.sorted + start;
-        for (uint32_t q = t; q < size; q += 256u) a[q] = dec_key_record(nb.records[start + q], ox, oy, oz, nb.inv_h, nullptr, 0u);
+        for (uint32_t q = t; q < size; q += 256u) a[q] = dec_key_record(g, nb.records[start + q]);
         __syncthreads();
         dec_bitonic(a, size);
         if (in_lds)
@@ -281,7 +181,7 @@ __global__ __launch_bounds__(256) void k_dec_heads(uint64_t n, DecimateJob job) 
 __global__ __launch_bounds__(64) void k_dec_popc(uint64_t n, const uint32_t* __restrict__ keep, uint32_t* __restrict__ partials) {
     const uint32_t lane = threadIdx.x;
     const uint64_t w = (uint64_t)blockIdx.x * kExtractGroupWords + lane;
-    const uint32_t c = dec_wave_sum((lane < kExtractGroupWords && w * 32u < n) ? extract_popc(keep[w]) : 0u);
+    const uint32_t c = wave_sum((lane < kExtractGroupWords && w * 32u < n) ? extract_popc(keep[w]) : 0u);
     if (lane == 0u) partials[blockIdx.x] = c;
 }
 
@@ -340,8 +240,8 @@ __global__ __launch_bounds__(256) void k_dec_map(uint64_t n, DecimateJob job) {
             largest = max(largest, len);
         }
     }
-    single = dec_wave_sum(single);
-    largest = dec_wave_max(largest);
+    single = wave_sum(single);
+    largest = wave_max(largest);
     if (lane == 0u) {
         atomicAdd(&s_single, single);
         atomicMax(&s_largest, largest);
@@ -409,7 +309,7 @@ __global__ __launch_bounds__(64) void k_dec_merge(uint64_t n_src, uint64_t n_dst
             }
         }
     }
-    max_a = dec_wave_max(max_a);
+    max_a = wave_max(max_a);
     const float M = __shfl(acc_m, 0, 64);  // column 0 under the mass weights: W = M
     const bool mass = dec_mass(M);
     const float acc = mass ? acc_m : acc_u;
@@ -470,12 +370,6 @@ __global__ __launch_bounds__(64) void k_dec_merge(uint64_t n_src, uint64_t n_dst
     }
 }
 
-hipError_t launch_decimate_extent(hipStream_t s, uint64_t n, const ModelFilter& f, const uint4* pc, const DecimateJob& job) {
-    const uint32_t groups = (uint32_t)extract_groups(n);
-    GSX_LAUNCH(k_dec_extent, dim3(groups), dim3(256), 0, s, n, f, pc, job.nb.partials);
-    GSX_LAUNCH(k_dec_extent_finish, dim3(1), dim3(64), 0, s, job.nb.partials, groups, job.words);
-    return hipGetLastError();
-}
 hipError_t launch_decimate_order(hipStream_t s, uint64_t n, const DecimateJob& job) {
     GSX_LAUNCH(k_dec_order, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, s, n, job);
     GSX_LAUNCH(k_dec_sort_big, dim3(kDecSortGroups), dim3(256), 0, s, n, job);

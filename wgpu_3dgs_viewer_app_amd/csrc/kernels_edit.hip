@@ -157,8 +157,7 @@ __global__ __launch_bounds__(256) void k_selection_op(uint32_t n_words, uint32_t
                                                        uint32_t* __restrict__ selection) {
     const uint32_t w = blockIdx.x * 256u + threadIdx.x;
     if (w >= n_words) return;
-    const uint32_t f = flags[w], s = selection[w];
-    selection[w] = op == GSX_SELECTION_SET ? f : (op == GSX_SELECTION_ADD ? (s | f) : (s & ~f));
+    selection[w] = prop_apply_op(op, selection[w], flags[w]);
 }
 
 hipError_t launch_edit_prepare(hipStream_t s, uint32_t n, const uint32_t* selection, uint32_t* edited, float4* edit_a,

@@ -23,72 +23,26 @@
 // capacity), a bucket's end against the participant count before the walk.
 #include "gsx_internal.h"
 #include "knn_math.h"
+#include "neighbors_grid.h"
+#include "selection_write.h"
+#include "wave_reduce.h"
 
 namespace gsx {
 
 namespace {
 constexpr float kKnnInf = __builtin_huge_valf();
 
-__device__ inline uint32_t knn_wave_sum(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ inline float knn_wave_min(float x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fminf(x, __shfl_xor(x, o, 64));
-    return x;
-}
-__device__ inline float knn_wave_max(float x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
-    return x;
-}
-// (a + b is the same double in both lanes of a pair: every lane ends with the same sum, the same on every call)
-__device__ inline double knn_wave_dsum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ inline unsigned long long knn_wave_min64(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long y = __shfl_xor(x, o, 64);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-
-// The workgroup's statistics partial, valid in thread 0 afterwards: count, minimum, maximum, and a double sum added in lane order
-// inside a wave's butterfly and in wave order across the four.
+// The workgroup's statistics partial, valid in thread 0 afterwards: count, minimum, maximum, and a double sum added in the order of
+// the wave's butterfly and in wave order across the four (wave_reduce.h).
 struct KnnStatsPartial {
     uint32_t count;
     float mn, mx;
     double sum;
 };
 __device__ inline KnnStatsPartial knn_combine_stats(uint32_t count, float mn, float mx, double sum) {
-    __shared__ uint32_t s_u[4][3];
-    __shared__ double s_d[4];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    count = knn_wave_sum(count);
-    mn = knn_wave_min(mn);
-    mx = knn_wave_max(mx);
-    sum = knn_wave_dsum(sum);
-    if (lane == 0u) {
-        s_u[wave][0] = count; s_u[wave][1] = __float_as_uint(mn); s_u[wave][2] = __float_as_uint(mx);
-        s_d[wave] = sum;
-    }
-    __syncthreads();
-    KnnStatsPartial p{count, mn, mx, sum};
-    if (t == 0u) {
-        for (uint32_t w = 1; w < 4u; ++w) {
-            p.count += s_u[w][0];
-            p.mn = fminf(p.mn, __uint_as_float(s_u[w][1]));
-            p.mx = fmaxf(p.mx, __uint_as_float(s_u[w][2]));
-            p.sum += s_d[w];
-        }
-    }
-    return p;
+    return group_fold(KnnStatsPartial{wave_sum(count), wave_min(mn), wave_max(mx), wave_sum(sum)}, [](KnnStatsPartial a, const KnnStatsPartial& b) {
+        return KnnStatsPartial{a.count + b.count, fminf(a.mn, b.mn), fmaxf(a.mx, b.mx), a.sum + b.sum};
+    });
 }
 __device__ inline void knn_store_double(uint32_t* __restrict__ at, double v) {  // at: an even word offset of a 128-byte aligned block
     *reinterpret_cast<double*>(at) = v;
@@ -123,39 +77,21 @@ __global__ __launch_bounds__(256) void k_knn_query(uint64_t n, const uint4* __re
     bool unresolved = false;
     uint4 self = make_uint4(0u, 0u, 0u, 0u);
     if (p < count) {
-        const NeighborJob& nb = job.nb;
-        const uint32_t total = nb.result[kNbCount];
-        const float ox = __uint_as_float(nb.result[kNbOrigin + 0]), oy = __uint_as_float(nb.result[kNbOrigin + 1]),
-                    oz = __uint_as_float(nb.result[kNbOrigin + 2]);
-        const float r2 = nb.r2, inv_h = nb.inv_h;
+        const NbFrame g = nb_frame(job.nb);
+        const float r2 = job.nb.r2;
         self = src[p];
         const float px = __uint_as_float(self.x), py = __uint_as_float(self.y), pz = __uint_as_float(self.z);
-        const uint32_t cx = nb_cell(px, ox, inv_h), cy = nb_cell(py, oy, inv_h), cz = nb_cell(pz, oz, inv_h);
         float b[K];
         knn_clear(b, job.k);
-        bool full_of_zeros = false;  // the k-th best is 0: nothing can lower the row any more
-#pragma unroll 1
-        for (uint32_t c = 0; c < 27u && !full_of_zeros; ++c) {
-            // (a coordinate below 0 wraps above kNbMaxCell: there is no such cell)
-            const uint32_t vx = cx + (c % 3u) - 1u, vy = cy + ((c / 3u) % 3u) - 1u, vz = cz + (c / 9u) - 1u;
-            if (vx > kNbMaxCell || vy > kNbMaxCell || vz > kNbMaxCell) continue;
-            const uint32_t bucket = nb_bucket(vx, vy, vz, nb.bits);
-            uint32_t q = bucket ? nb.table[bucket - 1u] : 0u;
-            const uint32_t end = min(nb.table[bucket], total);
-#pragma unroll 1
-            for (; q < end && !full_of_zeros; ++q) {
-                const uint4 r = nb.records[q];
-                const float rx = __uint_as_float(r.x), ry = __uint_as_float(r.y), rz = __uint_as_float(r.z);
-                const float d2 = nb_d2(px, py, pz, rx, ry, rz);
-                // (a value that is not below the k-th best changes no row: the test spares the chain)
-                if (d2 <= r2 && r.w != self.w && d2 < knn_kth(b)) {
-                    if (nb_cell(rx, ox, inv_h) == vx && nb_cell(ry, oy, inv_h) == vy && nb_cell(rz, oz, inv_h) == vz) {
-                        knn_insert(b, d2);
-                        full_of_zeros = knn_kth(b) == 0.0f;
-                    }
-                }
+        nb_walk(g, job.nb, nb_cell3(g, self), [&](const uint4& r, const NbVisit& v) {
+            const float d2 = nb_d2(px, py, pz, __uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z));
+            // (a value that is not below the k-th best changes no row: the test spares the chain and comes before the cell test)
+            if (d2 <= r2 && r.w != self.w && d2 < knn_kth(b) && v.holds(r)) {
+                knn_insert(b, d2);
+                return knn_kth(b) != 0.0f;  // the k-th best is 0: nothing can lower the row any more
             }
-        }
+            return true;
+        });
         if (knn_proven(knn_kth(b), r2))
             knn_store_row(n, job, self.w, b);
         else
@@ -202,8 +138,7 @@ __global__ __launch_bounds__(256) void k_knn_brute(uint64_t n, const uint4* __re
         if ((uint32_t)q + job.k < (uint32_t)K) continue;  // (uniform)
         const float mine = head < (uint32_t)K ? s_best[head][t] : kKnnInf;
         // (d2 is +0 or above, never NaN: the bits order as the values do; the lane breaks ties)
-        unsigned long long key = ((unsigned long long)__float_as_uint(mine) << 32) | t;
-        key = knn_wave_min64(key);
+        const uint64_t key = wave_min(((uint64_t)__float_as_uint(mine) << 32) | t);
         if (lane == 0u) s_wave[wave] = key;
         __syncthreads();
         unsigned long long best = s_wave[0];
@@ -280,13 +215,12 @@ __global__ __launch_bounds__(256) void k_knn_stats_finish(uint32_t pass, uint32_
 }
 
 __global__ __launch_bounds__(256) void k_knn_select(uint64_t n, KnnJob job) {
-    __shared__ uint32_t s_part[4][2];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const uint32_t t = threadIdx.x;
     const uint64_t base = (uint64_t)blockIdx.x * kExtractGroup;
     const bool outliers = job.mode == kKnnSelectOutliers;
     const float threshold = __uint_as_float(job.words[kKnnThreshold]);
     const bool any_scored = job.words[kKnnScored] != 0u;
-    uint32_t hit_count = 0, selected = 0;  // lanes 0 and 32 of a wave
+    SelectCounts counts;
 #pragma unroll 1
     for (uint32_t k = 0; k < 4u; ++k) {
         if (base + k * 256u >= n) break;  // (uniform)
@@ -296,51 +230,9 @@ __global__ __launch_bounds__(256) void k_knn_select(uint64_t n, KnnJob job) {
             const float s = job.scores[i];
             hit = outliers ? (any_scored && s > threshold) : (s >= job.lo && s <= job.hi);
         }
-        const unsigned long long hits64 = __ballot(hit);
-        if ((lane & 31u) == 0u && i < n) {  // this lane reads and writes the word of its 32: no other wave touches it
-            const uint64_t w = i >> 5;
-            const uint32_t hits = (uint32_t)(hits64 >> lane);
-            const uint32_t old = job.nb.selection_valid ? job.nb.selection[w] : 0u;
-            const uint32_t now = (job.nb.op == (uint32_t)GSX_SELECTION_SET ? hits : (job.nb.op == (uint32_t)GSX_SELECTION_ADD ? (old | hits) : (old & ~hits))) &
-                                 extract_tail_mask(n, w);
-            job.nb.selection[w] = now;
-            hit_count += extract_popc(hits);
-            selected += extract_popc(now);
-        }
+        select_write(job.nb.sel, hit, i, n, counts);
     }
-    hit_count = knn_wave_sum(hit_count);
-    selected = knn_wave_sum(selected);
-    if (lane == 0u) {
-        s_part[wave][0] = hit_count;
-        s_part[wave][1] = selected;
-    }
-    __syncthreads();
-    if (t == 0u) {
-        uint32_t* out = job.partials + (size_t)blockIdx.x * kKnnPartialWords;
-        out[0] = (s_part[0][0] + s_part[1][0]) + (s_part[2][0] + s_part[3][0]);
-        out[1] = (s_part[0][1] + s_part[1][1]) + (s_part[2][1] + s_part[3][1]);
-    }
-}
-
-__global__ __launch_bounds__(256) void k_knn_select_finish(uint32_t n_partials, KnnJob job) {
-    __shared__ uint32_t s_part[4][2];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    uint32_t hit_count = 0, selected = 0;
-    for (uint32_t j = t; j < n_partials; j += 256u) {
-        hit_count += job.partials[(size_t)j * kKnnPartialWords + 0u];
-        selected += job.partials[(size_t)j * kKnnPartialWords + 1u];
-    }
-    hit_count = knn_wave_sum(hit_count);
-    selected = knn_wave_sum(selected);
-    if (lane == 0u) {
-        s_part[wave][0] = hit_count;
-        s_part[wave][1] = selected;
-    }
-    __syncthreads();
-    if (t == 0u) {
-        job.words[kKnnHit] = (s_part[0][0] + s_part[1][0]) + (s_part[2][0] + s_part[3][0]);
-        job.words[kKnnSelected] = (s_part[0][1] + s_part[1][1]) + (s_part[2][1] + s_part[3][1]);
-    }
+    select_store_partial(job.nb.sel, counts);
 }
 
 hipError_t launch_knn_fill(hipStream_t s, uint64_t n, const KnnJob& job) {
@@ -378,8 +270,7 @@ hipError_t launch_knn_stats(hipStream_t s, uint64_t n, const KnnJob& job) {
 hipError_t launch_knn_select(hipStream_t s, uint64_t n, const KnnJob& job) {
     const uint32_t groups = (uint32_t)extract_groups(n);
     GSX_LAUNCH(k_knn_select, dim3(groups), dim3(256), 0, s, n, job);
-    GSX_LAUNCH(k_knn_select_finish, dim3(1), dim3(256), 0, s, groups, job);
-    return hipGetLastError();
+    return launch_select_finish(s, job.nb.sel, groups, job.words + kKnnHit, job.words + kKnnSelected);
 }
 
 }  // namespace gsx

@@ -8,17 +8,19 @@
 //     kPropReduce  count / non-finite count / min and max as order-preserving integer keys, for an AUTO_RANGE histogram;
 //     kPropHist    the same four and below / above, and the bin counted in LDS (uint32 counters, up to 4096 = 16 KiB), flushed with
 //                  non-returning global integer adds of the non-zero counters;
-//     kPropSelect  ballots the 64 hits into the wave's two selection words; lanes 0 and 32 apply the op to the word they read and
-//                  write it back, tail bits clear, and count hits and selected bits.
+//     kPropSelect  decides the lane's hit; the write into the wave's two selection words, the partial and its sum are
+//                  selection_write.h's (select_write, k_select_finish), shared with the other selects.
 //   CLS: kClsPc reads only the 16-byte position + colour element (properties 0..9); kClsCovSingle / kClsCovHalf read the covariance
 //   planes through pod_planes.h's exact decode and run ex_solve (properties 10..12), only for Gaussians that pass the filter.
 // Every cross-workgroup combination is an integer add, min or max: the result is the same bits in any order.  A workgroup leaves
-// ONE partial (kPropPartialWords words, plain stores); k_property_finish, one workgroup, combines the at most kPropMaxGroups of them
-// into the result block.  Only the histogram's bins meet in global atomics.
+// ONE partial (kPropPartialWords words, plain stores); k_property_finish (the select: k_select_finish), one workgroup, combines the
+// at most kPropMaxGroups of them into the result block.  Only the histogram's bins meet in global atomics.
 // Built with -ffp-contract=off.  Plane offsets are 64-bit.  Nothing of the model but the selection (kPropSelect) is written.
 #include "gsx_internal.h"
 #include "pod_planes.h"
 #include "property_math.h"
+#include "selection_write.h"
+#include "wave_reduce.h"
 
 namespace gsx {
 
@@ -75,20 +77,28 @@ __device__ inline float prop_value(const PropertyJob& job, const float* s_xf, co
     }
 }
 
-__device__ inline uint32_t wave_sum(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ inline uint32_t wave_min(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = min(x, (uint32_t)__shfl_xor(x, o, 64));
-    return x;
-}
-__device__ inline uint32_t wave_max(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = max(x, (uint32_t)__shfl_xor(x, o, 64));
-    return x;
+// What k_property leaves per workgroup and k_property_finish combines (kPropPartialWords words, the last two unused): integer sums,
+// minimum and maximum of order-preserving keys: the same bits in any order.
+struct PropPartial {
+    uint32_t count = 0, below = 0, above = 0, nonfinite = 0, kmin = kPropKeyMinIdentity, kmax = kPropKeyMaxIdentity;
+    __device__ void merge(const PropPartial& b) {
+        count += b.count; below += b.below; above += b.above; nonfinite += b.nonfinite;
+        kmin = min(kmin, b.kmin);
+        kmax = max(kmax, b.kmax);
+    }
+    __device__ void take(float v) {  // a finite value
+        count += 1u;
+        kmin = min(kmin, prop_key(v));
+        kmax = max(kmax, prop_key(v));
+    }
+};
+// The workgroup's partial from its lanes', valid in thread 0.
+__device__ inline PropPartial prop_fold(const PropPartial& p) {
+    return group_fold(PropPartial{wave_sum(p.count), wave_sum(p.below), wave_sum(p.above), wave_sum(p.nonfinite), wave_min(p.kmin), wave_max(p.kmax)},
+                      [](PropPartial a, const PropPartial& b) {
+                          a.merge(b);
+                          return a;
+                      });
 }
 }  // namespace
 
@@ -102,8 +112,7 @@ __global__ __launch_bounds__(256) void k_property_reset(uint32_t* __restrict__ r
 template <int CLS, uint32_t MODE>
 __global__ __launch_bounds__(256) void k_property(uint64_t n, ModelFilter f, PropPlanes src, PropertyJob job) {
     __shared__ uint32_t s_bins[MODE == kPropHist ? kPropMaxBins : 1u];
-    __shared__ uint32_t s_part[4][6];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const uint32_t t = threadIdx.x;
     __shared__ float s_xf[CLS == kClsPc ? 16 : 1];
     if (CLS == kClsPc && t == 0u) {
 #pragma unroll
@@ -128,8 +137,8 @@ __global__ __launch_bounds__(256) void k_property(uint64_t n, ModelFilter f, Pro
         __syncthreads();
     }
 
-    // per lane: c0 count (hist, reduce) or hits (select); c1 below or selected; c2 above; c3 non-finite; the keys of min and max
-    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, kmin = kPropKeyMinIdentity, kmax = kPropKeyMaxIdentity;
+    PropPartial p;        // per lane (hist, reduce)
+    SelectCounts counts;  // (select)
     const uint64_t chunks = extract_groups(n);
     for (uint64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
         const uint64_t base = c * kExtractGroup;
@@ -145,13 +154,8 @@ __global__ __launch_bounds__(256) void k_property(uint64_t n, ModelFilter f, Pro
             const float v = keep ? prop_value<CLS>(job, s_xf, src, i) : 0.0f;
             if (MODE == kPropReduce) {
                 if (keep) {
-                    if (prop_finite(v)) {
-                        c0 += 1u;
-                        kmin = min(kmin, prop_key(v));
-                        kmax = max(kmax, prop_key(v));
-                    } else {
-                        c3 += 1u;
-                    }
+                    if (prop_finite(v)) p.take(v);
+                    else p.nonfinite += 1u;
                 }
             } else if (MODE == kPropHist) {
                 uint32_t cls = kPropNonfinite;
@@ -159,61 +163,31 @@ __global__ __launch_bounds__(256) void k_property(uint64_t n, ModelFilter f, Pro
                 if (keep) {
                     cls = prop_classify(range, v);
                     if (cls == kPropNonfinite) {
-                        c3 += 1u;
+                        p.nonfinite += 1u;
                     } else {
-                        c0 += 1u;
-                        kmin = min(kmin, prop_key(v));
-                        kmax = max(kmax, prop_key(v));
-                        if (cls == kPropBelow) c1 += 1u;
-                        else if (cls == kPropAbove) c2 += 1u;
+                        p.take(v);
+                        if (cls == kPropBelow) p.below += 1u;
+                        else if (cls == kPropAbove) p.above += 1u;
                         else binned = true;
                     }
                 }
                 if (binned) atomicAdd(&s_bins[cls], 1u);
             } else {  // kPropSelect
-                const bool hit = keep && prop_hit(range, v, job.bins != 0u, job.bin_lo, job.bin_hi);
-                const unsigned long long hits64 = __ballot(hit);
-                // The wave's lanes have read the words of their Gaussians above (prop_keep: the selection as it was before the call);
-                // this lane now reads and writes the word of its 32: no other wave touches it.
-                if ((lane & 31u) == 0u && i < n) {
-                    const uint64_t w = i >> 5;
-                    const uint32_t hits = (uint32_t)(hits64 >> lane);
-                    const uint32_t old = job.selection_valid ? job.selection[w] : 0u;
-                    const uint32_t now = prop_apply_op(job.op, old, hits) & extract_tail_mask(n, w);
-                    job.selection[w] = now;
-                    c0 += extract_popc(hits);
-                    c1 += extract_popc(now);
-                }
+                select_write(job.sel, keep && prop_hit(range, v, job.bins != 0u, job.bin_lo, job.bin_hi), i, n, counts);
             }
         }
     }
     if (MODE == kPropValues) return;
+    if (MODE == kPropSelect) {
+        select_store_partial(job.sel, counts);
+        return;
+    }
 
-    // ---- the workgroup's partials: across the wave by butterflies, across the waves through LDS, then one atomic a counter ----
-    c0 = wave_sum(c0);
-    c1 = wave_sum(c1);
-    if (MODE != kPropSelect) {
-        c2 = wave_sum(c2);
-        c3 = wave_sum(c3);
-        kmin = wave_min(kmin);
-        kmax = wave_max(kmax);
-    }
-    if (lane == 0u) {
-        s_part[wave][0] = c0; s_part[wave][1] = c1; s_part[wave][2] = c2; s_part[wave][3] = c3; s_part[wave][4] = kmin; s_part[wave][5] = kmax;
-    }
-    __syncthreads();
-    if (t == 0u) {
-        uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, mn = kPropKeyMinIdentity, mx = kPropKeyMaxIdentity;
-        for (uint32_t w = 0; w < 4u; ++w) {
-            a0 += s_part[w][0]; a1 += s_part[w][1]; a2 += s_part[w][2]; a3 += s_part[w][3];
-            mn = min(mn, s_part[w][4]);
-            mx = max(mx, s_part[w][5]);
-        }
-        // ONE partial per workgroup, plain stores: 2048 workgroups adding to the same few words took longer than the stream itself
-        // (DESIGN section 4); k_property_finish combines them
-        uint32_t* p = job.partials + (size_t)blockIdx.x * kPropPartialWords;
-        p[0] = a0; p[1] = a1; p[2] = a2; p[3] = a3; p[4] = mn; p[5] = mx;
-    }
+    // ---- the workgroup's partial: across the wave by butterflies, across the waves through LDS (wave_reduce.h) ----
+    p = prop_fold(p);
+    // ONE partial per workgroup, plain stores: 2048 workgroups adding to the same few words took longer than the stream itself
+    // (DESIGN section 4); k_property_finish combines them
+    if (t == 0u) *reinterpret_cast<PropPartial*>(job.partials + (size_t)blockIdx.x * kPropPartialWords) = p;
     if (MODE == kPropHist) {  // (the barrier above is behind every LDS add)
         for (uint32_t j = t; j < range.bins; j += 256u) {
             const uint32_t cnt = s_bins[j];
@@ -225,46 +199,23 @@ __global__ __launch_bounds__(256) void k_property(uint64_t n, ModelFilter f, Pro
 // One workgroup: the partials of k_property combined (integer sums, min and max: any order gives the same bits) into the result
 // block's words of the mode.
 __global__ __launch_bounds__(256) void k_property_finish(uint32_t mode, const uint32_t* __restrict__ partials, uint32_t n_partials, uint32_t* __restrict__ result) {
-    __shared__ uint32_t s_part[4][6];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, mn = kPropKeyMinIdentity, mx = kPropKeyMaxIdentity;
-    for (uint32_t j = t; j < n_partials; j += 256u) {
-        const uint32_t* p = partials + (size_t)j * kPropPartialWords;
-        a0 += p[0]; a1 += p[1]; a2 += p[2]; a3 += p[3];
-        mn = min(mn, p[4]);
-        mx = max(mx, p[5]);
-    }
-    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3);
-    mn = wave_min(mn);
-    mx = wave_max(mx);
-    if (lane == 0u) {
-        s_part[wave][0] = a0; s_part[wave][1] = a1; s_part[wave][2] = a2; s_part[wave][3] = a3; s_part[wave][4] = mn; s_part[wave][5] = mx;
-    }
-    __syncthreads();
+    const uint32_t t = threadIdx.x;
+    PropPartial p;
+    for (uint32_t j = t; j < n_partials; j += 256u) p.merge(*reinterpret_cast<const PropPartial*>(partials + (size_t)j * kPropPartialWords));
+    p = prop_fold(p);
     if (t != 0u) return;
-    a0 = a1 = a2 = a3 = 0u;
-    mn = kPropKeyMinIdentity;
-    mx = kPropKeyMaxIdentity;
-    for (uint32_t w = 0; w < 4u; ++w) {
-        a0 += s_part[w][0]; a1 += s_part[w][1]; a2 += s_part[w][2]; a3 += s_part[w][3];
-        mn = min(mn, s_part[w][4]);
-        mx = max(mx, s_part[w][5]);
-    }
-    if (mode == kPropSelect) {
-        result[kPropHit] = a0;
-        result[kPropSelected] = a1;
-    } else if (mode == kPropReduce) {
-        result[kPropAutoCount] = a0;
-        result[kPropAutoNonfinite] = a3;
-        result[kPropAutoMinKey] = mn;
-        result[kPropAutoMaxKey] = mx;
+    if (mode == kPropReduce) {
+        result[kPropAutoCount] = p.count;
+        result[kPropAutoNonfinite] = p.nonfinite;
+        result[kPropAutoMinKey] = p.kmin;
+        result[kPropAutoMaxKey] = p.kmax;
     } else {
-        result[kPropCount] = a0;
-        result[kPropBelowAt] = a1;
-        result[kPropAboveAt] = a2;
-        result[kPropNonfiniteAt] = a3;
-        result[kPropMinKey] = mn;
-        result[kPropMaxKey] = mx;
+        result[kPropCount] = p.count;
+        result[kPropBelowAt] = p.below;
+        result[kPropAboveAt] = p.above;
+        result[kPropNonfiniteAt] = p.nonfinite;
+        result[kPropMinKey] = p.kmin;
+        result[kPropMaxKey] = p.kmax;
     }
 }
 
@@ -286,6 +237,7 @@ hipError_t launch_property_cls(hipStream_t s, uint32_t mode, uint64_t n, const M
         case kPropSelect: GSX_LAUNCH((k_property<CLS, kPropSelect>), grid, block, 0, s, n, f, src, job); break;
         default: return hipErrorInvalidValue;
     }
+    if (mode == kPropSelect) return launch_select_finish(s, job.sel, groups, job.result + kPropHit, job.result + kPropSelected);
     if (mode != kPropValues) GSX_LAUNCH(k_property_finish, dim3(1), dim3(256), 0, s, mode, job.partials, groups, job.result);
     return hipGetLastError();
 }

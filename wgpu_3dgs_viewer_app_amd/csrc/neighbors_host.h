@@ -14,27 +14,34 @@ constexpr size_t kNbWsTotal = kNbWsHist + 4 * (kNbMaxCount + 1u);  // 16 512
 constexpr size_t kNbWsPartials = kNbWsTotal + 128;
 static_assert(kNbWsHist == 128 && kNbWsPartials % 128 == 0, "the workspace regions are whole 128-byte lines");
 
+// The regions of a workspace one after the other, whole 128-byte lines each, from `at` bytes behind `ws` (nullptr where only the
+// size is asked for: the addresses are integers until the end).
+struct WsCursor {
+    char* ws;
+    size_t at;
+    template <class T>
+    T* take(size_t bytes) {
+        const size_t here = at;
+        at += extract_pad128(bytes);
+        return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(ws) + here);
+    }
+};
+
 // The workspace of a model of n Gaussians under a table of 2^bits buckets; returns its bytes.
 inline size_t neighbor_ws(char* ws, uint64_t n, uint32_t bits, NeighborJob* job) {
     const size_t words = size_t(1) << bits, blocks = (words + kNbScanBlock - 1u) / kNbScanBlock;
-    size_t at = kNbWsPartials;
-    const auto take = [&](size_t bytes) {  // the next region: whole 128-byte lines
-        const size_t here = at;
-        at += extract_pad128(bytes);
-        return reinterpret_cast<uintptr_t>(ws) + here;
-    };
-    const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
-    job->result = reinterpret_cast<uint32_t*>(base);
-    job->hist = reinterpret_cast<uint32_t*>(base + kNbWsHist);
-    job->scan_total = reinterpret_cast<uint64_t*>(base + kNbWsTotal);
-    job->partials = reinterpret_cast<uint32_t*>(take(4 * kNbPartialWords * (size_t)extract_groups(n)));
-    job->participants = reinterpret_cast<uint32_t*>(take(4 * (size_t)((n + 31u) / 32u)));
-    job->table = reinterpret_cast<uint32_t*>(take(4 * words));
-    job->scan_sums = reinterpret_cast<uint32_t*>(take(4 * blocks));
-    job->scan_bases = reinterpret_cast<uint32_t*>(take(4 * blocks));
-    job->counts = reinterpret_cast<uint32_t*>(take(4 * (size_t)n));
-    job->records = reinterpret_cast<uint4*>(take(16 * (size_t)n));
-    return at;
+    WsCursor c{ws, 0};
+    job->result = c.take<uint32_t>(kNbWsHist);
+    job->hist = c.take<uint32_t>(kNbWsTotal - kNbWsHist);
+    job->scan_total = c.take<uint64_t>(kNbWsPartials - kNbWsTotal);
+    job->partials = c.take<uint32_t>(4 * kNbPartialWords * (size_t)extract_groups(n));
+    job->participants = c.take<uint32_t>(4 * (size_t)((n + 31u) / 32u));
+    job->table = c.take<uint32_t>(4 * words);
+    job->scan_sums = c.take<uint32_t>(4 * blocks);
+    job->scan_bases = c.take<uint32_t>(4 * blocks);
+    job->counts = c.take<uint32_t>(4 * (size_t)n);
+    job->records = c.take<uint4>(16 * (size_t)n);
+    return c.at;
 }
 
 // what the calls check about (filter, flags, radius, max_count, grid_bits)

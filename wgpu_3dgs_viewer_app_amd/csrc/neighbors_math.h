@@ -5,17 +5,8 @@
 // Plain float32 / integer arithmetic, <math.h> only; no HIP include (the functions are __host__ __device__ under hipcc).  Built with
 // -ffp-contract=off wherever it is included.
 //
-// Why a pair with d2 <= r2 lies in cells that differ by at most 1 per axis (the query visits 27 cells and must miss nobody):
-//   d2 is a rounded sum of non-negative terms, so d2 <= r2 gives fl(dx * dx) <= r2 for every axis, and |dx| <= rmax, the largest
-//   float32-representable bound with fl(rmax^2) <= r2: nb_grid takes sqrt(nextafter(r2, inf)) in double, which is above it also where
-//   r2 is a denormal.  dx = fl(xj - xi), so the real difference is at most rmax (1 + 2^-24).
-//   The cell edge is h = rmax (1 + 2^-5).  u(x) = fl(fl(x - origin) * inv_h) with inv_h = fl(1 / h) is monotone in x (every step is
-//   a correctly rounded monotone operation), and so is the cell c(x) = min(floor(u), kNbMaxCell) (x >= origin: u >= 0).  For xi <=
-//   xj of a pair: if c(xi) is the clamp, so is c(xj).  Otherwise u(xi) < 2^15, and both u differ from the real t = (x - origin) / h
-//   by three roundings, at most 3.0001 * 2^-24 * (2^15 + 1) < 0.0059 each (an underflowing product errs by 2^-150, far less).  The
-//   real t differ by at most (1 + 2^-24) / (1 + 2^-5) (1 + 2^-23) < 0.9698 (the last factor: h's own rounding).  So u(xj) - u(xi) <
-//   0.9698 + 0.0118 < 1 and floor(u(xj)) <= floor(u(xi)) + 1; the clamp is monotone and only joins cells.  A difference x - origin
-//   that overflows is +inf, its cell the clamp.  No NaN arises from finite inputs (inv_h is finite and positive: 1e-23 < h < 2e19).
+// Why a pair with d2 <= r2 lies in cells that differ by at most 1 per axis — the walk over 27 cells misses nobody — is proven where
+// the walk is written: neighbors_grid.h, nb_walk.  The proof rests on nb_grid and nb_cell as they stand here.
 #pragma once
 #include <math.h>
 #include <stdint.h>

@@ -2,8 +2,8 @@
 // of kernels_property.hip and the host restatement of tests/property_driver.cpp both include it, so the two cannot drift.
 // It holds the value of a property from the stored words of a Gaussian (position and colour word; the dequantised covariance), the
 // histogram's geometry for a run-time bin count (bounds_math.h's recipe restated: the bin of a value, the edge of a bin), the class
-// of a value under a range (non-finite, below, above, a bin), the hit test of gsx_model_select_range, the selection op on a word,
-// and the order-preserving integer key min / max are reduced in.
+// of a value under a range (non-finite, below, above, a bin), the hit test of gsx_model_select_range, and the order-preserving
+// integer key min / max are reduced in.  (The selection op on a word, prop_apply_op, is edit_math.h's: k_selection_op applies it too.)
 // Plain float32 / integer arithmetic, <math.h> only besides export_math.h (ex_solve) and edit_math.h (em_rgb_to_hsv); no HIP
 // include (the functions are __host__ __device__ under hipcc).  Built with -ffp-contract=off wherever it is included.
 #pragma once
@@ -128,10 +128,6 @@ GSX_HD inline bool prop_hit(const PropRange& a, float v, bool use_bins, uint32_t
     const uint32_t c = prop_classify(a, v);
     if (c >= kPropAbove) return false;
     return !use_bins || (c >= bin_lo && c <= bin_hi);
-}
-// k_selection_op's meaning on one word: Set, Add, Remove
-GSX_HD inline uint32_t prop_apply_op(uint32_t op, uint32_t old, uint32_t hits) {
-    return op == (uint32_t)GSX_SELECTION_SET ? hits : (op == (uint32_t)GSX_SELECTION_ADD ? (old | hits) : (old & ~hits));
 }
 
 }  // namespace gsx
