@@ -760,6 +760,93 @@ gsx_status gsx_model_knn(gsx_viewer* v, const char* key, const gsx_knn_desc* des
 gsx_status gsx_model_select_knn(gsx_viewer* v, const char* key, const gsx_knn_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected,
                                 gsx_knn_stats_t* out_stats /* nullable */);
 
+/* ---- model nearest, across models: for every Gaussian of a source model the nearest Gaussian of a target model, its index and
+ *      squared distance, the one-sided chamfer and Hausdorff distances, a selection by them, and one least-squares registration
+ *      step, on the device (spec/RENDER_SPEC.md §23 [BUILD-SPEC]).  What two captures of one scene, or a model and its decimated or
+ *      converted copy, need: the overlap before a gsx_model_merge, a selection carried from one model to the other, how far a
+ *      decimated model is from its source, one capture registered onto another.  No Gaussian crosses to the host.
+ *      Participants: a target (a Gaussian of dst_key) participates if it passes desc->dst_filter (GSX_BOUNDS_* bits) and its three
+ *      stored coordinates are finite: gsx_model_neighbors' rule.  A query (a Gaussian of src_key) participates if it passes
+ *      desc->src_filter, its stored coordinates are finite and its mapped position q is finite.  stats.count and stats.targets are
+ *      their numbers; what passes a filter and fails the finiteness test goes to n_nonfinite and targets_nonfinite.
+ *      Mapping: desc->xform is a row-major 3x4 float32 matrix from the source's model space into the targets'; per row
+ *      q_r = ((m_r0*x + m_r1*y) + m_r2*z) + m_r3, every operation rounded to float32.  With GSX_NEAREST_MODEL_TRANSFORMS in
+ *      desc->flags desc->xform is ignored: the matrix is inv(M_dst) * M_src of the two models' current gsx_update_model_transform
+ *      values, M = T R S as in gsx_model_merge, the quaternions normalised, computed in double and rounded to float32 once; a
+ *      target scale component of 0 is GSX_ERR_INVALID_ARG.  Either way stats.xform returns the matrix used.
+ *      Answer: d2(q, t) = (dx*dx + dy*dy) + dz*dz in float32, gsx_model_neighbors' distance, in the targets' model space.
+ *      out_d2[i] (nullable; the source's length) is the smallest d2 over the participating targets that are in reach, out_index[i]
+ *      (nullable) the target's index, among equal d2 the smallest index.  In reach: d2 <= fl(max_distance * max_distance), or, with
+ *      max_distance 0 (unlimited), d2 finite.  GSX_NEAREST_NONE and +inf for a query that does not participate or has no target in
+ *      reach.  src_key may equal dst_key; nothing is excluded by index (with disjoint filters: from the selection to the rest).
+ *      Statistics over the found queries: n_found; d_min and d_max = sqrtf of the least and the largest d2 (d_max: the one-sided
+ *      Hausdorff distance); mean = sum sqrtf(d2) / n_found (the one-sided chamfer distance) and rms = sqrt(sum d2 / n_found) in
+ *      double, the sums combined from per-workgroup partials in index order: the same bits on every call; all 0 for n_found = 0.
+ *      Cost: max_distance bounds it.  Without it a query far from every target is asked again at four times the radius until the
+ *      grid is coarse and then costs one pass over all targets in the exact fallback (stats.n_brute), as a far point of
+ *      gsx_model_knn does; with it the last grid round runs at max_distance and what it leaves is "none".  While the unresolved
+ *      times the targets exceed the fallback's budget of 2^37 distance tests the rounds go on instead, on grids whose cells hold
+ *      ever more targets: millions of queries beyond the targets' box cost on the order of queries x targets distance tests.
+ *      Set max_distance for such a pair of models.
+ *      Knobs that change no result: radius_hint, grid_bits and max_rounds as in gsx_knn_desc (the table is over the targets);
+ *      stats.first_radius, rounds, n_brute and grid_bits report what ran.
+ *      gsx_model_select_nearest writes the SOURCE's selection.  GSX_NEAREST_SELECT_RANGE: the query participates and lo <=
+ *      sqrtf(d2) <= hi (lo <= hi, neither NaN; hi = +inf also takes the participants for which nothing was found).
+ *      GSX_NEAREST_SELECT_TRANSFER: a target was found and it is selected in dst_key as the call begins (a target model without a
+ *      selection: no hits; lo and hi 0).  selection_op, a model without a selection, the tail bits, GSX_BOUNDS_SELECTED reading the
+ *      selection as it was before the call (also where src_key equals dst_key), *out_hit / *out_selected (nullable), ordering and
+ *      frame consistency: gsx_model_select_range's.  gsx_model_nearest and gsx_model_align_step write nothing a frame reads.
+ *      gsx_model_align_step: one step of point-to-point registration; the iteration is the caller's loop.  The search above with
+ *      desc->nearest (its max_distance rejects correspondences), then over the found pairs (q, t), in double and in index order:
+ *      their number and means, and about the means rounded to float32 the products of the float32 differences: H = sum (q - qm)
+ *      (t - tm)^T, sum |q - qm|^2, sum d2.  The host solves for the similarity t ~ s R q + p: the unit quaternion (x, y, z, w;
+ *      w >= 0) is the dominant eigenvector of Horn's 4x4 matrix of H; with GSX_ALIGN_SCALE s = sum (t - tm) . R (q - qm) /
+ *      sum |q - qm|^2, otherwise 1; p = tm - s R qm.  out->pos, quat, scale: that delta, in double, in the targets' model space; xform_next =
+ *      delta o xform, composed in double and rounded once: the next step's desc->nearest.xform; n_pairs; rms_before = sqrt(sum d2 /
+ *      n_pairs); nearest: the search's statistics.  Fewer than 3 pairs, no spread among the q, or pairs that determine no single
+ *      rotation (all on one line): GSX_OK, out->degenerate = 1, the identity delta and xform_next = the matrix used.
+ *      Errors: a null viewer, key, desc or stats / out pointer (out_stats of the select is nullable), unknown filter, flag, mode or
+ *      op bits, a max_distance that is not 0 and one gsx_model_neighbors refuses as a radius, a radius_hint that is negative or NaN
+ *      or positive and refused, grid_bits > 24, max_rounds > 64, a matrix entry that is not finite, bounds the mode does not allow,
+ *      a reserved word != 0: GSX_ERR_INVALID_ARG; an unknown src_key or dst_key: GSX_ERR_NOT_FOUND; a viewer with a communicator,
+ *      or a sharded model: GSX_ERR_UNSUPPORTED; an allocation failure: GSX_ERR_OOM, both models as they were.  No queries or no
+ *      targets: GSX_OK with zeros and rows of GSX_NEAREST_NONE / +inf (a select with Set then clears the selection). ---- */
+#define GSX_NEAREST_NONE 0xFFFFFFFFu
+#define GSX_NEAREST_MODEL_TRANSFORMS 1u
+#define GSX_NEAREST_SELECT_RANGE 0u
+#define GSX_NEAREST_SELECT_TRANSFER 1u
+#define GSX_ALIGN_SCALE 1u
+typedef struct gsx_nearest_desc {
+    uint32_t src_filter; uint32_t dst_filter; uint32_t flags; uint32_t grid_bits; /* GSX_BOUNDS_* twice, GSX_NEAREST_MODEL_TRANSFORMS */
+    float max_distance; float radius_hint; uint32_t max_rounds; uint32_t reserved;
+    float xform[12];
+} gsx_nearest_desc; /* 80 B */
+typedef struct gsx_nearest_stats_t {
+    uint64_t count; uint64_t n_nonfinite; uint64_t targets; uint64_t targets_nonfinite; uint64_t n_found; uint64_t n_brute;
+    double mean; double rms;
+    float d_min; float d_max; float first_radius; uint32_t rounds; uint32_t grid_bits; uint32_t reserved;
+    float xform[12];
+} gsx_nearest_stats_t; /* 136 B */
+typedef struct gsx_nearest_select_desc {
+    gsx_nearest_desc nearest;
+    uint32_t selection_op; uint32_t mode; float lo; float hi; /* gsx_selection_op, GSX_NEAREST_SELECT_* */
+} gsx_nearest_select_desc; /* 96 B */
+typedef struct gsx_align_desc { gsx_nearest_desc nearest; uint32_t flags; uint32_t reserved; } gsx_align_desc; /* 88 B; flags: GSX_ALIGN_SCALE */
+typedef struct gsx_align_step_t {
+    double pos[3]; double quat[4]; double scale;
+    float xform_next[12];
+    uint64_t n_pairs; double rms_before;
+    uint32_t degenerate; uint32_t reserved;
+    gsx_nearest_stats_t nearest;
+} gsx_align_step_t; /* 272 B */
+void gsx_nearest_desc_default(gsx_nearest_desc* d); /* no filters, no flags, unlimited, the identity matrix, everything else 0 */
+gsx_status gsx_model_nearest(gsx_viewer* v, const char* src_key, const char* dst_key, const gsx_nearest_desc* desc,
+                             uint32_t* out_index /* nullable, the source's length */, float* out_d2 /* nullable, the source's length */,
+                             gsx_nearest_stats_t* out);
+gsx_status gsx_model_select_nearest(gsx_viewer* v, const char* src_key, const char* dst_key, const gsx_nearest_select_desc* desc, uint64_t* out_hit,
+                                    uint64_t* out_selected, gsx_nearest_stats_t* out_stats /* nullable */);
+gsx_status gsx_model_align_step(gsx_viewer* v, const char* src_key, const char* dst_key, const gsx_align_desc* desc, gsx_align_step_t* out);
+
 /* ---- model transform: move, rotate, scale or mirror the kept Gaussians of a resident model where they lie, on the device
  *      (spec/RENDER_SPEC.md §21 [BUILD-SPEC]).  The edit behind "grab the selection and move it": no copy of the model, the Gaussian
  *      order, every index, the mask, the selection and the edit records stay.  gsx_update_model_transform moves a whole model

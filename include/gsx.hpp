@@ -321,6 +321,60 @@ struct MultiModelViewerModel {
         check(gsx_model_select_knn(v_, key_.c_str(), &desc, &hit, &selected, stats));
         return {hit, selected};
     }
+    // gsx_model_nearest: for every Gaussian of this model, mapped by desc.xform (or by the two models' transforms), the nearest
+    // Gaussian of the model dst_key: index (GSX_NEAREST_NONE where none) and squared distance (+inf there), both nullable, on the
+    // device, bit for bit the brute-force answer with ties going to the smaller index.  The stats carry the one-sided chamfer (mean)
+    // and Hausdorff (d_max) distances and the matrix used.
+    gsx_nearest_stats_t nearest(const std::string& dst_key, const gsx_nearest_desc& desc, std::vector<uint32_t>* index = nullptr,
+                                std::vector<float>* d2 = nullptr) const {
+        uint64_t n = 0;
+        check(gsx_model_len(v_, key_.c_str(), &n));
+        if (index) index->assign((size_t)n, GSX_NEAREST_NONE);
+        if (d2) d2->assign((size_t)n, std::numeric_limits<float>::infinity());
+        gsx_nearest_stats_t out{};
+        check(gsx_model_nearest(v_, key_.c_str(), dst_key.c_str(), &desc, index ? index->data() : nullptr, d2 ? d2->data() : nullptr, &out));
+        return out;
+    }
+    // gsx_model_select_nearest: writes THIS model's selection; the hit set is, by desc.mode, the Gaussians whose distance to the model
+    // dst_key lies in [lo, hi] or those whose nearest target is selected there.  Returns {hit, selected afterwards}.
+    std::pair<uint64_t, uint64_t> select_nearest(const std::string& dst_key, const gsx_nearest_select_desc& desc, gsx_nearest_stats_t* stats = nullptr) {
+        uint64_t hit = 0, selected = 0;
+        check(gsx_model_select_nearest(v_, key_.c_str(), dst_key.c_str(), &desc, &hit, &selected, stats));
+        return {hit, selected};
+    }
+    // gsx_model_align_step: one least-squares step of point-to-point registration of this model onto the model dst_key.
+    gsx_align_step_t align_step(const std::string& dst_key, const gsx_align_desc& desc) const {
+        gsx_align_step_t out{};
+        check(gsx_model_align_step(v_, key_.c_str(), dst_key.c_str(), &desc, &out));
+        return out;
+    }
+    // Iterative closest point: align_step until rms_before changes by less than tol relatively or does not fall any more (at the
+    // float32 rounding of the positions it only flickers: a rise is the end), a step is degenerate or max_iters steps ran; every step starts from the step before's xform_next.  Returns the last step: its nearest.xform is the final
+    // matrix.  delta (nullable, 12 doubles, row-major 3x4) receives the composed similarity D with final = D o initial.
+    gsx_align_step_t align(const std::string& dst_key, gsx_align_desc desc, uint32_t max_iters = 30, double tol = 1e-6, double* delta = nullptr) const {
+        double D[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        gsx_align_step_t out{};
+        double last = -1.0;
+        for (uint32_t it = 0; it < max_iters; ++it) {
+            out = align_step(dst_key, desc);
+            const double now = out.rms_before;
+            if (out.degenerate || (last >= 0.0 && (now >= last || last - now <= tol * last))) break;
+            last = now;
+            const double x = out.quat[0], y = out.quat[1], z = out.quat[2], w = out.quat[3], s = out.scale;
+            const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z),
+                                 2 * (y * z - w * x), 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
+            double next[12];
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 4; ++c)
+                    next[4 * r + c] = s * (R[3 * r] * D[c] + R[3 * r + 1] * D[4 + c] + R[3 * r + 2] * D[8 + c]) + (c == 3 ? out.pos[r] : 0.0);
+            for (int k = 0; k < 12; ++k) D[k] = next[k];
+            desc.nearest.flags &= ~GSX_NEAREST_MODEL_TRANSFORMS;  // (from the second step on the matrix is the step before's)
+            for (int k = 0; k < 12; ++k) desc.nearest.xform[k] = out.xform_next[k];
+        }
+        if (delta)
+            for (int k = 0; k < 12; ++k) delta[k] = D[k];
+        return out;
+    }
 };
 
 class MultiModelViewer {

@@ -44,6 +44,11 @@ pub const GSX_KNN_SCORE_KTH: u32 = 0;
 pub const GSX_KNN_SCORE_MEAN: u32 = 1;
 pub const GSX_KNN_SELECT_RANGE: u32 = 0;
 pub const GSX_KNN_SELECT_OUTLIERS: u32 = 1;
+pub const GSX_NEAREST_NONE: u32 = 0xFFFF_FFFF;
+pub const GSX_NEAREST_MODEL_TRANSFORMS: u32 = 1;
+pub const GSX_NEAREST_SELECT_RANGE: u32 = 0;
+pub const GSX_NEAREST_SELECT_TRANSFER: u32 = 1;
+pub const GSX_ALIGN_SCALE: u32 = 1;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -220,6 +225,42 @@ pub struct gsx_knn_select_desc {
     pub filter: u32, pub flags: u32, pub selection_op: u32, pub mode: u32, pub k: u32, pub score: u32, pub radius_hint: f32,
     pub grid_bits: u32, pub max_rounds: u32, pub lo: f32, pub hi: f32, pub std_ratio: f32,
 }
+/// gsx_model_nearest, 80 bytes: the GSX_BOUNDS_* filters of the queries and of the targets, flags (GSX_NEAREST_MODEL_TRANSFORMS),
+/// max_distance (0: unlimited), the row-major 3x4 matrix from the source's model space into the targets', and three knobs that change
+/// no result: radius_hint, grid_bits, max_rounds (gsx_knn_desc's)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_nearest_desc {
+    pub src_filter: u32, pub dst_filter: u32, pub flags: u32, pub grid_bits: u32, pub max_distance: f32, pub radius_hint: f32,
+    pub max_rounds: u32, pub reserved: u32, pub xform: [f32; 12],
+}
+/// the result of gsx_model_nearest, 136 bytes: participating queries and targets and the non-finite of both, the found queries, the
+/// queries the exact fallback answered, the double mean distance (one-sided chamfer) and rms, the least and the largest distance
+/// (one-sided Hausdorff), the first radius, the grid rounds, the table, the matrix used
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_nearest_stats_t {
+    pub count: u64, pub n_nonfinite: u64, pub targets: u64, pub targets_nonfinite: u64, pub n_found: u64, pub n_brute: u64,
+    pub mean: f64, pub rms: f64, pub d_min: f32, pub d_max: f32, pub first_radius: f32, pub rounds: u32, pub grid_bits: u32,
+    pub reserved: u32, pub xform: [f32; 12],
+}
+/// gsx_model_select_nearest, 96 bytes: mode GSX_NEAREST_SELECT_RANGE (lo <= distance <= hi) or _TRANSFER (the nearest target is
+/// selected; lo and hi 0)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_nearest_select_desc { pub nearest: gsx_nearest_desc, pub selection_op: u32, pub mode: u32, pub lo: f32, pub hi: f32 }
+/// gsx_model_align_step, 88 bytes: the search and flags (GSX_ALIGN_SCALE)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_align_desc { pub nearest: gsx_nearest_desc, pub flags: u32, pub reserved: u32 }
+/// the result of gsx_model_align_step, 272 bytes: the delta t ~ scale R(quat) q + pos (quat x, y, z, w), xform_next = delta o the matrix
+/// used, the pairs, the rms distance before the step, whether the step was degenerate, the search's statistics
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_align_step_t {
+    pub pos: [f64; 3], pub quat: [f64; 4], pub scale: f64, pub xform_next: [f32; 12], pub n_pairs: u64, pub rms_before: f64,
+    pub degenerate: u32, pub reserved: u32, pub nearest: gsx_nearest_stats_t,
+}
 /// gsx_model_apply_transform, 64 bytes: the GSX_BOUNDS_* filter, flags (GSX_EXTRACT_INVERT), the transform as
 /// gsx_update_model_transform takes it (quat x, y, z, w), the pivot it rotates and scales about, reserved (0)
 #[repr(C)]
@@ -376,6 +417,10 @@ extern "C" {
     pub fn gsx_knn_desc_default(d: *mut gsx_knn_desc);
     pub fn gsx_model_knn(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_knn_desc, out_d2: *mut f32, out_score: *mut f32, out: *mut gsx_knn_stats_t) -> gsx_status;
     pub fn gsx_model_select_knn(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_knn_select_desc, out_hit: *mut u64, out_selected: *mut u64, out_stats: *mut gsx_knn_stats_t) -> gsx_status;
+    pub fn gsx_nearest_desc_default(d: *mut gsx_nearest_desc);
+    pub fn gsx_model_nearest(v: *mut gsx_viewer, src_key: *const c_char, dst_key: *const c_char, desc: *const gsx_nearest_desc, out_index: *mut u32, out_d2: *mut f32, out: *mut gsx_nearest_stats_t) -> gsx_status;
+    pub fn gsx_model_select_nearest(v: *mut gsx_viewer, src_key: *const c_char, dst_key: *const c_char, desc: *const gsx_nearest_select_desc, out_hit: *mut u64, out_selected: *mut u64, out_stats: *mut gsx_nearest_stats_t) -> gsx_status;
+    pub fn gsx_model_align_step(v: *mut gsx_viewer, src_key: *const c_char, dst_key: *const c_char, desc: *const gsx_align_desc, out: *mut gsx_align_step_t) -> gsx_status;
     pub fn gsx_transform_desc_default(d: *mut gsx_transform_desc);
     pub fn gsx_model_apply_transform(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_transform_desc, out_count: *mut u64) -> gsx_status;
     pub fn gsx_decimate_desc_default(d: *mut gsx_decimate_desc);

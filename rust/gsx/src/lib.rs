@@ -296,6 +296,65 @@ impl MultiModelViewerModel {
         check(unsafe { sys::gsx_model_select_knn(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected, &mut out) })?;
         Ok((hit, selected, out))
     }
+    /// `gsx_model_nearest`: for every Gaussian of this model, mapped by `desc.xform` (or by the two models' transforms), the nearest
+    /// Gaussian of the model `dst_key`, on the device, bit for bit the brute-force answer with ties going to the smaller index.
+    /// Returns `(index, d2, stats)`: `GSX_NEAREST_NONE` and `+inf` where there is none (both empty without `rows`); the stats carry
+    /// the one-sided chamfer (`mean`) and Hausdorff (`d_max`) distances and the matrix used.
+    pub fn nearest(&self, dst_key: &str, desc: &sys::gsx_nearest_desc, rows: bool) -> Result<(Vec<u32>, Vec<f32>, sys::gsx_nearest_stats_t), Error> {
+        let dst = CString::new(dst_key).unwrap();
+        let mut n = 0u64;
+        check(unsafe { sys::gsx_model_len(self.v, self.key.as_ptr(), &mut n) })?;
+        let mut index = vec![sys::GSX_NEAREST_NONE; if rows { n as usize } else { 0 }];
+        let mut d2 = vec![f32::INFINITY; if rows { n as usize } else { 0 }];
+        let mut out = sys::gsx_nearest_stats_t::default();
+        let (index_ptr, d2_ptr) = if rows { (index.as_mut_ptr(), d2.as_mut_ptr()) } else { (std::ptr::null_mut(), std::ptr::null_mut()) };
+        check(unsafe { sys::gsx_model_nearest(self.v, self.key.as_ptr(), dst.as_ptr(), desc, index_ptr, d2_ptr, &mut out) })?;
+        Ok((index, d2, out))
+    }
+    /// `gsx_model_select_nearest`: writes THIS model's selection; the hit set is, by `desc.mode`, the Gaussians whose distance to the
+    /// model `dst_key` lies in `[lo, hi]` or those whose nearest target is selected there.  Returns `(hit, selected, stats)`.
+    pub fn select_nearest(&mut self, dst_key: &str, desc: &sys::gsx_nearest_select_desc) -> Result<(u64, u64, sys::gsx_nearest_stats_t), Error> {
+        let dst = CString::new(dst_key).unwrap();
+        let (mut hit, mut selected) = (0u64, 0u64);
+        let mut out = sys::gsx_nearest_stats_t::default();
+        check(unsafe { sys::gsx_model_select_nearest(self.v, self.key.as_ptr(), dst.as_ptr(), desc, &mut hit, &mut selected, &mut out) })?;
+        Ok((hit, selected, out))
+    }
+    /// `gsx_model_align_step`: one least-squares step of point-to-point registration of this model onto the model `dst_key`.
+    pub fn align_step(&self, dst_key: &str, desc: &sys::gsx_align_desc) -> Result<sys::gsx_align_step_t, Error> {
+        let dst = CString::new(dst_key).unwrap();
+        let mut out = sys::gsx_align_step_t::default();
+        check(unsafe { sys::gsx_model_align_step(self.v, self.key.as_ptr(), dst.as_ptr(), desc, &mut out) })?;
+        Ok(out)
+    }
+    /// Iterative closest point: `align_step` until `rms_before` changes by less than `tol` relatively or does not fall any more (at
+    /// the float32 rounding of the positions it only flickers: a rise is the end), a step is degenerate or `max_iters` steps ran; every step starts from the step before's `xform_next`.  Returns the last step (its `nearest.xform` is
+    /// the final matrix) and the composed similarity `D` (row-major 3x4, `f64`) with `final = D o initial`.
+    pub fn align(&self, dst_key: &str, desc: &sys::gsx_align_desc, max_iters: u32, tol: f64) -> Result<(sys::gsx_align_step_t, [f64; 12]), Error> {
+        let mut desc = *desc;
+        let mut d = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0f64];
+        let mut out = sys::gsx_align_step_t::default();
+        let mut last = -1.0f64;
+        for _ in 0..max_iters {
+            out = self.align_step(dst_key, &desc)?;
+            let now = out.rms_before;
+            if out.degenerate != 0 || (last >= 0.0 && (now >= last || last - now <= tol * last)) { break; }
+            last = now;
+            let (x, y, z, w, s) = (out.quat[0], out.quat[1], out.quat[2], out.quat[3], out.scale);
+            let r = [1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y), 2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z),
+                     2.0 * (y * z - w * x), 2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)];
+            let mut next = [0.0f64; 12];
+            for row in 0..3 {
+                for c in 0..4 {
+                    next[4 * row + c] = s * (r[3 * row] * d[c] + r[3 * row + 1] * d[4 + c] + r[3 * row + 2] * d[8 + c]) + if c == 3 { out.pos[row] } else { 0.0 };
+                }
+            }
+            d = next;
+            desc.nearest.flags &= !sys::GSX_NEAREST_MODEL_TRANSFORMS; // from the second step on the matrix is the step before's
+            desc.nearest.xform = out.xform_next;
+        }
+        Ok((out, d))
+    }
 }
 
 pub struct Preprocessor(*mut sys::gsx_viewer);

@@ -55,6 +55,7 @@ EXPORTS = (
     "gsx_neighbor_desc_default", "gsx_model_neighbors", "gsx_model_select_neighbors",
     "gsx_cluster_desc_default", "gsx_model_clusters", "gsx_model_select_clusters",
     "gsx_knn_desc_default", "gsx_model_knn", "gsx_model_select_knn",
+    "gsx_nearest_desc_default", "gsx_model_nearest", "gsx_model_select_nearest", "gsx_model_align_step",
     "gsx_transform_desc_default", "gsx_model_apply_transform",
     "gsx_decimate_desc_default", "gsx_model_decimate", "gsx_model_decimate_edge",
 )
@@ -230,6 +231,53 @@ class KnnSelectDesc(C.Structure):
     _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("selection_op", C.c_uint32), ("mode", C.c_uint32), ("k", C.c_uint32),
                 ("score", C.c_uint32), ("radius_hint", C.c_float), ("grid_bits", C.c_uint32), ("max_rounds", C.c_uint32), ("lo", C.c_float),
                 ("hi", C.c_float), ("std_ratio", C.c_float)]
+
+
+#: ``gsx_model_nearest``: the index of a query without a target in reach
+GSX_NEAREST_NONE = 0xFFFFFFFF
+#: ``gsx_nearest_desc.flags``: the matrix is inv(M_dst) * M_src of the two models' transforms, not ``xform``
+GSX_NEAREST_MODEL_TRANSFORMS = 1
+#: ``gsx_nearest_select_desc.mode``
+GSX_NEAREST_SELECT_RANGE, GSX_NEAREST_SELECT_TRANSFER = 0, 1
+#: ``gsx_align_desc.flags``: solve for a uniform scale too
+GSX_ALIGN_SCALE = 1
+
+
+class NearestDesc(C.Structure):
+    """``gsx_nearest_desc`` (80 bytes): the ``GSX_BOUNDS_*`` filters of the queries and of the targets, flags
+    (``GSX_NEAREST_MODEL_TRANSFORMS``), ``max_distance`` (0: unlimited), the row-major 3x4 ``xform`` from the source's model space
+    into the targets', and three knobs that change no result: ``radius_hint``, ``grid_bits``, ``max_rounds`` (``gsx_knn_desc``'s)."""
+    _fields_ = [("src_filter", C.c_uint32), ("dst_filter", C.c_uint32), ("flags", C.c_uint32), ("grid_bits", C.c_uint32),
+                ("max_distance", C.c_float), ("radius_hint", C.c_float), ("max_rounds", C.c_uint32), ("reserved", C.c_uint32),
+                ("xform", C.c_float * 12)]
+
+
+class NearestStats(C.Structure):
+    """``gsx_nearest_stats_t`` (136 bytes): the participating queries and targets and the non-finite of both, the found queries, the
+    queries the exact fallback answered, the double mean distance and rms, the least and largest distance, what ran (first radius,
+    grid rounds, table) and the matrix used."""
+    _fields_ = [("count", C.c_uint64), ("n_nonfinite", C.c_uint64), ("targets", C.c_uint64), ("targets_nonfinite", C.c_uint64),
+                ("n_found", C.c_uint64), ("n_brute", C.c_uint64), ("mean", C.c_double), ("rms", C.c_double), ("d_min", C.c_float),
+                ("d_max", C.c_float), ("first_radius", C.c_float), ("rounds", C.c_uint32), ("grid_bits", C.c_uint32), ("reserved", C.c_uint32),
+                ("xform", C.c_float * 12)]
+
+
+class NearestSelectDesc(C.Structure):
+    """``gsx_nearest_select_desc`` (96 bytes): the search, the ``gsx_selection_op``, the ``GSX_NEAREST_SELECT_*`` mode and the distance
+    range ``[lo, hi]`` (mode RANGE)."""
+    _fields_ = [("nearest", NearestDesc), ("selection_op", C.c_uint32), ("mode", C.c_uint32), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+class AlignDesc(C.Structure):
+    """``gsx_align_desc`` (88 bytes): the search and flags (``GSX_ALIGN_SCALE``)."""
+    _fields_ = [("nearest", NearestDesc), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AlignStep(C.Structure):
+    """``gsx_align_step_t`` (272 bytes): the delta ``t ~ scale * R(quat) q + pos`` (``quat`` x, y, z, w), ``xform_next`` = delta o
+    the matrix used, the pairs, the rms distance before the step, whether the step was degenerate, the search's statistics."""
+    _fields_ = [("pos", C.c_double * 3), ("quat", C.c_double * 4), ("scale", C.c_double), ("xform_next", C.c_float * 12), ("n_pairs", C.c_uint64),
+                ("rms_before", C.c_double), ("degenerate", C.c_uint32), ("reserved", C.c_uint32), ("nearest", NearestStats)]
 
 
 class TransformDesc(C.Structure):
@@ -511,6 +559,10 @@ def load() -> C.CDLL:
         "gsx_knn_desc_default": ([C.POINTER(KnnDesc)], None),
         "gsx_model_knn": ([vp, cp, C.POINTER(KnnDesc), C.c_void_p, C.c_void_p, C.POINTER(KnnStats)], C.c_int32),
         "gsx_model_select_knn": ([vp, cp, C.POINTER(KnnSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(KnnStats)], C.c_int32),
+        "gsx_nearest_desc_default": ([C.POINTER(NearestDesc)], None),
+        "gsx_model_nearest": ([vp, cp, cp, C.POINTER(NearestDesc), C.c_void_p, C.c_void_p, C.POINTER(NearestStats)], C.c_int32),
+        "gsx_model_select_nearest": ([vp, cp, cp, C.POINTER(NearestSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(NearestStats)], C.c_int32),
+        "gsx_model_align_step": ([vp, cp, cp, C.POINTER(AlignDesc), C.POINTER(AlignStep)], C.c_int32),
         "gsx_transform_desc_default": ([C.POINTER(TransformDesc)], None),
         "gsx_model_apply_transform": ([vp, cp, C.POINTER(TransformDesc), C.POINTER(C.c_uint64)], C.c_int32),
         "gsx_decimate_desc_default": ([C.POINTER(DecimateDesc)], None),

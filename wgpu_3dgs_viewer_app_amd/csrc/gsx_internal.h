@@ -1182,6 +1182,53 @@ hipError_t launch_knn_brute(hipStream_t s, uint64_t n, const uint4* src, uint32_
 hipError_t launch_knn_stats(hipStream_t s, uint64_t n, const KnnJob& job);   // words[10..13], [16..23]
 hipError_t launch_knn_select(hipStream_t s, uint64_t n, const KnnJob& job);  // selection, words[14..15]
 
+// Model nearest across models (kernels_nearest.hip; gsx_model_nearest, gsx_model_select_nearest, gsx_model_align_step): for every
+// Gaussian of a source model, mapped by a 3x4 matrix, the nearest participant of a target model and its index, by rounds over the
+// grid above built over the TARGETS (`nb`, once a round) and an exact fallback (nearest_math.h).  Everything indexed by "n" below is
+// the source's; the regions lie behind the grid's.  Its words (kNearestWords 32-bit words; the doubles at even word offsets):
+//   [0..1] the entries of list 0 / list 1  [2] queries that pass the filter without a finite position  [3] found
+//   [4] d_min  [5] d_max (float bits)  [6] hit  [7] selected afterwards  [8] the sum of the distances  [10] the sum of d2 (doubles)
+// `align` (kNearestAlignDoubles doubles): [0] pairs [1..3] sum q [4..6] sum t | [8..16] H [17] sum |q - qm|^2 [18] sum |t - tm|^2 [19] sum d2.
+enum : uint32_t {
+    kNearestList = 0, kNearestNonfinite = 2, kNearestFound = 3, kNearestMin = 4, kNearestMax = 5, kNearestHit = 6, kNearestSelected = 7,
+    kNearestSum = 8, kNearestSum2 = 10, kNearestWords = 32
+};
+constexpr uint32_t kNearestPartialDoubles = 16;  // 128 B a workgroup: the statistics use 4, the align passes 7 and 12
+constexpr uint32_t kNearestAlignDoubles = 32;
+struct NearestJob {
+    NeighborJob nb;           // the grid of the round over the targets; nb.records holds every target after any round's scatter
+    float xform[12];          // row-major 3x4: the source's model space into the targets'
+    float cap2;               // nearest_cap2: a candidate has d2 <= min(nb.r2, cap2)
+    uint32_t final_round;     // the round's r2 is at or above cap2: what it leaves unresolved has no target in reach
+    uint32_t mode;            // select: GSX_NEAREST_SELECT_*
+    float lo, hi;             // select, RANGE
+    uint64_t n_dst;           // the targets' model length: an index read back is checked against it
+    const uint4* dst_pc;      // the targets' positions (align: t by index)
+    const uint32_t* dst_selection;  // select, TRANSFER: the targets' selection words, or nullptr: none selected
+    uint32_t* words;          // kNearestWords words
+    double* partials;         // extract_groups(n) x kNearestPartialDoubles doubles
+    double* align;            // kNearestAlignDoubles doubles
+    uint32_t* participants;   // ceil(n / 32) words: the queries that pass the filter with a finite stored and mapped position
+    uint32_t* transfer;       // ceil(n / 32) words (TRANSFER): the queries whose target is selected, taken before the selection is written
+    uint32_t* out_index;      // n words, GSX_NEAREST_NONE before the search
+    float* out_d2;            // n floats, +inf before the search
+    uint4* list[2];           // n entries each: (q.x, q.y, q.z bits, source index), in any order
+    gsx_model_bounds_t* box;  // the targets' count, box and trimmed box (launch_bounds_*), with its partials and histogram
+    BoundsPartial* box_partials;
+    uint32_t* box_hist;
+    SelectionWrite sel;       // select: the SOURCE's selection; its partials are extract_groups(n) x kSelectPartialWords words
+};
+// participants, out_index / out_d2 = none, and the first list, list[1] (words[0..2] zeroed by the caller); n > 0
+hipError_t launch_nearest_map(hipStream_t s, uint64_t n, const ModelFilter& f, const uint4* pc, const NearestJob& job);
+// One grid round: the `count` entries of src are answered, or appended to list[to] unless the round is final (words[to] zeroed by the caller).
+hipError_t launch_nearest_query(hipStream_t s, uint64_t n, const uint4* src, uint32_t count, uint32_t to, const NearestJob& job);
+// The exact fallback: one workgroup an entry of src against all `total` records of the grid.
+hipError_t launch_nearest_brute(hipStream_t s, uint64_t n, const uint4* src, uint32_t count, uint32_t total, const NearestJob& job);
+hipError_t launch_nearest_stats(hipStream_t s, uint64_t n, const NearestJob& job);     // words[3..5], [8..11]
+hipError_t launch_nearest_transfer(hipStream_t s, uint64_t n, const NearestJob& job);  // transfer
+hipError_t launch_nearest_select(hipStream_t s, uint64_t n, const NearestJob& job);    // the source's selection, words[6..7]
+hipError_t launch_nearest_align(hipStream_t s, uint64_t n, const uint4* pc, const NearestJob& job);  // align (both passes)
+
 // Model decimate (kernels_decimate.hip; gsx_model_decimate, gsx_model_decimate_edge): the Gaussians that share a cell of the grid
 // above (launch_neighbors_reduce / _cell / _scan / _scatter on `nb`, the cell edge given instead of a radius) become one
 // moment-matched Gaussian (decimate_math.h).  One launch_decimate_* per pass, in this order on one stream, after the grid's.  The

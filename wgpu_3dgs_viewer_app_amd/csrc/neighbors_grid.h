@@ -52,6 +52,14 @@ struct NbVisit {
 //   real t differ by at most (1 + 2^-24) / (1 + 2^-5) (1 + 2^-23) < 0.9698 (the last factor: h's own rounding).  So u(xj) - u(xi) <
 //   0.9698 + 0.0118 < 1 and floor(u(xj)) <= floor(u(xi)) + 1; the clamp is monotone and only joins cells.  A difference x - origin
 //   that overflows is +inf, its cell the clamp.  No NaN arises from finite inputs (inv_h is finite and positive: 1e-23 < h < 2e19).
+// Below the origin (a query q of another model, nb_cell_signed; the records' own x stay at or above the origin): u is the same
+//   monotone function for x < origin, where it is negative, and the bounds above hold for |u| < 2^15 whatever the sign: a pair (q, xj)
+//   within rmax differs by less than 1 in u, so floor(u(xj)) - floor(u(q)) is -1, 0 or 1 also where u(q) < 0 (floor, not truncation:
+//   nb_cell_signed takes floorf).  Every record has u >= 0, a cell of 0 or above.  So a query with floor(u(q)) = -1 finds its partners
+//   in cell 0 alone, which the walk visits (the cells -2 and -1 wrap above kNbMaxCell and are dropped), and a query with floor(u(q))
+//   <= -2 has u(q) < -1 <= u(xj) - 1 for every record: no record is within rmax on this axis.  nb_cell_signed returns -2 for all of
+//   them, and for a difference that overflows to -inf: the caller skips the walk.  Above the box a query's cell may be the clamp while a
+//   partner's is kNbMaxCell - 1 or the clamp: the clamp only joins cells, the difference stays at most 1.
 template <class V>
 __device__ inline void nb_walk(const NbFrame& g, const NeighborJob& job, const NbCell& own, V visit) {
     bool go = true;  // (tested where the loops test their ends, as a count against a cap would be: a return from inside costs more)

@@ -63,6 +63,16 @@ GSX_NB_HD inline uint32_t nb_cell(float x, float origin, float inv_h) {
     return u >= (float)kNbMaxCell ? kNbMaxCell : (uint32_t)u;  // (u >= 0; +inf clamps)
 }
 
+// The cell of a coordinate that need not lie at or above the origin (a query of another model: gsx_model_nearest, spec section 23):
+// floor(u) for the same u, clamped to [-2, kNbMaxCell]; x and origin finite.  At or above the origin it is nb_cell's cell.  -1 is
+// the cell below the grid's first, whose neighbour 0 holds records; -2 stands for every cell further down, none of whose neighbours
+// holds any (neighbors_grid.h: nb_walk's proof, extended below the origin).  A difference that overflows to -inf gives -2.
+GSX_NB_HD inline int32_t nb_cell_signed(float x, float origin, float inv_h) {
+    const float u = floorf((x - origin) * inv_h);
+    if (u >= (float)kNbMaxCell) return (int32_t)kNbMaxCell;
+    return u >= -2.0f ? (int32_t)u : -2;
+}
+
 // The 32-bit hash of a cell; its low `bits` bits are the bucket.
 GSX_NB_HD inline uint32_t nb_hash(uint32_t cx, uint32_t cy, uint32_t cz) {
     uint32_t k = cx * 0x9E3779B1u + cy * 0x85EBCA77u + cz * 0xC2B2AE3Du;

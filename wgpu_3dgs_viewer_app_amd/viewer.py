@@ -378,6 +378,69 @@ def _knn_stats(out, d2, score) -> ModelKnn:
 
 
 @dataclasses.dataclass
+class ModelNearest:
+    """What ``MultiModelViewerModel.nearest`` returns.  ``index`` (uint32, one per Gaussian of this model, or ``None``): the nearest
+    participating Gaussian of the target model, ``_lib.GSX_NEAREST_NONE`` where this one does not participate or nothing is in
+    reach; ``d2`` (float32): the squared distance in the target's model space, ``+inf`` there; ``count`` / ``n_nonfinite``: the
+    participating queries and those that pass the filter without a finite position; ``targets`` / ``targets_nonfinite``: the same
+    of the target model; ``n_found``; ``d_min``, ``d_max`` (the one-sided Hausdorff distance), ``mean`` (the one-sided chamfer
+    distance), ``rms``: over the found queries; ``first_radius``, ``rounds``, ``n_brute``, ``grid_bits``: what the search ran;
+    ``xform`` (float32, ``(3, 4)``): the matrix used."""
+
+    index: np.ndarray | None
+    d2: np.ndarray | None
+    count: int
+    n_nonfinite: int
+    targets: int
+    targets_nonfinite: int
+    n_found: int
+    d_min: np.float32
+    d_max: np.float32
+    mean: float
+    rms: float
+    first_radius: np.float32
+    rounds: int
+    n_brute: int
+    grid_bits: int
+    xform: np.ndarray
+
+
+def _nearest_stats(out, index, d2) -> ModelNearest:
+    return ModelNearest(index, d2, int(out.count), int(out.n_nonfinite), int(out.targets), int(out.targets_nonfinite), int(out.n_found),
+                        np.float32(out.d_min), np.float32(out.d_max), float(out.mean), float(out.rms), np.float32(out.first_radius),
+                        int(out.rounds), int(out.n_brute), int(out.grid_bits), np.array(out.xform[:], np.float32).reshape(3, 4))
+
+
+def _nearest_desc(xform, model_transforms, src_filter, dst_filter, max_distance, radius_hint, grid_bits, max_rounds) -> "_lib.NearestDesc":
+    m = np.eye(3, 4, dtype=np.float32) if xform is None else np.ascontiguousarray(xform, np.float32).reshape(3, 4)
+    return _lib.NearestDesc(int(src_filter), int(dst_filter), _lib.GSX_NEAREST_MODEL_TRANSFORMS if model_transforms else 0, int(grid_bits),
+                            float(max_distance), float(radius_hint), int(max_rounds), 0, (C.c_float * 12)(*m.reshape(-1)))
+
+
+@dataclasses.dataclass
+class ModelAlignStep:
+    """What ``MultiModelViewerModel.align_step`` returns: the delta ``t ~ scale * R(quat) q + pos`` in the target's model space
+    (``quat`` x, y, z, w with w >= 0; float64), ``xform_next`` (float32, ``(3, 4)``) = delta o the matrix used, the next step's ``xform``;
+    ``n_pairs``; ``rms_before``: the pairs' rms distance before the step; ``degenerate``: too few pairs or no single best rotation,
+    the delta is the identity; ``nearest``: the search's statistics, without arrays."""
+
+    pos: np.ndarray
+    quat: np.ndarray
+    scale: float
+    xform_next: np.ndarray
+    n_pairs: int
+    rms_before: float
+    degenerate: bool
+    nearest: ModelNearest
+
+
+def _compose34(a, b):
+    """a o b of two 3x4 similarities, in float64"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.concatenate([a[:, :3] @ b[:, :3], (a[:, :3] @ b[:, 3] + a[:, 3])[:, None]], axis=1)
+
+
+@dataclasses.dataclass
 class ModelDecimate:
     """What ``MultiModelViewerModel.decimate`` and ``decimate_count`` return.  ``count``: participants (pass the filter, finite
     position); ``n_nonfinite``: passed the filter with a NaN or infinite coordinate (dropped); ``cells``: occupied cells, the new
@@ -594,6 +657,75 @@ class MultiModelViewerModel:
         _lib.check(self._v._L.gsx_model_select_knn(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected),
                                                    C.byref(out)))
         return int(hit.value), int(selected.value), _knn_stats(out, None, None)
+
+    def nearest(self, dst_key: str, xform=None, model_transforms: bool = False, src_filter: int = 0, dst_filter: int = 0,
+                max_distance: float = 0.0, radius_hint: float = 0.0, grid_bits: int = 0, max_rounds: int = 0,
+                rows: bool = True) -> ModelNearest:
+        """``gsx_model_nearest``: for every Gaussian of this model the nearest Gaussian of ``viewer.models[dst_key]`` (index and
+        squared distance; ``rows=False`` returns the statistics alone), on the device, bit for bit the brute-force answer with ties
+        going to the smaller index.  ``xform`` (3x4, default the identity) maps this model's space into the target's;
+        ``model_transforms=True`` takes it from the two models' transforms instead.  The filters are ``_lib.GSX_BOUNDS_*`` bits;
+        ``max_distance`` (0: unlimited) bounds both the answer and the cost.  ``.mean`` is the one-sided chamfer distance, ``.d_max``
+        the one-sided Hausdorff distance."""
+        n = self.gaussian_buffers.gaussians_buffer.len()
+        desc = _nearest_desc(xform, model_transforms, src_filter, dst_filter, max_distance, radius_hint, grid_bits, max_rounds)
+        index = np.full(n, _lib.GSX_NEAREST_NONE, np.uint32) if rows else None
+        d2 = np.full(n, np.inf, np.float32) if rows else None
+        out = _lib.NearestStats()
+        _lib.check(self._v._L.gsx_model_nearest(self._v._h, self._key.encode(), dst_key.encode(), C.byref(desc), index.ctypes.data if rows else None,
+                                                d2.ctypes.data if rows else None, C.byref(out)))
+        return _nearest_stats(out, index, d2)
+
+    def select_nearest(self, dst_key: str, lo: float = 0.0, hi: float = 0.0, transfer: bool = False, op: int = 0, xform=None,
+                       model_transforms: bool = False, src_filter: int = 0, dst_filter: int = 0, max_distance: float = 0.0,
+                       radius_hint: float = 0.0, grid_bits: int = 0, max_rounds: int = 0) -> tuple[int, int, ModelNearest]:
+        """``gsx_model_select_nearest``: writes THIS model's selection.  The hit set is the Gaussians whose distance to the target
+        model lies in ``[lo, hi]`` (``hi`` may be ``inf``: also those without a target in reach) or, with ``transfer=True``, those
+        whose nearest target is selected in ``dst_key``: a selection carried across models.  Overlap before a merge:
+        ``b.select_nearest("a", 0.0, d)``, then ``extract(..., SELECTED, invert=True)``.  Returns ``(hit, selected, stats)``."""
+        desc = _lib.NearestSelectDesc(_nearest_desc(xform, model_transforms, src_filter, dst_filter, max_distance, radius_hint, grid_bits, max_rounds),
+                                      int(op), _lib.GSX_NEAREST_SELECT_TRANSFER if transfer else _lib.GSX_NEAREST_SELECT_RANGE, float(lo), float(hi))
+        hit, selected, out = C.c_uint64(), C.c_uint64(), _lib.NearestStats()
+        _lib.check(self._v._L.gsx_model_select_nearest(self._v._h, self._key.encode(), dst_key.encode(), C.byref(desc), C.byref(hit),
+                                                       C.byref(selected), C.byref(out)))
+        return int(hit.value), int(selected.value), _nearest_stats(out, None, None)
+
+    def align_step(self, dst_key: str, xform=None, model_transforms: bool = False, with_scale: bool = False, src_filter: int = 0,
+                   dst_filter: int = 0, max_distance: float = 0.0, radius_hint: float = 0.0, grid_bits: int = 0,
+                   max_rounds: int = 0) -> ModelAlignStep:
+        """``gsx_model_align_step``: one least-squares step of point-to-point registration of this model onto ``dst_key``: the
+        nearest search (``max_distance`` rejects correspondences), the pairs' sums on the device, Horn's closed form on the host."""
+        desc = _lib.AlignDesc(_nearest_desc(xform, model_transforms, src_filter, dst_filter, max_distance, radius_hint, grid_bits, max_rounds),
+                              _lib.GSX_ALIGN_SCALE if with_scale else 0, 0)
+        out = _lib.AlignStep()
+        _lib.check(self._v._L.gsx_model_align_step(self._v._h, self._key.encode(), dst_key.encode(), C.byref(desc), C.byref(out)))
+        vec = lambda a: np.array(a[:], np.float32)  # noqa: E731
+        return ModelAlignStep(np.array(out.pos[:], np.float64), np.array(out.quat[:], np.float64), float(out.scale), vec(out.xform_next).reshape(3, 4), int(out.n_pairs),
+                              float(out.rms_before), bool(out.degenerate), _nearest_stats(out.nearest, None, None))
+
+    def align(self, dst_key: str, max_iters: int = 30, tol: float = 1e-6, xform=None, model_transforms: bool = False, **step_args):
+        """Iterative closest point: ``align_step`` until ``rms_before`` changes by less than ``tol`` relatively or does not fall any
+        more (with exact correspondences it ends at the float32 rounding of the positions, where it only flickers: a rise is the
+        end, whatever ``tol``), a step is degenerate or ``max_iters`` steps ran.  Returns ``(xform_final, D, steps)``: the final float32 3x4 matrix, the composed similarity
+        ``D`` (float64 3x4) with ``xform_final = D o xform_initial`` up to the steps' roundings, and the list of steps.  With an
+        identity start ``D`` is what ``apply_transform`` bakes or ``update_model_transform`` shows."""
+        steps, D, last = [], np.eye(3, 4), None
+        for _ in range(int(max_iters)):
+            st = self.align_step(dst_key, xform=xform, model_transforms=model_transforms and not steps, **step_args)
+            steps.append(st)
+            if xform is None:
+                xform = st.nearest.xform
+            if st.degenerate or (last is not None and (st.rms_before >= last or last - st.rms_before <= tol * last)):
+                break
+            last = st.rms_before
+            q = st.quat.astype(np.float64)
+            x, y, z, w = q / np.linalg.norm(q)
+            R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                          [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                          [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+            D = _compose34(np.concatenate([float(st.scale) * R, st.pos.astype(np.float64)[:, None]], axis=1), D)
+            xform = st.xform_next
+        return np.asarray(xform, np.float32).reshape(3, 4), D, steps
 
     def _decimate(self, dst_key, cell, filter, invert, grid_bits, want_map):  # noqa: A002
         desc = _lib.DecimateDesc(int(filter), _lib.GSX_EXTRACT_INVERT if invert else 0, float(cell), int(grid_bits))
