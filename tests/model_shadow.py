@@ -1,15 +1,21 @@
 """A host shadow of a viewer's models, for tests/test_model_shadow_cpu.py and tests/test_gpu_model_fuzz.py: what a long session of
-model operations (gsx_model_extract, _merge, _convert, _set_pod_kind, _apply_transform, _import_ply, the selects by property, neighbour
-count, cluster and nearest neighbours, gsx_mask_evaluate, the uploads) leaves in every model, kept on the host, without a GPU and
-without libgsx.  Per model key: the pod kind, the dequantised planes as gsx_model_download_pod returns them, the model transform, the
-mask bits, the selection bits, the stored edit records (each or none) and show-unedited.
+model operations (gsx_model_extract, _merge, _convert, _set_pod_kind, _apply_transform, _import_ply, _decimate, the selects by
+property, neighbour count, cluster, nearest neighbours and nearest in another model, gsx_mask_evaluate, the uploads) leaves in every
+model, kept on the host, without a GPU and without libgsx.  Per model key: the pod kind, the dequantised planes as
+gsx_model_download_pod returns them, the model transform, the mask bits, the selection bits, the stored edit records (each or none)
+and show-unedited.
 
 No arithmetic is stated here.  Every operation is applied with the restatements the repository already has: the kept set, its order
 and the participation set of the spatial calls are tests/extract_ref.py's `kept`; the selects are property_ref / neighbors_ref /
 clusters_ref / knn_ref (bit-exact float32 answers: the words are compared exactly); a mask program is oracle.mask_evaluate over the
 shadow's positions; positions after a transform or a baked merge are transform_ref.position, bit for bit; bounds are
 bounds_ref.reference.  Extract, an identity-source merge and a translation reproduce the shadow's own rows for the kept indices,
-byte for byte, and every row outside a transform's kept set stays as it was.
+byte for byte, and every row outside a transform's kept set stays as it was.  A decimate's cells, map, statistics and order are
+decimate_ref.assign's; its one-member cells are the shadow's own rows; its merged rows are VERIFIED, not adopted: they are the float32
+rows of tests/decimate_driver.cpp (which shares csrc/decimate_math.h with the kernels) played on the shadow's planes of the source,
+uploaded in the source's kind into the other viewer, and the two downloads must be the same bytes in every plane.  The nearest calls
+across two models are nearest_ref's `brute` under the matrix nearest_ref.model_matrix gives (index, d2 and every selection word bit for
+bit); the delta of an align step is BOUNDED, not exact: within tests/test_gpu_nearest.py's formula of the float64 SVD solve.
 
 What the shadow ADOPTS from the device instead of verifying, on purpose (the per-op suites bound these against float64): the baked
 covariance and SH of gsx_model_merge and of a scaling or rotating gsx_model_apply_transform (the kept rows only), the covariance and
@@ -33,9 +39,11 @@ import oracle
 from tests import bounds_ref as B
 from tests import clusters_ref as CL
 from tests import common
+from tests import decimate_ref as D
 from tests import extract_ref as X
 from tests import knn_ref as K
 from tests import merge_ref as M
+from tests import nearest_ref as R
 from tests import neighbors_ref as N
 from tests import property_ref as P
 from tests import transform_ref as T
@@ -60,20 +68,26 @@ SPATIAL_N = 2500
 
 CAMERA = ("cam_step", "cam_jump", "viewport", "visibility", "display", "model_transform")
 STATE = ("mask_eval", "sel_upload", "sel_edit", "edits_upload", "unedited", "rect_query")
-SELECTS = ("select_range", "select_neighbors", "select_clusters", "select_knn")
-READ_ONLY = ("bounds", "histogram", "property_values", "neighbors", "clusters", "knn", "export", "export_ply")
-MODEL_CHANGING = ("xf_translate", "xf_scale", "xf_full", "set_pod_kind", "convert", "extract", "merge", "ply_roundtrip", "remove_add")
+SELECTS = ("select_range", "select_neighbors", "select_clusters", "select_knn", "select_nearest")
+READ_ONLY = ("bounds", "histogram", "property_values", "neighbors", "clusters", "knn", "export", "export_ply", "decimate_edge", "nearest", "align_step")
+MODEL_CHANGING = ("xf_translate", "xf_scale", "xf_full", "set_pod_kind", "convert", "extract", "merge", "ply_roundtrip", "remove_add", "decimate")
 FEATURES = ("depth_test", "hit_pairs", "gizmos")
-SPATIAL = ("select_neighbors", "select_clusters", "select_knn", "neighbors", "clusters", "knn")
+SPATIAL = ("select_neighbors", "select_clusters", "select_knn", "neighbors", "clusters", "knn", "nearest", "select_nearest", "align_step")
+NEAREST_FAMILY = ("nearest", "select_nearest", "align_step")  # two keys: the queries' model `key` and the targets' `dst`
 OP_KINDS = CAMERA + STATE + SELECTS + READ_ONLY + MODEL_CHANGING + FEATURES
 #: the variants condition (b) asks a non-trivial hit set of, each at least once over the seed set
 SELECT_VARIANTS = ("select_range:model", "select_range:world", "select_neighbors", "select_clusters:0", "select_clusters:1", "select_clusters:2",
-                   "select_knn:range", "select_knn:std_ratio")
+                   "select_knn:range", "select_knn:std_ratio", "select_nearest:range", "select_nearest:transfer")
+#: condition (f): src != dst under GSX_NEAREST_MODEL_TRANSFORMS; src != dst of different pod kinds; src == dst with different filters and
+#: a query that is no target; a max_distance within which some but not all queries find a target
+NEAREST_CASES = ("nearest:model_transforms", "nearest:kinds", "nearest:same_disjoint", "nearest:max_distance")
 VIEWPORTS = [(W, H), (80, 64), (96, 80), (83, 51), (320, 240)]  # the last: 300 tiles, blocks of several tiles
 MASK_EXPRS = [None, "0", "!1", "0 - 1", "0 | 1"]
 FILTERS = [0, X.MASKED, X.SKIP_HIDDEN, X.MASKED | X.SKIP_HIDDEN, X.SELECTED, X.MASKED | X.SELECTED, X.SKIP_HIDDEN | X.SELECTED,
            X.MASKED | X.SKIP_HIDDEN | X.SELECTED]
 ZERO3, ONE3, IDENT = np.zeros(3, F), np.ones(3, F), np.array([0, 0, 0, 1], F)
+IDENTITY34 = np.eye(3, 4, dtype=F)
+ALIGN_TOL_MAX = 1e-3  # an align draw whose tolerance formula exceeds this is drawn again (tests/test_gpu_nearest.py's bound on "the inverse motion")
 
 
 def mask_shapes():
@@ -157,7 +171,7 @@ _MEMO: dict = {}
 def memo(fn, *arrays_then_args):
     """fn(*arrays_then_args), remembered by the bytes of its arguments: a draw and the op it draws ask the same brute-force
     restatement of the same positions"""
-    h = hashlib.blake2b(fn.__name__.encode(), digest_size=16)
+    h = hashlib.blake2b((fn.__module__ + "." + fn.__qualname__).encode(), digest_size=16)
     for a in arrays_then_args:
         h.update(np.ascontiguousarray(a).tobytes() if isinstance(a, np.ndarray) else repr(a).encode())
     key = h.digest()
@@ -308,6 +322,98 @@ class Shadow:
             hit = part & (s > F(threshold)) if np.isfinite(s[part]).any() else np.zeros(m.n, bool)
         return self._select(m, hit, op)
 
+    def decimate(self, src, dst, cell, flt=0, invert=False, driver=None):
+        """gsx_model_decimate.  Returns (stats, map, exact rows of dst's planes): stats = (count, n_nonfinite, cells, singletons,
+        largest_cell) and the map are decimate_ref.assign's over the kept set; dst holds one row per cell in ascending order of the
+        cell's representative (its smallest index).  A one-member cell's row is src's stored row, exact in every plane.  A merged
+        cell's row is `driver`'s float32 row (tests/decimate_driver.cpp played on src's planes), which the device quantises once in
+        src's kind: known where the kind stores float32; without a driver it is the representative's row and unknown in every plane.
+        0 cells create nothing."""
+        s = self.models[src]
+        kept = np.zeros(s.n, bool)
+        kept[s.kept(flt, invert)] = True
+        dmap, count, nonfinite, members = D.assign(s.pos, kept, cell)
+        cells = int(members.size)
+        stats = (count, nonfinite, cells, int((members == 1).sum()), int(members.max()) if cells else 0)
+        if cells == 0:
+            return stats, dmap, None
+        idx = np.nonzero(dmap != D.NO_CELL)[0]
+        rep = np.full(cells, s.n, np.int64)
+        np.minimum.at(rep, dmap[idx].astype(np.int64), idx)
+        rows, merged = _rows(s.planes, rep), members > 1
+        if driver is not None:
+            want = D.play(driver, s.planes, kept, cell)
+            assert (want["count"], want["n_nonfinite"], want["cells"], want["singletons"], want["largest_cell"]) == stats and np.array_equal(want["map"], dmap)
+            for mine, theirs in zip(rows, want["planes"]):
+                assert mine[~merged].tobytes() == np.ascontiguousarray(theirs[~merged]).tobytes()  # (copied, not computed)
+                mine[merged] = theirs[merged]
+        d = self.add(dst, s.kind, rows, s.mt)
+        known = [True, True, s.kind[0] == 0, s.kind[1] == 0] if driver is not None else [False] * 4
+        return stats, dmap, [~merged | np.full(d.n, k) for k in known]
+
+    def nearest(self, src, dst, src_filter=0, dst_filter=0, xform=None, model_transforms=False, max_distance=0.0):
+        """gsx_model_nearest restated: nearest_ref's participants and `brute` (remembered: a draw and its op ask the same) over the
+        two shadow models, under `xform` (the matrix a device returned, or None: nearest_ref.model_matrix of the two model
+        transforms, or the identity).  Both selections are read as they are now."""
+        s, t = self.models[src], self.models[dst]
+        if xform is None:
+            xform = R.model_matrix(s.mt, t.mt) if model_transforms else IDENTITY34
+        xform = np.ascontiguousarray(xform, F).reshape(3, 4)
+        q, q_part, q_bad = R.query_participates(xform, s.pos, s.passes(src_filter))
+        t_pass = t.passes(dst_filter)
+        t_part = N.participates(t.pos, t_pass)
+        index, d2 = memo(R.brute, q, q_part, t.pos, t_part, float(max_distance))
+        return dict(xform=xform, q=q, index=index, d2=d2, q_part=q_part, count=int(q_part.sum()), n_nonfinite=int(q_bad.sum()), t_part=t_part,
+                    targets=int(t_part.sum()), targets_nonfinite=int((t_pass & ~t_part).sum()), **R.stats(index, d2))
+
+    def select_nearest(self, src, dst, transfer=False, lo=0.0, hi=0.0, op=0, src_filter=0, dst_filter=0, xform=None, model_transforms=False,
+                       max_distance=0.0):
+        """gsx_model_select_nearest: writes the SOURCE's selection.  GSX_BOUNDS_SELECTED on either side and the transfer read the
+        selections as they are before the call, also where src is dst"""
+        s, t = self.models[src], self.models[dst]
+        before = None if t.sel is None else t.sel.copy()
+        ref = self.nearest(src, dst, src_filter, dst_filter, xform, model_transforms, max_distance)
+        hit = R.hit(ref["index"], ref["d2"], ref["q_part"], R.SELECT_TRANSFER if transfer else R.SELECT_RANGE, lo, hi, before)
+        return self._select(s, hit, op)
+
+    def align(self, src, dst, xform, with_scale=False, src_filter=0, dst_filter=0, max_distance=0.0):
+        """gsx_model_align_step restated: the pairs of `nearest`, nearest_ref.align_sums and align_solve.  `tol` is
+        tests/test_gpu_nearest.py's bound on quaternion, scale and pos, from the reference's own Horn matrix; `degenerate` is spec
+        §23's: fewer than 3 pairs, no spread among the queries, or an eigenvalue gap at or below 1e-9 of the matrix's norm"""
+        ref = self.nearest(src, dst, src_filter, dst_filter, xform, False, max_distance)
+        found = ref["index"] != R.NONE
+        sums = R.align_sums(ref["q"][found], self.models[dst].pos[ref["index"][found]])
+        n = sums["n"]
+        Nm = R.horn_matrix(sums["H"])
+        w = np.linalg.eigvalsh(Nm)
+        norm, gap = float(np.linalg.norm(Nm)), float(w[-1] - w[-2])
+        degenerate = n < 3 or sums["spread_q"] == 0 or gap <= 1e-9 * norm
+        out = dict(nearest=ref, n_pairs=n, degenerate=degenerate, norm=norm, gap=gap, tol=np.inf, angle=0.0,
+                   rms_before=float(np.sqrt(ref["d2"][found].astype(np.float64).sum() / n)) if n else 0.0)
+        if not degenerate:
+            want = R.align_solve(sums, with_scale)
+            out.update(want, tol=10 * (2 * n * 2.0 ** -53) * norm / gap, angle=float(np.degrees(2 * np.arccos(min(1.0, want["quat"][3])))))
+        return out
+
+
+def unmet(cases, decimates):
+    """conditions (e), (f) and (h) of tests/test_gpu_model_fuzz.py over a seed set, stated once: `cases` is the union of the
+    sessions' `cases`, `decimates` all their `decimates` records.  Returns what is not met."""
+    out = []
+    if not any(d["filtered"] for d in decimates):
+        out.append("(e) no decimate of a source with a mask or selection filter in force")
+    if not any(d["kind_differs"] for d in decimates):
+        out.append("(e) no decimate of a source whose kind is not the seed's start kind")
+    for d in decimates:
+        if not (MIN_N <= d["cells"] < d["count"] and 0 < d["singletons"] < d["cells"]):
+            out.append(f"(e) a decimate without both merged cells and singletons, or below MIN_N: {d}")
+    if not any(d["largest_cell"] >= 3 for d in decimates):
+        out.append("(e) no decimate with a cell of three or more members")
+    out += [f"(f) no nearest-family call with {c}" for c in NEAREST_CASES if c not in cases]
+    if "align:rotation" not in cases:
+        out.append("(h) no align draw that is not degenerate with a reference rotation above 1 degree")
+    return out
+
 
 # ---- the schedule -------------------------------------------------------------------------------------------------------------------
 def plan(seed):
@@ -354,8 +460,12 @@ def _plain(v):
 class Session:
     """One seed: the shadow, the view state both viewers are given, the random stream and the log of ops drawn so far."""
 
-    def __init__(self, seed):
+    def __init__(self, seed, driver=None):
         self.seed = seed
+        self.driver = driver           # tests/decimate_driver.cpp, built (decimate_ref.build_driver): the merged rows of a decimate
+        self.cases: set = set()        # NEAREST_CASES and "align:rotation" as the draws met them (conditions (f) and (h))
+        self.decimates: list = []      # a record per decimate (condition (e))
+        self.parent: dict = {}         # key -> the model it was extracted, converted or decimated from
         self.rng = np.random.default_rng(7000 + seed)
         self.lanes, self.host_verify = 1 + seed % 3, seed % 3
         self.kind = START_KINDS[seed % len(START_KINDS)]
@@ -430,6 +540,116 @@ class Session:
             r, k = float(F(mul * memo(K.kth_distance_median, m.pos, m.part(0), k))), k + 1
         return r
 
+    def _kept_bits(self, m, flt, invert):
+        out = np.zeros(m.n, bool)
+        out[m.kept(flt, invert)] = True
+        return out
+
+    def _target(self, m, flt, invert):
+        """a cell count for gsx_model_decimate_edge: within [max(MIN_N, kept / 4), kept / 2], or the lower end where that is empty"""
+        k = int(m.kept(flt, invert).size)
+        lo = max(MIN_N, k // 4)
+        return int(self.rng.integers(lo, max(lo, k // 2) + 1))
+
+    def _decimate_cell(self, m, flt, invert):
+        """(cell, flt, invert) of a decimate that leaves at least MIN_N cells: the edge decimate_ref.find_edge gives for a drawn
+        target; where that leaves fewer (the count is not monotone in the edge) the median nearest-neighbour distance; where that
+        does too, the same without a filter"""
+        for f, inv in ((flt, invert), (0, False)):
+            kept = self._kept_bits(m, f, inv)
+            edge, cells = memo(D.find_edge, m.pos, kept, self._target(m, f, inv))
+            if cells < MIN_N:
+                edge = F(self._radius(m, 1, 1.0))
+                cells = D.assign(m.pos, kept, edge)[3].size
+            if cells >= MIN_N:
+                return float(edge), f, inv
+        raise AssertionError("no cell edge leaves MIN_N cells")
+
+    def _descends(self, key, ancestor):
+        while key in self.parent:
+            key = self.parent[key]
+            if key == ancestor:
+                return True
+        return False
+
+    def _target_key(self, key, same=0.3, prefer_descendant=False):
+        """the target model of a nearest-family call from `key`: another model of at most SPATIAL_N, or `key` itself with probability
+        `same` and where there is no other"""
+        sh = self.shadow
+        others = [k for k in self.keys() if k != key and sh.models[k].n <= SPATIAL_N]
+        if not others or self.rng.random() < same:
+            return key
+        if prefer_descendant and any(self._descends(k, key) for k in others):
+            others = [k for k in others if self._descends(k, key)]
+        return others[int(self.rng.integers(len(others)))]
+
+    def _rigid(self, max_deg, max_shift, centre=ZERO3, scale=1.0, min_deg=0.0):
+        """float32[3, 4]: a rotation by min_deg .. max_deg about a random axis through `centre`, scaled about it, then a shift of at
+        most max_shift"""
+        rng = self.rng
+        axis, shift = rng.normal(size=3), rng.normal(size=3)
+        half = np.radians(rng.uniform(min_deg, max_deg)) / 2
+        A = scale * R.quat_rows(np.concatenate([axis / np.linalg.norm(axis) * np.sin(half), [np.cos(half)]]))
+        c = np.asarray(centre, np.float64)
+        b = c - A @ c + shift / np.linalg.norm(shift) * rng.uniform(0, max_shift)
+        return np.concatenate([A, b[:, None]], axis=1).astype(F)
+
+    def _nearest_args(self, key, dst, n_of):
+        """the parameters the nearest-family calls share, alternated on `n_of` so that the seed set meets condition (f): the mapping
+        (src != dst: the model transforms, a drawn similarity, the identity; src == dst: the identity), the two filters (src == dst
+        with a mask and a selection: one against the other) and, every other time, a max_distance: the power-of-two multiple of the
+        targets' median nearest-neighbour distance nearest to the queries' median distance within which some but not all find a target"""
+        sh, rng = self.shadow, self.rng
+        s, t = sh.models[key], sh.models[dst]
+        a = dict(dst=dst, model_transforms=False, xform=None, src_filter=self._filter(s)[0], dst_filter=self._filter(t)[0], max_distance=0.0)
+        if key != dst:
+            how = n_of % 3
+            if how == 0:
+                a.update(model_transforms=True)
+            elif how == 1:
+                a.update(xform=self._rigid(40.0, 0.5, scale=float(rng.uniform(0.8, 1.25))))
+        elif s.mask is not None and s.sel is not None:
+            fs, fd = (X.SELECTED, X.MASKED) if n_of % 2 else (X.MASKED, X.SELECTED)
+            if min(s.kept(fs).size, s.kept(fd).size) >= MIN_N:
+                a.update(src_filter=fs, dst_filter=fd)
+        ref = sh.nearest(key, dst, a["src_filter"], a["dst_filter"], a["xform"], a["model_transforms"])
+        if (n_of // 3) % 2 == 0 and ref["n_found"]:
+            d2 = ref["d2"][ref["index"] != R.NONE]
+            r = self._radius(t, 1, 1.0)
+            reach = [float(F(r * 2.0 ** k)) for k in range(-6, 9)]
+            some = [md for md in reach if 0 < int((d2 <= R.cap2(md)).sum()) < ref["count"]]
+            if some:
+                mid = max(float(np.sqrt(np.median(d2))), min(some))
+                a.update(max_distance=min(some, key=lambda md: abs(np.log(md / mid))))
+                ref = sh.nearest(key, dst, a["src_filter"], a["dst_filter"], a["xform"], a["model_transforms"], a["max_distance"])
+                self.cases.add("nearest:max_distance")
+        if key != dst and a["model_transforms"]:
+            self.cases.add("nearest:model_transforms")
+        if key != dst and s.kind != t.kind:
+            self.cases.add("nearest:kinds")
+        if key == dst and a["src_filter"] != a["dst_filter"] and (ref["q_part"] & ~ref["t_part"]).any():
+            self.cases.add("nearest:same_disjoint")
+        return a, ref
+
+    def _align_args(self, key):
+        """dst, a small rigid `xform` about the targets' centre (at most 5 degrees, a shift of at most half their median
+        nearest-neighbour distance), with_scale and the filters of an align step, drawn again (then from the model onto itself, without
+        filters) while the reference's tolerance formula exceeds ALIGN_TOL_MAX"""
+        sh, rng = self.shadow, self.rng
+        for attempt in range(4):
+            dst = self._target_key(key, prefer_descendant=True) if attempt < 2 else key
+            s, t = sh.models[key], sh.models[dst]
+            fs, fd = (self._filter(s)[0], self._filter(t)[0]) if attempt < 2 else (0, 0)
+            centre = B.reference(t.pos, t.passes(fd))["center"]
+            a = dict(dst=dst, xform=self._rigid(5.0, 0.5 * self._radius(t, 1, 1.0), centre, min_deg=0.5), with_scale=bool(rng.random() < 0.5),
+                     src_filter=fs, dst_filter=fd, max_distance=0.0)
+            ref = sh.align(key, a["dst"], a["xform"], a["with_scale"], fs, fd)
+            if ref["degenerate"] or ref["tol"] <= ALIGN_TOL_MAX:
+                break
+        if not ref["degenerate"] and ref["angle"] > 1.0:
+            self.cases.add("align:rotation")
+        return a
+
     def draw(self, kind):
         rng, sh, v = self.rng, self.shadow, self.view
         keys = self.keys()
@@ -482,12 +702,23 @@ class Session:
                 op.update(mode=mode, r=self._radius(m, 1, 1.0 if mode != CL.LARGEST else 1.5), size_lo=by_size, size_hi=by_size)
                 if mode == CL.SEEDED and not m.selection().any():
                     op.update(seeds=int(rng.integers(1 << 30)))  # a model without a selection gets a sparse one first
+            elif kind == "select_nearest":
+                transfer = bool(n_of % 2)
+                a, ref = self._nearest_args(key, self._target_key(key), n_of // 2)
+                op.update(a, flt=a["src_filter"], transfer=transfer, lo=0.0, hi=0.0)
+                del op["src_filter"]
+                if not transfer:
+                    d = np.sqrt(ref["d2"][ref["index"] != R.NONE])
+                    lo, hi = np.quantile(d, [0.25, 0.6]).astype(F) if d.size else (F(0), F(0))
+                    op.update(lo=float(lo), hi=float(hi))
+                elif not sh.models[op["dst"]].selection().any():
+                    op.update(dst_seeds=int(rng.integers(1 << 30)))  # a target model without a selection gets one first
             else:
                 part, _, s = sh.knn_scores(key, 3, K.SCORE_KTH, op["flt"])
                 outliers = bool(n_of % 2)  # (score above mean + std_ratio * std; the range is then not looked at and must be 0)
                 op.update(k=3, score=K.SCORE_KTH, lo=0.0, hi=0.0 if outliers else float(np.median(s[part & np.isfinite(s)])), std_ratio=1.0 if outliers else None)
         elif kind in READ_ONLY:
-            flt, invert = self._filter(m, invertible=kind in ("export", "export_ply"))
+            flt, invert = self._filter(m, invertible=kind in ("export", "export_ply", "decimate_edge"))
             op.update(key=key, flt=flt, inflight=inflight if rng.random() < 0.5 else 0)
             if kind == "bounds":
                 op.update(trim=int(rng.choice([0, 50])))
@@ -501,6 +732,16 @@ class Session:
                 op.update(r=self._radius(m, 2, 1.0))
             elif kind == "knn":
                 op.update(k=int(rng.choice([1, 3, 8])), score=int(rng.integers(0, 2)))
+            elif kind == "decimate_edge":
+                op.update(invert=invert, target=self._target(m, flt, invert))
+            elif kind == "nearest":
+                a, _ = self._nearest_args(key, self._target_key(key), self.ran.get(kind, 0) + self.seed)
+                op.update(a, flt=a["src_filter"])
+                del op["src_filter"]
+            elif kind == "align_step":
+                a = self._align_args(key)
+                op.update(a, flt=a["src_filter"])
+                del op["src_filter"]
             else:
                 op.update(invert=invert)
         elif kind in ("xf_translate", "xf_scale", "xf_full"):
@@ -525,6 +766,19 @@ class Session:
                       remove_src=bool(rng.random() < 0.5), inflight=inflight)
             if kind == "convert":
                 op.update(to=KINDS[int(rng.integers(len(KINDS)))])
+            self.parent[op["dst"]] = key
+        elif kind == "decimate":
+            flt, invert = self._filter(m, invertible=True)
+            if (self.ran.get(kind, 0) + self.seed) % 2 == 0:  # every other one: a model that has a mask or a selection, under that filter
+                dressed = [(k, f) for k in keys for f, bits in ((X.MASKED, sh.models[k].mask), (X.SELECTED, sh.models[k].sel))
+                           if bits is not None and sh.models[k].kept(f).size >= 2 * MIN_N]
+                if dressed:
+                    (key, flt), invert = dressed[int(rng.integers(len(dressed)))], False
+                    m = sh.models[key]
+            cell, flt, invert = self._decimate_cell(m, flt, invert)
+            op.update(key=key, dst=self._new_key(), cell=cell, flt=flt, invert=invert, evict=self._evict([key]), remove_src=bool(rng.random() < 0.5),
+                      inflight=inflight)
+            self.parent[op["dst"]] = key
         elif kind == "merge":
             other = [k for k in keys if k != key and sh.models[k].n + m.n <= MAX_N]
             srcs = [key, other[int(rng.integers(len(other)))]] if other else ([key, key] if 2 * m.n <= MAX_N else [key])
@@ -593,7 +847,7 @@ class Session:
             return []
         elif kind in READ_ONLY:
             if dev is not None:
-                dev.read_only(op, sh.models[op["key"]])
+                dev.read_only(op, sh)
             return []
         elif kind in MODEL_CHANGING:
             return self._apply_model_op(op, dev)
@@ -609,8 +863,20 @@ class Session:
             m.sel = random_bits(m.n, op["seeds"], 0.02)
             if dev is not None:
                 dev.upload_selection(key, m.sel)
-        got = dev.select(op) if dev is not None else None  # (hit, selected[, threshold])
-        if kind == "select_range":
+        if op.get("dst_seeds") is not None:
+            t = sh.models[op["dst"]]
+            t.sel = random_bits(t.n, op["dst_seeds"], 0.3)
+            if dev is not None:
+                dev.upload_selection(op["dst"], t.sel)
+        got = dev.select(op) if dev is not None else None  # (hit, selected[, threshold or the matrix used])
+        if kind == "select_nearest":
+            target = None if sh.models[op["dst"]].sel is None else sh.models[op["dst"]].sel.copy()
+            want = sh.select_nearest(key, op["dst"], op["transfer"], op["lo"], op["hi"], op["op"], op["flt"], op["dst_filter"],
+                                     op["xform"] if got is None else got[2], op["model_transforms"], op["max_distance"])
+            variant = "select_nearest:" + ("transfer" if op["transfer"] else "range")
+            if dev is not None and op["dst"] != key:  # the target's selection is read, never written
+                dev.check_selection(op["dst"], sh.models[op["dst"]].selection() if target is None else target, upload=False)
+        elif kind == "select_range":
             want, variant = sh.select_range(key, op["prop"], op["lo"], op["hi"], world=op["world"], **a), "select_range:" + ("world" if op["world"] else "model")
         elif kind == "select_neighbors":
             want, variant = sh.select_neighbors(key, op["r"], op["lo"], op["hi"], **a), kind
@@ -655,6 +921,23 @@ class Session:
                 removed.append(op["key"])
                 if dev is not None:
                     dev.remove([op["key"]])
+        elif kind == "decimate":
+            key, dst, src = op["key"], op["dst"], sh.models[op["key"]]
+            assert self.driver is not None, "a session that decimates needs the built tests/decimate_driver.cpp"
+            stats, dmap, exact[dst] = sh.decimate(key, dst, op["cell"], op["flt"], op["invert"], self.driver)
+            in_force = bool(op["flt"] & X.MASKED and src.mask is not None) or bool(op["flt"] & X.SELECTED and src.sel is not None)
+            self.decimates.append(dict(filtered=in_force, kind_differs=src.kind != self.kind, count=stats[0], cells=stats[2], singletons=stats[3],
+                                       largest_cell=stats[4]))
+            if dev is not None:
+                got = dev.live.models[key].decimate(dst, op["cell"], op["flt"], op["invert"], want_map=True)
+                assert (got.count, got.n_nonfinite, got.cells, got.singletons, got.largest_cell) == stats, (got, stats)
+                assert np.array_equal(got.map, dmap), "the decimate's map"
+            changed, requantised = [dst], [dst]  # (rebuilt from the driver's float32 rows, uploaded in src's kind: test_gpu_decimate's yardstick)
+            if op["remove_src"]:
+                sh.remove(key)
+                removed.append(key)
+                if dev is not None:
+                    dev.remove([key])
         elif kind == "merge":
             srcs = list(op["srcs"])
             if op.get("via"):

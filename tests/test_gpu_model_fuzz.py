@@ -11,14 +11,29 @@ device instead.  A failure's message names the seed, the step and the ops so far
 
 Conditions that keep this from passing vacuously, asserted by test_conditions_over_the_seed_set: (a) every op kind ran; (b) every
 select variant had a hit set neither empty nor full; (c) every op kind that changes a model was followed, before the next such op, by
-a speculated frame of a model it changed; (d) model-changing ops ran with two frames enqueued and not waited for.  The run of camera
-steps after a model-changing op is model_shadow.POST_OP_RUN = 5: a changed model's first frame on each of up to three lanes is
-unspeculated, the fourth and fifth speculate.
+a speculated frame of a model it changed (a decimated model among them); (d) model-changing ops ran with two frames enqueued and not
+waited for.  The run of camera steps after a model-changing op is model_shadow.POST_OP_RUN = 5: a changed model's first frame on each
+of up to three lanes is unspeculated, the fourth and fifth speculate.  For gsx_model_decimate and the nearest calls across two models,
+stated once in model_shadow.unmet and proven for the default seeds without a GPU by tests/test_model_shadow_cpu.py: (e) some decimate
+had a source under a mask or selection filter and some a source of another kind than the seed's first, every decimate left at least
+MIN_N cells, merged ones and singletons both, and some cell had three members or more; (f) a nearest call ran between two models
+under GSX_NEAREST_MODEL_TRANSFORMS, between two of different pod kinds, from a model to itself with different filters, and with a
+max_distance that some but not all queries met; (g) a decimate and a select_nearest ran with two frames enqueued and not waited for;
+(h) an align step was not degenerate with a reference rotation above 1 degree.
 
-Cost, measured on an MI355X: a seed takes 0.4 to 0.75 s, of which 0.10 to 0.22 s are the hundred frames of both viewers (a seed of
-test_gpu_speculation.py::test_fuzz_operation_sequences, which has no host reference, takes 0.08 to 0.15 s); the rest is the host's
-brute-force restatements and the downloads.  That is why a seed has only two ops beyond its walk through the kinds, and why the
-spatial ops draw a model of at most model_shadow.SPATIAL_N Gaussians when there is one."""
+A decimated model is settled as a requantised one: the other viewer's copy is uploaded from the float32 rows of
+tests/decimate_driver.cpp (built once per module, a host program) in the source's kind, and the two downloads are the same bytes in
+every plane.  The matrix of GSX_NEAREST_MODEL_TRANSFORMS is nearest_ref.model_matrix bit for bit, except the entries that are nothing
+but the float64 rounding noise of a sum that cancels (_matrix_noise: the off-diagonal 1e-17s between a model and its decimated copy,
+which share a transform), where the device's entry must be noise too; index, d2 and the selection words are then `brute`'s under the
+RETURNED matrix, bit for bit.  The align delta is bounded by tests/test_gpu_nearest.py's formula from the reference's own Horn matrix:
+over the default seeds and the directed test the bound was 7.3e-13 to 8.3e-12 and the deviation 1.2e-16 to 8.9e-16 (359 to 2534 pairs).
+
+Cost, measured on an MI355X in one session: a seed takes 0.41 to 1.11 s, of which 0.09 to 0.25 s are the hundred and more frames of
+both viewers; the same seeds took 0.39 to 0.91 s (frames 0.11 to 0.15 s) before decimate, decimate_edge, nearest, select_nearest and
+align_step joined the walk (a seed of test_gpu_speculation.py::test_fuzz_operation_sequences, which has no host reference, takes 0.08
+to 0.15 s); the rest is the host's brute-force restatements, the driver's process and the downloads.  That is why a seed has only two
+ops beyond its walk through the kinds, and why the spatial ops draw models of at most model_shadow.SPATIAL_N Gaussians when there are."""
 import os
 import time
 import types
@@ -30,12 +45,15 @@ from tests import bounds_ref as B
 from tests import clusters_ref as CL
 from tests import common
 from tests import convert_ref as CV
+from tests import decimate_ref as D
 from tests import extract_ref as X
 from tests import knn_ref as K
 from tests import model_shadow as S
+from tests import nearest_ref as R
 from tests import neighbors_ref as N
 from tests import property_ref as P
 from tests.test_gpu_depth_test import ndc_of
+from tests.test_gpu_nearest import SUM_RTOL
 from wgpu_3dgs_viewer_app_amd import camera, mask as mask_mod, parallel, query
 from wgpu_3dgs_viewer_app_amd.mask import MaskEvaluator, MaskOp
 from wgpu_3dgs_viewer_app_amd.ply import Gaussians
@@ -47,7 +65,13 @@ SEEDS = [int(x) for x in os.environ.get("GSX_MODEL_FUZZ_SEEDS", ",".join(str(s) 
 MODES = [GaussianDisplayMode.Splat, GaussianDisplayMode.Ellipse, GaussianDisplayMode.Point]
 LINES = np.concatenate([HitPair((-1.5, 0.0, 0.0), (1.5, 0.6, 0.0), (255, 40, 40, 255), 30.0), HitPair((0.0, -1.0, -1.0), (0.3, 1.0, 1.0), (40, 255, 40, 200), 20.0)])
 #: what the seeds of this run saw, for the conditions over the seed set
-SEEN = dict(seeds=[], ran={}, nontrivial=set(), speculated_after=set(), in_flight_ops=0)
+SEEN = dict(seeds=[], ran={}, nontrivial=set(), speculated_after=set(), in_flight_ops={}, cases=set(), decimates=[])
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    """tests/decimate_driver.cpp, a stand-alone host program: the merged rows of every decimate"""
+    return D.build_driver(tmp_path_factory.mktemp("decimate"))
 
 
 def _kind(k):
@@ -257,6 +281,11 @@ class Device:
             return model.select_neighbors(op["r"], op["lo"], op["hi"], **a)
         if kind == "select_clusters":
             return model.select_clusters(op["r"], op["mode"], op["size_lo"], op["size_hi"], **a)
+        if kind == "select_nearest":
+            hit, selected, st = model.select_nearest(op["dst"], op["lo"], op["hi"], op["transfer"], op["op"], op["xform"], op["model_transforms"], op["flt"],
+                                                     op["dst_filter"], op["max_distance"])
+            _check_xform(st.xform, op, self.s.shadow.models[op["key"]], self.s.shadow.models[op["dst"]])
+            return hit, selected, st.xform
         hit, selected, st = model.select_knn(op["k"], op["score"], op["lo"], op["hi"], op["std_ratio"], **a)
         if op["std_ratio"] is not None:  # the threshold within one unit in the last place of the restatement's (tests/test_gpu_knn.py)
             part, _, s = self.s.shadow.knn_scores(op["key"], op["k"], op["score"], op["flt"])
@@ -264,20 +293,94 @@ class Device:
             assert abs(int(_bits(st.threshold)[0]) - int(_bits(K.threshold(ks["mean"], ks["std"], op["std_ratio"]))[0])) <= 1
         return hit, selected, st.threshold
 
-    def check_selection(self, key, bits):
-        assert np.array_equal(X.bits(self.live.models[key].gaussian_buffers.selection_buffer.download(), bits.size), bits), "selection bits"
-        self.rebuilt.models[key].gaussian_buffers.selection_buffer.upload(X.words(bits))
+    def check_selection(self, key, bits, upload=True):
+        assert np.array_equal(X.bits(self.live.models[key].gaussian_buffers.selection_buffer.download(), bits.size), bits), (key, "selection bits")
+        if upload:
+            self.rebuilt.models[key].gaussian_buffers.selection_buffer.upload(X.words(bits))
 
     # ---- read-only calls ----
-    def read_only(self, op, m):
-        read_only_call(self.live.models[op["key"]], m, op)
+    def read_only(self, op, shadow):
+        read_only_call(self.live.models[op["key"]], shadow.models[op["key"]], op, shadow)
 
 
-def read_only_call(model, m, op):
-    """one read-only call of the model against the restatement over the shadow model `m`"""
+def _matrix_noise(s_mt, t_mt):
+    """float64[3, 4]: 64 * 2^-53 times the sum of the absolute values of the terms of every entry of inv(M_dst) M_src: what two
+    float64 evaluations of that product may differ by.  An entry of nearest_ref.model_matrix that is smaller than this is the
+    rounding noise of a sum that cancels (a model and its extracted, converted or decimated copy share a transform: the product is
+    the identity, and its off-diagonal entries are some 1e-17 of either sign): it has no bits to compare with."""
+    (ps, qs, ss), (pd, qd, sd) = ([np.asarray(a, np.float64) for a in mt] for mt in (s_mt, t_mt))
+    Rs, Rd = (np.abs(R.quat_rows(q / np.linalg.norm(q))) for q in (qs, qd))
+    A = (Rd.T @ Rs) * ss[None, :] / sd[:, None]
+    b = (Rd.T @ (np.abs(ps) + np.abs(pd))) / sd
+    return 64 * 2.0 ** -53 * np.concatenate([A, b[:, None]], axis=1)
+
+
+def _check_xform(got, op, s, t):
+    """the matrix a nearest-family call used: nearest_ref.model_matrix of the two shadow transforms, the op's own, or the identity, bit
+    for bit; where an entry of the reference is itself below its float64 rounding noise, the device's must be too"""
+    if not op["model_transforms"]:
+        _same_f32(got, S.IDENTITY34 if op["xform"] is None else op["xform"], "the matrix of the nearest search")
+        return
+    want, noise = R.model_matrix(s.mt, t.mt), _matrix_noise(s.mt, t.mt)
+    cancels = np.abs(want.astype(np.float64)) <= noise
+    assert (noise < 1e-13).all() and not cancels.all()
+    assert np.array_equal(_bits(got)[~cancels], _bits(want)[~cancels]), ("the matrix of the model transforms", got, want)
+    assert (np.abs(got.astype(np.float64))[cancels] <= noise[cancels]).all(), ("the entries that cancel", got, want)
+
+
+def _check_nearest(got, ref, what):
+    """the search's statistics against Shadow.nearest's: everything exact but the two float64 sums"""
+    assert (got.count, got.n_nonfinite, got.targets, got.targets_nonfinite, got.n_found) == (
+        ref["count"], ref["n_nonfinite"], ref["targets"], ref["targets_nonfinite"], ref["n_found"]), what
+    _same_f32(got.d_min, ref["d_min"], (what, "d_min"))
+    _same_f32(got.d_max, ref["d_max"], (what, "d_max"))
+    assert got.mean == pytest.approx(ref["mean"], rel=SUM_RTOL, abs=0) and got.rms == pytest.approx(ref["rms"], rel=SUM_RTOL, abs=0), what
+
+
+def read_only_call(model, m, op, shadow=None):
+    """one read-only call of the model against the restatement over the shadow model `m` (`shadow`: the models, for the calls that
+    name a second one)"""
     kind, flt = op["kind"], op["flt"]
     passes, part = m.passes(flt), m.part(flt)
-    if kind == "bounds":
+    if kind == "decimate_edge":
+        kept = np.zeros(m.n, bool)
+        kept[m.kept(flt, op["invert"])] = True
+        edge, cells = model.decimate_edge(op["target"], flt, op["invert"])
+        want_edge, want_cells = S.memo(D.find_edge, m.pos, kept, op["target"])
+        _same_f32(edge, want_edge, "decimate_edge")
+        assert cells == want_cells
+        got = model.decimate_count(edge, flt, op["invert"], want_map=True)
+        dmap, count, nonfinite, members = D.assign(m.pos, kept, edge)
+        assert (got.count, got.n_nonfinite, got.cells, got.singletons, got.largest_cell) == (
+            count, nonfinite, members.size, int((members == 1).sum()), int(members.max()) if members.size else 0) and got.cells == cells
+        assert np.array_equal(got.map, dmap)
+    elif kind == "nearest":
+        t = shadow.models[op["dst"]]
+        got = model.nearest(op["dst"], op["xform"], op["model_transforms"], flt, op["dst_filter"], op["max_distance"])
+        _check_xform(got.xform, op, m, t)
+        ref = shadow.nearest(op["key"], op["dst"], flt, op["dst_filter"], got.xform, max_distance=op["max_distance"])
+        assert np.array_equal(got.index, ref["index"]), "nearest index"
+        _same_f32(got.d2, ref["d2"], "nearest d2")
+        _check_nearest(got, ref, "nearest")
+    elif kind == "align_step":
+        st = model.align_step(op["dst"], op["xform"], False, op["with_scale"], flt, op["dst_filter"], op["max_distance"])
+        ref = shadow.align(op["key"], op["dst"], op["xform"], op["with_scale"], flt, op["dst_filter"], op["max_distance"])
+        _same_f32(st.nearest.xform, op["xform"], "the matrix of the align step")
+        _check_nearest(st.nearest, ref["nearest"], "align_step")
+        assert (st.n_pairs, st.degenerate) == (ref["n_pairs"], ref["degenerate"]), (st.n_pairs, st.degenerate, ref["n_pairs"], ref["degenerate"], ref["gap"], ref["norm"])
+        assert st.rms_before == pytest.approx(ref["rms_before"], rel=SUM_RTOL, abs=0)
+        if ref["degenerate"]:
+            assert np.array_equal(st.quat, [0, 0, 0, 1]) and st.scale == 1 and not st.pos.any()
+            _same_f32(st.xform_next, op["xform"], "a degenerate step's xform_next")
+        else:
+            dev = max(np.abs(st.quat - ref["quat"]).max(), abs(st.scale - ref["scale"]), np.abs(st.pos - ref["pos"]).max())
+            print(f"align: {op['key']} -> {op['dst']}, {ref['n_pairs']} pairs, scale {op['with_scale']}, angle {ref['angle']:.3g} deg, |N| {ref['norm']:.6g} "
+                  f"gap {ref['gap']:.6g} tol {ref['tol']:.3g} deviation {dev:.3g}")
+            assert ref["tol"] <= S.ALIGN_TOL_MAX, "the draw promised a pair whose tolerance formula stays within the directed test's bound"
+            assert st.quat[3] >= 0 and dev <= ref["tol"], (dev, ref["tol"])
+            nxt = R.compose(dict(quat=st.quat, scale=st.scale, pos=st.pos), op["xform"])
+            assert (np.abs(st.xform_next.astype(np.float64) - nxt.astype(np.float64)) <= np.spacing(np.abs(st.xform_next))).all(), "xform_next"
+    elif kind == "bounds":
         got = model.bounds(masked=bool(flt & X.MASKED), skip_hidden=bool(flt & X.SKIP_HIDDEN), selected=bool(flt & X.SELECTED), trim_permille=op["trim"])
         want = B.reference(m.pos, passes)
         assert (got.count, got.n_nonfinite) == (want["count"], want["n_nonfinite"])
@@ -325,9 +428,9 @@ def read_only_call(model, m, op):
 
 # ---- 1. the lock-step fuzz ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("seed", SEEDS)
-def test_fuzz_model_operations(seed, monkeypatch):
+def test_fuzz_model_operations(seed, monkeypatch, driver):
     t0 = time.perf_counter()
-    s = S.Session(seed)
+    s = S.Session(seed, driver)
     dev = Device(s, monkeypatch)
     step = -1
     try:
@@ -337,7 +440,8 @@ def test_fuzz_model_operations(seed, monkeypatch):
             changed = s.apply(op, dev)
             if kind in S.MODEL_CHANGING:
                 dev.watch = (kind, changed)
-                SEEN["in_flight_ops"] += s.lanes > 1 and op.get("inflight", 0) >= 2
+            if s.lanes > 1 and op.get("inflight", 0) >= 2:
+                SEEN["in_flight_ops"][kind] = SEEN["in_flight_ops"].get(kind, 0) + 1
             dev.frame()
     except Exception as e:
         raise AssertionError(f"{type(e).__name__}: {e}\n  at step {step} of {s.replay()}") from e
@@ -347,13 +451,15 @@ def test_fuzz_model_operations(seed, monkeypatch):
     for k, c in s.ran.items():
         SEEN["ran"][k] = SEEN["ran"].get(k, 0) + c
     SEEN["nontrivial"] |= s.nontrivial
+    SEEN["cases"] |= s.cases
+    SEEN["decimates"] += s.decimates
     print(f"seed {seed}: lanes {s.lanes}, host_verify {s.host_verify}, kind {_kind(s.kind)}, {step + 1} frames, {dev.speculated} speculated, "
           f"{time.perf_counter() - t0:.2f} s of which {dev.frame_s:.2f} s in the frames of both viewers, ops {dict(sorted(s.ran.items()))}")
     assert dev.speculated > 0
 
 
 def test_conditions_over_the_seed_set():
-    """(a) to (d) of the module docstring, over the default seed set, which test_fuzz_model_operations ran before this.  A replay of
+    """(a) to (h) of the module docstring, over the default seed set, which test_fuzz_model_operations ran before this.  A replay of
     other seeds through GSX_MODEL_FUZZ_SEEDS has no such set to answer for."""
     if set(SEEDS) != set(S.DEFAULT_SEEDS):
         pytest.skip("GSX_MODEL_FUZZ_SEEDS names other seeds than the default set the conditions are stated over")
@@ -365,7 +471,11 @@ def test_conditions_over_the_seed_set():
     assert not trivial, f"(b) selects that never selected something and not everything: {trivial}"
     cold = [k for k in S.MODEL_CHANGING if k not in SEEN["speculated_after"]]
     assert not cold, f"(c) model-changing ops never followed by a speculated frame of the changed model: {cold}"
-    assert SEEN["in_flight_ops"] > 0, "(d) no op ran with two frames enqueued and not waited for"
+    assert sum(SEEN["in_flight_ops"].get(k, 0) for k in S.MODEL_CHANGING) > 0, "(d) no op ran with two frames enqueued and not waited for"
+    unmet = S.unmet(SEEN["cases"], SEEN["decimates"])
+    assert not unmet, f"(e), (f), (h): {unmet}"
+    cold = [k for k in ("decimate", "select_nearest") if not SEEN["in_flight_ops"].get(k)]
+    assert not cold, f"(g) never ran with two frames enqueued and not waited for: {cold}"
 
 
 # ---- 2. directed ------------------------------------------------------------------------------------------------------------------------
@@ -383,17 +493,24 @@ def _enqueue(v, pose, keys):
 
 def test_read_only_calls_between_frames_in_flight():
     """Two identical viewers with two lanes.  One enqueues two frames (one per lane), makes a read-only call, two frames, the next
-    call ... through all eight, with no host wait but the call's own; its twin only renders.  Every frame of both lanes is the
-    twin's, and every answer is the restatement's."""
-    n = 3000
+    call ... through all of model_shadow.READ_ONLY, with no host wait but the call's own; its twin only renders.  A second model "t",
+    the first 1200 Gaussians of "m" under a small rigid motion, is in every frame and is the target of the nearest search and the
+    align step.  Every frame of both lanes is the twin's, and every answer is the restatement's."""
+    n, n_t = 3000, 1200
     g = common.small_scene(n, 91)
+    moved = g[:n_t].copy()
+    half = np.radians(2.0) / 2
+    motion = np.concatenate([R.quat_rows([0.0, 0.0, np.sin(half), np.cos(half)]), [[0.02], [-0.01], [0.015]]], axis=1).astype(F)
+    moved["pos"] = R.map_points(motion, g["pos"][:n_t])
     rng = np.random.default_rng(91)
     shadow = S.Shadow()
     with _two_lanes() as v, _two_lanes() as twin:
         for vv in (v, twin):
-            vv.add_model("m", n)
-            vv.models["m"].gaussian_buffers.gaussians_buffer.update_range(0, g)
+            for key, rows in (("m", g), ("t", moved)):
+                vv.add_model(key, rows.shape[0])
+                vv.models[key].gaussian_buffers.gaussians_buffer.update_range(0, rows)
         m = shadow.add("m", S.SINGLE, CV.pod(v, "m"))
+        t = shadow.add("t", S.SINGLE, CV.pod(v, "t"))
         m.mask, m.sel, m.edits = rng.random(n) < 0.8, rng.random(n) < 0.4, S.normalise_edits(S.random_edits(n, 91))
         for vv in (v, twin):
             bufs = vv.models["m"].gaussian_buffers
@@ -402,26 +519,33 @@ def test_read_only_calls_between_frames_in_flight():
             bufs.gaussians_edit_buffer.upload(m.edits)
         r = float(F(K.kth_distance_median(m.pos, m.part(0), 2)))
         flt = X.MASKED | X.SKIP_HIDDEN
+        reach = float(F(K.kth_distance_median(t.pos, t.part(0), 1)))  # the targets' median nearest-neighbour distance
         calls = [dict(kind="bounds", flt=flt, trim=50), dict(kind="histogram", flt=flt, prop=P.HUE, bins=64, world=False, auto=True),
                  dict(kind="property_values", flt=0, prop=P.POS_Y, world=True), dict(kind="neighbors", flt=flt, r=r), dict(kind="clusters", flt=X.SELECTED, r=r),
-                 dict(kind="knn", flt=flt, k=3, score=K.SCORE_MEAN), dict(kind="export", flt=X.SELECTED, invert=True), dict(kind="export_ply", flt=flt, invert=False)]
+                 dict(kind="knn", flt=flt, k=3, score=K.SCORE_MEAN), dict(kind="export", flt=X.SELECTED, invert=True), dict(kind="export_ply", flt=flt, invert=False),
+                 dict(kind="decimate_edge", flt=flt, invert=False, target=600),
+                 dict(kind="nearest", dst="t", flt=flt, dst_filter=0, xform=None, model_transforms=False, max_distance=reach),
+                 dict(kind="align_step", key="t", dst="m", flt=0, dst_filter=X.MASKED, xform=S.IDENTITY34, with_scale=True, max_distance=0.0)]
         assert [c["kind"] for c in calls] == list(S.READ_ONLY)
+        found = shadow.nearest("m", "t", flt, 0, max_distance=reach)
+        assert 0 < found["n_found"] < found["count"]  # the max_distance rejects some queries and not all
         speculated = 0
         for k, call in enumerate(calls):
             poses = (10 + 2 * k, 11 + 2 * k)
             for pose in poses:
-                _enqueue(v, pose, ["m"])
-            read_only_call(v.models["m"], m, call)
+                _enqueue(v, pose, ["m", "t"])
+            key = call.setdefault("key", "m")
+            read_only_call(v.models[key], shadow.models[key], call, shadow)
             got = [v.debug_download_lane_framebuffer(lane) for lane in (0, 1)]
             want = []
             for pose in poses:
-                _enqueue(twin, pose, ["m"])
+                _enqueue(twin, pose, ["m", "t"])
                 want.append(twin.download_framebuffer())
             assert want[0][..., :3].max() > 0 and not np.array_equal(want[0], want[1])
             assert any(all(np.array_equal(got[a], want[b]) for a, b in zip((0, 1), order)) for order in ((0, 1), (1, 0))), (k, call["kind"])
             v.poll()
             speculated += v.frame_stats("m")["speculated"]
-        assert speculated >= 6
+        assert speculated >= 9  # (6 of 8 calls before decimate_edge, nearest and align_step joined: the same share of 11)
 
 
 def test_a_key_removed_and_reused():
