@@ -926,6 +926,62 @@ gsx_status gsx_model_decimate(gsx_viewer* v, const char* src_key, const char* ds
 gsx_status gsx_model_decimate_edge(gsx_viewer* v, const char* key, uint32_t filter, uint32_t flags, uint64_t target_cells,
                                    float* out_cell, uint64_t* out_cells);
 
+/* ---- visibility: which Gaussians the camera sees, and how much (spec/RENDER_SPEC.md section 24; kernels_visibility.hip).
+ *      gsx_model_visibility draws the model ALONE — what gsx_render_frame(&key, 1) would draw: the viewer's current camera,
+ *      viewport, model transform, Gaussian transform and spec parameters; the mask, the hidden edits, the opacity edits and
+ *      show_unedited as in a frame — and keeps, per Gaussian, what the compositor computes and throws away.  Pixel p walks its tile's
+ *      front-to-back list with the compositor's per-pixel sequence (support test, alpha by display mode clamped by alpha_max /
+ *      alpha_min, w = T * alpha in float32, T *= 1 - alpha, closed at T < t_epsilon; records behind a closed pixel get nothing):
+ *        peak   = max over pixels of w;
+ *        weight = sum over pixels of round_to_nearest(w * 2^24), a 64-bit integer, reported as double / 2^24;
+ *        pixels = the pixels that blended the Gaussian (support hit, pixel open, alpha not removed by alpha_min).
+ *      A maximum and integer sums: two calls return the same bytes, whatever ran before and however many frames are in flight.
+ *      out_transmittance: the final T of every pixel of this view (height * width floats, row-major).
+ *      The planes: 16 bytes a Gaussian, owned by the model, allocated by the first call, counted by gsx_debug_device_bytes, freed
+ *      by gsx_model_visibility_reset and gsx_model_remove, and dropped by every call that rewrites the model's pod planes or its
+ *      count (the uploads, gsx_model_import_ply, gsx_model_apply_transform unless the identity, gsx_model_convert / set_pod_kind).
+ *      A mask, selection or edit change KEEPS them: the planes describe the views that were folded, not the model as it is now.
+ *      Without GSX_VIS_ACCUMULATE a call replaces the planes (views = 1); with it peak becomes the maximum, weight and pixels the
+ *      sums, views + 1; the viewport may differ from view to view; (views + 1) * width * height >= 2^32 is refused (the pixel
+ *      plane would wrap).
+ *      gsx_model_select_visibility: selects the Gaussians that pass `filter` (GSX_BOUNDS_* bits) and whose resident measure lies in
+ *      [lo, hi] (inclusive; hi = +inf allowed) under `selection_op`; "never seen" is GSX_VIS_PEAK in [0, 0].
+ *      State: the call is ordered after every frame in flight, draws into scratch of its own (the viewer's framebuffer, every
+ *      lane's and the query hit buffers keep the last frame), and leaves the model unsorted: gsx_preprocess + gsx_sort before the
+ *      next gsx_render (which refuses otherwise); gsx_render_frame needs nothing, and draws bit for bit the frame it would have
+ *      drawn without the call.
+ *      Out of scope (GSX_ERR_INVALID_ARG, by design, not forgotten): the depth test GSX_DEPTH_LESS; overlay lines or mask gizmos
+ *      set; a band (gsx_viewer_set_band) or an external framebuffer set; a sharded model.
+ *      Other errors: null viewer / key / desc, unknown flag bits, a reserved word != 0, an unknown measure or op, a NaN or reversed
+ *      range, a select or a download without planes: GSX_ERR_INVALID_ARG; unknown key: GSX_ERR_NOT_FOUND.  A refused call leaves the
+ *      planes untouched. ---- */
+#define GSX_VIS_ACCUMULATE 1u   /* fold this view into the model's resident planes instead of replacing them */
+typedef enum gsx_visibility_measure { GSX_VIS_PEAK = 0, GSX_VIS_WEIGHT = 1, GSX_VIS_PIXELS = 2 } gsx_visibility_measure;
+typedef struct gsx_visibility_desc { uint32_t flags; uint32_t reserved[3]; } gsx_visibility_desc; /* 16 B */
+typedef struct gsx_visibility_select_desc {
+    uint32_t measure;       /* gsx_visibility_measure */
+    uint32_t filter;        /* GSX_BOUNDS_* bits */
+    uint32_t selection_op;  /* GSX_SELECTION_SET / _ADD / _REMOVE */
+    uint32_t reserved;      /* 0 */
+    double lo, hi;          /* inclusive */
+} gsx_visibility_select_desc; /* 32 B */
+typedef struct gsx_visibility_stats_t {
+    uint64_t n_visible;     /* after cull, this view */
+    uint64_t n_seen;        /* Gaussians with peak > 0 in the resident planes after this call */
+    uint64_t n_pairs;       /* (pixel, Gaussian) pairs blended in this view */
+    uint64_t weight_fixed;  /* sum over this view's pairs of the 2^-24 fixed-point weights */
+    float peak_max;         /* largest resident peak */
+    uint32_t views;         /* views folded into the planes */
+} gsx_visibility_stats_t; /* 40 B */
+void gsx_visibility_desc_default(gsx_visibility_desc* d);               /* flags 0 */
+void gsx_visibility_select_desc_default(gsx_visibility_select_desc* d); /* PEAK in (0, +inf]: lo = the smallest positive float, SET, no filter */
+gsx_status gsx_model_visibility(gsx_viewer* v, const char* key, const gsx_visibility_desc* desc, float* out_peak /* n, nullable */,
+                                double* out_weight /* n, nullable */, uint32_t* out_pixels /* n, nullable */,
+                                float* out_transmittance /* height * width of this view, nullable */, gsx_visibility_stats_t* out /* nullable */);
+gsx_status gsx_model_select_visibility(gsx_viewer* v, const char* key, const gsx_visibility_select_desc* desc, uint64_t* out_hit,
+                                       uint64_t* out_selected);
+gsx_status gsx_model_visibility_reset(gsx_viewer* v, const char* key); /* frees the planes */
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

@@ -375,6 +375,47 @@ struct MultiModelViewerModel {
             for (int k = 0; k < 12; ++k) delta[k] = D[k];
         return out;
     }
+    // gsx_model_visibility: draws this model ALONE with the viewer's current camera and keeps, per Gaussian and on the device, the
+    // peak blending weight T * alpha, the summed weight (2^-24 fixed point, as double) and the pixel count; accumulate folds the
+    // view into the planes an earlier call left.  Every output is nullable.  The model goes through preprocess + sort again before
+    // the next render(); render_frame() needs nothing.
+    gsx_visibility_stats_t visibility(bool accumulate = false, std::vector<float>* peak = nullptr, std::vector<double>* weight = nullptr,
+                                      std::vector<uint32_t>* pixels = nullptr, std::vector<float>* transmittance = nullptr,
+                                      uint32_t width = 0, uint32_t height = 0) {
+        uint64_t n = 0;
+        check(gsx_model_len(v_, key_.c_str(), &n));
+        if (peak) peak->assign((size_t)n, 0.0f);
+        if (weight) weight->assign((size_t)n, 0.0);
+        if (pixels) pixels->assign((size_t)n, 0u);
+        if (transmittance) transmittance->assign((size_t)width * height, 1.0f);  // (the viewport of the view: the caller knows it)
+        gsx_visibility_desc desc{};
+        gsx_visibility_desc_default(&desc);
+        desc.flags = accumulate ? GSX_VIS_ACCUMULATE : 0u;
+        gsx_visibility_stats_t out{};
+        check(gsx_model_visibility(v_, key_.c_str(), &desc, peak ? peak->data() : nullptr, weight ? weight->data() : nullptr,
+                                   pixels ? pixels->data() : nullptr, transmittance ? transmittance->data() : nullptr, &out));
+        return out;
+    }
+    // gsx_model_select_visibility: selects the Gaussians that pass desc.filter and whose resident measure lies in [lo, hi];
+    // "never seen" is GSX_VIS_PEAK in [0, 0].  Returns {hit, selected afterwards}.
+    std::pair<uint64_t, uint64_t> select_visibility(const gsx_visibility_select_desc& desc) {
+        uint64_t hit = 0, selected = 0;
+        check(gsx_model_select_visibility(v_, key_.c_str(), &desc, &hit, &selected));
+        return {hit, selected};
+    }
+    // gsx_model_visibility_reset: frees the resident planes
+    void visibility_reset() { check(gsx_model_visibility_reset(v_, key_.c_str())); }
+    // Resets the planes, then folds one view per camera (16 floats of view and of projection each, column-major): every Gaussian's
+    // best and summed contribution over an orbit.  The viewer keeps the last camera.  Returns the last view's statistics.
+    gsx_visibility_stats_t visibility_orbit(const std::vector<std::pair<const float*, const float*>>& cameras, uint32_t width, uint32_t height) {
+        visibility_reset();
+        gsx_visibility_stats_t out{};
+        for (const auto& c : cameras) {
+            check(gsx_update_camera(v_, c.first, c.second, width, height));
+            out = visibility(true);
+        }
+        return out;
+    }
 };
 
 class MultiModelViewer {

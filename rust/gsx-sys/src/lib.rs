@@ -49,6 +49,10 @@ pub const GSX_NEAREST_MODEL_TRANSFORMS: u32 = 1;
 pub const GSX_NEAREST_SELECT_RANGE: u32 = 0;
 pub const GSX_NEAREST_SELECT_TRANSFER: u32 = 1;
 pub const GSX_ALIGN_SCALE: u32 = 1;
+pub const GSX_VIS_ACCUMULATE: u32 = 1;
+pub const GSX_VIS_PEAK: u32 = 0;
+pub const GSX_VIS_WEIGHT: u32 = 1;
+pub const GSX_VIS_PIXELS: u32 = 2;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -278,6 +282,20 @@ pub struct gsx_decimate_desc { pub filter: u32, pub flags: u32, pub cell: f32, p
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_decimate_stats_t { pub count: u64, pub n_nonfinite: u64, pub cells: u64, pub singletons: u64, pub largest_cell: u32, pub grid_bits: u32 }
+/// gsx_model_visibility, 16 bytes: flags (GSX_VIS_ACCUMULATE), reserved (0)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_visibility_desc { pub flags: u32, pub reserved: [u32; 3] }
+/// gsx_model_select_visibility, 32 bytes: the GSX_VIS_* measure, the GSX_BOUNDS_* filter, the selection op, reserved (0), the
+/// inclusive range [lo, hi] of the resident measure (hi = +inf allowed)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_visibility_select_desc { pub measure: u32, pub filter: u32, pub selection_op: u32, pub reserved: u32, pub lo: f64, pub hi: f64 }
+/// the result of gsx_model_visibility, 40 bytes: Gaussians after cull in this view, Gaussians with a resident peak > 0, the (pixel,
+/// Gaussian) pairs blended in this view and the sum of their 2^-24 fixed-point weights, the largest resident peak, the views folded
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_visibility_stats_t { pub n_visible: u64, pub n_seen: u64, pub n_pairs: u64, pub weight_fixed: u64, pub peak_max: f32, pub views: u32 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }
@@ -426,6 +444,11 @@ extern "C" {
     pub fn gsx_decimate_desc_default(d: *mut gsx_decimate_desc);
     pub fn gsx_model_decimate(v: *mut gsx_viewer, src_key: *const c_char, dst_key: *const c_char, desc: *const gsx_decimate_desc, out_map: *mut u32, out: *mut gsx_decimate_stats_t) -> gsx_status;
     pub fn gsx_model_decimate_edge(v: *mut gsx_viewer, key: *const c_char, filter: u32, flags: u32, target_cells: u64, out_cell: *mut f32, out_cells: *mut u64) -> gsx_status;
+    pub fn gsx_visibility_desc_default(d: *mut gsx_visibility_desc);
+    pub fn gsx_visibility_select_desc_default(d: *mut gsx_visibility_select_desc);
+    pub fn gsx_model_visibility(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_visibility_desc, out_peak: *mut f32, out_weight: *mut f64, out_pixels: *mut u32, out_transmittance: *mut f32, out: *mut gsx_visibility_stats_t) -> gsx_status;
+    pub fn gsx_model_select_visibility(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_visibility_select_desc, out_hit: *mut u64, out_selected: *mut u64) -> gsx_status;
+    pub fn gsx_model_visibility_reset(v: *mut gsx_viewer, key: *const c_char) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

@@ -190,6 +190,43 @@ impl MultiModelViewerModel {
         check(unsafe { sys::gsx_model_apply_transform(self.v, self.key.as_ptr(), desc, &mut count) })?;
         Ok(count)
     }
+    /// `gsx_model_visibility`: draws this model ALONE with the viewer's current camera and keeps, per Gaussian and on the device, the
+    /// peak blending weight `T * alpha`, the summed weight (2^-24 fixed point, as `f64`) and the pixel count; `accumulate` folds the
+    /// view into the planes an earlier call left.  Returns `(peak, weight, pixels, stats)` (the three empty without `rows`).  The
+    /// model goes through `preprocess` + `sort` again before the next `render`; `render_frame` needs nothing.
+    pub fn visibility(&mut self, accumulate: bool, rows: bool) -> Result<(Vec<f32>, Vec<f64>, Vec<u32>, sys::gsx_visibility_stats_t), Error> {
+        let mut n = 0u64;
+        check(unsafe { sys::gsx_model_len(self.v, self.key.as_ptr(), &mut n) })?;
+        let len = if rows { n as usize } else { 0 };
+        let (mut peak, mut weight, mut pixels) = (vec![0f32; len], vec![0f64; len], vec![0u32; len]);
+        let desc = sys::gsx_visibility_desc { flags: if accumulate { sys::GSX_VIS_ACCUMULATE } else { 0 }, reserved: [0; 3] };
+        let mut out = sys::gsx_visibility_stats_t::default();
+        let (p, w, c) = if rows { (peak.as_mut_ptr(), weight.as_mut_ptr(), pixels.as_mut_ptr()) } else { (std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut()) };
+        check(unsafe { sys::gsx_model_visibility(self.v, self.key.as_ptr(), &desc, p, w, c, std::ptr::null_mut(), &mut out) })?;
+        Ok((peak, weight, pixels, out))
+    }
+    /// `gsx_model_select_visibility`: selects the Gaussians that pass `desc.filter` and whose resident measure lies in `[lo, hi]`;
+    /// "never seen" is `GSX_VIS_PEAK` in `[0, 0]`.  Returns `(hit, selected)`.
+    pub fn select_visibility(&mut self, desc: &sys::gsx_visibility_select_desc) -> Result<(u64, u64), Error> {
+        let (mut hit, mut selected) = (0u64, 0u64);
+        check(unsafe { sys::gsx_model_select_visibility(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected) })?;
+        Ok((hit, selected))
+    }
+    /// `gsx_model_visibility_reset`: frees the resident planes.
+    pub fn visibility_reset(&mut self) -> Result<(), Error> {
+        check(unsafe { sys::gsx_model_visibility_reset(self.v, self.key.as_ptr()) })
+    }
+    /// Resets the planes, then folds one view per camera (`(view, proj)`, 16 column-major floats each): every Gaussian's best and
+    /// summed contribution over an orbit.  The viewer keeps the last camera.  Returns the last view's result.
+    pub fn visibility_orbit(&mut self, cameras: &[([f32; 16], [f32; 16])], size: (u32, u32), rows: bool) -> Result<(Vec<f32>, Vec<f64>, Vec<u32>, sys::gsx_visibility_stats_t), Error> {
+        self.visibility_reset()?;
+        let mut out = (Vec::new(), Vec::new(), Vec::new(), sys::gsx_visibility_stats_t::default());
+        for (k, (view, proj)) in cameras.iter().enumerate() {
+            check(unsafe { sys::gsx_update_camera(self.v, view.as_ptr(), proj.as_ptr(), size.0, size.1) })?;
+            out = self.visibility(true, rows && k + 1 == cameras.len())?;
+        }
+        Ok(out)
+    }
     /// `gsx_model_decimate` without a destination: how a grid of edge `desc.cell` would divide the model.  Returns the statistics
     /// and the cell every Gaussian would go into (`0xFFFF_FFFF`: it does not participate).  Nothing is created.
     pub fn decimate_count(&self, desc: &sys::gsx_decimate_desc) -> Result<(sys::gsx_decimate_stats_t, Vec<u32>), Error> {

@@ -1,0 +1,43 @@
+"""The scenes of the visibility tests (spec/RENDER_SPEC.md §24), shared by tests/test_visibility_cpu.py and tests/test_gpu_visibility.py.
+
+REF: the scenes whose planes are compared with tests/visibility_ref.py.  The comparison excludes nothing, but a Gaussian with an
+UNCERTAIN pair (a pixel whose float64 T came within the tolerance of t_epsilon: visibility_ref) is only held to a range, so these
+scenes are made to close few pixels: at most 2 % of their Gaussians may have such a pair, which test_visibility_cpu.py proves for
+these very seeds with the oracle's projection and test_gpu_visibility.py asserts again on the device's.  The shapes are the smallest at
+which k_vis_tiles can still go wrong: 5 x 3 tiles; partial tiles with an odd height (a lane's second pixel outside); one tile; less
+than one tile; a list of more than 256 entries (two LDS batches and the pipeline's third gather).
+
+SOLID: the same shapes, opaque enough to close most pixels — for what is compared bit for bit (the transmittance against a rendered
+frame, determinism, accumulation), where the closing matters and no reference does."""
+import numpy as np
+
+from tests import common
+from wgpu_3dgs_viewer_app_amd import camera
+
+#: name -> (n, width, height, seed, scale multiplier, opacity multiplier, orbit pose)
+REF = {
+    "5x3": (400, 80, 48, 71, 12.0, 1.0, 5),
+    "partial": (400, 83, 51, 72, 10.0, 1.0, 6),
+    "one-tile": (400, 16, 16, 81, 6.0, 1.0, 5),
+    "7x5": (400, 7, 5, 81, 6.0, 0.3, 5),
+    "long-list": (1500, 48, 32, 73, 14.0, 0.3, 5),
+}
+SOLID = {
+    "5x3": (400, 80, 48, 71, 20.0, 1.0, 5),
+    "partial": (400, 83, 51, 72, 20.0, 1.0, 6),
+    "one-tile": (400, 16, 16, 73, 12.0, 1.0, 5),
+    "7x5": (400, 7, 5, 73, 6.0, 1.0, 5),
+    "long-list": (1500, 48, 32, 73, 14.0, 1.0, 5),
+}
+#: the pod kinds of the GPU tests as (gsx_sh_kind, gsx_cov3d_kind): f32, Norm8 + Half
+KINDS = {"f32": (0, 0), "Norm8-Half": (2, 1)}
+UNCERTAIN_CAP = 0.02
+
+
+def scene(spec):
+    """(gaussians, camera, (width, height)) of a REF / SOLID entry"""
+    n, w, h, seed, mul, op, pose = spec
+    g = common.small_scene(n, seed, 3, mul)
+    if op != 1.0:
+        g["color"][:, 3] = (g["color"][:, 3].astype(np.float32) * np.float32(op)).astype(np.uint8)
+    return g, camera.orbit_pose(pose), (w, h)

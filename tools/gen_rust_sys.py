@@ -11,7 +11,7 @@ src = open(os.path.join(ROOT, "include", "gsx.h")).read()
 code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
 protos = re.findall(r"^(gsx_status|void|uint32_t|uint64_t|const char\*)\s+(gsx_\w+)\s*\(([^;]*?)\);", code, flags=re.M | re.S)
 
-SCALAR = {"uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i32", "float": "f32", "char": "c_char", "void": "c_void",
+SCALAR = {"uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i32", "float": "f32", "double": "f64", "char": "c_char", "void": "c_void",
           "gsx_sh_kind": "gsx_sh_kind", "gsx_cov3d_kind": "gsx_cov3d_kind", "gsx_display_mode": "gsx_display_mode", "gsx_status": "gsx_status", "gsx_buffer_kind": "gsx_buffer_kind",
           "gsx_depth_compare": "gsx_depth_compare"}
 
@@ -98,6 +98,10 @@ pub const GSX_NEAREST_MODEL_TRANSFORMS: u32 = 1;
 pub const GSX_NEAREST_SELECT_RANGE: u32 = 0;
 pub const GSX_NEAREST_SELECT_TRANSFER: u32 = 1;
 pub const GSX_ALIGN_SCALE: u32 = 1;
+pub const GSX_VIS_ACCUMULATE: u32 = 1;
+pub const GSX_VIS_PEAK: u32 = 0;
+pub const GSX_VIS_WEIGHT: u32 = 1;
+pub const GSX_VIS_PIXELS: u32 = 2;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -327,6 +331,20 @@ pub struct gsx_decimate_desc { pub filter: u32, pub flags: u32, pub cell: f32, p
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_decimate_stats_t { pub count: u64, pub n_nonfinite: u64, pub cells: u64, pub singletons: u64, pub largest_cell: u32, pub grid_bits: u32 }
+/// gsx_model_visibility, 16 bytes: flags (GSX_VIS_ACCUMULATE), reserved (0)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_visibility_desc { pub flags: u32, pub reserved: [u32; 3] }
+/// gsx_model_select_visibility, 32 bytes: the GSX_VIS_* measure, the GSX_BOUNDS_* filter, the selection op, reserved (0), the
+/// inclusive range [lo, hi] of the resident measure (hi = +inf allowed)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_visibility_select_desc { pub measure: u32, pub filter: u32, pub selection_op: u32, pub reserved: u32, pub lo: f64, pub hi: f64 }
+/// the result of gsx_model_visibility, 40 bytes: Gaussians after cull in this view, Gaussians with a resident peak > 0, the (pixel,
+/// Gaussian) pairs blended in this view and the sum of their 2^-24 fixed-point weights, the largest resident peak, the views folded
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_visibility_stats_t { pub n_visible: u64, pub n_seen: u64, pub n_pairs: u64, pub weight_fixed: u64, pub peak_max: f32, pub views: u32 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }

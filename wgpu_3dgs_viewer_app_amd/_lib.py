@@ -58,6 +58,8 @@ EXPORTS = (
     "gsx_nearest_desc_default", "gsx_model_nearest", "gsx_model_select_nearest", "gsx_model_align_step",
     "gsx_transform_desc_default", "gsx_model_apply_transform",
     "gsx_decimate_desc_default", "gsx_model_decimate", "gsx_model_decimate_edge",
+    "gsx_visibility_desc_default", "gsx_visibility_select_desc_default", "gsx_model_visibility", "gsx_model_select_visibility",
+    "gsx_model_visibility_reset",
 )
 
 
@@ -278,6 +280,31 @@ class AlignStep(C.Structure):
     the matrix used, the pairs, the rms distance before the step, whether the step was degenerate, the search's statistics."""
     _fields_ = [("pos", C.c_double * 3), ("quat", C.c_double * 4), ("scale", C.c_double), ("xform_next", C.c_float * 12), ("n_pairs", C.c_uint64),
                 ("rms_before", C.c_double), ("degenerate", C.c_uint32), ("reserved", C.c_uint32), ("nearest", NearestStats)]
+
+
+#: ``gsx_visibility_desc.flags``: fold this view into the model's resident planes instead of replacing them
+GSX_VIS_ACCUMULATE = 1
+#: ``gsx_visibility_select_desc.measure``
+GSX_VIS_PEAK, GSX_VIS_WEIGHT, GSX_VIS_PIXELS = 0, 1, 2
+
+
+class VisibilityDesc(C.Structure):
+    """``gsx_visibility_desc`` (16 bytes): flags (``GSX_VIS_ACCUMULATE``), reserved (0)."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class VisibilitySelectDesc(C.Structure):
+    """``gsx_visibility_select_desc`` (32 bytes): the ``GSX_VIS_*`` measure, the ``GSX_BOUNDS_*`` filter, the ``gsx_selection_op``,
+    reserved (0) and the inclusive range ``[lo, hi]`` of the resident measure (``hi`` may be ``inf``)."""
+    _fields_ = [("measure", C.c_uint32), ("filter", C.c_uint32), ("selection_op", C.c_uint32), ("reserved", C.c_uint32),
+                ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class VisibilityStats(C.Structure):
+    """``gsx_visibility_stats_t`` (40 bytes): Gaussians after cull in this view, Gaussians with a resident peak > 0, the (pixel,
+    Gaussian) pairs blended in this view and the sum of their 2^-24 fixed-point weights, the largest resident peak, the views folded."""
+    _fields_ = [("n_visible", C.c_uint64), ("n_seen", C.c_uint64), ("n_pairs", C.c_uint64), ("weight_fixed", C.c_uint64),
+                ("peak_max", C.c_float), ("views", C.c_uint32)]
 
 
 class TransformDesc(C.Structure):
@@ -565,6 +592,11 @@ def load() -> C.CDLL:
         "gsx_model_align_step": ([vp, cp, cp, C.POINTER(AlignDesc), C.POINTER(AlignStep)], C.c_int32),
         "gsx_transform_desc_default": ([C.POINTER(TransformDesc)], None),
         "gsx_model_apply_transform": ([vp, cp, C.POINTER(TransformDesc), C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_visibility_desc_default": ([C.POINTER(VisibilityDesc)], None),
+        "gsx_visibility_select_desc_default": ([C.POINTER(VisibilitySelectDesc)], None),
+        "gsx_model_visibility": ([vp, cp, C.POINTER(VisibilityDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(VisibilityStats)], C.c_int32),
+        "gsx_model_select_visibility": ([vp, cp, C.POINTER(VisibilitySelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_model_visibility_reset": ([vp, cp], C.c_int32),
         "gsx_decimate_desc_default": ([C.POINTER(DecimateDesc)], None),
         "gsx_model_decimate": ([vp, cp, cp, C.POINTER(DecimateDesc), C.c_void_p, C.POINTER(DecimateStats)], C.c_int32),
         "gsx_model_decimate_edge": ([vp, cp, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_uint64)], C.c_int32),

@@ -516,6 +516,7 @@ gsx_status gsx_model_upload_range(gsx_viewer* v, const char* key, uint64_t start
         HIPCHK(gsx::op::StreamSynchronize(v->stream));  // the caller's memory may be reused after return
     }
     m->tuner.reset();
+    drop_visibility(m);
     return GSX_OK;
 }
 
@@ -531,6 +532,7 @@ gsx_status gsx_model_upload_pod_device(gsx_viewer* v, const char* key, uint64_t 
     if (start > m->n || n > m->n - start) return fail(GSX_ERR_INVALID_ARG, "gsx_model_upload_pod_device: range exceeds model");
     HIPCHK(launch_pack_pod(v->stream, d_pos, d_color, m->has_sh ? d_sh : nullptr, d_cov3d, n, start, m->n, m->pod()));
     m->tuner.reset();
+    drop_visibility(m);
     return GSX_OK;
 }
 

@@ -73,6 +73,7 @@ gsx_status import_rows(gsx_viewer* v, Model* m, uint64_t start, const char* rows
     HIPCHK(e1);
     HIPCHK(e2);
     m->tuner.reset();
+    drop_visibility(m);
     return GSX_OK;
 }
 

@@ -56,6 +56,7 @@ gsx_status gsx_model_apply_transform(gsx_viewer* v, const char* key, const gsx_t
     // planes and this tuner and copy the hash at their next frame (lane_sync).
     m->tuner.reset();
     m->mask_program_hash = 0;
+    drop_visibility(m);  // (the planes were measured on the old pod planes; hipFree waits for the kernel above)
     return GSX_OK;
 }
 

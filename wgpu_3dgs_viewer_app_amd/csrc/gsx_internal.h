@@ -1278,6 +1278,38 @@ enum { kImportAuto = 0, kImportSlab = 1, kImportDirect = 2, kImportGeneral = 3 }
 hipError_t launch_import_rows(hipStream_t s, const void* d_rows, uint64_t n, uint64_t start, uint64_t model_n, const PodPlanes& pod,
                               const ImportLayout& lay, int read = kImportAuto);
 
+// Visibility (kernels_visibility.hip; gsx_model_visibility, gsx_model_select_visibility; spec section 24).  The model's resident
+// planes, 16 bytes a Gaussian in one buffer: [weight, n x u64 | peak, n x u32: the float's bits | pixels, n x u32].  The words of a
+// call: [0..1] n_pairs (u64)  [2..3] weight_fixed (u64)  [4] n_seen  [5] peak_max's bits  [6] hit  [7] selected.
+enum : uint32_t { kVisPairs = 0, kVisWeight = 2, kVisSeen = 4, kVisPeakMax = 5, kVisHit = 6, kVisSelected = 7, kVisWords = 32 };
+constexpr uint32_t kVisFixedBits = 24;  // weight = sum of round_to_nearest(w * 2^24)
+struct VisPlanes {
+    unsigned long long* weight;
+    uint32_t* peak;
+    uint32_t* pixels;
+};
+inline VisPlanes vis_planes(void* p, uint64_t n) {
+    VisPlanes v;
+    v.weight = static_cast<unsigned long long*>(p);
+    v.peak = reinterpret_cast<uint32_t*>(v.weight + n);
+    v.pixels = v.peak + n;
+    return v;
+}
+// One 128-lane workgroup a tile over the model's COMPLETE per-tile lists (a progressive = 0 frame's ranges and list): k_composite's
+// per-pixel sequence without colour; max / integer adds into the planes, the view's pair count and weight sum into words[0..3],
+// the final T of every pixel into `transmittance` (w_px x h_px; nullable).
+hipError_t launch_vis_tiles(hipStream_t s, const FrameConsts& f, const uint2* ranges, const uint32_t* list, const Records& rec, const VisPlanes& planes,
+                            float* transmittance, uint32_t* words);
+hipError_t launch_vis_stats(hipStream_t s, uint64_t n, const VisPlanes& planes, uint32_t* words);  // words[4..5] (zeroed before)
+struct VisSelectJob {
+    VisPlanes planes;
+    uint32_t measure;    // gsx_visibility_measure
+    double lo, hi;
+    SelectionWrite sel;  // its partials: extract_groups(n) x kSelectPartialWords words
+    uint32_t* words;
+};
+hipError_t launch_vis_select(hipStream_t s, uint64_t n, const ModelFilter& f, const VisSelectJob& job);  // the selection, words[6..7]
+
 // Compositing and resolve.
 // carry: continue from the (C, T) already in fb (later slabs / models behind); done: saturated-tile bitmap
 // (read to skip tiles when carrying, updated when a tile saturates; nullable).

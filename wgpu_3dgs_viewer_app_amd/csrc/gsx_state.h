@@ -252,6 +252,10 @@ struct Model {
     bool repair_counted = false;
     bool verify_state_zeroed = false;   // the last feedback kernel zeroed the verification's counters and need bitmap on its way
     uint32_t pack_rounds = 16;     // tile size (x 256 records) of the last pack_count: its table layout (kernels_shard.hip)
+    // gsx_model_visibility (gsx_api_visibility.cpp; spec section 24): the resident planes, 16 bytes a Gaussian (vis_planes), and how many
+    // views were folded into them.  Dropped (drop_visibility) by every call that rewrites the pod planes or the count
+    DevBuf vis;
+    uint32_t vis_views = 0;
     bool pack_list = false, pack_travellers = false;  // how the last pack_count addressed the records / whether it left travellers to shade   // gsx_shard_repair_count has left masks / table / travellers for the repair pack
 
     ~Model() {
@@ -508,6 +512,9 @@ struct gsx_viewer {
     // buffer for "the kernel is done with the buffer" and one for "the copy is done with it".  Both calls wait for both streams before
     // they return, so the buffers never serve two calls at once.  Allocated by the first call that moves rows (row_streams), grown when
     // a call asks for larger staging, freed with the viewer
+    // gsx_model_visibility (gsx_api_visibility.cpp; owner only): the framebuffer its frame is drawn into instead of `fb`, and [the
+    // call's words, 128 B | the select's partials | the view's transmittance], allocated by the first call.  Nothing a frame reads
+    DevBuf vis_fb, vis_ws;
     DevBuf row_stage[2];
     hipStream_t row_stream = nullptr;
     hipEvent_t row_kernel_done[2]{}, row_copy_done[2]{};
@@ -739,6 +746,11 @@ inline ModelFilter model_filter(const Model* m, uint32_t filter_bits, bool inver
     }
     f.invert = invert ? 1u : 0u;
     return f;
+}
+// the visibility planes describe the pod planes they were measured on: every call that rewrites those, or the count, drops them
+inline void drop_visibility(Model* m) {
+    m->vis.release();
+    m->vis_views = 0;
 }
 // the copy stream and the events of the row staging buffers, created on first use (gsx_api_export.cpp)
 gsx_status row_streams(gsx_viewer* v);

@@ -441,6 +441,27 @@ def _compose34(a, b):
 
 
 @dataclasses.dataclass
+class ModelVisibility:
+    """What ``MultiModelViewerModel.visibility`` returns: the model's resident planes after the call and this view's statistics.
+    ``peak`` (float32, one per Gaussian, or ``None``): the largest blending weight ``T * alpha`` any pixel of any folded view gave
+    it; ``weight`` (float64): the sum of those weights over the pixels, in 2^-24 fixed point; ``pixels`` (uint32): the pixels that
+    blended it; ``transmittance`` (float32 ``(H, W)``, or ``None``): the final ``T`` of every pixel of THIS view; ``n_visible``: after
+    cull, this view; ``n_seen``: Gaussians with ``peak > 0``; ``n_pairs`` and ``weight_fixed``: this view's blended (pixel, Gaussian)
+    pairs and the integer sum of their fixed-point weights; ``peak_max``; ``views``: the views folded into the planes."""
+
+    peak: np.ndarray | None
+    weight: np.ndarray | None
+    pixels: np.ndarray | None
+    transmittance: np.ndarray | None
+    n_visible: int
+    n_seen: int
+    n_pairs: int
+    weight_fixed: int
+    peak_max: np.float32
+    views: int
+
+
+@dataclasses.dataclass
 class ModelDecimate:
     """What ``MultiModelViewerModel.decimate`` and ``decimate_count`` return.  ``count``: participants (pass the filter, finite
     position); ``n_nonfinite``: passed the filter with a NaN or infinite coordinate (dropped); ``cells``: occupied cells, the new
@@ -760,6 +781,52 @@ class MultiModelViewerModel:
         _lib.check(self._v._L.gsx_model_decimate_edge(self._v._h, self._key.encode(), int(filter), _lib.GSX_EXTRACT_INVERT if invert else 0,
                                                       int(target), C.byref(cell), C.byref(cells)))
         return np.float32(cell.value), int(cells.value)
+
+    def visibility(self, accumulate: bool = False, rows: bool = True, transmittance: bool = False) -> ModelVisibility:
+        """``gsx_model_visibility``: draws this model ALONE with the viewer's current camera, viewport, transforms and spec
+        parameters (what ``render_frame([key])`` would draw) and keeps, per Gaussian and on the device, what the compositor throws
+        away: the peak blending weight, the summed weight and the pixel count.  ``accumulate`` folds the view into the planes an
+        earlier call left (maximum, sums) instead of replacing them.  ``rows=False`` returns the statistics alone.  The model must go
+        through ``preprocess`` + ``sort`` again before ``render``; ``render_frame`` needs nothing."""
+        n = self.gaussian_buffers.gaussians_buffer.len()
+        w, h = self._v.size
+        desc = _lib.VisibilityDesc(_lib.GSX_VIS_ACCUMULATE if accumulate else 0)
+        peak = np.zeros(n, np.float32) if rows else None
+        weight = np.zeros(n, np.float64) if rows else None
+        pixels = np.zeros(n, np.uint32) if rows else None
+        trans = np.empty((h, w), np.float32) if transmittance else None
+        out = _lib.VisibilityStats()
+        _lib.check(self._v._L.gsx_model_visibility(self._v._h, self._key.encode(), C.byref(desc), peak.ctypes.data if rows else None,
+                                                   weight.ctypes.data if rows else None, pixels.ctypes.data if rows else None,
+                                                   trans.ctypes.data if transmittance else None, C.byref(out)))
+        return ModelVisibility(peak, weight, pixels, trans, int(out.n_visible), int(out.n_seen), int(out.n_pairs), int(out.weight_fixed),
+                               np.float32(out.peak_max), int(out.views))
+
+    def select_visibility(self, measure: int = 0, lo: float = 0.0, hi: float = float("inf"), op: int = 0, filter: int = 0) -> tuple[int, int]:  # noqa: A002
+        """``gsx_model_select_visibility``: selects the Gaussians that pass ``filter`` (``_lib.GSX_BOUNDS_*`` bits) and whose resident
+        measure (``_lib.GSX_VIS_PEAK`` / ``_WEIGHT`` / ``_PIXELS``) lies in ``[lo, hi]``.  "Never seen" is ``select_visibility(GSX_VIS_PEAK,
+        0, 0)``; a contribution prune is that, then ``extract(dst, SELECTED, invert=True)``.  Returns ``(hit, selected)``."""
+        desc = _lib.VisibilitySelectDesc(int(measure), int(filter), int(op), 0, float(lo), float(hi))
+        hit, selected = C.c_uint64(), C.c_uint64()
+        _lib.check(self._v._L.gsx_model_select_visibility(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected)))
+        return int(hit.value), int(selected.value)
+
+    def visibility_reset(self) -> None:
+        """``gsx_model_visibility_reset``: frees the resident planes."""
+        _lib.check(self._v._L.gsx_model_visibility_reset(self._v._h, self._key.encode()))
+
+    def visibility_orbit(self, cameras, size=None, rows: bool = True) -> ModelVisibility:
+        """Resets the planes, then folds one view per camera of ``cameras`` (``update_camera`` with ``size``, default the viewer's
+        current viewport): the planes then hold every Gaussian's best and summed contribution over the orbit.  Returns the last
+        call's result (the planes after all views).  The viewer keeps the last camera."""
+        size = self._v.size if size is None else size
+        self.visibility_reset()
+        cameras = list(cameras)
+        out = None
+        for k, cam in enumerate(cameras):
+            self._v.update_camera(cam, size)
+            out = self.visibility(accumulate=True, rows=rows and k + 1 == len(cameras))
+        return out
 
     def _export_desc(self, filter, invert, bake_edits, fmt, staging_bytes):  # noqa: A002
         return _lib.ExportDesc(int(filter), (_lib.GSX_EXTRACT_INVERT if invert else 0) | (_lib.GSX_EXPORT_BAKE_EDITS if bake_edits else 0),
