@@ -1,9 +1,11 @@
 // knn_driver.cpp — csrc/knn_math.h and csrc/neighbors_math.h played on the host through a plain C++ version of the whole search of the
 // nearest neighbours (spec §20), for tests/test_knn_cpu.py: a stand-alone program the test builds with the address and
-// undefined-behaviour sanitizers and -ffp-contract=off.  The search is the device's, step for step: the extent, the radius floor and
-// the first radius, section 18's hashed grid by a counting sort, rounds of one query an entry over 27 cells with the own-cell test, the
-// proven rule, the unresolved list, the rule that goes to the exact fallback, and the fallback as 256 strided per-lane lists merged
-// with multiplicity by (value bits, lane).  Every float crosses as the hex of its bits.  stdin, one command a line (hex words):
+// undefined-behaviour sanitizers and -ffp-contract=off.  The loop over the rounds is the library's own, not a restatement:
+// csrc/radius_search.h, which gsx_api_knn.cpp runs, derives the radius floor and the first radius, rebuilds the grid, decides when the
+// unresolved go to the exact fallback and counts the rounds; this file supplies the work (but for one input: it hands the loop the
+// whole box where the device hands it the 10 permille trimmed box of the bounds passes): section 18's hashed grid by a counting sort
+// (grid_replay.h), a round of one query an entry over 27 cells with the own-cell test and the proven rule, the unresolved list, and the
+// fallback as 256 strided per-lane lists merged with multiplicity by (value bits, lane).  Every float crosses as the hex of its bits.  stdin, one command a line (hex words):
 //   "search <k> <score> <hint> <grid_bits> <max_rounds> <x y z> ..."
 //        stdout "search <participants> <rounds> <n_brute> <first radius> <rows that differ from the O(n^2) loop> <scores that differ>"
 //               "rows <n * k values>"  "scores <n values>"
@@ -22,72 +24,18 @@
 #include <string>
 #include <vector>
 
+#include "grid_replay.h"
 #include "knn_math.h"
 #include "neighbors_math.h"
+#include "radius_search.h"
 
 using namespace gsx;
 
-static std::vector<uint32_t> words(const char* s) {
-    std::vector<uint32_t> v;
-    char* end = nullptr;
-    for (;;) {
-        while (*s == ' ') ++s;
-        const unsigned long x = strtoul(s, &end, 16);
-        if (end == s) break;
-        v.push_back((uint32_t)x);
-        s = end;
-    }
-    return v;
-}
-static uint32_t bits_of(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return u;
-}
 static double double_of(uint32_t lo, uint32_t hi) {
     const uint64_t u = ((uint64_t)hi << 32) | lo;
     double d;
     memcpy(&d, &u, 8);
     return d;
-}
-
-struct Rec {
-    float x, y, z;
-    uint32_t index;
-};
-struct Grid {
-    NbGrid g;
-    float origin[3];
-    uint32_t bits;
-    std::vector<uint32_t> ends;  // the table after the scatter: bucket b holds records [ends[b - 1], ends[b])
-    std::vector<Rec> records;
-};
-
-static Grid build_grid(const std::vector<Rec>& part, float radius, uint32_t bits) {
-    Grid gr;
-    gr.g = nb_grid(radius);
-    gr.bits = bits;
-    for (int a = 0; a < 3; ++a) gr.origin[a] = INFINITY;
-    for (const Rec& r : part) {
-        gr.origin[0] = fminf(gr.origin[0], r.x);
-        gr.origin[1] = fminf(gr.origin[1], r.y);
-        gr.origin[2] = fminf(gr.origin[2], r.z);
-    }
-    const auto bucket = [&](const Rec& r) {
-        return nb_bucket(nb_cell(r.x, gr.origin[0], gr.g.inv_h), nb_cell(r.y, gr.origin[1], gr.g.inv_h), nb_cell(r.z, gr.origin[2], gr.g.inv_h), bits);
-    };
-    std::vector<uint32_t> table(size_t(1) << bits, 0u);
-    for (const Rec& r : part) table[bucket(r)] += 1u;
-    uint32_t at = 0;
-    for (uint32_t& w : table) {  // sizes -> starts
-        const uint32_t size = w;
-        w = at;
-        at += size;
-    }
-    gr.records.resize(part.size());
-    for (const Rec& r : part) gr.records[table[bucket(r)]++] = r;  // starts -> ends
-    gr.ends = table;
-    return gr;
 }
 
 // k_knn_query's lane: true where the row is proven (b holds it)
@@ -167,28 +115,25 @@ static void search(const std::vector<float>& pos, uint32_t k, uint32_t score, fl
     }
     const uint32_t P = (uint32_t)part.size();
     out.participants = P;
-    double ext[3] = {0.0, 0.0, 0.0};
-    for (int a = 0; a < 3 && P; ++a) ext[a] = (double)mx[a] - (double)mn[a];
-    float radius = knn_clamp_radius(hint > 0.0f ? hint : knn_first_radius(ext, P, k), knn_radius_floor(ext));
-    out.first_radius = radius;
-    if (!nb_radius_ok(radius)) abort();
+    RadiusSearch s{{}, {}, P, hint, k, 0.0f, max_rounds};  // (uncapped; the extents stay 0 without participants)
+    for (int a = 0; a < 3 && P; ++a) s.ext[a] = s.trimmed[a] = (double)mx[a] - (double)mn[a];
     const uint32_t bits = grid_bits ? grid_bits : nb_auto_bits(n);
-    Grid gr = build_grid(part, radius, bits);
+    Grid gr;
+    std::vector<Rec> list[2];
+    const std::vector<Rec>* src = &gr.records;  // the first list: the grid's records
     const auto store = [&](const Rec& self, const float (&b)[K]) {
         out.scores[self.index] = knn_score(b, k, score);
         knn_store(b, k, &out.rows[(size_t)self.index * k]);
     };
-    std::vector<Rec> list = gr.records;
-    uint32_t rounds = 0;
-    const auto next_radius = [&] { return rounds ? knn_next_radius(radius) : radius; };
-    while (!list.empty() && !knn_go_brute(list.size(), P, rounds, max_rounds, next_radius(), knn_coarse(next_radius(), ext))) {
-        if (rounds) {
-            radius = knn_next_radius(radius);
-            if (!nb_radius_ok(radius)) abort();
-            gr = build_grid(part, radius, bits);
-        }
-        std::vector<Rec> next;
-        for (const Rec& self : list) {
+    const auto grid = [&](float r, bool final_round) {
+        if (!nb_radius_ok(r) || final_round) abort();
+        gr = build_grid(part, r, bits);
+        return false;
+    };
+    const auto round = [&](uint32_t i, uint32_t U, bool, uint32_t* left) {
+        std::vector<Rec>& next = list[i & 1u];
+        next.clear();
+        for (const Rec& self : *src) {
             float b[K];
             if (query_entry<K>(gr, self, k, b))
                 store(self, b);
@@ -196,16 +141,22 @@ static void search(const std::vector<float>& pos, uint32_t k, uint32_t score, fl
                 next.push_back(self);
         }
         std::reverse(next.begin(), next.end());  // (the list's order is free)
-        list.swap(next);
-        rounds += 1u;
-    }
-    for (const Rec& self : list) {
-        float row[K];
-        brute_entry<K>(gr.records, self, k, row);
-        store(self, row);
-    }
-    out.rounds = rounds;
-    out.n_brute = (uint32_t)list.size();
+        *left = (uint32_t)next.size();
+        src = &next;
+        return false;
+    };
+    const auto brute = [&](uint32_t) {
+        for (const Rec& self : *src) {
+            float row[K];
+            brute_entry<K>(gr.records, self, k, row);
+            store(self, row);
+        }
+        return false;
+    };
+    radius_search<bool>(s, P, grid, round, brute);
+    out.first_radius = s.first_radius;
+    out.rounds = s.rounds;
+    out.n_brute = s.n_brute;
 }
 
 // the definition: every pair, self excluded by index, the k smallest with multiplicity

@@ -1,13 +1,14 @@
 // nearest_driver.cpp — csrc/nearest_math.h, csrc/align_math.h, csrc/knn_math.h and csrc/neighbors_math.h played on the host through a
 // plain C++ version of the whole nearest search across models (spec §23), for tests/test_nearest_cpu.py: a stand-alone program the
-// test builds with the address and undefined-behaviour sanitizers and -ffp-contract=off.  The search is the device's, step for step
-// (but for one input of two rules that choose a path and no result: the first radius and knn_coarse take the targets' whole box here,
-// where the device hands them the 10 permille trimmed box of the bounds passes; tests/test_gpu_nearest.py covers a box that is a point):
-// the queries mapped by the matrix, the targets' extent, radius floor and first radius, section 18's hashed grid over the targets by a
-// counting sort, rounds of one query an entry over 27 cells from its SIGNED cell with the own-cell test, the best (d2, index) pair,
-// the proven rule under the max_distance cap, the final round, the unresolved list, the rule that goes to the exact fallback, and the
-// fallback as 256 strided lanes folded by the key (d2 bits << 32) | index.  Every float crosses as the hex of its bits.  stdin, one
-// command a line (hex words):
+// test builds with the address and undefined-behaviour sanitizers and -ffp-contract=off.  The loop over the rounds is the library's
+// own, not a restatement: csrc/radius_search.h, which gsx_api_nearest.cpp runs, derives the radius floor and the first radius under
+// the max_distance cap, rebuilds the grid, says which round is final, decides when the unresolved go to the exact fallback and counts
+// the rounds.  This file supplies the work (but for one input of two rules that choose a path and no result: the first radius and
+// knn_coarse take the targets' whole box here, where the device hands the loop the 10 permille trimmed box of the bounds passes;
+// tests/test_gpu_nearest.py covers a box that is a point): the queries mapped by the matrix, the targets' extent, section 18's hashed
+// grid over the targets by a counting sort (grid_replay.h), a round of one query an entry over 27 cells from its SIGNED cell with the
+// own-cell test, the best (d2, index) pair and the proven rule under the cap, the unresolved list, and the fallback as 256 strided
+// lanes folded by the key (d2 bits << 32) | index.  Every float crosses as the hex of its bits.  stdin, one command a line (hex words):
 //   "search <max_distance> <hint> <grid_bits> <max_rounds> <n queries> <12 matrix words> <query x y z> ... <target x y z> ..."
 //        stdout "search <queries that participate> <targets> <rounds> <n_brute> <first radius> <indices that differ from the O(n m) loop>
 //                <d2 that differ> <signed cells seen: bit 0: -2, bit 1: -1, bit 2: 0, bit 3: the clamp>"
@@ -27,68 +28,13 @@
 #include <vector>
 
 #include "align_math.h"
+#include "grid_replay.h"
 #include "knn_math.h"
 #include "nearest_math.h"
 #include "neighbors_math.h"
+#include "radius_search.h"
 
 using namespace gsx;
-
-static std::vector<uint32_t> words(const char* s) {
-    std::vector<uint32_t> v;
-    char* end = nullptr;
-    for (;;) {
-        while (*s == ' ') ++s;
-        const unsigned long x = strtoul(s, &end, 16);
-        if (end == s) break;
-        v.push_back((uint32_t)x);
-        s = end;
-    }
-    return v;
-}
-static uint32_t bits_of(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return u;
-}
-
-struct Rec {
-    float x, y, z;
-    uint32_t index;
-};
-struct Grid {
-    NbGrid g;
-    float origin[3];
-    uint32_t bits;
-    std::vector<uint32_t> ends;  // the table after the scatter: bucket b holds records [ends[b - 1], ends[b])
-    std::vector<Rec> records;
-};
-
-static Grid build_grid(const std::vector<Rec>& part, float radius, uint32_t bits) {
-    Grid gr;
-    gr.g = nb_grid(radius);
-    gr.bits = bits;
-    for (int a = 0; a < 3; ++a) gr.origin[a] = INFINITY;
-    for (const Rec& r : part) {
-        gr.origin[0] = fminf(gr.origin[0], r.x);
-        gr.origin[1] = fminf(gr.origin[1], r.y);
-        gr.origin[2] = fminf(gr.origin[2], r.z);
-    }
-    const auto bucket = [&](const Rec& r) {
-        return nb_bucket(nb_cell(r.x, gr.origin[0], gr.g.inv_h), nb_cell(r.y, gr.origin[1], gr.g.inv_h), nb_cell(r.z, gr.origin[2], gr.g.inv_h), bits);
-    };
-    std::vector<uint32_t> table(size_t(1) << bits, 0u);
-    for (const Rec& r : part) table[bucket(r)] += 1u;
-    uint32_t at = 0;
-    for (uint32_t& w : table) {  // sizes -> starts
-        const uint32_t size = w;
-        w = at;
-        at += size;
-    }
-    gr.records.resize(part.size());
-    for (const Rec& r : part) gr.records[table[bucket(r)]++] = r;  // starts -> ends
-    gr.ends = table;
-    return gr;
-}
 
 static uint32_t g_cells_seen = 0;
 static void see_cell(int32_t c) {
@@ -167,9 +113,9 @@ static void search(const float* m, const std::vector<float>& qpos, const std::ve
     const size_t n = qpos.size() / 3, n_dst = tpos.size() / 3;
     out.index.assign(n, kNearestNone);
     out.d2.assign(n, INFINITY);
-    std::vector<Rec> list, part;
-    mapped(m, qpos, list);
-    std::reverse(list.begin(), list.end());  // (the first list's order is free)
+    std::vector<Rec> list[2], part;
+    mapped(m, qpos, list[1]);
+    std::reverse(list[1].begin(), list[1].end());  // (the first list's order is free)
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (size_t i = 0; i < n_dst; ++i) {
         const Rec r{tpos[3 * i], tpos[3 * i + 1], tpos[3 * i + 2], (uint32_t)i};
@@ -179,37 +125,28 @@ static void search(const float* m, const std::vector<float>& qpos, const std::ve
         mx[0] = fmaxf(mx[0], r.x); mx[1] = fmaxf(mx[1], r.y); mx[2] = fmaxf(mx[2], r.z);
     }
     const uint32_t P = (uint32_t)part.size();
-    out.queries = (uint32_t)list.size();
+    out.queries = (uint32_t)list[1].size();
     out.targets = P;
-    if (!P || list.empty()) return;
+    if (!P || list[1].empty()) return;
     const float cap2 = nearest_cap2(max_distance);
-    double ext[3];
-    for (int a = 0; a < 3; ++a) ext[a] = (double)mx[a] - (double)mn[a];
-    const float floor_ = knn_radius_floor(ext);
-    float radius = nearest_round_radius(knn_clamp_radius(hint > 0.0f ? hint : knn_first_radius(ext, P, 1u), floor_), floor_, max_distance);
-    out.first_radius = radius;
-    if (!nb_radius_ok(radius)) abort();
+    RadiusSearch s{{}, {}, P, hint, 1u, max_distance, max_rounds};
+    for (int a = 0; a < 3; ++a) s.ext[a] = s.trimmed[a] = (double)mx[a] - (double)mn[a];
     const uint32_t bits = grid_bits ? grid_bits : nb_auto_bits(n_dst);
-    Grid gr = build_grid(part, radius, bits);
+    Grid gr;
+    const std::vector<Rec>* src = &list[1];  // the first list: the mapped queries
     const auto store = [&](const Rec& self, float best, uint32_t best_index) {
         out.index[self.index] = best_index;
         out.d2[self.index] = best;
     };
-    uint32_t rounds = 0;
-    const auto next_radius = [&] {
-        if (!rounds) return radius;
-        const float next = knn_next_radius(radius);
-        return next == 0.0f ? 0.0f : nearest_round_radius(next, floor_, max_distance);
+    const auto grid = [&](float r, bool) {
+        if (!nb_radius_ok(r)) abort();
+        gr = build_grid(part, r, bits);
+        return false;
     };
-    while (!list.empty() && !knn_go_brute(list.size(), P, rounds, max_rounds, next_radius(), knn_coarse(next_radius(), ext))) {
-        if (rounds) {
-            radius = next_radius();
-            if (!nb_radius_ok(radius)) abort();
-            gr = build_grid(part, radius, bits);
-        }
-        const bool final_round = nearest_final(gr.g.r2, cap2);
-        std::vector<Rec> next;
-        for (const Rec& self : list) {
+    const auto round = [&](uint32_t i, uint32_t U, bool final_round, uint32_t* left) {
+        std::vector<Rec>& next = list[i & 1u];  // (round 0 reads list[1]: every round reads the list the one before wrote)
+        next.clear();
+        for (const Rec& self : *src) {
             float best;
             uint32_t best_index;
             if (query_entry(gr, self, cap2, best, best_index))
@@ -218,18 +155,23 @@ static void search(const float* m, const std::vector<float>& qpos, const std::ve
                 next.push_back(self);
         }
         std::reverse(next.begin(), next.end());  // (the list's order is free)
-        list.swap(next);
-        rounds += 1u;
-        if (final_round && !list.empty()) abort();
-    }
-    for (const Rec& self : list) {
-        float best;
-        uint32_t best_index;
-        brute_entry(gr.records, self, cap2, best, best_index);
-        if (best_index != kNearestNone) store(self, best, best_index);
-    }
-    out.rounds = rounds;
-    out.n_brute = (uint32_t)list.size();
+        *left = (uint32_t)next.size();
+        src = &next;
+        return false;
+    };
+    const auto brute = [&](uint32_t) {
+        for (const Rec& self : *src) {
+            float best;
+            uint32_t best_index;
+            brute_entry(gr.records, self, cap2, best, best_index);
+            if (best_index != kNearestNone) store(self, best, best_index);
+        }
+        return false;
+    };
+    radius_search<bool>(s, out.queries, grid, round, brute);
+    out.first_radius = s.first_radius;
+    out.rounds = s.rounds;
+    out.n_brute = s.n_brute;
 }
 
 // the definition: every pair, the least (d2, index) within the cap

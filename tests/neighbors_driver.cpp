@@ -18,27 +18,10 @@
 #include <string>
 #include <vector>
 
+#include "grid_replay.h"
 #include "neighbors_math.h"
 
 using namespace gsx;
-
-static std::vector<uint32_t> words(const char* s) {
-    std::vector<uint32_t> v;
-    char* end = nullptr;
-    for (;;) {
-        while (*s == ' ') ++s;
-        const unsigned long x = strtoul(s, &end, 16);
-        if (end == s) break;
-        v.push_back((uint32_t)x);
-        s = end;
-    }
-    return v;
-}
-static uint32_t bits_of(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return u;
-}
 
 struct Rng {
     uint64_t s;

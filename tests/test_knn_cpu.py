@@ -109,6 +109,12 @@ def test_the_rules_have_one_copy_and_the_build_lists_the_sources():
     assert '#include "neighbors_math.h"' in math_h and "nb_d2(" not in math_h.split("#pragma once")[1]  # the distance is section 18's
     makefile = _read("wgpu_3dgs_viewer_app_amd", "csrc", "Makefile")
     assert "kernels_knn.hip" in makefile and "gsx_api_knn.cpp" in makefile and "-ffp-contract=off" in makefile
+    # the loop over the rounds has one copy too: the library and the driver run radius_search.h, and neither decides the fallback itself
+    search = driver.split("static void search(")[1].split("\n}\n")[0]
+    assert '#include "radius_search.h"' in api and '#include "radius_search.h"' in driver and "radius_search<" in api and "radius_search<" in search
+    assert "knn_go_brute(" not in api and "knn_go_brute(" not in search and "#include <hip" not in _read("wgpu_3dgs_viewer_app_amd", "csrc", "radius_search.h")
+    sources = [_read("tests", f) for f in sorted(os.listdir(os.path.join(ROOT, "tests"))) if f.endswith((".cpp", ".h"))]
+    assert sum(s.count("struct Grid {") for s in sources) == 1 and sum(s.count("Grid build_grid(") for s in sources) == 1  # grid_replay.h
 
 
 # ---- 2. csrc/knn_math.h: the driver -----------------------------------------------------------------------------------------------

@@ -129,6 +129,12 @@ def test_the_rules_have_one_copy_and_the_build_lists_the_sources():
     assert "below the origin" in _read("wgpu_3dgs_viewer_app_amd", "csrc", "neighbors_grid.h").lower()  # the proof is extended in writing
     makefile = _read("wgpu_3dgs_viewer_app_amd", "csrc", "Makefile")
     assert "kernels_nearest.hip" in makefile and "gsx_api_nearest.cpp" in makefile and "-ffp-contract=off" in makefile
+    # the loop over the rounds has one copy too: the library and the driver run radius_search.h, and neither decides the fallback itself
+    search = driver.split("static void search(")[1].split("\n}\n")[0]
+    assert '#include "radius_search.h"' in api and '#include "radius_search.h"' in driver and "radius_search<" in api and "radius_search<" in search
+    assert "knn_go_brute(" not in api and "knn_go_brute(" not in search
+    sources = [_read("tests", f) for f in sorted(os.listdir(os.path.join(ROOT, "tests"))) if f.endswith((".cpp", ".h"))]
+    assert sum(s.count("struct Grid {") for s in sources) == 1 and sum(s.count("Grid build_grid(") for s in sources) == 1  # grid_replay.h
 
 
 # ---- 2. the driver ------------------------------------------------------------------------------------------------------------------

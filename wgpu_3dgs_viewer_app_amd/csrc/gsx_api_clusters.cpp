@@ -27,10 +27,8 @@ size_t cluster_ws(char* ws, uint64_t n, uint32_t bits, ClusterJob* job) {
 // The workspace (grown if need be: the only step that can fail for memory) and the job of a call; n > 0.
 gsx_status cluster_job(gsx_viewer* v, const Model* m, float radius, uint32_t grid_bits, ClusterJob* job) {
     const uint32_t bits = grid_bits ? grid_bits : nb_auto_bits(m->n);
-    ClusterJob sized{};
-    HIPCHK(v->extract_ws.ensure(cluster_ws(nullptr, m->n, bits, &sized)));
-    *job = ClusterJob{};
-    cluster_ws(v->extract_ws.as<char>(), m->n, bits, job);
+    const gsx_status st = place_job(v, job, [&](char* ws, ClusterJob* j) { return cluster_ws(ws, m->n, bits, j); });
+    if (st) return st;
     const NbGrid g = nb_grid(radius);
     job->nb.r2 = g.r2;
     job->nb.inv_h = g.inv_h;

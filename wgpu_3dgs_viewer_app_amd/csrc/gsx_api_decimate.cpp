@@ -47,11 +47,9 @@ gsx_status check_filter(const char* fn, uint32_t filter, uint32_t flags, uint32_
 
 // The workspace (grown if need be: the only step before dst that can fail for memory) and the job of a model; n > 0.
 gsx_status decimate_job(gsx_viewer* v, const Model* m, uint32_t bits, DecimateJob* job) {
-    DecimateJob sized{};
-    HIPCHK(v->extract_ws.ensure(decimate_ws(nullptr, neighbor_ws(nullptr, m->n, bits, &sized.nb), m->n, &sized)));
-    *job = DecimateJob{};
-    char* ws = v->extract_ws.as<char>();
-    decimate_ws(ws, neighbor_ws(ws, m->n, bits, &job->nb), m->n, job);
+    // (decimate's regions start behind the grid's bytes)
+    const gsx_status st = place_job(v, job, [&](char* ws, DecimateJob* j) { return decimate_ws(ws, neighbor_ws(ws, m->n, bits, &j->nb), m->n, j); });
+    if (st) return st;
     job->nb.bits = bits;
     job->nb.max_count = 1u;
     return GSX_OK;

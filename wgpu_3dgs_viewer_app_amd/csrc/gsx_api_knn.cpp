@@ -2,12 +2,12 @@
 // gsx_model_select_knn.  The filter is model_filter's, the grid section 18's (neighbors_host.h), rebuilt once a round at the round's
 // radius, the rules knn_math.h's, the workspace the model operations' (v->extract_ws): the grid's regions, then [the kNN's words, 128 B
 // | its partials, 32 B a workgroup | the box, its partials and histogram | the scores, 4 B a Gaussian | two lists, 16 B a Gaussian
-// each | the rows, 4 k B a Gaussian, only when the caller wants them].  The host looks at the device once for the box and once a
-// round for the unresolved count.
+// each | the rows, 4 k B a Gaussian, only when the caller wants them].  The host looks at the device once for the box
+// (participants_box) and once a round for the unresolved count; the rounds' schedule is radius_search.h's, its uncapped case.
 #include "gsx_state.h"
-#include "bounds_math.h"
 #include "knn_math.h"
 #include "neighbors_host.h"
+#include "radius_search.h"
 
 using namespace gsx;
 
@@ -23,9 +23,7 @@ size_t knn_ws(char* ws, uint64_t n, uint32_t bits, uint32_t k, bool rows, KnnJob
     WsCursor c{ws, neighbor_ws(ws, n, bits, &job->nb)};
     job->words = c.take<uint32_t>(4 * kKnnWords);
     job->partials = c.take<uint32_t>(4 * kKnnPartialWords * (size_t)extract_groups(n));
-    job->box = c.take<gsx_model_bounds_t>(sizeof(gsx_model_bounds_t));
-    job->box_partials = c.take<BoundsPartial>(sizeof(BoundsPartial) * kBoundsMaxGroups);
-    job->box_hist = c.take<uint32_t>(4 * 3u * kBoundsBins);
+    job->box = take_box(c);
     job->scores = c.take<float>(4 * (size_t)n);
     job->list[0] = c.take<uint4>(16 * (size_t)n);
     job->list[1] = c.take<uint4>(16 * (size_t)n);
@@ -49,10 +47,8 @@ gsx_status check_knn(const char* fn, uint32_t filter, uint32_t flags, uint32_t k
 // The workspace (grown if need be: the only step that can fail for memory) and the job of a call; n > 0.
 gsx_status knn_job(gsx_viewer* v, const Model* m, uint32_t k, uint32_t score, uint32_t grid_bits, bool rows, KnnJob* job) {
     const uint32_t bits = grid_bits ? grid_bits : nb_auto_bits(m->n);
-    KnnJob sized{};
-    HIPCHK(v->extract_ws.ensure(knn_ws(nullptr, m->n, bits, k, rows, &sized)));
-    *job = KnnJob{};
-    knn_ws(v->extract_ws.as<char>(), m->n, bits, k, rows, job);
+    const gsx_status st = place_job(v, job, [&](char* ws, KnnJob* j) { return knn_ws(ws, m->n, bits, k, rows, j); });
+    if (st) return st;
     job->nb.bits = bits;
     job->nb.max_count = kNbMaxCount;
     job->k = k;
@@ -65,53 +61,30 @@ gsx_status knn_job(gsx_viewer* v, const Model* m, uint32_t k, uint32_t score, ui
 gsx_status run_knn(gsx_viewer* v, const Model* m, const ModelFilter& f, KnnJob& job, float radius_hint, uint32_t max_rounds, gsx_knn_stats_t* stats) {
     const uint64_t n = m->n;
     HIPCHK(gsx::op::MemsetAsync(job.words, 0, 4 * kKnnWords, v->stream));
-    // the participants' count, box and trimmed box: gsx_model_bounds' passes, whose participants are the same
-    const uint64_t looked_at = f.select_none ? 0 : n;  // (selected Gaussians of a model without a selection: none)
-    if (looked_at) HIPCHK(launch_bounds_reduce(v->stream, m->pc.as<float4>(), n, f, job.box_partials));
-    HIPCHK(launch_bounds_finish(v->stream, job.box_partials, looked_at ? bounds_reduce_groups(n) : 0u, looked_at != 0, job.box, job.box_hist));
-    if (looked_at) HIPCHK(launch_bounds_trim(v->stream, m->pc.as<float4>(), n, f, kKnnTrimPermille, job.box, job.box_hist));
-    HIPCHK(launch_knn_fill(v->stream, n, job));
-    HIPCHK(gsx::op::StreamSynchronize(v->stream));
-    gsx_model_bounds_t box;
-    HIPCHK(gsx::op::Memcpy(&box, job.box, sizeof box, hipMemcpyDeviceToHost));
-    const uint32_t P = (uint32_t)box.count;
-    stats->count = box.count;
-    stats->n_nonfinite = box.n_nonfinite;
-    double ext[3], trimmed[3];
-    for (int a = 0; a < 3; ++a) {
-        ext[a] = (double)box.max[a] - (double)box.min[a];
-        trimmed[a] = (double)box.trim_max[a] - (double)box.trim_min[a];
-    }
-    const float floor_ = knn_radius_floor(ext);
-    float radius = knn_clamp_radius(radius_hint > 0.0f ? radius_hint : knn_first_radius(trimmed, P, job.k), floor_);
-    stats->first_radius = radius;
-    const auto grid = [&](float r) {  // the participant bits, the table and the records at radius r
-        const NbGrid g = nb_grid(r);
-        job.nb.r2 = g.r2;
-        job.nb.inv_h = g.inv_h;
-        return enqueue_grid(v, m, f, job.nb);
-    };
-    gsx_status st = grid(radius);  // (also without participants: the select reads the participant bits)
+    RadiusSearch s{{}, {}, 0u, radius_hint, job.k, 0.0f, max_rounds};  // (uncapped)
+    gsx_status st = participants_box(v, m, f, job.box, [&] { return launch_knn_fill(v->stream, n, job); }, &s, &stats->n_nonfinite);
     if (st) return st;
-    const uint4* src = job.nb.records;
-    uint32_t U = P, rounds = 0;
-    const auto next_radius = [&] { return rounds ? knn_next_radius(radius) : radius; };  // the radius of the round to come
-    while (U && !knn_go_brute(U, P, rounds, max_rounds, next_radius(), knn_coarse(next_radius(), trimmed))) {
-        if (rounds) {
-            radius = knn_next_radius(radius);
-            if ((st = grid(radius))) return st;
-        }
-        const uint32_t to = rounds & 1u;
+    stats->count = s.P;
+    const uint4* src = job.nb.records;  // the first list: the grid's records
+    // the participant bits, the table and the records at radius r (also without participants: the select reads the participant bits)
+    const auto grid = [&](float r, bool) { return enqueue_grid_at(v, m, f, job.nb, r); };
+    const auto round = [&](uint32_t i, uint32_t U, bool, uint32_t* left) -> gsx_status {
+        const uint32_t to = i & 1u;
         HIPCHK(gsx::op::MemsetAsync(job.words + kKnnList + to, 0, 4, v->stream));
         HIPCHK(launch_knn_query(v->stream, n, src, U, to, job));
-        rounds += 1u;
         HIPCHK(gsx::op::StreamSynchronize(v->stream));  // the one look a round: how many are left
-        HIPCHK(gsx::op::Memcpy(&U, job.words + kKnnList + to, 4, hipMemcpyDeviceToHost));
+        HIPCHK(gsx::op::Memcpy(left, job.words + kKnnList + to, 4, hipMemcpyDeviceToHost));
         src = job.list[to];
-    }
-    if (U) HIPCHK(launch_knn_brute(v->stream, n, src, U, P, job));
-    stats->rounds = rounds;
-    stats->n_brute = U;
+        return GSX_OK;
+    };
+    const auto brute = [&](uint32_t U) -> gsx_status {
+        HIPCHK(launch_knn_brute(v->stream, n, src, U, s.P, job));
+        return GSX_OK;
+    };
+    if ((st = radius_search<gsx_status>(s, s.P, grid, round, brute))) return st;
+    stats->first_radius = s.first_radius;
+    stats->rounds = s.rounds;
+    stats->n_brute = s.n_brute;
     HIPCHK(launch_knn_stats(v->stream, n, job));
     return GSX_OK;
 }

@@ -4,13 +4,13 @@
 // solve align_math.h's, the workspace the model operations' (v->extract_ws): the grid's regions for the targets, then [the words, 128
 // B | the align sums, 256 B | the partials, 128 B a workgroup of the source | the box, its partials and histogram | the select's
 // partials | the source's participant and transfer bits | index and d2, 4 B a source Gaussian each | two lists, 16 B a source
-// Gaussian each].  The host looks at the device once for the box and the first list's length and once a round for the unresolved
-// count.
+// Gaussian each].  The host looks at the device once for the box (participants_box) and the first list's length and once a round
+// for the unresolved count; the rounds' schedule is radius_search.h's.
 #include "gsx_state.h"
 #include "align_math.h"
-#include "bounds_math.h"
 #include "nearest_math.h"
 #include "neighbors_host.h"
+#include "radius_search.h"
 
 using namespace gsx;
 
@@ -28,9 +28,7 @@ size_t nearest_ws(char* ws, uint64_t n, uint64_t n_dst, uint32_t bits, NearestJo
     job->words = c.take<uint32_t>(4 * kNearestWords);
     job->align = c.take<double>(8 * kNearestAlignDoubles);
     job->partials = c.take<double>(8 * kNearestPartialDoubles * groups);
-    job->box = c.take<gsx_model_bounds_t>(sizeof(gsx_model_bounds_t));
-    job->box_partials = c.take<BoundsPartial>(sizeof(BoundsPartial) * kBoundsMaxGroups);
-    job->box_hist = c.take<uint32_t>(4 * 3u * kBoundsBins);
+    job->box = take_box(c);
     job->sel.partials = c.take<uint32_t>(4 * kSelectPartialWords * groups);
     job->participants = c.take<uint32_t>(4 * bit_words);
     job->transfer = c.take<uint32_t>(4 * bit_words);
@@ -82,10 +80,8 @@ gsx_status nearest_models(gsx_viewer* v, const char* fn, const char* src_key, co
 // The workspace (grown if need be: the only step that can fail for memory) and the job of a call; the source has n > 0 Gaussians.
 gsx_status nearest_job(gsx_viewer* v, const Model* src, const Model* dst, const gsx_nearest_desc& d, const float xform[12], NearestJob* job) {
     const uint32_t bits = d.grid_bits ? d.grid_bits : nb_auto_bits(dst->n);
-    NearestJob sized{};
-    HIPCHK(v->extract_ws.ensure(nearest_ws(nullptr, src->n, dst->n, bits, &sized)));
-    *job = NearestJob{};
-    nearest_ws(v->extract_ws.as<char>(), src->n, dst->n, bits, job);
+    const gsx_status st = place_job(v, job, [&](char* ws, NearestJob* j) { return nearest_ws(ws, src->n, dst->n, bits, j); });
+    if (st) return st;
     job->nb.bits = bits;
     job->nb.max_count = kNbMaxCount;
     for (int k = 0; k < 12; ++k) job->xform[k] = xform[k];
@@ -99,71 +95,45 @@ gsx_status nearest_job(gsx_viewer* v, const Model* src, const Model* dst, const 
 // the stream reaches its end, and so are the source's participant bits.
 gsx_status run_nearest(gsx_viewer* v, const Model* src, const Model* dst, const ModelFilter& fs, const ModelFilter& fd, NearestJob& job,
                        const gsx_nearest_desc& d, gsx_nearest_stats_t* stats) {
-    const uint64_t n = src->n, n_dst = dst->n;
+    const uint64_t n = src->n;
     HIPCHK(gsx::op::MemsetAsync(job.words, 0, 4 * kNearestWords, v->stream));
     HIPCHK(gsx::op::MemsetAsync(job.align, 0, 8 * kNearestAlignDoubles, v->stream));
-    // the targets' count, box and trimmed box: gsx_model_bounds' passes, whose participants are the same
-    const uint64_t looked_at = fd.select_none ? 0 : n_dst;  // (selected Gaussians of a model without a selection: none)
-    if (looked_at) HIPCHK(launch_bounds_reduce(v->stream, dst->pc.as<float4>(), n_dst, fd, job.box_partials));
-    HIPCHK(launch_bounds_finish(v->stream, job.box_partials, looked_at ? bounds_reduce_groups(n_dst) : 0u, looked_at != 0, job.box, job.box_hist));
-    if (looked_at) HIPCHK(launch_bounds_trim(v->stream, dst->pc.as<float4>(), n_dst, fd, kKnnTrimPermille, job.box, job.box_hist));
-    HIPCHK(launch_nearest_map(v->stream, n, fs, extract_planes(src, false).pc, job));
-    HIPCHK(gsx::op::StreamSynchronize(v->stream));
-    gsx_model_bounds_t box;
-    HIPCHK(gsx::op::Memcpy(&box, job.box, sizeof box, hipMemcpyDeviceToHost));
+    RadiusSearch s{{}, {}, 0u, d.radius_hint, 1u, d.max_distance, d.max_rounds};  // (the participants are the targets)
+    gsx_status st = participants_box(v, dst, fd, job.box, [&] { return launch_nearest_map(v->stream, n, fs, extract_planes(src, false).pc, job); }, &s,
+                                     &stats->targets_nonfinite);
+    if (st) return st;
     uint32_t head[4];
     HIPCHK(gsx::op::Memcpy(head, job.words, sizeof head, hipMemcpyDeviceToHost));
-    const uint32_t P = (uint32_t)box.count, Q = head[kNearestList + 1u];
+    const uint32_t Q = head[kNearestList + 1u];
     stats->count = Q;
     stats->n_nonfinite = head[kNearestNonfinite];
-    stats->targets = box.count;
-    stats->targets_nonfinite = box.n_nonfinite;
-    uint32_t U = P ? Q : 0u, rounds = 0;
-    if (U) {
-        double ext[3], trimmed[3];
-        for (int a = 0; a < 3; ++a) {
-            ext[a] = (double)box.max[a] - (double)box.min[a];
-            trimmed[a] = (double)box.trim_max[a] - (double)box.trim_min[a];
-        }
-        const float floor_ = knn_radius_floor(ext);
-        float radius = nearest_round_radius(knn_clamp_radius(d.radius_hint > 0.0f ? d.radius_hint : knn_first_radius(trimmed, P, 1u), floor_), floor_, d.max_distance);
-        stats->first_radius = radius;
-        const auto grid = [&](float r) {  // the targets' table and records at radius r
-            const NbGrid g = nb_grid(r);
-            job.nb.r2 = g.r2;
-            job.nb.inv_h = g.inv_h;
-            job.final_round = nearest_final(g.r2, job.cap2) ? 1u : 0u;
-            return enqueue_grid(v, dst, fd, job.nb);
-        };
-        gsx_status st = grid(radius);  // (the fallback reads its records)
-        if (st) return st;
-        const uint4* list = job.list[1];
-        const auto next_radius = [&] {  // the radius of the round to come, 0 where the radius cannot grow
-            if (!rounds) return radius;
-            const float next = knn_next_radius(radius);
-            return next == 0.0f ? 0.0f : nearest_round_radius(next, floor_, d.max_distance);
-        };
-        while (U && !knn_go_brute(U, P, rounds, d.max_rounds, next_radius(), knn_coarse(next_radius(), trimmed))) {
-            if (rounds) {
-                radius = next_radius();
-                if ((st = grid(radius))) return st;
-            }
-            const uint32_t to = rounds & 1u;
-            HIPCHK(gsx::op::MemsetAsync(job.words + kNearestList + to, 0, 4, v->stream));
-            HIPCHK(launch_nearest_query(v->stream, n, list, U, to, job));
-            rounds += 1u;
-            if (job.final_round) {  // what it did not find has no target within max_distance
-                U = 0;
-                break;
-            }
-            HIPCHK(gsx::op::StreamSynchronize(v->stream));  // the one look a round: how many are left
-            HIPCHK(gsx::op::Memcpy(&U, job.words + kNearestList + to, 4, hipMemcpyDeviceToHost));
-            list = job.list[to];
-        }
-        if (U) HIPCHK(launch_nearest_brute(v->stream, n, list, U, P, job));
+    stats->targets = s.P;
+    const uint4* list = job.list[1];  // the first list: k_nearest_map's
+    // the targets' table and records at radius r (the fallback reads its records)
+    const auto grid = [&](float r, bool final_round) {
+        job.final_round = final_round ? 1u : 0u;
+        return enqueue_grid_at(v, dst, fd, job.nb, r);
+    };
+    const auto round = [&](uint32_t i, uint32_t U, bool final_round, uint32_t* left) -> gsx_status {
+        const uint32_t to = i & 1u;
+        HIPCHK(gsx::op::MemsetAsync(job.words + kNearestList + to, 0, 4, v->stream));
+        HIPCHK(launch_nearest_query(v->stream, n, list, U, to, job));
+        if (final_round) return GSX_OK;  // what it did not find has no target within max_distance: nothing to wait for
+        HIPCHK(gsx::op::StreamSynchronize(v->stream));  // the one look a round: how many are left
+        HIPCHK(gsx::op::Memcpy(left, job.words + kNearestList + to, 4, hipMemcpyDeviceToHost));
+        list = job.list[to];
+        return GSX_OK;
+    };
+    const auto brute = [&](uint32_t U) -> gsx_status {
+        HIPCHK(launch_nearest_brute(v->stream, n, list, U, s.P, job));
+        return GSX_OK;
+    };
+    if (s.P && Q) {  // (without queries or targets there is no search, and first_radius stays 0)
+        if ((st = radius_search<gsx_status>(s, Q, grid, round, brute))) return st;
+        stats->first_radius = s.first_radius;
     }
-    stats->rounds = rounds;
-    stats->n_brute = U;
+    stats->rounds = s.rounds;
+    stats->n_brute = s.n_brute;
     HIPCHK(launch_nearest_stats(v->stream, n, job));
     return GSX_OK;
 }

@@ -15,10 +15,8 @@ static_assert(GSX_NEIGHBOR_MAX_COUNT == kNbMaxCount, "neighbors_math.h restates 
 // The workspace (grown if need be: the only step that can fail for memory) and the job of a call; n > 0.
 gsx_status neighbor_job(gsx_viewer* v, const Model* m, float radius, uint32_t max_count, uint32_t grid_bits, NeighborJob* job) {
     const uint32_t bits = grid_bits ? grid_bits : nb_auto_bits(m->n);
-    NeighborJob sized{};
-    HIPCHK(v->extract_ws.ensure(neighbor_ws(nullptr, m->n, bits, &sized)));
-    *job = NeighborJob{};
-    neighbor_ws(v->extract_ws.as<char>(), m->n, bits, job);
+    const gsx_status st = place_job(v, job, [&](char* ws, NeighborJob* j) { return neighbor_ws(ws, m->n, bits, j); });
+    if (st) return st;
     const NbGrid g = nb_grid(radius);
     job->r2 = g.r2;
     job->inv_h = g.inv_h;

@@ -1159,6 +1159,12 @@ enum : uint32_t {
     kKnnList = 0, kKnnScored = 10, kKnnScoreMin = 11, kKnnScoreMax = 12,
     kKnnThreshold = 13, kKnnHit = 14, kKnnSelected = 15, kKnnSum = 16, kKnnMean = 18, kKnnSs = 20, kKnnStd = 22, kKnnWords = 32
 };
+// the workspace of launch_bounds_* where a search takes its radii from the participants' box (neighbors_host.h: participants_box)
+struct BoxWs {
+    gsx_model_bounds_t* box;
+    BoundsPartial* partials;
+    uint32_t* hist;
+};
 constexpr uint32_t kKnnPartialWords = 8;  // 32 B a workgroup: count | min | max | - | the double sum
 struct KnnJob {
     NeighborJob nb;           // the grid of the round; nb.records holds every participant after any round's scatter
@@ -1170,9 +1176,7 @@ struct KnnJob {
     float* scores;            // n floats, filled with +inf before the search
     float* rows;              // n * k floats, filled with +inf, or nullptr: the rows are not wanted
     uint4* list[2];           // n records each: the unresolved entries of a round (x, y, z bits, original index), in any order
-    gsx_model_bounds_t* box;  // the participants' count, box and trimmed box (launch_bounds_*), with its partials and histogram
-    BoundsPartial* box_partials;
-    uint32_t* box_hist;
+    BoxWs box;                // the participants' count, box and trimmed box
 };
 hipError_t launch_knn_fill(hipStream_t s, uint64_t n, const KnnJob& job);                                           // scores, rows = +inf
 // One grid round: the `count` entries of src (the grid's records, or a list) are answered or appended to list[to] (words[to] zeroed by the caller).
@@ -1213,9 +1217,7 @@ struct NearestJob {
     uint32_t* out_index;      // n words, GSX_NEAREST_NONE before the search
     float* out_d2;            // n floats, +inf before the search
     uint4* list[2];           // n entries each: (q.x, q.y, q.z bits, source index), in any order
-    gsx_model_bounds_t* box;  // the targets' count, box and trimmed box (launch_bounds_*), with its partials and histogram
-    BoundsPartial* box_partials;
-    uint32_t* box_hist;
+    BoxWs box;                // the targets' count, box and trimmed box
     SelectionWrite sel;       // select: the SOURCE's selection; its partials are extract_groups(n) x kSelectPartialWords words
 };
 // participants, out_index / out_d2 = none, and the first list, list[1] (words[0..2] zeroed by the caller); n > 0

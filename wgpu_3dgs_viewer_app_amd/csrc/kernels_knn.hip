@@ -1,7 +1,8 @@
 // kernels_knn.hip — the nearest neighbours for gfx950 (spec/RENDER_SPEC.md §20, "Model nearest neighbours"): gsx_model_knn and
 // gsx_model_select_knn.  The grid is section 18's (kernels_neighbors.hip builds it, once a round); the rules are knn_math.h's.
-// The participants' count, box and trimmed box, from which the host derives the search radii, come from the bounds kernels
-// (kernels_bounds.hip), whose participants are the same: the filter and three finite coordinates.
+// The participants' count, box and trimmed box, from which the host derives the search radii (radius_search.h, called by
+// gsx_api_knn.cpp), come from the bounds kernels (kernels_bounds.hip), whose participants are the same: the filter and three finite
+// coordinates.
 //   k_knn_fill      scores[] and rows[] = +inf: what a Gaussian that does not participate keeps;
 //   k_knn_query<K>  one lane per entry of `src` (round 1: the grid's records in bucket order, so a wave's lanes share cells; later
 //                   rounds: the unresolved list): the 27 cells around the entry's own, walked as k_nb_query walks them.  A record
@@ -9,7 +10,7 @@
 //                   best live in K registers (knn_insert: an unrolled compare-exchange chain, no runtime index).  The row is proven
 //                   iff its k-th smallest is <= r2 (knn_math.h): a proven lane stores its score, and its row if rows are wanted; one
 //                   that is not proven drops what it has and appends its 16-byte entry to the next list: one returning add a wave
-//                   (ballot, popcount, lane 0 adds, shuffle).  The list's order differs from call to call; no result depends on it;
+//                   (wave_reduce.h: wave_append).  The list's order differs from call to call; no result depends on it;
 //   k_knn_brute<K>  the exact fallback, one workgroup per list entry: the lanes stride over all records, each keeps its K best; the
 //                   256 lists go to LDS and are merged in k steps: every lane offers the head of its list, a wave and workgroup
 //                   minimum of (value bits, lane) picks one, the winner advances its head.  Equal values of different lanes all
@@ -72,8 +73,7 @@ __device__ inline void knn_store_row(uint64_t n, const KnnJob& job, uint32_t ind
 template <int K>
 __global__ __launch_bounds__(256) void k_knn_query(uint64_t n, const uint4* __restrict__ src, uint32_t count, uint4* __restrict__ next, uint32_t* __restrict__ next_count,
                                                    KnnJob job) {
-    const uint32_t t = threadIdx.x, lane = t & 63u;
-    const uint32_t p = blockIdx.x * 256u + t;
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     bool unresolved = false;
     uint4 self = make_uint4(0u, 0u, 0u, 0u);
     if (p < count) {
@@ -97,17 +97,7 @@ __global__ __launch_bounds__(256) void k_knn_query(uint64_t n, const uint4* __re
         else
             unresolved = true;
     }
-    // the wave's unresolved entries draw consecutive slots of the next list with one returning add (every lane arrives here)
-    const unsigned long long pending = __ballot(unresolved);
-    if (pending) {
-        uint32_t slot0 = 0;
-        if (lane == 0u) slot0 = atomicAdd(next_count, (uint32_t)__popcll(pending));
-        slot0 = __shfl(slot0, 0, 64);
-        if (unresolved) {
-            const uint32_t slot = slot0 + (uint32_t)__popcll(pending & ((1ull << lane) - 1ull));
-            if (slot < n) next[slot] = self;  // (always: at most `count` <= n entries are appended)
-        }
-    }
+    wave_append(unresolved, self, next, next_count, n);  // (every lane arrives here; at most `count` <= n entries are appended)
 }
 
 template <int K>

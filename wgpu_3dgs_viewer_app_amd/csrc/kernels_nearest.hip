@@ -1,11 +1,12 @@
 // kernels_nearest.hip — the nearest search across models for gfx950 (spec/RENDER_SPEC.md §23, "Model nearest (across models)"):
 // gsx_model_nearest, gsx_model_select_nearest and gsx_model_align_step.  The grid is section 18's, built over the TARGETS
-// (kernels_neighbors.hip, once a round); the rules are nearest_math.h's and knn_math.h's.  The queries are the SOURCE's Gaussians,
+// (kernels_neighbors.hip, once a round); the rules are nearest_math.h's and knn_math.h's, the rounds' schedule radius_search.h's (called
+// by gsx_api_nearest.cpp).  The queries are the SOURCE's Gaussians,
 // mapped by a 3x4 matrix: they are no members of the grid and may lie outside its box (neighbors_math.h: nb_cell_signed).  "n" is
 // the source's length everywhere.
 //   k_nearest_map       index order over the source: the participant bits (the filter, a finite stored position, a finite mapped
 //                       position q), out_index / out_d2 = none / +inf, and one 16-byte entry (q, source index) a participant,
-//                       appended to the first list with one returning add a wave; the list's order is free;
+//                       appended to the first list with one returning add a wave (wave_reduce.h: wave_append); the list's order is free;
 //   k_nearest_query     one lane per entry, k_knn_query's shape with ONE best (d2, index) pair in registers: the 27 cells around the
 //                       query's signed cell; a record is a candidate if d2 <= min(r2, cap2) and its own cell IS the visited cell, and
 //                       replaces the best if it has the smaller d2 or the same d2 and the smaller index.  There is no early end at
@@ -66,20 +67,6 @@ __device__ inline void nearest_map(const NearestJob& job, const uint4& e, float&
     qy = nearest_map_row(job.xform + 4, x, y, z);
     qz = nearest_map_row(job.xform + 8, x, y, z);
 }
-// The wave's lanes with `on` draw consecutive slots of a list with one returning add; called by all 64 lanes.
-__device__ inline void nearest_append(bool on, const uint4& entry, uint4* __restrict__ list, uint32_t* __restrict__ list_count, uint64_t capacity) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long pending = __ballot(on);
-    if (pending) {
-        uint32_t slot0 = 0;
-        if (lane == 0u) slot0 = atomicAdd(list_count, (uint32_t)__popcll(pending));
-        slot0 = __shfl(slot0, 0, 64);
-        if (on) {
-            const uint32_t slot = slot0 + (uint32_t)__popcll(pending & ((1ull << lane) - 1ull));
-            if (slot < capacity) list[slot] = entry;  // (always: a list takes at most n entries)
-        }
-    }
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_nearest_map(uint64_t n, ModelFilter f, const uint4* __restrict__ pc, NearestJob job) {
@@ -107,7 +94,7 @@ __global__ __launch_bounds__(256) void k_nearest_map(uint64_t n, ModelFilter f, 
             job.out_d2[i] = kNearestInf;
             if ((lane & 31u) == 0u) job.participants[i >> 5] = (uint32_t)(part64 >> lane);  // (bits at and above n are clear)
         }
-        nearest_append(part, entry, job.list[1], job.words + kNearestList + 1u, n);
+        wave_append(part, entry, job.list[1], job.words + kNearestList + 1u, n);
     }
     nonfinite = wave_sum(nonfinite);
     if (lane == 0u && nonfinite) atomicAdd(job.words + kNearestNonfinite, nonfinite);  // (an integer sum: the same in any order)
@@ -146,7 +133,7 @@ __global__ __launch_bounds__(256) void k_nearest_query(uint64_t n, const uint4* 
             unresolved = job.final_round == 0u;
         }
     }
-    nearest_append(unresolved, self, next, next_count, n);  // (every lane arrives here)
+    wave_append(unresolved, self, next, next_count, n);  // (every lane arrives here)
 }
 
 __global__ __launch_bounds__(256) void k_nearest_brute(uint64_t n, const uint4* __restrict__ src, uint32_t total, NearestJob job) {

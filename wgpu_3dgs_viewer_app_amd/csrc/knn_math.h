@@ -1,5 +1,6 @@
 // knn_math.h — the rules of the nearest-neighbour search (spec/RENDER_SPEC.md §20, "Model nearest neighbours"), written once: the
-// kernels of kernels_knn.hip, the host side of gsx_api_knn.cpp and the host restatement of tests/knn_driver.cpp all include it, so
+// kernels of kernels_knn.hip, the host side of gsx_api_knn.cpp, radius_search.h (the order in which the radii and the fallback rule
+// are applied: the library's loop, which tests/knn_driver.cpp runs too) and the driver's host version of the work all include it, so
 // they cannot drift.  It holds the insertion chain that keeps a lane's K best, the rule that proves a row, the two scores, the
 // outlier threshold, the search radii (floor, first estimate, growth) and the rule that sends the unresolved to the exact fallback.
 // The distance, the cell and the grid are neighbors_math.h's; nothing of them is restated here.

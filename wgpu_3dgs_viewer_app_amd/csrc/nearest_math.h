@@ -1,6 +1,7 @@
 // nearest_math.h — the rules of the nearest search across models (spec/RENDER_SPEC.md §23, "Model nearest (across models)"), written
-// once: the kernels of kernels_nearest.hip, the host side of gsx_api_nearest.cpp and the host restatement of tests/nearest_driver.cpp
-// all include it, so they cannot drift.  It holds the mapping of a query into the targets' space, the order among candidates (d2,
+// once: the kernels of kernels_nearest.hip, the host side of gsx_api_nearest.cpp, radius_search.h (the order in which the cap, the
+// round's radius and the final round are applied: the library's loop, which tests/nearest_driver.cpp runs too) and the driver's host
+// version of the work all include it, so they cannot drift.  It holds the mapping of a query into the targets' space, the order among candidates (d2,
 // then the smaller target index), the cap that max_distance puts on d2, the radius of a round under that cap, and the matrix between
 // two model transforms.  The distance, the cells (nb_cell_signed) and the grid are neighbors_math.h's, the radii and the rule that
 // goes to the exact fallback knn_math.h's, the unit quaternion merge_math.h's; nothing of them is restated here.

@@ -1,6 +1,6 @@
-// wave_reduce.h — the reductions of the model operations' kernels (kernels_property / _neighbors / _clusters / _knn / _decimate.hip),
-// written once: a value over the 64 lanes of a wave, and the four waves' values over a workgroup of 256.  Device code only.  The
-// frame pipeline's kernels keep their own, tuned per kernel.
+// wave_reduce.h — the reductions of the model operations' kernels (kernels_property / _neighbors / _clusters / _knn / _nearest /
+// _decimate.hip), written once: a value over the 64 lanes of a wave, the four waves' values over a workgroup of 256, and the wave's
+// append to a list (kernels_knn / _nearest.hip).  Device code only.  The frame pipeline's kernels keep their own, tuned per kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,6 +23,23 @@ __device__ inline uint32_t wave_min(uint32_t x) { return wave_fold(x, [](uint32_
 __device__ inline uint32_t wave_max(uint32_t x) { return wave_fold(x, [](uint32_t a, uint32_t b) { return b > a ? b : a; }); }
 __device__ inline uint64_t wave_min(uint64_t x) { return wave_fold(x, [](uint64_t a, uint64_t b) { return b < a ? b : a; }); }
 __device__ inline uint64_t wave_max(uint64_t x) { return wave_fold(x, [](uint64_t a, uint64_t b) { return b > a ? b : a; }); }
+
+// The wave's lanes with `on` draw consecutive slots of a list with one returning add (ballot, popcount, lane 0 adds, shuffle) and
+// store their 16-byte entry there; a slot at or beyond `capacity` is not written.  The list's order differs from call to call.  Called
+// by all 64 lanes.
+__device__ inline void wave_append(bool on, const uint4& entry, uint4* __restrict__ list, uint32_t* __restrict__ list_count, uint64_t capacity) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long pending = __ballot(on);
+    if (pending) {
+        uint32_t slot0 = 0;
+        if (lane == 0u) slot0 = atomicAdd(list_count, (uint32_t)__popcll(pending));
+        slot0 = __shfl(slot0, 0, 64);
+        if (on) {
+            const uint32_t slot = slot0 + (uint32_t)__popcll(pending & ((1ull << lane) - 1ull));
+            if (slot < capacity) list[slot] = entry;  // (always: a list takes at most as many entries as it has room for)
+        }
+    }
+}
 
 // Over the workgroup of 256: `mine` is already reduced over the wave.  Lane 0 of the waves 1..3 stores it to LDS (wave 0's stays in
 // thread 0's registers), one barrier, and thread 0 folds the waves 0..3 in wave order: merge(merge(merge(wave 0, wave 1), wave 2),
