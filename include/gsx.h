@@ -982,6 +982,55 @@ gsx_status gsx_model_select_visibility(gsx_viewer* v, const char* key, const gsx
                                        uint64_t* out_selected);
 gsx_status gsx_model_visibility_reset(gsx_viewer* v, const char* key); /* frees the planes */
 
+/* ---- depth map: the splats' depth per pixel (spec/RENDER_SPEC.md section 25; kernels_depthmap.hip).
+ *      gsx_render_depth_map walks the models of `keys_far_to_near` in the order gsx_render_frame composites them — the LAST key
+ *      first — with the viewer's current camera, viewport, transforms and spec parameters, the mask and the edits as in a frame.
+ *      Pixel p walks each model's complete front-to-back tile list with the compositor's per-pixel sequence (support test, alpha by
+ *      display mode clamped by alpha_max / alpha_min, w = T * alpha in float32, T *= 1 - alpha, closed at T < t_epsilon; records
+ *      behind a closed pixel add nothing); T is carried from model to model.  d is a Gaussian's view depth: the float whose bits are
+ *      its depth key.  Per pixel, height * width values a plane, row-major, row 0 at the top:
+ *        transmittance  the final T: the T channel of gsx_render_frame over the same keys, bit for bit;
+ *        alpha          A = sum of w (A <- A + w), and
+ *        sum            S = sum of w * d (S <- fma(w, d, S)), both float32 in walk order; the expected depth is S / A, left to the
+ *                       caller — the library makes no division;
+ *        surface        d of the first record after whose blend T < desc.threshold (0.5: the median depth; 1.0: the first record
+ *                       that lowers T at all), +inf without such a crossing;
+ *        index, layer   that record's Gaussian index and its model's position in `keys_far_to_near`; 0xFFFFFFFF without a crossing;
+ *        ndc            only with GSX_DEPTH_MAP_NDC: clamp(P23 / surface - P22, 0, 1) in float32, 1.0 without a crossing — the
+ *                       depth test's own relation (gsx_viewer_set_depth_test) read backwards.  The flag needs the projection the
+ *                       depth test needs.  A splat lying on the surface itself may pass or fail a later test: parity in that band
+ *                       of a few ulps is not pinned, as for the depth test.
+ *      The statistics are integers and bit patterns: two calls return the same bytes in every plane and in the statistics,
+ *      whatever ran before and however many frames are in flight.  Without a crossing surface_min = +inf and surface_max = 0.
+ *      The planes are device memory of the viewer (counted by gsx_debug_device_bytes); gsx_depth_map_device_ptrs returns them.  They
+ *      stay valid until the next gsx_render_depth_map, a viewport change or gsx_viewer_destroy; `ndc` is NULL unless the last call
+ *      set the flag.  The ndc plane is tightly packed [height][width] float32 and can be handed straight to
+ *      gsx_viewer_set_depth_buffer_device(v, ndc, width, height, 4 * width).  Ordering: the call's writes are made on the viewer's
+ *      stream and are complete when it returns; a frame dealt afterwards — on the viewer or on a lane — reads behind them.
+ *      State: the call is ordered after every frame in flight, draws into scratch of its own (the viewer's framebuffer, every
+ *      lane's and the query hit buffers keep the last frame), and leaves every model named unsorted: gsx_preprocess + gsx_sort
+ *      before the next gsx_render (which refuses otherwise); gsx_render_frame needs nothing, and draws bit for bit the frame it
+ *      would have drawn without the call.
+ *      Out of scope (GSX_ERR_INVALID_ARG, by design, not forgotten): the depth test GSX_DEPTH_LESS; overlay lines or mask gizmos
+ *      set; a band (gsx_viewer_set_band) or an external framebuffer set; a sharded model or a viewer with a communicator.
+ *      Other errors: null viewer / keys / desc, n_keys == 0, a key named twice, unknown flag bits, a reserved word != 0, a threshold
+ *      that is not finite or outside [t_epsilon, 1], GSX_DEPTH_MAP_NDC with another projection, device pointers without a depth map
+ *      of this viewport: GSX_ERR_INVALID_ARG; unknown key: GSX_ERR_NOT_FOUND.  A refused call leaves the planes as they were.
+ *      gsx_depth_map_unproject (host only, float64 inside): the world-space point that the camera (view, proj: column-major, as
+ *      gsx_update_camera takes them) sees at pixel position (px, py) — pixel (i, j) has its centre at (i + 0.5, j + 0.5) — at
+ *      view depth `view_depth` (a value of the surface plane, or S / A). ---- */
+#define GSX_DEPTH_MAP_NDC 1u   /* also write the ndc plane */
+typedef struct gsx_depth_map_desc { uint32_t flags; float threshold; uint32_t reserved[2]; } gsx_depth_map_desc; /* 16 B */
+typedef struct gsx_depth_map_stats_t { uint64_t n_covered, n_crossed; float surface_min, surface_max; uint32_t models, reserved; } gsx_depth_map_stats_t; /* 32 B */
+void gsx_depth_map_desc_default(gsx_depth_map_desc* d); /* flags 0, threshold 0.5 */
+gsx_status gsx_render_depth_map(gsx_viewer* v, const char* const* keys_far_to_near, uint32_t n_keys, const gsx_depth_map_desc* desc,
+                                float* out_surface, float* out_sum, float* out_alpha, float* out_transmittance,
+                                uint32_t* out_index, uint32_t* out_layer, gsx_depth_map_stats_t* out); /* every out_* nullable, height * width */
+gsx_status gsx_depth_map_device_ptrs(gsx_viewer* v, void** surface, void** sum, void** alpha, void** transmittance,
+                                     void** index, void** layer, void** ndc, uint32_t* width, uint32_t* height); /* every out nullable */
+gsx_status gsx_depth_map_unproject(const float view[16], const float proj[16], uint32_t width, uint32_t height,
+                                   float px, float py, float view_depth, float out_world[3]);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

@@ -460,6 +460,48 @@ public:
     void set_depth_buffer_device(const float* d_ptr, UVec2 sz, uint64_t row_pitch_bytes) {
         check(gsx_viewer_set_depth_buffer_device(v_, d_ptr, sz.x, sz.y, row_pitch_bytes));
     }
+    // gsx_render_depth_map: walks the models in the order render_frame composites them (the LAST key first) with the viewer's current
+    // camera and keeps per pixel ([size.y][size.x], row 0 at the top) the surface depth — the view depth of the first record after
+    // whose blend T < threshold, +inf without one — that record's Gaussian index and layer (0xFFFFFFFF without), S = sum w * d,
+    // A = sum w and the final T (the rendered frame's, bit for bit).  Every vector is optional.  The planes stay on the device
+    // (depth_map_device_ptrs); with ndc = true an NDC depth plane is written as well, which set_depth_buffer_device takes as it is
+    // (the writes are complete when the call returns).  The framebuffer keeps the last frame; every model named needs
+    // preprocess() + sort() before the next render(); render_frame() needs nothing.
+    struct DepthMapPlanes { void *surface, *sum, *alpha, *transmittance, *index, *layer, *ndc; UVec2 size; };
+    gsx_depth_map_stats_t render_depth_map(const std::vector<std::string>& model_render_keys, float threshold = 0.5f, bool ndc = false,
+                                           std::vector<float>* surface = nullptr, std::vector<float>* sum = nullptr, std::vector<float>* alpha = nullptr,
+                                           std::vector<float>* transmittance = nullptr, std::vector<uint32_t>* index = nullptr,
+                                           std::vector<uint32_t>* layer = nullptr) {
+        std::vector<const char*> k;
+        for (const auto& s : model_render_keys) k.push_back(s.c_str());
+        const size_t npx = (size_t)size.x * size.y;
+        for (auto* f : {surface, sum, alpha, transmittance})
+            if (f) f->assign(npx, 0.0f);
+        for (auto* u : {index, layer})
+            if (u) u->assign(npx, 0xFFFFFFFFu);
+        gsx_depth_map_desc desc{};
+        gsx_depth_map_desc_default(&desc);
+        desc.flags = ndc ? GSX_DEPTH_MAP_NDC : 0u;
+        desc.threshold = threshold;
+        gsx_depth_map_stats_t out{};
+        check(gsx_render_depth_map(v_, k.data(), (uint32_t)k.size(), &desc, surface ? surface->data() : nullptr, sum ? sum->data() : nullptr,
+                                   alpha ? alpha->data() : nullptr, transmittance ? transmittance->data() : nullptr, index ? index->data() : nullptr,
+                                   layer ? layer->data() : nullptr, &out));
+        return out;
+    }
+    // gsx_depth_map_device_ptrs: the last depth map's planes on the device (ndc: nullptr unless it was asked for), valid until the
+    // next render_depth_map, a viewport change or the viewer's end
+    DepthMapPlanes depth_map_device_ptrs() {
+        DepthMapPlanes p{};
+        check(gsx_depth_map_device_ptrs(v_, &p.surface, &p.sum, &p.alpha, &p.transmittance, &p.index, &p.layer, &p.ndc, &p.size.x, &p.size.y));
+        return p;
+    }
+    // gsx_depth_map_unproject (host only): the world-space point seen at pixel position (px, py) at view depth view_depth
+    static std::array<float, 3> depth_map_unproject(const float view[16], const float proj[16], UVec2 sz, float px, float py, float view_depth) {
+        std::array<float, 3> w{};
+        check(gsx_depth_map_unproject(view, proj, sz.x, sz.y, px, py, view_depth, w.data()));
+        return w;
+    }
     // MeasurementRenderer::update_hit_pairs (src/renderer/measurement.rs:133-167): the measurement lines, drawn by the library with depth
     // write before the splats of every frame from then on (gsx.h, the overlay block); an empty vector clears them
     void update_hit_pairs(const std::vector<gsx_overlay_line>& lines) {

@@ -53,6 +53,8 @@ pub const GSX_VIS_ACCUMULATE: u32 = 1;
 pub const GSX_VIS_PEAK: u32 = 0;
 pub const GSX_VIS_WEIGHT: u32 = 1;
 pub const GSX_VIS_PIXELS: u32 = 2;
+pub const GSX_DEPTH_MAP_NDC: u32 = 1;
+pub const GSX_DEPTH_MAP_NONE: u32 = 0xFFFF_FFFF;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -296,6 +298,16 @@ pub struct gsx_visibility_select_desc { pub measure: u32, pub filter: u32, pub s
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_visibility_stats_t { pub n_visible: u64, pub n_seen: u64, pub n_pairs: u64, pub weight_fixed: u64, pub peak_max: f32, pub views: u32 }
+/// gsx_render_depth_map, 16 bytes: flags (GSX_DEPTH_MAP_NDC), the transmittance threshold of the surface (0.5: the median depth;
+/// 1.0: the first record that lowers T at all), reserved (0)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_depth_map_desc { pub flags: u32, pub threshold: f32, pub reserved: [u32; 2] }
+/// the result of gsx_render_depth_map, 32 bytes: pixels with A > 0, pixels with a crossing, the smallest and largest surface over the
+/// crossings (+inf and 0 without one), the number of models, reserved
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_depth_map_stats_t { pub n_covered: u64, pub n_crossed: u64, pub surface_min: f32, pub surface_max: f32, pub models: u32, pub reserved: u32 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }
@@ -449,6 +461,10 @@ extern "C" {
     pub fn gsx_model_visibility(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_visibility_desc, out_peak: *mut f32, out_weight: *mut f64, out_pixels: *mut u32, out_transmittance: *mut f32, out: *mut gsx_visibility_stats_t) -> gsx_status;
     pub fn gsx_model_select_visibility(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_visibility_select_desc, out_hit: *mut u64, out_selected: *mut u64) -> gsx_status;
     pub fn gsx_model_visibility_reset(v: *mut gsx_viewer, key: *const c_char) -> gsx_status;
+    pub fn gsx_depth_map_desc_default(d: *mut gsx_depth_map_desc);
+    pub fn gsx_render_depth_map(v: *mut gsx_viewer, keys_far_to_near: *const *const c_char, n_keys: u32, desc: *const gsx_depth_map_desc, out_surface: *mut f32, out_sum: *mut f32, out_alpha: *mut f32, out_transmittance: *mut f32, out_index: *mut u32, out_layer: *mut u32, out: *mut gsx_depth_map_stats_t) -> gsx_status;
+    pub fn gsx_depth_map_device_ptrs(v: *mut gsx_viewer, surface: *mut *mut c_void, sum: *mut *mut c_void, alpha: *mut *mut c_void, transmittance: *mut *mut c_void, index: *mut *mut c_void, layer: *mut *mut c_void, ndc: *mut *mut c_void, width: *mut u32, height: *mut u32) -> gsx_status;
+    pub fn gsx_depth_map_unproject(view: *const f32, proj: *const f32, width: u32, height: u32, px: f32, py: f32, view_depth: f32, out_world: *mut f32) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

@@ -457,6 +457,44 @@ impl<G: GaussianPod> MultiModelViewer<G> {
         }
         check(unsafe { sys::gsx_viewer_upload_depth_buffer(self.handle.0, depth.as_ptr(), size.0, size.1) })
     }
+    /// `gsx_render_depth_map`: walks the models in the order a frame composites them (the LAST key first) with the viewer's current
+    /// camera and keeps per pixel (`[height][width]`, row 0 at the top) the surface depth — the view depth of the first record after
+    /// whose blend `T < threshold`, `+inf` without one — that record's Gaussian index and layer (`GSX_DEPTH_MAP_NONE` without),
+    /// `S = sum w * d`, `A = sum w` and the final `T`.  `rows`: download the planes (surface, sum, alpha, transmittance, index,
+    /// layer), otherwise they stay on the device alone (`depth_map_device_ptrs`).  With `ndc` an NDC depth plane is written as well,
+    /// which `gsx_viewer_set_depth_buffer_device` takes as it is.
+    #[allow(clippy::type_complexity)]
+    pub fn render_depth_map(&mut self, model_render_keys: &[String], threshold: f32, ndc: bool, rows: bool, size: (u32, u32))
+        -> Result<([Vec<f32>; 4], [Vec<u32>; 2], sys::gsx_depth_map_stats_t), Error> {
+        let keys: Vec<CString> = model_render_keys.iter().map(|k| CString::new(k.as_str()).unwrap()).collect();
+        let ptrs: Vec<*const std::os::raw::c_char> = keys.iter().map(|k| k.as_ptr()).collect();
+        let n = if rows { size.0 as usize * size.1 as usize } else { 0 };
+        let mut f: [Vec<f32>; 4] = [vec![0f32; n], vec![0f32; n], vec![0f32; n], vec![0f32; n]];
+        let mut u: [Vec<u32>; 2] = [vec![sys::GSX_DEPTH_MAP_NONE; n], vec![sys::GSX_DEPTH_MAP_NONE; n]];
+        let desc = sys::gsx_depth_map_desc { flags: if ndc { sys::GSX_DEPTH_MAP_NDC } else { 0 }, threshold, reserved: [0; 2] };
+        let mut out = sys::gsx_depth_map_stats_t::default();
+        let fp = |v: &mut Vec<f32>| if rows { v.as_mut_ptr() } else { std::ptr::null_mut() };
+        let (p0, p1, p2, p3) = (fp(&mut f[0]), fp(&mut f[1]), fp(&mut f[2]), fp(&mut f[3]));
+        let up = |v: &mut Vec<u32>| if rows { v.as_mut_ptr() } else { std::ptr::null_mut() };
+        let (q0, q1) = (up(&mut u[0]), up(&mut u[1]));
+        check(unsafe { sys::gsx_render_depth_map(self.handle.0, ptrs.as_ptr(), ptrs.len() as u32, &desc, p0, p1, p2, p3, q0, q1, &mut out) })?;
+        Ok((f, u, out))
+    }
+    /// `gsx_depth_map_device_ptrs`: the last depth map's planes on the device — surface, sum, alpha, transmittance, index, layer, ndc
+    /// (null unless it was asked for) — and its size; valid until the next `render_depth_map`, a viewport change or the viewer's end.
+    pub fn depth_map_device_ptrs(&self) -> Result<([*mut std::os::raw::c_void; 7], (u32, u32)), Error> {
+        let mut p = [std::ptr::null_mut(); 7];
+        let (mut w, mut h) = (0u32, 0u32);
+        let q = p.as_mut_ptr();
+        check(unsafe { sys::gsx_depth_map_device_ptrs(self.handle.0, q, q.add(1), q.add(2), q.add(3), q.add(4), q.add(5), q.add(6), &mut w, &mut h) })?;
+        Ok((p, (w, h)))
+    }
+    /// `gsx_depth_map_unproject` (host only): the world-space point seen at pixel position `(px, py)` at view depth `view_depth`.
+    pub fn depth_map_unproject(view: &[f32; 16], proj: &[f32; 16], size: (u32, u32), px: f32, py: f32, view_depth: f32) -> Result<[f32; 3], Error> {
+        let mut w = [0f32; 3];
+        check(unsafe { sys::gsx_depth_map_unproject(view.as_ptr(), proj.as_ptr(), size.0, size.1, px, py, view_depth, w.as_mut_ptr()) })?;
+        Ok(w)
+    }
     /// `MeasurementRenderer::update_hit_pairs(&device, &hit_pairs, &camera)` (src/renderer/measurement.rs:133-167): the measurement
     /// lines, drawn by the library with depth write before the splats of every frame from then on (`gsx.h`, the overlay block) — no
     /// depth attachment has to be handed over for them.  An empty slice clears them.

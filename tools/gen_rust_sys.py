@@ -102,6 +102,8 @@ pub const GSX_VIS_ACCUMULATE: u32 = 1;
 pub const GSX_VIS_PEAK: u32 = 0;
 pub const GSX_VIS_WEIGHT: u32 = 1;
 pub const GSX_VIS_PIXELS: u32 = 2;
+pub const GSX_DEPTH_MAP_NDC: u32 = 1;
+pub const GSX_DEPTH_MAP_NONE: u32 = 0xFFFF_FFFF;
 
 pub type gsx_status = i32;
 pub const GSX_OK: gsx_status = 0;
@@ -345,6 +347,16 @@ pub struct gsx_visibility_select_desc { pub measure: u32, pub filter: u32, pub s
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_visibility_stats_t { pub n_visible: u64, pub n_seen: u64, pub n_pairs: u64, pub weight_fixed: u64, pub peak_max: f32, pub views: u32 }
+/// gsx_render_depth_map, 16 bytes: flags (GSX_DEPTH_MAP_NDC), the transmittance threshold of the surface (0.5: the median depth;
+/// 1.0: the first record that lowers T at all), reserved (0)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_depth_map_desc { pub flags: u32, pub threshold: f32, pub reserved: [u32; 2] }
+/// the result of gsx_render_depth_map, 32 bytes: pixels with A > 0, pixels with a crossing, the smallest and largest surface over the
+/// crossings (+inf and 0 without one), the number of models, reserved
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_depth_map_stats_t { pub n_covered: u64, pub n_crossed: u64, pub surface_min: f32, pub surface_max: f32, pub models: u32, pub reserved: u32 }
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }

@@ -60,6 +60,7 @@ EXPORTS = (
     "gsx_decimate_desc_default", "gsx_model_decimate", "gsx_model_decimate_edge",
     "gsx_visibility_desc_default", "gsx_visibility_select_desc_default", "gsx_model_visibility", "gsx_model_select_visibility",
     "gsx_model_visibility_reset",
+    "gsx_depth_map_desc_default", "gsx_render_depth_map", "gsx_depth_map_device_ptrs", "gsx_depth_map_unproject",
 )
 
 
@@ -305,6 +306,25 @@ class VisibilityStats(C.Structure):
     Gaussian) pairs blended in this view and the sum of their 2^-24 fixed-point weights, the largest resident peak, the views folded."""
     _fields_ = [("n_visible", C.c_uint64), ("n_seen", C.c_uint64), ("n_pairs", C.c_uint64), ("weight_fixed", C.c_uint64),
                 ("peak_max", C.c_float), ("views", C.c_uint32)]
+
+
+#: ``gsx_depth_map_desc.flags``: also write the ndc plane (what ``gsx_viewer_set_depth_buffer_device`` takes)
+GSX_DEPTH_MAP_NDC = 1
+#: index and layer of a pixel without a crossing (its surface is ``inf``)
+GSX_DEPTH_MAP_NONE = 0xFFFFFFFF
+
+
+class DepthMapDesc(C.Structure):
+    """``gsx_depth_map_desc`` (16 bytes): flags (``GSX_DEPTH_MAP_NDC``), the transmittance threshold of the surface (0.5: the median
+    depth; 1.0: the first record that lowers T at all), reserved (0)."""
+    _fields_ = [("flags", C.c_uint32), ("threshold", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class DepthMapStats(C.Structure):
+    """``gsx_depth_map_stats_t`` (32 bytes): pixels with ``A > 0``, pixels with a crossing, the smallest and largest surface over the
+    crossings (``inf`` and 0 without one), the number of models, reserved."""
+    _fields_ = [("n_covered", C.c_uint64), ("n_crossed", C.c_uint64), ("surface_min", C.c_float), ("surface_max", C.c_float),
+                ("models", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class TransformDesc(C.Structure):
@@ -597,6 +617,12 @@ def load() -> C.CDLL:
         "gsx_model_visibility": ([vp, cp, C.POINTER(VisibilityDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(VisibilityStats)], C.c_int32),
         "gsx_model_select_visibility": ([vp, cp, C.POINTER(VisibilitySelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
         "gsx_model_visibility_reset": ([vp, cp], C.c_int32),
+        "gsx_depth_map_desc_default": ([C.POINTER(DepthMapDesc)], None),
+        "gsx_render_depth_map": ([vp, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(DepthMapDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.POINTER(DepthMapStats)], C.c_int32),
+        "gsx_depth_map_device_ptrs": ([vp] + [C.POINTER(C.c_void_p)] * 7 + [C.POINTER(C.c_uint32)] * 2, C.c_int32),
+        "gsx_depth_map_unproject": ([C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                     C.POINTER(C.c_float)], C.c_int32),
         "gsx_decimate_desc_default": ([C.POINTER(DecimateDesc)], None),
         "gsx_model_decimate": ([vp, cp, cp, C.POINTER(DecimateDesc), C.c_void_p, C.POINTER(DecimateStats)], C.c_int32),
         "gsx_model_decimate_edge": ([vp, cp, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_uint64)], C.c_int32),

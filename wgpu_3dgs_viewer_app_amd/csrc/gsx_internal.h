@@ -1312,6 +1312,27 @@ struct VisSelectJob {
 };
 hipError_t launch_vis_select(hipStream_t s, uint64_t n, const ModelFilter& f, const VisSelectJob& job);  // the selection, words[6..7]
 
+// Depth map (kernels_depthmap.hip; gsx_render_depth_map; spec section 25).  The viewer's planes, one value a pixel, row-major
+// [h_px][w_px], in one buffer behind the call's words: [0] pixels with A > 0  [1] pixels with a crossing  [2] / [3] the bits of the
+// smallest (inverted: ~bits, so that all words start as 0 and [2] is a maximum too) / largest surface over the crossings.
+enum : uint32_t { kDepthMapCovered = 0, kDepthMapCrossed = 1, kDepthMapMin = 2, kDepthMapMax = 3, kDepthMapWords = 32 };
+constexpr uint32_t kDepthMapNone = 0xFFFFFFFFu;  // index and layer of a pixel without a crossing (its surface is +inf)
+struct DepthMapPlanes {
+    float* surface;
+    float* sum;
+    float* alpha;
+    float* transmittance;
+    uint32_t* index;
+    uint32_t* layer;
+};
+// One 128-lane workgroup a tile over ONE model's complete per-tile lists (a progressive = 0 frame's ranges and list): the compositor's
+// per-pixel sequence without colour, the record's depth from the key plane.  first: the nearest model — every pixel of the planes is
+// written; otherwise the pixels continue from the planes (T, A, S, crossed or not) and a tile without entries is left alone.
+hipError_t launch_depth_tiles(hipStream_t s, const FrameConsts& f, const uint2* ranges, const uint32_t* list, const Records& rec,
+                              const DepthMapPlanes& planes, float threshold, uint32_t layer, bool first);
+// the statistics into words[0..3] (initialised before) and, with ndc != nullptr, ndc = clamp(p23 / surface - p22, 0, 1), 1 without a crossing
+hipError_t launch_depth_finish(hipStream_t s, uint64_t npx, const DepthMapPlanes& planes, float* ndc, float p22, float p23, uint32_t* words);
+
 // Compositing and resolve.
 // carry: continue from the (C, T) already in fb (later slabs / models behind); done: saturated-tile bitmap
 // (read to skip tiles when carrying, updated when a tile saturates; nullable).

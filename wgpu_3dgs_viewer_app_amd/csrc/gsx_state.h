@@ -515,6 +515,13 @@ struct gsx_viewer {
     // gsx_model_visibility (gsx_api_visibility.cpp; owner only): the framebuffer its frame is drawn into instead of `fb`, and [the
     // call's words, 128 B | the select's partials | the view's transmittance], allocated by the first call.  Nothing a frame reads
     DevBuf vis_fb, vis_ws;
+    // gsx_render_depth_map (gsx_api_depthmap.cpp; owner only; spec section 25): [the call's words, 128 B | seven planes of
+    // depth_map_w x depth_map_h: surface, sum, alpha, transmittance, index, layer, ndc], allocated by the first call; its frames are
+    // drawn into vis_fb.  depth_map_w = 0: no call has succeeded at this size.  Nothing a frame reads, unless the caller hands the
+    // ndc plane to gsx_viewer_set_depth_buffer_device
+    DevBuf depth_map;
+    uint32_t depth_map_w = 0, depth_map_h = 0;
+    bool depth_map_ndc = false;  // the last call wrote the ndc plane
     DevBuf row_stage[2];
     hipStream_t row_stream = nullptr;
     hipEvent_t row_kernel_done[2]{}, row_copy_done[2]{};

@@ -462,6 +462,39 @@ class ModelVisibility:
 
 
 @dataclasses.dataclass
+class DepthMap:
+    """What ``MultiModelViewer.render_depth_map`` returns: per pixel, ``(H, W)`` arrays (or ``None`` with ``planes=False``).
+    ``surface`` (float32): the view depth of the first record after whose blend ``T < threshold``, ``inf`` without such a crossing;
+    ``sum`` and ``alpha`` (float32): ``S = sum w * d`` and ``A = sum w`` in walk order — the expected depth is ``sum / alpha`` where
+    ``alpha > 0``; ``transmittance`` (float32): the final ``T``, the rendered frame's bit for bit; ``index`` and ``layer`` (uint32):
+    the surface record's Gaussian index and its model's position in the keys, ``_lib.GSX_DEPTH_MAP_NONE`` without a crossing;
+    ``n_covered``: pixels with ``alpha > 0``; ``n_crossed``: pixels with a crossing; ``surface_min`` / ``surface_max`` over the
+    crossings; ``models``."""
+
+    surface: np.ndarray | None
+    sum: np.ndarray | None
+    alpha: np.ndarray | None
+    transmittance: np.ndarray | None
+    index: np.ndarray | None
+    layer: np.ndarray | None
+    n_covered: int
+    n_crossed: int
+    surface_min: np.float32
+    surface_max: np.float32
+    models: int
+
+
+def depth_map_unproject(view, proj, size, px: float, py: float, view_depth: float) -> np.ndarray:
+    """``gsx_depth_map_unproject`` (host only): the world-space point the camera sees at pixel position ``(px, py)`` — pixel
+    ``(i, j)`` has its centre at ``(i + 0.5, j + 0.5)`` — at view depth ``view_depth`` (a value of ``DepthMap.surface``)."""
+    v = np.ascontiguousarray(view, np.float32).reshape(16)
+    p = np.ascontiguousarray(proj, np.float32).reshape(16)
+    out = np.empty(3, np.float32)
+    _lib.check(_lib.load().gsx_depth_map_unproject(_f32p(v), _f32p(p), int(size[0]), int(size[1]), float(px), float(py), float(view_depth), _f32p(out)))
+    return out
+
+
+@dataclasses.dataclass
 class ModelDecimate:
     """What ``MultiModelViewerModel.decimate`` and ``decimate_count`` return.  ``count``: participants (pass the filter, finite
     position); ``n_nonfinite``: passed the filter with a NaN or infinite coordinate (dropped); ``cells``: occupied cells, the new
@@ -1155,6 +1188,36 @@ class MultiModelViewer:
         keys = [k.encode() for k in model_render_keys]
         arr = (C.c_char_p * max(len(keys), 1))(*keys)
         _lib.check(self._L.gsx_render_frame(self._h, arr, len(keys)))
+
+    # -- the splats' depth per pixel (spec section 25) --
+    def render_depth_map(self, model_render_keys: Sequence[str], threshold: float = 0.5, ndc: bool = False, planes: bool = True) -> DepthMap:
+        """``gsx_render_depth_map``: walks the models in the order ``render_frame`` composites them (the last key first) with the
+        viewer's current camera and keeps per pixel the surface depth (first record after whose blend ``T < threshold``), its Gaussian
+        and model, ``sum w * d``, ``sum w`` and the final ``T``.  The planes stay on the device (``depth_map_device_ptrs``); with
+        ``ndc=True`` an NDC depth plane is written as well, which ``set_depth_buffer_device`` takes as it is.  The framebuffer keeps
+        the last frame; the next ``render_frame`` is the frame it would have been.  ``planes=False`` downloads nothing."""
+        keys = [k.encode() for k in model_render_keys]
+        arr = (C.c_char_p * max(len(keys), 1))(*keys)
+        desc = _lib.DepthMapDesc(_lib.GSX_DEPTH_MAP_NDC if ndc else 0, float(threshold))
+        w, h = self.size
+        f32 = [np.empty((h, w), np.float32) if planes else None for _ in range(4)]
+        u32 = [np.empty((h, w), np.uint32) if planes else None for _ in range(2)]
+        out = _lib.DepthMapStats()
+        _lib.check(self._L.gsx_render_depth_map(self._h, arr, len(keys), C.byref(desc), *[a.ctypes.data if planes else None for a in f32 + u32],
+                                                C.byref(out)))
+        return DepthMap(*f32, *u32, int(out.n_covered), int(out.n_crossed), np.float32(out.surface_min), np.float32(out.surface_max), int(out.models))
+
+    def depth_map_device_ptrs(self) -> dict:
+        """Device addresses of the last depth map's planes by name (``surface``, ``sum``, ``alpha``, ``transmittance``, ``index``,
+        ``layer``, ``ndc`` — ``None`` unless the call asked for it) and its ``size``; valid until the next ``render_depth_map``, a
+        viewport change or the viewer's end."""
+        names = ("surface", "sum", "alpha", "transmittance", "index", "layer", "ndc")
+        ptrs = [C.c_void_p() for _ in names]
+        w, h = C.c_uint32(), C.c_uint32()
+        _lib.check(self._L.gsx_depth_map_device_ptrs(self._h, *[C.byref(p) for p in ptrs], C.byref(w), C.byref(h)))
+        out = {n: p.value for n, p in zip(names, ptrs)}
+        out["size"] = (int(w.value), int(h.value))
+        return out
 
     # -- several GPUs: the index-sharded frame as one library call (include/gsx.h "multi-GPU"; no reference counterpart) --
     def comm_init_group(self, group: "CommGroup", rank: int) -> None:
