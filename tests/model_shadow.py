@@ -1,9 +1,9 @@
 """A host shadow of a viewer's models, for tests/test_model_shadow_cpu.py and tests/test_gpu_model_fuzz.py: what a long session of
 model operations (gsx_model_extract, _merge, _convert, _set_pod_kind, _apply_transform, _import_ply, _decimate, the selects by
-property, neighbour count, cluster, nearest neighbours and nearest in another model, gsx_mask_evaluate, the uploads) leaves in every
-model, kept on the host, without a GPU and without libgsx.  Per model key: the pod kind, the dequantised planes as
-gsx_model_download_pod returns them, the model transform, the mask bits, the selection bits, the stored edit records (each or none)
-and show-unedited.
+property, neighbour count, cluster, nearest neighbours, nearest in another model and visibility, gsx_mask_evaluate, the uploads,
+gsx_model_visibility and gsx_render_depth_map) leaves in every model, kept on the host, without a GPU and without libgsx.  Per model
+key: the pod kind, the dequantised planes as gsx_model_download_pod returns them, the model transform, the mask bits, the selection
+bits, the stored edit records (each or none), show-unedited and the resident visibility planes (or none).
 
 No arithmetic is stated here.  Every operation is applied with the restatements the repository already has: the kept set, its order
 and the participation set of the spatial calls are tests/extract_ref.py's `kept`; the selects are property_ref / neighbors_ref /
@@ -24,6 +24,33 @@ by the GPU test), the colour, SH and covariance a PLY round trip writes (the pos
 compressed kind, and the selection and stored edits a frame itself writes (a rectangle query's postprocess, a selection edit that
 persists: both viewers of the fuzz run those, their downloads are compared, the shadow takes them).  `verify` checks the count, the
 order and every row the shadow does know before `adopt` takes the rest.
+
+The calls that draw a model's own unspeculated frame in the middle of a session (csrc/frame_isolation.h) are three op kinds.  "visibility"
+is the CAMERA op that hides models, so they go by other names.  `vis_view` (READ_ONLY: gsx_model_visibility of `key`, `accumulate`;
+`prime` is the pose of a first view where an accumulating call finds no planes), `depth_map` (READ_ONLY: gsx_render_depth_map over the
+step's painter's order, hidden models left out, `threshold` one of THRESHOLDS, `ndc`, and `as_depth_buffer`: the ndc plane becomes the
+depth buffer of the frames that follow; `hide` and `size` hide one more model and change the viewport first) and `select_visibility`
+(SELECTS: `measure`, `op`, `flt`, the range as two quantile fractions `q_lo`, `q_hi` of the positive values or None for "never seen" —
+the draw cannot know the planes, so `lo` and `hi` are resolved when the op is applied, from the shadow's adopted planes; `view`: a model
+without planes gets a view first, `touch`: a mask, a selection and an edit change come between the view and the select).  Both calls
+refuse while the depth test, the overlay lines or the gizmos are on: with `clear` those go off first, on both viewers, through the
+ordinary state ops, and the View follows; without it the call is expected to be refused (where nothing is on, `feature` goes on first).
+A refusal must leave what is resident as it was, so something always is: where the model holds no planes, or the viewer no depth map of
+the viewport, the session puts an unrefused call of the same kind in front (`primed` in the call's record), with the features that are
+on switched off for it and on again after.  Every fourth depth map is drawn without the ndc plane.  The calls that drop a model's
+planes are steered to meet some: set_pod_kind and remove_add go to a model that holds planes, and where there is none the drawn model
+gets a view first (`view_first`), as does every other transform.  An op that takes a view or changes state first (`view_first`, and a
+select_visibility's `view` and `touch`) enqueues its frames in flight itself, after that and right in front of its own call, so that
+"two frames enqueued and not waited for" is true of the call the record names; after a `touch` a frame of both viewers comes in
+between, because a frame of `live` alone would persist a selection edit onto the selection just uploaded.
+The shadow keeps per model `vis` — None, or the planes adopted from the device after they were verified (peak float32, the weight as
+fixed-point int64, pixels uint32), `views`, where they were taken and which mask / selection / edit changes they survived — and sets
+it to None exactly where the library calls drop_visibility: a fresh upload (a new ShadowModel), set_pod_kind, remove_add and a
+gsx_model_apply_transform that is not the identity and keeps something; a model made by extract, convert, merge, decimate or a PLY
+round trip starts without.  Mask, selection, edit, show-unedited, model-transform and camera changes keep it.  After a dropping call
+on a model that held planes a select by them must be refused at once (`_planes_dropped`).  Per session `depth_map` is None or the size,
+the ndc flag and the adopted planes; a `viewport` op of another size sets it to None.  Without a device there are no planes: `vis`
+then records residency alone, which is all that conditions (i) to (m) of the fuzz (`unmet_views`) depend on.
 
 `plan(seed)` is the schedule of a fuzz seed (every op kind once in a seeded order, then random ones, camera steps in between and a
 run of them after each op that changes a model); `Session` draws each op's parameters from the shadow as it stands and applies it, to
@@ -68,8 +95,10 @@ SPATIAL_N = 2500
 
 CAMERA = ("cam_step", "cam_jump", "viewport", "visibility", "display", "model_transform")
 STATE = ("mask_eval", "sel_upload", "sel_edit", "edits_upload", "unedited", "rect_query")
-SELECTS = ("select_range", "select_neighbors", "select_clusters", "select_knn", "select_nearest")
-READ_ONLY = ("bounds", "histogram", "property_values", "neighbors", "clusters", "knn", "export", "export_ply", "decimate_edge", "nearest", "align_step")
+SELECTS = ("select_range", "select_neighbors", "select_clusters", "select_knn", "select_nearest", "select_visibility")
+READ_ONLY = ("bounds", "histogram", "property_values", "neighbors", "clusters", "knn", "export", "export_ply", "decimate_edge", "nearest", "align_step",
+             "vis_view", "depth_map")
+VIEW_CALLS = ("vis_view", "depth_map")  # they draw a model's own frame in the middle of the session (csrc/frame_isolation.h)
 MODEL_CHANGING = ("xf_translate", "xf_scale", "xf_full", "set_pod_kind", "convert", "extract", "merge", "ply_roundtrip", "remove_add", "decimate")
 FEATURES = ("depth_test", "hit_pairs", "gizmos")
 SPATIAL = ("select_neighbors", "select_clusters", "select_knn", "neighbors", "clusters", "knn", "nearest", "select_nearest", "align_step")
@@ -77,7 +106,16 @@ NEAREST_FAMILY = ("nearest", "select_nearest", "align_step")  # two keys: the qu
 OP_KINDS = CAMERA + STATE + SELECTS + READ_ONLY + MODEL_CHANGING + FEATURES
 #: the variants condition (b) asks a non-trivial hit set of, each at least once over the seed set
 SELECT_VARIANTS = ("select_range:model", "select_range:world", "select_neighbors", "select_clusters:0", "select_clusters:1", "select_clusters:2",
-                   "select_knn:range", "select_knn:std_ratio", "select_nearest:range", "select_nearest:transfer")
+                   "select_knn:range", "select_knn:std_ratio", "select_nearest:range", "select_nearest:transfer",
+                   "select_visibility:peak", "select_visibility:weight", "select_visibility:pixels")
+#: the variants whose hit sets only the device run can show: the shadow holds no visibility planes without a device to adopt them from
+DEVICE_ONLY_VARIANTS = ("select_visibility:peak", "select_visibility:weight", "select_visibility:pixels")
+VIS_MEASURES = ("peak", "weight", "pixels")  # GSX_VIS_PEAK, _WEIGHT, _PIXELS
+THRESHOLDS = (1e-4, 0.5, 1.0)  # of a depth map: t_epsilon (the crossing is the closing), the median surface, the front surface
+VIS_QUANTILES = (0.25, 0.6)  # a select_visibility's range, as fractions of the positive values of its measure
+SEEN_AT_ALL = (1e-45, float("inf"))  # the range of "every Gaussian that was seen": its hit count is n_seen
+PARTIAL_OR_LARGE = ((83, 51), (320, 240))
+DROPPERS = ("apply_transform", "set_pod_kind", "remove_add")  # the calls that drop a model's visibility planes (condition (j))
 #: condition (f): src != dst under GSX_NEAREST_MODEL_TRANSFORMS; src != dst of different pod kinds; src == dst with different filters and
 #: a query that is no target; a max_distance within which some but not all queries find a target
 NEAREST_CASES = ("nearest:model_transforms", "nearest:kinds", "nearest:same_disjoint", "nearest:max_distance")
@@ -129,6 +167,15 @@ class ShadowModel:
     sel: np.ndarray | None = None
     edits: np.ndarray | None = None
     unedited: bool = False
+    #: the resident visibility planes (Model::vis), or None: `views`, `at` (the (pose, viewport) of every view folded in), `survived`
+    #: (the mask / sel / edit changes since the first of them) and the planes adopted from the device after they were verified: peak
+    #: float32, weight as fixed-point int64 (units of 2^-24), pixels uint32.  Without a device the planes are None: residency alone.
+    vis: dict | None = None
+    vis_lost: str | None = None  # what dropped resident planes last (the library's drop_visibility), while none were taken since
+
+    def drop_vis(self, by):
+        if self.vis is not None:
+            self.vis, self.vis_lost = None, by
 
     @property
     def n(self):
@@ -235,6 +282,7 @@ class Shadow:
         m = self.models[key]
         same = tuple(kind) == m.kind
         m.kind = tuple(kind)
+        m.drop_vis("set_pod_kind")  # (the library replaces the model)
         return [np.full(m.n, True), np.full(m.n, True), np.full(m.n, same), np.full(m.n, same)]
 
     def merge(self, dst, srcs, flt=0, invert=False, drop_edits=False):
@@ -269,7 +317,8 @@ class Shadow:
         idx = m.kept(flt, invert)
         mode = T.mode(t, q, s)
         exact = _all(m.n)
-        if mode != T.IDENTITY and idx.size:
+        if mode != T.IDENTITY and idx.size:  # (gsx_api_transform.cpp returns before the drop for the identity and for an empty kept set)
+            m.drop_vis("apply_transform")
             m.planes[0][idx] = T.position(m.planes[0][idx], t, q, s, pivot)
             if mode in (T.NO_ROTATION, T.FULL):
                 exact[3][idx] = False
@@ -321,6 +370,17 @@ class Shadow:
         else:
             hit = part & (s > F(threshold)) if np.isfinite(s[part]).any() else np.zeros(m.n, bool)
         return self._select(m, hit, op)
+
+    def vis_values(self, key, measure):
+        """float64: the adopted planes as gsx_model_select_visibility compares them (the weight in units of 1, exact)"""
+        v = self.models[key].vis
+        return (v["peak"].astype(np.float64), v["weight"].astype(np.float64) / 2.0 ** 24, v["pixels"].astype(np.float64))[measure]
+
+    def select_visibility(self, key, measure, lo, hi, op=0, flt=0):
+        """gsx_model_select_visibility over the adopted planes: lo <= x <= hi among the Gaussians the filter passes"""
+        m = self.models[key]
+        x = self.vis_values(key, measure)
+        return self._select(m, m.passes(flt) & (x >= lo) & (x <= hi), op)
 
     def decimate(self, src, dst, cell, flt=0, invert=False, driver=None):
         """gsx_model_decimate.  Returns (stats, map, exact rows of dst's planes): stats = (count, n_nonfinite, cells, singletons,
@@ -396,10 +456,51 @@ class Shadow:
         return out
 
 
-def unmet(cases, decimates):
-    """conditions (e), (f) and (h) of tests/test_gpu_model_fuzz.py over a seed set, stated once: `cases` is the union of the
-    sessions' `cases`, `decimates` all their `decimates` records.  Returns what is not met."""
+def unmet_views(views, selects, refusals, depth_maps):
+    """conditions (i) to (m) of tests/test_gpu_model_fuzz.py over a seed set: the sessions' `vis_views`, `vis_selects`, `vis_refusals`
+    and `depth_maps` records, which depend on the draws alone (what is resident, not what the planes hold)"""
     out = []
+    ran = [r for r in views if not r["refused"]]
+    if not any(r["views"] >= 2 and r["other_view"] for r in ran):
+        out.append("(i) no vis_view accumulated onto planes taken at another pose or viewport")
+    if not any(r["dressed"] for r in ran):
+        out.append("(i) no vis_view of a model with a mask and stored edits")
+    if not any(r["kind_differs"] for r in ran):
+        out.append("(i) no vis_view of a model whose kind is not the seed's start kind")
+    if set(DROPPERS) - set(refusals):
+        out.append(f"(j) select_visibility was not refused for dropped planes after each of {DROPPERS}: {sorted(set(refusals))}")
+    if not any(not r["refused"] and r["survived"] >= {"mask", "sel", "edit"} for r in selects):
+        out.append("(j) no select_visibility on planes that survived a mask, a selection and an edit change")
+    walked = [r for r in depth_maps if not r["refused"]]
+    if not any(r["n_keys"] >= 3 for r in walked):
+        out.append("(k) no depth_map walked three models or more")
+    if not any(r["hidden_out"] for r in walked):
+        out.append("(k) no depth_map with a hidden model left out")
+    if not any(tuple(r["size"]) in PARTIAL_OR_LARGE for r in walked):
+        out.append("(k) no depth_map at 83 x 51 or 320 x 240")
+    out += [f"(k) no depth_map with the threshold {t}" for t in THRESHOLDS if not any(r["threshold"] == t for r in walked)]
+    if not any(r["as_depth_buffer"] and r["lanes"] > 1 and r["frames"] >= 2 for r in walked):
+        out.append("(k) no ndc plane was the depth buffer of two frames or more on a seed with several lanes")
+    if not any(r["size_changed_after"] for r in walked):
+        out.append("(k) no depth_map was followed by a viewport of another size (which drops it)")
+    if not any(not r["ndc"] for r in walked):
+        out.append("(k) no depth_map without the ndc plane")
+    for name, recs in (("vis_view", views), ("depth_map", depth_maps)):
+        if not any(r["refused"] for r in recs) or sum(not r["refused"] for r in recs) < 2:
+            out.append(f"(l) {name} was not refused once and run twice: {[r['refused'] for r in recs]}")
+        if not any(r["refused"] and r["resident"] for r in recs):
+            out.append(f"(l) no {name} was refused with {'planes' if name == 'vis_view' else 'a map of the same viewport'} resident")
+    for name, recs in (("vis_view", views), ("depth_map", depth_maps), ("select_visibility", selects)):
+        if not any(r["inflight"] and not r["refused"] for r in recs):
+            out.append(f"(m) {name} never ran with two frames enqueued and not waited for")
+    return out
+
+
+def unmet(cases, decimates, vis=None):
+    """conditions (e), (f) and (h) of tests/test_gpu_model_fuzz.py over a seed set, stated once: `cases` is the union of the
+    sessions' `cases`, `decimates` all their `decimates` records; with `vis` (dict(views, selects, refusals, depth_maps): the
+    sessions' records of the visibility and depth map calls) also (i) to (m), unmet_views.  Returns what is not met."""
+    out = [] if vis is None else unmet_views(vis["views"], vis["selects"], vis["refusals"], vis["depth_maps"])
     if not any(d["filtered"] for d in decimates):
         out.append("(e) no decimate of a source with a mask or selection filter in force")
     if not any(d["kind_differs"] for d in decimates):
@@ -465,6 +566,12 @@ class Session:
         self.driver = driver           # tests/decimate_driver.cpp, built (decimate_ref.build_driver): the merged rows of a decimate
         self.cases: set = set()        # NEAREST_CASES and "align:rotation" as the draws met them (conditions (f) and (h))
         self.decimates: list = []      # a record per decimate (condition (e))
+        self.vis_views: list = []      # a record per vis_view, per select_visibility and per depth_map (conditions (i) to (m)); the
+        self.vis_selects: list = []    # dropping calls after which a select_visibility was refused for planes that had been resident
+        self.vis_refusals: list = []
+        self.depth_maps: list = []
+        self.depth_map = None          # gsx_viewer::depth_map: None, or dict(size, ndc, planes: the device's, adopted)
+        self._ndc_buffer = None        # the depth_maps record whose ndc plane is the depth buffer now
         self.parent: dict = {}         # key -> the model it was extracted, converted or decimated from
         self.rng = np.random.default_rng(7000 + seed)
         self.lanes, self.host_verify = 1 + seed % 3, seed % 3
@@ -540,6 +647,14 @@ class Session:
             r, k = float(F(mul * memo(K.kth_distance_median, m.pos, m.part(0), k))), k + 1
         return r
 
+    def _with_planes(self, kind, key):
+        """a pod kind change and a new upload go to a model that holds visibility planes, where there is one; where there is none the
+        op's `view_first` gives the drawn model some: the call must drop them (condition (j))"""
+        have = [k for k in self.keys() if self.shadow.models[k].vis is not None]
+        if have:
+            key = have[0]
+        return key, self.shadow.models[key]
+
     def _kept_bits(self, m, flt, invert):
         out = np.zeros(m.n, bool)
         out[m.kept(flt, invert)] = True
@@ -552,18 +667,18 @@ class Session:
         return int(self.rng.integers(lo, max(lo, k // 2) + 1))
 
     def _decimate_cell(self, m, flt, invert):
-        """(cell, flt, invert) of a decimate that leaves at least MIN_N cells: the edge decimate_ref.find_edge gives for a drawn
-        target; where that leaves fewer (the count is not monotone in the edge) the median nearest-neighbour distance; where that
-        does too, the same without a filter"""
+        """(cell, flt, invert, the cells' member counts) of a decimate that leaves at least MIN_N cells: the edge
+        decimate_ref.find_edge gives for a drawn target; where that leaves fewer (the count is not monotone in the edge) the median
+        nearest-neighbour distance; where that does too, the same without a filter; None where no edge does"""
         for f, inv in ((flt, invert), (0, False)):
             kept = self._kept_bits(m, f, inv)
             edge, cells = memo(D.find_edge, m.pos, kept, self._target(m, f, inv))
             if cells < MIN_N:
                 edge = F(self._radius(m, 1, 1.0))
-                cells = D.assign(m.pos, kept, edge)[3].size
-            if cells >= MIN_N:
-                return float(edge), f, inv
-        raise AssertionError("no cell edge leaves MIN_N cells")
+            members = D.assign(m.pos, kept, float(edge))[3]
+            if members.size >= MIN_N:
+                return float(edge), f, inv, members
+        return None
 
     def _descends(self, key, ancestor):
         while key in self.parent:
@@ -663,7 +778,10 @@ class Session:
         if kind == "cam_jump":
             op.update(pose=int(rng.integers(0, 240)))
         elif kind == "viewport":
-            op.update(size=VIEWPORTS[int(rng.integers(len(VIEWPORTS)))])
+            i = int(rng.integers(len(VIEWPORTS)))
+            if self.depth_map is not None and tuple(VIEWPORTS[i]) == tuple(v.size):  # another size: the change drops the depth map
+                i = (i + 1) % len(VIEWPORTS)
+            op.update(size=VIEWPORTS[i])
         elif kind == "visibility":
             hidden = [k for k in keys if rng.random() < 0.3]
             op.update(hidden=hidden if len(hidden) < len(keys) else hidden[1:])
@@ -685,6 +803,51 @@ class Session:
         elif kind == "rect_query":
             x0, y0 = float(rng.uniform(0, v.size[0] * 0.5)), float(rng.uniform(0, v.size[1] * 0.5))
             op.update(p0=(x0, y0), p1=(x0 + float(rng.uniform(10, v.size[0] * 0.5)), y0 + float(rng.uniform(10, v.size[1] * 0.5))), op=int(rng.integers(0, 3)))
+        elif kind in VIEW_CALLS or kind == "select_visibility":
+            # Steered by n_of (the seed plus the times the kind ran) so that the seed set meets conditions (i) to (m) whatever the
+            # walk's order; every random number is drawn whether or not it is used, so that the stream does not depend on the state.
+            n_of = self.ran.get(kind, 0) + self.seed
+            coin, coin2, pick, pose = float(rng.random()), float(rng.random()), int(rng.integers(1 << 30)), int(rng.integers(0, 240))
+            flying = inflight if (n_of // 2) % 2 == 0 or coin2 < 0.5 else 0
+            feature = FEATURES[int(rng.integers(len(FEATURES)))]
+            touch = dict(expr=MASK_EXPRS[1 + int(rng.integers(len(MASK_EXPRS) - 1))], sel=int(rng.integers(1 << 30)), edits=int(rng.integers(1 << 30)))
+            # the step's frame of a vis_view or depth_map carries a rectangle query, as fractions of the viewport the call runs at.  The
+            # device adaptor hands it to `live` BEFORE the call and not again: the call switches the query off for its own frame and
+            # must put it back
+            rect = [float(x) for x in (rng.uniform(0, 0.5), rng.uniform(0, 0.5), rng.uniform(0.1, 0.5), rng.uniform(0.1, 0.5))] + [int(rng.integers(0, 3))]
+            if kind == "vis_view":
+                # every fourth is refused (no clear; where nothing is on, `feature` is switched on first).  Every other one accumulates:
+                # onto the planes the model has, or onto a first view taken at `prime`, another pose.  The model: one with a mask
+                # and stored edits, or one of another kind than the seed's first, where there is one
+                dressed = [k for k in keys if sh.models[k].mask is not None and sh.models[k].edits is not None]
+                other = [k for k in keys if sh.models[k].kind != self.kind]
+                prefer = (dressed or other) if (n_of // 2) % 2 == 0 else (other or dressed)
+                accumulate = n_of % 2 == 0
+                op.update(key=prefer[pick % len(prefer)] if prefer else key, accumulate=accumulate, prime=(pose if pose != v.pose else (pose + 1) % 240) if accumulate else None,
+                          clear=n_of % 4 != 1 and coin < 0.9, feature=feature, rect=rect, inflight=flying)
+            elif kind == "depth_map":
+                # every third is refused; the thresholds in turn; every other one hands its ndc plane to the depth test;
+                # every fourth hides one more model first, every fourth moves to a viewport with partial tiles or of 300 tiles first
+                ndc = n_of % 4 != 3  # (every fourth without the ndc plane)
+                op.update(threshold=THRESHOLDS[(n_of // 3) % 3], ndc=ndc, as_depth_buffer=ndc and n_of % 2 == 0, clear=n_of % 3 != 0 and coin < 0.9, feature=feature,
+                          hide=pick if n_of % 4 == 1 else None, size=PARTIAL_OR_LARGE[(n_of // 4) % 2] if n_of % 4 == 2 else None, rect=rect, inflight=flying)
+            else:
+                # every fourth as the session stands, on a model whose planes were dropped where there is one: refused without planes.
+                # The others on a model with planes (those that survived most first); a model without gets a view first (`view`), and
+                # every other one a mask, a selection and an edit change between the view and the select (`touch`).  The range:
+                # two quantiles of the positive values, every fourth the Gaussians never seen
+                as_is = n_of % 4 == 1
+                have = sorted((k for k in keys if sh.models[k].vis is not None), key=lambda k: -len(sh.models[k].vis["survived"]))
+                lost = [k for k in keys if sh.models[k].vis is None and sh.models[k].vis_lost]
+                bare = [k for k in keys if sh.models[k].vis is None]
+                if as_is:
+                    pool = lost or bare or keys
+                    key = pool[pick % len(pool)]
+                elif have:
+                    key = have[0]
+                q = (None, None) if n_of % 4 == 3 else VIS_QUANTILES
+                op.update(key=key, measure=n_of % 3, op=int(rng.integers(0, 3)), flt=self._filter(sh.models[key], False)[0], q_lo=q[0], q_hi=q[1], view=not as_is,
+                          touch=touch if n_of % 2 == 0 else None, inflight=flying)
         elif kind in SELECTS:
             op.update(key=key, op=int(rng.integers(0, 3)), flt=self._filter(m, False)[0], inflight=inflight if rng.random() < 0.5 else 0)
             n_of = self.ran.get(kind, 0) + self.seed
@@ -756,10 +919,13 @@ class Session:
                 s = rng.uniform(0.8, 1.25, 3).astype(F)
                 s[int(rng.integers(3))] *= F(-1)  # a reflection
             pivot = B.reference(m.pos, m.selection())["center"] if selected else ZERO3
-            op.update(key=key, t=t, q=q, s=s, pivot=pivot, flt=X.SELECTED if selected else 0, inflight=inflight)
+            # every other one on a model that holds visibility planes (it gets a view first where it has none): the call drops them
+            op.update(key=key, t=t, q=q, s=s, pivot=pivot, flt=X.SELECTED if selected else 0, view_first=(self.ran.get(kind, 0) + self.seed) % 2 == 0,
+                      inflight=inflight)
         elif kind == "set_pod_kind":
+            key, m = self._with_planes(kind, key)
             others = [k for k in KINDS if k != m.kind]
-            op.update(key=key, to=others[int(rng.integers(len(others)))], inflight=inflight)
+            op.update(key=key, to=others[int(rng.integers(len(others)))], view_first=True, inflight=inflight)
         elif kind in ("convert", "extract"):
             flt, invert = self._filter(m, invertible=True)
             op.update(key=key, dst=self._new_key(), flt=flt, invert=invert, drop_edits=bool(rng.random() < 0.3), evict=self._evict([key]),
@@ -775,7 +941,20 @@ class Session:
                 if dressed:
                     (key, flt), invert = dressed[int(rng.integers(len(dressed)))], False
                     m = sh.models[key]
-            cell, flt, invert = self._decimate_cell(m, flt, invert)
+            # condition (e) asks merged cells and singletons of EVERY decimate: a model that holds every position twice (merged with
+            # itself) has no singleton under any edge, so another model is taken then, unfiltered
+            first = None
+            for k, f, inv in [(key, flt, invert)] + [(k, 0, False) for k in keys if k != key]:
+                found = self._decimate_cell(sh.models[k], f, inv)
+                if found is None:
+                    continue
+                first = first or (k,) + found[:3]
+                if 0 < int((found[3] == 1).sum()) < found[3].size:
+                    first = (k,) + found[:3]
+                    break
+            assert first is not None, "no cell edge leaves MIN_N cells"
+            key, cell, flt, invert = first
+            m = sh.models[key]
             op.update(key=key, dst=self._new_key(), cell=cell, flt=flt, invert=invert, evict=self._evict([key]), remove_src=bool(rng.random() < 0.5),
                       inflight=inflight)
             self.parent[op["dst"]] = key
@@ -788,8 +967,10 @@ class Session:
         elif kind == "ply_roundtrip":
             op.update(key=key, dst=self._new_key(), evict=self._evict([key]), inflight=inflight)
         elif kind == "remove_add":
+            key, m = self._with_planes(kind, key)
             n = int(rng.integers(1500, 4001))
-            op.update(key=key, n=n if n != m.n else n + 1, scene_seed=int(rng.integers(1000, 100000)), mt=self._random_mt(), inflight=inflight)
+            op.update(key=key, n=n if n != m.n else n + 1, scene_seed=int(rng.integers(1000, 100000)), mt=self._random_mt(), view_first=True,
+                      inflight=inflight)
         elif kind == "depth_test":
             op.update(on=not v.depth)
         elif kind == "hit_pairs":
@@ -804,18 +985,35 @@ class Session:
         return f"seed {self.seed} step {len(self.log) - 1} ops {self.log}"
 
     # ---- applying ----
-    def apply(self, op, dev=None):
-        """apply a drawn op to the shadow and, with `dev`, to the device in lock-step.  Returns the keys whose model changed."""
+    def _touched(self, key, what):
+        """a mask, selection ("sel") or edit change of a model: its visibility planes, where it has some, survive it"""
+        m = self.shadow.models.get(key)
+        if m is not None and m.vis is not None:
+            m.vis["survived"].add(what)
+
+    def apply(self, op, dev=None, sub=False):
+        """apply a drawn op to the shadow and, with `dev`, to the device in lock-step.  Returns the keys whose model changed.  `sub`:
+        a state op that another op switches first (a clear, a feature, a viewport, a touch): part of that op's step."""
         kind, sh, v = op["kind"], self.shadow, self.view
-        v.rect = None
-        if dev is not None and op.get("inflight"):
-            dev.enqueue_frames(op["inflight"])
+        dropped = False
+        if not sub:
+            v.rect = None
+            if self._ndc_buffer is not None:  # the frame of the step before this one read the ndc plane as its depth buffer
+                self._ndc_buffer["frames"] += 1
+            # (an op that takes a view or changes state first enqueues its frames itself, right in front of its own call)
+            if dev is not None and op.get("inflight") and kind != "select_visibility" and "view_first" not in op:
+                dev.enqueue_frames(op["inflight"])
         if kind == "cam_step":
             v.pose = (v.pose + 1) % 240
         elif kind == "cam_jump":
             v.pose = op["pose"]
         elif kind == "viewport":
+            if self.depth_map is not None and tuple(op["size"]) != self.depth_map["size"]:
+                self.depth_map["rec"]["size_changed_after"] = dropped = True
+                self.depth_map = None
             v.size = tuple(op["size"])
+            if v.depth:
+                self._ndc_buffer = None  # (the viewers get _depth(size))
         elif kind == "visibility":
             v.hidden = set(op["hidden"])
         elif kind == "display":
@@ -824,26 +1022,33 @@ class Session:
             sh.models[op["key"]].mt = tuple(np.array(a, F) for a in op["mt"])
         elif kind == "mask_eval":
             sh.mask_evaluate(op["key"], op["expr"], self.shapes)
+            self._touched(op["key"], "mask")
         elif kind == "sel_upload":
             m = sh.models[op["key"]]
             m.sel = None if op["density"] is None else random_bits(m.n, op["rseed"], op["density"])
+            self._touched(op["key"], "sel")
         elif kind == "sel_edit":
             v.sel_edit_on = bool(op["flag"] & 1)
         elif kind == "edits_upload":
             m = sh.models[op["key"]]
             m.edits = None if op["rseed"] is None else normalise_edits(random_edits(m.n, op["rseed"]))
+            self._touched(op["key"], "edit")
         elif kind == "unedited":
             sh.models[op["key"]].unedited = op["on"]
         elif kind == "rect_query":
             v.rect = op
         elif kind == "depth_test":
             v.depth = op["on"]
+            self._ndc_buffer = None  # (on: the viewers get _depth(size); off: nothing reads the plane)
         elif kind == "hit_pairs":
             v.lines = op["on"]
         elif kind == "gizmos":
             v.gizmos = op["on"]
         elif kind in SELECTS:
             self._apply_select(op, dev)
+            return []
+        elif kind in VIEW_CALLS:
+            self._apply_view_call(op, dev)
             return []
         elif kind in READ_ONLY:
             if dev is not None:
@@ -853,19 +1058,158 @@ class Session:
             return self._apply_model_op(op, dev)
         if dev is not None:
             dev.state_op(op)
+            if dropped:
+                dev.depth_map_dropped()
         return []
+
+    # ---- the calls that draw a model's own frame: gsx_model_visibility, gsx_render_depth_map ----
+    def _features_off(self, dev):
+        """the depth test, the lines and the gizmos that are on go off, on both viewers, through the ordinary state ops.  Returns
+        their names."""
+        v = self.view
+        on = [name for name, flag in (("depth_test", v.depth), ("hit_pairs", v.lines), ("gizmos", v.gizmos)) if flag]
+        for name in on:
+            self.apply({"kind": name, "on": False}, dev, sub=True)
+        return on
+
+    def _features_on(self, dev, names):
+        for name in names:
+            self.apply({"kind": name, "on": True}, dev, sub=True)
+
+    def _switch(self, dev, clear, feature):
+        """`clear`: the features that are on go off.  Otherwise the call is to be refused: where nothing is on, `feature` goes on
+        first.  Returns whether the call is refused."""
+        v = self.view
+        if clear:
+            self._features_off(dev)
+        elif not (v.depth or v.lines or v.gizmos):
+            self._features_on(dev, [feature])
+        return v.depth or v.lines or v.gizmos
+
+    def _view_first(self, key, dev):
+        """a model without visibility planes gets a view, with the features that are on switched off for it and on again after"""
+        if self.shadow.models[key].vis is None:
+            on = self._features_off(dev)
+            self._view(key, self.view.pose, False, dev)
+            self._features_on(dev, on)
+
+    def _view(self, key, pose, accumulate, dev):
+        """one gsx_model_visibility of `key` at `pose` that is not refused: the device's planes are verified by `dev` against the
+        shadow's as they stand, then adopted.  Returns (views, whether it folded into planes taken at another pose or viewport)."""
+        m = self.shadow.models[key]
+        before, at = m.vis, (pose, tuple(self.view.size))
+        folds = accumulate and before is not None
+        planes = dict(peak=None, weight=None, pixels=None) if dev is None else dev.vis_view(key, pose, accumulate, m)
+        m.vis = dict(planes, views=before["views"] + 1 if folds else 1, at=(before["at"] if folds else []) + [at], survived=before["survived"] if folds else set())
+        m.vis_lost = None
+        return m.vis["views"], bool(folds and any(a != at for a in before["at"]))
+
+    def _apply_view_call(self, op, dev):
+        kind, sh, v = op["kind"], self.shadow, self.view
+        if kind == "depth_map":
+            if op["size"] is not None and tuple(op["size"]) != tuple(v.size):
+                self.apply({"kind": "viewport", "size": op["size"]}, dev, sub=True)
+            shown = [k for k in self.keys() if k not in v.hidden]
+            if op["hide"] is not None and len(shown) >= 2:
+                v.hidden = v.hidden | {shown[op["hide"] % len(shown)]}
+        flying = self.lanes > 1 and op["inflight"] >= 2
+        (fx, fy, fw, fh, rop), (w, h) = op["rect"], v.size
+        v.rect = dict(p0=(fx * w, fy * h), p1=((fx + fw) * w, (fy + fh) * h), op=rop)  # this step's query, in force across the call
+        # A call that is to be refused must leave what is resident as it was, so something is: where the model holds no planes, or
+        # the viewer no depth map of this viewport, an unrefused call of the same kind comes first (`primed`), with the features that
+        # are on switched off for it and on again after.  (The frames in flight are then in front of that call.)
+        resident = sh.models[op["key"]].vis is not None if kind == "vis_view" else self.depth_map is not None
+        primed = not op["clear"] and not resident
+        if primed:
+            on = self._features_off(dev)
+            if kind == "vis_view":
+                self._view(op["key"], v.pose, False, dev)
+            else:
+                self._depth_map(dict(op, as_depth_buffer=False), dict(size_changed_after=False), dev)
+            self._features_on(dev, on)
+        refused = self._switch(dev, op["clear"], op["feature"])
+        if kind == "vis_view":
+            key = op["key"]
+            m = sh.models[key]
+            rec = dict(refused=refused, resident=m.vis is not None, primed=primed, views=0, other_view=False, dressed=m.mask is not None and m.edits is not None,
+                       kind_differs=m.kind != self.kind, inflight=flying and not primed)
+            if refused:
+                if dev is not None:
+                    dev.vis_refused(key, m)
+            else:
+                if op["accumulate"] and m.vis is None:  # nothing to accumulate onto: a first view from elsewhere
+                    self._view(key, op["prime"], False, dev)
+                rec["views"], rec["other_view"] = self._view(key, v.pose, op["accumulate"], dev)
+            self.vis_views.append(rec)
+            return
+        alive = self.keys()
+        shown = [k for k in alive if k not in v.hidden] or alive  # (Device._order: the step's painter's order is of these)
+        rec = dict(refused=refused, resident=self.depth_map is not None, primed=primed, n_keys=len(shown), hidden_out=len(shown) < len(alive), size=tuple(v.size),
+                   threshold=op["threshold"], ndc=op["ndc"], as_depth_buffer=False, lanes=self.lanes, frames=0, size_changed_after=False,
+                   inflight=flying and not primed)
+        if refused:
+            if dev is not None:
+                dev.depth_map_refused(self.depth_map)
+        else:
+            self._depth_map(op, rec, dev)
+        self.depth_maps.append(rec)
+
+    def _depth_map(self, op, rec, dev):
+        """one gsx_render_depth_map that is not refused: the device's planes are verified by `dev`, then adopted"""
+        v = self.view
+        planes = None if dev is None else dev.depth_map(op, self.shadow)
+        self.depth_map = dict(size=tuple(v.size), ndc=op["ndc"], planes=planes, rec=rec)
+        if op["as_depth_buffer"]:  # (dev.depth_map switched the depth test on, against the ndc plane)
+            v.depth, rec["as_depth_buffer"], self._ndc_buffer = True, True, rec
 
     def _apply_select(self, op, dev):
         kind, key, sh = op["kind"], op["key"], self.shadow
         m = sh.models[key]
         a = dict(op=op["op"], flt=op["flt"])
+        if kind == "select_visibility":
+            touched = False
+            if op["view"] and m.vis is None:  # a model without planes gets a view first
+                self._switch(dev, True, None)
+                self._view(key, self.view.pose, False, dev)
+            if op["touch"] is not None and m.vis is not None and not m.vis["survived"] >= {"mask", "sel", "edit"}:
+                t, touched = op["touch"], True  # the planes survive a mask, a selection and an edit change, through the ordinary state ops
+                self.apply({"kind": "mask_eval", "key": key, "expr": t["expr"]}, dev, sub=True)
+                self.apply({"kind": "sel_upload", "key": key, "rseed": t["sel"], "density": 0.5}, dev, sub=True)
+                self.apply({"kind": "edits_upload", "key": key, "rseed": t["edits"]}, dev, sub=True)
+            if dev is not None and op["inflight"]:
+                # The frames in flight come last, so that nothing but the select (or its refusal) follows them.  A frame of `live`
+                # alone would persist a selection edit onto the selection just uploaded, which `rebuilt` has not drawn yet: a frame
+                # of both viewers, compared as every other, comes first then
+                if touched:
+                    dev.frame()
+                dev.enqueue_frames(op["inflight"])
+            self.vis_selects.append(dict(refused=m.vis is None, survived=frozenset(m.vis["survived"]) if m.vis is not None else frozenset(),
+                                         inflight=self.lanes > 1 and op["inflight"] >= 2))
+            if m.vis is None:  # refused, and the selection stays
+                if m.vis_lost:
+                    self.vis_refusals.append(m.vis_lost)
+                if dev is not None:
+                    dev.select_refused(key)
+                    dev.check_selection(key, m.selection(), upload=False)
+                return
+            self._touched(key, "sel")
+            if m.vis["peak"] is None:  # without a device there are no planes to select by: residency alone
+                return
+            # the range the draw could not know: two quantiles of the positive values of the adopted plane, or "never seen"
+            x = sh.vis_values(key, op["measure"])
+            seen = x[x > 0]
+            lo, hi = (0.0, 0.0) if op["q_lo"] is None or not seen.size else (float(q) for q in np.quantile(seen, [op["q_lo"], op["q_hi"]]))
+            op.update(lo=lo, hi=hi)
+            self.log[-1].update(lo=lo, hi=hi)
         if op.get("seeds") is not None:
             m.sel = random_bits(m.n, op["seeds"], 0.02)
+            self._touched(key, "sel")
             if dev is not None:
                 dev.upload_selection(key, m.sel)
         if op.get("dst_seeds") is not None:
             t = sh.models[op["dst"]]
             t.sel = random_bits(t.n, op["dst_seeds"], 0.3)
+            self._touched(op["dst"], "sel")
             if dev is not None:
                 dev.upload_selection(op["dst"], t.sel)
         got = dev.select(op) if dev is not None else None  # (hit, selected[, threshold or the matrix used])
@@ -876,6 +1220,8 @@ class Session:
             variant = "select_nearest:" + ("transfer" if op["transfer"] else "range")
             if dev is not None and op["dst"] != key:  # the target's selection is read, never written
                 dev.check_selection(op["dst"], sh.models[op["dst"]].selection() if target is None else target, upload=False)
+        elif kind == "select_visibility":
+            want, variant = sh.select_visibility(key, op["measure"], op["lo"], op["hi"], **a), "select_visibility:" + VIS_MEASURES[op["measure"]]
         elif kind == "select_range":
             want, variant = sh.select_range(key, op["prop"], op["lo"], op["hi"], world=op["world"], **a), "select_range:" + ("world" if op["world"] else "model")
         elif kind == "select_neighbors":
@@ -888,6 +1234,7 @@ class Session:
             variant = "select_knn:" + ("range" if op["std_ratio"] is None else "std_ratio")
         if 0 < want[0] < m.n:
             self.nontrivial.add(variant)
+        self._touched(key, "sel")
         if dev is not None:
             assert tuple(got[:2]) == want, (kind, got, want)
             dev.check_selection(key, m.sel)
@@ -895,6 +1242,13 @@ class Session:
     def _apply_model_op(self, op, dev):
         kind, sh = op["kind"], self.shadow
         removed, changed, requantised = list(op.get("evict", [])), [], []
+        if "view_first" in op:  # then the frames in flight, right in front of the call that drops the planes
+            if op["view_first"]:
+                self._view_first(op["key"], dev)
+            if dev is not None and op["inflight"]:
+                dev.enqueue_frames(op["inflight"])
+        # did the model a transform, a pod kind change or a new upload goes to hold visibility planes?
+        had = {op["key"]: sh.models[op["key"]].vis is not None} if kind in ("xf_translate", "xf_scale", "xf_full", "set_pod_kind", "remove_add") else {}
         for k in removed:
             sh.remove(k)
         if dev is not None and removed:
@@ -972,18 +1326,34 @@ class Session:
             changed = [dst]
         elif kind == "remove_add":
             key = op["key"]
+            sh.models[key].drop_vis("remove_add")
+            lost = sh.models[key].vis_lost
             sh.remove(key)
             g = self.scene(op["n"], op["scene_seed"])
-            sh.add(key, self.kind, oracle.convert(g), op["mt"])
+            sh.add(key, self.kind, oracle.convert(g), op["mt"]).vis_lost = lost
             if dev is not None:
                 dev.remove([key])
                 dev.new_model(key, g, op["mt"])
                 self._take_upload(key, dev)
             self.view.hidden.discard(key)
+            self._planes_dropped(key, had.get(key), dev)
             return [key]
         self._settle(changed, requantised, exact, dev, kind)
+        for key in had:
+            self._planes_dropped(key, had[key], dev)
         self.view.hidden -= set(changed) | set(removed)
         return changed
+
+    def _planes_dropped(self, key, had, dev):
+        """after a call that drops the visibility planes (an upload, a pod kind change, a transform that moves something) of a model
+        that had some: a select by them is refused at once, and leaves the selection alone"""
+        m = self.shadow.models.get(key)
+        if not had or m is None or m.vis is not None:
+            return
+        self.vis_refusals.append(m.vis_lost)
+        if dev is not None:
+            dev.select_refused(key)
+            dev.check_selection(key, m.selection(), upload=False)
 
     def _extract(self, src, dst, flt, invert, drop_edits, to, exact, dev):
         sh = self.shadow

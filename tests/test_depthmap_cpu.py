@@ -5,7 +5,8 @@
 2. gsx_depth_map_unproject against a float64 numpy inverse of view and proj, at pixel centres and corners.
 3. The header, the ctypes layer and the Rust and C++ facades declare the calls; the ABI stays 3.
 4. The test conditions: for every scene the GPU tests compare with the reference, both pod kinds and both thresholds, at most 2 % of
-   the pixels have an uncertain crossing and at least 25 % cross, under the oracle's projection."""
+   the pixels have an uncertain crossing and at least 25 % cross, under the oracle's projection; the three-model scene
+   (visibility_scenes.THREE) as well, with its empty tiles where the GPU test needs them."""
 import ctypes as C
 import os
 import re
@@ -257,3 +258,30 @@ def test_reference_scenes_stay_inside_the_cap(name, kind, threshold):
         assert size[0] % 16 and size[1] % 2, "partial tiles, a lane's second pixel outside"
     if threshold == 1.0:
         assert np.array_equal(ref.index == NONE, ref.A == 0.0), "the front surface: a crossing exactly where anything was blended"
+
+
+def test_the_three_model_scene_stays_inside_the_cap_and_has_its_empty_tiles():
+    """visibility_scenes.THREE under the oracle's projection, walked near to far as test_gpu_depthmap.py walks the device's lists: the
+    cap and the floor of the GPU test hold for the reference alone, every model holds surfaces, "mid" has no entry in the right three
+    tile columns and "near" none in the left three, and "near" crosses pixels in tiles where the launches of "mid" find nothing."""
+    models, cam, (w, h) = S.three_models()
+    keys = list(models)
+    assert keys == ["far", "mid", "near"] and (w, h) == (83, 51) and all(50 <= g.shape[0] <= 500 for g in models.values())
+    f = common.oracle_frame(cam, w, h)
+    assert (f.tiles_x, f.tiles_y) == (6, 4)
+    ref, counts = None, {}
+    for layer in (2, 1, 0):  # the last key first
+        pr = oracle.project(f, *oracle.convert_pod(models[keys[layer]], 0, 0))
+        idx, nvis = oracle.depth_sort(pr["key"])
+        off, lst = oracle.tile_lists(f, idx, nvis, pr["rect"])
+        counts[keys[layer]] = np.diff(off).reshape(4, 6)
+        ref = D.walk(pr["mean2d"], pr["conic_opacity"], pr["key"], off, lst, w, h, f.k2, f.alpha_max, f.alpha_min, 1e-4, f.display_mode, 0.5, layer=layer, state=ref)
+    unc, crossed = float(ref.uncertain.mean()), float((ref.index != NONE).mean())
+    print(f"depth map of three models: {int(ref.uncertain.sum())} of {ref.uncertain.size} pixels uncertain, {crossed:.1%} cross, layers "
+          f"{[int((ref.layer == k).sum()) for k in range(3)]}, entries a tile: far {counts['far'].tolist()}, mid {counts['mid'].tolist()}, near {counts['near'].tolist()}")
+    assert unc <= S.UNCERTAIN_CAP and crossed >= 0.25
+    assert all((ref.layer == k).any() for k in range(3)), "every model holds surfaces"
+    assert (counts["far"] > 0).all() and not counts["mid"][:, 3:].any() and (counts["mid"][:, :3] > 0).all()
+    assert not counts["near"][:, :3].any() and (counts["near"][:, 3:] > 0).all()
+    # a pixel "near" crosses lies in a tile where the launch of "mid" returns early: the planes must keep it
+    assert (ref.layer[:, 48:] == 2).any()

@@ -198,6 +198,50 @@ def test_two_models_against_the_reference(order):
         _consistent(dm)
 
 
+def test_three_models_against_the_reference():
+    """visibility_scenes.THREE at 83 x 51: "mid" has no entry in the right three tile columns, so its launch (not the first) returns
+    early there and must leave the planes of the first launch alone; "near" has none in the left three, so the first launch writes
+    those tiles with an empty list.  The reference is chained through `state=` on the device's own lists."""
+    models, cam, (w, h) = S.three_models()
+    order = list(models)  # far to near
+    v = MultiModelViewer(sh=KINDS[0][0], cov3d=KINDS[0][1])
+    with v:
+        for key, g in models.items():
+            _load(v, g, key)
+        v.update_camera(cam, (w, h))
+        v.update_gaussian_transform(1.0, GaussianDisplayMode.Splat, GaussianShDegree.new(3), False)
+        v.set_render_options(progressive=0)
+        lists = {k: _device_lists(v, k, (w, h)) for k in order}
+        dm = v.render_depth_map(order)
+        f = common.oracle_frame(cam, w, h)
+        ref = None
+        for layer in (2, 1, 0):  # the last key first
+            pr, (off, lst) = lists[order[layer]]
+            ref = D.walk(pr["mean2d"], pr["conic_opacity"], pr["key"], off, lst, w, h, f.k2, f.alpha_max, f.alpha_min, 1e-4, 0, 0.5, layer=layer, state=ref)
+        unc, crossed, dev_a, dev_s, dev_t = D.check(ref, dm.surface, dm.sum, dm.alpha, dm.transmittance, dm.index, dm.layer, cap=S.UNCERTAIN_CAP, floor=0.25)
+        print(f"depth map of three models: uncertain {int(ref.uncertain.sum())} of {ref.uncertain.size}, crossed {crossed:.1%}, A off by {dev_a:.3e} of its "
+              f"bound, S by {dev_s:.3e}, T by {dev_t:.3e}, layers {[int((ref.layer == k).sum()) for k in range(3)]}")
+        assert all((ref.layer == k).any() for k in range(3)), "all three models hold surfaces"
+        assert dm.models == 3
+        _consistent(dm)
+        # the device's own lists: whole tiles of a launch that is not the first are empty, and so are tiles of the first launch
+        entries = {k: np.diff(np.asarray(lists[k][1][0], np.int64)).reshape(4, 6) for k in order}
+        assert not entries["mid"][:, 3:].any() and entries["mid"][:, :3].any(), "the launch of 'mid' returns early in the right three tile columns"
+        assert not entries["near"][:, :3].any() and entries["near"][:, 3:].any(), "the first launch writes the left three tile columns with an empty list"
+        # there: a pixel the first launch crossed, in a tile where a later launch returned early, keeps its crossing ...
+        kept = dm.layer == 2
+        assert (ref.layer[:, 48:] == 2).any() and kept[:, 48:].any() and not kept[:, :48].any()
+        assert (dm.index[kept] < models["near"].shape[0]).all()
+        # ... and the walk without the model that is absent from a half is, in that half, the same bytes: the early return changed
+        # nothing on the right, the first launch's write of an empty tile is the walk's neutral start on the left
+        for keys, cols, layers in ((["far", "near"], slice(48, None), (0, 2)), (["far", "mid"], slice(0, 48), (0, 1))):
+            two = v.render_depth_map(keys)
+            for p in ("surface", "sum", "alpha", "transmittance", "index"):
+                assert np.array_equal(_bits(getattr(two, p)[:, cols]), _bits(getattr(dm, p)[:, cols])), (keys, p)
+            on = two.layer[:, cols] != NONE
+            assert np.array_equal(np.asarray(layers, U32)[two.layer[:, cols][on]], dm.layer[:, cols][on]), (keys, "layer")
+
+
 # ---- 3. determinism and isolation --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("in_flight", [1, 2])
 def test_two_calls_return_the_same_bytes_whatever_ran_before(in_flight):

@@ -4,7 +4,8 @@ extract, merge and convert as tests/extract_ref.py's kept set says, `verify` fin
 seeds draw give hit sets that are neither empty nor full under the restatements alone (condition (b)), on the scenes the GPU test uses.
 A decimate follows the kept set, orders its cells by representative and takes its merged rows from tests/decimate_driver.cpp (a host
 program built once per module); select_nearest writes the source and reads both selections as they were; and the default seeds meet
-the fuzz's conditions (e), (f) and (h) on decimate, the nearest calls across two models and the align step."""
+the fuzz's conditions (e), (f) and (h) on decimate, the nearest calls across two models and the align step, and (i) to (m) on the
+visibility and depth map calls, which depend on what is resident when a call comes and not on what the planes hold."""
 import functools
 
 import numpy as np
@@ -40,6 +41,9 @@ def test_the_schedule_covers_every_op_kind_and_is_the_same_on_every_run():
     assert len(set(S.OP_KINDS)) == len(S.OP_KINDS) and set(S.MODEL_CHANGING) | set(S.SELECTS) | set(S.READ_ONLY) <= set(S.OP_KINDS)
     assert "decimate" in S.MODEL_CHANGING and "select_nearest" in S.SELECTS and {"decimate_edge", "nearest", "align_step"} <= set(S.READ_ONLY)
     assert set(S.NEAREST_FAMILY) <= set(S.SPATIAL) <= set(S.OP_KINDS) and {v.split(":")[0] for v in S.SELECT_VARIANTS} == set(S.SELECTS)
+    # the visibility and depth map calls: "visibility" is the camera op that hides models, the calls go by other names
+    assert set(S.VIEW_CALLS) == {"vis_view", "depth_map"} <= set(S.READ_ONLY) and "select_visibility" in S.SELECTS and "visibility" in S.CAMERA
+    assert set(S.DEVICE_ONLY_VARIANTS) == {"select_visibility:" + m for m in S.VIS_MEASURES} <= set(S.SELECT_VARIANTS)
     for seed in S.DEFAULT_SEEDS:
         p = S.plan(seed)
         assert p == S.plan(seed)
@@ -64,8 +68,10 @@ def test_the_drawn_parameters_are_the_same_on_every_run(seed, driver):
     for k, m in a.shadow.models.items():
         assert all(p.tobytes() == q.tobytes() for p, q in zip(m.planes, b.shadow.models[k].planes))  # (a decimate's merged rows too)
     kinds = [op["kind"] for op in a.log]
-    assert {"decimate", "decimate_edge", "nearest", "select_nearest", "align_step"} <= set(kinds)
+    assert {"decimate", "decimate_edge", "nearest", "select_nearest", "align_step", "vis_view", "depth_map", "select_visibility"} <= set(kinds)
     assert a.cases == b.cases and a.decimates == b.decimates and len(a.decimates) == kinds.count("decimate")
+    assert (a.vis_views, a.vis_selects, a.vis_refusals, a.depth_maps) == (b.vis_views, b.vis_selects, b.vis_refusals, b.depth_maps)
+    assert (len(a.vis_views), len(a.vis_selects), len(a.depth_maps)) == tuple(kinds.count(k) for k in ("vis_view", "select_visibility", "depth_map"))
 
 
 def test_the_default_seeds_meet_the_conditions_on_decimate_nearest_and_align(driver):
@@ -82,7 +88,43 @@ def test_the_default_seeds_meet_the_conditions_on_decimate_nearest_and_align(dri
     assert any(a == b for a, b in pairs) and any(a != b for a, b in pairs)  # the source as its own target, and another model
 
 
+def _vis_records(runs):
+    return dict(views=[r for s in runs for r in s.vis_views], selects=[r for s in runs for r in s.vis_selects],
+                refusals=[r for s in runs for r in s.vis_refusals], depth_maps=[r for s in runs for r in s.depth_maps])
+
+
+def test_the_default_seeds_meet_the_conditions_on_visibility_and_the_depth_map(driver):
+    """(i) to (m) of tests/test_gpu_model_fuzz.py, stated once in model_shadow.unmet_views.  They depend on the draws alone: on which
+    planes are RESIDENT when a call comes (the shadow follows the library's drops), not on what the planes hold."""
+    runs = [_host_run(seed, driver) for seed in S.DEFAULT_SEEDS]
+    vis = _vis_records(runs)
+    assert not S.unmet_views(**vis), S.unmet_views(**vis)
+    assert not S.unmet(set().union(*(s.cases for s in runs)), [d for s in runs for d in s.decimates], vis)
+    # nothing at all meets nothing: three of (i), two of (j), three and the three thresholds and three of (k), four of (l), three of (m)
+    assert len(S.unmet_views([], [], [], [])) == 21
+    # a refused call meets none of the conditions on the calls that ran
+    refused = dict(vis, views=[dict(r, refused=True) for r in vis["views"]], depth_maps=[dict(r, refused=True) for r in vis["depth_maps"]])
+    assert len(S.unmet_views(**refused)) == 3 + 9 + 2 + 2  # (all of (i) and (k), "run twice" of (l) and (m) for the two)
+    # every refused view and depth map found planes, or a map of its viewport, resident: the refusal has something to leave as it was.
+    # Some were there from an earlier op of the seed, the others from the unrefused call the session put in front (`primed`)
+    for recs in (vis["views"], vis["depth_maps"]):
+        assert all(r["resident"] for r in recs if r["refused"]) and any(r["primed"] for r in recs) and not any(r["primed"] and not r["refused"] for r in recs)
+    assert any(r["refused"] and not r["primed"] for r in vis["views"])
+    # a refusal without anything resident does not meet (l)
+    bare = dict(vis, views=[dict(r, resident=False) for r in vis["views"]], depth_maps=[dict(r, resident=False) for r in vis["depth_maps"]])
+    assert len(S.unmet_views(**bare)) == 2
+    # each of the three calls that drop a model's planes did so somewhere, and a select by them was refused at once; two do not meet (j)
+    assert set(vis["refusals"]) == set(S.DROPPERS) and len(S.unmet_views(**dict(vis, refusals=list(S.DROPPERS[:2])))) == 1
+    # some depth map ran without the ndc plane
+    assert any(not op["ndc"] for s in runs for op, r in zip([o for o in s.log if o["kind"] == "depth_map"], s.depth_maps) if not r["refused"])
+    # every measure of a select_visibility is drawn on resident planes somewhere (the hit sets are the device's to show: condition (b))
+    ran = {op["measure"] for s in runs for op, r in zip([o for o in s.log if o["kind"] == "select_visibility"], s.vis_selects) if not r["refused"]}
+    assert ran == {0, 1, 2}
+
+
 def test_every_select_variant_is_non_trivial_somewhere_in_the_default_seeds(driver):
+    """The three select_visibility variants are the device's to show (tests/test_gpu_model_fuzz.py asserts them with the others): the
+    host run holds no planes to select by, and says so here instead of dropping them silently."""
     seen, sizes = set(), []
     for seed in S.DEFAULT_SEEDS:
         s = _host_run(seed, driver)
@@ -90,7 +132,7 @@ def test_every_select_variant_is_non_trivial_somewhere_in_the_default_seeds(driv
         assert 1 <= len(s.shadow.models) <= S.MAX_MODELS
         sizes += [m.n for m in s.shadow.models.values()]
         assert all(s.ran.get(k) for k in S.OP_KINDS if k != "cam_step"), seed
-    assert seen == set(S.SELECT_VARIANTS), set(S.SELECT_VARIANTS) - seen
+    assert seen == set(S.SELECT_VARIANTS) - set(S.DEVICE_ONLY_VARIANTS), (set(S.SELECT_VARIANTS) - seen, seen & set(S.DEVICE_ONLY_VARIANTS))
     assert S.MIN_N <= min(sizes) and max(sizes) <= S.MAX_N
 
 
@@ -319,6 +361,48 @@ def test_apply_transform_touches_the_kept_rows_only():
     count, exact = sh.apply_transform("a", S.ZERO3, F([0, 0, 0, -1]), S.ONE3, pivot)  # the identity writes nothing
     assert count == 45 and all(e.all() for e in exact)
     assert all(np.array_equal(a, b) for a, b in zip(m.planes[1:], before[1:]))
+
+
+def test_visibility_planes_are_dropped_exactly_where_the_library_drops_them():
+    """Model::vis in the shadow: residency alone (no device to adopt planes from)"""
+    s = S.Session(1)
+    sh = s.shadow
+    m = _dressed(sh, "a", 45, 7)
+    _dressed(sh, "b", 30, 9)
+    t = F([0.25, 0, -1])
+
+    def view(key="a", accumulate=False):
+        return s._view(key, s.view.pose, accumulate, None)
+
+    assert m.vis is None and view() == (1, False) and m.vis["views"] == 1 and m.vis_lost is None
+    s.view.pose += 1
+    assert view(accumulate=True) == (2, True) and view(accumulate=True) == (3, True) and view() == (1, False)
+    # kept: mask, selection, edit, show-unedited, model transform, camera; the identity transform and an empty kept set
+    for op in (dict(kind="mask_eval", key="a", expr="0"), dict(kind="sel_upload", key="a", rseed=3, density=0.5), dict(kind="edits_upload", key="a", rseed=4),
+               dict(kind="unedited", key="a", on=True), dict(kind="model_transform", key="a", mt=(t, S.IDENT, S.ONE3)), dict(kind="cam_jump", pose=7),
+               dict(kind="viewport", size=(83, 51)), dict(kind="visibility", hidden=["a"])):
+        s.apply(op)
+    assert m.vis is not None and m.vis["survived"] == {"mask", "sel", "edit"}
+    sh.apply_transform("a", S.ZERO3, S.IDENT, S.ONE3)
+    m.sel = np.zeros(m.n, bool)
+    sh.apply_transform("a", t, S.IDENT, S.ONE3, flt=X.SELECTED)
+    assert m.vis is not None and m.vis_lost is None
+    # dropped: a transform that moves something, a pod kind change; a new model starts without
+    sh.apply_transform("a", t, S.IDENT, S.ONE3)
+    assert m.vis is None and m.vis_lost == "apply_transform"
+    view()
+    assert m.vis_lost is None and m.vis["survived"] == set()
+    sh.set_pod_kind("a", S.NORM8_HALF)
+    assert m.vis is None and m.vis_lost == "set_pod_kind"
+    sh.set_pod_kind("a", S.SINGLE)
+    assert m.vis_lost == "set_pod_kind"  # (nothing was resident: nothing was dropped)
+    view()
+    view("b")
+    sh.extract("a", "c")
+    sh.merge("d", ["a", "b"])
+    assert sh.models["c"].vis is None and sh.models["d"].vis is None and m.vis is not None and sh.models["b"].vis is not None
+    # the views of the two models are their own
+    assert sh.models["b"].vis["views"] == 1 and sh.models["b"].vis["at"] == m.vis["at"]
 
 
 def test_verify_finds_a_wrong_row_where_the_shadow_knows_it(driver):

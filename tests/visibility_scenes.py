@@ -41,3 +41,31 @@ def scene(spec):
     if op != 1.0:
         g["color"][:, 3] = (g["color"][:, 3].astype(np.float32) * np.float32(op)).astype(np.uint8)
     return g, camera.orbit_pose(pose), (w, h)
+
+
+#: the three-model walk of the depth map at 83 x 51 (6 x 4 tiles, partial at the right and at the bottom), far to near: key -> a
+#: REF-style entry and the tile columns [c0, c1) the model is confined to.  "far" covers the viewport.  "mid" keeps the left three tile
+#: columns only: its launch is not the walk's first, so it returns early in the tiles of the right and must leave their planes alone.
+#: "near" keeps the right three only: its launch is the first, and writes the tiles of the left with an empty list.  The seeds and
+#: opacities are chosen on the host so that the reference alone stays inside UNCERTAIN_CAP (tests/test_depthmap_cpu.py proves it)
+THREE = {
+    "far": ((400, 83, 51, 72, 10.0, 1.0, 6), (0, 6)),
+    "mid": ((500, 83, 51, 77, 6.0, 0.6, 6), (0, 3)),
+    "near": ((500, 83, 51, 76, 6.0, 0.6, 6), (3, 6)),
+}
+
+
+def three_models():
+    """({key: gaussians} far to near, camera, (width, height)) of THREE.  A model confined to tile columns keeps the Gaussians whose
+    tile rectangle (spec §4.7: integer, the same on the host and on the device) lies inside them under the oracle's projection."""
+    import oracle
+
+    out = {}
+    for key, (spec, (c0, c1)) in THREE.items():
+        g, cam, (w, h) = scene(spec)
+        if (c0, c1) != (0, 6):
+            pr = oracle.project(common.oracle_frame(cam, w, h), *oracle.convert_pod(g, 0, 0))
+            rect = pr["rect"].astype(np.int64)
+            g = g[(pr["key"] != 0xFFFFFFFF) & (rect[:, 0] >= c0) & (rect[:, 2] <= c1)].copy()
+        out[key] = g
+    return out, cam, (w, h)
