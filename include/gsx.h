@@ -1031,6 +1031,72 @@ gsx_status gsx_depth_map_device_ptrs(gsx_viewer* v, void** surface, void** sum, 
 gsx_status gsx_depth_map_unproject(const float view[16], const float proj[16], uint32_t width, uint32_t height,
                                    float px, float py, float view_depth, float out_world[3]);
 
+/* ---- model normals: a plane fitted to every Gaussian and its k nearest, the plane's unit normal, how far the neighbourhood is from
+ *      a plane, the neighbours' indices, and a selection by either, on the device (spec/RENDER_SPEC.md §26 [BUILD-SPEC];
+ *      kernels_normals.hip).  Selecting the floor: gsx_model_select_normals in mode GSX_NORMALS_SELECT_FACING with dir = up,
+ *      GSX_NORMALS_ABS, lo 0.95, hi 1; dropping what floats: mode GSX_NORMALS_SELECT_VARIATION.  No Gaussian crosses to the host.
+ *      Participants, distance and space are gsx_model_knn's word for word (the filter, three finite stored coordinates, the float32
+ *      d2, model space).  GSX_NORMALS_MIN_K <= k <= GSX_NORMALS_MAX_K.
+ *      Neighbour list: N(i) is the k smallest elements of { (d2(i, j), j) : j participates, j != i }, ordered by d2, then by index.
+ *      out_index[i * k + q] (nullable; n * k words) is the q-th element's index, GSX_NORMALS_NONE where the set has fewer than
+ *      q + 1 elements or the distance is +inf, and in the whole row of a Gaussian that does not participate.  The list's d2 are
+ *      gsx_model_knn's row for the same k bit for bit; with the index in the order, ties cannot make the list ambiguous.
+ *      Fitted: a participant whose k entries all have a finite d2 and whose k-th d2 is above 0.  Everybody else has the normal
+ *      (0, 0, 0) and the variation +inf.
+ *      The fit, in double: offsets q_0 = 0 (the Gaussian itself) and q_m = the float32 difference p_j - p_i per axis, m = 1 .. k in
+ *      list order; mean = (sum q_m) / (k + 1); scatter C_ab = sum (q_ma - mean_a)(q_mb - mean_b); both sums in ascending m without
+ *      contraction; the eigenvalues l0 >= l1 >= l2 and vectors of C by §14's fixed-sweep Jacobi solve in double, the eigenvalues
+ *      clamped at 0; ((l0 + l1) + l2) that is 0 or not finite: not fitted.  out_normal[i * 3 ..] (nullable) is the eigenvector of
+ *      l2 over its length, rounded to float32; out_variation[i] (nullable) = (float)(l2 / ((l0 + l1) + l2)), in [0, 1/3]: 0 on a
+ *      plane, 1/3 where the neighbourhood is isotropic.  The sums follow the list, so no grid can change a bit of the fit.
+ *      Sign.  GSX_NORMALS_ORIENT_CANONICAL: the first non-zero component of the float32 normal is positive.
+ *      GSX_NORMALS_ORIENT_TOWARD: toward[3] is a finite model-space point; the normal is negated iff sum_a n_a * ((double)toward_a -
+ *      (double)p_ia) < 0, the float32 normal in double, in axis order; a sum of exactly 0 falls back to the canonical rule.
+ *      Statistics over the fitted: n_fitted, variation_min and variation_max exact, mean = the double sum of the float32 variations
+ *      over n_fitted, folded from per-workgroup partials in index order: the same bits on every call; all 0 without any.
+ *      gsx_model_select_normals, the hit set by mode.  GSX_NORMALS_SELECT_VARIATION: fitted and lo <= variation <= hi.
+ *      GSX_NORMALS_SELECT_FACING: dir[3] finite and not zero, normalised in double and rounded to float32 d; c = (nx dx + ny dy) +
+ *      nz dz in float32, every operation rounded; |c| with the flag GSX_NORMALS_ABS; hit iff fitted and lo <= c <= hi.  lo <= hi,
+ *      neither NaN.  selection_op, a model without a selection, the tail bits, GSX_BOUNDS_SELECTED reading the selection as it
+ *      was before the call, *out_hit / *out_selected (nullable), ordering and frame consistency: gsx_model_select_knn's.
+ *      Knobs that change no result: radius_hint, grid_bits, max_rounds, as in gsx_knn_desc.  stats.first_radius, rounds, n_brute
+ *      and grid_bits report what ran; no list entry, normal, variation, statistic or selection word depends on them.
+ *      Errors: a null viewer, key, desc or stats pointer of gsx_model_normals, unknown filter or flag bits, k outside 3 .. 16, an
+ *      unknown orient, mode or op, a toward (orient TOWARD) or a bound that is not finite (a bound may be infinite, not NaN), a dir
+ *      (mode FACING) that is zero or not finite, lo > hi, a radius_hint, grid_bits or max_rounds gsx_model_knn refuses, a reserved
+ *      word != 0: GSX_ERR_INVALID_ARG; unknown key: GSX_ERR_NOT_FOUND; a viewer with a communicator, or a sharded model:
+ *      GSX_ERR_UNSUPPORTED; an allocation failure: GSX_ERR_OOM, the model and its selection as they were.  A model of 0 Gaussians,
+ *      or 0 participants: GSX_OK with zeros.  gsx_model_normals writes nothing a frame reads. ---- */
+#define GSX_NORMALS_MIN_K 3u
+#define GSX_NORMALS_MAX_K 16u
+#define GSX_NORMALS_ORIENT_CANONICAL 0u
+#define GSX_NORMALS_ORIENT_TOWARD 1u
+#define GSX_NORMALS_SELECT_VARIATION 0u
+#define GSX_NORMALS_SELECT_FACING 1u
+#define GSX_NORMALS_ABS 1u            /* gsx_normals_select_desc.flags: mode FACING tests |c| */
+#define GSX_NORMALS_NONE 0xFFFFFFFFu  /* out_index: no such neighbour */
+typedef struct gsx_normals_desc {
+    uint32_t filter; uint32_t flags; uint32_t k; uint32_t orient; /* GSX_BOUNDS_*, 0, 3 .. 16, GSX_NORMALS_ORIENT_* */
+    float radius_hint; uint32_t grid_bits; uint32_t max_rounds; uint32_t reserved;
+    float toward[3]; uint32_t reserved2;
+} gsx_normals_desc; /* 48 B */
+typedef struct gsx_normals_stats_t {
+    uint64_t count; uint64_t n_nonfinite; uint64_t n_fitted; uint64_t n_brute; double mean;
+    float variation_min; float variation_max; float first_radius; uint32_t rounds; uint32_t grid_bits; uint32_t reserved;
+} gsx_normals_stats_t; /* 64 B */
+typedef struct gsx_normals_select_desc {
+    uint32_t filter; uint32_t flags; uint32_t selection_op; uint32_t mode; /* GSX_BOUNDS_*, GSX_NORMALS_ABS, gsx_selection_op, GSX_NORMALS_SELECT_* */
+    uint32_t k; uint32_t orient; float radius_hint; uint32_t grid_bits;
+    uint32_t max_rounds; float lo; float hi; uint32_t reserved;
+    float dir[3]; float toward[3]; uint32_t reserved2[2];
+} gsx_normals_select_desc; /* 80 B */
+void gsx_normals_desc_default(gsx_normals_desc* d); /* no filter, flags 0, k 8, ORIENT_CANONICAL, everything else 0 */
+gsx_status gsx_model_normals(gsx_viewer* v, const char* key, const gsx_normals_desc* desc, float* out_normal /* nullable, n * 3 */,
+                             float* out_variation /* nullable, n */, uint32_t* out_index /* nullable, n * k, row i at i * k */,
+                             gsx_normals_stats_t* out);
+gsx_status gsx_model_select_normals(gsx_viewer* v, const char* key, const gsx_normals_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected,
+                                    gsx_normals_stats_t* out_stats /* nullable */);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

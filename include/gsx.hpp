@@ -321,6 +321,29 @@ struct MultiModelViewerModel {
         check(gsx_model_select_knn(v_, key_.c_str(), &desc, &hit, &selected, stats));
         return {hit, selected};
     }
+    // gsx_model_normals: a plane fitted in double to every Gaussian and its desc.k nearest (by squared distance, then index), among the
+    // Gaussians that pass desc.filter and have a finite position, on the device.  normal receives n * 3 floats ((0, 0, 0) where none
+    // is fitted), variation one float a Gaussian (+inf there), index (nullable) n * k words, row i at i * k, GSX_NORMALS_NONE where
+    // there is no such neighbour.
+    gsx_normals_stats_t normals(const gsx_normals_desc& desc, std::vector<float>& normal, std::vector<float>& variation,
+                                std::vector<uint32_t>* index = nullptr) const {
+        uint64_t n = 0;
+        check(gsx_model_len(v_, key_.c_str(), &n));
+        normal.assign((size_t)n * 3, 0.0f);
+        variation.assign((size_t)n, std::numeric_limits<float>::infinity());
+        if (index) index->assign((size_t)n * desc.k, GSX_NORMALS_NONE);
+        gsx_normals_stats_t out{};
+        check(gsx_model_normals(v_, key_.c_str(), &desc, normal.data(), variation.data(), index ? index->data() : nullptr, &out));
+        return out;
+    }
+    // gsx_model_select_normals: the hit set is, by desc.mode, the fitted Gaussians with a variation in [lo, hi] or with a cosine
+    // between their normal and desc.dir in [lo, hi]; desc.selection_op sets, adds or removes it, on the device.  Returns {hit,
+    // selected afterwards}; stats (nullable) receives the statistics.
+    std::pair<uint64_t, uint64_t> select_normals(const gsx_normals_select_desc& desc, gsx_normals_stats_t* stats = nullptr) {
+        uint64_t hit = 0, selected = 0;
+        check(gsx_model_select_normals(v_, key_.c_str(), &desc, &hit, &selected, stats));
+        return {hit, selected};
+    }
     // gsx_model_nearest: for every Gaussian of this model, mapped by desc.xform (or by the two models' transforms), the nearest
     // Gaussian of the model dst_key: index (GSX_NEAREST_NONE where none) and squared distance (+inf there), both nullable, on the
     // device, bit for bit the brute-force answer with ties going to the smaller index.  The stats carry the one-sided chamfer (mean)

@@ -333,6 +333,31 @@ impl MultiModelViewerModel {
         check(unsafe { sys::gsx_model_select_knn(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected, &mut out) })?;
         Ok((hit, selected, out))
     }
+    /// `gsx_model_normals`: a plane fitted in double to every Gaussian and its `desc.k` nearest (by squared distance, then index), among
+    /// the Gaussians that pass `desc.filter` and have a finite position, on the device.  Returns `(normal, variation, index, stats)`:
+    /// `normal` holds `n * 3` values (`0, 0, 0` where none is fitted), `variation` one a Gaussian (`+inf` there), `index` `n * k` words,
+    /// row `i` at `i * k` (empty without `indices`), `GSX_NORMALS_NONE` where there is no such neighbour.
+    #[allow(clippy::type_complexity)]
+    pub fn normals(&self, desc: &sys::gsx_normals_desc, indices: bool) -> Result<(Vec<f32>, Vec<f32>, Vec<u32>, sys::gsx_normals_stats_t), Error> {
+        let mut n = 0u64;
+        check(unsafe { sys::gsx_model_len(self.v, self.key.as_ptr(), &mut n) })?;
+        let mut normal = vec![0f32; n as usize * 3];
+        let mut variation = vec![f32::INFINITY; n as usize];
+        let mut index = vec![sys::GSX_NORMALS_NONE; if indices { n as usize * desc.k as usize } else { 0 }];
+        let mut out = sys::gsx_normals_stats_t::default();
+        let index_ptr = if indices { index.as_mut_ptr() } else { std::ptr::null_mut() };
+        check(unsafe { sys::gsx_model_normals(self.v, self.key.as_ptr(), desc, normal.as_mut_ptr(), variation.as_mut_ptr(), index_ptr, &mut out) })?;
+        Ok((normal, variation, index, out))
+    }
+    /// `gsx_model_select_normals`: the hit set is, by `desc.mode`, the fitted Gaussians with a variation in `[lo, hi]` or with a cosine
+    /// between their normal and `desc.dir` in `[lo, hi]`; `desc.selection_op` sets, adds or removes it, on the device.  Returns
+    /// `(hit, selected, stats)`.
+    pub fn select_normals(&mut self, desc: &sys::gsx_normals_select_desc) -> Result<(u64, u64, sys::gsx_normals_stats_t), Error> {
+        let (mut hit, mut selected) = (0u64, 0u64);
+        let mut out = sys::gsx_normals_stats_t::default();
+        check(unsafe { sys::gsx_model_select_normals(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected, &mut out) })?;
+        Ok((hit, selected, out))
+    }
     /// `gsx_model_nearest`: for every Gaussian of this model, mapped by `desc.xform` (or by the two models' transforms), the nearest
     /// Gaussian of the model `dst_key`, on the device, bit for bit the brute-force answer with ties going to the smaller index.
     /// Returns `(index, d2, stats)`: `GSX_NEAREST_NONE` and `+inf` where there is none (both empty without `rows`); the stats carry

@@ -93,6 +93,14 @@ pub const GSX_KNN_SCORE_KTH: u32 = 0;
 pub const GSX_KNN_SCORE_MEAN: u32 = 1;
 pub const GSX_KNN_SELECT_RANGE: u32 = 0;
 pub const GSX_KNN_SELECT_OUTLIERS: u32 = 1;
+pub const GSX_NORMALS_MIN_K: u32 = 3;
+pub const GSX_NORMALS_MAX_K: u32 = 16;
+pub const GSX_NORMALS_ORIENT_CANONICAL: u32 = 0;
+pub const GSX_NORMALS_ORIENT_TOWARD: u32 = 1;
+pub const GSX_NORMALS_SELECT_VARIATION: u32 = 0;
+pub const GSX_NORMALS_SELECT_FACING: u32 = 1;
+pub const GSX_NORMALS_ABS: u32 = 1;
+pub const GSX_NORMALS_NONE: u32 = 0xFFFF_FFFF;
 pub const GSX_NEAREST_NONE: u32 = 0xFFFF_FFFF;
 pub const GSX_NEAREST_MODEL_TRANSFORMS: u32 = 1;
 pub const GSX_NEAREST_SELECT_RANGE: u32 = 0;
@@ -357,6 +365,31 @@ pub struct gsx_depth_map_desc { pub flags: u32, pub threshold: f32, pub reserved
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct gsx_depth_map_stats_t { pub n_covered: u64, pub n_crossed: u64, pub surface_min: f32, pub surface_max: f32, pub models: u32, pub reserved: u32 }
+/// gsx_model_normals, 48 bytes: the GSX_BOUNDS_* filter, flags (0), k 3..=16, the GSX_NORMALS_ORIENT_* rule and its model-space point
+/// `toward`, and gsx_knn_desc's three knobs that change no result
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_normals_desc {
+    pub filter: u32, pub flags: u32, pub k: u32, pub orient: u32, pub radius_hint: f32, pub grid_bits: u32, pub max_rounds: u32, pub reserved: u32,
+    pub toward: [f32; 3], pub reserved2: u32,
+}
+/// the result of gsx_model_normals, 64 bytes: participants, those with a NaN / inf coordinate, the fitted Gaussians, the Gaussians the
+/// exact fallback answered, the variations' double mean, minimum and maximum, the first radius, the grid rounds, the table used
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_normals_stats_t {
+    pub count: u64, pub n_nonfinite: u64, pub n_fitted: u64, pub n_brute: u64, pub mean: f64,
+    pub variation_min: f32, pub variation_max: f32, pub first_radius: f32, pub rounds: u32, pub grid_bits: u32, pub reserved: u32,
+}
+/// gsx_model_select_normals, 80 bytes: mode GSX_NORMALS_SELECT_VARIATION (lo <= variation <= hi) or _FACING (lo <= the cosine between
+/// the normal and `dir` <= hi; its absolute value with the flag GSX_NORMALS_ABS)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_normals_select_desc {
+    pub filter: u32, pub flags: u32, pub selection_op: u32, pub mode: u32, pub k: u32, pub orient: u32, pub radius_hint: f32,
+    pub grid_bits: u32, pub max_rounds: u32, pub lo: f32, pub hi: f32, pub reserved: u32, pub dir: [f32; 3], pub toward: [f32; 3],
+    pub reserved2: [u32; 2],
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }

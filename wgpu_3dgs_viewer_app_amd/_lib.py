@@ -61,6 +61,7 @@ EXPORTS = (
     "gsx_visibility_desc_default", "gsx_visibility_select_desc_default", "gsx_model_visibility", "gsx_model_select_visibility",
     "gsx_model_visibility_reset",
     "gsx_depth_map_desc_default", "gsx_render_depth_map", "gsx_depth_map_device_ptrs", "gsx_depth_map_unproject",
+    "gsx_normals_desc_default", "gsx_model_normals", "gsx_model_select_normals",
 )
 
 
@@ -234,6 +235,43 @@ class KnnSelectDesc(C.Structure):
     _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("selection_op", C.c_uint32), ("mode", C.c_uint32), ("k", C.c_uint32),
                 ("score", C.c_uint32), ("radius_hint", C.c_float), ("grid_bits", C.c_uint32), ("max_rounds", C.c_uint32), ("lo", C.c_float),
                 ("hi", C.c_float), ("std_ratio", C.c_float)]
+
+
+#: the smallest and the largest ``k`` of ``gsx_model_normals``
+GSX_NORMALS_MIN_K, GSX_NORMALS_MAX_K = 3, 16
+#: ``gsx_normals_desc.orient``: the first non-zero component positive, or looking at ``toward``
+GSX_NORMALS_ORIENT_CANONICAL, GSX_NORMALS_ORIENT_TOWARD = 0, 1
+#: ``gsx_normals_select_desc.mode``
+GSX_NORMALS_SELECT_VARIATION, GSX_NORMALS_SELECT_FACING = 0, 1
+#: ``gsx_normals_select_desc.flags``: mode FACING tests the absolute cosine
+GSX_NORMALS_ABS = 1
+#: ``gsx_model_normals``: the index of a neighbour that does not exist
+GSX_NORMALS_NONE = 0xFFFFFFFF
+
+
+class NormalsDesc(C.Structure):
+    """``gsx_normals_desc`` (48 bytes): the ``GSX_BOUNDS_*`` filter, flags (0), ``k`` (3..16), the ``GSX_NORMALS_ORIENT_*`` rule and its
+    model-space point ``toward``, and ``gsx_knn_desc``'s three knobs that change no result."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("k", C.c_uint32), ("orient", C.c_uint32), ("radius_hint", C.c_float),
+                ("grid_bits", C.c_uint32), ("max_rounds", C.c_uint32), ("reserved", C.c_uint32), ("toward", C.c_float * 3),
+                ("reserved2", C.c_uint32)]
+
+
+class NormalsStats(C.Structure):
+    """``gsx_normals_stats_t`` (64 bytes): the participants, the non-finite, the fitted Gaussians' number and their variations' double
+    mean, minimum and maximum, and what ran: the first radius, the grid rounds, the Gaussians the exact fallback answered, the table."""
+    _fields_ = [("count", C.c_uint64), ("n_nonfinite", C.c_uint64), ("n_fitted", C.c_uint64), ("n_brute", C.c_uint64), ("mean", C.c_double),
+                ("variation_min", C.c_float), ("variation_max", C.c_float), ("first_radius", C.c_float), ("rounds", C.c_uint32),
+                ("grid_bits", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class NormalsSelectDesc(C.Structure):
+    """``gsx_normals_select_desc`` (80 bytes): the filter, flags (``GSX_NORMALS_ABS``), the ``gsx_selection_op``, the
+    ``GSX_NORMALS_SELECT_*`` mode, ``k``, the orient rule, the three knobs, the range ``[lo, hi]`` of the variation or of the cosine
+    between the normal and ``dir``, and ``toward``."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("selection_op", C.c_uint32), ("mode", C.c_uint32), ("k", C.c_uint32),
+                ("orient", C.c_uint32), ("radius_hint", C.c_float), ("grid_bits", C.c_uint32), ("max_rounds", C.c_uint32), ("lo", C.c_float),
+                ("hi", C.c_float), ("reserved", C.c_uint32), ("dir", C.c_float * 3), ("toward", C.c_float * 3), ("reserved2", C.c_uint32 * 2)]
 
 
 #: ``gsx_model_nearest``: the index of a query without a target in reach
@@ -606,6 +644,10 @@ def load() -> C.CDLL:
         "gsx_knn_desc_default": ([C.POINTER(KnnDesc)], None),
         "gsx_model_knn": ([vp, cp, C.POINTER(KnnDesc), C.c_void_p, C.c_void_p, C.POINTER(KnnStats)], C.c_int32),
         "gsx_model_select_knn": ([vp, cp, C.POINTER(KnnSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(KnnStats)], C.c_int32),
+        "gsx_normals_desc_default": ([C.POINTER(NormalsDesc)], None),
+        "gsx_model_normals": ([vp, cp, C.POINTER(NormalsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NormalsStats)], C.c_int32),
+        "gsx_model_select_normals": ([vp, cp, C.POINTER(NormalsSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(NormalsStats)],
+                                     C.c_int32),
         "gsx_nearest_desc_default": ([C.POINTER(NearestDesc)], None),
         "gsx_model_nearest": ([vp, cp, cp, C.POINTER(NearestDesc), C.c_void_p, C.c_void_p, C.POINTER(NearestStats)], C.c_int32),
         "gsx_model_select_nearest": ([vp, cp, cp, C.POINTER(NearestSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(NearestStats)], C.c_int32),

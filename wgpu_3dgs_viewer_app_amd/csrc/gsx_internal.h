@@ -1186,6 +1186,40 @@ hipError_t launch_knn_brute(hipStream_t s, uint64_t n, const uint4* src, uint32_
 hipError_t launch_knn_stats(hipStream_t s, uint64_t n, const KnnJob& job);   // words[10..13], [16..23]
 hipError_t launch_knn_select(hipStream_t s, uint64_t n, const KnnJob& job);  // selection, words[14..15]
 
+// Model normals (kernels_normals.hip; gsx_model_normals, gsx_model_select_normals): every participant's k nearest by (d2, index)
+// through the same rounds over the grid and the same exact fallback as the nearest neighbours, and a plane fitted to each list where
+// it is proven (normals_math.h).  Its own regions lie behind the grid's.  Its words (kNormalsWords 32-bit words):
+//   [0..1] the entries of list 0 / list 1
+//   [10] n_fitted  [11] variation_min  [12] variation_max (float bits)  [14] hit  [15] selected afterwards  [16] sum  [18] mean (doubles)
+enum : uint32_t {
+    kNormalsList = 0, kNormalsFitted = 10, kNormalsVarMin = 11, kNormalsVarMax = 12, kNormalsHit = 14, kNormalsSelected = 15,
+    kNormalsSum = 16, kNormalsMean = 18, kNormalsWords = 32
+};
+constexpr uint32_t kNormalsPartialWords = 8;  // 32 B a workgroup: count | min | max | - | the double sum
+struct NormalsJob {
+    NeighborJob nb;           // the grid of the round; nb.records holds every participant after any round's scatter
+    uint32_t k, orient;       // 3 .. 16; GSX_NORMALS_ORIENT_*
+    uint32_t mode, flags;     // select: GSX_NORMALS_SELECT_*, GSX_NORMALS_ABS; the selection is nb.sel
+    float toward[3];          // orient TOWARD
+    float dir[3];             // select, mode FACING: the unit direction
+    float lo, hi;             // select
+    const uint4* pc;          // the model's position + colour plane, n elements: the neighbours' positions are gathered from it by index
+    uint32_t* words;          // kNormalsWords words
+    uint32_t* partials;       // extract_groups(n) x kNormalsPartialWords words (the select's partials are nb.partials)
+    float* normals;           // n * 3 floats, 0 before the search
+    float* variation;         // n floats, +inf before the search
+    uint32_t* indices;        // n * k words, GSX_NORMALS_NONE before the search, or nullptr: the indices are not wanted
+    uint4* list[2];           // n records each: the unresolved entries of a round (x, y, z bits, original index), in any order
+    BoxWs box;                // the participants' count, box and trimmed box
+};
+hipError_t launch_normals_fill(hipStream_t s, uint64_t n, const NormalsJob& job);  // normals = 0, variation = +inf, indices = none
+// One grid round: the `count` entries of src (the grid's records, or a list) are fitted or appended to list[to] (words[to] zeroed by the caller).
+hipError_t launch_normals_query(hipStream_t s, uint64_t n, const uint4* src, uint32_t count, uint32_t to, const NormalsJob& job);
+// The exact fallback: one workgroup an entry of src against all `total` records of the grid.
+hipError_t launch_normals_brute(hipStream_t s, uint64_t n, const uint4* src, uint32_t count, uint32_t total, const NormalsJob& job);
+hipError_t launch_normals_stats(hipStream_t s, uint64_t n, const NormalsJob& job);   // words[10..12], [16..19]
+hipError_t launch_normals_select(hipStream_t s, uint64_t n, const NormalsJob& job);  // selection, words[14..15]
+
 // Model nearest across models (kernels_nearest.hip; gsx_model_nearest, gsx_model_select_nearest, gsx_model_align_step): for every
 // Gaussian of a source model, mapped by a 3x4 matrix, the nearest participant of a target model and its index, by rounds over the
 // grid above built over the TARGETS (`nb`, once a round) and an exact fallback (nearest_math.h).  Everything indexed by "n" below is

@@ -378,6 +378,37 @@ def _knn_stats(out, d2, score) -> ModelKnn:
 
 
 @dataclasses.dataclass
+class ModelNormals:
+    """What ``MultiModelViewerModel.normals`` returns.  ``normal`` (float32, ``(n, 3)``): the unit normal of the plane fitted to every
+    Gaussian and its k nearest, ``(0, 0, 0)`` where none is fitted; ``variation`` (float32, one per Gaussian): the smallest
+    eigenvalue's share of the neighbourhood's scatter, 0 on a plane, 1/3 where it is isotropic, ``+inf`` where none is fitted;
+    ``index`` (uint32, ``(n, k)``, or ``None`` without ``indices=True``): the k nearest by (squared distance, index),
+    ``_lib.GSX_NORMALS_NONE`` where there is none; ``count``: participants; ``n_nonfinite``; ``n_fitted``, ``variation_min``,
+    ``variation_max``, ``mean``: over the fitted; ``first_radius``, ``rounds``, ``n_brute``, ``grid_bits``: what the search ran (they
+    may differ with the knobs; nothing else does)."""
+
+    normal: np.ndarray | None
+    variation: np.ndarray | None
+    index: np.ndarray | None
+    count: int
+    n_nonfinite: int
+    n_fitted: int
+    variation_min: np.float32
+    variation_max: np.float32
+    mean: float
+    first_radius: np.float32
+    rounds: int
+    n_brute: int
+    grid_bits: int
+
+
+def _normals_stats(out, normal, variation, index) -> ModelNormals:
+    return ModelNormals(normal, variation, index, int(out.count), int(out.n_nonfinite), int(out.n_fitted), np.float32(out.variation_min),
+                        np.float32(out.variation_max), float(out.mean), np.float32(out.first_radius), int(out.rounds), int(out.n_brute),
+                        int(out.grid_bits))
+
+
+@dataclasses.dataclass
 class ModelNearest:
     """What ``MultiModelViewerModel.nearest`` returns.  ``index`` (uint32, one per Gaussian of this model, or ``None``): the nearest
     participating Gaussian of the target model, ``_lib.GSX_NEAREST_NONE`` where this one does not participate or nothing is in
@@ -711,6 +742,44 @@ class MultiModelViewerModel:
         _lib.check(self._v._L.gsx_model_select_knn(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected),
                                                    C.byref(out)))
         return int(hit.value), int(selected.value), _knn_stats(out, None, None)
+
+    def normals(self, k: int = 8, toward=None, filter: int = 0, radius_hint: float = 0.0, grid_bits: int = 0,  # noqa: A002
+                max_rounds: int = 0, indices: bool = False) -> ModelNormals:
+        """``gsx_model_normals``: a plane fitted in double to every Gaussian and its ``k`` (3..16) nearest (stored positions, model
+        space), among the Gaussians that pass ``filter`` and have a finite position: the plane's unit normal, the surface variation
+        and, with ``indices=True``, who the k nearest are, on the device.  The normal's first non-zero component is positive, or,
+        with ``toward`` (a model-space point), the normal looks at that point.  ``radius_hint``, ``grid_bits`` and ``max_rounds``
+        steer the search and change no result."""
+        n = self.gaussian_buffers.gaussians_buffer.len()
+        desc = _lib.NormalsDesc(int(filter), 0, int(k), _lib.GSX_NORMALS_ORIENT_CANONICAL if toward is None else _lib.GSX_NORMALS_ORIENT_TOWARD,
+                                float(radius_hint), int(grid_bits), int(max_rounds), 0,
+                                (C.c_float * 3)(*([0.0] * 3 if toward is None else [float(x) for x in toward])), 0)
+        normal = np.zeros((n, 3), np.float32)
+        variation = np.full(n, np.inf, np.float32)
+        index = np.full((n, min(max(int(k), 1), _lib.GSX_NORMALS_MAX_K)), _lib.GSX_NORMALS_NONE, np.uint32) if indices else None
+        out = _lib.NormalsStats()
+        _lib.check(self._v._L.gsx_model_normals(self._v._h, self._key.encode(), C.byref(desc), normal.ctypes.data, variation.ctypes.data,
+                                                index.ctypes.data if indices else None, C.byref(out)))
+        return _normals_stats(out, normal, variation, index)
+
+    def select_normals(self, k: int = 8, lo: float = 0.0, hi: float = 0.0, direction=None, absolute: bool = False, toward=None,
+                       op: int = 0, filter: int = 0, radius_hint: float = 0.0, grid_bits: int = 0,  # noqa: A002
+                       max_rounds: int = 0) -> tuple[int, int, ModelNormals]:
+        """``gsx_model_select_normals``: the fitted Gaussians whose variation lies in ``[lo, hi]`` or, with ``direction`` given, whose
+        normal's cosine with it does (its absolute value with ``absolute``) are the hit set; ``op`` (``_lib.GSX_SELECTION_*``) makes
+        it the selection, adds it or removes it, on the device.  The floor: ``select_normals(8, 0.95, 1.0, direction=up,
+        absolute=True)``, then ``bounds(SELECTED)``.  Returns ``(hit, selected, stats)``; the stats carry no arrays."""
+        facing = direction is not None
+        vec = lambda x: (C.c_float * 3)(*([0.0] * 3 if x is None else [float(c) for c in x]))  # noqa: E731
+        desc = _lib.NormalsSelectDesc(int(filter), _lib.GSX_NORMALS_ABS if absolute else 0, int(op),
+                                      _lib.GSX_NORMALS_SELECT_FACING if facing else _lib.GSX_NORMALS_SELECT_VARIATION, int(k),
+                                      _lib.GSX_NORMALS_ORIENT_CANONICAL if toward is None else _lib.GSX_NORMALS_ORIENT_TOWARD,
+                                      float(radius_hint), int(grid_bits), int(max_rounds), float(lo), float(hi), 0, vec(direction), vec(toward),
+                                      (C.c_uint32 * 2)(0, 0))
+        hit, selected, out = C.c_uint64(), C.c_uint64(), _lib.NormalsStats()
+        _lib.check(self._v._L.gsx_model_select_normals(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected),
+                                                       C.byref(out)))
+        return int(hit.value), int(selected.value), _normals_stats(out, None, None, None)
 
     def nearest(self, dst_key: str, xform=None, model_transforms: bool = False, src_filter: int = 0, dst_filter: int = 0,
                 max_distance: float = 0.0, radius_hint: float = 0.0, grid_bits: int = 0, max_rounds: int = 0,
