@@ -1097,6 +1097,68 @@ gsx_status gsx_model_normals(gsx_viewer* v, const char* key, const gsx_normals_d
 gsx_status gsx_model_select_normals(gsx_viewer* v, const char* key, const gsx_normals_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected,
                                     gsx_normals_stats_t* out_stats /* nullable */);
 
+/* ---- point-to-plane registration: a model's normals kept on the device, and one Gauss-Newton step that registers a source model
+ *      onto a target model's kept planes (spec/RENDER_SPEC.md §27 [BUILD-SPEC]; kernels_nearest.hip, csrc/align_plane_math.h).  Two
+ *      captures of one surface are never the same samples: a point-to-point step (gsx_model_align_step) pulls every sample towards
+ *      another sample and crawls; the plane step lets a sample slide along the target's surface and says which motions the pairs
+ *      determine.  The iteration is the caller's loop, as for gsx_model_align_step.
+ *      Kept normals.  gsx_model_normals_keep runs gsx_model_normals' computation (§26: the same desc, the same checks, the same
+ *      kernels) and keeps the 16 bytes a Gaussian it produces — the float32 normal and the variation; (0, 0, 0) and +inf where no
+ *      plane was fitted — resident with the model, as the visibility planes are.  A second keep replaces the first.
+ *      gsx_model_normals_kept reports the plane (present, the k, orient, filter and toward it was made with, the model's count and
+ *      n_fitted) and copies it out (out_normal, out_variation: nullable); without a plane it is GSX_OK with present = 0 and the
+ *      arrays untouched.  gsx_model_normals_reset frees it.  The plane describes the stored positions it was fitted on: an upload, a
+ *      device upload, an import, a transform that moves something and a pod kind change drop it, and it is freed with the model; a
+ *      selection, a mask upload, an edit, a rendered frame, gsx_model_normals / _select_normals and the calls of this section do
+ *      not.  The filter was evaluated when the plane was made: a later selection or mask does not change which Gaussians are fitted.
+ *      Models made by extract, merge, convert and decimate start without one.
+ *      gsx_model_align_plane_step.  The search is desc->nearest, exactly gsx_model_align_step's; out->nearest its statistics.  The
+ *      pairs used are the found pairs (q, t) whose target has a kept, fitted normal n (a finite variation) and, with max_variation >
+ *      0, variation <= max_variation; the other found pairs are counted in n_unfitted.  The sums, in double and in index order,
+ *      products of float32 values and of float32 differences taken in double without contraction: pass 0 the count and sum q, the
+ *      centre c = fl32(sum q / count); pass 1 per pair d = q - c and g = q - t per axis in float32, a = d x n (each component d_u n_v -
+ *      d_v n_u), e = (g_x n_x + g_y n_y) + g_z n_z, J = (a, n): the 21 upper-triangle entries of A = sum J J^T, the 6 of b = sum J e,
+ *      sum e^2 and sum d2; folded from per-workgroup partials in index order: the same bits on every call.  No sum depends on the
+ *      sign of n: the canonical orientation suffices.
+ *      The solve, on the host in double: A's eigenvalues (returned descending) and eigenvectors by cyclic Jacobi; rank = the number
+ *      of eigenvalues above 1e-9 x the largest; x = -sum over those of v (v . b) / lambda: the minimum-norm solution, exactly 0
+ *      along the undetermined directions (a floor against a floor has rank 3: the lift and two tilts).  With x = (omega, tau): quat
+ *      is the rotation by |omega| about omega / |omega| (x, y, z, w; w >= 0; the identity for |omega| = 0), pos = c + tau - R c, and
+ *      xform_next = delta o the matrix used, scale 1, rounded once to float32.  Fewer than 3 pairs used, or rank 0: degenerate = 1,
+ *      the identity delta and xform_next = the matrix used; not an error.  normal_matrix and rhs are returned: A^-1 is the
+ *      registration's uncertainty.  rms_before = sqrt(sum d2 / n_pairs), rms_plane_before = sqrt(sum e^2 / n_pairs).
+ *      Errors: gsx_model_normals' for the keep (GSX_ERR_OOM leaves the model and an older plane as they were) and
+ *      gsx_model_align_step's for the step, for the same conditions; unknown flag bits, a max_variation that is negative or NaN, a
+ *      reserved word != 0, or a dst_key without a kept plane (gsx_model_normals_keep first): GSX_ERR_INVALID_ARG.  No queries or no
+ *      targets: GSX_OK, degenerate, zeros. ---- */
+typedef struct gsx_normals_kept_t {
+    uint32_t present; uint32_t k; uint32_t orient; uint32_t filter; /* 0 / 1; what gsx_model_normals_keep was called with */
+    float toward[3]; uint32_t reserved;
+    uint64_t count; uint64_t n_fitted; /* the model's Gaussians when the plane was made; those with a plane */
+} gsx_normals_kept_t; /* 48 B */
+typedef struct gsx_align_plane_desc {
+    gsx_nearest_desc nearest;
+    uint32_t flags; float max_variation; uint32_t reserved[2]; /* 0; 0: no limit */
+} gsx_align_plane_desc; /* 96 B */
+typedef struct gsx_align_plane_step_t {
+    double pos[3]; double quat[4];   /* the delta: t ~ R(quat) q + pos */
+    double normal_matrix[21];        /* the upper triangle of A, row-major */
+    double rhs[6];                   /* b */
+    double eigenvalues[6];           /* of A, descending */
+    double centre[3];                /* c */
+    double rms_before; double rms_plane_before;
+    uint64_t n_pairs; uint64_t n_unfitted;
+    float xform_next[12];
+    uint32_t rank; uint32_t degenerate;
+    gsx_nearest_stats_t nearest;
+} gsx_align_plane_step_t; /* 568 B */
+gsx_status gsx_model_normals_keep(gsx_viewer* v, const char* key, const gsx_normals_desc* desc, gsx_normals_stats_t* out);
+gsx_status gsx_model_normals_kept(gsx_viewer* v, const char* key, gsx_normals_kept_t* out, float* out_normal /* nullable, n * 3 */,
+                                  float* out_variation /* nullable, n */);
+gsx_status gsx_model_normals_reset(gsx_viewer* v, const char* key);
+gsx_status gsx_model_align_plane_step(gsx_viewer* v, const char* src_key, const char* dst_key, const gsx_align_plane_desc* desc,
+                                      gsx_align_plane_step_t* out);
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

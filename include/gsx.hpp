@@ -398,6 +398,36 @@ struct MultiModelViewerModel {
             for (int k = 0; k < 12; ++k) delta[k] = D[k];
         return out;
     }
+    // gsx_model_normals_keep: normals() whose normals and variations stay on the device with the model (16 bytes a Gaussian), for
+    // align_plane_step; a second keep replaces the first.  An upload, an import, a transform and a pod kind change drop the plane.
+    gsx_normals_stats_t keep_normals(const gsx_normals_desc& desc) {
+        gsx_normals_stats_t out{};
+        check(gsx_model_normals_keep(v_, key_.c_str(), &desc, &out));
+        return out;
+    }
+    // gsx_model_normals_kept: whether a plane is resident and what it was made with; normal (n * 3) and variation (n), both nullable,
+    // receive its contents and stay as they are without a plane.
+    gsx_normals_kept_t kept_normals(std::vector<float>* normal = nullptr, std::vector<float>* variation = nullptr) const {
+        uint64_t n = 0;
+        check(gsx_model_len(v_, key_.c_str(), &n));
+        gsx_normals_kept_t out{};
+        check(gsx_model_normals_kept(v_, key_.c_str(), &out, nullptr, nullptr));
+        if (out.present && (normal || variation)) {
+            if (normal) normal->assign((size_t)n * 3, 0.0f);
+            if (variation) variation->assign((size_t)n, std::numeric_limits<float>::infinity());
+            check(gsx_model_normals_kept(v_, key_.c_str(), &out, normal ? normal->data() : nullptr, variation ? variation->data() : nullptr));
+        }
+        return out;
+    }
+    // gsx_model_normals_reset: frees the kept plane.
+    void reset_normals() { check(gsx_model_normals_reset(v_, key_.c_str())); }
+    // gsx_model_align_plane_step: one Gauss-Newton step of point-to-plane registration of this model onto the model dst_key, which
+    // needs keep_normals first.  The step moves only along what the pairs determine (out.rank of the six motions).
+    gsx_align_plane_step_t align_plane_step(const std::string& dst_key, const gsx_align_plane_desc& desc) const {
+        gsx_align_plane_step_t out{};
+        check(gsx_model_align_plane_step(v_, key_.c_str(), dst_key.c_str(), &desc, &out));
+        return out;
+    }
     // gsx_model_visibility: draws this model ALONE with the viewer's current camera and keeps, per Gaussian and on the device, the
     // peak blending weight T * alpha, the summed weight (2^-24 fixed point, as double) and the pixel count; accumulate folds the
     // view into the planes an earlier call left.  Every output is nullable.  The model goes through preprocess + sort again before

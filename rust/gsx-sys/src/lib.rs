@@ -341,6 +341,27 @@ pub struct gsx_normals_select_desc {
     pub grid_bits: u32, pub max_rounds: u32, pub lo: f32, pub hi: f32, pub reserved: u32, pub dir: [f32; 3], pub toward: [f32; 3],
     pub reserved2: [u32; 2],
 }
+/// gsx_model_normals_kept, 48 bytes: whether the model has kept normals, the k, orient, filter and toward they were made with, the
+/// model's Gaussians then and how many of them have a plane
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_normals_kept_t {
+    pub present: u32, pub k: u32, pub orient: u32, pub filter: u32, pub toward: [f32; 3], pub reserved: u32, pub count: u64, pub n_fitted: u64,
+}
+/// gsx_model_align_plane_step, 96 bytes: the search, flags (0) and the largest variation a target's plane may have (0: no limit)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_align_plane_desc { pub nearest: gsx_nearest_desc, pub flags: u32, pub max_variation: f32, pub reserved: [u32; 2] }
+/// the result of gsx_model_align_plane_step, 568 bytes: the delta t ~ R(quat) q + pos (quat x, y, z, w), the upper triangle of the 6x6
+/// normal matrix over (omega, tau), row-major, its right-hand side, its eigenvalues (descending), the centre, the pairs' rms distance
+/// and rms distance along the normal before the step, the pairs used and left out, xform_next, the rank, degenerate, the search
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_align_plane_step_t {
+    pub pos: [f64; 3], pub quat: [f64; 4], pub normal_matrix: [f64; 21], pub rhs: [f64; 6], pub eigenvalues: [f64; 6], pub centre: [f64; 3],
+    pub rms_before: f64, pub rms_plane_before: f64, pub n_pairs: u64, pub n_unfitted: u64, pub xform_next: [f32; 12], pub rank: u32,
+    pub degenerate: u32, pub nearest: gsx_nearest_stats_t,
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct gsx_query { pub kind: u32, pub selection_op: u32, pub p0: [f32; 2], pub p1: [f32; 2], pub radius: f32, pub reserved: u32 }
@@ -501,6 +522,10 @@ extern "C" {
     pub fn gsx_normals_desc_default(d: *mut gsx_normals_desc);
     pub fn gsx_model_normals(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_normals_desc, out_normal: *mut f32, out_variation: *mut f32, out_index: *mut u32, out: *mut gsx_normals_stats_t) -> gsx_status;
     pub fn gsx_model_select_normals(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_normals_select_desc, out_hit: *mut u64, out_selected: *mut u64, out_stats: *mut gsx_normals_stats_t) -> gsx_status;
+    pub fn gsx_model_normals_keep(v: *mut gsx_viewer, key: *const c_char, desc: *const gsx_normals_desc, out: *mut gsx_normals_stats_t) -> gsx_status;
+    pub fn gsx_model_normals_kept(v: *mut gsx_viewer, key: *const c_char, out: *mut gsx_normals_kept_t, out_normal: *mut f32, out_variation: *mut f32) -> gsx_status;
+    pub fn gsx_model_normals_reset(v: *mut gsx_viewer, key: *const c_char) -> gsx_status;
+    pub fn gsx_model_align_plane_step(v: *mut gsx_viewer, src_key: *const c_char, dst_key: *const c_char, desc: *const gsx_align_plane_desc, out: *mut gsx_align_plane_step_t) -> gsx_status;
     pub fn gsx_gaussian_edit_default(e: *mut gsx_gaussian_edit);
     pub fn gsx_update_query(v: *mut gsx_viewer, q: *const gsx_query) -> gsx_status;
     pub fn gsx_update_query_texture(v: *mut gsx_viewer, texels: *const u8, width: u32, height: u32) -> gsx_status;

@@ -417,6 +417,34 @@ impl MultiModelViewerModel {
         }
         Ok((out, d))
     }
+    /// `gsx_model_normals_keep`: `normals` whose normals and variations stay on the device with the model (16 bytes a Gaussian), for
+    /// `align_plane_step`; a second keep replaces the first.  An upload, an import, a transform and a pod kind change drop the plane.
+    pub fn keep_normals(&mut self, desc: &sys::gsx_normals_desc) -> Result<sys::gsx_normals_stats_t, Error> {
+        let mut out = sys::gsx_normals_stats_t::default();
+        check(unsafe { sys::gsx_model_normals_keep(self.v, self.key.as_ptr(), desc, &mut out) })?;
+        Ok(out)
+    }
+    /// `gsx_model_normals_kept`: whether a plane is resident and what it was made with and, with `rows`, its contents: `n * 3` normals
+    /// and `n` variations (both empty without a plane).
+    pub fn kept_normals(&self, rows: bool) -> Result<(sys::gsx_normals_kept_t, Vec<f32>, Vec<f32>), Error> {
+        let mut out = sys::gsx_normals_kept_t::default();
+        check(unsafe { sys::gsx_model_normals_kept(self.v, self.key.as_ptr(), &mut out, std::ptr::null_mut(), std::ptr::null_mut()) })?;
+        if out.present == 0 || !rows { return Ok((out, Vec::new(), Vec::new())); }
+        let n = out.count as usize;
+        let (mut normal, mut variation) = (vec![0.0f32; n * 3], vec![f32::INFINITY; n]);
+        check(unsafe { sys::gsx_model_normals_kept(self.v, self.key.as_ptr(), &mut out, normal.as_mut_ptr(), variation.as_mut_ptr()) })?;
+        Ok((out, normal, variation))
+    }
+    /// `gsx_model_normals_reset`: frees the kept plane.
+    pub fn reset_normals(&mut self) -> Result<(), Error> { check(unsafe { sys::gsx_model_normals_reset(self.v, self.key.as_ptr()) }) }
+    /// `gsx_model_align_plane_step`: one Gauss-Newton step of point-to-plane registration of this model onto the model `dst_key`, which
+    /// needs `keep_normals` first.  The step moves only along what the pairs determine (`rank` of the six motions).
+    pub fn align_plane_step(&self, dst_key: &str, desc: &sys::gsx_align_plane_desc) -> Result<sys::gsx_align_plane_step_t, Error> {
+        let dst = CString::new(dst_key).unwrap();
+        let mut out = sys::gsx_align_plane_step_t::default();
+        check(unsafe { sys::gsx_model_align_plane_step(self.v, self.key.as_ptr(), dst.as_ptr(), desc, &mut out) })?;
+        Ok(out)
+    }
 }
 
 pub struct Preprocessor(*mut sys::gsx_viewer);

@@ -62,6 +62,7 @@ EXPORTS = (
     "gsx_model_visibility_reset",
     "gsx_depth_map_desc_default", "gsx_render_depth_map", "gsx_depth_map_device_ptrs", "gsx_depth_map_unproject",
     "gsx_normals_desc_default", "gsx_model_normals", "gsx_model_select_normals",
+    "gsx_model_normals_keep", "gsx_model_normals_kept", "gsx_model_normals_reset", "gsx_model_align_plane_step",
 )
 
 
@@ -319,6 +320,28 @@ class AlignStep(C.Structure):
     the matrix used, the pairs, the rms distance before the step, whether the step was degenerate, the search's statistics."""
     _fields_ = [("pos", C.c_double * 3), ("quat", C.c_double * 4), ("scale", C.c_double), ("xform_next", C.c_float * 12), ("n_pairs", C.c_uint64),
                 ("rms_before", C.c_double), ("degenerate", C.c_uint32), ("reserved", C.c_uint32), ("nearest", NearestStats)]
+
+
+class NormalsKept(C.Structure):
+    """``gsx_normals_kept_t`` (48 bytes): whether a model has kept normals, the ``k``, ``orient``, ``filter`` and ``toward`` they were made
+    with, the model's Gaussian count then and how many have a plane."""
+    _fields_ = [("present", C.c_uint32), ("k", C.c_uint32), ("orient", C.c_uint32), ("filter", C.c_uint32), ("toward", C.c_float * 3),
+                ("reserved", C.c_uint32), ("count", C.c_uint64), ("n_fitted", C.c_uint64)]
+
+
+class AlignPlaneDesc(C.Structure):
+    """``gsx_align_plane_desc`` (96 bytes): the search, flags (0) and ``max_variation`` (0: no limit)."""
+    _fields_ = [("nearest", NearestDesc), ("flags", C.c_uint32), ("max_variation", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class AlignPlaneStep(C.Structure):
+    """``gsx_align_plane_step_t`` (568 bytes): the delta ``t ~ R(quat) q + pos``, the upper triangle of the 6x6 normal matrix, its
+    right-hand side, its eigenvalues (descending), the centre, the two rms residuals before the step, the pairs used and left out,
+    ``xform_next``, the rank, whether the step was degenerate, the search's statistics."""
+    _fields_ = [("pos", C.c_double * 3), ("quat", C.c_double * 4), ("normal_matrix", C.c_double * 21), ("rhs", C.c_double * 6),
+                ("eigenvalues", C.c_double * 6), ("centre", C.c_double * 3), ("rms_before", C.c_double), ("rms_plane_before", C.c_double),
+                ("n_pairs", C.c_uint64), ("n_unfitted", C.c_uint64), ("xform_next", C.c_float * 12), ("rank", C.c_uint32),
+                ("degenerate", C.c_uint32), ("nearest", NearestStats)]
 
 
 #: ``gsx_visibility_desc.flags``: fold this view into the model's resident planes instead of replacing them
@@ -648,6 +671,10 @@ def load() -> C.CDLL:
         "gsx_model_normals": ([vp, cp, C.POINTER(NormalsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NormalsStats)], C.c_int32),
         "gsx_model_select_normals": ([vp, cp, C.POINTER(NormalsSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(NormalsStats)],
                                      C.c_int32),
+        "gsx_model_normals_keep": ([vp, cp, C.POINTER(NormalsDesc), C.POINTER(NormalsStats)], C.c_int32),
+        "gsx_model_normals_kept": ([vp, cp, C.POINTER(NormalsKept), C.c_void_p, C.c_void_p], C.c_int32),
+        "gsx_model_normals_reset": ([vp, cp], C.c_int32),
+        "gsx_model_align_plane_step": ([vp, cp, cp, C.POINTER(AlignPlaneDesc), C.POINTER(AlignPlaneStep)], C.c_int32),
         "gsx_nearest_desc_default": ([C.POINTER(NearestDesc)], None),
         "gsx_model_nearest": ([vp, cp, cp, C.POINTER(NearestDesc), C.c_void_p, C.c_void_p, C.POINTER(NearestStats)], C.c_int32),
         "gsx_model_select_nearest": ([vp, cp, cp, C.POINTER(NearestSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(NearestStats)], C.c_int32),

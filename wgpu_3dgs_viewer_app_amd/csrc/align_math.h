@@ -28,7 +28,7 @@ struct AlignDelta {
 };
 
 constexpr double kAlignGap = 1e-9;   // a gap below this share of N's Frobenius norm: the rotation is not determined (collinear pairs)
-constexpr int kAlignSweeps = 64;     // cyclic Jacobi converges quadratically: a 4x4 matrix needs fewer than ten sweeps
+constexpr int kAlignSweeps = 64;     // cyclic Jacobi converges quadratically: a 4x4 or 6x6 matrix needs fewer than ten sweeps
 
 // Horn's N(H), symmetric, row-major, over the quaternion (w, x, y, z).
 inline void align_horn_matrix(const double H[9], double N[16]) {
@@ -40,45 +40,48 @@ inline void align_horn_matrix(const double H[9], double N[16]) {
     for (int k = 0; k < 16; ++k) N[k] = M[k];
 }
 
-// The eigenvalues (w[4]) and eigenvectors (the columns of V, row-major) of the symmetric 4x4 matrix A, by cyclic Jacobi: sweeps over
-// the six pairs until every off-diagonal element is exactly 0 or a sweep changes nothing any more.
-inline void align_jacobi4(const double A_in[16], double w[4], double V[16]) {
-    double A[16];
-    for (int k = 0; k < 16; ++k) {
+// The eigenvalues (w[N]) and eigenvectors (the columns of V, row-major) of the symmetric N x N matrix A, by cyclic Jacobi: sweeps over
+// the pairs (p, q), p < q, until every off-diagonal element is exactly 0 or a sweep changes nothing any more.  The one copy of the
+// rotation: the 4x4 matrix of Horn's solve below and the 6x6 normal matrix of align_plane_math.h both run it.
+template <int N>
+inline void align_jacobi(const double* A_in, double* w, double* V) {
+    double A[N * N];
+    for (int k = 0; k < N * N; ++k) {
         A[k] = A_in[k];
-        V[k] = (k % 5 == 0) ? 1.0 : 0.0;
+        V[k] = (k % (N + 1) == 0) ? 1.0 : 0.0;
     }
     for (int sweep = 0; sweep < kAlignSweeps; ++sweep) {
         double off = 0.0, diag = 0.0;
-        for (int p = 0; p < 4; ++p)
-            for (int q = 0; q < 4; ++q) (p == q ? diag : off) += A[4 * p + q] * A[4 * p + q];
+        for (int p = 0; p < N; ++p)
+            for (int q = 0; q < N; ++q) (p == q ? diag : off) += A[N * p + q] * A[N * p + q];
         if (off == 0.0 || off <= 1e-60 * diag) break;
-        for (int p = 0; p < 3; ++p)
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = A[4 * p + q];
+        for (int p = 0; p < N - 1; ++p)
+            for (int q = p + 1; q < N; ++q) {
+                const double apq = A[N * p + q];
                 if (apq == 0.0) continue;
-                const double theta = (A[4 * q + q] - A[4 * p + p]) / (2.0 * apq);
+                const double theta = (A[N * q + q] - A[N * p + p]) / (2.0 * apq);
                 const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
                 const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < 4; ++k) {  // A <- A J
-                    const double akp = A[4 * k + p], akq = A[4 * k + q];
-                    A[4 * k + p] = c * akp - s * akq;
-                    A[4 * k + q] = s * akp + c * akq;
+                for (int k = 0; k < N; ++k) {  // A <- A J
+                    const double akp = A[N * k + p], akq = A[N * k + q];
+                    A[N * k + p] = c * akp - s * akq;
+                    A[N * k + q] = s * akp + c * akq;
                 }
-                for (int k = 0; k < 4; ++k) {  // A <- J^T A
-                    const double apk = A[4 * p + k], aqk = A[4 * q + k];
-                    A[4 * p + k] = c * apk - s * aqk;
-                    A[4 * q + k] = s * apk + c * aqk;
+                for (int k = 0; k < N; ++k) {  // A <- J^T A
+                    const double apk = A[N * p + k], aqk = A[N * q + k];
+                    A[N * p + k] = c * apk - s * aqk;
+                    A[N * q + k] = s * apk + c * aqk;
                 }
-                for (int k = 0; k < 4; ++k) {  // V <- V J
-                    const double vkp = V[4 * k + p], vkq = V[4 * k + q];
-                    V[4 * k + p] = c * vkp - s * vkq;
-                    V[4 * k + q] = s * vkp + c * vkq;
+                for (int k = 0; k < N; ++k) {  // V <- V J
+                    const double vkp = V[N * k + p], vkq = V[N * k + q];
+                    V[N * k + p] = c * vkp - s * vkq;
+                    V[N * k + q] = s * vkp + c * vkq;
                 }
             }
     }
-    for (int k = 0; k < 4; ++k) w[k] = A[5 * k];
+    for (int k = 0; k < N; ++k) w[k] = A[(N + 1) * k];
 }
+inline void align_jacobi4(const double A_in[16], double w[4], double V[16]) { align_jacobi<4>(A_in, w, V); }
 
 // The rotation matrix of a unit quaternion (x, y, z, w), row-major.
 inline void align_quat_rows(const double q[4], double r[9]) {

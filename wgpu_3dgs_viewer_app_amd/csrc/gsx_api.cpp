@@ -517,6 +517,7 @@ gsx_status gsx_model_upload_range(gsx_viewer* v, const char* key, uint64_t start
     }
     m->tuner.reset();
     drop_visibility(m);
+    drop_normals(m);
     return GSX_OK;
 }
 
@@ -533,6 +534,7 @@ gsx_status gsx_model_upload_pod_device(gsx_viewer* v, const char* key, uint64_t 
     HIPCHK(launch_pack_pod(v->stream, d_pos, d_color, m->has_sh ? d_sh : nullptr, d_cov3d, n, start, m->n, m->pod()));
     m->tuner.reset();
     drop_visibility(m);
+    drop_normals(m);
     return GSX_OK;
 }
 

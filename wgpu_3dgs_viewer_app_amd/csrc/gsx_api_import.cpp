@@ -74,6 +74,7 @@ gsx_status import_rows(gsx_viewer* v, Model* m, uint64_t start, const char* rows
     HIPCHK(e2);
     m->tuner.reset();
     drop_visibility(m);
+    drop_normals(m);
     return GSX_OK;
 }
 

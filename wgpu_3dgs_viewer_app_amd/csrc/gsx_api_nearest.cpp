@@ -1,5 +1,6 @@
 // gsx_api_nearest.cpp — C ABI of the nearest search across models (spec/RENDER_SPEC.md section 23; kernels_nearest.hip):
-// gsx_model_nearest, gsx_model_select_nearest and gsx_model_align_step.  The filters are model_filter's, the grid section 18's
+// gsx_model_nearest, gsx_model_select_nearest and gsx_model_align_step, and section 27's gsx_model_align_plane_step (the solve
+// align_plane_math.h's, its sums and partials behind the workspace below, for that call alone).  The filters are model_filter's, the grid section 18's
 // (neighbors_host.h) over the TARGETS, rebuilt once a round at the round's radius, the rules nearest_math.h's and knn_math.h's, the
 // solve align_math.h's, the workspace the model operations' (v->extract_ws): the grid's regions for the targets, then [the words, 128
 // B | the align sums, 256 B | the partials, 128 B a workgroup of the source | the box, its partials and histogram | the select's
@@ -8,6 +9,7 @@
 // for the unresolved count; the rounds' schedule is radius_search.h's.
 #include "gsx_state.h"
 #include "align_math.h"
+#include "align_plane_math.h"
 #include "nearest_math.h"
 #include "neighbors_host.h"
 #include "radius_search.h"
@@ -18,6 +20,7 @@ namespace {
 
 static_assert(sizeof(gsx_nearest_desc) == 80 && sizeof(gsx_nearest_stats_t) == 136 && sizeof(gsx_nearest_select_desc) == 96, "spec section 23's layouts");
 static_assert(sizeof(gsx_align_desc) == 88 && sizeof(gsx_align_step_t) == 272, "spec section 23's layouts");
+static_assert(sizeof(gsx_align_plane_desc) == 96 && sizeof(gsx_align_plane_step_t) == 568, "spec section 27's layouts");
 static_assert(GSX_NEAREST_NONE == kNearestNone && GSX_NEAREST_MODEL_TRANSFORMS == kNearestModelTransforms, "nearest_math.h restates them");
 static_assert(GSX_NEAREST_SELECT_RANGE == kNearestSelectRange && GSX_NEAREST_SELECT_TRANSFER == kNearestSelectTransfer, "the kernels' modes");
 
@@ -78,9 +81,18 @@ gsx_status nearest_models(gsx_viewer* v, const char* fn, const char* src_key, co
 }
 
 // The workspace (grown if need be: the only step that can fail for memory) and the job of a call; the source has n > 0 Gaussians.
-gsx_status nearest_job(gsx_viewer* v, const Model* src, const Model* dst, const gsx_nearest_desc& d, const float xform[12], NearestJob* job) {
+// plane (nullable): the point-to-plane step's sums and partials, behind everything else and only for that call.
+gsx_status nearest_job(gsx_viewer* v, const Model* src, const Model* dst, const gsx_nearest_desc& d, const float xform[12], NearestJob* job,
+                       AlignPlaneJob* plane = nullptr) {
     const uint32_t bits = d.grid_bits ? d.grid_bits : nb_auto_bits(dst->n);
-    const gsx_status st = place_job(v, job, [&](char* ws, NearestJob* j) { return nearest_ws(ws, src->n, dst->n, bits, j); });
+    const gsx_status st = place_job(v, job, [&](char* ws, NearestJob* j) {
+        WsCursor c{ws, nearest_ws(ws, src->n, dst->n, bits, j)};
+        if (plane) {
+            plane->sums = c.take<double>(8 * kAlignPlaneDoubles);
+            plane->partials = c.take<double>(8 * kAlignPlanePartialDoubles * (size_t)extract_groups(src->n));
+        }
+        return c.at;
+    });
     if (st) return st;
     job->nb.bits = bits;
     job->nb.max_count = kNbMaxCount;
@@ -283,6 +295,70 @@ gsx_status gsx_model_align_step(gsx_viewer* v, const char* src_key, const char* 
     for (int k = 0; k < 4; ++k) out->quat[k] = delta.quat[k];
     out->scale = delta.scale;
     align_compose(delta, xform, out->xform_next);
+    return GSX_OK;
+}
+
+gsx_status gsx_model_align_plane_step(gsx_viewer* v, const char* src_key, const char* dst_key, const gsx_align_plane_desc* desc, gsx_align_plane_step_t* out) {
+    const char* fn = "gsx_model_align_plane_step";
+    if (!v || !src_key || !dst_key || !desc || !out) return fail(GSX_ERR_INVALID_ARG, "%s: null argument", fn);
+    gsx_status st = check_nearest(fn, desc->nearest);
+    if (st) return st;
+    if (desc->flags) return fail(GSX_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x (none are defined)", fn, desc->flags);
+    if (!(desc->max_variation >= 0.0f)) return fail(GSX_ERR_INVALID_ARG, "%s: max_variation %g is negative or NaN (0: no limit)", fn, (double)desc->max_variation);
+    if (desc->reserved[0] != 0u || desc->reserved[1] != 0u)
+        return fail(GSX_ERR_INVALID_ARG, "%s: the reserved words are %u, %u, not 0", fn, desc->reserved[0], desc->reserved[1]);
+    Model *src = nullptr, *dst = nullptr;
+    float xform[12];
+    if ((st = nearest_models(v, fn, src_key, dst_key, desc->nearest, &src, &dst, xform))) return st;
+    if (!dst->normals.p || dst->normals_kept.count != dst->n)
+        return fail(GSX_ERR_INVALID_ARG, "%s: model '%s' has no kept normals (gsx_model_normals_keep first; an upload, an import, a transform or a pod kind change drops them)",
+                    fn, dst_key);
+    *out = gsx_align_plane_step_t{};
+    out->quat[3] = 1.0;
+    out->degenerate = 1u;
+    for (int k = 0; k < 12; ++k) out->xform_next[k] = xform[k];
+    out->nearest = fresh_stats(dst, desc->nearest, xform);
+    const uint64_t n = src->n;
+    if (n == 0) return GSX_OK;
+    NearestJob job;
+    AlignPlaneJob plane{};
+    if ((st = nearest_job(v, src, dst, desc->nearest, xform, &job, &plane))) return st;
+    plane.normals = dst->normals.as<float>();
+    plane.variation = plane.normals + 3 * (size_t)dst->n;
+    plane.max_variation = desc->max_variation;
+    if ((st = run_nearest(v, src, dst, model_filter(src, desc->nearest.src_filter, false), model_filter(dst, desc->nearest.dst_filter, false), job, desc->nearest,
+                          &out->nearest)))
+        return st;
+    HIPCHK(gsx::op::MemsetAsync(plane.sums, 0, 8 * kAlignPlaneDoubles, v->stream));
+    HIPCHK(launch_nearest_align_plane(v->stream, n, extract_planes(src, false).pc, job, plane));
+    HIPCHK(gsx::op::StreamSynchronize(v->stream));
+    uint32_t host[kNearestWords];
+    HIPCHK(gsx::op::Memcpy(host, job.words, sizeof host, hipMemcpyDeviceToHost));
+    read_stats(host, &out->nearest);
+    double a[kAlignPlaneDoubles];
+    HIPCHK(gsx::op::Memcpy(a, plane.sums, sizeof a, hipMemcpyDeviceToHost));
+    AlignPlaneSums sums;
+    sums.n = a[0];
+    for (int k = 0; k < 3; ++k) sums.centre[k] = align_plane_centre(a[1 + k], sums.n);
+    for (uint32_t k = 0; k < kAlignPlaneTri; ++k) sums.A[k] = a[8 + k];
+    for (int k = 0; k < 6; ++k) sums.b[k] = a[29 + k];
+    sums.sum_e2 = a[35];
+    sums.sum_d2 = a[36];
+    out->n_pairs = (uint64_t)sums.n;
+    out->n_unfitted = (uint64_t)a[4];
+    out->rms_before = sums.n > 0.0 ? sqrt(sums.sum_d2 / sums.n) : 0.0;
+    out->rms_plane_before = sums.n > 0.0 ? sqrt(sums.sum_e2 / sums.n) : 0.0;
+    for (uint32_t k = 0; k < kAlignPlaneTri; ++k) out->normal_matrix[k] = sums.A[k];
+    for (int k = 0; k < 6; ++k) out->rhs[k] = sums.b[k];
+    const AlignPlaneDelta d = align_plane_solve(sums);
+    for (int k = 0; k < 6; ++k) out->eigenvalues[k] = d.eigenvalues[k];
+    for (int k = 0; k < 3; ++k) out->centre[k] = d.centre[k];
+    out->rank = d.rank;
+    out->degenerate = d.delta.degenerate ? 1u : 0u;
+    if (d.delta.degenerate) return GSX_OK;  // (the identity and xform_next = xform are in place)
+    for (int k = 0; k < 3; ++k) out->pos[k] = d.delta.pos[k];
+    for (int k = 0; k < 4; ++k) out->quat[k] = d.delta.quat[k];
+    align_compose(d.delta, xform, out->xform_next);
     return GSX_OK;
 }
 

@@ -1,5 +1,5 @@
 // gsx_api_normals.cpp — C ABI of the model normals (spec/RENDER_SPEC.md section 26; kernels_normals.hip): gsx_model_normals and
-// gsx_model_select_normals.  The filter is model_filter's, the grid section 18's (neighbors_host.h), rebuilt once a round at the
+// gsx_model_select_normals, and of section 27's kept normals: gsx_model_normals_keep, _kept and _reset (Model::normals).  The filter is model_filter's, the grid section 18's (neighbors_host.h), rebuilt once a round at the
 // round's radius, the rules normals_math.h's, the workspace the model operations' (v->extract_ws): the grid's regions, then [the
 // normals' words, 128 B | its partials, 32 B a workgroup | the box, its partials and histogram | the normals, 12 B a Gaussian | the
 // variations, 4 B a Gaussian | two lists, 16 B a Gaussian each | the indices, 4 k B a Gaussian, only when the caller wants them].  The
@@ -15,6 +15,7 @@ using namespace gsx;
 namespace {
 
 static_assert(sizeof(gsx_normals_desc) == 48 && sizeof(gsx_normals_stats_t) == 64 && sizeof(gsx_normals_select_desc) == 80, "spec section 26's layouts");
+static_assert(sizeof(gsx_normals_kept_t) == 48, "spec section 27's layout");
 static_assert(GSX_NORMALS_MIN_K == kNormalsMinK && GSX_NORMALS_MAX_K == kNormalsMaxK && GSX_NORMALS_MAX_K == kKnnMaxK, "normals_math.h restates the bounds on k");
 static_assert(GSX_NORMALS_ORIENT_CANONICAL == kNormalsOrientCanonical && GSX_NORMALS_ORIENT_TOWARD == kNormalsOrientToward, "the kernels' orients");
 static_assert(GSX_NORMALS_SELECT_VARIATION == kNormalsSelectVariation && GSX_NORMALS_SELECT_FACING == kNormalsSelectFacing, "the kernels' modes");
@@ -102,6 +103,65 @@ void read_stats(const uint32_t* w, gsx_normals_stats_t* stats) {
     __builtin_memcpy(&stats->mean, w + kNormalsMean, 8);
 }
 
+// the model takes the fresh plane; the older one, if any, is freed with `fresh`
+void adopt_normals(Model* m, DevBuf& fresh, const gsx_normals_kept_t& kept) {
+    std::swap(m->normals.p, fresh.p);
+    std::swap(m->normals.bytes, fresh.bytes);
+    std::swap(m->normals.borrowed, fresh.borrowed);
+    m->normals_kept = kept;
+}
+
+// gsx_model_normals and gsx_model_normals_keep: one computation.  keep: the normals and the variations stay with the model, in a buffer
+// allocated before anything runs and put in the older plane's place only when the stream has reached its end.
+gsx_status normals_call(gsx_viewer* v, const char* fn, const char* key, const gsx_normals_desc* desc, float* out_normal, float* out_variation, uint32_t* out_index,
+                        gsx_normals_stats_t* out, bool keep) {
+    if (!v || !key || !desc || !out) return fail(GSX_ERR_INVALID_ARG, "%s: null argument", fn);
+    if (desc->flags) return fail(GSX_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x (none are defined)", fn, desc->flags);
+    gsx_status st = check_normals(fn, desc->filter, desc->k, desc->orient, desc->toward, desc->radius_hint, desc->grid_bits, desc->max_rounds);
+    if (st) return st;
+    if (desc->reserved != 0u || desc->reserved2 != 0u) return fail(GSX_ERR_INVALID_ARG, "%s: the reserved words are %u, %u, not 0", fn, desc->reserved, desc->reserved2);
+    Model* m = nullptr;
+    if ((st = neighbor_model(v, fn, key, &m))) return st;
+    *out = gsx_normals_stats_t{};
+    out->grid_bits = desc->grid_bits ? desc->grid_bits : nb_auto_bits(m->n);
+    const uint64_t n = m->n;
+    gsx_normals_kept_t kept{};
+    kept.present = 1u;
+    kept.k = desc->k;
+    kept.orient = desc->orient;
+    kept.filter = desc->filter;
+    for (int a = 0; a < 3; ++a) kept.toward[a] = desc->orient == kNormalsOrientToward ? desc->toward[a] : 0.0f;
+    kept.count = n;
+    DevBuf fresh;
+    if (n == 0) {
+        if (keep) {
+            HIPCHK(fresh.ensure(16));
+            adopt_normals(m, fresh, kept);
+        }
+        return GSX_OK;
+    }
+    NormalsJob job;
+    if ((st = normals_job(v, m, desc->k, desc->orient, desc->toward, desc->grid_bits, out_index != nullptr, &job))) return st;
+    if (keep) HIPCHK(fresh.ensure(16 * (size_t)n));
+    if ((st = run_normals(v, m, model_filter(m, desc->filter, false), job, desc->radius_hint, desc->max_rounds, out))) return st;
+    if (keep) {
+        HIPCHK(gsx::op::MemcpyAsync(fresh.p, job.normals, 12 * (size_t)n, hipMemcpyDeviceToDevice, v->stream));
+        HIPCHK(gsx::op::MemcpyAsync(fresh.as<float>() + 3 * (size_t)n, job.variation, 4 * (size_t)n, hipMemcpyDeviceToDevice, v->stream));
+    }
+    HIPCHK(gsx::op::StreamSynchronize(v->stream));
+    uint32_t host[kNormalsWords];
+    HIPCHK(gsx::op::Memcpy(host, job.words, sizeof host, hipMemcpyDeviceToHost));
+    read_stats(host, out);
+    if (out_normal) HIPCHK(gsx::op::Memcpy(out_normal, job.normals, 12 * (size_t)n, hipMemcpyDeviceToHost));
+    if (out_variation) HIPCHK(gsx::op::Memcpy(out_variation, job.variation, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    if (out_index) HIPCHK(gsx::op::Memcpy(out_index, job.indices, 4 * (size_t)n * desc->k, hipMemcpyDeviceToHost));
+    if (keep) {
+        kept.n_fitted = out->n_fitted;
+        adopt_normals(m, fresh, kept);
+    }
+    return GSX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -115,28 +175,35 @@ void gsx_normals_desc_default(gsx_normals_desc* d) {
 
 gsx_status gsx_model_normals(gsx_viewer* v, const char* key, const gsx_normals_desc* desc, float* out_normal, float* out_variation, uint32_t* out_index,
                              gsx_normals_stats_t* out) {
-    if (!v || !key || !desc || !out) return fail(GSX_ERR_INVALID_ARG, "gsx_model_normals: null argument");
-    if (desc->flags) return fail(GSX_ERR_INVALID_ARG, "gsx_model_normals: unknown flag bits 0x%x (none are defined)", desc->flags);
-    gsx_status st = check_normals("gsx_model_normals", desc->filter, desc->k, desc->orient, desc->toward, desc->radius_hint, desc->grid_bits, desc->max_rounds);
-    if (st) return st;
-    if (desc->reserved != 0u || desc->reserved2 != 0u)
-        return fail(GSX_ERR_INVALID_ARG, "gsx_model_normals: the reserved words are %u, %u, not 0", desc->reserved, desc->reserved2);
+    return normals_call(v, "gsx_model_normals", key, desc, out_normal, out_variation, out_index, out, false);
+}
+
+gsx_status gsx_model_normals_keep(gsx_viewer* v, const char* key, const gsx_normals_desc* desc, gsx_normals_stats_t* out) {
+    return normals_call(v, "gsx_model_normals_keep", key, desc, nullptr, nullptr, nullptr, out, true);
+}
+
+gsx_status gsx_model_normals_kept(gsx_viewer* v, const char* key, gsx_normals_kept_t* out, float* out_normal, float* out_variation) {
+    if (!v || !key || !out) return fail(GSX_ERR_INVALID_ARG, "gsx_model_normals_kept: null argument");
     Model* m = nullptr;
-    if ((st = neighbor_model(v, "gsx_model_normals", key, &m))) return st;
-    *out = gsx_normals_stats_t{};
-    out->grid_bits = desc->grid_bits ? desc->grid_bits : nb_auto_bits(m->n);
-    const uint64_t n = m->n;
+    const gsx_status st = neighbor_model(v, "gsx_model_normals_kept", key, &m);
+    if (st) return st;
+    *out = m->normals_kept;  // (zeros without a plane)
+    if (!m->normals.p) return GSX_OK;
+    const size_t n = (size_t)m->normals_kept.count;
     if (n == 0) return GSX_OK;
-    NormalsJob job;
-    if ((st = normals_job(v, m, desc->k, desc->orient, desc->toward, desc->grid_bits, out_index != nullptr, &job))) return st;
-    if ((st = run_normals(v, m, model_filter(m, desc->filter, false), job, desc->radius_hint, desc->max_rounds, out))) return st;
     HIPCHK(gsx::op::StreamSynchronize(v->stream));
-    uint32_t host[kNormalsWords];
-    HIPCHK(gsx::op::Memcpy(host, job.words, sizeof host, hipMemcpyDeviceToHost));
-    read_stats(host, out);
-    if (out_normal) HIPCHK(gsx::op::Memcpy(out_normal, job.normals, 12 * (size_t)n, hipMemcpyDeviceToHost));
-    if (out_variation) HIPCHK(gsx::op::Memcpy(out_variation, job.variation, 4 * (size_t)n, hipMemcpyDeviceToHost));
-    if (out_index) HIPCHK(gsx::op::Memcpy(out_index, job.indices, 4 * (size_t)n * desc->k, hipMemcpyDeviceToHost));
+    if (out_normal) HIPCHK(gsx::op::Memcpy(out_normal, m->normals.p, 12 * n, hipMemcpyDeviceToHost));
+    if (out_variation) HIPCHK(gsx::op::Memcpy(out_variation, m->normals.as<float>() + 3 * n, 4 * n, hipMemcpyDeviceToHost));
+    return GSX_OK;
+}
+
+gsx_status gsx_model_normals_reset(gsx_viewer* v, const char* key) {
+    if (!v || !key) return fail(GSX_ERR_INVALID_ARG, "gsx_model_normals_reset: null argument");
+    Model* m = nullptr;
+    const gsx_status st = neighbor_model(v, "gsx_model_normals_reset", key, &m);
+    if (st) return st;
+    HIPCHK(gsx::op::StreamSynchronize(v->stream));  // (nothing enqueued reads the plane any more)
+    drop_normals(m);
     return GSX_OK;
 }
 

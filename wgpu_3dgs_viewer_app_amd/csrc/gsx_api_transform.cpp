@@ -57,6 +57,7 @@ gsx_status gsx_model_apply_transform(gsx_viewer* v, const char* key, const gsx_t
     m->tuner.reset();
     m->mask_program_hash = 0;
     drop_visibility(m);  // (the planes were measured on the old pod planes; hipFree waits for the kernel above)
+    drop_normals(m);
     return GSX_OK;
 }
 

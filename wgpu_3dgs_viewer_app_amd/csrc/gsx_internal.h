@@ -1264,6 +1264,20 @@ hipError_t launch_nearest_stats(hipStream_t s, uint64_t n, const NearestJob& job
 hipError_t launch_nearest_transfer(hipStream_t s, uint64_t n, const NearestJob& job);  // transfer
 hipError_t launch_nearest_select(hipStream_t s, uint64_t n, const NearestJob& job);    // the source's selection, words[6..7]
 hipError_t launch_nearest_align(hipStream_t s, uint64_t n, const uint4* pc, const NearestJob& job);  // align (both passes)
+// The point-to-plane step's sums (gsx_model_align_plane_step; spec section 27; align_plane_math.h) over the found pairs whose target
+// has a kept, fitted normal (variation finite and, with max_variation > 0, at most that).  Its regions are its own, sized only when
+// that call runs: `sums` (kAlignPlaneDoubles doubles):
+//   [0] pairs used [1..3] sum q [4] found pairs left out | [8..28] A's upper triangle, row-major [29..34] b [35] sum e^2 [36] sum d2.
+constexpr uint32_t kAlignPlanePartialDoubles = 32;  // 256 B a workgroup: pass 0 uses 5, pass 1 29
+constexpr uint32_t kAlignPlaneDoubles = 40;
+struct AlignPlaneJob {
+    const float* normals;     // the TARGETS' kept plane: n_dst * 3 floats, then
+    const float* variation;   // n_dst floats, +inf where no plane was fitted
+    float max_variation;      // 0: no limit
+    double* partials;         // extract_groups(n) x kAlignPlanePartialDoubles doubles
+    double* sums;             // kAlignPlaneDoubles doubles
+};
+hipError_t launch_nearest_align_plane(hipStream_t s, uint64_t n, const uint4* pc, const NearestJob& job, const AlignPlaneJob& plane);  // sums (both passes)
 
 // Model decimate (kernels_decimate.hip; gsx_model_decimate, gsx_model_decimate_edge): the Gaussians that share a cell of the grid
 // above (launch_neighbors_reduce / _cell / _scan / _scatter on `nb`, the cell edge given instead of a radius) become one

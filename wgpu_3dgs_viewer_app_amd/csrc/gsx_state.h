@@ -256,6 +256,10 @@ struct Model {
     // views were folded into them.  Dropped (drop_visibility) by every call that rewrites the pod planes or the count
     DevBuf vis;
     uint32_t vis_views = 0;
+    // gsx_model_normals_keep (gsx_api_normals.cpp; spec section 27): the resident normals, 16 bytes a Gaussian in one buffer
+    // [normal, n x 3 floats | variation, n floats], and what they were made with.  Dropped (drop_normals) where the visibility planes are
+    DevBuf normals;
+    gsx_normals_kept_t normals_kept{};
     bool pack_list = false, pack_travellers = false;  // how the last pack_count addressed the records / whether it left travellers to shade   // gsx_shard_repair_count has left masks / table / travellers for the repair pack
 
     ~Model() {
@@ -758,6 +762,11 @@ inline ModelFilter model_filter(const Model* m, uint32_t filter_bits, bool inver
 inline void drop_visibility(Model* m) {
     m->vis.release();
     m->vis_views = 0;
+}
+// the kept normals describe the stored positions they were fitted on: dropped beside every drop_visibility but the visibility reset's
+inline void drop_normals(Model* m) {
+    m->normals.release();
+    m->normals_kept = gsx_normals_kept_t{};
 }
 // the copy stream and the events of the row staging buffers, created on first use (gsx_api_export.cpp)
 gsx_status row_streams(gsx_viewer* v);

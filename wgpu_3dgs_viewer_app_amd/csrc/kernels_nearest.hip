@@ -1,5 +1,5 @@
 // kernels_nearest.hip — the nearest search across models for gfx950 (spec/RENDER_SPEC.md §23, "Model nearest (across models)"):
-// gsx_model_nearest, gsx_model_select_nearest and gsx_model_align_step.  The grid is section 18's, built over the TARGETS
+// gsx_model_nearest, gsx_model_select_nearest, gsx_model_align_step and §27's gsx_model_align_plane_step.  The grid is section 18's, built over the TARGETS
 // (kernels_neighbors.hip, once a round); the rules are nearest_math.h's and knn_math.h's, the rounds' schedule radius_search.h's (called
 // by gsx_api_nearest.cpp).  The queries are the SOURCE's Gaussians,
 // mapped by a 3x4 matrix: they are no members of the grid and may lie outside its box (neighbors_math.h: nb_cell_signed).  "n" is
@@ -21,7 +21,9 @@
 //   k_nearest_transfer  the queries whose target is selected, as bits, before the select writes (source and targets may be one model);
 //   k_nearest_select    k_knn_select's shape with the two hit rules;
 //   k_nearest_align     index order, twice: the pairs' count and the sums of q and t, then about the float32 means the products of
-//                       the float32 differences, taken and summed in double; partials and finish as the statistics'.
+//                       the float32 differences, taken and summed in double; partials and finish as the statistics';
+//   k_nearest_align_plane  gsx_model_align_plane_step (spec §27): the same two passes over the found pairs whose target has a kept,
+//                       fitted normal: the 6x6 normal matrix, its right-hand side and the two residual sums, with partials of its own.
 // Every loop is bounded by n, 27, a bucket's or a list's length; no lane waits for another's progress; no kernel caps its grid.
 // Built with -ffp-contract=off.  Bounds: a source index is checked against n before a store by it, a target index against the
 // targets' length before a load by it, a list slot against n (a list's capacity), a bucket's end against the target count.
@@ -47,19 +49,27 @@ __device__ inline NearestStatsPartial nearest_combine_stats(uint32_t count, floa
                           return NearestStatsPartial{a.count + b.count, fminf(a.mn, b.mn), fmaxf(a.mx, b.mx), a.sum + b.sum, a.sum2 + b.sum2};
                       });
 }
-constexpr uint32_t kAlignTerms = 12;  // pass 0 uses 7 of them: n, sum q, sum t; pass 1 all: H, the two spreads, sum d2
-struct AlignPartial {
-    double v[kAlignTerms];
+// T double sums a lane, folded over the wave and then over the workgroup's four waves in a fixed order
+template <uint32_t T>
+struct DoubleTerms {
+    double v[T];
 };
-__device__ inline AlignPartial nearest_combine_align(AlignPartial p) {
+template <uint32_t T>
+__device__ inline DoubleTerms<T> combine_terms(DoubleTerms<T> p) {
 #pragma unroll
-    for (uint32_t k = 0; k < kAlignTerms; ++k) p.v[k] = wave_sum(p.v[k]);
-    return group_fold(p, [](AlignPartial a, const AlignPartial& b) {
+    for (uint32_t k = 0; k < T; ++k) p.v[k] = wave_sum(p.v[k]);
+    return group_fold(p, [](DoubleTerms<T> a, const DoubleTerms<T>& b) {
 #pragma unroll
-        for (uint32_t k = 0; k < kAlignTerms; ++k) a.v[k] += b.v[k];
+        for (uint32_t k = 0; k < T; ++k) a.v[k] += b.v[k];
         return a;
     });
 }
+constexpr uint32_t kAlignTerms = 12;  // pass 0 uses 7 of them: n, sum q, sum t; pass 1 all: H, the two spreads, sum d2
+using AlignPartial = DoubleTerms<kAlignTerms>;
+__device__ inline AlignPartial nearest_combine_align(AlignPartial p) { return combine_terms(p); }
+constexpr uint32_t kAlignPlaneTerms = 29;  // pass 0 uses 5 of them: pairs, sum q, left out; pass 1 all: A (21), b (6), sum e^2, sum d2
+using AlignPlanePartial = DoubleTerms<kAlignPlaneTerms>;
+static_assert(kAlignPlaneTerms <= kAlignPlanePartialDoubles && 8u + kAlignPlaneTerms <= kAlignPlaneDoubles, "the partials and the sums hold every term");
 // the mapped position of a stored one
 __device__ inline void nearest_map(const NearestJob& job, const uint4& e, float& qx, float& qy, float& qz) {
     const float x = __uint_as_float(e.x), y = __uint_as_float(e.y), z = __uint_as_float(e.z);
@@ -327,6 +337,94 @@ __global__ __launch_bounds__(256) void k_nearest_align_finish(uint32_t pass, uin
     for (uint32_t k = 0; k < terms; ++k) out[k] = p.v[k];
 }
 
+// The point-to-plane step's sums (spec section 27; align_plane_math.h), k_nearest_align's shape over the found pairs whose target has a
+// kept, fitted normal n within the variation limit.  pass 0: the used pairs' count, the sum of q, and the found pairs left out;
+// pass 1: about the centre c of pass 0 rounded to float32, d = q - c and g = q - t in float32, and in double a = d x n, e = g . n,
+// J = (a, n): the upper triangle of sum J J^T, sum J e, sum e^2 and the sum of d2.  Nothing changes with the sign of n.
+__global__ __launch_bounds__(256) void k_nearest_align_plane(uint64_t n, uint32_t pass, const uint4* __restrict__ pc, NearestJob job, AlignPlaneJob plane) {
+    const uint32_t t = threadIdx.x;
+    const uint64_t base = (uint64_t)blockIdx.x * kExtractGroup;
+    float c[3] = {0.0f, 0.0f, 0.0f};
+    if (pass) {
+        const double pairs = plane.sums[0];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) c[a] = pairs > 0.0 ? (float)(plane.sums[1 + a] / pairs) : 0.0f;
+    }
+    AlignPlanePartial p;
+#pragma unroll
+    for (uint32_t k = 0; k < kAlignPlaneTerms; ++k) p.v[k] = 0.0;
+#pragma unroll 1
+    for (uint32_t k = 0; k < 4u; ++k) {
+        const uint64_t i = base + k * 256u + t;
+        if (i >= n) break;
+        const uint32_t target = job.out_index[i];
+        if (target == kNearestNone || target >= job.n_dst) continue;
+        const float variation = plane.variation[target];
+        if (!(variation < kNearestInf) || (plane.max_variation > 0.0f && !(variation <= plane.max_variation))) {  // (unfitted: +inf)
+            if (pass == 0u) p.v[4] += 1.0;
+            continue;
+        }
+        float q[3];
+        nearest_map(job, pc[i], q[0], q[1], q[2]);
+        if (pass == 0u) {
+            p.v[0] += 1.0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) p.v[1 + a] += (double)q[a];
+            continue;
+        }
+        const uint4 e4 = job.dst_pc[target];
+        const float tt[3] = {__uint_as_float(e4.x), __uint_as_float(e4.y), __uint_as_float(e4.z)};
+        const float* nn = plane.normals + 3u * (size_t)target;
+        double d[3], g[3], J[6];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            d[a] = (double)(q[a] - c[a]);
+            g[a] = (double)(q[a] - tt[a]);
+            J[3 + a] = (double)nn[a];
+        }
+        J[0] = d[1] * J[5] - d[2] * J[4];
+        J[1] = d[2] * J[3] - d[0] * J[5];
+        J[2] = d[0] * J[4] - d[1] * J[3];
+        const double e = (g[0] * J[3] + g[1] * J[4]) + g[2] * J[5];
+        uint32_t at = 0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+#pragma unroll
+            for (int col = r; col < 6; ++col) p.v[at++] += J[r] * J[col];
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) p.v[21 + r] += J[r] * e;
+        p.v[27] += e * e;
+        p.v[28] += (double)job.out_d2[i];
+    }
+    p = combine_terms(p);
+    if (t == 0u) {
+        double* out = plane.partials + (size_t)blockIdx.x * kAlignPlanePartialDoubles;
+#pragma unroll
+        for (uint32_t k = 0; k < kAlignPlaneTerms; ++k) out[k] = p.v[k];
+    }
+}
+
+// One workgroup: the partials in index order.
+__global__ __launch_bounds__(256) void k_nearest_align_plane_finish(uint32_t pass, uint32_t n_partials, AlignPlaneJob plane) {
+    const uint32_t t = threadIdx.x;
+    AlignPlanePartial p;
+#pragma unroll
+    for (uint32_t k = 0; k < kAlignPlaneTerms; ++k) p.v[k] = 0.0;
+    for (uint32_t j = t; j < n_partials; j += 256u) {
+        const double* in = plane.partials + (size_t)j * kAlignPlanePartialDoubles;
+#pragma unroll
+        for (uint32_t k = 0; k < kAlignPlaneTerms; ++k) p.v[k] += in[k];
+    }
+    p = combine_terms(p);
+    if (t != 0u) return;
+    double* out = plane.sums + (pass ? 8u : 0u);  // pass 0: [0..4]; pass 1: [8..36]
+    const uint32_t terms = pass ? kAlignPlaneTerms : 5u;
+#pragma unroll
+    for (uint32_t k = 0; k < kAlignPlaneTerms; ++k)  // (unrolled: the terms stay in registers)
+        if (k < terms) out[k] = p.v[k];
+}
+
 hipError_t launch_nearest_map(hipStream_t s, uint64_t n, const ModelFilter& f, const uint4* pc, const NearestJob& job) {
     GSX_LAUNCH(k_nearest_map, dim3((uint32_t)extract_groups(n)), dim3(256), 0, s, n, f, pc, job);
     return hipGetLastError();
@@ -359,6 +457,15 @@ hipError_t launch_nearest_align(hipStream_t s, uint64_t n, const uint4* pc, cons
     for (uint32_t pass = 0; pass < 2u; ++pass) {
         GSX_LAUNCH(k_nearest_align, dim3(groups), dim3(256), 0, s, n, pass, pc, job);
         GSX_LAUNCH(k_nearest_align_finish, dim3(1), dim3(256), 0, s, pass, groups, job);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_nearest_align_plane(hipStream_t s, uint64_t n, const uint4* pc, const NearestJob& job, const AlignPlaneJob& plane) {
+    const uint32_t groups = (uint32_t)extract_groups(n);
+    for (uint32_t pass = 0; pass < 2u; ++pass) {
+        GSX_LAUNCH(k_nearest_align_plane, dim3(groups), dim3(256), 0, s, n, pass, pc, job, plane);
+        GSX_LAUNCH(k_nearest_align_plane_finish, dim3(1), dim3(256), 0, s, pass, groups, plane);
     }
     return hipGetLastError();
 }

@@ -465,6 +465,54 @@ class ModelAlignStep:
     nearest: ModelNearest
 
 
+@dataclasses.dataclass
+class ModelNormalsKept:
+    """What ``MultiModelViewerModel.kept_normals`` returns: ``present``; the ``k``, ``orient`` (``_lib.GSX_NORMALS_ORIENT_*``),
+    ``filter`` and ``toward`` the plane was made with; ``count``: the model's Gaussians then; ``n_fitted``; ``normal`` (float32,
+    ``(n, 3)``) and ``variation`` (float32, ``n``): the resident plane's contents, ``None`` without a plane or with ``rows=False``."""
+
+    present: bool
+    k: int
+    orient: int
+    filter: int
+    toward: np.ndarray
+    count: int
+    n_fitted: int
+    normal: np.ndarray | None
+    variation: np.ndarray | None
+
+
+@dataclasses.dataclass
+class ModelAlignPlaneStep:
+    """What ``MultiModelViewerModel.align_plane_step`` returns: the delta ``t ~ R(quat) q + pos`` in the target's model space (``quat``
+    x, y, z, w with w >= 0; float64); ``normal_matrix`` (float64, 21: the upper triangle of the 6x6 ``A = sum J J^T`` over
+    ``(omega, tau)``, row-major), ``rhs`` (``b``), ``eigenvalues`` (descending), ``centre``; ``rms_before`` and ``rms_plane_before``: the
+    used pairs' rms distance and rms distance along the target's normal before the step; ``n_pairs`` used and ``n_unfitted`` left
+    out; ``xform_next`` (float32, ``(3, 4)``); ``rank``: how many of the six motions the pairs determine; ``degenerate``; ``nearest``:
+    the search's statistics, without arrays.  ``matrix()`` is ``A`` in full."""
+
+    pos: np.ndarray
+    quat: np.ndarray
+    normal_matrix: np.ndarray
+    rhs: np.ndarray
+    eigenvalues: np.ndarray
+    centre: np.ndarray
+    rms_before: float
+    rms_plane_before: float
+    n_pairs: int
+    n_unfitted: int
+    xform_next: np.ndarray
+    rank: int
+    degenerate: bool
+    nearest: ModelNearest
+    scale: float = 1.0
+
+    def matrix(self) -> np.ndarray:
+        A = np.zeros((6, 6))
+        A[np.triu_indices(6)] = self.normal_matrix
+        return A + np.triu(A, 1).T
+
+
 def _compose34(a, b):
     """a o b of two 3x4 similarities, in float64"""
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
@@ -826,21 +874,72 @@ class MultiModelViewerModel:
         return ModelAlignStep(np.array(out.pos[:], np.float64), np.array(out.quat[:], np.float64), float(out.scale), vec(out.xform_next).reshape(3, 4), int(out.n_pairs),
                               float(out.rms_before), bool(out.degenerate), _nearest_stats(out.nearest, None, None))
 
-    def align(self, dst_key: str, max_iters: int = 30, tol: float = 1e-6, xform=None, model_transforms: bool = False, **step_args):
+    def keep_normals(self, k: int = 8, toward=None, filter: int = 0, radius_hint: float = 0.0, grid_bits: int = 0,  # noqa: A002
+                     max_rounds: int = 0) -> ModelNormals:
+        """``gsx_model_normals_keep``: ``normals`` with the same arguments, whose normals and variations stay on the device with the
+        model (16 bytes a Gaussian) for ``align_plane_step``; a second keep replaces the first.  An upload, an import, a transform
+        and a pod kind change drop the plane; a selection, a mask, an edit and a frame do not.  Returns the statistics, no arrays."""
+        desc = _lib.NormalsDesc(int(filter), 0, int(k), _lib.GSX_NORMALS_ORIENT_CANONICAL if toward is None else _lib.GSX_NORMALS_ORIENT_TOWARD,
+                                float(radius_hint), int(grid_bits), int(max_rounds), 0,
+                                (C.c_float * 3)(*([0.0] * 3 if toward is None else [float(x) for x in toward])), 0)
+        out = _lib.NormalsStats()
+        _lib.check(self._v._L.gsx_model_normals_keep(self._v._h, self._key.encode(), C.byref(desc), C.byref(out)))
+        return _normals_stats(out, None, None, None)
+
+    def kept_normals(self, rows: bool = True) -> ModelNormalsKept:
+        """``gsx_model_normals_kept``: whether a plane is resident, what it was made with and (``rows``) its contents."""
+        n = self.gaussian_buffers.gaussians_buffer.len()
+        normal = np.zeros((n, 3), np.float32) if rows else None
+        variation = np.full(n, np.inf, np.float32) if rows else None
+        out = _lib.NormalsKept()
+        _lib.check(self._v._L.gsx_model_normals_kept(self._v._h, self._key.encode(), C.byref(out), normal.ctypes.data if rows else None,
+                                                     variation.ctypes.data if rows else None))
+        present = bool(out.present)
+        return ModelNormalsKept(present, int(out.k), int(out.orient), int(out.filter), np.array(out.toward[:], np.float32), int(out.count),
+                                int(out.n_fitted), normal if present else None, variation if present else None)
+
+    def reset_normals(self) -> None:
+        """``gsx_model_normals_reset``: frees the kept plane."""
+        _lib.check(self._v._L.gsx_model_normals_reset(self._v._h, self._key.encode()))
+
+    def align_plane_step(self, dst_key: str, xform=None, model_transforms: bool = False, max_variation: float = 0.0, src_filter: int = 0,
+                         dst_filter: int = 0, max_distance: float = 0.0, radius_hint: float = 0.0, grid_bits: int = 0,
+                         max_rounds: int = 0) -> ModelAlignPlaneStep:
+        """``gsx_model_align_plane_step``: one Gauss-Newton step of point-to-plane registration of this model onto ``dst_key``, which
+        needs ``keep_normals`` first: ``align_step``'s search, the 6x6 normal equations on the device, a spectral solve on the host
+        that moves only along what the pairs determine (``rank``).  ``max_variation`` (0: no limit) leaves out targets whose
+        neighbourhood is far from a plane."""
+        desc = _lib.AlignPlaneDesc(_nearest_desc(xform, model_transforms, src_filter, dst_filter, max_distance, radius_hint, grid_bits, max_rounds),
+                                   0, float(max_variation), (C.c_uint32 * 2)(0, 0))
+        out = _lib.AlignPlaneStep()
+        _lib.check(self._v._L.gsx_model_align_plane_step(self._v._h, self._key.encode(), dst_key.encode(), C.byref(desc), C.byref(out)))
+        vec = lambda a: np.array(a[:], np.float64)  # noqa: E731
+        return ModelAlignPlaneStep(vec(out.pos), vec(out.quat), vec(out.normal_matrix), vec(out.rhs), vec(out.eigenvalues), vec(out.centre),
+                                   float(out.rms_before), float(out.rms_plane_before), int(out.n_pairs), int(out.n_unfitted),
+                                   np.array(out.xform_next[:], np.float32).reshape(3, 4), int(out.rank), bool(out.degenerate),
+                                   _nearest_stats(out.nearest, None, None))
+
+    def align(self, dst_key: str, max_iters: int = 30, tol: float = 1e-6, xform=None, model_transforms: bool = False, method: str = "point",
+              **step_args):
         """Iterative closest point: ``align_step`` until ``rms_before`` changes by less than ``tol`` relatively or does not fall any
         more (with exact correspondences it ends at the float32 rounding of the positions, where it only flickers: a rise is the
         end, whatever ``tol``), a step is degenerate or ``max_iters`` steps ran.  Returns ``(xform_final, D, steps)``: the final float32 3x4 matrix, the composed similarity
         ``D`` (float64 3x4) with ``xform_final = D o xform_initial`` up to the steps' roundings, and the list of steps.  With an
-        identity start ``D`` is what ``apply_transform`` bakes or ``update_model_transform`` shows."""
+        identity start ``D`` is what ``apply_transform`` bakes or ``update_model_transform`` shows.  ``method="plane"`` runs the same
+        loop over ``align_plane_step`` (``dst_key`` needs ``keep_normals`` first) and stops on ``rms_plane_before``."""
+        if method not in ("point", "plane"):
+            raise ValueError(f"align: method {method!r} is not 'point' or 'plane'")
+        plane = method == "plane"
         steps, D, last = [], np.eye(3, 4), None
         for _ in range(int(max_iters)):
-            st = self.align_step(dst_key, xform=xform, model_transforms=model_transforms and not steps, **step_args)
+            st = (self.align_plane_step if plane else self.align_step)(dst_key, xform=xform, model_transforms=model_transforms and not steps, **step_args)
             steps.append(st)
             if xform is None:
                 xform = st.nearest.xform
-            if st.degenerate or (last is not None and (st.rms_before >= last or last - st.rms_before <= tol * last)):
+            rms = st.rms_plane_before if plane else st.rms_before
+            if st.degenerate or (last is not None and (rms >= last or last - rms <= tol * last)):
                 break
-            last = st.rms_before
+            last = rms
             q = st.quat.astype(np.float64)
             x, y, z, w = q / np.linalg.norm(q)
             R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
