@@ -1159,6 +1159,90 @@ gsx_status gsx_model_normals_reset(gsx_viewer* v, const char* key);
 gsx_status gsx_model_align_plane_step(gsx_viewer* v, const char* src_key, const char* dst_key, const gsx_align_plane_desc* desc,
                                       gsx_align_plane_step_t* out);
 
+/* ---- the plane of a model: a robust consensus fit of ONE plane to the model's Gaussians, a select by the signed distance to a plane,
+ *      and the rigid motion that stands a plane level (spec/RENDER_SPEC.md §28 [BUILD-SPEC]; kernels_plane.hip, csrc/plane_math.h).
+ *      Everything is in model space.  The participants are §18's: the GSX_BOUNDS_* filter (the fit: inverted as a whole by the flag
+ *      GSX_EXTRACT_INVERT, as gsx_model_extract inverts it) and three finite stored coordinates; the others that pass the filter are
+ *      counted in n_nonfinite.
+ *      The residual of a participant p against a plane: r = ((nx px + ny py) + nz pz) - offset in float32, every operation rounded.
+ *      An inlier has |r| <= tolerance (inclusive) and, with min_cos > 0, a kept fitted normal k (gsx_model_normals_keep first) with
+ *      |c| >= min_cos, c = (kx nx + ky ny) + kz nz in float32 (§26's FACING cosine).
+ *      gsx_model_fit_plane.  n_candidates planes are made, all participants are tested against each (N x H tests, on the device), the
+ *      valid candidate with the most inliers wins (ties: the smaller index), and up to refine_iters rounds fit a least-squares plane
+ *      to the current plane's inliers and recount.  Candidates: slot s of candidate h probes the indices mix(seed, h, s, t) mod n,
+ *      t = 0 .. 63 (mix: output (h << 16 | s << 8 | t) of the splitmix64 stream seeded with seed) and takes the first participant
+ *      (NORMALS: the first participant with a fitted kept normal).  GSX_PLANE_SAMPLE_TRIPLES: three slots a, b, c, which must be
+ *      three different indices; u = b - a, v = c - a in float32, u x v and its length in double, the quotient rounded to float32, the
+ *      offset (nx ax + ny ay) + nz az in float32.  GSX_PLANE_SAMPLE_NORMALS: one slot, its kept normal, the offset likewise.
+ *      GSX_PLANE_SAMPLE_CALLER: `candidates`, used as given: they are NOT normalised, so a residual is a distance only for a unit
+ *      normal.  A candidate is invalid if a slot found nothing in 64 probes, two slots coincide, the cross product's length is zero
+ *      or not finite, or (CALLER) a component is not finite or the normal is zero: it scores 0, is reported as normal 0, offset 0
+ *      and is not counted in n_valid.  out_candidates and out_counts (nullable, n_candidates entries) receive every candidate and
+ *      its exact inlier count.  The same seed gives the same bytes.
+ *      Refinement.  Pass 0 sums the count, sum p and sum r^2 in double over the plane's inliers; the centre is c = fl32(sum p /
+ *      count); pass 1 sums the six products of d = p - c (float32) in double; the normal is the eigenvector of the smallest
+ *      eigenvalue (fixed-sweep Jacobi in double), rounded to float32, signed by §26's rule (orient, toward) at the centre; offset =
+ *      (float)((nx cx + ny cy) + nz cz).  A recount that gives fewer inliers than the plane before ends the call with the plane
+ *      before: n_inliers >= candidate_inliers.  Per-workgroup partials are folded in index order: the same bits on every call.
+ *      centroid, eigenvalues (descending), sums (sum p, the six scatter terms xx xy xz yy yz zz, then sum r^2 of the accepted plane
+ *      over its own inliers) and rms = sqrt(sum r^2 / n_inliers) describe the last accepted fit and are 0 without one.  No valid
+ *      candidate (winner = GSX_PLANE_NONE), or a winner with fewer than 3 inliers: degenerate = 1, GSX_OK, the planes all zero.
+ *      gsx_model_select_plane: the hit set is the participants with lo <= r <= hi (signed; a bound may be infinite) and, with
+ *      min_cos > 0, the facing rule above; written with selection_op; the tail bits, a model without a selection and
+ *      GSX_BOUNDS_SELECTED reading the selection as it was before the call are gsx_model_select_knn's rules.
+ *      gsx_plane_level (host only, computed in double and rounded once to float32): quat (x, y, z, w; w >= 0) is the shortest-arc rotation that takes the plane's unit
+ *      normal to up / |up|; where they are antiparallel, the half turn about e x n normalised, e the coordinate axis along which
+ *      |n| is smallest (the first of equals).  pos = -(offset / |n|) up / |up|: the rotated plane passes through the origin's
+ *      height.  The pair is what gsx_update_model_transform or gsx_model_apply_transform takes with scale 1.
+ *      Recipes.  Level a capture: fit_plane, gsx_plane_level with the world's up, gsx_update_model_transform.  Remove the floor:
+ *      select_plane(lo = -inf, hi = tolerance), then gsx_model_extract with GSX_BOUNDS_SELECTED and GSX_EXTRACT_INVERT.
+ *      Peel the next plane: select_plane(-tolerance, tolerance) with GSX_SELECTION_ADD, then fit again with filter
+ *      GSX_BOUNDS_SELECTED and flags GSX_EXTRACT_INVERT: the participants are the Gaussians no plane has taken yet (on a model
+ *      without a selection: all).
+ *      Errors.  GSX_ERR_INVALID_ARG: a null viewer, key, desc or out; unknown filter, flag, sample, orient or op values;
+ *      n_candidates outside 1 .. 1024; a tolerance that is negative or not finite; bounds with lo > hi or a NaN; min_cos outside
+ *      [0, 1]; refine_iters > 8; CALLER without candidates; a reserved word != 0; a select plane with a non-finite component or a
+ *      zero normal; min_cos > 0 or sample NORMALS on a model without kept normals; a toward that is not finite.  GSX_ERR_NOT_FOUND:
+ *      an unknown key.  GSX_ERR_UNSUPPORTED: a viewer with a communicator, a sharded model.  GSX_ERR_OOM: the model and its
+ *      selection are left as they were.  No Gaussians or no participants: GSX_OK, degenerate, zeros.  Nothing a frame reads is
+ *      written, but the selection by the select call. ---- */
+typedef struct gsx_plane_t { float normal[3]; float offset; } gsx_plane_t; /* 16 B: the points p with n . p = offset */
+#define GSX_PLANE_MAX_CANDIDATES 1024u
+#define GSX_PLANE_MAX_REFINE 8u
+#define GSX_PLANE_NONE 0xFFFFFFFFu
+#define GSX_PLANE_SAMPLE_TRIPLES 0u   /* three sampled participants */
+#define GSX_PLANE_SAMPLE_NORMALS 1u   /* one sampled participant and its kept normal (gsx_model_normals_keep first) */
+#define GSX_PLANE_SAMPLE_CALLER  2u   /* the planes the caller passes */
+typedef struct gsx_plane_fit_desc {
+    uint32_t filter; uint32_t flags; uint32_t sample; uint32_t n_candidates; /* GSX_BOUNDS_*; GSX_EXTRACT_INVERT; GSX_PLANE_SAMPLE_*; 1 .. 1024 */
+    uint64_t seed;
+    float tolerance; float min_cos;       /* finite, >= 0; 0: off, otherwise in (0, 1] */
+    uint32_t refine_iters; uint32_t orient; /* 0 .. 8; GSX_NORMALS_ORIENT_* */
+    float toward[3]; uint32_t reserved[3];
+} gsx_plane_fit_desc; /* 64 B */
+typedef struct gsx_plane_fit_t {
+    gsx_plane_t plane; gsx_plane_t candidate; /* the result; the winning candidate */
+    uint32_t winner; uint32_t n_valid;
+    uint64_t count; uint64_t n_nonfinite;     /* participants; filtered Gaussians without a finite position */
+    uint64_t candidate_inliers; uint64_t n_inliers;
+    float centroid[3]; uint32_t refine_done;
+    double eigenvalues[3]; double rms;
+    double sums[10];
+    uint32_t degenerate; uint32_t reserved;
+} gsx_plane_fit_t; /* 208 B */
+typedef struct gsx_plane_select_desc {
+    gsx_plane_t plane;
+    float lo; float hi; float min_cos; uint32_t filter;
+    uint32_t selection_op; uint32_t reserved[3];
+} gsx_plane_select_desc; /* 48 B */
+void gsx_plane_fit_desc_default(gsx_plane_fit_desc* desc);       /* TRIPLES, 256 candidates, seed 0, tolerance 0, 2 refine rounds */
+void gsx_plane_select_desc_default(gsx_plane_select_desc* desc); /* the plane z = 0, lo = hi = 0, GSX_SELECTION_SET */
+gsx_status gsx_model_fit_plane(gsx_viewer* v, const char* key, const gsx_plane_fit_desc* desc, const gsx_plane_t* candidates /* CALLER only */,
+                               gsx_plane_t* out_candidates /* nullable, n_candidates */, uint32_t* out_counts /* nullable, n_candidates */,
+                               gsx_plane_fit_t* out);
+gsx_status gsx_model_select_plane(gsx_viewer* v, const char* key, const gsx_plane_select_desc* desc, uint64_t* out_hit, uint64_t* out_selected);
+gsx_status gsx_plane_level(const gsx_plane_t* plane, const float up[3], float quat_xyzw[4], float pos[3]); /* host only */
+
 /* ---- selection, per-Gaussian edits, queries.  The app builds the pods and calls
  *      the crate (src/tab/scene.rs:740-835, 601-614, 651-657; app.rs:1479-1564); the arithmetic is the build's,
  *      spec/RENDER_SPEC.md §7 [BUILD-SPEC].  None of this costs anything while no selection / edit / query exists. ---- */

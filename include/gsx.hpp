@@ -428,6 +428,47 @@ struct MultiModelViewerModel {
         check(gsx_model_align_plane_step(v_, key_.c_str(), dst_key.c_str(), &desc, &out));
         return out;
     }
+    // gsx_model_fit_plane: the model's dominant plane by consensus, on the device: desc.n_candidates planes (sampled from triples,
+    // from kept normals, or the caller's `candidates`, which are used as given), every participant tested against every plane, the
+    // winner refined by least squares.  out_candidates and out_counts (nullable) receive every candidate and its exact inlier count.
+    // Level a capture: plane_level(fit.plane, up, quat, pos), then update_model_transform.  Remove the floor: select_plane with lo =
+    // -inf, hi = tolerance, then extract with GSX_BOUNDS_SELECTED and GSX_EXTRACT_INVERT.  Peel the next plane: select_plane with
+    // GSX_SELECTION_ADD, then fit again with filter GSX_BOUNDS_SELECTED and flags GSX_EXTRACT_INVERT.
+    static gsx_plane_fit_desc plane_fit_desc() {
+        gsx_plane_fit_desc d{};
+        gsx_plane_fit_desc_default(&d);
+        return d;
+    }
+    gsx_plane_fit_t fit_plane(const gsx_plane_fit_desc& desc, const std::vector<gsx_plane_t>* candidates = nullptr,
+                              std::vector<gsx_plane_t>* out_candidates = nullptr, std::vector<uint32_t>* out_counts = nullptr) const {
+        if (candidates && candidates->size() < desc.n_candidates) throw std::invalid_argument("fit_plane: fewer candidates than desc.n_candidates");
+        const size_t rows = desc.n_candidates <= GSX_PLANE_MAX_CANDIDATES ? desc.n_candidates : 0;  // (the call refuses more)
+        if (out_candidates) out_candidates->assign(rows, gsx_plane_t{});
+        if (out_counts) out_counts->assign(rows, 0u);
+        gsx_plane_fit_t out{};
+        check(gsx_model_fit_plane(v_, key_.c_str(), &desc, candidates ? candidates->data() : nullptr, out_candidates && rows ? out_candidates->data() : nullptr,
+                                  out_counts && rows ? out_counts->data() : nullptr, &out));
+        return out;
+    }
+    // gsx_model_select_plane: the participants whose signed residual against desc.plane lies in [lo, hi] (a bound may be infinite)
+    // and, with min_cos > 0, whose kept normal is within that cosine of the plane's; desc.selection_op sets, adds or removes the hit
+    // set, on the device.  Returns {hit, selected afterwards}.
+    static gsx_plane_select_desc plane_select_desc() {
+        gsx_plane_select_desc d{};
+        gsx_plane_select_desc_default(&d);
+        return d;
+    }
+    std::pair<uint64_t, uint64_t> select_plane(const gsx_plane_select_desc& desc) {
+        uint64_t hit = 0, selected = 0;
+        check(gsx_model_select_plane(v_, key_.c_str(), &desc, &hit, &selected));
+        return {hit, selected};
+    }
+    // gsx_plane_level (host only): the shortest-arc rotation (x, y, z, w; w >= 0) that takes the plane's unit normal to up / |up| and
+    // the translation that puts the rotated plane through the origin's height: update_model_transform's or apply_transform's
+    // arguments with scale 1.
+    static void plane_level(const gsx_plane_t& plane, const float up[3], float quat_xyzw[4], float pos[3]) {
+        check(gsx_plane_level(&plane, up, quat_xyzw, pos));
+    }
     // gsx_model_visibility: draws this model ALONE with the viewer's current camera and keeps, per Gaussian and on the device, the
     // peak blending weight T * alpha, the summed weight (2^-24 fixed point, as double) and the pixel count; accumulate folds the
     // view into the planes an earlier call left.  Every output is nullable.  The model goes through preprocess + sort again before

@@ -445,6 +445,52 @@ impl MultiModelViewerModel {
         check(unsafe { sys::gsx_model_align_plane_step(self.v, self.key.as_ptr(), dst.as_ptr(), desc, &mut out) })?;
         Ok(out)
     }
+    /// `gsx_plane_fit_desc_default`: triples, 256 candidates, seed 0, tolerance 0, two refine rounds.
+    pub fn plane_fit_desc() -> sys::gsx_plane_fit_desc {
+        let mut d = sys::gsx_plane_fit_desc::default();
+        unsafe { sys::gsx_plane_fit_desc_default(&mut d) };
+        d
+    }
+    /// `gsx_plane_select_desc_default`: the plane z = 0, lo = hi = 0, `GSX_SELECTION_SET`.
+    pub fn plane_select_desc() -> sys::gsx_plane_select_desc {
+        let mut d = sys::gsx_plane_select_desc::default();
+        unsafe { sys::gsx_plane_select_desc_default(&mut d) };
+        d
+    }
+    /// `gsx_model_fit_plane`: the model's dominant plane by consensus, on the device: `desc.n_candidates` planes (sampled from triples,
+    /// from kept normals, or the caller's `candidates`, used as given), every participant tested against every plane, the winner
+    /// refined by least squares.  With `rows`, every candidate and its exact inlier count come back too.  Level a capture:
+    /// `plane_level(&fit.plane, up)`, then `update_model_transform`.  Remove the floor: `select_plane` with `lo = -inf`, `hi =
+    /// tolerance`, then `extract` with `GSX_BOUNDS_SELECTED` and `GSX_EXTRACT_INVERT`.  Peel the next plane: `select_plane` with
+    /// `GSX_SELECTION_ADD`, then fit again with filter `GSX_BOUNDS_SELECTED` and flags `GSX_EXTRACT_INVERT`.
+    pub fn fit_plane(&self, desc: &sys::gsx_plane_fit_desc, candidates: Option<&[sys::gsx_plane_t]>, rows: bool)
+                     -> Result<(sys::gsx_plane_fit_t, Vec<sys::gsx_plane_t>, Vec<u32>), Error> {
+        if let Some(c) = candidates { assert!(c.len() >= desc.n_candidates as usize, "fit_plane: fewer candidates than desc.n_candidates"); }
+        let n = if rows && desc.n_candidates <= sys::GSX_PLANE_MAX_CANDIDATES { desc.n_candidates as usize } else { 0 };
+        let (mut planes, mut counts) = (vec![sys::gsx_plane_t::default(); n], vec![0u32; n]);
+        let mut out = sys::gsx_plane_fit_t::default();
+        check(unsafe {
+            sys::gsx_model_fit_plane(self.v, self.key.as_ptr(), desc, candidates.map_or(std::ptr::null(), |c| c.as_ptr()),
+                                     if n > 0 { planes.as_mut_ptr() } else { std::ptr::null_mut() }, if n > 0 { counts.as_mut_ptr() } else { std::ptr::null_mut() }, &mut out)
+        })?;
+        Ok((out, planes, counts))
+    }
+    /// `gsx_model_select_plane`: the participants whose signed residual against `desc.plane` lies in `[lo, hi]` (a bound may be
+    /// infinite) and, with `min_cos > 0`, whose kept normal is within that cosine of the plane's; `desc.selection_op` sets, adds or
+    /// removes the hit set, on the device.  Returns `(hit, selected afterwards)`.
+    pub fn select_plane(&mut self, desc: &sys::gsx_plane_select_desc) -> Result<(u64, u64), Error> {
+        let (mut hit, mut selected) = (0u64, 0u64);
+        check(unsafe { sys::gsx_model_select_plane(self.v, self.key.as_ptr(), desc, &mut hit, &mut selected) })?;
+        Ok((hit, selected))
+    }
+    /// `gsx_plane_level` (host only): `(quat, pos)` — the shortest-arc rotation (x, y, z, w; w >= 0) that takes the plane's unit normal
+    /// to `up / |up|` and the translation that puts the rotated plane through the origin's height: `update_model_transform`'s or
+    /// `apply_transform`'s arguments with scale 1.
+    pub fn plane_level(plane: &sys::gsx_plane_t, up: [f32; 3]) -> Result<([f32; 4], [f32; 3]), Error> {
+        let (mut quat, mut pos) = ([0f32; 4], [0f32; 3]);
+        check(unsafe { sys::gsx_plane_level(plane, up.as_ptr(), quat.as_mut_ptr(), pos.as_mut_ptr()) })?;
+        Ok((quat, pos))
+    }
 }
 
 pub struct Preprocessor(*mut sys::gsx_viewer);

@@ -106,6 +106,12 @@ pub const GSX_NEAREST_MODEL_TRANSFORMS: u32 = 1;
 pub const GSX_NEAREST_SELECT_RANGE: u32 = 0;
 pub const GSX_NEAREST_SELECT_TRANSFER: u32 = 1;
 pub const GSX_ALIGN_SCALE: u32 = 1;
+pub const GSX_PLANE_MAX_CANDIDATES: u32 = 1024;
+pub const GSX_PLANE_MAX_REFINE: u32 = 8;
+pub const GSX_PLANE_NONE: u32 = 0xFFFF_FFFF;
+pub const GSX_PLANE_SAMPLE_TRIPLES: u32 = 0;
+pub const GSX_PLANE_SAMPLE_NORMALS: u32 = 1;
+pub const GSX_PLANE_SAMPLE_CALLER: u32 = 2;
 pub const GSX_VIS_ACCUMULATE: u32 = 1;
 pub const GSX_VIS_PEAK: u32 = 0;
 pub const GSX_VIS_WEIGHT: u32 = 1;
@@ -410,6 +416,35 @@ pub struct gsx_align_plane_step_t {
     pub pos: [f64; 3], pub quat: [f64; 4], pub normal_matrix: [f64; 21], pub rhs: [f64; 6], pub eigenvalues: [f64; 6], pub centre: [f64; 3],
     pub rms_before: f64, pub rms_plane_before: f64, pub n_pairs: u64, pub n_unfitted: u64, pub xform_next: [f32; 12], pub rank: u32,
     pub degenerate: u32, pub nearest: gsx_nearest_stats_t,
+}
+/// a plane, 16 bytes: the points p with normal . p = offset (model space)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_plane_t { pub normal: [f32; 3], pub offset: f32 }
+/// gsx_model_fit_plane, 64 bytes: the filter (GSX_BOUNDS_*), flags (GSX_EXTRACT_INVERT), sample (GSX_PLANE_SAMPLE_*), the candidates
+/// (1 .. 1024), the seed, the inlier tolerance, min_cos (0: off), the refine rounds (0 .. 8), the sign rule of the refined normal
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_plane_fit_desc {
+    pub filter: u32, pub flags: u32, pub sample: u32, pub n_candidates: u32, pub seed: u64, pub tolerance: f32, pub min_cos: f32,
+    pub refine_iters: u32, pub orient: u32, pub toward: [f32; 3], pub reserved: [u32; 3],
+}
+/// the result of gsx_model_fit_plane, 208 bytes: the plane, the winning candidate and its index (GSX_PLANE_NONE without one), the valid
+/// candidates, the participants, the filtered Gaussians without a finite position, the candidate's and the plane's inliers, and of the
+/// last accepted refine round the centroid, the eigenvalues (descending), the rms residual and the sums (sum p, the scatter xx xy xz yy
+/// yz zz, sum r^2); the rounds accepted; degenerate
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_plane_fit_t {
+    pub plane: gsx_plane_t, pub candidate: gsx_plane_t, pub winner: u32, pub n_valid: u32, pub count: u64, pub n_nonfinite: u64,
+    pub candidate_inliers: u64, pub n_inliers: u64, pub centroid: [f32; 3], pub refine_done: u32, pub eigenvalues: [f64; 3], pub rms: f64,
+    pub sums: [f64; 10], pub degenerate: u32, pub reserved: u32,
+}
+/// gsx_model_select_plane, 48 bytes: the plane, the signed residual's range (a bound may be infinite), min_cos, the filter, the op
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct gsx_plane_select_desc {
+    pub plane: gsx_plane_t, pub lo: f32, pub hi: f32, pub min_cos: f32, pub filter: u32, pub selection_op: u32, pub reserved: [u32; 3],
 }
 #[repr(C)]
 #[derive(Clone, Copy)]

@@ -63,6 +63,7 @@ EXPORTS = (
     "gsx_depth_map_desc_default", "gsx_render_depth_map", "gsx_depth_map_device_ptrs", "gsx_depth_map_unproject",
     "gsx_normals_desc_default", "gsx_model_normals", "gsx_model_select_normals",
     "gsx_model_normals_keep", "gsx_model_normals_kept", "gsx_model_normals_reset", "gsx_model_align_plane_step",
+    "gsx_plane_fit_desc_default", "gsx_plane_select_desc_default", "gsx_model_fit_plane", "gsx_model_select_plane", "gsx_plane_level",
 )
 
 
@@ -342,6 +343,41 @@ class AlignPlaneStep(C.Structure):
                 ("eigenvalues", C.c_double * 6), ("centre", C.c_double * 3), ("rms_before", C.c_double), ("rms_plane_before", C.c_double),
                 ("n_pairs", C.c_uint64), ("n_unfitted", C.c_uint64), ("xform_next", C.c_float * 12), ("rank", C.c_uint32),
                 ("degenerate", C.c_uint32), ("nearest", NearestStats)]
+
+
+#: ``gsx_plane_fit_desc.sample``; the most candidates and refine rounds; "no winner"
+GSX_PLANE_SAMPLE_TRIPLES, GSX_PLANE_SAMPLE_NORMALS, GSX_PLANE_SAMPLE_CALLER = 0, 1, 2
+GSX_PLANE_MAX_CANDIDATES, GSX_PLANE_MAX_REFINE, GSX_PLANE_NONE = 1024, 8, 0xFFFFFFFF
+
+
+class Plane(C.Structure):
+    """``gsx_plane_t`` (16 bytes): the points ``p`` with ``normal . p = offset``."""
+    _fields_ = [("normal", C.c_float * 3), ("offset", C.c_float)]
+
+
+class PlaneFitDesc(C.Structure):
+    """``gsx_plane_fit_desc`` (64 bytes): filter (``GSX_BOUNDS_*``), flags (``GSX_EXTRACT_INVERT``), sample (``GSX_PLANE_SAMPLE_*``),
+    n_candidates (1 .. 1024), seed, tolerance, min_cos (0: off), refine_iters (0 .. 8), orient and toward (the normals' rule), reserved."""
+    _fields_ = [("filter", C.c_uint32), ("flags", C.c_uint32), ("sample", C.c_uint32), ("n_candidates", C.c_uint32), ("seed", C.c_uint64),
+                ("tolerance", C.c_float), ("min_cos", C.c_float), ("refine_iters", C.c_uint32), ("orient", C.c_uint32), ("toward", C.c_float * 3),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class PlaneFit(C.Structure):
+    """``gsx_plane_fit_t`` (208 bytes): the plane, the winning candidate and its index, the valid candidates, the participants, the
+    filtered Gaussians without a finite position, the candidate's and the plane's inliers, and of the last accepted fit the centroid,
+    the eigenvalues (descending), the rms residual and the sums; the refine rounds accepted; degenerate."""
+    _fields_ = [("plane", Plane), ("candidate", Plane), ("winner", C.c_uint32), ("n_valid", C.c_uint32), ("count", C.c_uint64),
+                ("n_nonfinite", C.c_uint64), ("candidate_inliers", C.c_uint64), ("n_inliers", C.c_uint64), ("centroid", C.c_float * 3),
+                ("refine_done", C.c_uint32), ("eigenvalues", C.c_double * 3), ("rms", C.c_double), ("sums", C.c_double * 10),
+                ("degenerate", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PlaneSelectDesc(C.Structure):
+    """``gsx_plane_select_desc`` (48 bytes): the plane, the signed residual's range ``[lo, hi]`` (a bound may be infinite), min_cos,
+    filter, selection_op, reserved."""
+    _fields_ = [("plane", Plane), ("lo", C.c_float), ("hi", C.c_float), ("min_cos", C.c_float), ("filter", C.c_uint32),
+                ("selection_op", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 #: ``gsx_visibility_desc.flags``: fold this view into the model's resident planes instead of replacing them
@@ -675,6 +711,11 @@ def load() -> C.CDLL:
         "gsx_model_normals_kept": ([vp, cp, C.POINTER(NormalsKept), C.c_void_p, C.c_void_p], C.c_int32),
         "gsx_model_normals_reset": ([vp, cp], C.c_int32),
         "gsx_model_align_plane_step": ([vp, cp, cp, C.POINTER(AlignPlaneDesc), C.POINTER(AlignPlaneStep)], C.c_int32),
+        "gsx_plane_fit_desc_default": ([C.POINTER(PlaneFitDesc)], None),
+        "gsx_plane_select_desc_default": ([C.POINTER(PlaneSelectDesc)], None),
+        "gsx_model_fit_plane": ([vp, cp, C.POINTER(PlaneFitDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PlaneFit)], C.c_int32),
+        "gsx_model_select_plane": ([vp, cp, C.POINTER(PlaneSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int32),
+        "gsx_plane_level": ([C.POINTER(Plane), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 4), C.POINTER(C.c_float * 3)], C.c_int32),
         "gsx_nearest_desc_default": ([C.POINTER(NearestDesc)], None),
         "gsx_model_nearest": ([vp, cp, cp, C.POINTER(NearestDesc), C.c_void_p, C.c_void_p, C.POINTER(NearestStats)], C.c_int32),
         "gsx_model_select_nearest": ([vp, cp, cp, C.POINTER(NearestSelectDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(NearestStats)], C.c_int32),

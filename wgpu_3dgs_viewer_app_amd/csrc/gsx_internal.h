@@ -1279,6 +1279,38 @@ struct AlignPlaneJob {
 };
 hipError_t launch_nearest_align_plane(hipStream_t s, uint64_t n, const uint4* pc, const NearestJob& job, const AlignPlaneJob& plane);  // sums (both passes)
 
+// Model plane (kernels_plane.hip; gsx_model_fit_plane, gsx_model_select_plane; spec section 28; plane_math.h).  The fit's passes, in this
+// order on one stream: the participant bits, the candidates, the score; then, a refine round at a time and the host's solve between
+// them, the moments (pass 0: count, sum p, sum r^2; pass 1: the scatter about pass 0's centre).  Its words:
+//   [0] participants  [1] filtered Gaussians without a finite position  [2] hit  [3] selected afterwards.
+// `sums` (kPlaneSumDoubles doubles): [0] count [1..3] sum p [4] sum r^2 | [8..13] the scatter xx xy xz yy yz zz.
+enum : uint32_t { kPlaneCount = 0, kPlaneNonfinite = 1, kPlaneHit = 2, kPlaneSelected = 3, kPlaneWords = 32 };
+constexpr uint32_t kPlanePartialDoubles = 8;  // 64 B a workgroup: pass 0 uses 5, pass 1 6
+constexpr uint32_t kPlaneSumDoubles = 16;
+struct PlaneJob {
+    const uint4* pc;              // the model's position + colour plane, n elements
+    const float* normals;         // the kept plane: n * 3 floats, then
+    const float* variation;       // n floats, +inf where no plane was fitted; both nullptr where the call needs none
+    float tolerance, min_cos;     // min_cos 0: off
+    float lo, hi;                 // select
+    uint32_t sample;              // GSX_PLANE_SAMPLE_*
+    uint32_t n_candidates;        // 1 .. kPlaneMaxCandidates
+    uint64_t seed;
+    uint32_t* words;              // kPlaneWords words
+    uint32_t* participants;       // ceil(n / 32) words: the filter and a finite position (bits at and above n are clear)
+    float4* planes;               // kPlaneMaxCandidates planes as they are scored: an invalid one carries a NaN offset
+    uint32_t* valid;              // kPlaneMaxCandidates words: 0 / 1
+    uint32_t* counts;             // kPlaneMaxCandidates words, zeroed in front of the score
+    double* partials;             // extract_groups(n) x kPlanePartialDoubles doubles
+    double* sums;                 // kPlaneSumDoubles doubles
+    SelectionWrite sel;           // select: its partials are kPropMaxGroups x kSelectPartialWords words
+};
+hipError_t launch_plane_participants(hipStream_t s, uint64_t n, const ModelFilter& f, const PlaneJob& job);  // participants, words[0..1] (zeroed before)
+hipError_t launch_plane_candidates(hipStream_t s, uint64_t n, const PlaneJob& job);                          // planes, valid (CALLER: planes hold the caller's)
+hipError_t launch_plane_score(hipStream_t s, uint64_t n, const PlaneJob& job);                               // counts
+hipError_t launch_plane_moments(hipStream_t s, uint64_t n, uint32_t pass, const float4& plane, const PlaneJob& job);  // sums of the pass
+hipError_t launch_plane_select(hipStream_t s, uint64_t n, const ModelFilter& f, const float4& plane, const PlaneJob& job);  // the selection, words[2..3]
+
 // Model decimate (kernels_decimate.hip; gsx_model_decimate, gsx_model_decimate_edge): the Gaussians that share a cell of the grid
 // above (launch_neighbors_reduce / _cell / _scan / _scatter on `nb`, the cell edge given instead of a radius) become one
 // moment-matched Gaussian (decimate_math.h).  One launch_decimate_* per pass, in this order on one stream, after the grid's.  The

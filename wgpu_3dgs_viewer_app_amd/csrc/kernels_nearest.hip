@@ -49,21 +49,7 @@ __device__ inline NearestStatsPartial nearest_combine_stats(uint32_t count, floa
                           return NearestStatsPartial{a.count + b.count, fminf(a.mn, b.mn), fmaxf(a.mx, b.mx), a.sum + b.sum, a.sum2 + b.sum2};
                       });
 }
-// T double sums a lane, folded over the wave and then over the workgroup's four waves in a fixed order
-template <uint32_t T>
-struct DoubleTerms {
-    double v[T];
-};
-template <uint32_t T>
-__device__ inline DoubleTerms<T> combine_terms(DoubleTerms<T> p) {
-#pragma unroll
-    for (uint32_t k = 0; k < T; ++k) p.v[k] = wave_sum(p.v[k]);
-    return group_fold(p, [](DoubleTerms<T> a, const DoubleTerms<T>& b) {
-#pragma unroll
-        for (uint32_t k = 0; k < T; ++k) a.v[k] += b.v[k];
-        return a;
-    });
-}
+// (DoubleTerms<T>, combine_terms: wave_reduce.h)
 constexpr uint32_t kAlignTerms = 12;  // pass 0 uses 7 of them: n, sum q, sum t; pass 1 all: H, the two spreads, sum d2
 using AlignPartial = DoubleTerms<kAlignTerms>;
 __device__ inline AlignPartial nearest_combine_align(AlignPartial p) { return combine_terms(p); }

@@ -1,5 +1,5 @@
 // wave_reduce.h — the reductions of the model operations' kernels (kernels_property / _neighbors / _clusters / _knn / _nearest /
-// _decimate.hip), written once: a value over the 64 lanes of a wave, the four waves' values over a workgroup of 256, and the wave's
+// _decimate / _plane.hip), written once: a value over the 64 lanes of a wave, the four waves' values over a workgroup of 256, and the wave's
 // append to a list (kernels_knn / _nearest.hip).  Device code only.  The frame pipeline's kernels keep their own, tuned per kernel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -60,6 +60,23 @@ __device__ inline P group_fold(P mine, F merge) {
         }
     }
     return mine;
+}
+
+// T double sums a lane, folded over the wave and then over the workgroup's four waves in a fixed order (kernels_nearest.hip's align
+// passes, kernels_plane.hip's moments): valid in thread 0 alone.  Called by every thread.
+template <uint32_t T>
+struct DoubleTerms {
+    double v[T];
+};
+template <uint32_t T>
+__device__ inline DoubleTerms<T> combine_terms(DoubleTerms<T> p) {
+#pragma unroll
+    for (uint32_t k = 0; k < T; ++k) p.v[k] = wave_sum(p.v[k]);
+    return group_fold(p, [](DoubleTerms<T> a, const DoubleTerms<T>& b) {
+#pragma unroll
+        for (uint32_t k = 0; k < T; ++k) a.v[k] += b.v[k];
+        return a;
+    });
 }
 
 }  // namespace gsx

@@ -483,6 +483,45 @@ class ModelNormalsKept:
 
 
 @dataclasses.dataclass
+class ModelPlaneFit:
+    """What ``MultiModelViewerModel.fit_plane`` returns.  ``plane`` and ``candidate`` are float32 ``(nx, ny, nz, offset)``: the points
+    ``p`` with ``n . p = offset`` in model space, the result and the winning candidate; ``winner`` its index (``None`` without a valid
+    candidate); ``n_valid`` candidates; ``count`` participants; ``n_nonfinite``; ``candidate_inliers``; ``n_inliers`` (never fewer); of
+    the last accepted refine round ``centroid`` (float32), ``eigenvalues`` (float64, descending), ``rms`` and ``sums`` (float64, 10: sum p,
+    the scatter xx xy xz yy yz zz, sum r^2); ``refine_done``; ``degenerate``; ``candidates`` (float32, ``(H, 4)``) and ``counts``
+    (uint32, ``H``): every candidate and its exact inlier count, ``None`` with ``rows=False``."""
+
+    plane: np.ndarray
+    candidate: np.ndarray
+    winner: int | None
+    n_valid: int
+    count: int
+    n_nonfinite: int
+    candidate_inliers: int
+    n_inliers: int
+    centroid: np.ndarray
+    eigenvalues: np.ndarray
+    rms: float
+    sums: np.ndarray
+    refine_done: int
+    degenerate: bool
+    candidates: np.ndarray | None
+    counts: np.ndarray | None
+
+
+def plane_level(plane, up=(0.0, 0.0, 1.0)) -> tuple[np.ndarray, np.ndarray]:
+    """``gsx_plane_level`` (host only): ``(quat, pos)``, float32 — the shortest-arc rotation (x, y, z, w; w >= 0) that takes the unit
+    normal of ``plane`` (``nx, ny, nz, offset``) to ``up / |up|``, and the translation that puts the rotated plane through the
+    origin's height: what ``update_model_transform`` or ``apply_transform`` takes with scale 1 to stand a capture level."""
+    pl = np.ascontiguousarray(plane, np.float32).reshape(4)
+    c_plane = _lib.Plane((C.c_float * 3)(*[float(x) for x in pl[:3]]), float(pl[3]))
+    c_up = (C.c_float * 3)(*[float(x) for x in up])
+    quat, pos = (C.c_float * 4)(), (C.c_float * 3)()
+    _lib.check(_lib.load().gsx_plane_level(C.byref(c_plane), C.byref(c_up), C.byref(quat), C.byref(pos)))
+    return np.array(quat[:], np.float32), np.array(pos[:], np.float32)
+
+
+@dataclasses.dataclass
 class ModelAlignPlaneStep:
     """What ``MultiModelViewerModel.align_plane_step`` returns: the delta ``t ~ R(quat) q + pos`` in the target's model space (``quat``
     x, y, z, w with w >= 0; float64); ``normal_matrix`` (float64, 21: the upper triangle of the 6x6 ``A = sum J J^T`` over
@@ -918,6 +957,49 @@ class MultiModelViewerModel:
                                    float(out.rms_before), float(out.rms_plane_before), int(out.n_pairs), int(out.n_unfitted),
                                    np.array(out.xform_next[:], np.float32).reshape(3, 4), int(out.rank), bool(out.degenerate),
                                    _nearest_stats(out.nearest, None, None))
+
+    def fit_plane(self, tolerance: float, n_candidates: int = 256, sample: int = _lib.GSX_PLANE_SAMPLE_TRIPLES, seed: int = 0,
+                  min_cos: float = 0.0, refine_iters: int = 2, toward=None, filter: int = 0, invert: bool = False,  # noqa: A002
+                  candidates=None, rows: bool = True) -> ModelPlaneFit:
+        """``gsx_model_fit_plane``: the model's dominant plane by consensus, on the device.  ``n_candidates`` planes (1 .. 1024) are
+        made from three sampled participants (``GSX_PLANE_SAMPLE_TRIPLES``), from one sampled participant and its kept normal
+        (``_NORMALS``: ``keep_normals`` first) or taken from ``candidates`` (``(H, 4)`` float32, used as given; sets ``_CALLER``); every
+        participant is tested against every plane (inlier: ``|r| <= tolerance`` and, with ``min_cos > 0``, a kept normal within that
+        cosine of the plane's); the plane with the most inliers wins and is refined by up to ``refine_iters`` least-squares rounds.
+        Level a capture: ``q, t = plane_level(fit.plane, up)``, then ``update_model_transform``.  Remove the floor:
+        ``select_plane(fit.plane, -inf, tolerance)``, then ``extract`` with ``SELECTED`` inverted.  Peel the next plane:
+        ``select_plane(fit.plane, -tolerance, tolerance, op=GSX_SELECTION_ADD)``, then ``fit_plane(..., filter=SELECTED,
+        invert=True)``."""
+        if candidates is not None:
+            cand = np.ascontiguousarray(candidates, np.float32).reshape(-1, 4)
+            sample, n_candidates = _lib.GSX_PLANE_SAMPLE_CALLER, len(cand)
+        H = int(n_candidates)
+        desc = _lib.PlaneFitDesc(int(filter), _lib.GSX_EXTRACT_INVERT if invert else 0, int(sample), H, int(seed) & 0xFFFFFFFFFFFFFFFF, float(tolerance),
+                                 float(min_cos), int(refine_iters), _lib.GSX_NORMALS_ORIENT_CANONICAL if toward is None else _lib.GSX_NORMALS_ORIENT_TOWARD,
+                                 (C.c_float * 3)(*([0.0] * 3 if toward is None else [float(x) for x in toward])), (C.c_uint32 * 3)(0, 0, 0))
+        want = rows and 1 <= H <= _lib.GSX_PLANE_MAX_CANDIDATES
+        planes = np.zeros((H, 4), np.float32) if want else None
+        counts = np.zeros(H, np.uint32) if want else None
+        out = _lib.PlaneFit()
+        _lib.check(self._v._L.gsx_model_fit_plane(self._v._h, self._key.encode(), C.byref(desc), cand.ctypes.data if candidates is not None else None,
+                                                  planes.ctypes.data if want else None, counts.ctypes.data if want else None, C.byref(out)))
+        pl = lambda q: np.array([q.normal[0], q.normal[1], q.normal[2], q.offset], np.float32)  # noqa: E731
+        return ModelPlaneFit(pl(out.plane), pl(out.candidate), None if out.winner == _lib.GSX_PLANE_NONE else int(out.winner), int(out.n_valid),
+                             int(out.count), int(out.n_nonfinite), int(out.candidate_inliers), int(out.n_inliers), np.array(out.centroid[:], np.float32),
+                             np.array(out.eigenvalues[:], np.float64), float(out.rms), np.array(out.sums[:], np.float64), int(out.refine_done),
+                             bool(out.degenerate), planes, counts)
+
+    def select_plane(self, plane, lo: float, hi: float, min_cos: float = 0.0, op: int = 0, filter: int = 0) -> tuple[int, int]:  # noqa: A002
+        """``gsx_model_select_plane``: the participants whose signed residual ``r = n . p - offset`` against ``plane`` (``nx, ny, nz,
+        offset``) lies in ``[lo, hi]`` (a bound may be infinite: everything above the floor is ``lo=tolerance, hi=inf``) and, with
+        ``min_cos > 0``, whose kept normal is within that cosine of the plane's, are the hit set; ``op`` (``_lib.GSX_SELECTION_*``)
+        makes it the selection, adds it or removes it, on the device.  Returns ``(hit, selected)``."""
+        pl = np.ascontiguousarray(plane, np.float32).reshape(4)
+        desc = _lib.PlaneSelectDesc(_lib.Plane((C.c_float * 3)(*[float(x) for x in pl[:3]]), float(pl[3])), float(lo), float(hi), float(min_cos),
+                                    int(filter), int(op), (C.c_uint32 * 3)(0, 0, 0))
+        hit, selected = C.c_uint64(), C.c_uint64()
+        _lib.check(self._v._L.gsx_model_select_plane(self._v._h, self._key.encode(), C.byref(desc), C.byref(hit), C.byref(selected)))
+        return int(hit.value), int(selected.value)
 
     def align(self, dst_key: str, max_iters: int = 30, tol: float = 1e-6, xform=None, model_transforms: bool = False, method: str = "point",
               **step_args):
